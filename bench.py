@@ -10,10 +10,18 @@ A step = one iteration of eval_BreastPathQ_SSL_CR.train() at the per-GPU shapes 
 (`--batch_size 512 --mu 7` over 8 GPUs -> b=64/GPU: 192 labeled + 448 strong-unlabeled student images, 448 weak-unlabeled
 teacher images = 1088 distinct patches), full fine-tune (--modules_student 0), MSE+MSE loss, Adam: teacher eval forward,
 student train-mode forward, losses, full backward, gradient all-reduce (N>1), fused Adam update.  Weak scaling: the
-per-GPU batch is fixed.  Inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0; at N=1 the line
-also carries the other BASELINE.json configurations measured in the same process (`also`: forward-only = config 2, RSP = config 3,
-the reference-default frozen backbone, and the fp32 exact-parity mode, config 5's shape in bf16 and fp8) and the CPU baseline of BASELINE.md section 3 (run alone, after the GPU
-legs of record).
+per-GPU batch is fixed.  Inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the outputs (--dump-outputs), the line.
+--full adds everything else, as separate legs after the timed steps: the sclk / socket-power sampler over the warm-up and timed
+steps, the roofline leg (every conv launch bracketed by HIP events) with in-run rocprofv3 --pmc counters, and at N=1 the CPU
+baseline of BASELINE.md section 3 and the other BASELINE.json configurations (`also`: forward-only = config 2, RSP = config 3,
+the reference-default frozen backbone, the fp32 exact-parity mode, config 5's shape in bf16 and fp8).  The --no-* options
+switch single legs of --full off.
+
+--dump-outputs DIR writes what the last timed step returned (losses, features, logits, ... as DIR/<name>.npy, float32) and a
+seeded sample of the parameters the optimizer updated (DIR/updated_params_sample.npy): the inputs and the initial weights are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -66,10 +74,16 @@ def parse():
                          "roofline leg is always serialised (sslcr_profile forces both off)")
     ap.add_argument("--wgrad-stream", type=int, default=0, choices=[0, 1],
                     help="1 = backward's weight-gradient launches on a second HIP stream; bit-identical.  See --aux-stream")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the other configurations (forward-only, RSP, frozen, fp32 parity, config 5)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the in-run rocprofv3 --pmc passes (MFMA busy, HBM traffic per kernel)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: power / clock sampling, roofline leg, in-run counters, CPU baseline, "
+                         "the other configurations (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs and a seeded sample of the updated parameters as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline leg (and the counters that go with it)")
+    ap.add_argument("--no-also", action="store_true",
+                    help="--full: skip the other configurations (forward-only, RSP, frozen, fp32 parity, config 5)")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the in-run rocprofv3 --pmc passes (MFMA busy, HBM traffic per kernel)")
     ap.add_argument("--virtual-ranks", type=int, default=0,
                     help="W > 1: run the SHARDED job's control flow on ONE GPU -- W engine contexts (one host thread and one stream each) "
                          "that exchange through the engine's virtual communicator (sslcr_vcomm_*) instead of RCCL, through the same code "
@@ -77,7 +91,10 @@ def parse():
                          "the multi-rank control flow (a rank-0-only step would hang here exactly as under RCCL), not a scaling number")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--also-child", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def synth_u8(shape, seed, device):
@@ -375,9 +392,10 @@ def make_workload(name, eng, args, device, rank, world, modules_student=None):
     return step, 3 * B, 3 * B * (F_FWD + F_BWD_FULL), cfg, (ms, cs, opt)
 
 
-def timed(step, warmup, steps, barrier, per_step=None):
+def timed(step, warmup, steps, barrier, per_step=None, last=None):
     """W untimed steps, then exactly K steps between two barrier + synchronize points (host clock: the contract's number).
-    per_step (a list): also gets each step's duration in ms from HIP events recorded on the launch stream between the steps."""
+    per_step (a list): also gets each step's duration in ms from HIP events recorded on the launch stream between the steps.
+    last (a list): also gets what the last timed step returned."""
     for _ in range(warmup):
         step()
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)] if per_step is not None else None
@@ -386,14 +404,53 @@ def timed(step, warmup, steps, barrier, per_step=None):
     if ev:
         ev[0].record()
     for i in range(steps):
-        step()
+        r = step()
         if ev:
             ev[i + 1].record()
     barrier()
     dt = time.perf_counter() - t0
     if ev:
         per_step.extend(ev[i].elapsed_time(ev[i + 1]) for i in range(steps))
+    if last is not None:
+        last.append(r)
     return dt
+
+
+DUMP_BYTES = 64 << 20               # --dump-outputs: at most this much in all
+DUMP_MAX_ELEMS = 1 << 22            # an output larger than this (elements) is written as a seeded sample of that many
+PARAM_SAMPLE_ELEMS = 1 << 20        # elements of the concatenated updated parameters that are written
+
+
+def _sample(flat, n, seed):
+    """a fixed, seeded sample of n elements of the 1-D tensor flat (sorted indices: the same positions in every run)"""
+    idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(seed))[:n].sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(out_dir, result, params):
+    """--dump-outputs: what the last timed step returned (a dict of tensors -> <key>.npy, a tuple -> output<i>.npy) and a seeded
+    sample of the parameters the step's optimizer updated (updated_params_sample.npy), as float32 (float64 stays float64).
+    All or nothing: the size bound is checked before the first file is written.  -> {name: [shape, sampled]}"""
+    import numpy as np
+    items = list(result.items()) if isinstance(result, dict) else [(f"output{i}", t) for i, t in enumerate(result)]
+    items = [(name, t.detach(), DUMP_MAX_ELEMS) for name, t in items]
+    if params:
+        items.append(("updated_params_sample", torch.cat([p.detach().reshape(-1) for p in params]), PARAM_SAMPLE_ELEMS))
+    arrays, written = {}, {}
+    for k, (name, t, cap) in enumerate(items):
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        sampled = t.numel() > cap
+        if sampled:
+            t = _sample(t.reshape(-1), cap, 1000 + k)
+        arrays[name] = np.ascontiguousarray(t.cpu().numpy())
+        written[name] = [list(arrays[name].shape), sampled]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: the outputs take {total / 2**20:.1f} MB, more than {DUMP_BYTES >> 20} MB; nothing written")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return written
 
 
 def also_child(args):
@@ -693,18 +750,25 @@ def run_rank(args, rank, world, device, eng, ranks, want_transport):
     barrier = ranks.barrier
 
     step, patches, flops_step, cfg, keep = make_workload(args.workload, eng, args, device, rank, world)
-    per_step_ms = []
-    # sclk and socket power of this GPU over the warm-up and the timed steps themselves (rank 0; a thread reading two sysfs files every
-    # 20 ms): the clock the value was measured at.  (A separate one-second leg in front of the roofline leg was tried first: the part
+    per_step_ms, last = [], []
+    # --full: sclk and socket power of this GPU over the warm-up and the timed steps themselves (rank 0; a thread reading two sysfs files
+    # every 20 ms): the clock the value was measured at.  (A separate one-second leg in front of the roofline leg was tried first: the part
     # settles ~5 % lower after a second of sustained load, which moved the per-kernel numbers of that leg away from the timed region's.)
-    sampler = PowerSampler(device.index or 0) if rank == 0 else None
+    sampler = PowerSampler(device.index or 0) if rank == 0 and args.full else None
     if sampler:
         sampler.__enter__()
-    dt = timed(step, args.warmup, args.steps, barrier, per_step_ms)
+    dt = timed(step, args.warmup, args.steps, barrier, per_step_ms, last)
     power = None
     if sampler:
         sampler.__exit__()
         power = sampler.summary()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before anything else steps the workload: the outputs and parameters of the last timed step
+        opt = next((k for k in keep if isinstance(k, torch.optim.Optimizer)), None)
+        params = [p for g in opt.param_groups for p in g["params"]] if opt is not None else []
+        dumped = dump_outputs(args.dump_outputs, last[0], params)
+    last.clear()
     dt = ranks.max_over_ranks(rank, dt)
     ms_per_step = dt / args.steps * 1e3
     value = patches * world * args.steps / dt
@@ -724,6 +788,8 @@ def run_rank(args, rank, world, device, eng, ranks, want_transport):
            "ranks_seen": cworld, "collective_transport": transport}
     if power:
         out["power_clock"] = power
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if want_transport == "virtual":
         out["virtual_ranks"] = world
         out["note"] = (f"{world} virtual ranks on ONE GPU (sslcr_vcomm): the sharded job's control flow, not a scaling number -- value is "
@@ -732,6 +798,7 @@ def run_rank(args, rank, world, device, eng, ranks, want_transport):
     ps = sorted(per_step_ms)
     out["ms_per_step_median_events"] = round(ps[len(ps) // 2] if len(ps) % 2 else 0.5 * (ps[len(ps) // 2 - 1] + ps[len(ps) // 2]), 3)
     out["ms_per_step_min_max_events"] = [round(ps[0], 3), round(ps[-1], 3)]
+    out["timed_steps_events"] = len(ps)             # iterations of the timed loop, one HIP event pair each
     from ssl_cr_histo_amd import _lib as _L
     import hashlib
     with open(_L.LIB_PATH, "rb") as f:
@@ -743,7 +810,7 @@ def run_rank(args, rank, world, device, eng, ranks, want_transport):
     # (rank 0 stepping alone would wait for its peers for ever, and they for it at the final barrier); only rank 0 reads the table.
     rows = []
     nprof = max(2, min(5, args.steps))
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         eng.profile(True)
         for _ in range(nprof):
             step()
@@ -756,7 +823,8 @@ def run_rank(args, rank, world, device, eng, ranks, want_transport):
     work = [step, keep]
     del step, keep
     if rank == 0:
-        rank0_only_legs(args, world, out, rows, nprof, ms_per_step, work)
+        if args.full:
+            rank0_only_legs(args, world, out, rows, nprof, ms_per_step, work)
         out["parity"] = parity_record(out)
         print(json.dumps(out), flush=True)
     work.clear()

@@ -694,7 +694,7 @@ def test_bench_line_contract():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--no-also", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "2", "--no-also", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -743,7 +743,7 @@ def test_bench_virtual_ranks_control_flow():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--virtual-ranks", "2", "--steps", "2", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--virtual-ranks", "2", "--steps", "2", "--warmup", "1",
                         "--no-cpu-baseline", "--no-also", "--no-pmc"], capture_output=True, text=True, timeout=240, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -753,6 +753,45 @@ def test_bench_virtual_ranks_control_flow():
     assert d["config"]["global_batch_patches"] == 2 * 1088 and d["config"]["bn_sync"] is True
     assert abs(d["value"] - 2 * 1088 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
     assert "roofline" in d and d["roofline"]["launches"] > 0           # the roofline leg ran (on both ranks) and rank 0 read its table
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
+    """a plain bench.py run (no --full): the headline line without the --full legs, --steps iterations of the timed loop (one HIP
+    event pair each), and --dump-outputs writing the last timed step's outputs and a seeded sample of the updated parameters as
+    float32 .npy files.  Inputs and weights are seeded, so the dump depends only on how many steps ran before it: 1 warm-up + 3
+    timed and 2 + 2 give the same arrays (to the run-to-run level) -- the dump is the 4th step's, i.e. the last timed one --
+    while 1 + 2 stops one Adam update short and differs by it."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    shapes = {"losses": [4], "feats": [640, 768], "logits": [640, 1], "logits_t": [448, 1], "updated_params_sample": [1 << 20]}
+    got = {}
+    for warmup, steps in ((1, 3), (2, 2), (1, 2)):
+        out = tmp_path / f"w{warmup}s{steps}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, cwd=root)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == steps and d["warmup"] == warmup and d["timed_steps_events"] == steps
+        assert d["dtype"] == "bf16" and d["unit"] == "images/s" and d["higher_is_better"] is True
+        assert abs(d["value"] - 1088 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+        for k in ("roofline", "roofline_hbm", "pmc_status", "cpu_baseline", "also", "power_clock", "conv_kernels"):
+            assert k not in d, k
+        assert {k: v[0] for k, v in d["dump_outputs"]["arrays"].items()} == shapes
+        arrs = {k: np.load(out / f"{k}.npy") for k in shapes}
+        assert all(a.dtype == np.float32 and list(a.shape) == shapes[k] and np.isfinite(a).all() for k, a in arrs.items())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        got[(warmup, steps)] = arrs
+    a, b, c = got[(1, 3)], got[(2, 2)], got[(1, 2)]
+    assert abs(float(a["losses"][0]) - float(b["losses"][0])) <= 1e-3 * abs(float(b["losses"][0]))
+    for k in ("feats", "logits", "logits_t", "updated_params_sample"):
+        assert np.abs(a[k] - b[k]).max() <= 2e-2 * max(1.0, float(np.abs(b[k]).max())), k
+    same = float(np.abs(a["updated_params_sample"] - b["updated_params_sample"]).mean())
+    one_update = float(np.abs(a["updated_params_sample"] - c["updated_params_sample"]).mean())
+    assert one_update > 1e-6 and same <= 0.1 * one_update, (same, one_update)
 
 
 def test_triplet_branches_as_segments_equal_pass_by_pass():

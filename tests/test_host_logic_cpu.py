@@ -213,3 +213,39 @@ def test_colour_op_restatements_and_draw_orders():
     assert out.max() == dark.max() and out.dtype == np.uint8
     assert [p[0] for p in A.RandAugmentDevice.POOL] == ["HSV", "Noise", "Scale_Resize_Crop", "Shift_Scale_Rotate", "Color", "Blur_img",
                                                          "Brightness", "Contrast", "Rotate_Crop"]      # models/randaugment.py:105-117
+
+
+def test_bench_dump_outputs_writes_float_arrays_and_fixed_samples(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every returned tensor as <name>.npy in float32 (float64 kept), outputs larger than the cap as a
+    seeded sample that is the same in every run, the updated parameters as one seeded sample, and a hard bound on the total."""
+    import os
+    import sys
+    import numpy as np
+    import pytest
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+    monkeypatch.setattr(bench, "PARAM_SAMPLE_ELEMS", 500)
+    g = torch.Generator().manual_seed(0)
+    res = {"losses": torch.rand(4, generator=g), "feats": torch.randn(64, 768, generator=g).bfloat16(),
+           "f64": torch.randn(10, generator=g, dtype=torch.float64)}
+    params = [torch.randn(30, 20, generator=g), torch.randn(700, generator=g)]
+    w1 = bench.dump_outputs(str(tmp_path / "a"), res, params)
+    w2 = bench.dump_outputs(str(tmp_path / "b"), res, params)
+    assert w1 == w2 == {"losses": [[4], False], "feats": [[1000], True], "f64": [[10], False], "updated_params_sample": [[500], True]}
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in w1}
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in w1}
+    assert a["losses"].dtype == np.float32 and a["feats"].dtype == np.float32 and a["f64"].dtype == np.float64
+    assert np.array_equal(a["losses"], res["losses"].numpy()) and np.array_equal(a["f64"], res["f64"].numpy())
+    for k in w1:
+        assert np.array_equal(a[k], b[k]), k
+    flat = torch.cat([p.reshape(-1) for p in params]).numpy()
+    assert np.isin(a["updated_params_sample"], flat).all() and np.isin(a["feats"], res["feats"].float().numpy()).all()
+    bench.dump_outputs(str(tmp_path / "t"), (torch.zeros(3), torch.ones(2, 2)), [])
+    assert np.load(tmp_path / "t" / "output1.npy").shape == (2, 2)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1024)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "c"), res, params)
+    assert not (tmp_path / "c").exists()            # all or nothing: no partial dump that looks complete

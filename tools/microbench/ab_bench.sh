@@ -4,7 +4,7 @@ cp ssl_cr_histo_amd/libsslcr.so /tmp/cur.so
 for r in 1 2; do
 for f in exp/lib_*.so; do
   cp $f ssl_cr_histo_amd/libsslcr.so
-  python bench.py 2>/dev/null | tail -1 > /tmp/b.json
+  python bench.py --full 2>/dev/null | tail -1 > /tmp/b.json
   python - "$f" <<PY
 import json, sys
 d = json.load(open("/tmp/b.json"))

@@ -3,7 +3,7 @@
 cp ssl_cr_histo_amd/libsslcr.so /tmp/cur.so
 for f in exp/lib_*.so; do
   cp $f ssl_cr_histo_amd/libsslcr.so
-  python bench.py --workload rsp --no-cpu-baseline 2>/dev/null | tail -1 > /tmp/b.json
+  python bench.py --full --workload rsp --no-cpu-baseline 2>/dev/null | tail -1 > /tmp/b.json
   python - "$f" <<PY
 import json, sys
 d = json.load(open("/tmp/b.json"))

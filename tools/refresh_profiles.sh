@@ -1,7 +1,7 @@
 #!/bin/bash
 # Evidence of one round, written under gpurun_out/<tag>/ on the GPU box (copy what is to be judged into profiles/):
 #   tools/refresh_profiles.sh r03
-#   bench.json                     the default bench command's JSON line (counters measured in-run by its rocprofv3 --pmc children)
+#   bench.json                     the bench.py --full JSON line (counters measured in-run by its rocprofv3 --pmc children)
 #   bench_under_rocprofv3.json     the same command under rocprofv3 --kernel-trace --stats ...
 #   kernel_stats.csv               ... and that run's per-kernel summary
 #   pmc_step.json                  tools/pmc_step.sh: per-kernel MFMA-busy / VALU per MFMA / HBM traffic of the step
@@ -11,9 +11,9 @@
 R=$GRAFT_REPO_ROOT; T=${1:-r03}; O=$R/gpurun_out/$T
 mkdir -p $O
 cd $R
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o p -- python $R/bench.py --aux-stream 0 --wgrad-stream 0 > $O/bench_under_rocprofv3.json 2> $O/bench_under_rocprofv3.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o p -- python $R/bench.py --full --aux-stream 0 --wgrad-stream 0 > $O/bench_under_rocprofv3.json 2> $O/bench_under_rocprofv3.err
 cp $O/prof/p_kernel_stats.csv $O/kernel_stats.csv 2>/dev/null || cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv
 rm -rf $O/prof
 cd $R
