@@ -188,8 +188,10 @@ typedef struct sslcr_bn_finalize_desc {
      with sums_in. */
   int nseg, seg_stride;
   /* library version >= 6.  NULL: two launches (row reduction, finalize).  Else ceil(C / 32) ints, ZERO before the first call and
-     left at zero by every call, not shared with a launch that may run concurrently: the row reduction's last workgroup per
-     channel block finalizes it in the same launch (same arithmetic, same bits, one launch less per BatchNorm). */
+     left at zero by every call, not shared with a launch that may run concurrently; with SSLCR_BN_ONE_LAUNCH=1 in the environment
+     (read once per process) the row reduction's last workgroup per channel block then finalizes it in the same launch (same
+     arithmetic, same bits, one launch less per BatchNorm).  Without that variable the two launches run either way: the one-launch
+     form measured slower in the stream (bn_eltwise.hip). */
   int* tickets;
 } sslcr_bn_finalize_desc;
 int sslcr_bn_finalize(const sslcr_bn_finalize_desc* d, void* stream);

@@ -1,0 +1,121 @@
+"""CPU-only: the route table (tests/kernel_routes.py) against the library's routing -- each row's descriptor maps to exactly its
+kernel name -- and against the step's profiles: every conv / stride-2 / stride-2 dgrad / wgrad instance that a profiled step
+launched has a row.  (No device here: device_cus() falls back to 256, the MI355X's count, which the routing of the persistent
+kernels depends on.)"""
+import csv
+import os
+import re
+
+import pytest
+
+from kernel_routes import ROUTES
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the routing caches these A/B switches in statics: a set one would route (and pass) a different table
+SWITCHES = ("SSLCR_PP64", "SSLCR_S2", "SSLCR_S2D", "SSLCR_BN_ONE_LAUNCH")
+FAKE = 4096        # a non-NULL pointer for the descriptor fields that select a route (nothing is launched)
+
+
+@pytest.fixture(scope="module")
+def lib():
+    set_ = [k for k in SWITCHES if k in os.environ]
+    assert not set_, f"unset {set_}: the kernel routing reads them once into statics, so this table would not be what runs"
+    from ssl_cr_histo_amd import _lib, build
+    if not os.path.exists(_lib.LIB_PATH):
+        build.build()
+    return _lib.lib()
+
+
+def flags_of(spec):
+    f = {}
+    for t in spec.split():
+        k, _, v = t.partition("=")
+        f[k] = int(v) if v else True
+    return f
+
+
+def conv_desc(op, shape, spec):
+    from ssl_cr_histo_amd import _lib as L
+    N, H, W, C, K, R, stride, pad = shape
+    f = flags_of(spec)
+    p = lambda k: FAKE if f.get(k) else None      # noqa: E731
+    PH, PW = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - R) // stride + 1
+    if op == "dgrad":      # x = dY [N, PH, PW, K], w = [C][R][S][K], pixel space = the input's four parity planes
+        d = L.ConvDesc(FAKE, FAKE, FAKE, None, None, None, None, None, N, PH, PW, K, C, R, R, stride, pad, PH, PW, H, W, 1, 1, 0, 0, 0, 2,
+                       0, 0, 0)
+        d.par4 = 1
+        return d
+    d = L.ConvDesc(FAKE, FAKE, FAKE, p("in_scale"), p("in_scale"), p("bias"), p("residual"), p("stats"), N, H, W, C, K, R, R, stride,
+                   pad, PH, PW, PH, PW, 1, 0, int(bool(f.get("in_scale"))), int(bool(f.get("relu"))), 0, 0, 0, 0, 0)
+    d.out_scale = p("out_scale")
+    if f.get("mask"):
+        d.mask_x = d.mask_scale = d.mask_shift = d.mask_mean = FAKE
+    if f.get("seg"):
+        d.seg_images, d.seg_stride = f["seg"], C
+    return d
+
+
+def wgrad_desc(shape, spec):
+    from ssl_cr_histo_amd import _lib as L
+    N, H, W, C, K, R, stride, pad = shape
+    f = flags_of(spec)
+    OH, OW = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - R) // stride + 1
+    xf = FAKE if f.get("in_scale") else None
+    return L.WgradDesc(FAKE, FAKE, FAKE, xf, xf, int(bool(xf)), N, H, W, C, K, R, R, stride, pad, OH, OW, f.get("seg", 0),
+                       C if f.get("seg") else 0)
+
+
+@pytest.mark.parametrize("row", ROUTES, ids=[f"{r[0]}-{r[1]}-{'x'.join(map(str, r[2]))}-{r[3].replace(' ', '+')}" for r in ROUTES])
+def test_route_maps_to_exactly_its_kernel(lib, row):
+    op, dt, shape, spec, name, tail = row
+    if op == "wgrad":
+        assert lib.sslcr_conv2d_wgrad_kernel_name(dt, wgrad_desc(shape, spec)).decode() == name
+        return
+    if op == "s2pair":
+        N, H, W, C, K, R, stride, pad = shape
+        d3 = conv_desc("fwd", shape, spec)
+        d1 = conv_desc("fwd", (N, H, W, C, K, 1, 2, 0), spec.replace("relu", ""))
+        assert lib.sslcr_conv2d_s2_pair_ok(dt, d3, d1) == 1
+        single = lib.sslcr_conv2d_kernel_name(dt, d3).decode()
+        # conv_s2_name(a, pair): the pair launches the same EVAL instance with PAIR = true
+        assert single.startswith("sslcr::conv_s2_kernel<false, ") and single.replace("<false, ", "<true, ") == name, single
+        return
+    d = conv_desc(op, shape, spec)
+    assert lib.sslcr_conv2d_kernel_name(dt, d).decode() == name
+    if flags_of(spec).get("seg"):
+        assert lib.sslcr_conv2d_segments_ok(dt, d) == 1
+
+
+def _table_names():
+    return {r[4] for r in ROUTES} | {r[5] for r in ROUTES if r[5]}
+
+
+def _is_route(name):
+    # conv / stride-2 / stride-2 dgrad / wgrad instances; wgrad_fold_kernel is the ordered fold of the wgrad slabs, launched behind
+    # a wgrad instance (no descriptor routes to it)
+    return re.match(r"sslcr::(conv|wgrad)", name) and "wgrad_fold" not in name and "fp8" not in name
+
+
+def test_every_profiled_instance_has_a_row():
+    with open(os.path.join(ROOT, "profiles", "r06_final_kernel_stats.csv")) as f:
+        names = [row["Name"] for row in csv.DictReader(f)]
+    insts = {re.sub(r"^void ", "", n).split("(")[0] for n in names}
+    insts = {n for n in insts if _is_route(n)}
+    assert len(insts) >= 25
+    missing = sorted(insts - _table_names())
+    assert not missing, f"profiled instances without a route row: {missing}"
+
+
+def test_every_truncated_profile_name_has_a_row():
+    """profiles/r06_final_rsp_kstats.txt prints the names cut off: match them by prefix"""
+    table = _table_names()
+    found = 0
+    with open(os.path.join(ROOT, "profiles", "r06_final_rsp_kstats.txt")) as f:
+        for line in f:
+            m = re.search(r"(sslcr::\S.*)$", line.rstrip())
+            if not m or not _is_route(m.group(1)):
+                continue
+            prefix = m.group(1).split("(")[0]
+            found += 1
+            assert any(t.startswith(prefix) for t in table), f"no route row starts with {prefix!r}"
+    assert found >= 15

@@ -9,6 +9,8 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from oracle import kernels_ref as R  # noqa: E402
+import _f64 as B  # noqa: E402
+from kernel_routes import ROUTES  # noqa: E402
 
 
 def _k():
@@ -1289,3 +1291,176 @@ def test_bn_bwd_segments_equal_separate_launches(mode, dtype):
             assert torch.equal(g[sl].view(torch.uint8), gs.view(torch.uint8)), s
         assert torch.allclose(sums[s], sums_s, rtol=1e-9, atol=1e-9 * float(sums_s.abs().max())), s      # fp64 atomics: order only
     assert torch.allclose(dg, dg1, rtol=1e-6, atol=1e-6) and torch.allclose(db, db1, rtol=1e-6, atol=1e-6)
+
+
+# ---------------------------------------------------------------- float64 per-element bounds over the route table
+def _route_flags(spec):
+    f = {}
+    for t in spec.split():
+        k, _, v = t.partition("=")
+        f[k] = int(v) if v else True
+    return f
+
+
+def _channel_scale(seed, n):
+    """a per-channel scale with both signs, and channel 0 scaled by 1e3 next to channel 1 scaled by 1e-3: a per-channel epilogue or
+    prologue mix-up moves an element by orders of magnitude"""
+    s = rnd(seed, (n,)).abs() + 0.25
+    s[::3] *= -1.0
+    s[0] *= 1e3
+    s[1] *= 1e-3
+    return s
+
+
+@pytest.mark.parametrize("row", ROUTES, ids=[f"{r[0]}-{r[1]}-{'x'.join(map(str, r[2]))}-{r[3].replace(' ', '+')}" for r in ROUTES])
+def test_conv_route_f64(row):
+    """every row of tests/kernel_routes.py through the kernels wrappers: the launch is EXACTLY the row's instance, and y, the
+    BatchNorm partial statistics and dW hold the float64 per-element bounds of tests/_f64.py (operands as the kernel sees them)"""
+    K = _k()
+    op, dt, shape, spec, name, _ = row
+    f = _route_flags(spec)
+    N, H, W, C, Ko, Rr, stride, pad = shape
+    OH, OW = (H + 2 * pad - Rr) // stride + 1, (W + 2 * pad - Rr) // stride + 1
+    seg = f.get("seg", 0)
+    nseg, n_img = (N // seg, seg) if seg else (1, N)
+    f32 = dt == 0
+    x = q(rnd(501, (N, H, W, C)), dt)
+    xt, kw = x, {}
+    if f.get("in_scale"):
+        sc = torch.stack([_channel_scale(502 + s, C) for s in range(nseg)])
+        sh = rnd(510, (nseg, C))
+        xt = torch.cat([B.xform(x[s * n_img:(s + 1) * n_img], sc[s], sh[s], True, dt) for s in range(nseg)])
+        kw = dict(in_scale=(sc if seg else sc[0]).contiguous().to(DEV), in_shift=(sh if seg else sh[0]).contiguous().to(DEV), in_relu=True)
+    if seg:
+        kw["seg_images"] = seg
+    if op == "wgrad":
+        dy = q(rnd(511, (N, OH, OW, Ko)), dt)
+        base = rnd(512, (Ko, Rr, Rr, C))
+        dw = base.clone().to(DEV)
+        K.conv2d_wgrad(to_dev(x, dt), to_dev(dy, dt), dw, Rr, Rr, stride, pad, **kw)
+        assert K.last_wgrad_kernel == name, K.last_wgrad_kernel
+        want, mag = B.conv_wgrad(xt, dy, (Ko, Rr, Rr, C), stride, pad, base=base)
+        B.check(dw, want, B.bound(want, mag, N * OH * OW, 0, f32), "wgrad", name, dims="krsc")
+        return
+    w = q(rnd(513, (Ko, Rr, Rr, C), 0.05), dt)
+    if op == "dgrad":
+        dy = q(rnd(514, (N, OH, OW, Ko)), dt)
+        dx = torch.full((N, H, W, C), float("nan"), dtype=K.tdtype(dt), device=DEV)
+        K.conv2d(to_dev(dy, dt), to_dev(w.permute(3, 1, 2, 0).contiguous(), dt), stride, pad, transposed=True, out=dx, out_hw=(H, W),
+                 pixel_hw=(OH, OW), pix_mul=2, par4=True)
+        assert K.last_conv_kernel == name, K.last_conv_kernel
+        want, mag = B.conv_dgrad(dy, w, stride, pad, (H, W))
+        B.check(dx, want, B.bound(want, mag, Rr * Rr * Ko, dt, f32), "dgrad", name)
+        return
+    bias = rnd(515, (Ko,)) if f.get("bias") else None
+    res = q(rnd(516, (N, OH, OW, Ko)), dt) if f.get("residual") else None
+    osc = _channel_scale(517, Ko) if f.get("out_scale") else None
+    relu = bool(f.get("relu"))
+    n = Rr * Rr * C
+    if op == "s2pair":
+        w1 = q(rnd(518, (Ko, 1, 1, C), 0.1), dt)
+        b1 = rnd(519, (Ko,)) if bias is not None else None
+        s1 = _channel_scale(520, Ko) if osc is not None else None
+        dev = lambda t: t.to(DEV) if t is not None else None      # noqa: E731
+        out = K.conv2d_s2_pair(to_dev(x, dt), to_dev(w, dt), to_dev(w1, dt), bias3=dev(bias), bias1=dev(b1), relu3=relu,
+                               want_stats=bool(f.get("stats")), scale3=dev(osc), scale1=dev(s1))
+        # the pair launches the single conv's instance with PAIR = true (conv_s2_name); the single launch gives the same bits
+        ys = K.conv2d(to_dev(x, dt), to_dev(w, dt), stride, pad, bias=dev(bias), relu=relu, out_scale=dev(osc), want_stats=bool(f.get("stats")))
+        assert K.last_conv_kernel.replace("<false, ", "<true, ") == name, K.last_conv_kernel
+        assert torch.equal((ys[0] if f.get("stats") else ys).view(torch.int16), out[0].view(torch.int16))
+        for y, st, ww, bb, ss, r, p, rl, what in ((out[0], out[2] if f.get("stats") else None, w, bias, osc, 3, 1, relu, "3x3 / 2"),
+                                                  (out[1], out[3] if f.get("stats") else None, w1, b1, s1, 1, 0, False, "1x1 / 2")):
+            want, mag, acc, amag = B.conv_fwd(x, ww, 2, p, out_scale=ss, bias=bb, relu=rl)
+            B.check(y, want, B.bound(want, mag, r * r * C, dt, f32), f"pair {what}", name)
+            if st is not None:
+                B.check_stats(st, acc, amag, r * r * C, f"pair {what} statistics", name, f32)
+        return
+    if f.get("mask"):
+        xbn = q(rnd(521, (N, OH, OW, Ko), 2.0) + 0.3, dt)
+        msc, msh, mmu = _channel_scale(522, Ko), rnd(523, (Ko,)), rnd(524, (Ko,))
+        y, stats = K.conv2d(to_dev(x, dt), to_dev(w, dt), stride, pad, want_stats=True,
+                            mask=(to_dev(xbn, dt), msc.to(DEV), msh.to(DEV), mmu.to(DEV)))
+        assert K.last_conv_kernel == name, K.last_conv_kernel
+        _, _, acc, amag = B.conv_fwd(x, w, stride, pad)
+        # the kernel's mask: fmaf(x, scale, shift) > 0 in fp32; its second sum takes (x - mean) rounded to fp32
+        keep = ((xbn.double() * msc.double() + msh.double()).float() > 0).double()
+        g, gmag = acc * keep, amag * keep
+        B.check(y, g, B.bound(g, gmag, n, dt, f32), "masked dgrad", name)
+        d = (xbn.float() - mmu).double().reshape(-1, Ko)
+        e = B.bound(g, gmag, n, 0, f32).reshape(-1, Ko)
+        g = g.reshape(-1, Ko)
+        lam = B.LAM * (g.shape[0] ** 0.5) * B.U
+        st = stats.double().sum(0).cpu()
+        B.check(st[0], g.sum(0), e.sum(0) + lam * g.abs().sum(0), "sum g", name, dims="k")
+        B.check(st[1], (g * d).sum(0), (e * d.abs()).sum(0) + lam * (g * d).abs().sum(0), "sum g (x - mean)", name, dims="k")
+        return
+    out = K.conv2d(to_dev(x, dt), to_dev(w, dt), stride, pad, bias=bias.to(DEV) if bias is not None else None,
+                   residual=to_dev(res, dt) if res is not None else None, relu=relu, out_scale=osc.to(DEV) if osc is not None else None,
+                   want_stats=bool(f.get("stats")), **kw)
+    assert K.last_conv_kernel == name, K.last_conv_kernel
+    y, stats = out if f.get("stats") else (out, None)
+    want, mag, acc, amag = B.conv_fwd(xt, w, stride, pad, out_scale=osc, bias=bias, residual=res, relu=relu)
+    B.check(y, want, B.bound(want, mag, n, dt, f32), "forward", name)
+    if stats is not None:
+        if seg:     # segment s owns rows [s, s + 1) * rows / nseg
+            rows = stats.shape[0] // nseg
+            for s in range(nseg):
+                sl = slice(s * n_img, (s + 1) * n_img)
+                B.check_stats(stats[s * rows:(s + 1) * rows], acc[sl], amag[sl], n, f"statistics of segment {s}", name, f32)
+        else:
+            B.check_stats(stats, acc, amag, n, "statistics", name, f32)
+
+
+# ---------------------------------------------------------------- the one-launch BatchNorm finalize (bn_reduce_finalize_kernel)
+def _bn_finalize_outputs():
+    """every output of sslcr_bn_finalize on seeded partial rows: plain, segments, C not a multiple of 32, and the sums_out form
+    (with its ticket words); the caller's SSLCR_BN_ONE_LAUNCH picks the form"""
+    from ssl_cr_histo_amd import _lib as L
+    K = _k()
+    out = {}
+    for nseg, rows, Cn in ((1, 200, 128), (3, 120, 80), (1, 64, 40)):
+        g = np.random.RandomState(600 + Cn)
+        part = torch.from_numpy(g.standard_normal((rows, 2, Cn)).astype(np.float32))
+        part[:, 1] = part[:, 1].abs() * 30 + 40
+        part = part.to(DEV)
+        gamma, beta = (rnd(601, (Cn,)).abs() + 0.5).to(DEV), rnd(602, (Cn,)).to(DEV)
+        rm, rv, nbt = rnd(603, (Cn,)).to(DEV), (rnd(604, (Cn,)).abs() + 0.5).to(DEV), torch.zeros(1, dtype=torch.int64, device=DEV)
+        res = K.bn_finalize(part, 4096.0 * rows / nseg, gamma, beta, running_mean=rm, running_var=rv, nbt=nbt, replay=3, nseg=nseg)
+        for k, t in zip(("scale", "shift", "mean", "invstd", "rm", "rv", "nbt"), res + (rm, rv, nbt)):
+            out[f"{nseg}/{Cn}/{k}"] = t.cpu()
+        # sums_out: rows -> per-segment sums only
+        sums = torch.full((nseg, 2, Cn), float("nan"), dtype=torch.float64, device=DEV)
+        stage = torch.empty((nseg, 32, 2, Cn), dtype=torch.float64, device=DEV)
+        tickets = torch.zeros((Cn + 31) // 32, dtype=torch.int32, device=DEV)
+        d = L.BnFinalizeDesc(L.ptr(part), rows, Cn, 0.0, None, None, None, None, None, None, None, None, None, 0.1, 1e-5, 1,
+                             L.ptr(sums), None, L.ptr(stage), nseg if nseg > 1 else 0, 2 * Cn if nseg > 1 else 0, L.ptr(tickets))
+        L.check(L.lib().sslcr_bn_finalize(d, L.stream_ptr()))
+        out[f"{nseg}/{Cn}/sums"] = sums.cpu()
+        out[f"{nseg}/{Cn}/tickets"] = tickets.cpu()
+    torch.cuda.synchronize()
+    return out
+
+
+def test_bn_finalize_one_launch_same_bits(tmp_path):
+    """SSLCR_BN_ONE_LAUNCH=1 (read once into a static, so in a child process of its own): the ticketed one-launch finalize gives the
+    two-launch form's bits -- segments, C not a multiple of 32, sums_out -- and leaves every ticket word at zero"""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    path = tmp_path / "one_launch.pt"
+    code = (f"import sys; sys.path[:0] = [{os.path.dirname(here)!r}, {here!r}]\n"
+            "import torch, test_kernels_gpu as T\n"
+            f"torch.save(T._bn_finalize_outputs(), {str(path)!r})\n")
+    env = dict(os.environ, SSLCR_BN_ONE_LAUNCH="1")
+    r = subprocess.run([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:]
+    one = torch.load(path)
+    assert "SSLCR_BN_ONE_LAUNCH" not in os.environ
+    two = _bn_finalize_outputs()
+    assert one.keys() == two.keys()
+    for k in two:
+        assert torch.equal(one[k], two[k]), k
+        if k.endswith("tickets"):
+            assert int(one[k].abs().sum()) == 0, k
+    assert bool(torch.isfinite(two["3/80/sums"]).all())
