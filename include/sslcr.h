@@ -29,7 +29,8 @@ extern "C" {
 #define SSLCR_BF16 1
 #define SSLCR_FP8 2   /* engine mode only (sslcr_create): bf16 storage and backward, fp8 e4m3 forward for the eligible 3x3 convs */
 
-/* the library round (6 here).  ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums. */
+/* the library round (7 here).  ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
+ * 7 = sslcr_randaug_v2_slot added (nothing else changed). */
 int sslcr_version(void);
 const char* sslcr_last_error(void);
 
@@ -355,6 +356,41 @@ typedef struct sslcr_brightness_contrast_desc {
   int N, H, W;
 } sslcr_brightness_contrast_desc;
 int sslcr_brightness_contrast(const sslcr_brightness_contrast_desc* d, void* stream);
+
+/* ---- device-side RandAugment of the RSP v2 pipeline (library version >= 7): the Pillow ops of Pretraining_v2/models/randaugment.py
+ *      (augment_pool(), :176-190) on a uint8 batch in HBM, replacing the per-tile PIL chain of RandAugment.__call__ (:203-213) that
+ *      Pretraining_v2/dataset.py:85-95 runs on the host for the three tiles of every triplet.  One call serves ONE op slot of a whole
+ *      batch: image n takes op[n] with its own parameters; SSLCR_AUGV2_COPY passes it through.  The random draws stay on the host, in
+ *      the reference's order (ssl_cr_histo_amd/augment.py); the kernels are deterministic and equal Pillow byte for byte
+ *      (csrc/augment_v2.hip spells out the arithmetic).  Reference lines per code: */
+#define SSLCR_AUGV2_COPY 0            /* identity() :38-41 */
+#define SSLCR_AUGV2_BRIGHTNESS 1      /* brightness() :52-57, ImageEnhance.Brightness(img).enhance(factor) */
+#define SSLCR_AUGV2_CONTRAST 2        /* contrast() :44-49, ImageEnhance.Contrast */
+#define SSLCR_AUGV2_COLOR 3           /* color() :160-165, ImageEnhance.Color */
+#define SSLCR_AUGV2_AUTOCONTRAST 4    /* autocontrast() :147-157, ImageOps.autocontrast */
+#define SSLCR_AUGV2_EQUALIZE 5        /* equalize() :168-172, ImageOps.equalize */
+#define SSLCR_AUGV2_SHARPNESS 6       /* sharpness() :60-65, ImageEnhance.Sharpness (blend with ImageFilter.SMOOTH) */
+#define SSLCR_AUGV2_NEAREST_FIXED 7   /* rotate() :68-74, Image.rotate: Pillow's 16.16 fixed-point nearest walk, fill 0 */
+#define SSLCR_AUGV2_NEAREST_TABLE 8   /* translate_x() / translate_y() :77-94: Pillow's scale path (per-image index tables), fill 0 */
+#define SSLCR_AUGV2_BICUBIC 9         /* shear_x() / shear_y() :97-122: Image.transform(AFFINE, BICUBIC) in float64, fill 0 */
+typedef struct sslcr_augv2_desc {
+  const uint8_t* src;       /* [N][3][H][W] (src_hwc=0) or [N][H][W][3] (src_hwc=1, what the v2 dataset holds) */
+  uint8_t* dst;             /* [N][3][H][W] (dst_hwc=0, what the stem ingests) or [N][H][W][3]; must NOT alias src */
+  const int32_t* op;        /* [N] device ints: SSLCR_AUGV2_* */
+  const float* factor;      /* [N] device floats: the enhance() factor float32(val / 10 * 1.8 + 0.1) of the four ImageEnhance ops */
+  const int32_t* fixed;     /* [N][6] device ints a0..a5 for NEAREST_FIXED: out(x, y) = in((a2 + a0 x + a1 y) >> 16, (a5 + a3 x + a4 y) >> 16);
+                               NULL when ops_mask has no such op */
+  const double* shift;      /* [N][2] device doubles (px, py) for NEAREST_TABLE: the a2 / a5 of the AFFINE tuple (1, 0, px, 0, 1, py); or NULL */
+  const double* affine;     /* [N][6] device doubles a0..a5 for BICUBIC: xin = a0 (x + 0.5) + a1 (y + 0.5) + a2, yin likewise; or NULL */
+  uint32_t* hist;           /* workspace [N][3][256], zeroed by the call; needed when ops_mask has CONTRAST / AUTOCONTRAST / EQUALIZE */
+  unsigned long long* lsum; /* workspace [N], likewise */
+  uint8_t* lut;             /* workspace [N][3][256]; needed when ops_mask has BRIGHTNESS or one of the three above */
+  int32_t* tab;             /* workspace [N][W + H]; needed when ops_mask has NEAREST_TABLE: per image the source column of every output
+                               column, then the source row of every output row, -1 = outside (built on the device from shift) */
+  unsigned ops_mask;        /* bit (1 << code) set for every code that occurs in op[]: the host planned the slot and knows */
+  int N, H, W, src_hwc, dst_hwc;
+} sslcr_augv2_desc;
+int sslcr_randaug_v2_slot(const sslcr_augv2_desc* d, void* stream);
 
 /* ==================================================================================================
  * Engine: the whole ResNet18 TripletNet(_Finetune)+head graph, forward / backward / update, orchestrated

@@ -63,6 +63,8 @@ ColourAugDesc = _S("ColourAugDesc", [("src", vp), ("dst", vp), ("shift", vp), ("
                                      ("rgb_from_hed", f64 * 9), ("N", i32), ("H", i32), ("W", i32), ("hwc", i32)])
 BrightnessContrastDesc = _S("BrightnessContrastDesc", [("src", vp), ("dst", vp), ("alpha_beta", vp), ("apply", vp), ("stats", vp),
                                                        ("N", i32), ("H", i32), ("W", i32)])
+AugV2Desc = _S("AugV2Desc", [(k, vp) for k in ("src", "dst", "op", "factor", "fixed", "shift", "affine", "hist", "lsum", "lut", "tab")] +
+                [("ops_mask", C.c_uint)] + [(k, i32) for k in ("N", "H", "W", "src_hwc", "dst_hwc")])
 PackDesc = _S("PackDesc", [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("gamma", vp), ("beta", vp), ("rmean", vp),
                            ("rvar", vp), ("eps", f32), ("bias_out", vp)] + [(k, i32) for k in ("K", "C", "R", "S", "dgrad_flip")] + [("scale_out", vp)])
 
@@ -113,6 +115,7 @@ SIGNATURES = {
     "sslcr_weak_augment": (i32, [P(WeakAugDesc), vp]),
     "sslcr_hed_colour_augment": (i32, [P(ColourAugDesc), vp]),
     "sslcr_brightness_contrast": (i32, [P(BrightnessContrastDesc), vp]),
+    "sslcr_randaug_v2_slot": (i32, [P(AugV2Desc), vp]),
 }
 
 _lib = None

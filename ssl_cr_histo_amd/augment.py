@@ -226,3 +226,238 @@ class RandAugmentDevice:
                         res = res["image"]
                     cur[i] = torch.from_numpy(res).permute(2, 0, 1).to(cur.device)
         return cur
+
+
+# ------------------------------------------------------------------------------------------------ RSP v2: the Pillow RandAugment pool
+# Pretraining_v2/models/randaugment.py:38-190.  Twelve of the fourteen ops are plain Pillow calls; csrc/augment_v2.hip restates them
+# byte for byte, one op SLOT of a whole batch per call.  The host side below makes the draws and turns each op's level into the
+# numbers Pillow itself would derive from it (enhance factor, 16.16 rotation coefficients, translate index tables, shear matrix).
+V2_COPY, V2_BRIGHTNESS, V2_CONTRAST, V2_COLOR, V2_AUTOCONTRAST, V2_EQUALIZE, V2_SHARPNESS, V2_NEAREST_FIXED, V2_NEAREST_TABLE, V2_BICUBIC = range(10)
+_V2_STATS = (1 << V2_CONTRAST) | (1 << V2_AUTOCONTRAST) | (1 << V2_EQUALIZE)
+_V2_ENHANCE = {"brightness": V2_BRIGHTNESS, "contrast": V2_CONTRAST, "color": V2_COLOR, "sharpness": V2_SHARPNESS}
+_V2_POINT = dict(_V2_ENHANCE, identity=V2_COPY, autocontrast=V2_AUTOCONTRAST, equalize=V2_EQUALIZE)
+del _V2_POINT["sharpness"]
+
+
+def _v2_batch(batch_u8, hwc, who):
+    if not batch_u8.is_cuda or batch_u8.dtype != torch.uint8 or not batch_u8.is_contiguous() or batch_u8.dim() != 4:
+        raise ValueError(f"{who}: contiguous uint8 CUDA batch [N,3,H,W] or [N,H,W,3] expected")
+    if (batch_u8.shape[3] if hwc else batch_u8.shape[1]) != 3:
+        raise ValueError("three colour channels expected")
+    return (batch_u8.shape[1], batch_u8.shape[2]) if hwc else (batch_u8.shape[2], batch_u8.shape[3])
+
+
+def enhance_factor(val):
+    """``(factor / MAX_LEVEL) * 1.8 + 0.1`` (models/randaugment.py:45) as the float32 Image.blend receives"""
+    import numpy as np
+    return float(np.float32(val / 10 * 1.8 + 0.1))
+
+
+def rotate_coefficients(degrees, hw):
+    """``Image.rotate(degrees)`` for an H x W image -> Pillow's six 16.16 integers (Image.rotate's matrix about the centre, then
+    affine_fixed's FIX(), the half-pixel centre folded into a2 / a5)."""
+    import math
+    h, w = hw
+    a = -math.radians(degrees % 360.0)
+    m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
+    cx, cy = w / 2, h / 2
+    m[2] = m[0] * (-cx) + m[1] * (-cy) + m[2] + cx
+    m[5] = m[3] * (-cx) + m[4] * (-cy) + m[5] + cy
+    for x, y in ((0, 0), (w, h)):      # Pillow walks in fixed point only while both corners stay inside 16 bits
+        if not (abs(x * m[0] + y * m[1] + m[2]) < 32768.0 and abs(x * m[3] + y * m[4] + m[5]) < 32768.0):
+            raise ValueError(f"rotate: a {h}x{w} image leaves Pillow's fixed-point range")
+
+    def fix(v):
+        return int(math.floor(v * 65536.0 + 0.5))
+    return [fix(m[0]), fix(m[1]), fix(m[2] + m[0] * 0.5 + m[1] * 0.5), fix(m[3]), fix(m[4]), fix(m[5] + m[3] * 0.5 + m[4] * 0.5)]
+
+
+def randaug_v2_slot(batch_u8, codes, *, factor=None, fixed=None, shift=None, affine=None, hwc=False, out_hwc=None, out=None,
+                    workspace=None):
+    """One op slot on a uint8 batch in HBM: image n takes ``codes[n]`` (V2_*) with row n of the tables its code reads -- factor [N]
+    (the ImageEnhance ops), fixed [N,6] (NEAREST_FIXED), shift [N,2] = (px, py) (NEAREST_TABLE), affine [N,6] (BICUBIC).  -> a new
+    batch in the layout ``out_hwc`` asks for (default: the input's).  ``workspace``: what ``v2_workspace`` returns, to reuse it."""
+    import numpy as np
+    h, w = _v2_batch(batch_u8, hwc, "randaug_v2_slot")
+    n, dev = batch_u8.shape[0], batch_u8.device
+    out_hwc = hwc if out_hwc is None else out_hwc
+    codes = np.asarray(codes, dtype=np.int32)
+    if codes.shape != (n,) or codes.min() < V2_COPY or codes.max() > V2_BICUBIC:
+        raise ValueError("codes must be [N] op codes")
+    mask = 0
+    for c in np.unique(codes):
+        mask |= 1 << int(c)
+
+    def table(t, dtype, shape, needed, name):
+        if not needed:
+            return None
+        if t is None:
+            raise ValueError(f"randaug_v2_slot: {name} is needed by the ops of this slot")
+        t = np.ascontiguousarray(np.asarray(t, dtype=dtype))
+        if t.shape != shape or not np.isfinite(t).all():
+            raise ValueError(f"{name} must be {list(shape)} finite numbers")
+        return torch.from_numpy(t).to(dev)
+    t_op = torch.from_numpy(codes).to(dev)
+    t_f = table(factor, np.float32, (n,), mask & sum(1 << c for c in _V2_ENHANCE.values()), "factor")
+    t_fx = table(fixed, np.int32, (n, 6), mask & (1 << V2_NEAREST_FIXED), "fixed")
+    t_s = table(shift, np.float64, (n, 2), mask & (1 << V2_NEAREST_TABLE), "shift")
+    t_a = table(affine, np.float64, (n, 6), mask & (1 << V2_BICUBIC), "affine")
+    hist = lsum = lut = tab = None
+    if mask & (_V2_STATS | (1 << V2_BRIGHTNESS) | (1 << V2_NEAREST_TABLE)):
+        hist, lsum, lut, tab = workspace if workspace is not None else v2_workspace(n, h, w, dev)
+    shape = (n, h, w, 3) if out_hwc else (n, 3, h, w)
+    dst = out if out is not None else torch.empty(shape, dtype=torch.uint8, device=dev)
+    if tuple(dst.shape) != shape or dst.dtype != torch.uint8 or not dst.is_contiguous() or dst.device != dev:
+        raise ValueError("out: contiguous uint8 batch of the output layout expected")
+    d = L.AugV2Desc(L.ptr(batch_u8), L.ptr(dst), L.ptr(t_op), L.ptr(t_f), L.ptr(t_fx), L.ptr(t_s), L.ptr(t_a),
+                    L.ptr(hist), L.ptr(lsum), L.ptr(lut), L.ptr(tab), mask, n, h, w, int(hwc), int(out_hwc))
+    L.check(L.lib().sslcr_randaug_v2_slot(d, L.stream_ptr()))
+    return dst
+
+
+def v2_workspace(n, h, w, device):
+    """scratch of ``randaug_v2_slot`` for N images of H x W: histograms, luma sums, LUTs, translate index tables"""
+    return (torch.empty((n, 768), dtype=torch.int32, device=device), torch.empty((n,), dtype=torch.int64, device=device),
+            torch.empty((n, 768), dtype=torch.uint8, device=device), torch.empty((n, w + h), dtype=torch.int32, device=device))
+
+
+def _v2_apply(apply, n):
+    return [True] * n if apply is None else [bool(a) for a in apply]
+
+
+def pil_point_ops(batch_u8, names, factors=None, **kw):
+    """The point-wise family: per image one of identity / brightness / contrast / color (ImageEnhance, ``factors[n]`` the enhance
+    factor) / autocontrast / equalize (ImageOps), or None = unchanged."""
+    codes = [_V2_POINT[nm or "identity"] for nm in names]
+    return randaug_v2_slot(batch_u8, codes, factor=factors, **kw)
+
+
+def pil_sharpness(batch_u8, factors, apply=None, **kw):
+    """``ImageEnhance.Sharpness(img).enhance(factors[n])`` where apply[n]."""
+    ap = _v2_apply(apply, batch_u8.shape[0])
+    return randaug_v2_slot(batch_u8, [V2_SHARPNESS if a else V2_COPY for a in ap], factor=factors, **kw)
+
+
+def pil_rotate(batch_u8, degrees, apply=None, *, hwc=False, **kw):
+    """``img.rotate(degrees[n])`` (nearest, fill 0) where apply[n]."""
+    hw = _v2_batch(batch_u8, hwc, "pil_rotate")
+    ap = _v2_apply(apply, batch_u8.shape[0])
+    fixed = [rotate_coefficients(dg, hw) if a else [0] * 6 for dg, a in zip(degrees, ap)]
+    return randaug_v2_slot(batch_u8, [V2_NEAREST_FIXED if a else V2_COPY for a in ap], fixed=fixed, hwc=hwc, **kw)
+
+
+def pil_translate(batch_u8, pixels_xy, apply=None, *, hwc=False, **kw):
+    """``img.transform(size, AFFINE, (1, 0, px, 0, 1, py))`` (nearest, fill 0) with pixels_xy[n] = (px, py) where apply[n]."""
+    ap = _v2_apply(apply, batch_u8.shape[0])
+    return randaug_v2_slot(batch_u8, [V2_NEAREST_TABLE if a else V2_COPY for a in ap], shift=[tuple(p) for p in pixels_xy], hwc=hwc, **kw)
+
+
+def pil_affine_bicubic(batch_u8, coefficients, apply=None, **kw):
+    """``img.transform(size, AFFINE, coefficients[n], BICUBIC)`` (fill 0) where apply[n]; shear_x is (1, lv, 0, 0, 1, 0), shear_y
+    (1, 0, 0, lv, 1, 0)."""
+    ap = _v2_apply(apply, batch_u8.shape[0])
+    return randaug_v2_slot(batch_u8, [V2_BICUBIC if a else V2_COPY for a in ap], affine=coefficients, **kw)
+
+
+class RandAugmentV2Device:
+    """Batched counterpart of the RSP v2 ``RandAugment(n, m)`` (Pretraining_v2/models/randaugment.py:195-213) for a uint8 batch in HBM,
+    [N,H,W,3] as the v2 dataset holds it or [N,3,H,W]; -> [N,3,H,W] uint8, what the stem ingests.
+
+    Per image the reference draws ``ops = random.sample(augment_pool, k=n)`` and per op ``val = np.random.uniform(1, m)``; rotate,
+    translate and shear then draw ``random.choice([1, 0])``, 0 negating the level.  The same draws are made here on the host, image
+    after image, from ``rng`` (a ``random.Random`` or the ``random`` module) and ``np_rng`` (a ``RandomState`` or ``numpy.random``);
+    the twelve Pillow ops then run on the device, one launch per op slot.  ``hed`` / ``hsv`` need scikit-image: they go through
+    ``host_ops[name](img_hwc_uint8_numpy, val) -> numpy`` if given (a round trip through host memory for that image and slot), else
+    NotImplementedError names the op.  A host op draws from numpy's global generator when it RUNS, after the whole batch has been
+    planned, so only batches served by the device ops alone consume the streams in the reference's image-by-image order."""
+
+    POOL = ("identity", "contrast", "brightness", "sharpness", "rotate", "translate_x", "translate_y", "shear_x", "shear_y",
+            "hed", "hsv", "autocontrast", "color", "equalize")         # augment_pool() order: random.sample depends on it
+    SIGNED = ("rotate", "translate_x", "translate_y", "shear_x", "shear_y")
+    HOST = ("hed", "hsv")
+
+    def __init__(self, n, m, rng, np_rng, host_ops=None):
+        self.n, self.m, self.rng, self.np_rng, self.host_ops = n, m, rng, np_rng, host_ops or {}
+
+    def plan(self, count):
+        """the draws of ``count`` successive RandAugment calls -> [[(name, val, sign)] * n] * count; sign is None where none is drawn"""
+        plan = []
+        for _ in range(count):
+            row = []
+            for name in self.rng.sample(self.POOL, k=self.n):
+                val = float(self.np_rng.uniform(1, self.m))
+                if name in self.HOST and name not in self.host_ops:
+                    raise NotImplementedError(f"RandAugment v2 op {name} (scikit-image) has no device kernel; pass host_ops[{name!r}]")
+                row.append((name, val, self.rng.choice([1, 0]) if name in self.SIGNED else None))
+            plan.append(row)
+        return plan
+
+    @staticmethod
+    def _layout(batch_u8, hwc):
+        if hwc is not None:
+            return bool(hwc)
+        last, first = batch_u8.shape[3] == 3, batch_u8.shape[1] == 3
+        if last == first:
+            raise ValueError("RandAugmentV2Device: pass hwc= for a batch whose layout the shape does not tell")
+        return last
+
+    def run(self, batch_u8, plan, hwc=None):
+        """apply a plan (one row per image) -> [N,3,H,W]"""
+        hwc = self._layout(batch_u8, hwc)
+        h, w = _v2_batch(batch_u8, hwc, "RandAugmentV2Device")
+        N = batch_u8.shape[0]
+        if len(plan) != N:
+            raise ValueError("one plan row per image expected")
+        import numpy as np
+        ws = v2_workspace(N, h, w, batch_u8.device)
+        cur = batch_u8
+        for slot in range(max(self.n, 1)):            # n = 0 still converts the layout
+            codes, factor = np.zeros(N, np.int32), np.zeros(N, np.float32)
+            fixed, affine, shift = np.zeros((N, 6), np.int32), np.zeros((N, 6), np.float64), np.zeros((N, 2), np.float64)
+            host = []
+            for i in range(N if self.n else 0):
+                name, val, sign = plan[i][slot]
+                if name in _V2_ENHANCE:
+                    codes[i], factor[i] = _V2_ENHANCE[name], enhance_factor(val)
+                elif name in _V2_POINT:
+                    codes[i] = _V2_POINT[name]
+                elif name in self.HOST:
+                    host.append(i)
+                else:
+                    lv = val / 10 * {"rotate": 30., "translate_x": float(10), "translate_y": float(10), "shear_x": 0.3, "shear_y": 0.3}[name]
+                    lv = lv if sign == 1 else -lv
+                    if name == "rotate":
+                        codes[i], fixed[i] = V2_NEAREST_FIXED, rotate_coefficients(lv, (h, w))
+                    elif name == "translate_x":
+                        codes[i], shift[i, 0] = V2_NEAREST_TABLE, lv
+                    elif name == "translate_y":
+                        codes[i], shift[i, 1] = V2_NEAREST_TABLE, lv
+                    else:
+                        codes[i], affine[i] = V2_BICUBIC, (1, lv, 0, 0, 1, 0) if name == "shear_x" else (1, 0, 0, lv, 1, 0)
+            nxt = randaug_v2_slot(cur, codes, factor=factor, fixed=fixed, shift=shift, affine=affine, hwc=hwc if slot == 0 else False,
+                                  out_hwc=False, workspace=ws)
+            for i in host:
+                name, val, _ = plan[i][slot]
+                img = nxt[i].permute(1, 2, 0).contiguous().cpu().numpy()
+                nxt[i] = torch.from_numpy(self.host_ops[name](img, val)).permute(2, 0, 1).to(nxt.device)
+            cur = nxt
+        return cur
+
+    def __call__(self, batch_u8, hwc=None):
+        return self.run(batch_u8, self.plan(batch_u8.shape[0]), hwc)
+
+
+class TripletRandAugmentV2:
+    """``TensorDataset_Transform.__getitem__`` (Pretraining_v2/dataset.py:85-95) for a whole RSP batch that sits in HBM: the transform
+    on the three tile batches D1, D2, D3, the draws made triplet by triplet in the order D1, D2, D3 as the dataset makes them sample
+    by sample.  -> three [N,3,H,W] uint8 batches."""
+
+    def __init__(self, n, m, rng, np_rng, host_ops=None):
+        self.aug = RandAugmentV2Device(n, m, rng, np_rng, host_ops)
+
+    def __call__(self, d1, d2, d3, hwc=None):
+        N = d1.shape[0]
+        if d2.shape[0] != N or d3.shape[0] != N:
+            raise ValueError("three batches of one length expected")
+        plan = self.aug.plan(3 * N)
+        return tuple(self.aug.run(d, plan[k::3], hwc) for k, d in enumerate((d1, d2, d3)))

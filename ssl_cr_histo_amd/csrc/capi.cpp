@@ -30,7 +30,7 @@ using namespace sslcr;
 
 extern "C" {
 
-int sslcr_version(void) { return 6; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
+int sslcr_version(void) { return 7; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
 const char* sslcr_last_error(void) { return g_err; }
 
 int sslcr_conv2d(int dtype, const sslcr_conv_desc* d, void* stream) {
@@ -216,6 +216,22 @@ int sslcr_brightness_contrast(const sslcr_brightness_contrast_desc* d, void* str
   NEED(d && d->src && d->dst && d->alpha_beta && d->stats, "null");
   NEED(d->N > 0 && d->H > 0 && d->W > 0, "empty batch");
   return check(launch_brightness_contrast(*d, (hipStream_t)stream), "brightness_contrast");
+}
+int sslcr_randaug_v2_slot(const sslcr_augv2_desc* d, void* stream) {
+  NEED(d && d->src && d->dst && d->op, "null");
+  NEED(d->src != d->dst, "dst aliases src");
+  NEED(d->N > 0 && d->N <= 65535 && d->H > 0 && d->W > 0 && d->H <= 16384 && d->W <= 16384, "batch shape");
+  const unsigned m = d->ops_mask;
+  NEED(m < (1u << (SSLCR_AUGV2_BICUBIC + 1)), "ops_mask names an unknown op");
+  const unsigned stats = 1u << SSLCR_AUGV2_CONTRAST | 1u << SSLCR_AUGV2_AUTOCONTRAST | 1u << SSLCR_AUGV2_EQUALIZE;
+  const unsigned enhance = 1u << SSLCR_AUGV2_BRIGHTNESS | 1u << SSLCR_AUGV2_CONTRAST | 1u << SSLCR_AUGV2_COLOR | 1u << SSLCR_AUGV2_SHARPNESS;
+  NEED(!(m & stats) || (d->hist && d->lsum), "hist / lsum workspace");
+  NEED(!(m & (stats | 1u << SSLCR_AUGV2_BRIGHTNESS)) || d->lut, "lut workspace");
+  NEED(!(m & enhance) || d->factor, "factor");
+  NEED(!(m & 1u << SSLCR_AUGV2_NEAREST_FIXED) || d->fixed, "fixed");
+  NEED(!(m & 1u << SSLCR_AUGV2_NEAREST_TABLE) || (d->shift && d->tab), "shift / tab workspace");
+  NEED(!(m & 1u << SSLCR_AUGV2_BICUBIC) || d->affine, "affine");
+  return check(launch_augv2(*d, (hipStream_t)stream), "randaug_v2_slot");
 }
 int sslcr_pack_stem(int dtype, const sslcr_pack_desc* d, void* stream) {
   DT_OK(dtype);
