@@ -206,6 +206,9 @@ typedef struct sslcr_bn_act_desc {      /* y = relu(x*scale+shift [+ res*rscale+
                              ReLU mask of a residual block's output as BatchNorm backward wants it (sslcr_bn_bwd_desc.yact_bits):
                              a sixteenth of the bytes of y */
 } sslcr_bn_act_desc;
+/* Widths: every C % 8 == 0, in both dtypes (16-byte chunks of 8 bf16 / 4 fp32 channels; C / 8 resp. C / 4 chunks per pixel need NOT
+ * divide 256).  A thread keeps its chunk's constants across its grid-stride trips: the launch rounds its grid so that the stride is
+ * a multiple of the chunks per pixel (unchanged where that count is a power of two up to 256, every ResNet width). */
 int sslcr_bn_act(int dtype, const sslcr_bn_act_desc* d, void* stream);
 
 typedef struct sslcr_pool_fwd_desc {    /* maxpool3x3/2 pad 1 of relu(bn(x))   (K8); scale = shift = argmax = NULL: plain
@@ -253,6 +256,9 @@ typedef struct sslcr_bn_bwd_desc {
  * on a stream (and any call that needs more than before) allocates with hipMalloc / hipStreamSynchronize INSIDE the call, so these
  * entry points must not be issued under hipStreamBeginCapture unless an earlier un-captured call on that stream has sized the scratch.
  * The scratch is released by sslcr_destroy. */
+/* Widths: sslcr_bn_bwd_reduce serves the widths whose 16-byte chunks per pixel (C / 8 bf16, C / 4 fp32) divide 256 and fails for
+ * every other; sslcr_bn_bwd_apply (plain, segment and pool forms) serves every C that is a multiple of the chunk (8 bf16, 4 fp32)
+ * from sums the caller provides -- like sslcr_bn_act it rounds its grid so that a thread keeps its channels. */
 int sslcr_bn_bwd_reduce(int dtype, const sslcr_bn_bwd_desc* d, void* stream);
 int sslcr_bn_bwd_apply(int dtype, const sslcr_bn_bwd_desc* d, void* stream);
 int sslcr_bn_param_grads(const double* sums, const float* invstd, float* dgamma, float* dbeta, int C, void* stream);

@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const BnActArgs a) {
   const char* x = reinterpret_cast<const char*>(a.x) + seg_bytes;
   const char* r = a.res ? reinterpret_cast<const char*>(a.res) + seg_bytes : nullptr;
   char* y = reinterpret_cast<char*>(a.y) + seg_bytes;
-  // grid stride is a multiple of cols: the thread's EPC channels (and their constants) are fixed for the whole loop
+  // grid stride is a multiple of cols (ew_grid_cols): the thread's EPC channels (and their constants) are fixed for the whole loop
   const int cb = (int)(((size_t)blockIdx.x * 256 + threadIdx.x) % cols) * EPC;
   float sc[EPC], sh[EPC], rsc[EPC], rsh[EPC];
 #pragma unroll
@@ -273,15 +273,30 @@ static inline int ew_grid(size_t work_items) {
   size_t b = (work_items + 255) / 256;
   return (int)(b < 1 ? 1 : (b > cap ? cap : b));
 }
+// The grid of a kernel that reads its per-channel constants ONCE per thread, ahead of the grid-stride loop (bn_act, the generic
+// pooling form, the bn_bwd apply passes): a thread keeps its channel chunk only while the stride, grid * 256 chunks, is a multiple
+// of cols = C / EPC.  Where the loop takes a second trip (the cap cut the grid) the grid is rounded DOWN to a multiple of
+// m = cols / gcd(cols, 256) -- m = 1 for every power-of-two cols up to 256 (every ResNet width): those launches are ew_grid()'s.
+// A width whose m exceeds the capped grid gets m workgroups, or one trip if that already covers the tensor.
+static inline int ew_grid_cols(size_t work_items, int cols) {
+  const size_t b = (size_t)ew_grid(work_items);
+  if (b * 256 >= work_items || cols < 1) return (int)b;          // one trip: no thread meets a second chunk
+  size_t g = (size_t)cols, r = 256;
+  while (r) { const size_t t = g % r; g = r; r = t; }            // g = gcd(cols, 256)
+  const size_t m = (size_t)cols / g;
+  if (m <= b) return (int)(b - b % m);
+  const size_t one = (work_items + 255) / 256;
+  return (int)(m < one ? m : one);
+}
 
 hipError_t launch_bn_act(int dtype, const BnActArgs& a, hipStream_t st) {
   const int nseg = a.nseg > 1 ? a.nseg : 1;
   if (a.pixels % nseg != 0) return hipErrorInvalidValue;
   const size_t per = a.pixels / nseg;
   if (dtype == DT_BF16) {
-    hipLaunchKernelGGL(bn_act_kernel<bf16_t>, dim3(ew_grid(per * (a.C / 8)), nseg), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(bn_act_kernel<bf16_t>, dim3(ew_grid_cols(per * (a.C / 8), a.C / 8), nseg), dim3(256), 0, st, a);
   } else {
-    hipLaunchKernelGGL(bn_act_kernel<float>, dim3(ew_grid(per * (a.C / 4)), nseg), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(bn_act_kernel<float>, dim3(ew_grid_cols(per * (a.C / 4), a.C / 4), nseg), dim3(256), 0, st, a);
   }
   return hipGetLastError();
 }
@@ -296,7 +311,7 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(const PoolFwdArgs 
   const size_t total = (size_t)a.N * a.OH * a.OW * cols;
   const char* x = reinterpret_cast<const char*>(a.x);
   char* y = reinterpret_cast<char*>(a.y);
-  float psc[EPC], psh[EPC];                  // fixed channels per thread (grid stride is a multiple of cols)
+  float psc[EPC], psh[EPC];                  // fixed channels per thread (grid stride is a multiple of cols: ew_grid_cols)
   {
     const int cb0 = (int)(((size_t)blockIdx.x * 256 + threadIdx.x) % cols) * EPC;
 #pragma unroll
@@ -484,9 +499,9 @@ hipError_t launch_bn_relu_maxpool(int dtype, const PoolFwdArgs& a, hipStream_t s
     return hipGetLastError();
   }
   if (dtype == DT_BF16) {
-    hipLaunchKernelGGL(bn_relu_maxpool_kernel<bf16_t>, dim3(ew_grid(px * (a.C / 8))), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(bn_relu_maxpool_kernel<bf16_t>, dim3(ew_grid_cols(px * (a.C / 8), a.C / 8)), dim3(256), 0, st, a);
   } else {
-    hipLaunchKernelGGL(bn_relu_maxpool_kernel<float>, dim3(ew_grid(px * (a.C / 4))), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(bn_relu_maxpool_kernel<float>, dim3(ew_grid_cols(px * (a.C / 4), a.C / 4)), dim3(256), 0, st, a);
   }
   return hipGetLastError();
 }
@@ -774,7 +789,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdArgs a0) {
   const int cols = a.C / EPC;
   const size_t total = a.pixels * cols;
   const float invM = (float)(1.0 / a.count);
-  // the grid stride (gridDim.x*256) is a multiple of cols, so a thread always works on the same EPC channels:
+  // the grid stride (gridDim.x*256) is a multiple of cols (ew_grid_cols), so a thread always works on the same EPC channels:
   // dx = cA*g + cB*x + cC with cA = scale, cB = -scale*invstd^2*mean(g*(x-mu)), cC = -scale*mean(g) - cB*mu
   const int cb = (int)(((size_t)blockIdx.x * 256 + threadIdx.x) % cols) * EPC;
   float cA[EPC], cB[EPC], cC[EPC], rsc[EPC], rsh[EPC];
@@ -964,7 +979,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pool_kernel(const BnBwdArgs 
   const size_t N = a.pixels / ((size_t)a.pH * a.pW);
   const size_t total = N * BH * BW * cols;
   const float invM = (float)(1.0 / a.count);
-  const int cb = (int)(((size_t)blockIdx.x * 256 + threadIdx.x) % cols) * EPC;      // grid stride is a multiple of cols
+  const int cb = (int)(((size_t)blockIdx.x * 256 + threadIdx.x) % cols) * EPC;      // grid stride is a multiple of cols (ew_grid_cols)
   float cA[EPC], cB[EPC], cC[EPC], rsh[EPC];
 #pragma unroll
   for (int e = 0; e < EPC; ++e) {
@@ -1167,8 +1182,8 @@ hipError_t launch_bn_bwd_reduce_pair(int dtype, const BnBwdArgs& a, const BnBwdA
 }
 hipError_t launch_bn_bwd_apply_pair(int dtype, const BnBwdArgs& a, const BnBwdArgs& b, int from_g, hipStream_t st) {
   if (!bn_bwd_pair_ok(a, b)) return hipErrorInvalidValue;
-  if (dtype == DT_BF16) hipLaunchKernelGGL(bn_bwd_apply_pair_kernel<bf16_t>, dim3(ew_grid(a.pixels * (a.C / 8))), dim3(256), 0, st, a, b, from_g);
-  else hipLaunchKernelGGL(bn_bwd_apply_pair_kernel<float>, dim3(ew_grid(a.pixels * (a.C / 4))), dim3(256), 0, st, a, b, from_g);
+  if (dtype == DT_BF16) hipLaunchKernelGGL(bn_bwd_apply_pair_kernel<bf16_t>, dim3(ew_grid_cols(a.pixels * (a.C / 8), a.C / 8)), dim3(256), 0, st, a, b, from_g);
+  else hipLaunchKernelGGL(bn_bwd_apply_pair_kernel<float>, dim3(ew_grid_cols(a.pixels * (a.C / 4), a.C / 4)), dim3(256), 0, st, a, b, from_g);
   return hipGetLastError();
 }
 
@@ -1181,17 +1196,17 @@ hipError_t launch_bn_bwd_apply(int dtype, const BnBwdArgs& a0, hipStream_t st) {
   if (a.pool_dy) {
     const int epc = dtype == DT_BF16 ? 8 : 4;
     const size_t items = (a.pixels / ((size_t)a.pH * a.pW)) * ((a.pH + 1) / 2) * ((a.pW + 1) / 2) * (a.C / epc);
-    if (dtype == DT_BF16) hipLaunchKernelGGL(bn_bwd_apply_pool_kernel<bf16_t>, dim3(ew_grid(items)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(bn_bwd_apply_pool_kernel<float>, dim3(ew_grid(items)), dim3(256), 0, st, a);
+    if (dtype == DT_BF16) hipLaunchKernelGGL(bn_bwd_apply_pool_kernel<bf16_t>, dim3(ew_grid_cols(items, a.C / epc)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(bn_bwd_apply_pool_kernel<float>, dim3(ew_grid_cols(items, a.C / epc)), dim3(256), 0, st, a);
     return hipGetLastError();
   }
   const int nseg = a.nseg > 1 ? a.nseg : 1;
   if (a.pixels % nseg != 0) return hipErrorInvalidValue;
   const size_t per = a.pixels / nseg;
   if (dtype == DT_BF16) {
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, dim3(ew_grid(per * (a.C / 8)), nseg), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, dim3(ew_grid_cols(per * (a.C / 8), a.C / 8), nseg), dim3(256), 0, st, a);
   } else {
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(ew_grid(per * (a.C / 4)), nseg), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(ew_grid_cols(per * (a.C / 4), a.C / 4), nseg), dim3(256), 0, st, a);
   }
   return hipGetLastError();
 }

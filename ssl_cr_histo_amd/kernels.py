@@ -302,6 +302,8 @@ def bn_act(x, scale, shift, *, res=None, rscale=None, rshift=None, relu=True, ns
                     x.numel() // Cn, Cn, int(relu), nseg if nseg > 1 else 0, Cn if nseg > 1 else 0)
     bits = None
     if want_bits:
+        if x.dtype != torch.bfloat16:
+            raise ValueError("bn_act: the sign mask (sslcr_bn_act_desc.ybits) is written in bf16 only")
         bits = torch.full((x.numel() // 8,), 0xa5, dtype=torch.uint8, device=x.device)
         d.ybits = L.ptr(bits)
     L.check(L.lib().sslcr_bn_act(_dt(x), d, L.stream_ptr()))
@@ -347,8 +349,9 @@ def avgpool_bwd(dy, shape, dtype):
 
 
 def bn_bwd(dy, x, scale, shift, mean, invstd, *, yact=None, relu_from_x=False, want_g=False, count=None, pool=None,
-           g_in_reduce=False, nseg=1, dgamma=None, dbeta=None, yact_bits=None):
+           g_in_reduce=False, nseg=1, dgamma=None, dbeta=None, yact_bits=None, sums=None):
     """-> (dx, sums[2,C] fp64, g|None).  g_in_reduce: the reduce pass writes g and the apply pass reads it (needs yact, want_g).
+    sums (fp64 [2, C]): the apply pass alone, from the caller's sums -- for widths sslcr_bn_bwd_reduce does not serve.
     nseg > 1: x is nseg equal segments along its first dimension with constants [nseg, C]; sums come back [nseg, 2, C];
     dgamma / dbeta (fp32 [C], accumulated into) take every segment's contribution."""
     _chk(x, scale, shift, mean, invstd, yact, dgamma, dbeta)
@@ -356,7 +359,9 @@ def bn_bwd(dy, x, scale, shift, mean, invstd, *, yact=None, relu_from_x=False, w
         _chk(dy)
     Cn = x.shape[-1]
     pixels = x.numel() // Cn
-    sums = torch.zeros((nseg, 2, Cn) if nseg > 1 else (2, Cn), dtype=torch.float64, device=x.device)
+    apply_only = sums is not None
+    if not apply_only:
+        sums = torch.zeros((nseg, 2, Cn) if nseg > 1 else (2, Cn), dtype=torch.float64, device=x.device)
     dx = torch.empty_like(x)
     g = torch.empty_like(x) if want_g else None
     d = L.BnBwdDesc(L.ptr(dy), L.ptr(x), L.ptr(yact), L.ptr(scale), L.ptr(shift), L.ptr(mean), L.ptr(invstd), L.ptr(sums),
@@ -377,7 +382,8 @@ def bn_bwd(dy, x, scale, shift, mean, invstd, *, yact=None, relu_from_x=False, w
             _chk(pool[2])
             d.pool_y = L.ptr(pool[2])
         d.pH, d.pW, d.pOH, d.pOW = x.shape[1], x.shape[2], pdy.shape[1], pdy.shape[2]
-    L.check(L.lib().sslcr_bn_bwd_reduce(_dt(x), d, L.stream_ptr()))
+    if not apply_only:
+        L.check(L.lib().sslcr_bn_bwd_reduce(_dt(x), d, L.stream_ptr()))
     L.check(L.lib().sslcr_bn_bwd_apply(_dt(x), d, L.stream_ptr()))
     return dx, sums, g
 

@@ -137,3 +137,382 @@ def test_wgrad_partial_slab_rounded_to_bf16_fails():
     slabs[2] = _rne(slabs[2])
     with pytest.raises(AssertionError, match="worst err/bound"):
         B.check(fold(slabs), want, bnd, "wgrad with a slab rounded to bf16", dims="krsc")
+
+
+# ====================================================================================================================
+# The non-conv families (BatchNorm finalize / apply / backward, pooling, heads, losses): for each, an emulation of the kernel in fp32
+# torch -- the kernel's operations, in another summation order -- passes its bound, and every injected fault fails it.
+# CLOSE_ACCEPTS records which of the faults close() (max error against the tensor's maximum) lets through.
+# ====================================================================================================================
+import math  # noqa: E402
+
+import numpy as np  # noqa: E402
+
+CLOSE_ACCEPTS = {
+    "var_fp32": True, "finalize_scale_bf16": True, "act_scale_bf16": True, "stride": False, "argmax_last": True, "window_shift": False,
+    "cC_without_mean": False, "gemm_k_group": True, "accumulate_ignored": False, "ce_no_max": False, "loss_scale": False,
+}
+
+
+def _accepted(fn):
+    try:
+        fn()
+        return True
+    except AssertionError:
+        return False
+
+
+def _fails(fn):
+    with pytest.raises(AssertionError):
+        fn()
+
+
+# ---------------------------------------------------------------- bn_finalize
+def _finalize_case(rows=200, C=64, k=16, seed=760):
+    g = np.random.RandomState(seed)
+    mu, sd = g.standard_normal(C) * 2.0, np.abs(g.standard_normal(C)) + 0.5
+    mu[0], sd[0] = 1e3, 1.0
+    sd[1], mu[1] = 0.0, 2.5
+    v = mu[None, None, :] + sd[None, None, :] * g.standard_normal((rows, k, C))
+    part = torch.from_numpy(np.stack([v.sum(1), (v * v).sum(1)], 1).astype(np.float32))
+    return part, float(rows * k), rnd(761, (C,)).abs() + 0.5, rnd(762, (C,)), rnd(763, (C,)), rnd(764, (C,)).abs() + 0.5
+
+
+def _finalize_emul(part, count, gamma, beta, rm, rv, replay, fault=None):
+    eps, mom = float(np.float32(1e-5)), torch.tensor(0.1, dtype=torch.float32)
+    if fault == "var_fp32":
+        s, ss = part[:, 0].sum(0), part[:, 1].sum(0)
+        mean = s / np.float32(count)
+        var = (ss / np.float32(count) - mean * mean).clamp_min(0).double()
+        mean = mean.double()
+    else:
+        p = part.double().flip(0)                              # double, rows in the opposite order
+        mean = p[:, 0].sum(0) / count
+        var = (p[:, 1].sum(0) / count - mean * mean).clamp_min(0)
+    invstd = 1.0 / torch.sqrt(var + eps)
+    sc = gamma.double() * invstd
+    if fault == "finalize_scale_bf16":
+        sc = _rne(sc).double()
+    sh = beta.double() - mean * sc
+    unb = var * count / (count - 1.0)
+    rm, rv = rm.clone(), rv.clone()
+    for _ in range(replay):
+        rm = (1 - mom) * rm + mom * mean.float()
+        rv = (1 - mom) * rv + mom * unb.float()
+    return dict(scale=sc.float(), shift=sh.float(), mean=mean.float(), invstd=invstd.float(), running_mean=rm, running_var=rv)
+
+
+def _finalize_check(out, ref):
+    for k, t in out.items():
+        w, e = ref[k]
+        B.check(t.view(w.shape), w, e, "bn_finalize " + k, dims="zc")
+
+
+def test_bn_finalize_bound():
+    part, count, gamma, beta, rm, rv = _finalize_case()
+    ref = B.bn_finalize_ref(part, count, gamma, beta, rm, rv, replay=3)
+    _finalize_check(_finalize_emul(part, count, gamma, beta, rm, rv, 3), ref)
+    assert float(ref["invstd"][0][0, 1]) == pytest.approx(1.0 / math.sqrt(float(np.float32(1e-5))))      # the constant channel clamps to var = 0
+    want32 = {k: v[0].float() for k, v in ref.items()}
+    for fault in ("var_fp32", "finalize_scale_bf16"):
+        out = _finalize_emul(part, count, gamma, beta, rm, rv, 3, fault)
+        _fails(lambda: _finalize_check(out, ref))
+        # close() as test_bn_forward_chain applies it: the scale / shift go through bn_act's output, tolerance 3e-4 of the maximum
+        x = rnd(765, (64, 64))
+        y = lambda d: x * d["scale"].view(1, -1) + d["shift"].view(1, -1)      # noqa: E731
+        assert _accepted(lambda: close(y(out)[:, 1:], y(want32)[:, 1:], 3e-4 if fault == "var_fp32" else 1.5e-2)) == CLOSE_ACCEPTS[fault]
+
+
+# ---------------------------------------------------------------- bn_act (and the cached-constant defect)
+def _act_case(dtype, pixels=1500, C=40):
+    x, res = q(rnd(771, (pixels, 1, 1, C), 2.0), dtype), q(rnd(772, (pixels, 1, 1, C)), dtype)
+    sc, rsc = rnd(773, (C,)).abs() + 0.25, rnd(774, (C,)).abs() + 0.25
+    sc[::3] *= -1.0
+    sc[0] *= 1e3
+    sc[1] *= 1e-3
+    return x, res, sc, rnd(775, (C,)), rsc, rnd(776, (C,))
+
+
+def _act_emul(x, res, sc, sh, rsc, rsh, dtype, fault=None, cap=1):
+    C = x.shape[-1]
+    epc = 8 if dtype == 1 else 4
+    cols = C // epc
+    if fault == "act_scale_bf16":
+        sc = _rne(sc)
+    if fault == "stride":
+        # a grid capped at `cap` workgroups without the rounding: chunk i runs with the constants of column (i mod stride) mod cols
+        items = x.numel() // epc
+        col = B.cached_column(items, cols, B.capped_grid(items, cap))
+        ch = (col.view(-1, 1) * epc + torch.arange(epc).view(1, -1)).reshape(x.shape)
+        sc, sh, rsc, rsh = sc[ch], sh[ch], rsc[ch], rsh[ch]
+    v = (_fmaf(x, sc, sh) + _fmaf(res, rsc, rsh)).clamp_min(0.0)
+    return _rne(v) if dtype == 1 else v
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_bn_act_bound(dtype):
+    x, res, sc, sh, rsc, rsh = _act_case(dtype)
+    want, mag = B.bn_act_ref(x, sc, sh, res, rsc, rsh, relu=True)
+    bnd = B.bound(want, mag, 0, dtype)
+    B.check(_act_emul(x, res, sc, sh, rsc, rsh, dtype), want, bnd, "emulated bn_act")
+    # the fix's launch rule: the same cap, rounded -- no thread meets a foreign chunk
+    C, epc = x.shape[-1], 8 if dtype == 1 else 4
+    items = x.numel() // epc
+    assert int((B.cached_column(items, C // epc, B.rounded_grid(items, C // epc, 1)) != torch.arange(items) % (C // epc)).sum()) == 0
+    for fault in ("act_scale_bf16", "stride"):
+        y = _act_emul(x, res, sc, sh, rsc, rsh, dtype, fault)
+        _fails(lambda: B.check(y, want, bnd, fault))
+        got = _accepted(lambda: close(y, want.float(), 3e-4 if dtype == 0 else 1.5e-2, fault))
+        assert got == (CLOSE_ACCEPTS[fault] and (dtype == 1 or fault != "act_scale_bf16")), (fault, dtype, got)
+
+
+def test_cached_constant_defect_counts():
+    """the index arithmetic of the defect: with the part's 768-workgroup cap, cols = 5 on 204800 chunks hands 8192 chunks foreign
+    constants, cols = 7 on 250000 chunks 53392; cols = 3 and every power of two none; the rounded grid none anywhere"""
+    for cols, items, wrong in ((5, 204800, 8192), (7, 250000, 53392), (3, 204800, 0), (8, 400000, 0), (10, 204800, None), (6, 250000, 0)):
+        col = torch.arange(items) % cols
+        n = int((B.cached_column(items, cols, B.capped_grid(items, 768)) != col).sum())
+        assert n == wrong or (wrong is None and n > 0), (cols, items, n)
+        assert int((B.cached_column(items, cols, B.rounded_grid(items, cols, 768)) != col).sum()) == 0
+    for cols in (1, 2, 4, 8, 16, 32, 64, 128, 256):            # every ResNet width: the launch does not change
+        for items in (100, 196608, 196609, 10 ** 7):
+            assert B.rounded_grid(items, cols, 768) == B.capped_grid(items, 768)
+
+
+# ---------------------------------------------------------------- max-pool forward / backward, avg-pool
+def _pool_emul(x, sc, sh, dtype, fault=None):
+    N, H, W, C = x.shape
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    v = _fmaf(x, sc, sh).clamp_min(0.0)
+    best = torch.full((N, OH, OW, C), -math.inf)
+    arg = torch.zeros((N, OH, OW, C), dtype=torch.long)
+    for wi in range(9):
+        for oh in range(OH):
+            h = 2 * oh - 1 + wi // 3
+            if fault == "window_shift" and oh == OH - 1:
+                h -= 1                                        # the last output row reads its window one row too high
+            if h < 0 or h >= H:
+                continue
+            ws = [(ow, 2 * ow - 1 + wi % 3) for ow in range(OW) if 0 <= 2 * ow - 1 + wi % 3 < W]
+            if not ws:
+                continue
+            o, w = torch.tensor([a for a, _ in ws]), torch.tensor([b for _, b in ws])
+            cand = v[:, h][:, w]
+            cur = best[:, oh][:, o]
+            take = (cand >= cur) if fault == "argmax_last" else (cand > cur)
+            best[:, oh, o] = torch.where(take, cand, cur)
+            arg[:, oh, o] = torch.where(take, torch.full_like(arg[:, oh][:, o], wi), arg[:, oh][:, o])
+    arg = torch.where(best > 0, arg, torch.full_like(arg, 9))
+    return (_rne(best) if dtype == 1 else best), arg
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+@pytest.mark.parametrize("hw", [(9, 7), (16, 16)])
+def test_pool_bounds(hw, dtype):
+    N, (H, W), C = 2, hw, 24
+    x = q(rnd(781, (N, H, W, C), 2.0), dtype)
+    sc, sh = rnd(782, (C,)), rnd(783, (C,))
+    sc[1], sh[1] = 0.0, 0.25
+    r = B.maxpool_ref(x, sc, sh, dtype)
+    assert B.capped(r["unsure"], "near-ties") == 0
+    ref_t, idx = F.max_pool2d(F.relu(x.double() * sc.double() + sh.double()).permute(0, 3, 1, 2), 3, 2, 1, return_indices=True)
+    assert torch.equal(r["y"], ref_t.permute(0, 2, 3, 1))
+
+    def codes_ok(arg):
+        assert bool(((arg == r["code"]) | r["unsure"]).all()), "argmax codes differ from the float64 window"
+    y, arg = _pool_emul(x, sc, sh, dtype)
+    B.check(y, r["y"], r["bnd"], "emulated max-pool")
+    codes_ok(arg)
+    # backward through the codes, avg-pool forward / backward: fp32 in another order
+    dyp = q(rnd(784, tuple(y.shape)), dtype)
+    want, mag = B.maxpool_bwd_ref(dyp, arg, r["pre"], hw)
+    act = F.relu(x.double() * sc.double() + sh.double()).permute(0, 3, 1, 2).requires_grad_(True)
+    F.max_pool2d(act, 3, 2, 1).backward(dyp.double().permute(0, 3, 1, 2))
+    if dtype == 0:                                             # without exact ties autograd routes the gradient the same way
+        B.check((act.grad * (act > 0)).permute(0, 2, 3, 1).float()[..., 2:], want[..., 2:], B.bound(want, mag, 0, 0)[..., 2:], "autograd max-pool backward")
+    a64, amag, n = B.avgpool_ref(y)
+    B.check(y.flip(1).flip(2).sum((1, 2)) * np.float32(1.0 / n), a64, B.bound(a64, amag, n, 0), "emulated avg-pool", dims="nc")
+    # faults
+    yl, argl = _pool_emul(x, sc, sh, dtype, "argmax_last")
+    B.check(yl, r["y"], r["bnd"], "argmax_last values")        # the values are right ...
+    _fails(lambda: codes_ok(argl))                             # ... the codes are not (the scale == 0 channel ties everywhere)
+    assert _accepted(lambda: close(yl, r["y"].float(), 1e-6 if dtype == 0 else 1e-2)) == CLOSE_ACCEPTS["argmax_last"]
+    ys, _ = _pool_emul(x, sc, sh, dtype, "window_shift")
+    _fails(lambda: B.check(ys, r["y"], r["bnd"], "window_shift"))
+    assert _accepted(lambda: close(ys, r["y"].float(), 1e-6 if dtype == 0 else 1e-2)) == CLOSE_ACCEPTS["window_shift"]
+
+
+# ---------------------------------------------------------------- bn_bwd: the two sums and dx = cA g + cB x + cC
+def _bwd_case(dtype, shape=(3, 10, 10, 128)):
+    N, H, W, C = shape
+    x = rnd(791, shape, 2.0) + 0.7
+    x[..., 2] = rnd(792, shape[:3]) + 30.0                    # mean / std = 30
+    x = q(x, dtype)
+    dy = q(rnd(793, shape), dtype)
+    gamma, beta = rnd(794, (C,)).abs() + 0.5, rnd(795, (C,))
+    xs = x.double().reshape(-1, C)
+    mean, invstd = xs.mean(0), 1.0 / torch.sqrt(xs.var(0, unbiased=False) + 1e-5)
+    return x, dy, (gamma.double() * invstd).float(), (beta.double() - mean * gamma.double() * invstd).float(), mean.float(), invstd.float()
+
+
+def _bwd_emul(g, x, sc, invstd, mean, count, dtype, fault=None):
+    C = x.shape[-1]
+    g2, x2 = g.reshape(-1, C), x.reshape(-1, C)
+    # the reduce pass: fp32 running sums of 25 pixels each (another grouping than the kernel's), then double
+    s0 = g2.reshape(-1, 25, C).sum(1).double().sum(0)
+    s1 = (g2 * (x2 - mean)).reshape(-1, 25, C).sum(1).double().sum(0)
+    sums = torch.stack([s0, s1])
+    invM = np.float32(1.0 / count)
+    m0, m1 = s0.float() * invM, s1.float() * invM
+    cB = -sc * invstd * invstd * m1
+    cC = -sc * m0 - (0.0 if fault == "cC_without_mean" else cB * mean)
+    d = _fmaf(sc, g, _fmaf(cB, x, cC))
+    return sums, (_rne(d) if dtype == 1 else d)
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_bn_bwd_bounds(dtype):
+    x, dy, sc, sh, mean, invstd = _bwd_case(dtype)
+    C, count = x.shape[-1], x.numel() // x.shape[-1]
+    g64, gmag = B.bn_bwd_g(dy, x, sc, sh, relu_from_x=True)
+    g = g64.float()
+    sums, dx = _bwd_emul(g, x, sc, invstd, mean, count, dtype)
+    s64, sb = B.bn_bwd_sums_ref(g64, gmag, x, mean)
+    B.check(sums.view(1, 2, C), s64, sb, "emulated bn_bwd sums", dims="zsc")
+    want, bnd = B.bn_bwd_apply_ref(g64, x, sc, invstd, mean, sums, count, dtype)
+    B.check(dx, want, bnd, "emulated bn_bwd dx")
+    base_g, base_b = rnd(796, (C,)), rnd(797, (C,))
+    wg, bg, wb, bb = B.bn_param_grads_ref(sums, invstd, base_g, base_b)
+    B.check(base_g + (sums[1] * invstd.double()).float(), wg, bg, "emulated dgamma", dims="c")
+    B.check(base_b + sums[0].float(), wb, bb, "emulated dbeta", dims="c")
+    # a reduce pass that rounds (x - mean) to bf16 fails the sums' bound
+    bad = torch.stack([sums[0], (g * _rne(x - mean)).reshape(-1, C).double().sum(0)])
+    _fails(lambda: B.check(bad.view(1, 2, C), s64, sb, "sums with x - mean in bf16", dims="zsc"))
+    _, dxf = _bwd_emul(g, x, sc, invstd, mean, count, dtype, "cC_without_mean")
+    _fails(lambda: B.check(dxf, want, bnd, "cC_without_mean"))
+    assert _accepted(lambda: close(dxf, want.float(), 5e-4 if dtype == 0 else 2e-2)) == CLOSE_ACCEPTS["cC_without_mean"]
+
+
+def test_bn_bwd_pooled_reduce_bound():
+    """(x - mean) recovered from the stored pool output: the emulation in fp32 passes; recovered without the shift it fails"""
+    N, H, W, C = 2, 15, 13, 16
+    x = q(rnd(801, (N, H, W, C), 2.0) + 0.7, 1)
+    sc, sh, mean = rnd(802, (C,)).abs() + 0.25, rnd(803, (C,)), rnd(804, (C,))
+    sc[5], sh[5] = 0.0, 0.25
+    y, arg = _pool_emul(x, sc, sh, 1)
+    dyp = q(rnd(805, tuple(y.shape)), 1)
+    s64, sb = B.bn_bwd_pool_sums_ref(dyp, y, arg, x, sc, sh, mean)
+
+    def emul(with_shift=True):
+        rinv = torch.where(sc != 0, 1.0 / sc, torch.zeros_like(sc))
+        xm = (y - (sh if with_shift else 0.0)) * rinv - mean
+        n = torch.arange(N).view(N, 1, 1).expand(y.shape[:3])
+        a5 = arg[..., 5].clamp_max(8)
+        h = 2 * torch.arange(y.shape[1]).view(1, -1, 1) - 1 + a5 // 3
+        w = 2 * torch.arange(y.shape[2]).view(1, 1, -1) - 1 + a5 % 3
+        xm[..., 5] = x[n, h.clamp(0, H - 1), w.clamp(0, W - 1), 5] - mean[5]
+        d = torch.where(y > 0, dyp, torch.zeros_like(dyp))
+        return torch.stack([d.reshape(-1, C).flip(0).sum(0).double(), (d * xm).reshape(-1, C).flip(0).sum(0).double()])
+    B.check(emul(), s64, sb, "emulated pooled reduce", dims="sc")
+    _fails(lambda: B.check(emul(False), s64, sb, "pooled reduce without the shift", dims="sc"))
+
+
+# ---------------------------------------------------------------- heads
+@pytest.mark.parametrize("shape", [(37, 70, 10), (96, 256, 64)])
+def test_linear_bounds(shape):
+    M, Kd, Nn = shape
+    x, w, b, base = rnd(811, (M, Kd)), rnd(812, (Nn, Kd), 0.03), rnd(813, (Nn,)), rnd(814, (M, Nn))
+    want, mag = B.linear_ref(x, w, bias=b, base=base)
+    bnd = B.bound(want, mag, Kd, 0, True)
+
+    def emul(k_end=Kd, accumulate=True):
+        acc = torch.zeros((M, Nn))
+        for k0 in range(0, k_end, 4):                          # fp32, four k at a time in rising order (the kernel: interleaved over four waves)
+            acc = acc + x[:, k0:min(k0 + 4, k_end)] @ w[:, k0:min(k0 + 4, k_end)].t()
+        return acc + b + (base if accumulate else 0.0)
+    B.check(emul(), want, bnd, "emulated linear", dims="mn")
+    for fault, y in (("gemm_k_group", emul(k_end=(Kd - 1) // 4 * 4)), ("accumulate_ignored", emul(accumulate=False))):
+        _fails(lambda: B.check(y, want, bnd, fault, dims="mn"))
+        assert _accepted(lambda: close(y, want.float(), 5e-2 if fault == "gemm_k_group" else 5e-5)) == CLOSE_ACCEPTS[fault], fault
+    g = rnd(815, (M, Nn))
+    want, mag = B.colsum_ref(g, b)
+    B.check(b + g.flip(0).sum(0), want, B.bound(want, mag, M, 0), "emulated db", dims="n")
+
+
+# ---------------------------------------------------------------- losses
+X_EMUL = 2.0        # the emulation's expf / logf: float64 rounded to fp32 (1 u), doubled like the device constant
+
+
+def _exp32(t):
+    return torch.exp(t.double()).float()
+
+
+def _ce_emul(l, y, w, no_max=False):
+    m = torch.zeros((l.shape[0], 1)) if no_max else l.amax(1, keepdim=True)
+    s = _exp32(l - m).flip(1).sum(1, keepdim=True)
+    lse = m + torch.log(s.double()).float()
+    onehot = torch.zeros_like(l).scatter_(1, y.view(-1, 1), 1.0)
+    return (lse - l.gather(1, y.view(-1, 1))).squeeze(1), (_exp32(l - lse) - onehot) * np.float32(w)
+
+
+@pytest.mark.parametrize("C", [2, 9, 64])
+def test_loss_bounds(C):
+    nx = 300
+    l = rnd(821 + C, (nx, C))
+    l = l * (80.0 / float(l.abs().max()))
+    l[0] += 100.0
+    l[1] -= 100.0
+    y = torch.from_numpy(np.random.RandomState(822).randint(0, C, (nx,)).astype(np.int64))
+    inx = float(np.float32(1.0 / nx))
+    rows, e_rows, dl, e_dl = B.ce_rows(l, y, inx, X=X_EMUL)
+    lx, ex = B.loss_total(rows, e_rows, inx, 0)
+
+    def check(r, d, what):
+        B.check((r.flip(0).sum() * np.float32(inx)).view(1), torch.tensor([lx], dtype=torch.float64), torch.tensor([ex], dtype=torch.float64), what + " loss", dims="i")
+        B.check(d, dl, e_dl, what + " dlogits", dims="nc")
+    r, d = _ce_emul(l, y, inx)
+    check(r, d, "emulated cross-entropy")
+    rf, df = _ce_emul(l, y, inx, no_max=True)
+    _fails(lambda: check(rf, df, "ce_no_max"))
+    assert _accepted(lambda: close(df, dl.float(), 1e-5)) == CLOSE_ACCEPTS["ce_no_max"]
+    # mse over C columns: the mean takes 1 / (nx * C)
+    t = rnd(823, (nx,)).abs() * 40.0
+    sq, dm, e_dm = B.mse_rows(l, t.view(-1, 1).expand(nx, C), inx)
+    lm, em = B.loss_total(sq, torch.zeros(()), inx / C, 3)
+    d32 = l - t.view(-1, 1)
+    B.check(((d32 * d32).flip(0).sum() * (np.float32(inx) / np.float32(C))).view(1), torch.tensor([lm], dtype=torch.float64),
+            torch.tensor([em], dtype=torch.float64), "emulated mse", dims="i")
+    B.check(2.0 * d32 * np.float32(inx) / np.float32(C), dm, e_dm, "emulated mse dlogits", dims="nc")
+    bad = ((d32 * d32).sum() * np.float32(inx)).view(1)
+    _fails(lambda: B.check(bad, torch.tensor([lm], dtype=torch.float64), torch.tensor([em], dtype=torch.float64), "loss_scale", dims="i"))
+    assert _accepted(lambda: close(bad, torch.tensor([lm]), 1e-5)) == CLOSE_ACCEPTS["loss_scale"]
+    p, pb = B.softmax_col_ref(l, C - 1, X=X_EMUL)
+    m = l.amax(1, keepdim=True)
+    B.check(_exp32(l - m)[:, C - 1] / _exp32(l - m).sum(1), p, pb, "emulated softmax_col", dims="n")
+
+
+# ---------------------------------------------------------------- optimizer step
+@pytest.mark.parametrize("kind", [0, 1])
+def test_optimizer_bounds(kind):
+    n = 20000
+    p, g, m, v = rnd(831, (n,), 0.1), rnd(832, (n,)), rnd(833, (n,), 0.3), rnd(834, (n,)).abs() * 0.5 + 0.01
+    hp = dict(lr=1e-2, beta1=0.9, beta2=0.999, eps=1e-8, wd=1e-4, momentum=0.9, bc1=1 - 0.9 ** 4, bc2=1 - 0.999 ** 4, first_step=0)
+    ref = B.optimizer_ref(kind, p, g, m, v, **hp)
+    c = {k: torch.tensor(x, dtype=torch.float32) for k, x in hp.items()}
+
+    def emul(fault=None):
+        gg = _fmaf(c["wd"], p, g)
+        if kind == 0:
+            m1 = _fmaf(c["beta1"], m, (1 - c["beta1"]) * gg)
+            v1 = _fmaf(c["beta2"], v, (1 - c["beta2"]) * gg * gg)
+            den = v1.sqrt() / (1.0 if fault == "no_bias_correction" else c["bc2"].sqrt()) + c["eps"]
+            return dict(p=p - (c["lr"] / c["bc1"]) * (m1 / den), s1=m1, s2=v1)
+        buf = _fmaf(c["momentum"], m, gg)
+        d = buf if fault == "no_nesterov" else _fmaf(c["momentum"], buf, gg)
+        return dict(p=p - c["lr"] * d, s1=buf)
+    for k, t in emul().items():
+        B.check(t, *ref[k], f"emulated optimizer {k}", dims="i")
+    bad = emul("no_bias_correction" if kind == 0 else "no_nesterov")
+    _fails(lambda: B.check(bad["p"], *ref["p"], "optimizer fault", dims="i"))
+    # close() at the existing test's 2e-5 of the largest parameter
+    assert _accepted(lambda: close(bad["p"], ref["p"][0].float(), 2e-5)) is False

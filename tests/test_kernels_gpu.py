@@ -1,6 +1,8 @@
 """Per-kernel parity: every HIP kernel (through the C-ABI) against the CPU oracle (oracle/kernels_ref.py,
 torch CPU fp32) on seeded inputs.  fp32 mode must hold 1e-4 (exact-fp32 MFMA, summation order only);
 bf16 mode is checked against the oracle fed the SAME bf16-rounded inputs (tolerance = bf16 output rounding)."""
+import math
+
 import numpy as np
 import pytest
 import torch
@@ -1464,3 +1466,516 @@ def test_bn_finalize_one_launch_same_bits(tmp_path):
         if k.endswith("tickets"):
             assert int(one[k].abs().sum()) == 0, k
     assert bool(torch.isfinite(two["3/80/sums"]).all())
+
+
+# ---------------------------------------------------------------- the non-conv kernels against float64 (tests/nonconv_cases.py, tests/_f64.py)
+import nonconv_cases as NC  # noqa: E402
+
+
+def _nc_id(row):
+    op, dt, shape, flags, _ = row
+    d = {None: "", 0: "-f32", 1: "-bf16"}[dt]
+    return f"{op}{d}-{'x'.join('N' if v is None else str(v) for v in shape)}" + ("-" + flags.replace(" ", "+") if flags else "")
+
+
+def _nc(table):
+    return pytest.mark.parametrize("row", table, ids=[_nc_id(r) for r in table])
+
+
+def _ew_cap():
+    """workgroups ew_grid() caps an elementwise launch at: three per CU of the device"""
+    return 3 * torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def _over_cap(shape, dt, C=None):
+    """N = None -> the smallest batch whose 16-byte chunks exceed the capped grid's stride by 4 %"""
+    N, H, W, Cn = shape
+    if N is None:
+        cols = Cn // (8 if dt == 1 else 4)
+        N = -(-int(1.04 * _ew_cap() * 256) // (H * W * cols))
+        assert N * H * W * cols > _ew_cap() * 256
+    return N, H, W, Cn
+
+
+def _consts(seed, C, nseg=1):
+    sc = torch.stack([_channel_scale(seed + 7 * s, C) for s in range(nseg)])
+    sh = rnd(seed + 1, (nseg, C))
+    return (sc, sh) if nseg > 1 else (sc[0], sh[0])
+
+
+def _bits(t):
+    """the sign mask sslcr_bn_act writes: bit (e & 7) of byte e >> 3 = (t.flatten()[e] > 0)"""
+    m = (t.flatten() > 0).view(-1, 8).to(torch.int32)
+    return (m << torch.arange(8, dtype=torch.int32, device=t.device).view(1, 8)).sum(1).to(torch.uint8)
+
+
+def _run_bn_act(K, dt, shape, f, seed=700):
+    N, H, W, C = shape
+    nseg = 3 if f.get("nseg3") else 1
+    x = q(rnd(seed, (N, H, W, C), 2.0), dt)
+    sc, sh = _consts(seed + 1, C, nseg)
+    res = q(rnd(seed + 3, (N, H, W, C)), dt) if (f.get("res") or f.get("bnres")) else None
+    rsc, rsh = _consts(seed + 4, C, nseg) if f.get("bnres") else (None, None)
+    dev = lambda t: t.contiguous().to(DEV) if t is not None else None      # noqa: E731
+    out = K.bn_act(to_dev(x, dt), dev(sc), dev(sh), res=to_dev(res, dt) if res is not None else None, rscale=dev(rsc), rshift=dev(rsh),
+                   relu=bool(f.get("relu")), nseg=nseg, want_bits=bool(f.get("bits")))
+    y, bits = out if f.get("bits") else (out, None)
+    want, mag = B.bn_act_ref(x, sc, sh, res, rsc, rsh, relu=bool(f.get("relu")))
+    return y, bits, want, mag
+
+
+@_nc(NC.BN_ACT + [r for r in NC.STRIDE if r[0] == "bn_act"])
+def test_bn_act_f64(row):
+    """relu(fma(x, sc, sh) + fma(r, rsc, rsh)) per element against float64; ybits = the sign of the STORED value, bit for bit.  The rows
+    with N = None lie above the grid cap: every thread takes a second trip with the constants it cached before the loop"""
+    K = _k()
+    _, dt, shape, spec, _ = row
+    f = _route_flags(spec)
+    shape = _over_cap(shape, dt)
+    y, bits, want, mag = _run_bn_act(K, dt, shape, f)
+    B.check(y, want, B.bound(want, mag, 0, dt), "bn_act " + spec, "bn_act_kernel")
+    if bits is not None:
+        assert torch.equal(bits, _bits(y.float())), "ybits != sign of the stored y"
+
+
+def _pool_inputs(dt, shape, seed=720):
+    N, H, W, C = shape
+    x = q(rnd(seed, (N, H, W, C), 2.0), dt)
+    sc, sh = rnd(seed + 1, (C,)), rnd(seed + 2, (C,))
+    sc[1], sh[1] = 0.0, 0.25          # scale == 0: every window element ties at 0.25 -- the first one inside the map wins
+    if C > 9:
+        sc[9], sh[9] = 0.0, -0.5      # ... and ties at a non-positive value: code 9
+    sc[0], sc[2] = sc[0] * 1e3, sc[2] * 1e-3
+    return x, sc, sh
+
+
+def _check_pool_fwd(K, dt, x, sc, sh, what):
+    pooled, am = K.bn_relu_maxpool(to_dev(x, dt), sc.to(DEV), sh.to(DEV))
+    r = B.maxpool_ref(x, sc, sh, dt)
+    B.check(pooled, r["y"], r["bnd"], what + " values", "bn_relu_maxpool")
+    B.capped(r["unsure"], what + " near-ties")
+    got = am.cpu().long()
+    ok = (got == r["code"]) | r["unsure"]
+    assert bool(ok.all()), f"{what}: {int((~ok).sum())} argmax codes differ from the float64 window, first at {tuple(int(v) for v in (~ok).nonzero()[0])}"
+    return pooled, am, r
+
+
+@_nc([r for r in NC.STRIDE if r[0] == "bn_relu_maxpool"])
+def test_maxpool_generic_above_the_cap_f64(row):
+    """the generic pooling form (chunks per pixel do not divide 256) on an output above the grid cap: values and codes"""
+    K = _k()
+    _, dt, shape, _, _ = row
+    N, OH, OW, C = _over_cap(shape, dt)
+    x, sc, sh = _pool_inputs(dt, (N, 2 * OH, 2 * OW, C))
+    sc, sh = _channel_scale(731, C), rnd(732, (C,))          # constants a foreign chunk cannot stand in for
+    _check_pool_fwd(K, dt, x, sc, sh, f"generic max-pool C={C}")
+
+
+@_nc(NC.POOL)
+def test_pool_f64(row):
+    """max-pool forward (values, argmax codes against the float64 window), its backward through the codes, avg-pool forward / backward"""
+    K = _k()
+    _, dt, shape, spec, _ = row
+    f = _route_flags(spec)
+    shape = _over_cap(shape, dt)
+    N, H, W, C = shape
+    x, sc, sh = _pool_inputs(dt, shape)
+    if f.get("bwd_only"):
+        r = B.maxpool_ref(x, sc, sh, dt)
+        pooled, am = to_dev(q(r["y"].float(), dt), dt), r["code"].to(torch.uint8).to(DEV)
+    else:
+        pooled, am, r = _check_pool_fwd(K, dt, x, sc, sh, "max-pool")
+    OH, OW = pooled.shape[1:3]
+    dyp = q(rnd(725, (N, OH, OW, C)), dt)
+    dx = K.maxpool_relu_bwd(to_dev(dyp, dt), am, to_dev(x, dt), sc.to(DEV), sh.to(DEV))
+    want, mag = B.maxpool_bwd_ref(dyp, am.cpu(), r["pre"], (H, W))
+    unsure = B.mask_unsure(r["pre"], r["premag"])
+    B.capped(unsure, "pre-activations at the ReLU threshold")
+    bnd = torch.where(unsure, torch.full_like(mag, math.inf), B.bound(want, mag, 0, dt))
+    B.check(dx, want, bnd, "max-pool backward", "maxpool_relu_bwd_kernel")
+    ps = pooled.float().cpu()
+    ap = K.avgpool_fwd(pooled)
+    a64, amag, hw = B.avgpool_ref(ps)
+    B.check(ap, a64, B.bound(a64, amag, hw, 0), "avg-pool", "avgpool_fwd_kernel", dims="nc")
+    dyv = rnd(726, (N, C))
+    full = (N, H, W, C) if f.get("bwd_only") else tuple(pooled.shape)          # above the cap: the un-pooled map
+    dap = K.avgpool_bwd(dyv.to(DEV), full, dt)
+    w64 = (dyv.double() / (full[1] * full[2]))[:, None, None, :].expand(full)
+    B.check(dap, w64, B.bound(w64, w64.abs(), 0, dt), "avg-pool backward", "avgpool_bwd_kernel")
+
+
+def _bn_bwd_inputs(dt, shape, nseg, seed=740):
+    """x with a channel of mean / std = 30, and the fp32 constants a forward would have left: per segment"""
+    N, H, W, C = shape
+    x = rnd(seed, (N, H, W, C), 2.0) + 0.7
+    x[..., 2] = rnd(seed + 1, (N, H, W)) + 30.0
+    x = q(x, dt)
+    gamma, beta = _channel_scale(seed + 2, C), rnd(seed + 3, (C,))
+    xs = x.double().reshape(nseg, -1, C)
+    mean, var = xs.mean(1), xs.var(1, unbiased=False)
+    invstd = 1.0 / torch.sqrt(var + 1e-5)
+    sc = (gamma.double() * invstd).float()
+    sh = (beta.double() - mean * gamma.double() * invstd).float()
+    sq = (lambda t: t.contiguous()) if nseg > 1 else (lambda t: t[0].contiguous())
+    return x, sq(sc), sq(sh), sq(mean.float()), sq(invstd.float())
+
+
+@_nc(NC.BN_BWD)
+def test_bn_bwd_f64(row):
+    """both sums of the reduce pass, g, dx = cA g + cB x + cC from the kernel's own sums, and the affine gradients, against float64 --
+    g formed as each mode forms it"""
+    K = _k()
+    _, dt, shape, spec, _ = row
+    f = _route_flags(spec)
+    N, H, W, C = shape
+    nseg = 3 if f.get("nseg3") else 1
+    x, sc, sh, mean, invstd = _bn_bwd_inputs(dt, shape, nseg)
+    count = N * H * W // nseg
+    dev = lambda t: t.to(DEV) if t is not None else None      # noqa: E731
+    dy = q(rnd(745, (N, H, W, C)), dt)
+    kw, g_err, gather = {}, None, 0
+    yact = None
+    base_g, base_b = rnd(746, (C,)), rnd(747, (C,))
+    dg, db = base_g.to(DEV), base_b.to(DEV)
+    pooled_form = f.get("pool") or f.get("pool_y")
+    if pooled_form:
+        sc = sc.clone()
+        sc[5] = 0.0                                  # (pool_y: a channel that cannot be inverted fetches x at the argmax position)
+        sh = sh.clone()
+        sh[5] = 0.25
+        pooled, am = K.bn_relu_maxpool(to_dev(x, dt), dev(sc), dev(sh))
+        dyp = q(rnd(748, tuple(pooled.shape)), dt)
+        kw = dict(relu_from_x=True, pool=(to_dev(dyp, dt), am) + ((pooled,) if f.get("pool_y") else ()))
+        g64, gmag = B.bn_bwd_g(None, x, sc, sh, relu_from_x=True, pool=(dyp, am.cpu()))
+        g_err, gather = 3 * B.U * gmag, 3
+        dx, sums, g = K.bn_bwd(None, to_dev(x, dt), dev(sc), dev(sh), dev(mean), dev(invstd), want_g=True, dgamma=dg, dbeta=db, **kw)
+    else:
+        if f.get("yact") or f.get("yact_gir") or f.get("yact_bits"):
+            ya, _ = B.bn_act_ref(x, sc, sh, relu=True)
+            yact = q(ya.float(), dt)
+            kw = dict(yact=to_dev(yact, dt), g_in_reduce=bool(f.get("yact_gir")))
+            if f.get("yact_bits"):
+                kw["yact_bits"] = _bits(kw["yact"].float())
+        elif f.get("from_x"):
+            kw = dict(relu_from_x=True)
+        g64, gmag = B.bn_bwd_g(dy, x, sc, sh, yact=yact, relu_from_x=bool(f.get("from_x")))
+        dx, sums, g = K.bn_bwd(to_dev(dy, dt), to_dev(x, dt), dev(sc), dev(sh), dev(mean), dev(invstd), want_g=True, nseg=nseg,
+                               dgamma=dg, dbeta=db, **kw)
+    name = "bn_bwd " + spec
+    if f.get("pool_y"):
+        s64, sb = B.bn_bwd_pool_sums_ref(dyp, pooled.float().cpu(), am.cpu(), x, sc, sh, mean)
+        B.check(sums.cpu(), s64, sb, name + " sums", "bn_bwd_reduce_pool_kernel", dims="sc")
+    else:
+        s64, sb = B.bn_bwd_sums_ref(g64, gmag, x, mean, gather)
+        B.check(sums.cpu().view(nseg, 2, C), s64, sb, name + " sums", "bn_bwd_reduce_kernel", dims="zsc")
+    if gather:
+        B.check(g, g64, B.bound(g64, gmag, 0, dt), name + " g", "bn_bwd_g")
+    else:
+        assert torch.equal(g.float().cpu().double(), g64), "g is dy under the mask, bit for bit"
+    want, bnd = B.bn_bwd_apply_ref(g64, x, sc, invstd, mean, sums, count, dt, g_err)
+    B.check(dx, want, bnd, name + " dx", "bn_bwd_apply")
+    wg, bg, wb, bb = B.bn_param_grads_ref(sums, invstd, base_g, base_b)
+    B.check(dg, wg, bg, name + " dgamma", "bn_bwd_param_grads", dims="c")
+    B.check(db, wb, bb, name + " dbeta", "bn_bwd_param_grads", dims="c")
+    # sslcr_bn_param_grads, the stand-alone launch: the same two roundings onto the same values
+    if nseg == 1:
+        dg2, db2 = base_g.to(DEV), base_b.to(DEV)
+        K.bn_param_grads(sums, dev(invstd), dg2, db2)
+        B.check(dg2, wg, bg, name + " dgamma (bn_param_grads)", "bn_param_grads_kernel", dims="c")
+        B.check(db2, wb, bb, name + " dbeta (bn_param_grads)", "bn_param_grads_kernel", dims="c")
+
+
+@_nc([r for r in NC.STRIDE if r[0] == "bn_bwd_apply"])
+def test_bn_bwd_apply_odd_width_above_the_cap_f64(row):
+    """sslcr_bn_bwd_apply alone (the reduce pass rejects these widths) from sums the test provides, above the grid cap"""
+    K = _k()
+    _, dt, shape, spec, _ = row
+    f = _route_flags(spec)
+    shape = _over_cap(shape, dt)
+    N, H, W, C = shape
+    x, sc, sh, mean, invstd = _bn_bwd_inputs(dt, shape, 1)
+    dy = q(rnd(745, shape), dt)
+    yact = None
+    if f.get("yact"):
+        yact = q(B.bn_act_ref(x, sc, sh, relu=True)[0].float(), dt)
+    g64, gmag = B.bn_bwd_g(dy, x, sc, sh, yact=yact, relu_from_x=bool(f.get("relu_from_x")))
+    xm = x.double() - mean.double()
+    sums = torch.stack([g64.reshape(-1, C).sum(0), (g64 * xm).reshape(-1, C).sum(0)]).to(DEV)
+    dx, _, g = K.bn_bwd(to_dev(dy, dt), to_dev(x, dt), sc.to(DEV), sh.to(DEV), mean.to(DEV), invstd.to(DEV), want_g=True, sums=sums,
+                        yact=to_dev(yact, dt) if yact is not None else None, relu_from_x=bool(f.get("relu_from_x")))
+    assert torch.equal(g.float().cpu().double(), g64), "g is dy under the mask, bit for bit"
+    want, bnd = B.bn_bwd_apply_ref(g64, x, sc, invstd, mean, sums, N * H * W, dt)
+    B.check(dx, want, bnd, f"bn_bwd_apply C={C} " + spec, "bn_bwd_apply_kernel")
+
+
+def test_cases_above_the_cap_would_meet_the_cached_constant_defect():
+    """the stride rows are only worth their time if a grid capped WITHOUT the rounding would hand their threads foreign constants"""
+    cap = _ew_cap()
+    for _, dt, shape, _, _ in NC.STRIDE:
+        N, H, W, C = _over_cap(shape, dt)
+        cols = C // (8 if dt == 1 else 4)
+        items = N * H * W * cols
+        col = torch.arange(items) % cols
+        assert int((B.cached_column(items, cols, B.capped_grid(items, cap)) != col).sum()) > 0, (shape, dt)
+        assert int((B.cached_column(items, cols, B.rounded_grid(items, cols, cap)) != col).sum()) == 0, (shape, dt)
+
+
+def _finalize_partials(rows, C, count1, seed=760):
+    """fp32 partial rows of a tensor with channel 0 at mean / std = 1e3 and a constant channel 1; k elements per row"""
+    k = 1 if count1 else 16
+    g = np.random.RandomState(seed)
+    mu, sd = g.standard_normal(C) * 2.0, np.abs(g.standard_normal(C)) + 0.5
+    mu[0], sd[0] = 1e3, 1.0
+    sd[1], mu[1] = 0.0, 2.5
+    v = mu[None, None, :] + sd[None, None, :] * g.standard_normal((rows, k, C))
+    part = np.stack([v.sum(1), (v * v).sum(1)], 1).astype(np.float32)
+    return torch.from_numpy(part), float(rows * k)
+
+
+@_nc(NC.BN_FINALIZE)
+def test_bn_finalize_f64(row):
+    """scale, shift, mean, invstd and the running statistics after three replayed updates, from fp32 partial rows, against an
+    extended-precision reference: the final fp32 rounding plus the double roundoff through the variance's condition number"""
+    K = _k()
+    _, _, (rows, C, nseg), spec, _ = row
+    f = _route_flags(spec)
+    part, total = _finalize_partials(rows, C, f.get("count1"))
+    count = total / nseg
+    gamma, beta = _channel_scale(761, C), rnd(762, (C,))
+    rm, rv = rnd(763, (C,)), rnd(764, (C,)).abs() + 0.5
+    rm_d, rv_d = rm.to(DEV), rv.to(DEV)
+    nbt = torch.zeros((), dtype=torch.int64, device=DEV)
+    got = K.bn_finalize(part.to(DEV), count, gamma.to(DEV), beta.to(DEV), running_mean=rm_d, running_var=rv_d, nbt=nbt, replay=3, nseg=nseg)
+    ref = B.bn_finalize_ref(part, count, gamma, beta, rm, rv, replay=3, nseg=nseg)
+    for name, t in zip(("scale", "shift", "mean", "invstd"), got):
+        B.check(t.view(nseg, C), ref[name][0], ref[name][1], f"bn_finalize {rows}x{C}/{nseg} {name}", "bn_finalize_kernel", dims="zc")
+    B.check(rm_d, *ref["running_mean"], f"bn_finalize {rows}x{C}/{nseg} running_mean", "bn_finalize_kernel", dims="c")
+    B.check(rv_d, *ref["running_var"], f"bn_finalize {rows}x{C}/{nseg} running_var", "bn_finalize_kernel", dims="c")
+    assert int(nbt.item()) == 3 * nseg
+    assert float(got[3].view(nseg, C)[0, 1]) == pytest.approx(1.0 / math.sqrt(float(np.float32(1e-5))), rel=1e-6)      # the constant channel
+
+
+@_nc(NC.GEMM)
+def test_linear_f64(row):
+    """forward (bias + ReLU, and plain), dx, dw and db into non-zero buffers, with and without the ReLU mask, against float64"""
+    K = _k()
+    _, _, (M, Kd, Nn), _, _ = row
+    x, w, b = rnd(781, (M, Kd)), rnd(782, (Nn, Kd), 0.03), rnd(783, (Nn,))
+    xd, wd, bd = x.to(DEV), w.to(DEV), b.to(DEV)
+    y = K.linear_fwd(xd, wd, bd, relu=True)
+    want, mag = B.linear_ref(x, w, bias=b, relu=True)
+    B.check(y, want, B.bound(want, mag, Kd, 0, True), "linear forward", "gemm_f32", dims="mn")
+    want, mag = B.linear_ref(x, w)
+    B.check(K.linear_fwd(xd, wd, None, relu=False), want, B.bound(want, mag, Kd, 0, True), "linear forward, plain", "gemm_f32", dims="mn")
+    dy = rnd(784, (M, Nn))
+    for masked in (True, False):
+        g = torch.where(y.cpu() > 0, dy, torch.zeros_like(dy)) if masked else dy
+        base_w, base_b, base_x = rnd(785, (Nn, Kd)), rnd(786, (Nn,)), rnd(787, (M, Kd))
+        dw, db, dxb = base_w.to(DEV), base_b.to(DEV), base_x.to(DEV)
+        dx = K.linear_bwd(xd, wd, dy.to(DEV), yact=y if masked else None, dw=dw, db=db)
+        tag = " (masked)" if masked else ""
+        want, mag = B.linear_ref(g, w.t())
+        B.check(dx, want, B.bound(want, mag, Nn, 0, True), "linear dx" + tag, "gemm_f32", dims="mk")
+        want, mag = B.linear_ref(g.t(), x.t(), base=base_w)
+        B.check(dw, want, B.bound(want, mag, M, 0, True), "linear dw" + tag, "gemm_f32", dims="nk")
+        want, mag = B.colsum_ref(g, base_b)
+        B.check(db, want, B.bound(want, mag, M, 0), "linear db" + tag, "relu_mask_colsum_kernel", dims="n")
+        K.linear_bwd(xd, wd, dy.to(DEV), yact=y if masked else None, dx=dxb, dx_accumulate=True)
+        want, mag = B.linear_ref(g, w.t(), base=base_x)
+        B.check(dxb, want, B.bound(want, mag, Nn, 0, True), "linear dx accumulated" + tag, "gemm_f32", dims="mk")
+
+
+def _logits(seed, shape, shift=False):
+    t = rnd(seed, shape)
+    t = t * (80.0 / float(t.abs().max()))
+    if shift:
+        t[0] += 100.0
+        t[1] -= 100.0
+    return t
+
+
+def test_device_expf_error_measured():
+    """the one constant of tests/_f64.py that cannot be derived: the device expf (and the add and divide around it) through softmax_col on
+    two-column logits (0, t), t in [-87, 0], against float64.  The recorded worst value must still hold"""
+    K = _k()
+    t = torch.from_numpy(-87.0 * np.random.RandomState(790).random_sample(200000).astype(np.float32))
+    lg = torch.stack([torch.zeros_like(t), t], 1).contiguous()
+    got = K.softmax_col(lg.to(DEV), 1).cpu().double()
+    e = torch.exp(t.double())
+    p = e / (1.0 + e)
+    worst = float(((got - p).abs() / (B.U * p)).max())
+    print(f"[f64] device expf through softmax_col | softmax_col_kernel | worst error {worst:.4f} u (recorded {B.EXPLOG_MEASURED_ULP})")
+    assert worst <= B.EXPLOG_MEASURED_ULP, f"measured {worst:.4f} u > the recorded {B.EXPLOG_MEASURED_ULP} u: re-derive EXPLOG_ULP"
+
+
+@_nc(NC.LOSS)
+def test_loss_f64(row):
+    """the three losses and dlogits against float64 with nx = 300 / nu = 700 rows (every thread's row loop takes a second trip) and
+    logits up to +-80; 'shift': rows offset by +-100, where softmax without the max subtraction overflows"""
+    K = _k()
+    _, _, (kind, Cn, nx, nu), spec, _ = row
+    shift = "shift" in spec
+    lg = _logits(800 + Cn, (nx + nu, Cn), shift)
+    lt = _logits(801 + Cn, (max(nu, 1), Cn))
+    lam = float(np.float32(0.7))
+    inx, inu = float(np.float32(1.0 / nx)), float(np.float32(1.0 / max(1, nu)))
+    ce = kind in (1, 2)
+    if ce:
+        tgt = torch.from_numpy(np.random.RandomState(802).randint(0, Cn, (nx,)).astype(np.int64))
+        out, dl = K.loss(kind, lg.to(DEV), logits_t=lt.to(DEV) if kind == 1 else None, target_i=tgt.to(DEV), nx=nx, lambda_u=0.7)
+        rows, e_rows, dlx, e_dlx = B.ce_rows(lg[:nx], tgt, inx)
+        lx, ex = B.loss_total(rows, e_rows, inx, 0)
+        correct = int((lg[:nx].argmax(1) == tgt).sum())
+    else:
+        tf = rnd(803, (nx,)).abs() * 40.0
+        out, dl = K.loss(kind, lg.to(DEV), logits_t=lt.to(DEV) if kind == 0 else None, target_f=tf.to(DEV), nx=nx, lambda_u=0.7)
+        sq, dlx, e_dlx = B.mse_rows(lg[:nx], tf.view(-1, 1).expand(nx, Cn), inx)
+        lx, ex = B.loss_total(sq, torch.zeros(()), inx / Cn, 3)
+        correct = None
+    lu, eu = 0.0, 0.0
+    dlu = e_dlu = torch.zeros((nu, Cn), dtype=torch.float64)
+    if kind == 1:
+        rows, e_rows, dlu, e_dlu = B.ce_rows(lg[nx:], lt.argmax(1), lam * inu)
+        lu, eu = B.loss_total(rows, e_rows, inu, 0)
+    elif kind == 0:
+        sq, dlu, e_dlu = B.mse_rows(lg[nx:], lt, lam * inu, ops=5)
+        lu, eu = B.loss_total(sq, torch.zeros(()), inu / Cn, 3)
+    total = lx + lam * lu
+    et = ex + lam * eu + 2 * B.U * (abs(lx) + lam * abs(lu))
+    o = out.cpu()
+    B.check(o[:3], torch.tensor([total, lx, lu], dtype=torch.float64), torch.tensor([et, ex, eu], dtype=torch.float64),
+            f"loss kind {kind} C={Cn} {spec}", "loss_kernel", dims="i")
+    if correct is not None:
+        assert int(o[3]) == correct
+    B.check(dl, torch.cat([dlx, dlu]), torch.cat([e_dlx, e_dlu]), f"dlogits kind {kind} C={Cn} {spec}", "loss_kernel", dims="nc")
+
+
+@_nc(NC.SOFTMAX)
+def test_softmax_col_f64(row):
+    K = _k()
+    _, _, (n, Cn), _, _ = row
+    lg = _logits(810 + Cn, (n, Cn))
+    for col in (0, Cn - 1):
+        want, bnd = B.softmax_col_ref(lg, col)
+        B.check(K.softmax_col(lg.to(DEV), col), want, bnd, f"softmax_col C={Cn} col={col}", "softmax_col_kernel", dims="n")
+
+
+def _stem_operands(K, shape, in_u8, dtype, seed):
+    N, H, W = shape
+    xu = torch.from_numpy(np.random.RandomState(seed).randint(0, 256, (N, 3, H, W), dtype=np.uint8))
+    w = rnd(seed + 1, (64, 3, 7, 7), 0.03)
+    bn = (_channel_scale(seed + 2, 64), rnd(seed + 3, (64,)), rnd(seed + 4, (64,)), rnd(seed + 5, (64,)).abs() + 0.5)
+    xin = (xu if in_u8 else xu.float()).to(DEV)
+    return xu, xu.permute(0, 2, 3, 1).double(), w, bn, xin
+
+
+def _check_folded_pack(w, bn, wk2, bias, dtype):
+    g, b, rm, rv = (t.double() for t in bn)
+    f = g / torch.sqrt(rv + float(np.float32(1e-5)))
+    w64 = w.double().permute(0, 2, 3, 1) * f.view(-1, 1, 1, 1)
+    B.check(wk2, w64, B.bound(w64, w64.abs(), 0, dtype), "folded stem filter", "pack_stem_kernel", dims="krsc")
+    B.check(bias, b - rm * f, 6 * B.U * (b.abs() + (rm * f).abs()), "folded stem bias", "pack_stem_kernel", dims="k")
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+@pytest.mark.parametrize("in_u8", [True, False])
+@pytest.mark.parametrize("shape", [(2, 64, 64), (3, 56, 40), (1, 256, 256), (2, 30, 34)])
+def test_stem_f64(shape, in_u8, dtype):
+    """the shapes of test_stem against float64: forward + partial statistics, the folded form, both weight gradients (into a non-zero
+    buffer; the pooled form from the dY its own apply pass stores) -- reduction lengths 147 and N * OH * OW"""
+    K = _k()
+    f32 = dtype == 0
+    xu, x, w, bn, xin = _stem_operands(K, shape, in_u8, dtype, 831)
+    N = shape[0]
+    wp, _ = K.pack_stem(w.to(DEV), dtype)
+    wk = B.stem_unpack(wp)
+    assert torch.equal(wk, q(w, dtype).permute(0, 2, 3, 1)), "the plain pack is the filter rounded to the storage dtype"
+    y, stats = K.stem_conv(xin, wp, want_stats=True)
+    want, mag, acc, amag = B.conv_fwd(x, wk, 2, 3)
+    B.check(y, want, B.bound(want, mag, 147, dtype, f32), "stem forward", "stem_fwd_kernel")
+    B.check_stats(stats, acc, amag, 147, "stem statistics", "stem_fwd_kernel", f32)
+    wp2, bias = K.pack_stem(w.to(DEV), dtype, bn=tuple(t.to(DEV) for t in bn))
+    wk2 = B.stem_unpack(wp2)
+    _check_folded_pack(w, bn, wk2, bias, dtype)
+    y2 = K.stem_conv(xin, wp2, bias=bias, relu=True)
+    want2, mag2, _, _ = B.conv_fwd(x, wk2, 2, 3, bias=bias.cpu(), relu=True)
+    B.check(y2, want2, B.bound(want2, mag2, 147, dtype, f32), "stem folded", "stem_fwd_kernel")
+    OH, OW = want.shape[1:3]
+    dy = q(rnd(837, (N, OH, OW, 64)), dtype)
+    base = rnd(838, (64, 3, 7, 7))
+    dw = base.clone().to(DEV)
+    K.stem_wgrad(xin, to_dev(dy, dtype), dw)
+    wantw, magw = B.conv_wgrad(x, dy, (64, 7, 7, 3), 2, 3, base=base.permute(0, 2, 3, 1))
+    B.check(dw.permute(0, 2, 3, 1), wantw, B.bound(wantw, magw, N * OH * OW, 0, f32), "stem wgrad", "stem_wgrad", dims="krsc")
+    # the pooled form: bn0's backward apply on the tile in LDS -- dY is what sslcr_bn_bwd_apply stores (checked in test_bn_bwd_f64)
+    gamma, beta = bn[0].abs() * 0.01 + 0.5, bn[1]
+    sc, sh, mean, invstd = K.bn_finalize(stats, N * OH * OW, gamma.to(DEV), beta.to(DEV))
+    pooled, am = K.bn_relu_maxpool(y, sc, sh)
+    dyp = to_dev(q(rnd(839, tuple(pooled.shape)), dtype), dtype)
+    dx, _, _ = K.bn_bwd(None, y, sc, sh, mean, invstd, relu_from_x=True, pool=(dyp, am, pooled))
+    dw2 = base.clone().to(DEV)
+    K.stem_wgrad_pool(xin, dw2, y, sc, sh, mean, invstd, (dyp, am, pooled))
+    wantp, magp = B.conv_wgrad(x, dx.float().cpu(), (64, 7, 7, 3), 2, 3, base=base.permute(0, 2, 3, 1))
+    B.check(dw2.permute(0, 2, 3, 1), wantp, B.bound(wantp, magp, N * OH * OW, 0, f32), "stem wgrad from the pooled gradient", "stem_wgrad_pool", dims="krsc")
+
+
+@pytest.mark.parametrize("in_u8", [True, False])
+@pytest.mark.parametrize("shape,split", [((2, 64, 64), 0), ((3, 256, 256), 0), ((5, 224, 224), 2), ((260, 64, 96), 0), ((3, 96, 64), 1)])
+def test_stem_conv_pool_f64(shape, split, in_u8):
+    """the shapes of test_stem_conv_pool_fused against float64, in the folded form and with the scale in the epilogue (out_scale)"""
+    K = _k()
+    xu, x, w, bn, xin = _stem_operands(K, shape, in_u8, 1, 841)
+    a, b = (xin[:split].contiguous(), xin[split:].contiguous()) if split else (xin, None)
+    wp2, bias = K.pack_stem(w.to(DEV), 1, bn=tuple(t.to(DEV) for t in bn))
+    wk2 = B.stem_unpack(wp2)
+    _check_folded_pack(w, bn, wk2, bias, 1)
+    y64, mag, _, _ = B.conv_fwd(x, wk2, 2, 3, bias=bias.cpu(), relu=True)
+    want, bnd = B.maxpool_plain_ref(y64, B.bound(y64, mag, 147, 1))
+    B.check(K.stem_conv_pool(a, wp2, bias, x2=b), want, bnd, "stem + pool, folded", "stem_conv_pool")
+    if shape[0] > 5:          # (the 260-image case is about workgroups walking into a second image: one form is enough)
+        return
+    wpu, bias_u, scale_u = K.pack_stem(w.to(DEV), 1, bn=tuple(t.to(DEV) for t in bn), unfold=True)
+    y64, mag, _, _ = B.conv_fwd(x, B.stem_unpack(wpu), 2, 3, out_scale=scale_u.cpu(), bias=bias_u.cpu(), relu=True)
+    want, bnd = B.maxpool_plain_ref(y64, B.bound(y64, mag, 147, 1))
+    B.check(K.stem_conv_pool(a, wpu, bias_u, x2=b, out_scale=scale_u), want, bnd, "stem + pool, out_scale", "stem_conv_pool")
+
+
+@pytest.mark.parametrize("kind", ["adam", "sgd"])
+def test_optimizer_step_f64(kind):
+    """one step of Adam / Nesterov SGD from a non-zero fp32 state against float64: p, s1, s2 per element; the shadow-weight packs the
+    update writes are the packs of the updated p, bit for bit"""
+    from ssl_cr_histo_amd import _lib as L
+    K = _k()
+    shapes = [(64, 3, 7, 7), (128, 64, 3, 3), (130,), (10, 768)]
+    ps = [rnd(850 + i, s, 0.1) for i, s in enumerate(shapes)]
+    gs = [rnd(860 + i, s) for i, s in enumerate(shapes)]
+    m0 = [rnd(870 + i, s, 0.3) for i, s in enumerate(shapes)]
+    v0 = [rnd(880 + i, s).abs() * 0.5 + 0.01 for i, s in enumerate(shapes)]
+    dev_p, s1, s2 = ([t.to(DEV).contiguous() for t in ts] for ts in (ps, m0, v0))
+    sh_f = torch.zeros((128, 3, 3, 64), dtype=torch.bfloat16, device=DEV)
+    sh_d = torch.zeros((64, 3, 3, 128), dtype=torch.bfloat16, device=DEV)
+    descs = (L.TensorDesc * len(shapes))()
+    keep, g_param_layout = [], []
+    for i, (p, g) in enumerate(zip(dev_p, gs)):
+        if g.dim() == 4 and i != 0:                           # engine grad layout KRSC against the parameter's KCRS
+            gd, (Kk, Cc, RS) = g.permute(0, 2, 3, 1).contiguous().to(DEV), (g.shape[0], g.shape[1], g.shape[2] * g.shape[3])
+        else:
+            gd, (Kk, Cc, RS) = g.to(DEV), (0, 0, 0)
+        keep.append(gd)
+        descs[i] = L.TensorDesc(L.ptr(p), L.ptr(gd), L.ptr(s1[i]), L.ptr(s2[i]), p.numel(), Kk, Cc, RS)
+        if i == 1:
+            descs[i].w_fwd, descs[i].w_dgrad, descs[i].pack_dtype, descs[i].dgrad_flip = L.ptr(sh_f), L.ptr(sh_d), 1, 1
+    dd = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(DEV)
+    step = 4
+    hp = dict(lr=1e-2, beta1=0.9, beta2=0.999, eps=1e-8, wd=1e-4, momentum=0.9, bc1=1 - 0.9 ** step, bc2=1 - 0.999 ** step, first_step=0)
+    o = L.OptDesc(0 if kind == "adam" else 1, hp["lr"], hp["beta1"], hp["beta2"], hp["eps"], hp["wd"], hp["momentum"], hp["bc1"], hp["bc2"], 0, 1.0)
+    L.check(L.lib().sslcr_optimizer_step(L.ptr(dd), len(shapes), max(p.numel() for p in dev_p), o, L.stream_ptr()))
+    torch.cuda.synchronize()
+    for i in range(len(shapes)):
+        ref = B.optimizer_ref(0 if kind == "adam" else 1, ps[i], gs[i], m0[i], v0[i], **hp)
+        for name, got in (("p", dev_p[i]), ("s1", s1[i])) + ((("s2", s2[i]),) if kind == "adam" else ()):
+            B.check(got.flatten(), ref[name][0].flatten(), ref[name][1].flatten(), f"{kind} tensor {i} {name}", "optimizer_kernel", dims="i")
+        if kind == "sgd":
+            assert torch.equal(s2[i].cpu(), v0[i]), "SGD leaves s2 alone"
+    wf1, wd1, _ = K.pack_conv(dev_p[1], 1, fwd=True, dgrad=True, dgrad_flip=True)
+    assert torch.equal(sh_f, wf1) and torch.equal(sh_d, wd1), "shadow weights written by the update != pack of the updated parameter"
