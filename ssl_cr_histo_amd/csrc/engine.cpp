@@ -312,40 +312,42 @@ int all_reduce(sslcr_ctx* c, int chan, void* buf, size_t count, bool f64, hipStr
   return 0;
 }
 
-// ---- launch wrappers: when profiling is on, bracket the kernel with HIP events on ITS stream and book the
-// algorithmic work (forward-conv FLOPs even for the strided dgrad gather, whose zero taps are not counted)
-hipError_t prof_conv(sslcr_ctx* c, int dt, const ConvArgs& a, hipStream_t st) {
-  if (!c->prof.on) return launch_conv(dt, a, st);
+// ---- launch wrappers.  The one profiling bracket: with the profiler off it is launch() and nothing else; with it on, two HIP events
+// around the launch on ITS stream and a record in rec[slot] (see Profiler).  `book` fills the record's name / flops / bytes -- the
+// algorithmic work (forward-conv FLOPs even for the strided dgrad gather, whose zero taps are not counted) -- and only runs when profiling
+template <class Book, class Launch>
+hipError_t profiled(sslcr_ctx* c, int slot, hipStream_t st, Book&& book, Launch&& launch) {
+  if (!c->prof.on) return launch();
   ProfRec r;
   r.e0 = c->prof.get(); r.e1 = c->prof.get();
-  const double es = c->esz();
-  const double rs = a.tap_mask ? (double)__builtin_popcount(a.tap_mask) : (double)a.R * a.S;
-  const double M = (double)a.N * a.PH * a.PW;
-  const double src = (double)a.N * a.H * a.W;
-  r.flops = a.transposed ? 2.0 * src * a.C * a.K * rs : 2.0 * M * a.K * a.C * rs;
-  r.bytes = (src * a.C + (double)a.K * rs * a.C + M * a.K * (a.residual ? 2.0 : 1.0) * (a.accumulate ? 2.0 : 1.0)) * es;
-  r.name = conv_kernel_name(dt, a);
+  book(r);
   (void)hipEventRecord(r.e0, st);
-  hipError_t e = launch_conv(dt, a, st);
+  hipError_t e = launch();
   (void)hipEventRecord(r.e1, st);
-  c->prof.rec[0].push_back(r);
+  c->prof.rec[slot].push_back(r);
   return e;
+}
+hipError_t prof_conv(sslcr_ctx* c, int dt, const ConvArgs& a, hipStream_t st) {
+  auto book = [&](ProfRec& r) {
+    const double es = c->esz();
+    const double rs = a.tap_mask ? (double)__builtin_popcount(a.tap_mask) : (double)a.R * a.S;
+    const double M = (double)a.N * a.PH * a.PW, src = (double)a.N * a.H * a.W;
+    r.flops = a.transposed ? 2.0 * src * a.C * a.K * rs : 2.0 * M * a.K * a.C * rs;
+    r.bytes = (src * a.C + (double)a.K * rs * a.C + M * a.K * (a.residual ? 2.0 : 1.0) * (a.accumulate ? 2.0 : 1.0)) * es;
+    r.name = conv_kernel_name(dt, a);
+  };
+  return profiled(c, 0, st, book, [&] { return launch_conv(dt, a, st); });
 }
 // a downsampling block's conv1 (3x3 / 2) and 1x1 / 2 projection of one input in one launch (conv_s2.hip)
 hipError_t prof_conv_pair(sslcr_ctx* c, const ConvArgs& a, const ConvArgs& d, hipStream_t st) {
-  if (!c->prof.on) return launch_conv_s2(a, &d, st);
-  ProfRec r;
-  r.e0 = c->prof.get(); r.e1 = c->prof.get();
-  const double es = c->esz();
-  const double M = (double)a.N * a.PH * a.PW, src = (double)a.N * a.H * a.W;
-  r.flops = 2.0 * M * a.K * a.C * 10.0;
-  r.bytes = (src * a.C + (double)a.K * 10.0 * a.C + 2.0 * M * a.K) * es;
-  r.name = conv_s2_name(a, true);
-  (void)hipEventRecord(r.e0, st);
-  hipError_t e = launch_conv_s2(a, &d, st);
-  (void)hipEventRecord(r.e1, st);
-  c->prof.rec[0].push_back(r);
-  return e;
+  auto book = [&](ProfRec& r) {
+    const double es = c->esz();
+    const double M = (double)a.N * a.PH * a.PW, src = (double)a.N * a.H * a.W;
+    r.flops = 2.0 * M * a.K * a.C * 10.0;
+    r.bytes = (src * a.C + (double)a.K * 10.0 * a.C + 2.0 * M * a.K) * es;
+    r.name = conv_s2_name(a, true);
+  };
+  return profiled(c, 0, st, book, [&] { return launch_conv_s2(a, &d, st); });
 }
 inline bool fp8_layer(const sslcr_ctx* c, const ConvL& L) {
   return c->fp8 && L.k == 3 && L.stride == 1 && L.cin % 128 == 0 && L.cout % 128 == 0;
@@ -366,33 +368,23 @@ hipError_t prof_conv_fwd(sslcr_ctx* c, int dt, const ConvArgs& a_in, const ConvL
   q.x_scale = 1.0f;
   q.x_scale_dev = L.f8s ? L.f8s + (folded ? 2 : 0) : nullptr;
   q.amax_out = L.f8s ? L.f8s + (folded ? 3 : 1) : nullptr;
-  if (!c->prof.on) return launch_conv_fp8(a, q, st);
-  ProfRec r;
-  r.e0 = c->prof.get(); r.e1 = c->prof.get();
-  const double M = (double)a.N * a.PH * a.PW;
-  r.flops = 2.0 * M * a.K * a.C * 9.0;
-  r.bytes = ((double)a.N * a.H * a.W * a.C + M * a.K * (a.residual ? 2.0 : 1.0)) * 2.0 + (double)a.K * 9.0 * a.C;
-  r.name = conv_fp8_name(a);
-  (void)hipEventRecord(r.e0, st);
-  hipError_t e = launch_conv_fp8(a, q, st);
-  (void)hipEventRecord(r.e1, st);
-  c->prof.rec[0].push_back(r);
-  return e;
+  auto book = [&](ProfRec& r) {
+    const double M = (double)a.N * a.PH * a.PW;
+    r.flops = 2.0 * M * a.K * a.C * 9.0;
+    r.bytes = ((double)a.N * a.H * a.W * a.C + M * a.K * (a.residual ? 2.0 : 1.0)) * 2.0 + (double)a.K * 9.0 * a.C;
+    r.name = conv_fp8_name(a);
+  };
+  return profiled(c, 0, st, book, [&] { return launch_conv_fp8(a, q, st); });
 }
 hipError_t prof_wgrad(sslcr_ctx* c, int dt, const WgradArgs& a, hipStream_t st) {
-  if (!c->prof.on) return launch_wgrad(dt, a, st);
-  ProfRec r;
-  r.e0 = c->prof.get(); r.e1 = c->prof.get();
-  const double es = c->esz();
-  const double M = (double)a.N * a.OH * a.OW;
-  r.flops = 2.0 * M * a.K * a.C * a.R * a.S;
-  r.bytes = ((double)a.N * a.H * a.W * a.C + M * a.K) * es + (double)a.K * a.R * a.S * a.C * 4.0;
-  r.name = wgrad_kernel_name(dt, a);
-  (void)hipEventRecord(r.e0, st);
-  hipError_t e = launch_wgrad(dt, a, st);
-  (void)hipEventRecord(r.e1, st);
-  c->prof.rec[1].push_back(r);
-  return e;
+  auto book = [&](ProfRec& r) {
+    const double es = c->esz();
+    const double M = (double)a.N * a.OH * a.OW;
+    r.flops = 2.0 * M * a.K * a.C * a.R * a.S;
+    r.bytes = ((double)a.N * a.H * a.W * a.C + M * a.K) * es + (double)a.K * a.R * a.S * a.C * 4.0;
+    r.name = wgrad_kernel_name(dt, a);
+  };
+  return profiled(c, 1, st, book, [&] { return launch_wgrad(dt, a, st); });
 }
 
 constexpr int kMaxSeg = 3;      // TripletNet branches run as segments of one launch (backbone_forward_train_segments)
@@ -567,22 +559,28 @@ int pack_conv_layer(sslcr_net* n, ConvL& L, const BnL& bn, int mode, hipStream_t
 }
 
 // ---------------------------------------------------------------- BN finalize (optionally synced across ranks)
-// nseg > 1: `rows` covers nseg segments (equal shares, in order), sv is segment 0's and the others follow seg_stride floats apart
-int finalize_bn(sslcr_net* n, const BnL& bn, const float* partials, int rows, double local_count, BnSaved& sv, int replay, hipStream_t st,
-                int nseg = 1, int seg_stride = 0) {
+// the descriptor of one BatchNorm's finalize launch, all but its count, segments and sums: what finalize_bn and finalize_bn_pair share
+BnFinalizeArgs bn_finalize_args(sslcr_net* n, const BnL& bn, const float* partials, int rows, BnSaved& sv, int replay) {
   sslcr_ctx* c = n->ctx;
   BnFinalizeArgs a;
   memset(&a, 0, sizeof(a));
   a.partials = partials; a.rows = rows; a.C = bn.C;
-  a.nseg = nseg; a.seg_stride = seg_stride;
-  if (nseg > 1 && sharded(c) && c->bn_sync) return fail("finalize_bn: segments with synced BatchNorm");
   a.gamma = n->params[bn.pg]; a.beta = n->params[bn.pb];
   a.scale = sv.scale; a.shift = sv.shift; a.mean = sv.mean; a.invstd = sv.invstd;
   a.running_mean = n->bn_rm[bn.bidx]; a.running_var = n->bn_rv[bn.bidx]; a.num_batches_tracked = n->bn_nbt[bn.bidx];
   if (n->f8_calib_pass) { a.running_mean = nullptr; a.running_var = nullptr; a.num_batches_tracked = nullptr; }
   a.momentum = 0.1f; a.eps = 1e-5f; a.replay = replay;
-  a.stage = c->bn_stage;
-  a.tickets = c->bn_tickets;
+  a.stage = c->bn_stage; a.tickets = c->bn_tickets;
+  return a;
+}
+
+// nseg > 1: `rows` covers nseg segments (equal shares, in order), sv is segment 0's and the others follow seg_stride floats apart
+int finalize_bn(sslcr_net* n, const BnL& bn, const float* partials, int rows, double local_count, BnSaved& sv, int replay, hipStream_t st,
+                int nseg = 1, int seg_stride = 0) {
+  sslcr_ctx* c = n->ctx;
+  if (nseg > 1 && sharded(c) && c->bn_sync) return fail("finalize_bn: segments with synced BatchNorm");
+  BnFinalizeArgs a = bn_finalize_args(n, bn, partials, rows, sv, replay);
+  a.nseg = nseg; a.seg_stride = seg_stride;
   if (sharded(c) && c->bn_sync) {
     // global-batch statistics: reduce rows -> [2][C] sums, all-reduce, finalize from the sums
     BnFinalizeArgs r = a;
@@ -607,20 +605,8 @@ int finalize_bn_pair(sslcr_net* n, const BnL& b1, const float* part1, int rows1,
     TRYI(finalize_bn(n, b1, part1, rows1, local_count, sv1, replay, st, nseg, seg_stride));
     return finalize_bn(n, bd, partd, rowsd, local_count, svd, replay, st, nseg, seg_stride);
   }
-  const BnL* bns[2] = {&b1, &bd};
-  const float* parts[2] = {part1, partd};
-  const int rowsv[2] = {rows1, rowsd};
-  BnSaved* svs[2] = {&sv1, &svd};
-  BnFinalizeArgs a[2];
+  BnFinalizeArgs a[2] = {bn_finalize_args(n, b1, part1, rows1, sv1, replay), bn_finalize_args(n, bd, partd, rowsd, svd, replay)};
   for (int i = 0; i < 2; ++i) {
-    memset(&a[i], 0, sizeof(a[i]));
-    a[i].partials = parts[i]; a[i].rows = rowsv[i]; a[i].C = bns[i]->C;
-    a[i].gamma = n->params[bns[i]->pg]; a[i].beta = n->params[bns[i]->pb];
-    a[i].scale = svs[i]->scale; a[i].shift = svs[i]->shift; a[i].mean = svs[i]->mean; a[i].invstd = svs[i]->invstd;
-    a[i].running_mean = n->bn_rm[bns[i]->bidx]; a[i].running_var = n->bn_rv[bns[i]->bidx]; a[i].num_batches_tracked = n->bn_nbt[bns[i]->bidx];
-    if (n->f8_calib_pass) { a[i].running_mean = nullptr; a[i].running_var = nullptr; a[i].num_batches_tracked = nullptr; }
-    a[i].momentum = 0.1f; a[i].eps = 1e-5f; a[i].replay = replay;
-    a[i].stage = c->bn_stage; a[i].tickets = c->bn_tickets;
     BnFinalizeArgs r = a[i];
     r.sums_out = c->bn_sums + (size_t)i * 2 * b1.C;
     TRY(launch_bn_finalize(r, st));                  // rows -> this rank's sums (the stage is consumed before the next launch reuses it)
@@ -1063,36 +1049,47 @@ struct PoolSrc {            // gradient arriving through the stem max-pool (see 
   const void* dy; const uint8_t* argmax; int H, W, OH, OW; const void* y;
 };
 
-// BatchNorm backward in three parts so that independent BatchNorms (a block's bn2 and its projection-shortcut BatchNorm) can
-// share ONE all-reduce of their sums: begin = the reduce pass into `sums` ([2][C] doubles), sync = the all-reduce, end = the apply pass
-// the next sums slot of this backward (nullptr when the ring is used up: the caller then uses c->bn_sums)
-double* take_sums(sslcr_ctx* c) {
-  if (!c->bn_ring.p || c->bn_ring_i >= sslcr_ctx::kBnRing) return nullptr;
-  return (double*)c->bn_ring.p + (size_t)(c->bn_ring_i++) * sslcr_ctx::kBnSlot;
-}
+// One BatchNorm backward as its call site asks for it; what is not set is zero.
+// nseg > 1 (sslcr_bn_bwd_desc.nseg): the tensors hold nseg passes one after the other, `pixels` is their total, the saved statistics
+// are pass 0's (the others seg_stride floats apart), the sums nseg consecutive ring slots, sum_rows / n_sum_rows cover all passes
+struct BnBwdReq {
+  const void *dy = nullptr, *x = nullptr, *yact = nullptr;   // incoming gradient, saved conv output, saved block output (its ReLU mask)
+  void *dx = nullptr, *gout = nullptr;                        // gradient of x; g = dy * (yact > 0) for whoever reads it next
+  int relu_from_x = 0;                                        // the ReLU mask is (bn(x) > 0)
+  size_t pixels = 0;
+  double count = 0.0;                                         // this rank's elements per channel of ONE BatchNorm batch
+  const PoolSrc* pool = nullptr;
+  int g_in_reduce = 0;                                        // the reduce pass writes gout, the apply pass reads it instead of (dy, yact)
+  // the dgrad that produced dy already left partial rows of (sum g, sum g (x - mean)) (sslcr_conv_desc.mask_x): no reduce pass
+  const float* sum_rows = nullptr;
+  int n_sum_rows = 0, nseg = 0, seg_stride = 0;
+  bool defer = false;                                         // the caller launches the reduce pass itself (the two-BatchNorm form)
+};
 
-// nseg consecutive slots (nullptr if the ring cannot serve them)
+// nseg consecutive sums slots of this backward (nullptr if the ring cannot serve them)
 double* take_sums_n(sslcr_ctx* c, int nseg) {
   if (!c->bn_ring.p || c->bn_ring_i + nseg > sslcr_ctx::kBnRing) return nullptr;
   double* p = (double*)c->bn_ring.p + (size_t)c->bn_ring_i * sslcr_ctx::kBnSlot;
   c->bn_ring_i += nseg;
   return p;
 }
+double* take_sums(sslcr_ctx* c) { return take_sums_n(c, 1); }      // the next slot
+double* take_sums_or_fixed(sslcr_ctx* c) {      // one slot, or the context's fixed pair of slots when the ring is used up
+  double* ring = take_sums(c);
+  return ring ? ring : c->bn_sums;
+}
 
-int bn_bwd_begin(sslcr_net* n, const BnL& bn, const BnSaved& sv, const void* dy, const void* x, const void* yact, int relu_from_x,
-                 void* dx, void* gout, size_t pixels, double count, hipStream_t st, double* sums, BnBwdArgs* out, const PoolSrc* pool = nullptr,
-                 int g_in_reduce = 0, const float* sum_rows = nullptr, int n_sum_rows = 0, bool sums_zeroed = false, int nseg = 1,
-                 int seg_stride = 0, bool defer = false) {
-  // nseg > 1 (sslcr_bn_bwd_desc.nseg): the tensors hold nseg passes one after the other, `pixels` is their total, sv is pass 0's
-  // (the others seg_stride floats apart), `sums` the first of nseg consecutive ring slots, sum_rows / n_sum_rows cover all passes
+// BatchNorm backward in three parts so that independent BatchNorms (a block's bn2 and its projection-shortcut BatchNorm) can
+// share ONE all-reduce of their sums: begin = the reduce pass into `sums` ([2][C] doubles), sync = the all-reduce, end = the apply pass
+int bn_bwd_begin(sslcr_net* n, const BnL& bn, const BnSaved& sv, const BnBwdReq& q, hipStream_t st, double* sums, BnBwdArgs* out) {
   sslcr_ctx* c = n->ctx;
   BnBwdArgs a;
   memset(&a, 0, sizeof(a));
-  a.dy = dy; a.x = x; a.yact = yact; a.scale = sv.scale; a.shift = sv.shift; a.mean = sv.mean; a.invstd = sv.invstd;
-  a.sums = sums; a.dx = dx; a.gout = gout; a.pixels = pixels; a.C = bn.C; a.relu_from_x = relu_from_x;
-  if (nseg > 1) { a.nseg = nseg; a.seg_stride = seg_stride; a.sums_stride = sslcr_ctx::kBnSlot; }
-  a.g_in_reduce = (g_in_reduce && yact && gout) ? 1 : 0;
-  a.yact_bits = ybits_of(n, yact);
+  a.dy = q.dy; a.x = q.x; a.yact = q.yact; a.scale = sv.scale; a.shift = sv.shift; a.mean = sv.mean; a.invstd = sv.invstd;
+  a.sums = sums; a.dx = q.dx; a.gout = q.gout; a.pixels = q.pixels; a.C = bn.C; a.relu_from_x = q.relu_from_x;
+  if (q.nseg > 1) { a.nseg = q.nseg; a.seg_stride = q.seg_stride; a.sums_stride = sslcr_ctx::kBnSlot; }
+  a.g_in_reduce = (q.g_in_reduce && q.yact && q.gout) ? 1 : 0;
+  a.yact_bits = ybits_of(n, q.yact);
   const bool synced = sharded(c) && c->bn_sync;
   if (n->rg[bn.pg] || n->rg[bn.pb]) {
     // dgamma/dbeta ride on the apply pass.  Synced BN: every rank holds the GLOBAL sums and the gradient all-reduce adds
@@ -1101,18 +1098,16 @@ int bn_bwd_begin(sslcr_net* n, const BnL& bn, const BnSaved& sv, const void* dy,
     a.pg_scale = synced ? 1.0f / c->world : 1.0f;
     if (!a.dgamma || !a.dbeta) { a.dgamma = nullptr; a.dbeta = nullptr; }
   }
-  if (pool) { a.pool_dy = pool->dy; a.pool_argmax = pool->argmax; a.pH = pool->H; a.pW = pool->W; a.pOH = pool->OH; a.pOW = pool->OW; a.pool_y = pool->y; }
-  a.count = synced ? count * c->world : count;
-  if (sum_rows) {
-    // the dgrad that produced dy already left partial rows of (sum g, sum g (x - mean)) (sslcr_conv_desc.mask_x): rows -> sums
+  if (const PoolSrc* s = q.pool) { a.pool_dy = s->dy; a.pool_argmax = s->argmax; a.pH = s->H; a.pW = s->W; a.pOH = s->OH; a.pOW = s->OW; a.pool_y = s->y; }
+  a.count = synced ? q.count * c->world : q.count;
+  if (q.sum_rows) {                                 // rows -> sums
     BnFinalizeArgs r;
     memset(&r, 0, sizeof(r));
-    r.partials = sum_rows; r.rows = n_sum_rows; r.C = bn.C; r.stage = c->bn_stage; r.sums_out = sums; r.tickets = c->bn_tickets;
-    if (nseg > 1) { r.nseg = nseg; r.seg_stride = sslcr_ctx::kBnSlot; }
+    r.partials = q.sum_rows; r.rows = q.n_sum_rows; r.C = bn.C; r.stage = c->bn_stage; r.sums_out = sums; r.tickets = c->bn_tickets;
+    if (q.nseg > 1) { r.nseg = q.nseg; r.seg_stride = sslcr_ctx::kBnSlot; }
     TRY(launch_bn_finalize(r, st));
-  } else if (!defer) {                              // (defer: the caller launches the reduce pass itself -- the two-BatchNorm form)
-    (void)sums_zeroed;                              // (the reduce pass overwrites its sums)
-    TRY(launch_bn_bwd_reduce(c->dtype, a, st));
+  } else if (!q.defer) {
+    TRY(launch_bn_bwd_reduce(c->dtype, a, st));     // (the reduce pass overwrites its sums: nothing to clear)
   }
   *out = a;
   return 0;
@@ -1124,9 +1119,7 @@ int bn_bwd_sync(sslcr_ctx* c, double* sums, size_t count, hipStream_t st) {
 }
 
 int bn_bwd_end(sslcr_ctx* c, const BnBwdArgs& a, hipStream_t st) {
-  if (c->prof.on) {
-    ProfRec r;
-    r.e0 = c->prof.get(); r.e1 = c->prof.get();
+  auto book = [&](ProfRec& r) {
     const bool pool = a.pool_dy != nullptr;
     if (pool) r.name = c->dtype == DT_BF16 ? "sslcr::bn_bwd_apply_pool_kernel<unsigned short>" : "sslcr::bn_bwd_apply_pool_kernel<float>";
     else r.name = c->dtype == DT_BF16 ? "sslcr::bn_bwd_apply_kernel<unsigned short>" : "sslcr::bn_bwd_apply_kernel<float>";
@@ -1135,33 +1128,18 @@ int bn_bwd_end(sslcr_ctx* c, const BnBwdArgs& a, hipStream_t st) {
     const double t = (double)a.pixels * a.C * c->esz();
     const double rd = (pool ? 0.25 * t + 0.25 * (double)a.pixels * a.C : t) + t + ((a.yact && !a.g_in_reduce) ? t : 0.0);
     r.bytes = rd + t + ((a.gout && !a.g_in_reduce) ? t : 0.0);
-    (void)hipEventRecord(r.e0, st);
-    hipError_t e = launch_bn_bwd_apply(c->dtype, a, st);
-    (void)hipEventRecord(r.e1, st);
-    c->prof.rec[2].push_back(r);
-    TRY(e);
-  } else {
-    TRY(launch_bn_bwd_apply(c->dtype, a, st));
-  }
-  return 0;
+  };
+  return check(profiled(c, 2, st, book, [&] { return launch_bn_bwd_apply(c->dtype, a, st); }), "launch_bn_bwd_apply");
 }
 
-int bn_backward(sslcr_net* n, const BnL& bn, const BnSaved& sv, const void* dy, const void* x, const void* yact, int relu_from_x,
-                void* dx, void* gout, size_t pixels, double count, hipStream_t st, const PoolSrc* pool = nullptr, int g_in_reduce = 0,
-                const float* sum_rows = nullptr, int n_sum_rows = 0, int nseg = 1, int seg_stride = 0) {
+int bn_backward(sslcr_net* n, const BnL& bn, const BnSaved& sv, const BnBwdReq& q, hipStream_t st) {
   sslcr_ctx* c = n->ctx;
+  const bool segs = q.nseg > 1;                  // the passes as segments: nseg consecutive ring slots (the caller checked there are)
+  double* sums = segs ? take_sums_n(c, q.nseg) : q.sum_rows ? c->bn_sums : take_sums_or_fixed(c);
+  if (!sums) return fail("bn_backward: no ring slots for the segments");
   BnBwdArgs a;
-  if (nseg > 1) {                                // the passes as segments: nseg consecutive ring slots (the caller checked there are)
-    double* sums = take_sums_n(c, nseg);
-    if (!sums) return fail("bn_backward: no ring slots for the segments");
-    TRYI(bn_bwd_begin(n, bn, sv, dy, x, yact, relu_from_x, dx, gout, pixels, count, st, sums, &a, pool, g_in_reduce, sum_rows, n_sum_rows, true,
-                      nseg, seg_stride));
-    return bn_bwd_end(c, a, st);
-  }
-  double* ring = sum_rows ? nullptr : take_sums(c);
-  double* sums = ring ? ring : c->bn_sums;
-  TRYI(bn_bwd_begin(n, bn, sv, dy, x, yact, relu_from_x, dx, gout, pixels, count, st, sums, &a, pool, g_in_reduce, sum_rows, n_sum_rows, ring != nullptr));
-  TRYI(bn_bwd_sync(c, sums, 2 * (size_t)bn.C, st));
+  TRYI(bn_bwd_begin(n, bn, sv, q, st, sums, &a));
+  if (!segs) TRYI(bn_bwd_sync(c, sums, 2 * (size_t)bn.C, st));      // (segments are not run with synced BatchNorm)
   return bn_bwd_end(c, a, st);
 }
 
@@ -1184,7 +1162,7 @@ int wg_join(sslcr_ctx* c, hipStream_t waiter) {
 // seg_images > 0: the N images are N / seg_images segments (TripletNet branches) whose producer BatchNorms sit seg_stride floats apart
 // kind: which scratch buffer holds dy (0 conv2 / dRaw2, 1 conv1 / dRaw1, 2 projection / dRawD); < 0 = always on the compute stream
 int wgrad_call(sslcr_net* n, const ConvL& L, const void* x, const void* dy, const BnSaved* pro, int N, int H, int W, int OH, int OW, hipStream_t st,
-               int seg_images = 0, int seg_stride = 0, int kind = -1) {
+               int kind, int seg_images = 0, int seg_stride = 0) {
   if (!n->rg[L.pidx]) return 0;
   sslcr_ctx* c = n->ctx;
   WgradArgs a;
@@ -1232,319 +1210,339 @@ int lowest_trainable(const sslcr_net* n) {
   return 60;
 }
 
-// Backward of the backbone for all passes, walked LAYER-major: per block the BatchNorm backward / dgrad chain runs pass by
-// pass (the reference's BatchNorm statistics are per branch), the weight gradients of conv1 and of the projection run ONCE
-// over the branches' contiguous (x, dy) tensors (alloc_passes; scratch buffers of one kind are contiguous across passes too).
-int backbone_backward(sslcr_net* n, int npass, hipStream_t st) {
-  sslcr_ctx* c = n->ctx;
-  const int dt = c->dtype;
-  const size_t es = c->esz();
-  PassState* P = n->pass;
-  const int N = P[0].N;
-  const Dims d = make_dims(P[0].H, P[0].W);
-  const int low = lowest_trainable(n);
-  if (low >= 60) return 0;
-  // transient buffers, one layer1-sized unit each, laid out [kind][pass]: dOut, G, dRaw2, dAct1, dRaw1, dXin, dRawD; behind
-  // them one stem-sized region for dRaw0 (used pass by pass)
-  const size_t unit = (((size_t)N * d.ph * d.pw * 64 * es) + 255) & ~(size_t)255;
-  const size_t stem_sz = (((size_t)N * d.oh0 * d.ow0 * 64 * es) + 255) & ~(size_t)255;
-  TRYI(c->scratch.ensure(7 * npass * unit + stem_sz));
-  char* S = (char*)c->scratch.p;
-  // pass p of a kind sits p * (tensor bytes of the current layer) behind pass 0: contiguous for the batched weight gradients
-  auto buf = [&](int kind, int p, size_t bytes) { return S + (size_t)kind * npass * unit + (size_t)p * bytes; };
-  int kOut = 0, kXin = 5;
-  const int kG = 1, kRaw2 = 2, kAct1 = 3, kRaw1 = 4, kRawD = 6;
-  char* dRaw0 = S + (size_t)7 * npass * unit;
-  // debug tap (pass 0 only): slot 0 G, 1 dRaw2, 2 dAct1, 3 dRaw1, 4 dRawD, 5 dXin
-  auto tap = [&](int blk, int slot, const void* src, int n_, int h_, int w_, int c_) -> int {
-    if (!n->tap) return 0;
-    const size_t bytes = (size_t)n_ * h_ * w_ * c_ * es;
-    TRYI(n->tapbuf[blk][slot].ensure(bytes));
-    TRY(hipMemcpyAsync(n->tapbuf[blk][slot].p, src, bytes, hipMemcpyDeviceToDevice, st));
-    int* d4 = n->tapdims[blk][slot];
-    d4[0] = n_; d4[1] = h_; d4[2] = w_; d4[3] = c_;
-    return 0;
-  };
+// ---------------------------------------------------------------- backbone backward, all passes
+// dgrad of a 3x3 stride-1 conv: a plain conv of dy [., K] with the flipped pack [C][R][S][K]
+ConvArgs dgrad3x3_s1_args(const ConvL& L, const void* dy, void* dx, int N, int oh, int ow) {
+  ConvArgs a = conv_args(L, dy, L.w_dg, dx, N, oh, ow);
+  a.C = L.cout; a.K = L.cin; a.transposed = 0; a.PH = oh; a.PW = ow; a.OH = oh; a.OW = ow;
+  return a;
+}
+// ... with the BatchNorm-backward front end: the dgrad applies the ReLU mask of the BatchNorm `s` over the saved `raw` to what it
+// writes and leaves that BatchNorm's two backward sums in its stats rows
+ConvArgs with_bn1_mask(ConvArgs a, const void* raw, const BnSaved& s) {
+  a.mask_x = raw; a.mask_scale = s.scale; a.mask_shift = s.shift; a.mask_mean = s.mean;
+  return a;
+}
+// stride-2 3x3 dgrad: the taps an input-pixel parity class (ph % 2, pw % 2) sees -- those with (p + pad - r) even -- as bits r * 3 + s
+unsigned parity_tap_mask(int ph, int pw) {
+  unsigned m = 0;
+  for (int r = 0; r < 3; ++r)
+    for (int s = 0; s < 3; ++s)
+      if (((ph + 1 - r) & 1) == 0 && ((pw + 1 - s) & 1) == 0) m |= 1u << (r * 3 + s);
+  return m;
+}
 
-  size_t hi_pending = n->goff[60];
-  int bucket = 1;
-  for (int p = 0; p < npass; ++p)
-    TRY(launch_avgpool_bwd(dt, n->dE[p], buf(kOut, p, (size_t)N * d.lh[7] * d.lw[7] * 512 * es), N, d.lh[7] * d.lw[7], 512, st));
-  for (int i = 7; i >= 0; --i) {
-    BlockL& B = n->blocks[i];
-    const int oh = d.lh[i], ow = d.lw[i];
-    const int xh = i == 0 ? d.ph : d.lh[i - 1], xw = i == 0 ? d.pw : d.lw[i - 1];
-    const size_t opix = (size_t)N * oh * ow;
-    const bool need_dx = low < B.pstart;          // something upstream of this block is trainable
-    const size_t so = opix * B.c2.cout * es, si = (size_t)N * xh * xw * B.c1.cin * es;     // bytes of this block's output / input per pass
+// One backward, walked LAYER-major: per block the BatchNorm backward / dgrad chain runs pass by pass (the reference's BatchNorm
+// statistics are per branch) or, where a kernel takes the branches as segments, once; the weight gradients of conv1 and of the
+// projection run ONCE over the branches' contiguous (x, dy) tensors (alloc_passes; scratch buffers of one kind are contiguous
+// across passes too).  Each stage is one part of a block's backward; block() fixes their order.
+// Transient buffers: one layer1-sized unit each, laid out [kind][pass], dOut and dXin being kinds 0 and 5 in turns (kOut, kXin);
+// behind them one stem-sized region for dRaw0 (used pass by pass)
+enum { kG = 1, kRaw2 = 2, kAct1 = 3, kRaw1 = 4, kRawD = 6, kKinds = 7 };
+struct Backward {
+  sslcr_net* n; sslcr_ctx* c; hipStream_t st;
+  int dt, npass, N; size_t es; PassState* P; Dims d;
+  int bn_stride;            // floats from one BatchNorm's saved statistics of pass p to those of pass p + 1 (the same for every BatchNorm)
+  char* S; size_t unit;     // scratch base, bytes of one unit
+  int kOut = 0, kXin = 5;
+  // the current block (enter): geometry, and which stages take the passes as one launch
+  int i; const BlockL* B;
+  int oh, ow, xh, xw;       // output / input spatial dims
+  size_t opix, so, si;      // per pass: output pixels, bytes of the block's output / input
+  bool c2_batched, seg_dg, seg_bn;
+
+  // pass p of a kind sits p * (tensor bytes of the current layer) behind pass 0: contiguous for the batched weight gradients
+  char* buf(int kind, int p, size_t bytes) const { return S + (size_t)kind * npass * unit + (size_t)p * bytes; }
+  char* dRaw0() const { return S + (size_t)kKinds * npass * unit; }
+  // debug tap (pass 0 only): slot 0 G, 1 dRaw2, 2 dAct1, 3 dRaw1, 4 dRawD, 5 dXin
+  int tap(int slot, const void* src, int h_, int w_, int c_) {
+    if (!n->tap) return 0;
+    const size_t bytes = (size_t)N * h_ * w_ * c_ * es;
+    TRYI(n->tapbuf[i][slot].ensure(bytes));
+    TRY(hipMemcpyAsync(n->tapbuf[i][slot].p, src, bytes, hipMemcpyDeviceToDevice, st));
+    int* d4 = n->tapdims[i][slot];
+    d4[0] = N; d4[1] = h_; d4[2] = w_; d4[3] = c_;
+    return 0;
+  }
+
+  // conv2's masked dgrad over all passes as segments: segment s masks with its own bn1
+  ConvArgs conv2_dgrad_segments_args(const void* dy, void* dx) const {
+    ConvArgs m = with_bn1_mask(dgrad3x3_s1_args(B->c2, dy, dx, N * npass, oh, ow), P[0].blk[i].raw1, P[0].bn[B->b1.bidx]);
+    m.seg_images = N; m.seg_stride = bn_stride;
+    return m;
+  }
+
+  void enter(int blk) {
+    i = blk; B = &n->blocks[i];
+    oh = d.lh[i]; ow = d.lw[i];
+    xh = i == 0 ? d.ph : d.lh[i - 1]; xw = i == 0 ? d.pw : d.lw[i - 1];
+    opix = (size_t)N * oh * ow;
+    so = opix * B->c2.cout * es; si = (size_t)N * xh * xw * B->c1.cin * es;
     // conv2's weight gradient applies bn1 + ReLU of its pass to the input on the fly: the halo kernel takes the passes as
     // segments with their own (scale, shift); other shapes go pass by pass
-    bool c2_batched = false;
+    c2_batched = false;
     if (npass > 1) {
       WgradArgs q;
       memset(&q, 0, sizeof(q));
-      q.N = N * npass; q.H = oh; q.W = ow; q.C = B.c2.cin; q.K = B.c2.cout; q.R = 3; q.S = 3; q.stride = 1; q.pad = 1; q.OH = oh; q.OW = ow;
+      q.N = N * npass; q.H = oh; q.W = ow; q.C = B->c2.cin; q.K = B->c2.cout; q.R = 3; q.S = 3; q.stride = 1; q.pad = 1; q.OH = oh; q.OW = ow;
       c2_batched = wgrad_halo_tw(q) != 0 && (wgrad_halo_tw(q) == 16 || N % 2 == 0);
     }
     // ... and conv2's dgrad with the BatchNorm-backward front end takes them as segments where the 16x16-tile kernel serves it
-    ConvArgs seg_m;
-    bool seg_dg = false;
+    seg_dg = false;
     if (npass > 1 && segments_on() && !c->prof.on) {
-      seg_m = conv_args(B.c2, nullptr, B.c2.w_dg, nullptr, N * npass, oh, ow);
-      seg_m.C = B.c2.cout; seg_m.K = B.c2.cin; seg_m.transposed = 0; seg_m.PH = oh; seg_m.PW = ow; seg_m.OH = oh; seg_m.OW = ow;
-      const BnSaved& s1 = P[0].bn[B.b1.bidx];
-      seg_m.mask_x = P[0].blk[i].raw1; seg_m.mask_scale = s1.scale; seg_m.mask_shift = s1.shift; seg_m.mask_mean = s1.mean;
-      seg_m.seg_images = N; seg_m.seg_stride = (int)(P[1].bn[B.b1.bidx].scale - s1.scale);
-      seg_dg = conv_h16_ok(dt, seg_m) && conv_segments_ok(dt, seg_m) && conv_partials_rows(seg_m) % npass == 0;
+      const ConvArgs m = conv2_dgrad_segments_args(nullptr, nullptr);
+      seg_dg = conv_h16_ok(dt, m) && conv_segments_ok(dt, m) && conv_partials_rows(m) % npass == 0;
     }
     // the elementwise BatchNorm-backward passes of the branches as segments of one launch (sslcr_bn_bwd_desc.nseg): the passes'
-    // saved tensors and scratch tensors are contiguous, their saved statistics seg_stride floats apart, their sums in
+    // saved tensors and scratch tensors are contiguous, their saved statistics bn_stride floats apart, their sums in
     // consecutive ring slots.  Not with synced BatchNorm (one all-reduce per pass) and not under the profiler.
-    const bool seg_bn = npass > 1 && segments_on() && !c->prof.on && !(sharded(c) && c->bn_sync) && c->bn_ring.p &&
-                        c->bn_ring_i + 2 * npass <= sslcr_ctx::kBnRing;
-    const int bn_stride = npass > 1 ? (int)(P[1].bn[0].scale - P[0].bn[0].scale) : 0;
-    if (seg_bn) {
-      char *dOut = buf(kOut, 0, so), *G = buf(kG, 0, so), *dRaw2 = buf(kRaw2, 0, so), *dRawD = buf(kRawD, 0, so);
-      TRYI(wg_wait(c, 0, st));
-      if (B.has_ds) TRYI(wg_wait(c, 2, st));
-      const size_t apix = opix * npass;
-      if (B.has_ds) {
-        BnBwdArgs a2, ad;
-        double* sums_2 = take_sums_n(c, npass);
-        if (!sums_2) return fail("backbone_backward: ring slots");
-        TRYI(bn_bwd_begin(n, B.b2, P[0].bn[B.b2.bidx], dOut, P[0].blk[i].raw2, P[0].blk[i].y, 0, dRaw2, G, apix, (double)opix, st, sums_2, &a2, nullptr, 1,
-                          nullptr, 0, true, npass, bn_stride));
-        TRYI(bn_bwd_begin(n, B.bd, P[0].bn[B.bd.bidx], G, P[0].blk[i].rawd, nullptr, 0, dRawD, nullptr, apix, (double)opix, st, sums_2 + 2 * B.b2.C, &ad,
-                          nullptr, 0, nullptr, 0, true, npass, bn_stride));
-        TRYI(bn_bwd_end(c, a2, st));
-        TRYI(bn_bwd_end(c, ad, st));
-      } else {
-        TRYI(bn_backward(n, B.b2, P[0].bn[B.b2.bidx], dOut, P[0].blk[i].raw2, P[0].blk[i].y, 0, dRaw2, G, apix, (double)opix, st, nullptr, 1, nullptr, 0,
-                         npass, bn_stride));
-      }
-      TRYI(tap(i, 0, G, N, oh, ow, B.c2.cout));
-      TRYI(tap(i, 1, dRaw2, N, oh, ow, B.c2.cout));
-      if (B.has_ds) TRYI(tap(i, 4, dRawD, N, oh, ow, B.ds.cout));
+    seg_bn = npass > 1 && segments_on() && !c->prof.on && !(sharded(c) && c->bn_sync) && c->bn_ring.p &&
+             c->bn_ring_i + 2 * npass <= sslcr_ctx::kBnRing;
+  }
+
+  // ---- bn2 stage: leaves G = dOut * (y > 0), dRaw2 and (projection shortcut) dRawD; taps 0, 1 and 4.
+  // bn2's REDUCE pass forms G from the block output's ReLU mask and writes it; its apply pass, the projection shortcut's BatchNorm
+  // and the identity path all read G, not (dOut, y) again.  nseg == 1: pass p; nseg == npass: all passes as segments of one launch
+  int bn2(int p, int nseg) {
+    const PassState& ps = P[p];
+    char *G = buf(kG, p, so), *dRaw2 = buf(kRaw2, p, so), *dRawD = buf(kRawD, p, so);
+    // (the previous block's side-stream weight gradients may still be reading dRaw2 / dRawD: order these writers behind them)
+    TRYI(wg_wait(c, 0, st));
+    if (B->has_ds) TRYI(wg_wait(c, 2, st));
+    BnBwdReq q2, qd;
+    q2.dy = buf(kOut, p, so); q2.x = ps.blk[i].raw2; q2.yact = ps.blk[i].y; q2.dx = dRaw2; q2.gout = G; q2.g_in_reduce = 1;
+    qd.dy = G; qd.x = ps.blk[i].rawd; qd.dx = dRawD;
+    q2.pixels = qd.pixels = opix * nseg; q2.count = qd.count = (double)opix;
+    if (nseg > 1) { q2.nseg = qd.nseg = nseg; q2.seg_stride = qd.seg_stride = bn_stride; }
+    if (!B->has_ds) TRYI(bn_backward(n, B->b2, ps.bn[B->b2.bidx], q2, st));
+    else TRYI(nseg > 1 ? bn2_and_shortcut_segments(q2, qd) : bn2_and_shortcut(ps, q2, qd));
+    if (p != 0) return 0;
+    TRYI(tap(0, G, oh, ow, B->c2.cout));
+    TRYI(tap(1, dRaw2, oh, ow, B->c2.cout));
+    return B->has_ds ? tap(4, dRawD, oh, ow, B->ds.cout) : 0;
+  }
+  int bn2_and_shortcut_segments(const BnBwdReq& q2, const BnBwdReq& qd) {
+    BnBwdArgs a2, ad;
+    double* sums_2 = take_sums_n(c, npass);
+    if (!sums_2) return fail("backbone_backward: ring slots");
+    TRYI(bn_bwd_begin(n, B->b2, P[0].bn[B->b2.bidx], q2, st, sums_2, &a2));
+    TRYI(bn_bwd_begin(n, B->bd, P[0].bn[B->bd.bidx], qd, st, sums_2 + 2 * B->b2.C, &ad));
+    TRYI(bn_bwd_end(c, a2, st));
+    return bn_bwd_end(c, ad, st);
+  }
+  // one pass: the two reduce passes run back to back, so that sharded runs exchange both BatchNorms' sums ([2][C] each, adjacent
+  // in one slot) in ONE all-reduce before the two apply passes
+  int bn2_and_shortcut(const PassState& ps, BnBwdReq q2, BnBwdReq qd) {
+    BnBwdArgs a2, ad;
+    double* sums_2 = take_sums_or_fixed(c);
+    q2.defer = qd.defer = true;
+    TRYI(bn_bwd_begin(n, B->b2, ps.bn[B->b2.bidx], q2, st, sums_2, &a2));
+    TRYI(bn_bwd_begin(n, B->bd, ps.bn[B->bd.bidx], qd, st, sums_2 + 2 * B->b2.C, &ad));
+    // both BatchNorms receive the same g = dOut * (y > 0): one reduce pass forms it, writes it once and leaves both pairs of
+    // sums, one apply pass reads it once for both (bn_bwd_reduce_pair_kernel); where that form does not apply, two passes each
+    const bool pair = bn_bwd_pair_ok(a2, ad);
+    // (g is read by nobody else in a downsampling block, so with the mask as bits it need not be written at all -- measured
+    //  SLOWER, 15.81 -> 15.90 ms same box: forming g from (dOut, bits) a second time costs the apply pass more than reading it.
+    //  SSLCR_BN_PAIR_G=0 selects that form; the debug tap always keeps g)
+    static const bool g_free = [] { const char* e = getenv("SSLCR_BN_PAIR_G"); return e && atoi(e) == 0; }();
+    const int keep_g = (n->tap || !a2.yact_bits || !g_free) ? 1 : 0;
+    if (pair) {
+      TRY(launch_bn_bwd_reduce_pair(dt, a2, ad, keep_g, st));
+    } else {
+      TRY(launch_bn_bwd_reduce(dt, a2, st));
+      TRY(launch_bn_bwd_reduce(dt, ad, st));
     }
-    for (int p = 0; p < npass; ++p) {
-      PassState& ps = P[p];
-      char *dOut = buf(kOut, p, so), *G = buf(kG, p, so), *dRaw2 = buf(kRaw2, p, so), *dAct1 = buf(kAct1, p, so), *dRaw1 = buf(kRaw1, p, so),
-           *dRawD = buf(kRawD, p, so);
-      // bn2 (+ relu mask from the block output): its REDUCE pass leaves G = dOut * (y > 0) in scratch; the apply pass, the
-      // projection shortcut's BatchNorm and the identity path all read G instead of (dOut, y) again
-      // (the previous block's side-stream weight gradients may still be reading dRaw2 / dRawD: order these writers behind them)
-      if (!seg_bn) {
-      TRYI(wg_wait(c, 0, st));
-      if (B.has_ds) TRYI(wg_wait(c, 2, st));
-      // ... and with a projection shortcut the two reduce passes run back to back, so that sharded runs exchange both
-      // BatchNorms' sums ([2][C] each, adjacent in bn_sums) in ONE all-reduce before the two apply passes
-      if (B.has_ds) {
-        BnBwdArgs a2, ad;
-        double* ring = take_sums(c);
-        double* sums_2 = ring ? ring : c->bn_sums;
-        double* sums_d = sums_2 + 2 * B.b2.C;
-        // both BatchNorms receive the same g = dOut * (y > 0): one reduce pass forms it, writes it once and leaves both pairs of
-        // sums, one apply pass reads it once for both (bn_bwd_reduce_pair_kernel); where that form does not apply, two passes each
-        TRYI(bn_bwd_begin(n, B.b2, ps.bn[B.b2.bidx], dOut, ps.blk[i].raw2, ps.blk[i].y, 0, dRaw2, G, opix, (double)opix, st, sums_2, &a2, nullptr, 1,
-                          nullptr, 0, ring != nullptr, 1, 0, true));
-        TRYI(bn_bwd_begin(n, B.bd, ps.bn[B.bd.bidx], G, ps.blk[i].rawd, nullptr, 0, dRawD, nullptr, opix, (double)opix, st, sums_d, &ad, nullptr, 0,
-                          nullptr, 0, ring != nullptr, 1, 0, true));
-        const bool pair = bn_bwd_pair_ok(a2, ad);
-        // (g is read by nobody else in a downsampling block, so with the mask as bits it need not be written at all -- measured
-        //  SLOWER, 15.81 -> 15.90 ms same box: forming g from (dOut, bits) a second time costs the apply pass more than reading it.
-        //  SSLCR_BN_PAIR_G=0 selects that form; the debug tap always keeps g)
-        static const bool g_free = [] { const char* e = getenv("SSLCR_BN_PAIR_G"); return e && atoi(e) == 0; }();
-        const int keep_g = (n->tap || !a2.yact_bits || !g_free) ? 1 : 0;
-        if (pair) {
-          TRY(launch_bn_bwd_reduce_pair(dt, a2, ad, keep_g, st));
-        } else {
-          TRY(launch_bn_bwd_reduce(dt, a2, st));
-          TRY(launch_bn_bwd_reduce(dt, ad, st));
-        }
-        TRYI(bn_bwd_sync(c, sums_2, 4 * (size_t)B.b2.C, st));
-        if (pair) {
-          if (c->prof.on) {
-            ProfRec r;
-            r.e0 = c->prof.get(); r.e1 = c->prof.get();
-            r.name = dt == DT_BF16 ? "sslcr::bn_bwd_apply_pair_kernel<unsigned short>" : "sslcr::bn_bwd_apply_pair_kernel<float>";
-            r.flops = 0.0;
-            r.bytes = (keep_g ? 5.0 : 5.0625) * (double)opix * B.b2.C * c->esz();   // reads g (or dy + mask bits), x of both BatchNorms; writes both dx
-            (void)hipEventRecord(r.e0, st);
-            hipError_t e = launch_bn_bwd_apply_pair(dt, a2, ad, keep_g, st);
-            (void)hipEventRecord(r.e1, st);
-            c->prof.rec[2].push_back(r);
-            TRY(e);
-          } else {
-            TRY(launch_bn_bwd_apply_pair(dt, a2, ad, keep_g, st));
-          }
-        } else {
-          TRYI(bn_bwd_end(c, a2, st));
-          TRYI(bn_bwd_end(c, ad, st));
-        }
-      } else {
-        TRYI(bn_backward(n, B.b2, ps.bn[B.b2.bidx], dOut, ps.blk[i].raw2, ps.blk[i].y, 0, dRaw2, G, opix, (double)opix, st, nullptr, 1));
-      }
-      if (p == 0) {
-        TRYI(tap(i, 0, G, N, oh, ow, B.c2.cout));
-        TRYI(tap(i, 1, dRaw2, N, oh, ow, B.c2.cout));
-        if (B.has_ds) TRYI(tap(i, 4, dRawD, N, oh, ow, B.ds.cout));
-      }
-      }
-      if (!c2_batched) TRYI(wgrad_call(n, B.c2, ps.blk[i].raw1, dRaw2, &ps.bn[B.b1.bidx], N, oh, ow, oh, ow, st, 0, 0, 0));
-      if (seg_dg) continue;                      // conv2's dgrad runs once over the passes, below
-      float* b1_rows = nullptr;
-      int b1_nrows = 0;
-      {
-        ConvArgs a = conv_args(B.c2, dRaw2, B.c2.w_dg, dAct1, N, oh, ow);      // dgrad 3x3/1: gather over dRaw2 [.,K] with [C][R][S][K]
-        a.C = B.c2.cout; a.K = B.c2.cin; a.transposed = 0; a.PH = oh; a.PW = ow; a.OH = oh; a.OW = ow;   // flipped pack
-        // where the 16x16-tile kernel serves this dgrad it also applies bn1's ReLU mask and leaves bn1's two backward sums
-        // in its stats rows: bn1's reduce pass over (dAct1, raw1) is not run
-        ConvArgs m = a;
-        const BnSaved& s1 = ps.bn[B.b1.bidx];
-        m.mask_x = ps.blk[i].raw1; m.mask_scale = s1.scale; m.mask_shift = s1.shift; m.mask_mean = s1.mean;
-        if (conv_h16_ok(dt, m)) {
-          TRYI(ensure_partials(c, m, &b1_rows, &b1_nrows));
-          m.stats = b1_rows;
-          a = m;
-        }
-        TRY(prof_conv(c, dt,a, st));
-        if (p == 0) {
-          TRYI(tap(i, 2, dAct1, N, oh, ow, B.c2.cin));
-          n->tap_flags[i] = b1_rows ? 1 : 0;
-        }
-      }
-      TRYI(wg_wait(c, 1, st));
-      TRYI(bn_backward(n, B.b1, ps.bn[B.b1.bidx], dAct1, ps.blk[i].raw1, nullptr, b1_rows ? 0 : 1, dRaw1, nullptr, opix, (double)opix, st,
-                       nullptr, 0, b1_rows, b1_nrows));
-      if (p == 0) TRYI(tap(i, 3, dRaw1, N, oh, ow, B.c1.cout));
+    TRYI(bn_bwd_sync(c, sums_2, 4 * (size_t)B->b2.C, st));
+    if (!pair) {
+      TRYI(bn_bwd_end(c, a2, st));
+      return bn_bwd_end(c, ad, st);
     }
-    if (seg_dg) {
-      // conv2's dgrad of the three branches as segments of one launch (their scratch tensors are contiguous): segment s masks
-      // with its own bn1 and leaves its own rows of bn1's backward sums
-      float* rows = nullptr;
-      int nrows = 0;
-      seg_m.x = buf(kRaw2, 0, so); seg_m.y = buf(kAct1, 0, so);
-      TRYI(ensure_partials(c, seg_m, &rows, &nrows));
-      seg_m.stats = rows;
-      TRY(prof_conv(c, dt, seg_m, st));
-      TRYI(tap(i, 2, buf(kAct1, 0, so), N, oh, ow, B.c2.cin));
-      n->tap_flags[i] = 1;
-      const int per = nrows / npass;
-      if (seg_bn) {
-        TRYI(wg_wait(c, 1, st));
-        TRYI(bn_backward(n, B.b1, P[0].bn[B.b1.bidx], buf(kAct1, 0, so), P[0].blk[i].raw1, nullptr, 0, buf(kRaw1, 0, so), nullptr, opix * npass,
-                         (double)opix, st, nullptr, 0, rows, nrows, npass, bn_stride));
-        TRYI(tap(i, 3, buf(kRaw1, 0, so), N, oh, ow, B.c1.cout));
-      }
-      for (int p = 0; p < npass && !seg_bn; ++p) {
-        PassState& ps = P[p];
-        TRYI(wg_wait(c, 1, st));
-        TRYI(bn_backward(n, B.b1, ps.bn[B.b1.bidx], buf(kAct1, p, so), ps.blk[i].raw1, nullptr, 0, buf(kRaw1, p, so), nullptr, opix, (double)opix, st,
-                         nullptr, 0, rows + (size_t)p * per * 2 * B.b1.C, per));
-        if (p == 0) TRYI(tap(i, 3, buf(kRaw1, 0, so), N, oh, ow, B.c1.cout));
-      }
+    auto book = [&](ProfRec& r) {
+      r.name = dt == DT_BF16 ? "sslcr::bn_bwd_apply_pair_kernel<unsigned short>" : "sslcr::bn_bwd_apply_pair_kernel<float>";
+      r.flops = 0.0;
+      r.bytes = (keep_g ? 5.0 : 5.0625) * (double)opix * B->b2.C * c->esz();   // reads g (or dy + mask bits), x of both BatchNorms; writes both dx
+    };
+    return check(profiled(c, 2, st, book, [&] { return launch_bn_bwd_apply_pair(dt, a2, ad, keep_g, st); }), "launch_bn_bwd_apply_pair");
+  }
+
+  // ---- conv2 dgrad + bn1 stage: leaves dAct1 and dRaw1, tap_flags; taps 2 and 3.
+  // bn1 of pass p (nseg == npass: of all passes as segments).  rows: the dgrad that wrote dAct1 applied bn1's ReLU mask and left
+  // bn1's sums in its stats rows, so no reduce pass over (dAct1, raw1) is run; nullptr: bn1 masks and reduces itself
+  int bn1(int p, int nseg, const float* rows, int nrows) {
+    TRYI(wg_wait(c, 1, st));
+    BnBwdReq q;
+    q.dy = buf(kAct1, p, so); q.x = P[p].blk[i].raw1; q.relu_from_x = rows ? 0 : 1; q.dx = buf(kRaw1, p, so);
+    q.pixels = opix * nseg; q.count = (double)opix; q.sum_rows = rows; q.n_sum_rows = nrows;
+    if (nseg > 1) { q.nseg = nseg; q.seg_stride = bn_stride; }
+    TRYI(bn_backward(n, B->b1, P[p].bn[B->b1.bidx], q, st));
+    return p == 0 ? tap(3, q.dx, oh, ow, B->c1.cout) : 0;
+  }
+  // pass p: where the 16x16-tile kernel serves this dgrad it takes the mask front end
+  int conv2_dgrad_bn1(int p) {
+    ConvArgs a = dgrad3x3_s1_args(B->c2, buf(kRaw2, p, so), buf(kAct1, p, so), N, oh, ow);
+    const ConvArgs m = with_bn1_mask(a, P[p].blk[i].raw1, P[p].bn[B->b1.bidx]);
+    float* rows = nullptr; int nrows = 0;
+    if (conv_h16_ok(dt, m)) {
+      TRYI(ensure_partials(c, m, &rows, &nrows));
+      a = m;
+      a.stats = rows;
     }
-    // weight gradients: one launch over the npass * N images (x and dy contiguous across passes)
+    TRY(prof_conv(c, dt, a, st));
+    if (p == 0) {
+      TRYI(tap(2, a.y, oh, ow, B->c2.cin));
+      n->tap_flags[i] = rows ? 1 : 0;
+    }
+    return bn1(p, 1, rows, nrows);
+  }
+  // all passes as segments of one launch (their scratch tensors are contiguous): segment s leaves its own rows of bn1's backward
+  // sums; bn1 then as segments too, or pass by pass on its share of the rows
+  int conv2_dgrad_bn1_segments() {
+    ConvArgs m = conv2_dgrad_segments_args(buf(kRaw2, 0, so), buf(kAct1, 0, so));
+    float* rows = nullptr; int nrows = 0;
+    TRYI(ensure_partials(c, m, &rows, &nrows));
+    m.stats = rows;
+    TRY(prof_conv(c, dt, m, st));
+    TRYI(tap(2, m.y, oh, ow, B->c2.cin));
+    n->tap_flags[i] = 1;
+    if (seg_bn) return bn1(0, npass, rows, nrows);
+    const int per = nrows / npass;
+    for (int p = 0; p < npass; ++p) TRYI(bn1(p, 1, rows + (size_t)p * per * 2 * B->b1.C, per));
+    return 0;
+  }
+
+  // ---- weight-gradient stage (the argument of wgrad_call behind the stream: which scratch buffer the launch reads, see
+  // sslcr_ctx::wg_stream): conv2 of pass p where the batched form does not take the shape; then one launch each over the npass * N
+  // images (x and dy contiguous across passes) for conv2 where it is batched, conv1 and the projection
+  int conv2_wgrad(int p) { return wgrad_call(n, B->c2, P[p].blk[i].raw1, buf(kRaw2, p, so), &P[p].bn[B->b1.bidx], N, oh, ow, oh, ow, st, 0); }
+  int wgrads() {
     if (c2_batched)
-      TRYI(wgrad_call(n, B.c2, P[0].blk[i].raw1, buf(kRaw2, 0, so), &P[0].bn[B.b1.bidx], N * npass, oh, ow, oh, ow, st, N,
-                      (int)(P[1].bn[B.b1.bidx].scale - P[0].bn[B.b1.bidx].scale), 0));
-    {
-      const char* X0 = i == 0 ? P[0].pooled : P[0].blk[i - 1].y;
-      TRYI(wgrad_call(n, B.c1, X0, buf(kRaw1, 0, so), nullptr, N * npass, xh, xw, oh, ow, st, 0, 0, 1));
-      if (B.has_ds) TRYI(wgrad_call(n, B.ds, X0, buf(kRawD, 0, so), nullptr, N * npass, xh, xw, oh, ow, st, 0, 0, 2));
-    }
-    if (need_dx) {
-      {
-        // conv1's dgrad (and the projection's) has no BatchNorm in it and is independent per image: one launch over all passes
-        const int NB = N * npass;
-        char *G = buf(kG, 0, so), *dRaw1 = buf(kRaw1, 0, so), *dXin = buf(kXin, 0, si), *dRawD = buf(kRawD, 0, so);
-        ConvArgs a = conv_args(B.c1, dRaw1, B.c1.w_dg, dXin, NB, oh, ow);
-        a.C = B.c1.cout; a.K = B.c1.cin; a.transposed = (B.c1.stride == 1) ? 0 : 1; a.PH = xh; a.PW = xw; a.OH = xh; a.OW = xw;
-        if (!B.has_ds) a.residual = G;
-        if (B.c1.stride == 1) {
-          TRY(prof_conv(c, dt,a, st));
-        } else {
-          // stride-2 dgrad: each input-pixel parity class (ph%2, pw%2) only sees the taps with (p + pad - r) even --
-          // 1 + 2 + 2 + 4 = 9 taps instead of 36 tap visits with three quarters zero-gathered; one launch with the class on
-          // grid z where the DMA-gather kernel serves the shape, else four launches
-          ConvArgs q4 = a;
-          q4.pix_mul = 2; q4.PH = xh / 2; q4.PW = xw / 2; q4.par4 = 1;
-          const bool one = xh % 2 == 0 && xw % 2 == 0 && conv_dma_bp(dt, q4) != 0 && conv_dma_bp(DT_BF16, q4) == conv_dma_bp(dt, q4) &&
-                           conv_halo_tw(dt, q4) == 0;
-          if (one) TRY(prof_conv(c, dt, q4, st));
-          for (int par = 0; par < (one ? 0 : 4); ++par) {
-            ConvArgs q = a;
-            const int ph_ = par >> 1, pw_ = par & 1;
-            q.pix_mul = 2; q.pix_off_h = ph_; q.pix_off_w = pw_;
-            q.PH = (xh - ph_ + 1) / 2; q.PW = (xw - pw_ + 1) / 2;
-            if (q.PH <= 0 || q.PW <= 0) continue;
-            unsigned m = 0;
-            for (int r = 0; r < 3; ++r)
-              for (int s2 = 0; s2 < 3; ++s2)
-                if (((ph_ + 1 - r) & 1) == 0 && ((pw_ + 1 - s2) & 1) == 0) m |= 1u << (r * 3 + s2);
-            q.tap_mask = m;
-            TRY(prof_conv(c, dt,q, st));
-          }
-        }
-        if (B.has_ds) {       // 1x1/2 projection: scatter-accumulate into the even positions of dXin
-          ConvArgs s = conv_args(B.ds, dRawD, B.ds.w_dg, dXin, NB, oh, ow);
-          s.C = B.ds.cout; s.K = B.ds.cin; s.stride = 1; s.pad = 0; s.PH = oh; s.PW = ow; s.OH = xh; s.OW = xw; s.osh = B.ds.stride;
-          s.accumulate = 1;
-          TRY(prof_conv(c, dt,s, st));
-        }
-        TRYI(tap(i, 5, dXin, N, xh, xw, B.c1.cin));
+      TRYI(wgrad_call(n, B->c2, P[0].blk[i].raw1, buf(kRaw2, 0, so), &P[0].bn[B->b1.bidx], N * npass, oh, ow, oh, ow, st, 0, N, bn_stride));
+    const char* X0 = i == 0 ? P[0].pooled : P[0].blk[i - 1].y;
+    TRYI(wgrad_call(n, B->c1, X0, buf(kRaw1, 0, so), nullptr, N * npass, xh, xw, oh, ow, st, 1));
+    if (B->has_ds) TRYI(wgrad_call(n, B->ds, X0, buf(kRawD, 0, so), nullptr, N * npass, xh, xw, oh, ow, st, 2));
+    return 0;
+  }
+
+  // ---- input-gradient stage: dXin = conv1's dgrad of dRaw1 + (identity shortcut) G or (projection) its dgrad of dRawD; tap 5.
+  // Neither dgrad has a BatchNorm in it and both are independent per image: one launch over all passes
+  int input_grad() {
+    const int NB = N * npass;
+    char* dXin = buf(kXin, 0, si);
+    ConvArgs a = conv_args(B->c1, buf(kRaw1, 0, so), B->c1.w_dg, dXin, NB, oh, ow);
+    a.C = B->c1.cout; a.K = B->c1.cin; a.transposed = (B->c1.stride == 1) ? 0 : 1; a.PH = xh; a.PW = xw; a.OH = xh; a.OW = xw;
+    if (!B->has_ds) a.residual = buf(kG, 0, so);
+    if (B->c1.stride == 1) {
+      TRY(prof_conv(c, dt, a, st));
+    } else {
+      // stride 2: each parity class only sees 1 + 2 + 2 + 4 = 9 taps instead of 36 tap visits with three quarters zero-gathered;
+      // one launch with the class on grid z where the DMA-gather kernel serves the shape, else four launches
+      ConvArgs q4 = a;
+      q4.pix_mul = 2; q4.PH = xh / 2; q4.PW = xw / 2; q4.par4 = 1;
+      const bool one = xh % 2 == 0 && xw % 2 == 0 && conv_dma_bp(dt, q4) != 0 && conv_dma_bp(DT_BF16, q4) == conv_dma_bp(dt, q4) &&
+                       conv_halo_tw(dt, q4) == 0;
+      if (one) TRY(prof_conv(c, dt, q4, st));
+      for (int par = 0; par < (one ? 0 : 4); ++par) {
+        ConvArgs q = a;
+        const int ph = par >> 1, pw = par & 1;
+        q.pix_mul = 2; q.pix_off_h = ph; q.pix_off_w = pw;
+        q.PH = (xh - ph + 1) / 2; q.PW = (xw - pw + 1) / 2;
+        if (q.PH <= 0 || q.PW <= 0) continue;
+        q.tap_mask = parity_tap_mask(ph, pw);
+        TRY(prof_conv(c, dt, q, st));
       }
-      const int t = kOut; kOut = kXin; kXin = t;      // ping-pong: this block's input gradient is the next dOut
+    }
+    if (B->has_ds) {       // 1x1/2 projection: scatter-accumulate into the even positions of dXin
+      ConvArgs s = conv_args(B->ds, buf(kRawD, 0, so), B->ds.w_dg, dXin, NB, oh, ow);
+      s.C = B->ds.cout; s.K = B->ds.cin; s.stride = 1; s.pad = 0; s.PH = oh; s.PW = ow; s.OH = xh; s.OW = xw; s.osh = B->ds.stride;
+      s.accumulate = 1;
+      TRY(prof_conv(c, dt, s, st));
+    }
+    return tap(5, dXin, xh, xw, B->c1.cin);
+  }
+
+  // the current block from dOut down to dRaw1 / dRawD, and its weight gradients.  Where stages go pass by pass, pass p's bn2, conv2
+  // weight gradient, dgrad and bn1 run before pass p + 1's
+  int block() {
+    if (seg_bn) TRYI(bn2(0, npass));
+    for (int p = 0; p < npass; ++p) {
+      if (!seg_bn) TRYI(bn2(p, 1));
+      if (!c2_batched) TRYI(conv2_wgrad(p));
+      if (!seg_dg) TRYI(conv2_dgrad_bn1(p));
+    }
+    if (seg_dg) TRYI(conv2_dgrad_bn1_segments());
+    return wgrads();
+  }
+
+  // ---- stem stage, pass p: max-pool + ReLU backward -> bn0 backward -> conv1 wgrad (no dgrad: the input is data).
+  // dOut (= dP, the pooled gradient) of pass p sits in its scratch unit, dRaw0 in the stem-sized region behind the units.  The
+  // max-pool + ReLU backward is folded into both BatchNorm-backward passes (the un-pooled gradient is never written out).
+  int stem(int p) {
+    const PassState& ps = P[p];
+    const PoolSrc pool{buf(kOut, p, (size_t)N * d.ph * d.pw * 64 * es), ps.argmax, d.oh0, d.ow0, d.ph, d.pw, ps.pooled};
+    const size_t spix = (size_t)N * d.oh0 * d.ow0;
+    BnBwdReq q;
+    q.x = ps.raw0; q.relu_from_x = 1; q.pixels = spix; q.count = (double)spix; q.pool = &pool;
+    StemWgradArgs w;
+    memset(&w, 0, sizeof(w));
+    w.x = ps.x; w.x2 = ps.x2; w.n_split = ps.n_split; w.dy = dRaw0(); w.dw = (float*)n->grads.p + n->goff[0];
+    w.N = N; w.H = ps.H; w.W = ps.W; w.OH = d.oh0; w.OW = d.ow0; w.in_f32 = ps.in_f32;
+    if (!(n->rg[0] && c->fuse_stem_bwd)) {          // two kernels: the apply pass writes dRaw0, the weight gradient reads it
+      q.dx = dRaw0();
+      TRYI(bn_backward(n, n->bn0, ps.bn[0], q, st));
+      if (n->rg[0]) TRY(launch_stem_wgrad(dt, w, st));
+      return 0;
+    }
+    // conv1 wgrad derives its dY tiles from the pooled gradient itself: the apply pass and its 2 x (N x 128 x 128 x 64)
+    // round trip through HBM are gone (sslcr_stem_wgrad_pool)
+    BnBwdArgs a;
+    double* sums0 = take_sums_or_fixed(c);
+    TRYI(bn_bwd_begin(n, n->bn0, ps.bn[0], q, st, sums0, &a));
+    TRYI(bn_bwd_sync(c, sums0, 2 * 64, st));
+    w.dy = nullptr;
+    auto book = [&](ProfRec& r) {
+      r.name = dt == DT_BF16 ? "sslcr::stem_wgrad_kernel<unsigned short, pool>" : "sslcr::stem_wgrad_kernel<float, pool>";
+      r.flops = 0.0;        // listed with the HBM-bound kernels (0.1 flop per byte)
+      const double t = (double)spix * 64 * c->esz();
+      r.bytes = 0.25 * t + 0.25 * (double)spix * 64 + t + (double)N * 3 * ps.H * ps.W * (ps.in_f32 ? 4 : 1);
+    };
+    return check(profiled(c, 2, st, book, [&] { return launch_stem_wgrad_pool(dt, w, a, st); }), "launch_stem_wgrad_pool");
+  }
+};
+
+int backbone_backward(sslcr_net* n, int npass, hipStream_t st) {
+  sslcr_ctx* c = n->ctx;
+  const int low = lowest_trainable(n);
+  if (low >= 60) return 0;
+  Backward b;
+  b.n = n; b.c = c; b.st = st; b.dt = c->dtype; b.es = c->esz();
+  b.P = n->pass; b.npass = npass; b.N = n->pass[0].N;
+  b.d = make_dims(n->pass[0].H, n->pass[0].W);
+  b.bn_stride = npass > 1 ? (int)(n->pass[1].bn[0].scale - n->pass[0].bn[0].scale) : 0;
+  const Dims& d = b.d; const int N = b.N;
+  b.unit = (((size_t)N * d.ph * d.pw * 64 * b.es) + 255) & ~(size_t)255;
+  const size_t stem_sz = (((size_t)N * d.oh0 * d.ow0 * 64 * b.es) + 255) & ~(size_t)255;
+  TRYI(c->scratch.ensure(kKinds * npass * b.unit + stem_sz));
+  b.S = (char*)c->scratch.p;
+  size_t hi_pending = n->goff[60];
+  int bucket = 1;
+  for (int p = 0; p < npass; ++p)
+    TRY(launch_avgpool_bwd(b.dt, n->dE[p], b.buf(b.kOut, p, (size_t)N * d.lh[7] * d.lw[7] * 512 * b.es), N, d.lh[7] * d.lw[7], 512, st));
+  for (int i = 7; i >= 0; --i) {
+    b.enter(i);
+    TRYI(b.block());
+    const bool need_dx = low < b.B->pstart;          // something upstream of this block is trainable
+    if (need_dx) {
+      TRYI(b.input_grad());
+      const int t = b.kOut; b.kOut = b.kXin; b.kXin = t;      // this block's input gradient is the next dOut
     }
     if (i == 6 || i == 4 || i == 2) {   // layer4 / layer3 / layer2 gradients are final: reduce them under the rest of backward
-      TRYI(launch_bucket_allreduce(n, bucket++, n->goff[B.pstart], hi_pending, st));
-      hi_pending = n->goff[B.pstart];
+      TRYI(launch_bucket_allreduce(n, bucket++, n->goff[b.B->pstart], hi_pending, st));
+      hi_pending = n->goff[b.B->pstart];
     }
     if (!need_dx) break;
   }
-  if (low < 3) {
-    // stem: maxpool+relu backward -> bn0 backward -> conv1 wgrad (no dgrad: the input is data), pass by pass.
-    // dOut (= dP, the pooled gradient) of pass p sits in its scratch unit, dRaw0 in the stem-sized region behind the units.  The
-    // max-pool + ReLU backward is folded into both BatchNorm-backward passes (the un-pooled gradient is never written out).
-    for (int p = 0; p < npass; ++p) {
-      PassState& ps = P[p];
-      PoolSrc pool{buf(kOut, p, (size_t)N * d.ph * d.pw * 64 * es), ps.argmax, d.oh0, d.ow0, d.ph, d.pw, ps.pooled};
-      const size_t spix = (size_t)N * d.oh0 * d.ow0;
-      StemWgradArgs w;
-      memset(&w, 0, sizeof(w));
-      w.x = ps.x; w.x2 = ps.x2; w.n_split = ps.n_split; w.dy = dRaw0; w.dw = (float*)n->grads.p + n->goff[0];
-      w.N = N; w.H = ps.H; w.W = ps.W; w.OH = d.oh0; w.OW = d.ow0; w.in_f32 = ps.in_f32;
-      if (n->rg[0] && c->fuse_stem_bwd) {
-        // conv1 wgrad derives its dY tiles from the pooled gradient itself: the apply pass and its 2 x (N x 128 x 128 x 64)
-        // round trip through HBM are gone (sslcr_stem_wgrad_pool)
-        BnBwdArgs a;
-        double* ring = take_sums(c);
-        double* sums0 = ring ? ring : c->bn_sums;
-        TRYI(bn_bwd_begin(n, n->bn0, ps.bn[0], nullptr, ps.raw0, nullptr, 1, nullptr, nullptr, spix, (double)spix, st, sums0, &a, &pool, 0, nullptr, 0,
-                          ring != nullptr));
-        TRYI(bn_bwd_sync(c, sums0, 2 * 64, st));
-        w.dy = nullptr;
-        if (c->prof.on) {
-          ProfRec r;
-          r.e0 = c->prof.get(); r.e1 = c->prof.get();
-          r.name = dt == DT_BF16 ? "sslcr::stem_wgrad_kernel<unsigned short, pool>" : "sslcr::stem_wgrad_kernel<float, pool>";
-          r.flops = 0.0;        // listed with the HBM-bound kernels (0.1 flop per byte)
-          const double t = (double)spix * 64 * c->esz();
-          r.bytes = 0.25 * t + 0.25 * (double)spix * 64 + t + (double)N * 3 * ps.H * ps.W * (ps.in_f32 ? 4 : 1);
-          (void)hipEventRecord(r.e0, st);
-          hipError_t e = launch_stem_wgrad_pool(dt, w, a, st);
-          (void)hipEventRecord(r.e1, st);
-          c->prof.rec[2].push_back(r);
-          TRY(e);
-        } else {
-          TRY(launch_stem_wgrad_pool(dt, w, a, st));
-        }
-        continue;
-      }
-      TRYI(bn_backward(n, n->bn0, ps.bn[0], nullptr, ps.raw0, nullptr, 1, dRaw0, nullptr, spix, (double)spix, st, &pool));
-      if (n->rg[0]) TRY(launch_stem_wgrad(dt, w, st));
-    }
-  }
+  if (low < 3)
+    for (int p = 0; p < npass; ++p) TRYI(b.stem(p));
   TRYI(launch_bucket_allreduce(n, bucket, 0, hi_pending, st));
   return 0;
 }
