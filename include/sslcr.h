@@ -78,7 +78,7 @@ typedef struct sslcr_conv_desc {
   const float* out_scale;
 } sslcr_conv_desc;
 int sslcr_conv2d(int dtype, const sslcr_conv_desc* d, void* stream);
-int sslcr_conv2d_partial_rows(const sslcr_conv_desc* d);
+int sslcr_conv2d_partial_rows(const sslcr_conv_desc* d);                /* -1: d is NULL, or no segment fits (seg_images > N) */
 int sslcr_conv2d_segments_ok(int dtype, const sslcr_conv_desc* d);      /* 1: this descriptor's seg_images is served */
 /* name of the kernel instance sslcr_conv2d would launch for this descriptor, spelled as rocprofv3 prints it (static string;
    lets tests and profiles tie a shape to the code path that serves it) */

@@ -293,7 +293,10 @@ int conv_dma_rows(const ConvArgs& a, int bp) {
 }
 
 template <typename T, int BP, int BKO>
-static hipError_t launch_d(const ConvArgs& a, hipStream_t st) {
+struct DmaInst { static std::string spell() { return kname("conv_dma_kernel", ktype<T>(), BP, BKO); } };
+
+template <typename T, int BP, int BKO>
+static hipError_t launch_d(DmaInst<T, BP, BKO>, const ConvArgs& a, hipStream_t st) {
   const int M = a.N * a.PH * a.PW;
   const size_t lds = 2 * (BP + BKO) * 128;
   auto kern = conv_dma_kernel<T, BP, BKO>;
@@ -308,14 +311,16 @@ static hipError_t launch_d(const ConvArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_conv_dma(int dtype, const ConvArgs& a, int bp, hipStream_t st) {
-  if (dtype == DT_BF16) return bp == 128 ? launch_d<bf16_t, 128, 128>(a, st) : launch_d<bf16_t, 256, 64>(a, st);
-  return bp == 128 ? launch_d<float, 128, 128>(a, st) : launch_d<float, 256, 64>(a, st);
+// the instance of pixel block bp (conv_dma_bp): f(DmaInst<T, BP, BKO>{})
+template <class F>
+static auto dma_pick(int dtype, int bp, F&& f) {
+  if (dtype == DT_BF16) return bp == 128 ? f(DmaInst<bf16_t, 128, 128>{}) : f(DmaInst<bf16_t, 256, 64>{});
+  return bp == 128 ? f(DmaInst<float, 128, 128>{}) : f(DmaInst<float, 256, 64>{});
 }
 
-const char* conv_dma_name(int dtype, int bp) {
-  if (dtype == DT_BF16) return bp == 128 ? "sslcr::conv_dma_kernel<unsigned short, 128, 128>" : "sslcr::conv_dma_kernel<unsigned short, 256, 64>";
-  return bp == 128 ? "sslcr::conv_dma_kernel<float, 128, 128>" : "sslcr::conv_dma_kernel<float, 256, 64>";
+hipError_t launch_conv_dma(int dtype, const ConvArgs& a, int bp, hipStream_t st) {
+  return dma_pick(dtype, bp, [&](auto inst) { return launch_d(inst, a, st); });
 }
+const char* conv_dma_name(int dtype, int bp) { return dma_pick(dtype, bp, InstName{}); }
 
 }  // namespace sslcr

@@ -84,7 +84,7 @@ __device__ unsigned long long g_h16_prof[16][8];
 //     256 pixels x BKO kouts, wave wp owns image wp, a fragment's 16 lanes are two image rows.  Every halo-ring pixel is padding, so
 //     the ring is zeroed once and a stage stages the 256 interior pixels only (4 loads per thread, no edge logic); halo rows are
 //     pitched 10 pixels with the swizzle key = halo column & 7 (conflict-free over the lane groups of ds_read_b128, enumerated for
-//     conv3x3_halo256's 8-wide form).  row0: first statistics row of this launch (a shape served by two launches, see launch_ht8).
+//     conv3x3_halo256's 8-wide form).  row0: first statistics row of this launch (a shape served by two launches, see launch_ht).
 // OSC (round 6): sslcr_conv_desc.out_scale -- eval-mode BatchNorm with its scale kept out of the filters, y = epilogue(acc * scale + bias).
 //     An instance (and a kernel name, conv3x3_h16s_kernel) of its own: as a run-time case inside the plain instance the sixteen scale
 //     values took the dominant instance of the step from 251 registers to 256 + 120 B of scratch (all of its launches, the dgrads too).
@@ -105,31 +105,25 @@ __global__ __launch_bounds__(256 * WK, WK == 1 ? 1 : 2) void conv3x3_h16s_kernel
 }
 
 // 16: 16x16 tiles of one image; 8: four whole 8x8 images per tile (128-kout blocks: ResNet18 layer4 at 256x256 input); 0: not served.
-// The same answer for both dtypes (sslcr_conv2d_partial_rows has no dtype: the launches must tile identically).
-static int h16_mode(int dtype, const ConvArgs& a) {
-  const int q = conv_halo256_mode(dtype, a);
-  if (q == 16 && conv_halo256_mode(DT_BF16, a) == 16) return 16;
+// q: the conv3x3_halo256 tiling of the descriptor that both dtypes agree on (conv_plan: the launches must tile identically)
+int conv_h16_mode(const ConvArgs& a, int q) {
   static const bool on8 = [] { const char* e = getenv("SSLCR_H16_TW8"); return !e || atoi(e) != 0; }();   // 0: conv3x3_halo256 keeps the shape (A/B runs)
-  if (q == 8 && on8 && conv_halo256_mode(DT_BF16, a) == 8 && a.K % 128 == 0 && !a.mask_x && (a.seg_images <= 0 || a.seg_images % 4 == 0)) return 8;
-  return 0;
-}
-bool conv_h16_ok(int dtype, const ConvArgs& a) {
-  if (a.in_scale && a.residual) return false;          // not a ResNet combination; the older halo kernels take it
+  const int mode = q == 16 ? 16 : (q == 8 && on8 && a.K % 128 == 0 && !a.mask_x && (a.seg_images <= 0 || a.seg_images % 4 == 0)) ? 8 : 0;
+  if (mode == 0) return 0;
+  if (a.in_scale && a.residual) return 0;              // not a ResNet combination; the older halo kernels take it
   if (a.mask_x) {
     // (a.stats is checked at launch: sslcr_conv2d_partial_rows asks before the rows buffer exists)
-    if (!a.mask_scale || !a.mask_shift || !a.mask_mean || a.in_scale || a.bias || a.residual || a.relu || a.out_scale) return false;
-    if (18 * 24 * 128 + 2 * 3 * (a.K % 128 == 0 ? 128 : 64) * 128 + 2 * a.C * 4 + 8 * 128 * 4 + 3 * a.K * 4 > 160 * 1024) return false;
+    if (!a.mask_scale || !a.mask_shift || !a.mask_mean || a.in_scale || a.bias || a.residual || a.relu || a.out_scale) return 0;
+    if (18 * 24 * 128 + 2 * 3 * (a.K % 128 == 0 ? 128 : 64) * 128 + 2 * a.C * 4 + 8 * 128 * 4 + 3 * a.K * 4 > 160 * 1024) return 0;
   }
   if (a.out_scale) {
     // one more K-float array in LDS (the input-transform and train-forward instances have no output scale: bias forms only)
-    if (a.in_scale || a.stats || !a.bias) return false;
-    const int mode = h16_mode(dtype, a);
-    if (mode == 0) return false;
+    if (a.in_scale || a.stats || !a.bias) return 0;
     const int bko = a.K % 128 == 0 ? 128 : 64;
     if (!(a.C == 64 && a.K == 64) &&
-        (mode == 16 ? 18 * 24 : 4 * 10 * 10) * 128 + 2 * 3 * bko * 128 + 2 * a.C * 4 + 8 * bko * 4 + 2 * a.K * 4 > 160 * 1024) return false;
+        (mode == 16 ? 18 * 24 : 4 * 10 * 10) * 128 + 2 * 3 * bko * 128 + 2 * a.C * 4 + 8 * bko * 4 + 2 * a.K * 4 > 160 * 1024) return 0;
   }
-  return h16_mode(dtype, a) != 0;
+  return mode;
 }
 static int h16_tiles(const ConvArgs& a, int nseg) {                     // per segment
   return a.H == 8 ? (a.N / nseg) / 4 : (a.N / nseg) * (a.H / 16) * (a.W / 16);
@@ -163,7 +157,6 @@ static ConvArgs h16_tailargs8(const ConvArgs& a, int tail, int dtype) {
   return t;
 }
 int conv_h16_rows(const ConvArgs& a) {
-  if (a.seg_images > 0 && conv_pp64_ok(DT_BF16, a)) return conv_pp64_rows(a);      // segments are bf16-only: the ping-pong kernel's own grid
   const int tail = h16_tail8(a);
   if (tail) return (h16_grid(h16_head8(a, tail), 128) + h16_grid(h16_tailargs8(a, tail, DT_BF16), 64)) * 4;
   return h16_grid(a, a.K % 128 == 0 ? 128 : 64) * 4;
@@ -177,8 +170,16 @@ static bool h16_raw(const ConvArgs& a) {
   return on && a.stats && !a.bias && !a.relu && !a.residual && !a.mask_x;
 }
 
-template <typename T, int BKO, int WK, bool XF, bool WR = false, bool RAW = false, int TW = 16, bool OSC = false>
-static hipError_t launch_h(const ConvArgs& a, hipStream_t st, int row0 = 0) {
+// one tag per template instance of the two kernels (OSC: conv3x3_h16s_kernel<T, BKO, WK, WR, TW>)
+template <typename T, int BKO, int WK, bool XF, bool WR, bool RAW, int TW, bool OSC>
+struct H16Inst {
+  static std::string spell() {
+    return OSC ? kname("conv3x3_h16s_kernel", ktype<T>(), BKO, WK, WR, TW) : kname("conv3x3_h16_kernel", ktype<T>(), BKO, WK, XF, WR, RAW, TW);
+  }
+};
+
+template <typename T, int BKO, int WK, bool XF, bool WR, bool RAW, int TW, bool OSC>
+static hipError_t launch_h(H16Inst<T, BKO, WK, XF, WR, RAW, TW, OSC>, const ConvArgs& a, hipStream_t st, int row0) {
   const size_t lds = (TW == 16 ? 18 * 24 : 4 * 10 * 10) * 128 + (WR ? 3 : 2) * 3 * BKO * 128 + 2 * a.C * sizeof(float) + 8 * BKO * sizeof(float) +
                      (a.mask_x ? 3 : (a.out_scale ? 2 : 1)) * a.K * sizeof(float);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
@@ -203,78 +204,45 @@ static hipError_t launch_h(const ConvArgs& a, hipStream_t st, int row0 = 0) {
   return hipGetLastError();
 }
 
-// four-image tiles, K % 128 == 0 (h16_mode == 8)
-template <typename T>
-static hipError_t launch_ht8(const ConvArgs& a, hipStream_t st) {
+// The instance of one (kout block, tile, filter residency) form that a's operands select: f(H16Inst<...>{}).  The RAW output stage
+// exists in the bf16 128-kout forms.
+template <typename T, int BKO, int TW, bool WR, class F>
+static auto h16_pick_form(const ConvArgs& a, F&& f) {
   const bool xf = a.in_scale != nullptr;
-  auto wide = [&](const ConvArgs& q) {
-    if (q.out_scale) return launch_h<T, 128, 2, false, false, false, 8, true>(q, st);
-    if constexpr (sizeof(T) == 2)
-      if (h16_raw(q)) return xf ? launch_h<T, 128, 2, true, false, true, 8>(q, st) : launch_h<T, 128, 2, false, false, true, 8>(q, st);
-    return xf ? launch_h<T, 128, 2, true, false, false, 8>(q, st) : launch_h<T, 128, 2, false, false, false, 8>(q, st);
-  };
+  if (a.out_scale) return f(H16Inst<T, BKO, 2, false, WR, false, TW, true>{});
+  if constexpr (sizeof(T) == 2 && BKO == 128)
+    if (h16_raw(a)) return xf ? f(H16Inst<T, BKO, 2, true, WR, true, TW, false>{}) : f(H16Inst<T, BKO, 2, false, WR, true, TW, false>{});
+  return xf ? f(H16Inst<T, BKO, 2, true, WR, false, TW, false>{}) : f(H16Inst<T, BKO, 2, false, WR, false, TW, false>{});
+}
+// ... and the form: the launch's instance -- of a four-image shape's two launches (launch_ht) the first, 128-kout one
+template <typename T, class F>
+static auto h16_pick(const ConvArgs& a, int mode, F&& f) {
+  if (mode == 8) return h16_pick_form<T, 128, 8, false>(a, f);         // (K % 128 == 0: conv_h16_mode)
+  if (a.K % 128 == 0) return h16_pick_form<T, 128, 16, false>(a, f);
+  if constexpr (sizeof(T) == 2)
+    if (h16_resident(a)) return h16_pick_form<T, 64, 16, true>(a, f);
+  return h16_pick_form<T, 64, 16, false>(a, f);
+}
+
+template <typename T>
+static hipError_t launch_ht(const ConvArgs& a, int mode, hipStream_t st) {
   const int tail = h16_tail8(a);
-  if (!tail) return wide(a);
+  if (!tail) return h16_pick<T>(a, mode, [&](auto inst) { return launch_h(inst, a, st, 0); });
+  // four-image tiles with a thin last round: the head's items in 128-kout blocks, the tail images' in 64-kout blocks
   const ConvArgs head = h16_head8(a, tail), tl = h16_tailargs8(a, tail, Elem<T>::DT);
-  hipError_t e = wide(head);
+  hipError_t e = h16_pick<T>(head, mode, [&](auto inst) { return launch_h(inst, head, st, 0); });
   if (e != hipSuccess) return e;
   const int row0 = h16_grid(head, 128) * 4;                             // the tail's statistics rows follow the head's
-  if (tl.out_scale) return launch_h<T, 64, 2, false, false, false, 8, true>(tl, st, row0);
-  return xf ? launch_h<T, 64, 2, true, false, false, 8>(tl, st, row0) : launch_h<T, 64, 2, false, false, false, 8>(tl, st, row0);
+  return h16_pick_form<T, 64, 8, false>(tl, [&](auto inst) { return launch_h(inst, tl, st, row0); });
 }
 
-template <typename T>
-static hipError_t launch_ht(const ConvArgs& a, hipStream_t st) {
-  const bool xf = a.in_scale != nullptr;
-  if (h16_mode(Elem<T>::DT, a) == 8) return launch_ht8<T>(a, st);
-  if (a.K % 128 == 0) {
-    if (a.out_scale) return launch_h<T, 128, 2, false, false, false, 16, true>(a, st);
-    if constexpr (sizeof(T) == 2)
-      if (h16_raw(a)) return xf ? launch_h<T, 128, 2, true, false, true>(a, st) : launch_h<T, 128, 2, false, false, true>(a, st);
-    return xf ? launch_h<T, 128, 2, true>(a, st) : launch_h<T, 128, 2, false>(a, st);
-  }
-  if constexpr (sizeof(T) == 2)
-    if (h16_resident(a)) {
-      if (conv_pp64_ok(DT_BF16, a)) return launch_conv_pp64(a, st);        // ping-pong form (conv_pp64.hip)
-      if (a.out_scale) return launch_h<T, 64, 2, false, true, false, 16, true>(a, st);
-      return xf ? launch_h<T, 64, 2, true, true>(a, st) : launch_h<T, 64, 2, false, true>(a, st);
-    }
-  if (a.out_scale) return launch_h<T, 64, 2, false, false, false, 16, true>(a, st);
-  return xf ? launch_h<T, 64, 2, true>(a, st) : launch_h<T, 64, 2, false>(a, st);
-}
-
-hipError_t launch_conv_h16(int dtype, const ConvArgs& a, hipStream_t st) {
+hipError_t launch_conv_h16(int dtype, const ConvArgs& a, int mode, hipStream_t st) {
   if (a.mask_x && !a.stats) return hipErrorInvalidValue;
-  return dtype == DT_BF16 ? launch_ht<bf16_t>(a, st) : launch_ht<float>(a, st);
+  return dtype == DT_BF16 ? launch_ht<bf16_t>(a, mode, st) : launch_ht<float>(a, mode, st);
 }
 
-// (the profiler's name of the launch -- of its first, 128-kout launch where a four-image shape takes two)
-const char* conv_h16_name(int dtype, const ConvArgs& a) {
-  const bool bf = dtype == DT_BF16, xf = a.in_scale != nullptr;
-  if (a.out_scale) {                          // conv3x3_h16s_kernel<T, BKO, WK, WR, TW>
-    if (h16_mode(dtype, a) == 8) return bf ? "sslcr::conv3x3_h16s_kernel<unsigned short, 128, 2, false, 8>" : "sslcr::conv3x3_h16s_kernel<float, 128, 2, false, 8>";
-    if (a.K % 128 == 0) return bf ? "sslcr::conv3x3_h16s_kernel<unsigned short, 128, 2, false, 16>" : "sslcr::conv3x3_h16s_kernel<float, 128, 2, false, 16>";
-    if (bf && h16_resident(a) && conv_pp64_ok(DT_BF16, a)) return conv_pp64_name(a);
-    if (bf && h16_resident(a)) return "sslcr::conv3x3_h16s_kernel<unsigned short, 64, 2, true, 16>";
-    return bf ? "sslcr::conv3x3_h16s_kernel<unsigned short, 64, 2, false, 16>" : "sslcr::conv3x3_h16s_kernel<float, 64, 2, false, 16>";
-  }
-  if (h16_mode(dtype, a) == 8) {
-    if (!bf) return xf ? "sslcr::conv3x3_h16_kernel<float, 128, 2, true, false, false, 8>" : "sslcr::conv3x3_h16_kernel<float, 128, 2, false, false, false, 8>";
-    if (h16_raw(a))
-      return xf ? "sslcr::conv3x3_h16_kernel<unsigned short, 128, 2, true, false, true, 8>" : "sslcr::conv3x3_h16_kernel<unsigned short, 128, 2, false, false, true, 8>";
-    return xf ? "sslcr::conv3x3_h16_kernel<unsigned short, 128, 2, true, false, false, 8>" : "sslcr::conv3x3_h16_kernel<unsigned short, 128, 2, false, false, false, 8>";
-  }
-  if (a.K % 128 == 0) {
-    if (bf && h16_raw(a))
-      return xf ? "sslcr::conv3x3_h16_kernel<unsigned short, 128, 2, true, false, true, 16>" : "sslcr::conv3x3_h16_kernel<unsigned short, 128, 2, false, false, true, 16>";
-    if (bf) return xf ? "sslcr::conv3x3_h16_kernel<unsigned short, 128, 2, true, false, false, 16>" : "sslcr::conv3x3_h16_kernel<unsigned short, 128, 2, false, false, false, 16>";
-    return xf ? "sslcr::conv3x3_h16_kernel<float, 128, 2, true, false, false, 16>" : "sslcr::conv3x3_h16_kernel<float, 128, 2, false, false, false, 16>";
-  }
-  if (bf && h16_resident(a) && conv_pp64_ok(DT_BF16, a)) return conv_pp64_name(a);
-  if (bf && h16_resident(a))
-    return xf ? "sslcr::conv3x3_h16_kernel<unsigned short, 64, 2, true, true, false, 16>" : "sslcr::conv3x3_h16_kernel<unsigned short, 64, 2, false, true, false, 16>";
-  if (bf) return xf ? "sslcr::conv3x3_h16_kernel<unsigned short, 64, 2, true, false, false, 16>" : "sslcr::conv3x3_h16_kernel<unsigned short, 64, 2, false, false, false, 16>";
-  return xf ? "sslcr::conv3x3_h16_kernel<float, 64, 2, true, false, false, 16>" : "sslcr::conv3x3_h16_kernel<float, 64, 2, false, false, false, 16>";
+const char* conv_h16_name(int dtype, const ConvArgs& a, int mode) {
+  return dtype == DT_BF16 ? h16_pick<bf16_t>(a, mode, InstName{}) : h16_pick<float>(a, mode, InstName{});
 }
 
 }  // namespace sslcr

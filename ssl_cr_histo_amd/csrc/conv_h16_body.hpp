@@ -248,7 +248,7 @@
   frags(0, 0, s_w);
 
   char* yg = reinterpret_cast<char*>(a.y);
-  // no residual with an input transform (conv_h16_ok): a residual load in the epilogue -- even one skipped at run time --
+  // no residual with an input transform (conv_h16_mode): a residual load in the epilogue -- even one skipped at run time --
   // made the compiler put a vmcnt(0) in front of every output store, i.e. eight serial write round trips per item
   const char* rg = (XF || RAW) ? nullptr : reinterpret_cast<const char*>(a.mask_x ? a.mask_x : a.residual);   // same shape, same prefetch
   // bf16 residual (teacher conv2 / the skip gradient of a block's first dgrad): requested with the next halo in the middle

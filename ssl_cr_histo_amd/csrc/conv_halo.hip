@@ -260,8 +260,12 @@ int conv_halo_tiles(const ConvArgs& a, int tw) {
   return (a.N / ni) * (a.H / 8) * (a.W / tw);
 }
 
+// (the reported name elides the tile arguments: the route tables and the recorded profiles have this family under one name per dtype)
 template <typename T, int TW, int BKO>
-static hipError_t launch_h(const ConvArgs& a, hipStream_t st) {
+struct HaloInst { static std::string spell() { return kname("conv3x3_halo_kernel", ktype<T>(), "..."); } };
+
+template <typename T, int TW, int BKO>
+static hipError_t launch_h(HaloInst<T, TW, BKO>, const ConvArgs& a, hipStream_t st) {
   constexpr int HP = (128 / (8 * TW)) * 10 * (TW + 2);
   const size_t lds = 2 * HP * 128 + 2 * a.C * sizeof(float);
   dim3 grid(conv_halo_tiles(a, TW), a.K / BKO);
@@ -269,15 +273,20 @@ static hipError_t launch_h(const ConvArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-template <typename T>
-static hipError_t launch_ht(const ConvArgs& a, int tw, hipStream_t st) {
+// the instance that serves a at tile width tw: f(HaloInst<T, TW, BKO>{})
+template <typename T, class F>
+static auto halo_pick(const ConvArgs& a, int tw, F&& f) {
   const bool wide = a.K % 128 == 0;
-  if (tw == 16) return wide ? launch_h<T, 16, 128>(a, st) : launch_h<T, 16, 64>(a, st);
-  return wide ? launch_h<T, 8, 128>(a, st) : launch_h<T, 8, 64>(a, st);
+  if (tw == 16) return wide ? f(HaloInst<T, 16, 128>{}) : f(HaloInst<T, 16, 64>{});
+  return wide ? f(HaloInst<T, 8, 128>{}) : f(HaloInst<T, 8, 64>{});
 }
 
 hipError_t launch_conv_halo(int dtype, const ConvArgs& a, int tw, hipStream_t st) {
-  return dtype == DT_BF16 ? launch_ht<bf16_t>(a, tw, st) : launch_ht<float>(a, tw, st);
+  auto go = [&](auto inst) { return launch_h(inst, a, st); };
+  return dtype == DT_BF16 ? halo_pick<bf16_t>(a, tw, go) : halo_pick<float>(a, tw, go);
+}
+const char* conv_halo_name(int dtype, const ConvArgs& a, int tw) {
+  return dtype == DT_BF16 ? halo_pick<bf16_t>(a, tw, InstName{}) : halo_pick<float>(a, tw, InstName{});
 }
 
 }  // namespace sslcr

@@ -343,7 +343,10 @@ int conv_halo256_tiles(const ConvArgs& a, int mode) {
 }
 
 template <typename T, int TW, int BKO, int WK, bool ONE>
-static hipError_t launch_q(const ConvArgs& a, hipStream_t st, int tile0 = 0, int ntiles = -1) {
+struct Halo256Inst { static std::string spell() { return kname("conv3x3_halo256_kernel", ktype<T>(), TW, BKO, WK, ONE); } };
+
+template <typename T, int TW, int BKO, int WK, bool ONE>
+static hipError_t launch_q(Halo256Inst<T, TW, BKO, WK, ONE>, const ConvArgs& a, hipStream_t st, int tile0 = 0, int ntiles = -1) {
   constexpr int HP = (256 / (TW * TW)) * (TW + 2) * (TW + 2);
   constexpr int TPB = (WK == 2 && !ONE) ? 3 : 1;
   const size_t lds = HP * 128 + 2 * TPB * BKO * 128 + 2 * a.C * sizeof(float);
@@ -359,15 +362,21 @@ static hipError_t launch_q(const ConvArgs& a, hipStream_t st, int tile0 = 0, int
   return hipGetLastError();
 }
 
+// the instance that serves a in this tile mode: f(Halo256Inst<...>{}) -- of the two launches a four-image shape with a thin last round
+// takes (launch_qt), the first, 128-kout one
+template <typename T, int TW, class F>
+static auto halo256_pick_tw(const ConvArgs& a, F&& f) {
+  if (a.K % 128 == 0) return f(Halo256Inst<T, TW, 128, 2, false>{});
+  return a.C == 8 * Elem<T>::EPC ? f(Halo256Inst<T, TW, 64, 1, true>{}) : f(Halo256Inst<T, TW, 64, 2, false>{});
+}
+template <typename T, class F>
+static auto halo256_pick(const ConvArgs& a, int mode, F&& f) {
+  return mode == 16 ? halo256_pick_tw<T, 16>(a, f) : halo256_pick_tw<T, 8>(a, f);
+}
+
 template <typename T>
 static hipError_t launch_qt(const ConvArgs& a, int mode, hipStream_t st) {
-  const bool wide = a.K % 128 == 0;
-  const bool one = a.C == 8 * Elem<T>::EPC;
-  if (mode == 16) {
-    if (wide) return launch_q<T, 16, 128, 2, false>(a, st);
-    return one ? launch_q<T, 16, 64, 1, true>(a, st) : launch_q<T, 16, 64, 2, false>(a, st);
-  }
-  if (wide) {
+  if (mode == 8 && a.K % 128 == 0) {
     // one workgroup per CU and (tile, 128-kout block) item: when the last round would occupy at most half the CUs (N=640 at
     // layer4: 640 items = 2.5 rounds of 256), its tiles run as 64-kout half-items on all of them instead -- ~0.6 of a round
     // instead of a whole one
@@ -376,18 +385,20 @@ static hipError_t launch_qt(const ConvArgs& a, int mode, hipStream_t st) {
     if (rem != 0 && 2 * rem <= cus && rem % kb == 0) {          // (also the whole launch when it has at most cus / 2 items: N=128)
       const int tail = rem / kb;
       if (tiles > tail) {
-        hipError_t e = launch_q<T, 8, 128, 2, false>(a, st, 0, tiles - tail);
+        hipError_t e = halo256_pick<T>(a, mode, [&](auto inst) { return launch_q(inst, a, st, 0, tiles - tail); });
         if (e != hipSuccess) return e;
       }
-      return launch_q<T, 8, 64, 2, false>(a, st, tiles - tail, tail);
+      return launch_q(Halo256Inst<T, 8, 64, 2, false>{}, a, st, tiles - tail, tail);
     }
-    return launch_q<T, 8, 128, 2, false>(a, st);
   }
-  return one ? launch_q<T, 8, 64, 1, true>(a, st) : launch_q<T, 8, 64, 2, false>(a, st);
+  return halo256_pick<T>(a, mode, [&](auto inst) { return launch_q(inst, a, st); });
 }
 
 hipError_t launch_conv_halo256(int dtype, const ConvArgs& a, int mode, hipStream_t st) {
   return dtype == DT_BF16 ? launch_qt<bf16_t>(a, mode, st) : launch_qt<float>(a, mode, st);
+}
+const char* conv_halo256_name(int dtype, const ConvArgs& a, int mode) {
+  return dtype == DT_BF16 ? halo256_pick<bf16_t>(a, mode, InstName{}) : halo256_pick<float>(a, mode, InstName{});
 }
 
 }  // namespace sslcr

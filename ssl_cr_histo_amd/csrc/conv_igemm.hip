@@ -256,7 +256,10 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a) {
 }
 
 template <typename T, int BP, int BKO>
-static hipError_t launch_cfg(const ConvArgs& a, hipStream_t st) {
+struct IgemmInst { static std::string spell() { return kname("conv_igemm_kernel", ktype<T>(), BP, BKO); } };
+
+template <typename T, int BP, int BKO>
+static hipError_t launch_cfg(IgemmInst<T, BP, BKO>, const ConvArgs& a, hipStream_t st) {
   const int M = a.N * a.PH * a.PW;
   dim3 grid(cdiv(M, BP), a.K / BKO);
   size_t lds = 2 * (BP + BKO) * 128 + 2 * a.C * sizeof(float);
@@ -271,110 +274,30 @@ static hipError_t launch_cfg(const ConvArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-static int g_conv_dtype_hint = DT_BF16;   // conv_partials_rows() is asked before the launch: both dtypes tile identically
-int conv_partials_rows(const ConvArgs& a) {
-  if (conv_h16_ok(g_conv_dtype_hint, a)) return conv_h16_rows(a);
-  const int q = conv_halo256_mode(g_conv_dtype_hint, a);
-  if (q) return conv_halo256_tiles(a, q) * 4;
-  const int tw = conv_halo_tw(g_conv_dtype_hint, a);
-  if (tw) return conv_halo_tiles(a, tw) * 2;
-  const int bp = conv_dma_bp(g_conv_dtype_hint, a);
-  if (bp) return conv_dma_rows(a, bp);
-  const int M = a.N * a.PH * a.PW;
-  return cdiv(M, conv_tile_bp(a)) * 2;
-}
-
-int conv_tile_bp(const ConvArgs& a) {
+static int igemm_bp(const ConvArgs& a) {
   const int M = a.N * a.PH * a.PW;
   return M >= 128 * 512 ? 128 : 64;     // keep >= ~512 workgroups on the 256 CUs when M is small
+}
+int conv_igemm_rows(const ConvArgs& a) { return cdiv(a.N * a.PH * a.PW, igemm_bp(a)) * 2; }
+
+// the instance that serves a: f(IgemmInst<T, BP, BKO>{})
+template <typename T, class F>
+static auto igemm_pick(const ConvArgs& a, F&& f) {
+  if (igemm_bp(a) == 128) return a.K % 128 == 0 ? f(IgemmInst<T, 128, 128>{}) : f(IgemmInst<T, 128, 64>{});
+  return f(IgemmInst<T, 64, 64>{});
 }
 
 template <typename T>
 static hipError_t launch_t(const ConvArgs& a, hipStream_t st) {
   constexpr int CE = 8 * Elem<T>::EPC;
   if (a.C % CE != 0 || a.K % 64 != 0) return hipErrorInvalidValue;
-  const int bp = conv_tile_bp(a);
-  if (bp == 128) {
-    if (a.K % 128 == 0) return launch_cfg<T, 128, 128>(a, st);
-    return launch_cfg<T, 128, 64>(a, st);
-  }
-  return launch_cfg<T, 64, 64>(a, st);
+  return igemm_pick<T>(a, [&](auto inst) { return launch_cfg(inst, a, st); });
 }
-
-// the template instance launch_conv() will pick, spelled like rocprofv3 prints it (minus the argument list)
-const char* conv_kernel_name(int dtype, const ConvArgs& a) {
-  const bool bf = dtype == DT_BF16;
-  const bool wide = a.K % 128 == 0;
-  if (conv_h16_ok(dtype, a)) return conv_h16_name(dtype, a);
-  const int q = conv_halo256_mode(dtype, a);
-  if (q && conv_halo256_mode(DT_BF16, a) == q) {
-    const bool one = a.C == (bf ? 64 : 32);
-    if (q == 16) {
-      if (wide) return bf ? "sslcr::conv3x3_halo256_kernel<unsigned short, 16, 128, 2, false>" : "sslcr::conv3x3_halo256_kernel<float, 16, 128, 2, false>";
-      if (one) return bf ? "sslcr::conv3x3_halo256_kernel<unsigned short, 16, 64, 1, true>" : "sslcr::conv3x3_halo256_kernel<float, 16, 64, 1, true>";
-      return bf ? "sslcr::conv3x3_halo256_kernel<unsigned short, 16, 64, 2, false>" : "sslcr::conv3x3_halo256_kernel<float, 16, 64, 2, false>";
-    }
-    if (wide) return bf ? "sslcr::conv3x3_halo256_kernel<unsigned short, 8, 128, 2, false>" : "sslcr::conv3x3_halo256_kernel<float, 8, 128, 2, false>";
-    if (one) return bf ? "sslcr::conv3x3_halo256_kernel<unsigned short, 8, 64, 1, true>" : "sslcr::conv3x3_halo256_kernel<float, 8, 64, 1, true>";
-    return bf ? "sslcr::conv3x3_halo256_kernel<unsigned short, 8, 64, 2, false>" : "sslcr::conv3x3_halo256_kernel<float, 8, 64, 2, false>";
-  }
-  const int tw = q ? 0 : conv_halo_tw(dtype, a);
-  if (tw && conv_halo_tw(DT_BF16, a) == tw) return bf ? "sslcr::conv3x3_halo_kernel<unsigned short, ...>" : "sslcr::conv3x3_halo_kernel<float, ...>";
-  if (!q && !tw && conv_s2_ok(dtype, a)) return conv_s2_name(a, false);
-  if (!q && !tw && conv_s2d_ok(dtype, a)) return conv_s2d_name();
-  const int dbp = (q || tw) ? 0 : conv_dma_bp(dtype, a);
-  if (dbp && conv_dma_bp(DT_BF16, a) == dbp) return conv_dma_name(dtype, dbp);
-  const int bp = conv_tile_bp(a);
-  if (bp == 128) {
-    if (wide) return bf ? "sslcr::conv_igemm_kernel<unsigned short, 128, 128>" : "sslcr::conv_igemm_kernel<float, 128, 128>";
-    return bf ? "sslcr::conv_igemm_kernel<unsigned short, 128, 64>" : "sslcr::conv_igemm_kernel<float, 128, 64>";
-  }
-  return bf ? "sslcr::conv_igemm_kernel<unsigned short, 64, 64>" : "sslcr::conv_igemm_kernel<float, 64, 64>";
-}
-
-int device_cus() {
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-  }();
-  return cus;
-}
-
-// Segments (sslcr_conv_desc.seg_images): which kernels have the form, and where the row ranges come out right.
-//   conv3x3_h16 / conv3x3_pp64: the grid is split into nseg groups of workgroups (their statistics rows are per workgroup)
-//   conv3x3_halo256: one workgroup per tile, rows in tile order; a tile's images must not straddle a segment
-//   conv_dma: rows in pixel order, no prologue; a pixel block must not straddle a segment
-bool conv_segments_ok(int dtype, const ConvArgs& a) {
-  if (a.seg_images <= 0) return true;
-  if (dtype != DT_BF16 || a.N % a.seg_images != 0 || a.transposed || a.par4) return false;
-  const int nseg = a.N / a.seg_images;
-  if (nseg > 8) return false;
-  if (conv_h16_ok(dtype, a)) return true;          // (with mask_x: mask_scale / mask_shift / mask_mean + s * seg_stride)
-  if (a.mask_x) return false;
-  const int q = conv_halo256_mode(dtype, a);
-  if (q) return q == 16 || a.seg_images % 4 == 0;
-  if (conv_halo_tw(dtype, a)) return false;
-  const int bp = conv_dma_bp(dtype, a);
-  if (bp) return !a.in_scale && ((long)a.seg_images * a.PH * a.PW) % bp == 0;
-  return false;
-}
-
-hipError_t launch_conv(int dtype, const ConvArgs& a, hipStream_t st) {
-  if (!conv_segments_ok(dtype, a)) return hipErrorInvalidValue;
-  if (a.out_scale && (!a.bias || a.stats || a.mask_x)) return hipErrorInvalidValue;      // the output scale exists in the bias (eval) epilogues only
-  if (conv_h16_ok(dtype, a)) return launch_conv_h16(dtype, a, st);
-  if (a.mask_x) return hipErrorInvalidValue;        // the BatchNorm-backward front end exists in the 16x16-tile kernel only
-  const int q = conv_halo256_mode(dtype, a);
-  if (q && conv_halo256_mode(DT_BF16, a) == q) return launch_conv_halo256(dtype, a, q, st);
-  const int tw = q ? 0 : conv_halo_tw(dtype, a);
-  if (tw && conv_halo_tw(DT_BF16, a) == tw) return launch_conv_halo(dtype, a, tw, st);   // (same tiling in both dtypes)
-  if (!q && !tw && conv_s2_ok(dtype, a)) return launch_conv_s2(a, nullptr, st);       // 3x3 / 2 on 16x16 output tiles (rows as conv_dma's)
-  if (!q && !tw && conv_s2d_ok(dtype, a)) return launch_conv_s2d(a, st);             // ... and its dgrad, the four parity classes in one pass
-  const int dbp = (q || tw) ? 0 : conv_dma_bp(dtype, a);
-  if (dbp && conv_dma_bp(DT_BF16, a) == dbp) return launch_conv_dma(dtype, a, dbp, st);
-  if (a.par4) return hipErrorInvalidValue;          // the one-launch parity form exists in the DMA-gather kernel only
+hipError_t launch_igemm(int dtype, const ConvArgs& a, hipStream_t st) {
   return dtype == DT_BF16 ? launch_t<bf16_t>(a, st) : launch_t<float>(a, st);
+}
+const char* conv_igemm_name(int dtype, const ConvArgs& a) {
+  return dtype == DT_BF16 ? igemm_pick<bf16_t>(a, InstName{}) : igemm_pick<float>(a, InstName{});
 }
 
 }  // namespace sslcr

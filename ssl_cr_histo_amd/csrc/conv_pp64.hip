@@ -445,8 +445,8 @@ static int pp64_grid(const ConvArgs& a) {
   return (pairs < per ? pairs : per) * nseg;
 }
 
-// bf16 64 -> 64 on 16x16-tileable maps, every operand combination conv3x3_h16's resident-filter form serves (its caller has
-// already checked conv_h16_ok); SSLCR_PP64=0 keeps the old kernel for same-box A/B runs
+// bf16 64 -> 64 on 16x16-tileable maps, every operand combination conv3x3_h16's resident-filter form serves (conv_plan asks where
+// conv_h16_mode has taken the descriptor); SSLCR_PP64=0 keeps the old kernel for same-box A/B runs
 bool conv_pp64_ok(int dtype, const ConvArgs& a) {
   static const bool on = [] { const char* e = getenv("SSLCR_PP64"); return !e || atoi(e) != 0; }();
   if ((size_t)a.N * a.H * a.W * 64 * 2 >= ((size_t)1 << 32)) return false;       // the kernel addresses with 32-bit byte offsets
@@ -461,6 +461,19 @@ int conv_pp64_rows(const ConvArgs& a) {
   if (a.seg_images > 0) return pp64_grid(a) * 4;
   const int tiles = a.N * (a.H / 16) * (a.W / 16);
   return (tiles < device_cus() ? tiles : device_cus()) * 4;
+}
+
+template <bool XF, int OP>
+struct Pp64Inst { static std::string spell() { return kname("conv3x3_pp64_kernel", XF, OP); } };
+// the instance that serves a: f(Pp64Inst<XF, OP>{})
+template <bool XF, int OP>
+static void launch_pp(Pp64Inst<XF, OP>, dim3 grid, size_t lds, hipStream_t st, const ConvArgs& a, int tiles, int rows) {
+  hipLaunchKernelGGL((conv3x3_pp64_kernel<XF, OP>), grid, dim3(512), lds, st, a, tiles, rows);
+}
+template <class F>
+static auto pp64_pick(const ConvArgs& a, F&& f) {
+  if (a.in_scale) return f(Pp64Inst<true, 0>{});
+  return a.mask_x ? f(Pp64Inst<false, 2>{}) : (a.residual ? f(Pp64Inst<false, 1>{}) : f(Pp64Inst<false, 0>{}));
 }
 
 hipError_t launch_conv_pp64(const ConvArgs& a, hipStream_t st) {
@@ -480,16 +493,12 @@ hipError_t launch_conv_pp64(const ConvArgs& a, hipStream_t st) {
   const int grid = pp64_grid(a);
   if (a.mask_x && !a.stats) return hipErrorInvalidValue;
   const int rows = conv_pp64_rows(a);
-  if (a.in_scale) hipLaunchKernelGGL((conv3x3_pp64_kernel<true, 0>), dim3(grid), dim3(512), lds, st, a, tiles, rows);
-  else if (a.mask_x) hipLaunchKernelGGL((conv3x3_pp64_kernel<false, 2>), dim3(grid), dim3(512), lds, st, a, tiles, rows);
-  else if (a.residual) hipLaunchKernelGGL((conv3x3_pp64_kernel<false, 1>), dim3(grid), dim3(512), lds, st, a, tiles, rows);
-  else hipLaunchKernelGGL((conv3x3_pp64_kernel<false, 0>), dim3(grid), dim3(512), lds, st, a, tiles, rows);
-  return hipGetLastError();
+  return pp64_pick(a, [&](auto inst) {
+    launch_pp(inst, dim3(grid), lds, st, a, tiles, rows);
+    return hipGetLastError();
+  });
 }
 
-const char* conv_pp64_name(const ConvArgs& a) {
-  if (a.in_scale) return "sslcr::conv3x3_pp64_kernel<true, 0>";
-  return a.mask_x ? "sslcr::conv3x3_pp64_kernel<false, 2>" : (a.residual ? "sslcr::conv3x3_pp64_kernel<false, 1>" : "sslcr::conv3x3_pp64_kernel<false, 0>");
-}
+const char* conv_pp64_name(const ConvArgs& a) { return pp64_pick(a, InstName{}); }
 
 }  // namespace sslcr

@@ -448,8 +448,8 @@ bool conv_s2_ok(int dtype, const ConvArgs& a) {
   if (a.relu && !a.bias) return false;          // the output clamp lives in the EVAL instance (chosen by the bias): conv_dma takes relu without one
   if (a.out_scale && !a.bias) return false;
   if (a.seg_images > 0 && a.N % a.seg_images != 0) return false;
-  // the statistics rows are asked for without a dtype (sslcr_conv2d_partial_rows) and the fp32 mode runs these shapes on the gather
-  // kernel: served only where that kernel's row count is this one's (M / 64: its 128-pixel tiles, M >= 2048)
+  // the statistics rows are asked for without a dtype (ConvPlan::rows of the bf16 plan, conv_route.cpp) and the fp32 mode runs these
+  // shapes on the gather kernel: served only where that route's rows are this one's (M / 64: its 128-pixel tiles, M >= 2048)
   if ((long)a.N * a.PH * a.PW < 2048) return false;
   return true;
 }
@@ -467,7 +467,10 @@ bool conv_s2_pair_ok(int dtype, const ConvArgs& a, const ConvArgs& d) {
 int conv_s2_rows(const ConvArgs& a) { return a.N * (a.PH / 16) * (a.PW / 16) * 4; }
 
 template <bool PAIR, bool EVAL>
-static hipError_t launch_s2(const ConvArgs& a, const ConvArgs& d, hipStream_t st) {
+struct S2Inst { static std::string spell() { return kname("conv_s2_kernel", PAIR, EVAL); } };
+
+template <bool PAIR, bool EVAL>
+static hipError_t launch_s2(S2Inst<PAIR, EVAL>, const ConvArgs& a, const ConvArgs& d, hipStream_t st) {
   const size_t lds = 3 * 289 * 128 + 3 * 128 * 128 + (EVAL ? 4 * 128 * sizeof(float) : 0);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
   auto kern = conv_s2_kernel<PAIR, EVAL>;
@@ -487,17 +490,18 @@ static hipError_t launch_s2(const ConvArgs& a, const ConvArgs& d, hipStream_t st
   return hipGetLastError();
 }
 
-// d == nullptr: the 3x3 / 2 conv alone
-hipError_t launch_conv_s2(const ConvArgs& a, const ConvArgs* d, hipStream_t st) {
+// the instance: f(S2Inst<PAIR, EVAL>{}) -- the bias selects the EVAL epilogue
+template <class F>
+static auto s2_pick(const ConvArgs& a, bool pair, F&& f) {
   const bool eval = a.bias != nullptr;
-  if (d) return eval ? launch_s2<true, true>(a, *d, st) : launch_s2<true, false>(a, *d, st);
-  return eval ? launch_s2<false, true>(a, a, st) : launch_s2<false, false>(a, a, st);
+  if (pair) return eval ? f(S2Inst<true, true>{}) : f(S2Inst<true, false>{});
+  return eval ? f(S2Inst<false, true>{}) : f(S2Inst<false, false>{});
 }
 
-const char* conv_s2_name(const ConvArgs& a, bool pair) {
-  const bool eval = a.bias != nullptr;
-  if (pair) return eval ? "sslcr::conv_s2_kernel<true, true>" : "sslcr::conv_s2_kernel<true, false>";
-  return eval ? "sslcr::conv_s2_kernel<false, true>" : "sslcr::conv_s2_kernel<false, false>";
+// d == nullptr: the 3x3 / 2 conv alone
+hipError_t launch_conv_s2(const ConvArgs& a, const ConvArgs* d, hipStream_t st) {
+  return s2_pick(a, d != nullptr, [&](auto inst) { return launch_s2(inst, a, d ? *d : a, st); });
 }
+const char* conv_s2_name(const ConvArgs& a, bool pair) { return s2_pick(a, pair, InstName{}); }
 
 }  // namespace sslcr

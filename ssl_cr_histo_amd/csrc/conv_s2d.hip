@@ -313,6 +313,7 @@ hipError_t launch_conv_s2d(const ConvArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-const char* conv_s2d_name() { return "sslcr::conv_s2d_kernel"; }
+struct S2dInst { static std::string spell() { return kname("conv_s2d_kernel"); } };
+const char* conv_s2d_name() { return InstName{}(S2dInst{}); }
 
 }  // namespace sslcr

@@ -235,7 +235,10 @@ static bool wgrad_wide(int dtype, const WgradArgs& a) {
 }
 
 template <typename T, int TAPS, int KH>
-static hipError_t launch_w(const WgradArgs& a, hipStream_t st) {
+struct WgradInst { static std::string spell() { return kname("wgrad_kernel", ktype<T>(), TAPS, KH); } };
+
+template <typename T, int TAPS, int KH>
+static hipError_t launch_w(WgradInst<T, TAPS, KH>, const WgradArgs& a, hipStream_t st) {
   constexpr int PS = Elem<T>::DT == DT_BF16 ? 32 : 16;
   const int M = a.N * a.OH * a.OW;
   const int total_steps = cdiv(M, PS);
@@ -283,32 +286,17 @@ hipError_t launch_probe_tr16(const uint16_t* in, const int* byte_addr, uint16_t*
   return hipGetLastError();
 }
 
-const char* wgrad_kernel_name(int dtype, const WgradArgs& a) {
-  const bool bf = dtype == DT_BF16;
-  const int tw = wgrad_halo_tw(a);
-  const bool wide = bf && a.K % 128 == 0;          // the 128-kout block, 8-wave form (wgrad_halo.hip)
-  if (tw && wgrad_dma_used(dtype, a)) {
-    const bool xf = a.in_scale != nullptr;
-    if (tw == 16) return xf ? "sslcr::wgrad3x3_dma_kernel<16, true>" : "sslcr::wgrad3x3_dma_kernel<16, false>";
-    return xf ? "sslcr::wgrad3x3_dma_kernel<8, true>" : "sslcr::wgrad3x3_dma_kernel<8, false>";
-  }
-  if (tw == 16) return bf ? (wide ? "sslcr::wgrad3x3_halo_kernel<unsigned short, 16, 2>" : "sslcr::wgrad3x3_halo_kernel<unsigned short, 16, 1>") : "sslcr::wgrad3x3_halo_kernel<float, 16, 1>";
-  if (tw == 8) return bf ? (wide ? "sslcr::wgrad3x3_halo_kernel<unsigned short, 8, 2>" : "sslcr::wgrad3x3_halo_kernel<unsigned short, 8, 1>") : "sslcr::wgrad3x3_halo_kernel<float, 8, 1>";
-  if (wgrad_s2_ok(dtype, a)) return a.OW % 16 == 0 ? "sslcr::wgrad_s2_kernel<16>" : "sslcr::wgrad_s2_kernel<8>";
-  const bool kw = wgrad_wide(dtype, a);
-  if (a.R == 3) return bf ? (kw ? "sslcr::wgrad_kernel<unsigned short, 9, 2>" : "sslcr::wgrad_kernel<unsigned short, 9, 1>") : "sslcr::wgrad_kernel<float, 9, 1>";
-  return bf ? (kw ? "sslcr::wgrad_kernel<unsigned short, 1, 2>" : "sslcr::wgrad_kernel<unsigned short, 1, 1>") : "sslcr::wgrad_kernel<float, 1, 1>";
-}
-
-hipError_t launch_wgrad(int dtype, const WgradArgs& a, hipStream_t st) {
-  const int tw = wgrad_halo_tw(a);
-  if (tw) return launch_wgrad_halo(dtype, a, tw, st);
-  if (a.seg_images > 0 && a.seg_images < a.N) return hipErrorInvalidValue;      // per-segment prologue: halo kernel only
-  if (wgrad_s2_ok(dtype, a)) return launch_wgrad_s2(a, st);                     // 3x3 / 2 on 4x16-tileable output maps: parity-plane halo form
+// the instance that serves a: f(WgradInst<T, TAPS, KH>{})
+template <class F>
+static auto wgrad_pick(int dtype, const WgradArgs& a, F&& f) {
   const bool three = a.R == 3;
-  if (wgrad_wide(dtype, a)) return three ? launch_w<bf16_t, 9, 2>(a, st) : launch_w<bf16_t, 1, 2>(a, st);
-  if (dtype == DT_BF16) return three ? launch_w<bf16_t, 9, 1>(a, st) : launch_w<bf16_t, 1, 1>(a, st);
-  return three ? launch_w<float, 9, 1>(a, st) : launch_w<float, 1, 1>(a, st);
+  if (wgrad_wide(dtype, a)) return three ? f(WgradInst<bf16_t, 9, 2>{}) : f(WgradInst<bf16_t, 1, 2>{});
+  if (dtype == DT_BF16) return three ? f(WgradInst<bf16_t, 9, 1>{}) : f(WgradInst<bf16_t, 1, 1>{});
+  return three ? f(WgradInst<float, 9, 1>{}) : f(WgradInst<float, 1, 1>{});
 }
+hipError_t launch_wgrad_generic(int dtype, const WgradArgs& a, hipStream_t st) {
+  return wgrad_pick(dtype, a, [&](auto inst) { return launch_w(inst, a, st); });
+}
+const char* wgrad_generic_name(int dtype, const WgradArgs& a) { return wgrad_pick(dtype, a, InstName{}); }
 
 }  // namespace sslcr

@@ -328,15 +328,16 @@ hipError_t profiled(sslcr_ctx* c, int slot, hipStream_t st, Book&& book, Launch&
   return e;
 }
 hipError_t prof_conv(sslcr_ctx* c, int dt, const ConvArgs& a, hipStream_t st) {
+  const ConvPlan plan = conv_plan(dt, a);
   auto book = [&](ProfRec& r) {
     const double es = c->esz();
     const double rs = a.tap_mask ? (double)__builtin_popcount(a.tap_mask) : (double)a.R * a.S;
     const double M = (double)a.N * a.PH * a.PW, src = (double)a.N * a.H * a.W;
     r.flops = a.transposed ? 2.0 * src * a.C * a.K * rs : 2.0 * M * a.K * a.C * rs;
     r.bytes = (src * a.C + (double)a.K * rs * a.C + M * a.K * (a.residual ? 2.0 : 1.0) * (a.accumulate ? 2.0 : 1.0)) * es;
-    r.name = conv_kernel_name(dt, a);
+    r.name = plan.name;
   };
-  return profiled(c, 0, st, book, [&] { return launch_conv(dt, a, st); });
+  return profiled(c, 0, st, book, [&] { return launch_conv(dt, a, plan, st); });
 }
 // a downsampling block's conv1 (3x3 / 2) and 1x1 / 2 projection of one input in one launch (conv_s2.hip)
 hipError_t prof_conv_pair(sslcr_ctx* c, const ConvArgs& a, const ConvArgs& d, hipStream_t st) {
@@ -377,15 +378,19 @@ hipError_t prof_conv_fwd(sslcr_ctx* c, int dt, const ConvArgs& a_in, const ConvL
   return profiled(c, 0, st, book, [&] { return launch_conv_fp8(a, q, st); });
 }
 hipError_t prof_wgrad(sslcr_ctx* c, int dt, const WgradArgs& a, hipStream_t st) {
+  const WgradPlan plan = wgrad_plan(dt, a);
   auto book = [&](ProfRec& r) {
     const double es = c->esz();
     const double M = (double)a.N * a.OH * a.OW;
     r.flops = 2.0 * M * a.K * a.C * a.R * a.S;
     r.bytes = ((double)a.N * a.H * a.W * a.C + M * a.K) * es + (double)a.K * a.R * a.S * a.C * 4.0;
-    r.name = wgrad_kernel_name(dt, a);
+    r.name = plan.name;
   };
-  return profiled(c, 1, st, book, [&] { return launch_wgrad(dt, a, st); });
+  return profiled(c, 1, st, book, [&] { return launch_wgrad(dt, a, plan, st); });
 }
+
+// the 16x16-tile kernels (conv3x3_h16 / conv3x3_pp64): the ones with the BatchNorm-backward front end (sslcr_conv_desc.mask_x)
+inline bool tile16(const ConvPlan& p) { return p.route == ConvRoute::H16 || p.route == ConvRoute::PP64; }
 
 constexpr int kMaxSeg = 3;      // TripletNet branches run as segments of one launch (backbone_forward_train_segments)
 const int kBlockCfg[8][3] ={{64, 64, 1}, {64, 64, 1}, {64, 128, 2}, {128, 128, 1}, {128, 256, 2}, {256, 256, 1}, {256, 512, 2}, {512, 512, 1}};
@@ -630,11 +635,15 @@ ConvArgs conv_args(const ConvL& L, const void* x, const void* w, void* y, int N,
   return a;
 }
 
-int ensure_partials(sslcr_ctx* c, const ConvArgs& a, float** out, int* rows, bool fp8 = false) {
-  *rows = fp8 ? conv_fp8_rows(a) : conv_partials_rows(a);
-  TRYI(c->partials.ensure((size_t)*rows * 2 * a.K * sizeof(float)));
+// the statistics buffer of a launch that writes nrows partial rows
+int partials_rows(sslcr_ctx* c, int nrows, int K, float** out) {
+  TRYI(c->partials.ensure((size_t)nrows * 2 * K * sizeof(float)));
   *out = (float*)c->partials.p;
   return 0;
+}
+int ensure_partials(sslcr_ctx* c, const ConvArgs& a, float** out, int* rows, bool fp8 = false) {
+  *rows = fp8 ? conv_fp8_rows(a) : conv_plan(DT_BF16, a).rows;      // (asked before the dtype's launch: the routes tile alike in both)
+  return partials_rows(c, *rows, a.K, out);
 }
 
 struct Dims {
@@ -768,8 +777,9 @@ int forward_blocks(sslcr_net* n, PassState& ps, int N, int H, int W, int replay,
       paired = !use_fp8(c, B.c1, a1) && conv_s2_pair_ok(dt, t1, td);
     }
     if (paired) {
-      if (segs && (!conv_segments_ok(dt, a1) || !conv_segments_ok(dt, ad))) return fail("forward_blocks: the paired stride-2 launch has no segment form here");
-      rows = conv_partials_rows(a1);
+      const ConvPlan p1 = conv_plan(dt, a1);
+      if (segs && (!p1.seg_ok || !conv_plan(dt, ad).seg_ok)) return fail("forward_blocks: the paired stride-2 launch has no segment form here");
+      rows = p1.rows;
       const size_t rb = (size_t)rows * 2 * a1.K * sizeof(float);
       TRYI(c->partials.ensure(2 * rb));
       part = (float*)c->partials.p;
@@ -780,7 +790,7 @@ int forward_blocks(sslcr_net* n, PassState& ps, int N, int H, int W, int replay,
     } else if (B.has_ds) {
       // two launches (fp32, layer4.0's 8x8 maps, ragged shapes), the projection right behind conv1 so that the two BatchNorms still
       // share one all-reduce of their sums when BatchNorm is synced across ranks
-      const int rows1 = conv_partials_rows(a1), rowsd = conv_partials_rows(ad);
+      const int rows1 = conv_plan(DT_BF16, a1).rows, rowsd = conv_plan(DT_BF16, ad).rows;
       const size_t rb1 = (((size_t)rows1 * 2 * a1.K * sizeof(float)) + 255) & ~(size_t)255;
       TRYI(c->partials.ensure(rb1 + (size_t)rowsd * 2 * ad.K * sizeof(float)));
       a1.stats = (float*)c->partials.p;
@@ -856,13 +866,14 @@ bool segments_servable(sslcr_net* n, int N, int H, int W) {
     a1.seg_images = N;
     ConvArgs a2 = conv_args(B.c2, nullptr, nullptr, nullptr, 3 * N, oh, ow);
     a2.seg_images = N; a2.in_scale = c->ones; a2.in_shift = c->zeros;
-    if (!conv_segments_ok(c->dtype, a1) || !conv_segments_ok(c->dtype, a2)) return false;
+    const ConvPlan p1 = conv_plan(c->dtype, a1), p2 = conv_plan(c->dtype, a2);
+    if (!p1.seg_ok || !p2.seg_ok) return false;
     if (B.has_ds) {
       ConvArgs ad = conv_args(B.ds, nullptr, nullptr, nullptr, 3 * N, xh, xw);
       ad.seg_images = N;
-      if (!conv_segments_ok(c->dtype, ad)) return false;
+      if (!conv_plan(c->dtype, ad).seg_ok) return false;
     }
-    if (conv_partials_rows(a1) % 3 || conv_partials_rows(a2) % 3) return false;
+    if (p1.rows % 3 || p2.rows % 3) return false;
     xh = oh; xw = ow;
   }
   return true;
@@ -1291,7 +1302,8 @@ struct Backward {
     seg_dg = false;
     if (npass > 1 && segments_on() && !c->prof.on) {
       const ConvArgs m = conv2_dgrad_segments_args(nullptr, nullptr);
-      seg_dg = conv_h16_ok(dt, m) && conv_segments_ok(dt, m) && conv_partials_rows(m) % npass == 0;
+      const ConvPlan p = conv_plan(dt, m);
+      seg_dg = tile16(p) && p.seg_ok && p.rows % npass == 0;
     }
     // the elementwise BatchNorm-backward passes of the branches as segments of one launch (sslcr_bn_bwd_desc.nseg): the passes'
     // saved tensors and scratch tensors are contiguous, their saved statistics bn_stride floats apart, their sums in
@@ -1382,8 +1394,10 @@ struct Backward {
     ConvArgs a = dgrad3x3_s1_args(B->c2, buf(kRaw2, p, so), buf(kAct1, p, so), N, oh, ow);
     const ConvArgs m = with_bn1_mask(a, P[p].blk[i].raw1, P[p].bn[B->b1.bidx]);
     float* rows = nullptr; int nrows = 0;
-    if (conv_h16_ok(dt, m)) {
-      TRYI(ensure_partials(c, m, &rows, &nrows));
+    const ConvPlan pm = conv_plan(dt, m);
+    if (tile16(pm)) {
+      nrows = pm.rows;
+      TRYI(partials_rows(c, nrows, m.K, &rows));
       a = m;
       a.stats = rows;
     }
@@ -1438,8 +1452,7 @@ struct Backward {
       // one launch with the class on grid z where the DMA-gather kernel serves the shape, else four launches
       ConvArgs q4 = a;
       q4.pix_mul = 2; q4.PH = xh / 2; q4.PW = xw / 2; q4.par4 = 1;
-      const bool one = xh % 2 == 0 && xw % 2 == 0 && conv_dma_bp(dt, q4) != 0 && conv_dma_bp(DT_BF16, q4) == conv_dma_bp(dt, q4) &&
-                       conv_halo_tw(dt, q4) == 0;
+      const bool one = xh % 2 == 0 && xw % 2 == 0 && conv_plan(dt, q4).par4_one_launch;
       if (one) TRY(prof_conv(c, dt, q4, st));
       for (int par = 0; par < (one ? 0 : 4); ++par) {
         ConvArgs q = a;

@@ -1,6 +1,8 @@
 // Internal kernel launch interface of the engine (host side).  The argument structs ARE the C-ABI
 // descriptors of include/sslcr.h.  Every launcher is asynchronous on `st`; no allocation, no sync.
 #pragma once
+#include <string>
+
 #include "common.hpp"
 #include "../../include/sslcr.h"
 
@@ -22,28 +24,80 @@ using PackArgs = sslcr_pack_desc;
 using Fp8Args = sslcr_fp8_desc;
 using PackFp8Args = sslcr_pack_fp8_desc;
 
-// conv_igemm.hip
-hipError_t launch_conv(int dtype, const ConvArgs& a, hipStream_t st);
-int conv_tile_bp(const ConvArgs& a);
-const char* conv_kernel_name(int dtype, const ConvArgs& a);
-const char* wgrad_kernel_name(int dtype, const WgradArgs& a);
-int conv_partials_rows(const ConvArgs& a);
-bool conv_segments_ok(int dtype, const ConvArgs& a);
+// ---- kernel names, in the profiler's spelling ("sslcr::conv_dma_kernel<unsigned short, 128, 128>"): every family has one tag type per
+// template instance, which spells the name from its template arguments; a family's *_pick() hands the tag of the instance it chooses to
+// a callable -- one that launches it, or InstName, which keeps the string in a function-local static per instance -- so that the
+// launch and the reported name cannot be two decisions
+inline std::string karg(const char* s) { return s; }
+inline std::string karg(bool v) { return v ? "true" : "false"; }
+inline std::string karg(int v) { return std::to_string(v); }
+template <class... A>
+std::string kname(const char* kernel, A... args) {
+  std::string s = std::string("sslcr::") + kernel;
+  const char* sep = "<";
+  ((s += sep + karg(args), sep = ", "), ...);
+  return sizeof...(A) ? s + ">" : s;
+}
+template <typename T> constexpr const char* ktype() { return sizeof(T) == 2 ? "unsigned short" : "float"; }
+struct InstName {
+  template <class I> const char* operator()(I) const {
+    static const std::string s = I::spell();
+    return s.c_str();
+  }
+};
+
+// conv_route.cpp: which kernel serves a descriptor, decided ONCE -- the launch, the reported name, the statistics rows and the segment
+// check all read this plan (and the engine, where it has to know the route)
+enum class ConvRoute { H16, PP64, HALO256, HALO, S2, S2D, DMA, IGEMM };
+struct ConvPlan {
+  ConvRoute route;      // the family the descriptor maps to (also where !ok: the name has always been answered for those)
+  int param;            // H16 / HALO256: tile mode (16 | 8); HALO: tile width; DMA: pixel block; else 0
+  int rows;             // partial-statistics rows the launch writes (-1: a grid split among segments, and seg_images > N)
+  bool seg_ok;          // the descriptor's seg_images (0 = none) has a form on this route
+  bool ok;              // launch_conv() takes it
+  bool par4_one_launch; // a par4 descriptor (the stride-2 dgrad's four parity classes at once) that conv_dma serves -- itself, or conv_s2d
+                        // in its place; where conv_dma would not, the engine keeps its four per-parity launches, conv_s2d or not
+  const char* name;     // the template instance, as the profiler prints it (minus the argument list)
+};
+ConvPlan conv_plan(int dtype, const ConvArgs& a);
+hipError_t launch_conv(int dtype, const ConvArgs& a, const ConvPlan& p, hipStream_t st);
+inline hipError_t launch_conv(int dtype, const ConvArgs& a, hipStream_t st) { return launch_conv(dtype, a, conv_plan(dtype, a), st); }
+inline const char* conv_kernel_name(int dtype, const ConvArgs& a) { return conv_plan(dtype, a).name; }
+inline int conv_partials_rows(const ConvArgs& a) { return conv_plan(DT_BF16, a).rows; }      // (the public call has no dtype)
+inline bool conv_segments_ok(int dtype, const ConvArgs& a) { return conv_plan(dtype, a).seg_ok; }
+enum class WgradRoute { HALO, HALO_DMA, S2, GENERIC };
+struct WgradPlan {
+  WgradRoute route;
+  int tw, KH;           // HALO / HALO_DMA: tile width and 64-kout halves per workgroup (else 0)
+  bool ok;              // launch_wgrad() takes it
+  const char* name;
+};
+WgradPlan wgrad_plan(int dtype, const WgradArgs& a);
+hipError_t launch_wgrad(int dtype, const WgradArgs& a, const WgradPlan& p, hipStream_t st);
+inline hipError_t launch_wgrad(int dtype, const WgradArgs& a, hipStream_t st) { return launch_wgrad(dtype, a, wgrad_plan(dtype, a), st); }
+inline const char* wgrad_kernel_name(int dtype, const WgradArgs& a) { return wgrad_plan(dtype, a).name; }
+inline bool wgrad_dma_used(int dtype, const WgradArgs& a) { return wgrad_plan(dtype, a).route == WgradRoute::HALO_DMA; }
 int device_cus();      // compute units of the current device (asked once per process, thread-safely; 256 if the query fails)
+// conv_igemm.hip: the generic gather kernel
+int conv_igemm_rows(const ConvArgs& a);
+hipError_t launch_igemm(int dtype, const ConvArgs& a, hipStream_t st);
+const char* conv_igemm_name(int dtype, const ConvArgs& a);
 // conv_halo.hip
 int conv_halo_tw(int dtype, const ConvArgs& a);
 int conv_halo_tiles(const ConvArgs& a, int tw);
 hipError_t launch_conv_halo(int dtype, const ConvArgs& a, int tw, hipStream_t st);
+const char* conv_halo_name(int dtype, const ConvArgs& a, int tw);
 // conv_halo256.hip
 int conv_halo256_mode(int dtype, const ConvArgs& a);
 int conv_halo256_tiles(const ConvArgs& a, int mode);
 hipError_t launch_conv_halo256(int dtype, const ConvArgs& a, int mode, hipStream_t st);
-// conv_h16.hip
-bool conv_h16_ok(int dtype, const ConvArgs& a);
+const char* conv_halo256_name(int dtype, const ConvArgs& a, int mode);
+// conv_h16.hip (mode: 16 | 8, 0 = not served; q = the conv3x3_halo256 tiling both dtypes agree on)
+int conv_h16_mode(const ConvArgs& a, int q);
 int conv_h16_rows(const ConvArgs& a);
-hipError_t launch_conv_h16(int dtype, const ConvArgs& a, hipStream_t st);
-const char* conv_h16_name(int dtype, const ConvArgs& a);
-// conv_pp64.hip: ping-pong form of the bf16 64 -> 64 resident-filter shape (same partial-row count as conv_h16_rows)
+hipError_t launch_conv_h16(int dtype, const ConvArgs& a, int mode, hipStream_t st);
+const char* conv_h16_name(int dtype, const ConvArgs& a, int mode);
+// conv_pp64.hip: ping-pong form of the bf16 64 -> 64 resident-filter shape, for the descriptors conv_h16 serves
 bool conv_pp64_ok(int dtype, const ConvArgs& a);
 hipError_t launch_conv_pp64(const ConvArgs& a, hipStream_t st);
 const char* conv_pp64_name(const ConvArgs& a);
@@ -70,8 +124,9 @@ const char* conv_fp8_name(const ConvArgs& a);
 hipError_t launch_conv_fp8(const ConvArgs& a, const Fp8Args& q, hipStream_t st);
 hipError_t launch_pack_fp8(const PackFp8Args& a, hipStream_t st);
 hipError_t launch_fp8_scale_update(float* slots, int n, hipStream_t st);
-// conv_wgrad.hip
-hipError_t launch_wgrad(int dtype, const WgradArgs& a, hipStream_t st);
+// conv_wgrad.hip: the generic gather form
+hipError_t launch_wgrad_generic(int dtype, const WgradArgs& a, hipStream_t st);
+const char* wgrad_generic_name(int dtype, const WgradArgs& a);
 int wgrad_halo_tw(const WgradArgs& a);
 // per-stream scratch for partial results that a follow-up launch on the SAME stream folds in a fixed order: the accumulator slabs of
 // the weight-gradient kernels (wgrad_fold_kernel) and the per-workgroup rows of the BatchNorm-backward reduce pass (bn_bwd_sums_kernel);
@@ -80,15 +135,18 @@ void* stream_scratch(hipStream_t st, size_t bytes);
 void stream_scratch_release();      // frees every stream's scratch (sslcr_destroy, after a device synchronise)
 hipError_t launch_wgrad_fold(const void* slabs, float* dw, int C, int gx, int gy, int splits, int taps, int kh_n, hipStream_t st);
 hipError_t launch_stem_wgrad_fold(const void* slabs, float* dw, int nwg, hipStream_t st);
-hipError_t launch_wgrad_halo(int dtype, const WgradArgs& a, int tw, hipStream_t st);
+int wgrad_halo_splits(const WgradArgs& a, int tw, int kh);      // pixel splits of the halo launch (the DMA form wants more than one)
+hipError_t launch_wgrad_halo(int dtype, const WgradArgs& a, const WgradPlan& p, hipStream_t st);
+const char* wgrad_halo_name(int dtype, int tw, int kh);
 // wgrad_dma.hip: the halo kernel's 128-kout bf16 instances with the operands staged by LDS DMA (same tiles, slabs and bits)
 bool wgrad_dma_ok(int dtype, const WgradArgs& a, int splits);
-bool wgrad_dma_used(int dtype, const WgradArgs& a);
+const char* wgrad_dma_name(const WgradArgs& a, int tw);
 hipError_t launch_wgrad_dma(const WgradArgs& a, int tw, int tps, int ntiles, int splits, void* slabs, hipStream_t st);
 hipError_t launch_probe_tr16(const uint16_t* in, const int* byte_addr, uint16_t* out, hipStream_t st);
 // wgrad_s2.hip: 3x3 / 2 weight gradient with the input region staged once per tile as parity planes (bf16, no producer transform)
 bool wgrad_s2_ok(int dtype, const WgradArgs& a);
 hipError_t launch_wgrad_s2(const WgradArgs& a, hipStream_t st);
+const char* wgrad_s2_name(const WgradArgs& a);
 // stem.hip
 hipError_t launch_stem(int dtype, const StemArgs& a, hipStream_t st);
 int stem_partials_rows(const StemArgs& a);

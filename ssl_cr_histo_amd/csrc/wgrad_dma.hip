@@ -385,7 +385,10 @@ bool wgrad_dma_ok(int dtype, const WgradArgs& a, int splits) {
 }
 
 template <int TW, bool XF>
-static hipError_t launch_wd_t(const WgradArgs& a, int tps, int ntiles, int splits, f32x4_t* slabs, hipStream_t st) {
+struct WgradDmaInst { static std::string spell() { return kname("wgrad3x3_dma_kernel", TW, XF); } };
+
+template <int TW, bool XF>
+static hipError_t launch_wd_t(WgradDmaInst<TW, XF>, const WgradArgs& a, int tps, int ntiles, int splits, f32x4_t* slabs, hipStream_t st) {
   constexpr int NI = 128 / (8 * TW), PITCH = TW == 16 ? 24 : 16;
   const int nseg = a.seg_images > 0 ? a.N / a.seg_images : 1;
   const size_t lds = (size_t)2 * (256 + NI * 10 * PITCH) * 128 + 512 * nseg;
@@ -402,11 +405,16 @@ static hipError_t launch_wd_t(const WgradArgs& a, int tps, int ntiles, int split
   return hipGetLastError();
 }
 
-hipError_t launch_wgrad_dma(const WgradArgs& a, int tw, int tps, int ntiles, int splits, void* slabs, hipStream_t st) {
-  f32x4_t* s = reinterpret_cast<f32x4_t*>(slabs);
+// the instance: f(WgradDmaInst<TW, XF>{})
+template <class F>
+static auto wd_pick(const WgradArgs& a, int tw, F&& f) {
   const bool xf = a.in_scale != nullptr;
-  if (tw == 16) return xf ? launch_wd_t<16, true>(a, tps, ntiles, splits, s, st) : launch_wd_t<16, false>(a, tps, ntiles, splits, s, st);
-  return xf ? launch_wd_t<8, true>(a, tps, ntiles, splits, s, st) : launch_wd_t<8, false>(a, tps, ntiles, splits, s, st);
+  if (tw == 16) return xf ? f(WgradDmaInst<16, true>{}) : f(WgradDmaInst<16, false>{});
+  return xf ? f(WgradDmaInst<8, true>{}) : f(WgradDmaInst<8, false>{});
 }
+hipError_t launch_wgrad_dma(const WgradArgs& a, int tw, int tps, int ntiles, int splits, void* slabs, hipStream_t st) {
+  return wd_pick(a, tw, [&](auto inst) { return launch_wd_t(inst, a, tps, ntiles, splits, reinterpret_cast<f32x4_t*>(slabs), st); });
+}
+const char* wgrad_dma_name(const WgradArgs& a, int tw) { return wd_pick(a, tw, InstName{}); }
 
 }  // namespace sslcr

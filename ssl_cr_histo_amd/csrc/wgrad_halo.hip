@@ -471,15 +471,14 @@ static int wh_splits(const WgradArgs& a, int TW, int KH, int* tps_out, int* ntil
   if (ntiles_out) *ntiles_out = ntiles;
   return cdiv(ntiles, tps);
 }
-// does the DMA form (wgrad_dma.hip) serve this launch?
-bool wgrad_dma_used(int dtype, const WgradArgs& a) {
-  const int tw = wgrad_halo_tw(a);
-  if (!tw || dtype != DT_BF16 || a.K % 128 != 0) return false;
-  return wgrad_dma_ok(dtype, a, wh_splits(a, tw, 2, nullptr, nullptr));
-}
+int wgrad_halo_splits(const WgradArgs& a, int tw, int kh) { return wh_splits(a, tw, kh, nullptr, nullptr); }
 
 template <typename T, int TW, int KH>
-static hipError_t launch_wh(const WgradArgs& a, hipStream_t st) {
+struct WgradHaloInst { static std::string spell() { return kname("wgrad3x3_halo_kernel", ktype<T>(), TW, KH); } };
+
+// dma: the operands go to LDS by DMA (WgradRoute::HALO_DMA, KH = 2 in bf16: wgrad_dma.hip) -- same tiles, slabs and bits
+template <typename T, int TW, int KH>
+static hipError_t launch_wh(WgradHaloInst<T, TW, KH>, const WgradArgs& a, bool dma, hipStream_t st) {
   constexpr bool BF = Elem<T>::DT == DT_BF16;
   constexpr int NI = 128 / (8 * TW);
   int tps, ntiles;
@@ -502,7 +501,7 @@ static hipError_t launch_wh(const WgradArgs& a, hipStream_t st) {
     slabs = reinterpret_cast<f32x4_t*>(stream_scratch(st, (size_t)gx * gy * splits * 36 * 256 * KH * sizeof(f32x4_t)));
     if (!slabs) return hipErrorOutOfMemory;        // (no atomic path to fall back to: its summation order would differ)
   }
-  if (KH == 2 && BF && wgrad_dma_ok(Elem<T>::DT, a, splits)) {      // operands by LDS DMA, same tiles / slabs / bits (wgrad_dma.hip)
+  if (dma) {
     hipError_t e = launch_wgrad_dma(a, TW, tps, ntiles, splits, slabs, st);
     if (e != hipSuccess) return e;
     return launch_wgrad_fold(slabs, a.dw, a.C, gx, gy, splits, 9, KH, st);
@@ -512,12 +511,18 @@ static hipError_t launch_wh(const WgradArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_wgrad_halo(int dtype, const WgradArgs& a, int tw, hipStream_t st) {
+// the instance of (tile width, kout halves): f(WgradHaloInst<T, TW, KH>{})
+template <class F>
+static auto wh_pick(int dtype, int tw, int kh, F&& f) {
   if (dtype == DT_BF16) {
-    if (a.K % 128 == 0) return tw == 16 ? launch_wh<bf16_t, 16, 2>(a, st) : launch_wh<bf16_t, 8, 2>(a, st);
-    return tw == 16 ? launch_wh<bf16_t, 16, 1>(a, st) : launch_wh<bf16_t, 8, 1>(a, st);
+    if (kh == 2) return tw == 16 ? f(WgradHaloInst<bf16_t, 16, 2>{}) : f(WgradHaloInst<bf16_t, 8, 2>{});
+    return tw == 16 ? f(WgradHaloInst<bf16_t, 16, 1>{}) : f(WgradHaloInst<bf16_t, 8, 1>{});
   }
-  return tw == 16 ? launch_wh<float, 16, 1>(a, st) : launch_wh<float, 8, 1>(a, st);
+  return tw == 16 ? f(WgradHaloInst<float, 16, 1>{}) : f(WgradHaloInst<float, 8, 1>{});
 }
+hipError_t launch_wgrad_halo(int dtype, const WgradArgs& a, const WgradPlan& p, hipStream_t st) {
+  return wh_pick(dtype, p.tw, p.KH, [&](auto inst) { return launch_wh(inst, a, p.route == WgradRoute::HALO_DMA, st); });
+}
+const char* wgrad_halo_name(int dtype, int tw, int kh) { return wh_pick(dtype, tw, kh, InstName{}); }
 
 }  // namespace sslcr

@@ -229,6 +229,19 @@ bool wgrad_s2_ok(int dtype, const WgradArgs& a) {
   return true;
 }
 
+template <int TW>
+struct WgradS2Inst { static std::string spell() { return kname("wgrad_s2_kernel", TW); } };
+// the instance: f(WgradS2Inst<TW>{}) -- 16-wide tiles, or whole rows of an 8-wide output map
+template <class F>
+static auto ws2_pick(const WgradArgs& a, F&& f) {
+  return a.OW % 16 == 0 ? f(WgradS2Inst<16>{}) : f(WgradS2Inst<8>{});
+}
+template <int TW>
+static void launch_ws2(WgradS2Inst<TW>, dim3 grid, size_t lds, hipStream_t st, const WgradArgs& a, int tps, int ntiles, f32x4_t* slabs) {
+  hipLaunchKernelGGL(wgrad_s2_kernel<TW>, grid, dim3(512), lds, st, a, tps, ntiles, slabs);
+}
+const char* wgrad_s2_name(const WgradArgs& a) { return ws2_pick(a, InstName{}); }
+
 hipError_t launch_wgrad_s2(const WgradArgs& a, hipStream_t st) {
   const bool w8 = a.OW % 16 != 0;
   const int ntiles = w8 ? a.N * (a.OH / 8) : a.N * (a.OH / 4) * (a.OW / 16);
@@ -254,8 +267,7 @@ hipError_t launch_wgrad_s2(const WgradArgs& a, hipStream_t st) {
     slabs = reinterpret_cast<f32x4_t*>(stream_scratch(st, (size_t)gx * gy * splits * 36 * 512 * sizeof(f32x4_t)));
     if (!slabs) return hipErrorOutOfMemory;
   }
-  if (w8) hipLaunchKernelGGL(wgrad_s2_kernel<8>, dim3(gx * gy * splits), dim3(512), lds, st, a, tps, ntiles, slabs);
-  else hipLaunchKernelGGL(wgrad_s2_kernel<16>, dim3(gx * gy * splits), dim3(512), lds, st, a, tps, ntiles, slabs);
+  ws2_pick(a, [&](auto inst) { launch_ws2(inst, dim3(gx * gy * splits), lds, st, a, tps, ntiles, slabs); return 0; });
   if (slabs) return launch_wgrad_fold(slabs, a.dw, a.C, gx, gy, splits, 9, 2, st);
   return hipGetLastError();
 }

@@ -119,3 +119,13 @@ def test_every_truncated_profile_name_has_a_row():
             found += 1
             assert any(t.startswith(prefix) for t in table), f"no route row starts with {prefix!r}"
     assert found >= 15
+
+
+@pytest.mark.parametrize("shape, seg", [((1, 16, 16, 64, 64, 3, 1, 1), 2), ((1, 16, 16, 128, 128, 3, 1, 1), 2), ((4, 8, 8, 512, 512, 3, 1, 1), 8)],
+                         ids=["pp64", "h16", "h16-4img"])
+def test_segment_larger_than_the_batch_has_no_rows(lib, shape, seg):
+    """seg_images > N on the kernels whose grid is split among the segments (N / seg_images = 0 groups): no rows and no segment form --
+    the grid arithmetic behind sslcr_conv2d_partial_rows used to divide by that zero"""
+    d = conv_desc("fwd", shape, f"stats seg={seg}")
+    assert lib.sslcr_conv2d_partial_rows(d) == -1
+    assert lib.sslcr_conv2d_segments_ok(1, d) == 0

@@ -6,11 +6,7 @@
 #include <vector>
 #include "../../ssl_cr_histo_amd/csrc/conv_h16.hip"
 namespace sslcr {                                  // what conv_h16.hip takes from its neighbours
-int conv_halo256_mode(int, const ConvArgs&) { return 16; }
-bool conv_pp64_ok(int, const ConvArgs&) { return false; }
 int device_cus() { return 256; }
-hipError_t launch_conv_pp64(const ConvArgs&, hipStream_t) { return hipErrorInvalidValue; }
-const char* conv_pp64_name(const ConvArgs&) { return ""; }
 }
 using namespace sslcr;
 
@@ -49,11 +45,11 @@ int main(int argc, char** argv) {
   if (op == 3) { a.in_scale = vec; a.in_shift = vec + C; a.in_relu = 1; a.stats = stats; }
   hipEvent_t e0, e1;
   hipEventCreate(&e0); hipEventCreate(&e1);
-  for (int i = 0; i < 3; ++i) launch_conv_h16(DT_BF16, a, 0);
+  for (int i = 0; i < 3; ++i) launch_conv_h16(DT_BF16, a, 16, 0);
   hipDeviceSynchronize();
   hipEventRecord(e0);
   const int reps = 10;
-  for (int i = 0; i < reps; ++i) launch_conv_h16(DT_BF16, a, 0);
+  for (int i = 0; i < reps; ++i) launch_conv_h16(DT_BF16, a, 16, 0);
   hipEventRecord(e1);
   hipEventSynchronize(e1);
   float ms = 0;

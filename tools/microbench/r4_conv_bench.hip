@@ -8,12 +8,7 @@
 #include "../../ssl_cr_histo_amd/csrc/conv_h16.hip"
 #include "conv_r4_proto.hip"
 namespace sslcr {
-int conv_halo256_mode(int, const ConvArgs&) { return 16; }
-bool conv_pp64_ok(int, const ConvArgs&) { return false; }
 int device_cus() { return 256; }
-hipError_t launch_conv_pp64(const ConvArgs&, hipStream_t) { return hipErrorInvalidValue; }
-const char* conv_pp64_name(const ConvArgs&) { return ""; }
-int conv_pp64_rows(const ConvArgs&) { return 0; }
 }
 using namespace sslcr;
 
@@ -46,10 +41,10 @@ int main(int argc, char** argv) {
   hipEventCreate(&e0); hipEventCreate(&e1);
   float ms[2];
   for (int k = 0; k < 2; ++k) {
-    for (int i = 0; i < 3; ++i) { if (k == 0) launch_conv_h16(DT_BF16, a, 0); else launch_conv_r4(b, 0); }
+    for (int i = 0; i < 3; ++i) { if (k == 0) launch_conv_h16(DT_BF16, a, 16, 0); else launch_conv_r4(b, 0); }
     hipDeviceSynchronize();
     hipEventRecord(e0);
-    for (int i = 0; i < 10; ++i) { if (k == 0) launch_conv_h16(DT_BF16, a, 0); else launch_conv_r4(b, 0); }
+    for (int i = 0; i < 10; ++i) { if (k == 0) launch_conv_h16(DT_BF16, a, 16, 0); else launch_conv_r4(b, 0); }
     hipEventRecord(e1);
     hipEventSynchronize(e1);
     hipEventElapsedTime(&ms[k], e0, e1);
