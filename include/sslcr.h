@@ -29,8 +29,10 @@ extern "C" {
 #define SSLCR_BF16 1
 #define SSLCR_FP8 2   /* engine mode only (sslcr_create): bf16 storage and backward, fp8 e4m3 forward for the eligible 3x3 convs */
 
-/* the library round (7 here).  ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
- * 7 = sslcr_randaug_v2_slot added (nothing else changed). */
+/* the library round (8 here).  ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
+ * 7 = sslcr_randaug_v2_slot added (nothing else changed); 8 = optimizer parameter groups, AdamW and the global gradient norm
+ * (sslcr_tensor_desc.group, sslcr_opt_desc.kind 2, sslcr_optimizer_step_groups, sslcr_grad_norm, sslcr_net_optimizer_step_groups,
+ * sslcr_net_grad_norm: all additive). */
 int sslcr_version(void);
 const char* sslcr_last_error(void);
 
@@ -297,15 +299,32 @@ typedef struct sslcr_tensor_desc {
   void* w_dgrad;          /* forward pack [K][RS][C] and dgrad pack [C][RS][K] (sslcr_pack_conv layouts), element type pack_dtype */
   int pack_dtype;         /* 0 fp32, 1 bf16 */
   int dgrad_flip;         /* dgrad pack with the taps reversed (stride-1 3x3 dgrad runs as a plain conv of dY) */
+  int group;              /* library version >= 8: the tensor's row of the `groups` table (torch param_groups); 0 with the one-row entries */
 } sslcr_tensor_desc;
 typedef struct sslcr_opt_desc {
-  int kind;               /* 0 adam, 1 sgd-nesterov */
+  int kind;               /* 0 adam, 1 sgd-nesterov; library version >= 8: 2 adamw (torch.optim.AdamW: p *= 1 - lr * wd first, then the
+                             Adam update of the plain gradient -- wd never enters the moments) */
   float lr, beta1, beta2, eps, wd, momentum;
   float bc1, bc2;
   int first_step;
   float grad_scale;
 } sslcr_opt_desc;
 int sslcr_optimizer_step(const sslcr_tensor_desc* device_descs, int ntensors, int max_n, const sslcr_opt_desc* o, void* stream);
+/* library version >= 8.  The same update with one sslcr_opt_desc row per torch param group (optimizer.param_groups: per-group lr,
+ * weight_decay, betas / eps or momentum, and the bias corrections of that group's betas): tensor t takes groups[t.group], every
+ * t.group < ngroups <= SSLCR_MAX_OPT_GROUPS (a tensor whose group lies past ngroups is left unchanged).  coef_dev: NULL, or a device float every gradient is multiplied with on top of
+ * grad_scale -- out2 + 1 of sslcr_grad_norm, i.e. the `p.grad.mul_(clip_coef_clamped)` of torch.nn.utils.clip_grad_norm_ without a
+ * pass of its own. */
+#define SSLCR_MAX_OPT_GROUPS 8
+int sslcr_optimizer_step_groups(const sslcr_tensor_desc* device_descs, int ntensors, int max_n, const sslcr_opt_desc* groups, int ngroups,
+                                const float* coef_dev, void* stream);
+/* library version >= 8.  torch.nn.utils.clip_grad_norm_(params, max_norm) (norm_type 2) up to the scaling itself: the 2-norm of the
+ * n floats at g (any n >= 0, any 4-byte-aligned base) and the clamped coefficient, left on the device with no host sync:
+ *   out2[0] = (float)sqrt(sum (double)g_i^2), out2[1] = min(1, max_norm / (out2[0] + 1e-6f))    (exactly 1.0f for max_norm = +inf).
+ * partials: workspace of sslcr_grad_norm_partials() doubles.  Two launches, no atomics, a fixed summation order: the same bits every
+ * run, and the same bits on every rank that holds the same buffer. */
+int sslcr_grad_norm(const float* g, size_t n, float max_norm, double* partials, float* out2, void* stream);
+int sslcr_grad_norm_partials(void);
 int sslcr_axpby(float* p, float* q, size_t n, float alpha, int copy_back, void* stream);
 int sslcr_fill(float* p, size_t n, float v, void* stream);
 
@@ -497,6 +516,8 @@ int sslcr_net_grad(sslcr_net* net, int param_index, float* out, void* stream);  
  *        4 dRawD = gradient at the projection conv's raw output                    5 dXin  = gradient at the block input
  *        6 raw1, 7 raw2, 8 rawd (saved raw conv outputs), 9 y (block output), 10 x (block input)
  *       11..14 bn1's saved scale, shift, mean, invstd (fp32 [C]; dims = {C,1,1,1})
+ *       15..20 (library version >= 8) the train-mode shadow weights as the conv kernels read them, engine storage dtype: conv1's
+ *              forward pack [K][R][S][C] (15) and dgrad pack [C][R][S][K] (16), conv2's (17, 18), the projection's (19, 20)
  * out == NULL: only dims4 / flags are filled. */
 int sslcr_net_debug_tap(sslcr_net* net, int on);
 /* 1 when the last train-mode forward of a TripletNet ran its three branches as segments of one launch per layer
@@ -506,6 +527,24 @@ int sslcr_net_debug_tensor(sslcr_net* net, int block, int kind, void* out, size_
 /* fused multi-tensor update of every requires_grad parameter; state1/state2 = per-parameter optimizer state
  * (exp_avg/exp_avg_sq or momentum_buffer) owned by the caller, NULL entries for frozen parameters */
 int sslcr_net_optimizer_step(sslcr_net* net, const sslcr_opt_desc* o, float* const* state1, float* const* state2, void* stream);
+/* library version >= 8.  The same step for a torch optimizer with several param groups (e.g. backbone / head learning rates, no
+ * weight decay on BatchNorm and bias), torch.optim.AdamW (kind 2) and torch.nn.utils.clip_grad_norm_ in front of optimizer.step():
+ * groups[group_of_param[i]] is the row of parameter i (named_parameters() order; ignored for frozen parameters; NULL = all 0).  The
+ * descriptor table is rebuilt when the state pointers, the trainable set or the group map changed.  clip: NULL = off (the launches
+ * and the arithmetic of sslcr_net_optimizer_step); else the global 2-norm of the gradient buffer is taken on `stream` in front of
+ * the update (sslcr_grad_norm) and every gradient is scaled by min(1, max_norm / (norm + 1e-6)).  The buffer is complete at that
+ * point -- sslcr_net_backward returns with the bucket all-reduces and the side-stream weight gradients joined into its stream --
+ * so sharded ranks reduce identical buffers in the same order and hold identical bits: no further collective. */
+typedef struct sslcr_clip_desc {
+  float max_norm;
+  float* out2;            /* optional device [2]: receives {norm, coef} of this step */
+} sslcr_clip_desc;
+int sslcr_net_optimizer_step_groups(sslcr_net* net, const sslcr_opt_desc* groups, int ngroups, const int* group_of_param,
+                                    float* const* state1, float* const* state2, const sslcr_clip_desc* clip, void* stream);
+/* {norm, coef} (sslcr_grad_norm) of the gradients the last sslcr_net_backward left, over exactly the elements sslcr_net_grad exposes
+ * for the requires_grad parameters: frozen parameters' ranges and the 64-element padding between parameters are zero in the flat
+ * buffer (it is cleared before every backward and only trainable parameters' ranges are written). */
+int sslcr_net_grad_norm(sslcr_net* net, float max_norm, float* out2_dev, void* stream);
 int sslcr_net_lookahead(sslcr_net* net, float* const* cached, float alpha, void* stream);   /* lookahead.py:93-97 */
 int sslcr_net_ema_from(sslcr_net* teacher, sslcr_net* student, float decay, void* stream);  /* decay 0 == deepcopy (:515-516) */
 

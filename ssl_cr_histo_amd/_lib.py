@@ -54,9 +54,12 @@ LossDesc = _S("LossDesc", [("kind", i32), ("logits", vp), ("logits_t", vp), ("ta
                            ("dlogits", vp), ("out", vp), ("nx", i32), ("nu", i32), ("C", i32), ("lambda_u", f32),
                            ("inv_nx_global", f32), ("inv_nu_global", f32)])
 TensorDesc = _S("TensorDesc", [("p", vp), ("g", vp), ("s1", vp), ("s2", vp), ("n", i32), ("K", i32), ("C", i32),
-                               ("RS", i32), ("w_fwd", vp), ("w_dgrad", vp), ("pack_dtype", i32), ("dgrad_flip", i32)])
+                               ("RS", i32), ("w_fwd", vp), ("w_dgrad", vp), ("pack_dtype", i32), ("dgrad_flip", i32),
+                               ("group", i32)])
 OptDesc = _S("OptDesc", [("kind", i32), ("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("wd", f32),
                          ("momentum", f32), ("bc1", f32), ("bc2", f32), ("first_step", i32), ("grad_scale", f32)])
+ClipDesc = _S("ClipDesc", [("max_norm", f32), ("out2", vp)])
+MAX_OPT_GROUPS = 8
 WeakAugDesc = _S("WeakAugDesc", [("src", vp), ("dst", vp), ("params", vp)] +
                  [(k, i32) for k in ("N", "SH", "SW", "OH", "OW", "src_hwc")])
 ColourAugDesc = _S("ColourAugDesc", [("src", vp), ("dst", vp), ("shift", vp), ("apply", vp), ("hed_from_rgb", f64 * 9),
@@ -108,6 +111,9 @@ SIGNATURES = {
     "sslcr_loss": (i32, [P(LossDesc), vp]),
     "sslcr_softmax_col": (i32, [vp, vp, i32, i32, i32, vp]),
     "sslcr_optimizer_step": (i32, [vp, i32, i32, P(OptDesc), vp]),
+    "sslcr_optimizer_step_groups": (i32, [vp, i32, i32, P(OptDesc), i32, vp, vp]),
+    "sslcr_grad_norm": (i32, [vp, sz, f32, vp, vp, vp]),
+    "sslcr_grad_norm_partials": (i32, []),
     "sslcr_axpby": (i32, [vp, vp, sz, f32, i32, vp]),
     "sslcr_fill": (i32, [vp, sz, f32, vp]),
     "sslcr_pack_conv": (i32, [i32, P(PackDesc), vp]),

@@ -30,7 +30,7 @@ using namespace sslcr;
 
 extern "C" {
 
-int sslcr_version(void) { return 7; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
+int sslcr_version(void) { return 8; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
 const char* sslcr_last_error(void) { return g_err; }
 
 int sslcr_conv2d(int dtype, const sslcr_conv_desc* d, void* stream) {
@@ -188,8 +188,25 @@ int sslcr_softmax_col(const float* logits, float* out, int n, int C, int col, vo
 }
 
 int sslcr_optimizer_step(const sslcr_tensor_desc* device_descs, int ntensors, int max_n, const sslcr_opt_desc* o, void* stream) {
-  NEED(device_descs && o && ntensors > 0 && max_n > 0, "args");
-  return check(launch_optimizer(device_descs, ntensors, max_n, *o, (hipStream_t)stream), "optimizer_step");
+  return sslcr_optimizer_step_groups(device_descs, ntensors, max_n, o, 1, nullptr, stream);
+}
+int sslcr_optimizer_step_groups(const sslcr_tensor_desc* device_descs, int ntensors, int max_n, const sslcr_opt_desc* groups, int ngroups,
+                                const float* coef_dev, void* stream) {
+  NEED(device_descs && groups && ntensors > 0 && max_n > 0, "args");
+  NEED(ngroups >= 1 && ngroups <= SSLCR_MAX_OPT_GROUPS, "ngroups must be 1..8");
+  OptTable tab = opt_table_noop();
+  for (int i = 0; i < ngroups; ++i) {
+    NEED(groups[i].kind >= 0 && groups[i].kind <= 2, "kind");
+    tab.row[i] = groups[i];
+  }
+  return check(launch_optimizer(device_descs, ntensors, max_n, tab, coef_dev, (hipStream_t)stream), "optimizer_step");
+}
+int sslcr_grad_norm_partials(void) { return GRAD_NORM_BLOCKS; }
+int sslcr_grad_norm(const float* g, size_t n, float max_norm, double* partials, float* out2, void* stream) {
+  NEED(partials && out2 && (g || n == 0), "null");
+  NEED((reinterpret_cast<uintptr_t>(g) & 3) == 0 && (reinterpret_cast<uintptr_t>(partials) & 7) == 0, "alignment");
+  NEED(!(max_norm < 0.f), "max_norm");
+  return check(launch_grad_norm(g, n, max_norm, partials, out2, (hipStream_t)stream), "grad_norm");
 }
 int sslcr_axpby(float* p, float* q, size_t n, float alpha, int copy_back, void* stream) {
   NEED(p && q, "null");

@@ -214,6 +214,7 @@ struct sslcr_net {
   BnL bn0;
   BlockL blocks[8];
   DevBuf shadow, grads, heads, descs, chunks, f8buf;
+  DevBuf norm_ws;     // gradient norm: GRAD_NORM_BLOCKS double partials, then {norm, coef}
   float* f8slots = nullptr;       // [n8][2] = {x_scale, amax since the last update}: two slots (train, eval) per fp8 conv, see ConvL::f8s
   int n8 = 0;
   bool f8_cal[2] = {false, false};  // the first forward of this net in (train, eval) mode has calibrated the activation scales
@@ -237,6 +238,7 @@ struct sslcr_net {
   int tap_flags[8] = {};            // bit 0: dAct1 was written with bn1's ReLU mask already applied (mask_x front end of the dgrad)
   std::vector<sslcr_tensor_desc> host_descs;
   std::vector<float*> st1, st2;
+  std::vector<int> group_of;      // parameter -> optimizer group of the descriptor table in `descs`
   int ndesc = 0, max_n = 0;
 };
 
@@ -1851,7 +1853,7 @@ int sslcr_net_create(sslcr_ctx* c, const sslcr_net_desc* d, sslcr_net** out) {
 int sslcr_net_destroy(sslcr_net* n) {
   if (!n) return 0;
   (void)hipDeviceSynchronize();
-  n->shadow.release(); n->grads.release(); n->heads.release(); n->descs.release(); n->f8buf.release();
+  n->shadow.release(); n->grads.release(); n->heads.release(); n->descs.release(); n->f8buf.release(); n->norm_ws.release();
   for (int i = 0; i < 3; ++i) n->pass[i].mem.release();
   for (auto& row : n->tapbuf)
     for (DevBuf& b : row) b.release();
@@ -1908,7 +1910,7 @@ int sslcr_net_debug_tap(sslcr_net* n, int on) {
 }
 
 int sslcr_net_debug_tensor(sslcr_net* n, int block, int kind, void* out, size_t out_bytes, int* dims4, int* flags, void* stream) {
-  if (!n || block < 0 || block > 7 || kind < 0 || kind > 14 || !dims4) return fail("sslcr_net_debug_tensor: invalid argument");
+  if (!n || block < 0 || block > 7 || kind < 0 || kind > 20 || !dims4) return fail("sslcr_net_debug_tensor: invalid argument");
   sslcr_ctx* c = n->ctx;
   hipStream_t st = (hipStream_t)stream;
   const BlockL& B = n->blocks[block];
@@ -1929,7 +1931,14 @@ int sslcr_net_debug_tensor(sslcr_net* n, int block, int kind, void* out, size_t 
   else if (kind == 8) { src = ps.blk[block].rawd; if (!B.has_ds) return fail("sslcr_net_debug_tensor: block %d has no projection", block); }
   else if (kind == 9) { src = ps.blk[block].y; }
   else if (kind == 10) { src = block == 0 ? ps.pooled : ps.blk[block - 1].y; dm[1] = xh; dm[2] = xw; dm[3] = B.c1.cin; }
-  else {                        // 11..14: bn1's saved scale, shift, mean, invstd (fp32 [C])
+  else if (kind >= 15) {        // 15..20: the train-mode shadow weights of conv1, conv2, the projection: forward pack, dgrad pack
+    const ConvL& L = kind < 17 ? B.c1 : kind < 19 ? B.c2 : B.ds;
+    if (kind >= 19 && !B.has_ds) return fail("sslcr_net_debug_tensor: block %d has no projection", block);
+    const bool fwd = (kind & 1) != 0;
+    src = fwd ? L.w_fwd : L.w_dg;
+    if (!src) return fail("sslcr_net_debug_tensor: block %d kind %d: this conv has no such pack", block, kind);
+    dm[0] = fwd ? L.cout : L.cin; dm[1] = dm[2] = L.k; dm[3] = fwd ? L.cin : L.cout;
+  } else {                      // 11..14: bn1's saved scale, shift, mean, invstd (fp32 [C])
     const BnSaved& sv = ps.bn[B.b1.bidx];
     const float* v[4] = {sv.scale, sv.shift, sv.mean, sv.invstd};
     src = v[kind - 11]; esz = 4; dm[0] = B.b1.C; dm[1] = dm[2] = dm[3] = 1;
@@ -1963,15 +1972,59 @@ int sslcr_net_grad(sslcr_net* n, int pidx, float* out, void* stream) {
   return 0;
 }
 
+// the flat gradient buffer holds exactly what sslcr_net_grad exposes for the trainable parameters and zeros elsewhere (frozen
+// parameters' ranges, the padding to 64 elements behind every parameter): net_backward clears it and only trainable parameters'
+// ranges are written, each with exactly psize elements -- so ONE reduction over [0, grad_count) is the global norm
+int net_grad_norm(sslcr_net* n, float max_norm, float* out2, hipStream_t st) {
+  TRYI(n->norm_ws.ensure(GRAD_NORM_BLOCKS * sizeof(double) + 2 * sizeof(float)));
+  double* partials = (double*)n->norm_ws.p;
+  TRY(launch_grad_norm((const float*)n->grads.p, n->grad_count, max_norm, partials, out2 ? out2 : (float*)(partials + GRAD_NORM_BLOCKS), st));
+  return 0;
+}
+
+int sslcr_net_grad_norm(sslcr_net* n, float max_norm, float* out2, void* stream) {
+  if (!n || !out2) return fail("sslcr_net_grad_norm: null");
+  if (!n->grads.p) return fail("sslcr_net_grad_norm: no gradients (run a backward first)");
+  if (max_norm < 0.f) return fail("sslcr_net_grad_norm: max_norm must not be negative");
+  return net_grad_norm(n, max_norm, out2, (hipStream_t)stream);
+}
+
 int sslcr_net_optimizer_step(sslcr_net* n, const sslcr_opt_desc* o, float* const* s1, float* const* s2, void* stream) {
-  if (!n || !o || !s1) return fail("sslcr_net_optimizer_step: null");
+  if (!o) return fail("sslcr_net_optimizer_step: null");
+  return sslcr_net_optimizer_step_groups(n, o, 1, nullptr, s1, s2, nullptr, stream);
+}
+
+int sslcr_net_optimizer_step_groups(sslcr_net* n, const sslcr_opt_desc* groups, int ngroups, const int* group_of, float* const* s1,
+                                    float* const* s2, const sslcr_clip_desc* clip, void* stream) {
+  if (!n || !groups || !s1) return fail("sslcr_net_optimizer_step: null");
+  if (ngroups < 1 || ngroups > SSLCR_MAX_OPT_GROUPS) return fail("sslcr_net_optimizer_step: %d param groups (1..%d are served)", ngroups, SSLCR_MAX_OPT_GROUPS);
   if (!n->grads.p) return fail("sslcr_net_optimizer_step: no gradients (run a backward first)");
+  if (clip && clip->max_norm < 0.f) return fail("sslcr_net_optimizer_step: max_norm must not be negative");
+  OptTable tab = opt_table_noop();
+  for (int g = 0; g < ngroups; ++g) {
+    if (groups[g].kind < 0 || groups[g].kind > 2) return fail("sslcr_net_optimizer_step: group %d has kind %d (0 adam, 1 sgd-nesterov, 2 adamw)", g, groups[g].kind);
+    tab.row[g] = groups[g];
+  }
+  for (int i = 0; i < n->nparams; ++i) {
+    const int g = group_of ? group_of[i] : 0;
+    if (n->rg[i] && (g < 0 || g >= ngroups)) return fail("sslcr_net_optimizer_step: parameter %d is in group %d of %d", i, g, ngroups);
+  }
   hipStream_t st = (hipStream_t)stream;
-  // (re)build the device descriptor table when the state pointers or the trainable set changed
+  // clipping: norm and coefficient stay on the device; the update reads the coefficient once per workgroup.  (In front of the
+  // early returns below: with nothing trainable the caller still gets {0, 1}.)
+  const float* coef = nullptr;
+  if (clip) {
+    TRYI(net_grad_norm(n, clip->max_norm, clip->out2, st));
+    coef = (clip->out2 ? clip->out2 : (const float*)((const double*)n->norm_ws.p + GRAD_NORM_BLOCKS)) + 1;
+  }
+  // (re)build the device descriptor table when the state pointers, the trainable set or the group map changed
   bool rebuild = n->ndesc == 0 || (int)n->st1.size() != n->nparams;
   if (!rebuild)
     for (int i = 0; i < n->nparams; ++i)
-      if (n->st1[i] != s1[i] || n->st2[i] != (s2 ? s2[i] : nullptr)) { rebuild = true; break; }
+      if (n->st1[i] != s1[i] || n->st2[i] != (s2 ? s2[i] : nullptr) || (n->rg[i] && n->group_of[i] != (group_of ? group_of[i] : 0))) {
+        rebuild = true;
+        break;
+      }
   if (rebuild) {
     n->host_descs.clear();
     n->max_n = 0;
@@ -1979,9 +2032,11 @@ int sslcr_net_optimizer_step(sslcr_net* n, const sslcr_opt_desc* o, float* const
     int packed_convs = 0;
     for (int i = 0; i < n->nparams; ++i) {
       if (!n->rg[i]) continue;
-      if (!s1[i] || (o->kind == 0 && (!s2 || !s2[i]))) return fail("sslcr_net_optimizer_step: missing optimizer state for parameter %d", i);
+      const int grp = group_of ? group_of[i] : 0;
+      if (!s1[i] || (groups[grp].kind != 1 && (!s2 || !s2[i]))) return fail("sslcr_net_optimizer_step: missing optimizer state for parameter %d", i);
       sslcr_tensor_desc t;
       memset(&t, 0, sizeof(t));
+      t.group = grp;
       t.p = n->params[i]; t.g = (float*)n->grads.p + n->goff[i]; t.s1 = s1[i]; t.s2 = s2 ? s2[i] : nullptr; t.n = n->psize[i];
       for (int b = 0; b < 8; ++b) {
         BlockL& B = n->blocks[b];
@@ -1994,7 +2049,7 @@ int sslcr_net_optimizer_step(sslcr_net* n, const sslcr_opt_desc* o, float* const
         }
       }
       // work list: OPT_CHUNK elements per entry
-      const int ti = (int)n->host_descs.size();
+      const int ti = (int)n->host_descs.size() | (t.group << OPT_CHUNK_GROUP_SHIFT);      // the chunk repeats the group (optim.hip)
       if (t.K > 0 && t.RS == 9 && t.w_fwd && t.w_dgrad && t.K % 16 == 0 && t.C % 16 == 0) {
         for (int tile = 0; tile < (t.K / 16) * (t.C / 16); ++tile) host_chunks.push_back({ti, -(tile + 1)});   // LDS-transposed tiles
       } else {
@@ -2016,10 +2071,12 @@ int sslcr_net_optimizer_step(sslcr_net* n, const sslcr_opt_desc* o, float* const
     TRY(hipStreamSynchronize(st));       // host_descs may be rebuilt before the copy would otherwise land
     n->st1.assign(s1, s1 + n->nparams);
     if (s2) n->st2.assign(s2, s2 + n->nparams); else n->st2.assign(n->nparams, nullptr);
+    n->group_of.assign(n->nparams, 0);
+    if (group_of) n->group_of.assign(group_of, group_of + n->nparams);
   }
   if (n->ndesc == 0) return 0;
   // sharded runs: every rank's loss is already scaled by 1/(global batch), so the all-reduced SUM is the exact gradient
-  TRY(launch_optimizer_chunks((const sslcr_tensor_desc*)n->descs.p, n->chunks.p, n->nchunks, *o, st));
+  TRY(launch_optimizer_chunks((const sslcr_tensor_desc*)n->descs.p, n->chunks.p, n->nchunks, tab, coef, st));
   n->packed_train = false; n->packed_eval = false;
   if (n->opt_packs_all) {
     // every block conv's shadow weights were rewritten with the update; only the stem's (its own K order) are left

@@ -183,11 +183,24 @@ hipError_t launch_hed_colour(const sslcr_colour_aug_desc& a, hipStream_t st);
 hipError_t launch_brightness_contrast(const sslcr_brightness_contrast_desc& a, hipStream_t st);
 hipError_t launch_augv2(const sslcr_augv2_desc& a, hipStream_t st);
 // optim.hip
-hipError_t launch_optimizer(const TensorDesc* d_descs, int ntensors, int max_n, const OptArgs& o, hipStream_t st);
+struct OptTable { OptArgs row[SSLCR_MAX_OPT_GROUPS]; };   // the kernels' by-value table: a tensor's row is row[TensorDesc.group]
+// every row a no-op (SGD with lr 0, momentum 1 and gradient scale 0: p and the momentum buffer are rewritten with their own values;
+// the SGD form because it touches only s1, which every descriptor has), so that a descriptor whose group lies past the caller's rows
+// -- the device-resident descriptors of sslcr_optimizer_step_groups cannot be checked on the host -- leaves its tensor as it was
+inline OptTable opt_table_noop() {
+  OptTable t;
+  for (OptArgs& o : t.row) { o.kind = 1; o.lr = 0.f; o.beta1 = 0.f; o.beta2 = 0.f; o.eps = 0.f; o.wd = 0.f; o.momentum = 1.f; o.bc1 = 1.f; o.bc2 = 1.f; o.first_step = 0; o.grad_scale = 0.f; }
+  return t;
+}
+// coef: NULL, or a device float the gradient scale is multiplied with (the clipping coefficient of launch_grad_norm)
+hipError_t launch_optimizer(const TensorDesc* d_descs, int ntensors, int max_n, const OptTable& tab, const float* coef, hipStream_t st);
 constexpr int OPT_CHUNK = 2048;     // elements per work-list entry
 constexpr int OPT_TILE = 16 * 16 * 9; // ... and per LDS-transposed 3x3 filter tile (chunk.y = -(tile + 1))
-hipError_t launch_optimizer_chunks(const TensorDesc* d_descs, const void* d_chunks /* int2 {tensor, first element} */, int nchunks,
-                                   const OptArgs& o, hipStream_t st);
+constexpr int OPT_CHUNK_GROUP_SHIFT = 24;   // chunk.x = tensor index | TensorDesc.group << 24
+hipError_t launch_optimizer_chunks(const TensorDesc* d_descs, const void* d_chunks /* int2 {tensor | group << 24, first element} */, int nchunks,
+                                   const OptTable& tab, const float* coef, hipStream_t st);
+constexpr int GRAD_NORM_BLOCKS = 1024;   // workgroups of the sum-of-squares pass = doubles in `partials` (a multiple of 256)
+hipError_t launch_grad_norm(const float* g, size_t n, float max_norm, double* partials /* [GRAD_NORM_BLOCKS] */, float* out2, hipStream_t st);
 hipError_t launch_axpby(float* p, float* q, size_t n, float alpha, int copy_back, hipStream_t st);
 hipError_t launch_fill(float* p, size_t n, float v, hipStream_t st);
 hipError_t launch_pack_conv(int dtype, const PackArgs& a, hipStream_t st);

@@ -5,16 +5,41 @@
 
 namespace sslcr {
 
+// The kernels take the optimizer rows BY VALUE (OptTable: up to SSLCR_MAX_OPT_GROUPS parameter groups); a tensor's row is
+// row[TensorDesc.group].  A workgroup serves one tensor, so the row and the effective gradient scale are wave-uniform: they are
+// read once per workgroup into scalar registers and the per-element arithmetic is what it was with a single sslcr_opt_desc.
+struct OptRow {
+  OptArgs o;
+  float gs;     // grad_scale, times the clipping coefficient where one is given
+  float keep;   // AdamW: 1 - lr * wd
+};
+// a wave-uniform float back into a scalar register (gfx950 has no scalar float ALU: the product would otherwise occupy a VGPR)
+__device__ __forceinline__ float uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+__device__ __forceinline__ OptRow opt_row(const OptTable& tab, int group, const float* __restrict__ coef) {
+  OptRow r;
+  r.o = tab.row[group & (SSLCR_MAX_OPT_GROUPS - 1)];
+  r.gs = coef ? uniform(r.o.grad_scale * coef[0]) : r.o.grad_scale;
+  r.keep = uniform(1.f - r.o.lr * r.o.wd);
+  return r;
+}
+
 // one parameter element: i indexes p / s1 / s2, gi the gradient.  Returns the new value.
-__device__ __forceinline__ float opt_update_g(const TensorDesc& d, const OptArgs& o, int i, float graw);
-__device__ __forceinline__ float opt_update(const TensorDesc& d, const OptArgs& o, int i, int gi) {
-  return opt_update_g(d, o, i, d.g[gi]);
+__device__ __forceinline__ float opt_update_g(const TensorDesc& d, const OptRow& r, int i, float graw);
+__device__ __forceinline__ float opt_update(const TensorDesc& d, const OptRow& r, int i, int gi) {
+  return opt_update_g(d, r, i, d.g[gi]);
 }
 // ... with the raw gradient element already in hand
-__device__ __forceinline__ float opt_update_g(const TensorDesc& d, const OptArgs& o, int i, float graw) {
+__device__ __forceinline__ float opt_update_g(const TensorDesc& d, const OptRow& r, int i, float graw) {
+  const OptArgs& o = r.o;
   float p = d.p[i];
-  const float g = fmaf(o.wd, p, graw * o.grad_scale);
-  if (o.kind == 0) {                  // Adam, L2 decay in the gradient, eps outside the sqrt
+  float g;
+  if (o.kind == 2) {                  // AdamW: decoupled decay first (torch: param.mul_(1 - lr * weight_decay)), no wd in the gradient
+    p *= r.keep;
+    g = graw * r.gs;
+  } else {
+    g = fmaf(o.wd, p, graw * r.gs);
+  }
+  if (o.kind != 1) {                  // Adam (0: L2 decay in the gradient) / AdamW (2), eps outside the sqrt
     float m = d.s1[i], v = d.s2[i];
     m = fmaf(o.beta1, m, (1.f - o.beta1) * g);
     v = fmaf(o.beta2, v, (1.f - o.beta2) * g * g);
@@ -43,8 +68,10 @@ __device__ __forceinline__ void opt_pack(const TensorDesc& d, int k, int c, int 
 }
 
 // generic form (sslcr_optimizer_step): a fixed number of workgroups per tensor
-__global__ __launch_bounds__(256) void optimizer_kernel(const TensorDesc* __restrict__ descs, const OptArgs o) {
+__global__ __launch_bounds__(256) void optimizer_kernel(const TensorDesc* __restrict__ descs, const OptTable tab,
+                                                        const float* __restrict__ coef) {
   const TensorDesc d = descs[blockIdx.y];
+  const OptRow o = opt_row(tab, d.group, coef);
   const int stride = gridDim.x * 256;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < d.n; i += stride) {
     int gi = i, k = 0, c = 0, rs = 0;
@@ -60,10 +87,10 @@ __global__ __launch_bounds__(256) void optimizer_kernel(const TensorDesc* __rest
   }
 }
 
-hipError_t launch_optimizer(const TensorDesc* d_descs, int ntensors, int max_n, const OptArgs& o, hipStream_t st) {
+hipError_t launch_optimizer(const TensorDesc* d_descs, int ntensors, int max_n, const OptTable& tab, const float* coef, hipStream_t st) {
   int bx = cdiv(max_n, 256 * 8);
   if (bx > 64) bx = 64;
-  hipLaunchKernelGGL(optimizer_kernel, dim3(bx, ntensors), dim3(256), 0, st, d_descs, o);
+  hipLaunchKernelGGL(optimizer_kernel, dim3(bx, ntensors), dim3(256), 0, st, d_descs, tab, coef);
   return hipGetLastError();
 }
 
@@ -73,10 +100,15 @@ hipError_t launch_optimizer(const TensorDesc* d_descs, int ntensors, int max_n, 
 // measured 0.3 ms/step slower: the 36-byte stride it puts on the three fp32 state arrays costs more than it saves.
 // The shadow weights of the updated value are written here, which removes the 19 pack launches that followed every step
 // (step 20.33 -> 20.24 ms).
-__global__ __launch_bounds__(256) void optimizer_chunks_kernel(const TensorDesc* __restrict__ descs, const int2* __restrict__ chunks,
-                                                               const OptArgs o) {
+// (waves_per_eu 5: the register allocator otherwise settles on 98 VGPRs -- one 8-register granule above the 96 that five waves per
+// SIMD allow, which is where this kernel ran before the group table; with the hint it takes 95 and no scratch)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void optimizer_chunks_kernel(const TensorDesc* __restrict__ descs, const int2* __restrict__ chunks,
+                                                               const OptTable tab, const float* __restrict__ coef) {
+  // chunk.x = tensor | group << OPT_CHUNK_GROUP_SHIFT: the work list repeats the tensor's group so that the row's scalar loads do
+  // not wait for the descriptor's (descriptor -> group -> row would be one more dependent load in front of every workgroup)
   const int2 ch = chunks[blockIdx.x];
-  const TensorDesc d = descs[ch.x];
+  const TensorDesc d = descs[ch.x & ((1 << OPT_CHUNK_GROUP_SHIFT) - 1)];
+  const OptRow o = opt_row(tab, ch.x >> OPT_CHUNK_GROUP_SHIFT, coef);
   if (ch.y < 0) {
     // 3x3 filter with shadow weights, tile (16 kout) x (16 cin) x 9 taps = 2304 elements through LDS, so that EVERY stream is
     // a run of >= 32 bytes: gradient [K][9][C] in (64-byte runs of 16 cin), parameter / moments [K][C][9] (576-byte runs),
@@ -137,9 +169,78 @@ __global__ __launch_bounds__(256) void optimizer_chunks_kernel(const TensorDesc*
     for (int i = ch.y + threadIdx.x; i < end; i += 256) opt_update(d, o, i, i);
   }
 }
-hipError_t launch_optimizer_chunks(const TensorDesc* d_descs, const void* d_chunks, int nchunks, const OptArgs& o, hipStream_t st) {
+hipError_t launch_optimizer_chunks(const TensorDesc* d_descs, const void* d_chunks, int nchunks, const OptTable& tab, const float* coef,
+                                   hipStream_t st) {
   if (nchunks < 1) return hipSuccess;
-  hipLaunchKernelGGL(optimizer_chunks_kernel, dim3(nchunks), dim3(256), 0, st, d_descs, reinterpret_cast<const int2*>(d_chunks), o);
+  hipLaunchKernelGGL(optimizer_chunks_kernel, dim3(nchunks), dim3(256), 0, st, d_descs, reinterpret_cast<const int2*>(d_chunks), tab, coef);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ global gradient norm (torch.nn.utils.clip_grad_norm_)
+// Deterministic and without atomics: GRAD_NORM_BLOCKS workgroups, each owning one fixed contiguous slice of the buffer.  The
+// slices are cut on 16-byte boundaries of the ADDRESS: the up-to-3 elements in front of the first boundary (any 4-byte-aligned
+// base is served) go to workgroup 0 as scalars, every slice is then a whole number of float4 quads, and the up-to-3 elements
+// behind the last whole quad go to the workgroup that owns them as scalars.  A thread walks its quads in a fixed order and
+// accumulates (double)g * (double)g -- exact: 48 significand bits -- in double; the block fold is a fixed tree.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, size_t n, double* __restrict__ partials) {
+  __shared__ double red[256];
+  size_t head = ((16 - (reinterpret_cast<uintptr_t>(g) & 15)) & 15) / 4;
+  if (head > n) head = n;
+  const size_t quads = (n - head) / 4;                                     // whole aligned quads behind the head
+  const size_t per = (quads + GRAD_NORM_BLOCKS - 1) / GRAD_NORM_BLOCKS;    // quads per workgroup
+  size_t q0 = per * blockIdx.x, q1 = q0 + per;
+  if (q0 > quads) q0 = quads;
+  if (q1 > quads) q1 = quads;
+  const float4* __restrict__ gv = reinterpret_cast<const float4*>(g + head);
+  double acc = 0.0;
+  for (size_t q = q0 + threadIdx.x; q < q1; q += 256) {
+    const float4 v = gv[q];
+    acc = fma((double)v.x, (double)v.x, acc);
+    acc = fma((double)v.y, (double)v.y, acc);
+    acc = fma((double)v.z, (double)v.z, acc);
+    acc = fma((double)v.w, (double)v.w, acc);
+  }
+  if (threadIdx.x == 0) {
+    if (blockIdx.x == 0)
+      for (size_t i = 0; i < head; ++i) acc = fma((double)g[i], (double)g[i], acc);
+    // the tail belongs to the workgroup whose slice ends the quads (the last one with work, or workgroup 0 when there are none)
+    const size_t owner = quads == 0 ? 0 : (quads - 1) / per;
+    if (blockIdx.x == owner)
+      for (size_t i = head + quads * 4; i < n; ++i) acc = fma((double)g[i], (double)g[i], acc);
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
+}
+// one workgroup: thread t folds partials [4t, 4t + 4) in index order, the 256 results fold in the same fixed tree;
+// out2 = {norm, coef} with torch's clip_grad_norm_ arithmetic: coef = min(1, max_norm / (norm + 1e-6))
+__global__ __launch_bounds__(256) void grad_norm_finalize_kernel(const double* __restrict__ partials, float max_norm, float* __restrict__ out2) {
+  __shared__ double red[256];
+  constexpr int PER = GRAD_NORM_BLOCKS / 256;
+  double acc = 0.0;
+#pragma unroll
+  for (int j = 0; j < PER; ++j) acc += partials[threadIdx.x * PER + j];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(red[0]);
+    out2[0] = norm;
+    // (a NaN norm gives coef 1 here -- fminf returns its other operand -- where torch's clamp keeps NaN; the NaN gradients reach
+    // the parameters either way)
+    out2[1] = fminf(1.f, max_norm / (norm + 1e-6f));
+  }
+}
+hipError_t launch_grad_norm(const float* g, size_t n, float max_norm, double* partials, float* out2, hipStream_t st) {
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(GRAD_NORM_BLOCKS), dim3(256), 0, st, g, n, partials);
+  hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, st, partials, max_norm, out2);
   return hipGetLastError();
 }
 

@@ -57,6 +57,9 @@ _ENGINE_SIGS = {
                                          C.c_void_p]),
     "sslcr_net_optimizer_step": (C.c_int, [C.c_void_p, C.POINTER(L.OptDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                            C.c_void_p]),
+    "sslcr_net_optimizer_step_groups": (C.c_int, [C.c_void_p, C.POINTER(L.OptDesc), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p),
+                                                  C.POINTER(C.c_void_p), C.POINTER(L.ClipDesc), C.c_void_p]),
+    "sslcr_net_grad_norm": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "sslcr_net_lookahead": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_float, C.c_void_p]),
     "sslcr_net_ema_from": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
     "sslcr_step_ssl_cr": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SslCrDesc), C.c_void_p]),
@@ -76,6 +79,65 @@ def _version_sig(tensors):
     return tuple((t.data_ptr(), t._version) for t in tensors)
 
 
+def plan_optimizer(inner, params, names=None):
+    """Map a torch optimizer onto the engine's group table.  Pure host logic: no device, nothing is modified.
+
+    inner: torch.optim.Adam, AdamW or SGD(nesterov=True, dampening=0) with 1..8 param groups that are pairwise disjoint and whose
+    union is exactly the requires_grad entries of `params` (named_parameters() order of (model, classifier)); `names` only serves
+    the error messages.  -> (rows, group_of_param): rows[g] is a dict with the fields of sslcr_opt_desc for param group g -- lr,
+    wd, beta1 / beta2 / eps or momentum, and bc1 / bc2 = 1 - beta ** step for the step ABOUT to be taken (the group's recorded
+    step + 1), first_step = 1 for an SGD group in which some parameter has no momentum buffer yet; group_of_param[i] is the group
+    of params[i], -1 for a frozen parameter."""
+    def name(i):
+        return names[i] if names is not None else f"parameter {i}"
+    if isinstance(inner, torch.optim.AdamW):          # (a subclass of Adam in some torch versions: test it first)
+        kind = 2
+    elif isinstance(inner, torch.optim.Adam):
+        kind = 0
+    elif isinstance(inner, torch.optim.SGD):
+        kind = 1
+    else:
+        raise L.SslcrError(f"optimizer {type(inner).__name__}: the engine serves Adam, AdamW and SGD(nesterov=True)")
+    groups = inner.param_groups
+    if not 1 <= len(groups) <= L.MAX_OPT_GROUPS:
+        raise L.SslcrError(f"{type(inner).__name__} has {len(groups)} param groups; the engine serves 1 to {L.MAX_OPT_GROUPS}")
+    index = {id(p): i for i, p in enumerate(params)}
+    group_of = [-1] * len(params)
+    rows = []
+    for gi, g in enumerate(groups):
+        if g.get("amsgrad", False) or g.get("maximize", False):
+            raise NotImplementedError(f"param group {gi}: amsgrad / maximize are not served")
+        step, first = 0.0, False
+        for p in g["params"]:
+            i = index.get(id(p))
+            if i is None:
+                raise L.SslcrError(f"param group {gi} holds a tensor of shape {tuple(p.shape)} that is no parameter of (model, classifier)")
+            if not params[i].requires_grad:
+                raise L.SslcrError(f"{name(i)} is frozen (requires_grad=False) but listed in param group {gi}")
+            if group_of[i] >= 0:
+                raise L.SslcrError(f"{name(i)} is listed in param groups {group_of[i]} and {gi}: groups must be disjoint")
+            group_of[i] = gi
+            st = inner.state.get(p, {})
+            if kind == 1:
+                first = first or st.get("momentum_buffer", None) is None
+            elif "step" in st:
+                step = float(st["step"])
+        if kind == 1:
+            if not g.get("nesterov", False) or g.get("dampening", 0) != 0:
+                raise NotImplementedError(f"param group {gi}: the engine serves SGD(momentum, nesterov=True, dampening=0)")
+            rows.append(dict(kind=1, lr=g["lr"], beta1=0.0, beta2=0.0, eps=0.0, wd=g["weight_decay"], momentum=g["momentum"], bc1=1.0,
+                             bc2=1.0, first_step=int(first)))
+        else:
+            b1, b2 = g["betas"]
+            rows.append(dict(kind=kind, lr=g["lr"], beta1=b1, beta2=b2, eps=g["eps"], wd=g["weight_decay"], momentum=0.0,
+                             bc1=1 - b1 ** (step + 1), bc2=1 - b2 ** (step + 1), first_step=0))
+    for i, p in enumerate(params):
+        if p.requires_grad and group_of[i] < 0:
+            raise L.SslcrError(f"{name(i)} requires grad but is in no param group: the groups' union must be exactly the "
+                               "requires_grad parameters of (model, classifier)")
+    return rows, group_of
+
+
 class BoundNet:
     """one (model, classifier) pair registered with the engine."""
 
@@ -93,6 +155,8 @@ class BoundNet:
         else:
             raise TypeError("classifier must be ssl_cr_histo_amd.net.FinetuneResNet or Classifier")
         self.params = [p for _, p in model.named_parameters()] + [p for _, p in classifier.named_parameters()]
+        self.param_names = ["model." + k for k, _ in model.named_parameters()] + ["classifier." + k for k, _ in classifier.named_parameters()]
+        self.last_grad_norm = None
         dev = engine.device
         for p in self.params:
             if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
@@ -181,8 +245,8 @@ class BoundNet:
         dims, flags = (C.c_int * 4)(), C.c_int()
         L.check(L.lib().sslcr_net_debug_tensor(self.handle, block, kind, None, 0, dims, C.byref(flags), L.stream_ptr()))
         shape = [d for d in dims]
-        dt = torch.float32 if kind >= 11 or self.engine.dtype == 0 else torch.bfloat16
-        out = torch.empty(shape if kind < 11 else shape[:1], dtype=dt, device=self.engine.device)
+        dt = torch.float32 if 11 <= kind <= 14 or self.engine.dtype == 0 else torch.bfloat16
+        out = torch.empty(shape[:1] if 11 <= kind <= 14 else shape, dtype=dt, device=self.engine.device)
         L.check(L.lib().sslcr_net_debug_tensor(self.handle, block, kind, L.ptr(out), out.numel() * out.element_size(), dims,
                                                C.byref(flags), L.stream_ptr()))
         return out, flags.value
@@ -193,52 +257,50 @@ class BoundNet:
         self._sig = _version_sig(self._tensors())
 
     # ------------------------------------------------------------------ optimizer (state lives in the torch optimizer)
-    def optimizer_step(self, optimizer):
+    def optimizer_step(self, optimizer, max_grad_norm=None):
+        """one step of `optimizer` (Adam, AdamW or SGD-Nesterov, up to 8 param groups; Lookahead wraps one) on the gradients the
+        engine holds.  max_grad_norm: torch.nn.utils.clip_grad_norm_(params, max_grad_norm) in front of the step, on the device
+        and without a sync; [norm, coef] of that step is then ``self.last_grad_norm``."""
         inner = getattr(optimizer, "optimizer", optimizer)           # Lookahead wraps the real optimizer
-        if len(inner.param_groups) != 1:
-            raise NotImplementedError("the reference builds a single param group; multiple groups are not supported")
-        g = inner.param_groups[0]
-        ids = {id(p) for p in g["params"]}
-        mine = {id(p) for p in self.params if p.requires_grad}
-        if ids != mine:
-            raise L.SslcrError("optimizer parameters must be exactly the requires_grad parameters of (model, classifier) "
-                               "-- the reference builds it with filter(lambda p: p.requires_grad, ...)")
+        rows, group_of = plan_optimizer(inner, self.params, self.param_names)
         s1, s2 = [None] * len(self.params), [None] * len(self.params)
-        if isinstance(inner, torch.optim.Adam):
-            if g.get("amsgrad", False) or g.get("maximize", False):
-                raise NotImplementedError("amsgrad/maximize are not used by the reference")
-            step = None
-            for i, p in enumerate(self.params):
-                if not p.requires_grad:
-                    continue
-                st = inner.state[p]
+        for i, p in enumerate(self.params):
+            if group_of[i] < 0:
+                continue
+            st = inner.state[p]
+            if rows[group_of[i]]["kind"] == 1:
+                if st.get("momentum_buffer", None) is None:
+                    st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                s1[i] = st["momentum_buffer"]
+            else:
                 if len(st) == 0:
                     st["step"] = torch.tensor(0.0)
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["step"] += 1
-                step = float(st["step"])
                 s1[i], s2[i] = st["exp_avg"], st["exp_avg_sq"]
-            b1, b2 = g["betas"]
-            o = L.OptDesc(0, g["lr"], b1, b2, g["eps"], g["weight_decay"], 0.0, 1 - b1 ** step, 1 - b2 ** step, 0, 1.0)
-        elif isinstance(inner, torch.optim.SGD):
-            if not g.get("nesterov", False) or g.get("dampening", 0) != 0:
-                raise NotImplementedError("the reference uses SGD(momentum, nesterov=True, dampening=0)")
-            first = False
-            for i, p in enumerate(self.params):
-                if not p.requires_grad:
-                    continue
-                st = inner.state[p]
-                if st.get("momentum_buffer", None) is None:
-                    st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    first = True
-                s1[i] = st["momentum_buffer"]
-            o = L.OptDesc(1, g["lr"], 0.0, 0.0, 0.0, g["weight_decay"], g["momentum"], 1.0, 1.0, int(first), 1.0)
-        else:
-            raise NotImplementedError(f"optimizer {type(inner).__name__}: the reference uses Adam and SGD-Nesterov")
+        table = (L.OptDesc * len(rows))(*[L.OptDesc(r["kind"], r["lr"], r["beta1"], r["beta2"], r["eps"], r["wd"], r["momentum"], r["bc1"],
+                                                    r["bc2"], r["first_step"], 1.0) for r in rows])
+        gmap = (C.c_int * len(group_of))(*[max(g, 0) for g in group_of])
+        clip = None
+        if max_grad_norm is not None:
+            if not float(max_grad_norm) >= 0.0:
+                raise L.SslcrError(f"max_grad_norm must be a non-negative number (got {max_grad_norm!r})")
+            out2 = torch.empty(2, dtype=torch.float32, device=self.engine.device)
+            clip = C.byref(L.ClipDesc(float(max_grad_norm), out2.data_ptr()))
         self._opt_keep = (s1, s2, _ptr_array(s1), _ptr_array(s2))
-        L.check(L.lib().sslcr_net_optimizer_step(self.handle, C.byref(o), self._opt_keep[2], self._opt_keep[3], L.stream_ptr()))
+        L.check(L.lib().sslcr_net_optimizer_step_groups(self.handle, table, len(rows), gmap, self._opt_keep[2], self._opt_keep[3], clip,
+                                                        L.stream_ptr()))
+        if max_grad_norm is not None:
+            self.last_grad_norm = out2
         self._note_buffers_changed()
+
+    def grad_norm(self, max_norm=float("inf")):
+        """-> device tensor [norm, coef]: the global 2-norm of the gradients of the last backward and
+        min(1, max_norm / (norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s two numbers.  No sync."""
+        out2 = torch.empty(2, dtype=torch.float32, device=self.engine.device)
+        L.check(L.lib().sslcr_net_grad_norm(self.handle, float(max_norm), L.ptr(out2), L.stream_ptr()))
+        return out2
 
     def lookahead(self, cached, alpha):
         arr = _ptr_array(cached)

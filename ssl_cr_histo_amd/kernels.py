@@ -435,3 +435,14 @@ def softmax_col(logits, col=-1):
     out = torch.empty(n, dtype=torch.float32, device=logits.device)
     L.check(L.lib().sslcr_softmax_col(L.ptr(logits), L.ptr(out), n, c, col % c, L.stream_ptr()))
     return out
+
+
+def grad_norm(flat, max_norm=float("inf")):
+    """-> device tensor [norm, coef] for a 1-D fp32 tensor (any length, any 4-byte-aligned view): its 2-norm, summed in double in a
+    fixed order, and min(1, max_norm / (norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_'s two numbers (sslcr_grad_norm).  No sync."""
+    if not flat.is_cuda or flat.dtype != torch.float32 or flat.dim() != 1 or (flat.numel() > 1 and flat.stride(0) != 1):
+        raise L.SslcrError("grad_norm: a dense 1-D fp32 device tensor expected (no CPU fallback)")
+    partials = torch.empty(L.lib().sslcr_grad_norm_partials(), dtype=torch.float64, device=flat.device)
+    out2 = torch.empty(2, dtype=torch.float32, device=flat.device)
+    L.check(L.lib().sslcr_grad_norm(L.ptr(flat), flat.numel(), float(max_norm), L.ptr(partials), L.ptr(out2), L.stream_ptr()))
+    return out2

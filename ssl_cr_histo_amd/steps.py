@@ -177,7 +177,7 @@ def bpq_cr_train(args, model_teacher, model_student, classifier_teacher, classif
         inputs_x = inputs_x.reshape(-1, 3, 256, 256)                         # :74 (hard-coded by the reference)
         targets_x = targets_x.float().to(eng.device)
         r = eng.step_ssl_cr(te, st, "mse", inputs_x, targets_x.reshape(-1), inputs_u_w, inputs_u_s, args.lambda_u)
-        st.optimizer_step(optimizer)
+        st.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         meters.add(r["losses"], inputs_x.shape[0])
         feats.append(r["feats"])
         targets.append(targets_x)
@@ -234,7 +234,7 @@ def cam_cr_train(args, model_teacher, model_student, classifier_teacher, classif
         x, y = _cat_shuffle(t_x, n_x, p_x.to(t_x.device)), _cat_shuffle(t_y, n_y, p_x.to(t_y.device)).long()
         u_w, u_s = _cat_shuffle(t_uw, n_uw, p_uw.to(t_uw.device)), _cat_shuffle(t_us, n_us, p_us.to(t_us.device))
         r = eng.step_ssl_cr(te, st, "ce", x, y, u_w, u_s, args.lambda_u)
-        st.optimizer_step(optimizer)
+        st.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         n = x.shape[0]
         meters.add(r["losses"], n)
         feats.append(r["feats"][:n])
@@ -284,7 +284,7 @@ def kather_cr_train(args, model_teacher, model_student, classifier_teacher, clas
         inputs_x = inputs_x.reshape(-1, 3, 256, 256)                          # :68
         targets_x = targets_x.reshape(-1).long()                              # :69
         r = eng.step_ssl_cr(te, st, "ce", inputs_x, targets_x, inputs_u_w, inputs_u_s, args.lambda_u)
-        st.optimizer_step(optimizer)
+        st.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         meters.add(r["losses"], inputs_x.shape[0])
         _maybe_print(args, batch_idx, "Train", epoch, _len(labeled_train_loader), t0, meters)
     m = meters.meters()
@@ -333,7 +333,7 @@ def _rsp_epoch(args, model, classifier, loader, criterion, optimizer, epoch, tra
         target = target.long().view(-1, 1).reshape(-1)
         r = eng.step_supervised(net, "ce", [i1, i2, i3], target, train=train)
         if train:
-            net.optimizer_step(optimizer)
+            net.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         meters.add(r["losses"], target.size(0))
         if train:
             feats.append(r["feats"])
@@ -373,7 +373,7 @@ def cam_sup_train(args, model, classifier, tumor_labeled_train_loader, normal_la
         perm = torch.randperm(2 * len(t_x))
         x, y = _cat_shuffle(t_x, n_x, perm.to(t_x.device)), _cat_shuffle(t_y, n_y, perm.to(t_y.device)).long()
         r = eng.step_supervised(net, "ce", [x], y, train=True)
-        net.optimizer_step(optimizer)
+        net.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         meters.add(r["losses"], x.shape[0])
         feats.append(r["feats"])
         targets.append(y.to(eng.device))
@@ -395,7 +395,7 @@ def bpq_sup_train(args, model, classifier, train_loader, criterion, optimizer, e
         x = input1.reshape(-1, 3, args.image_size, args.image_size)
         y = target.float().reshape(-1)
         r = eng.step_supervised(net, "mse", [x], y, train=True)
-        net.optimizer_step(optimizer)
+        net.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         meters.add(r["losses"], y.size(0))
         feats.append(r["feats"])
         targets.append(y.to(eng.device))
@@ -415,7 +415,7 @@ def kather_sup_train(args, model, classifier, train_loader, criterion, optimizer
         x = input.reshape(-1, 3, args.image_size, args.image_size)                   # :57
         y = target.reshape(-1).long()
         r = eng.step_supervised(net, "ce", [x], y, train=True)
-        net.optimizer_step(optimizer)
+        net.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         meters.add(r["losses"], y.size(0))
     m = meters.meters()
     return m["loss"].avg, m["acc"].avg
