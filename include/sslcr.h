@@ -29,10 +29,11 @@ extern "C" {
 #define SSLCR_BF16 1
 #define SSLCR_FP8 2   /* engine mode only (sslcr_create): bf16 storage and backward, fp8 e4m3 forward for the eligible 3x3 convs */
 
-/* the library round (8 here).  ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
+/* the library round (9 here).  ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
  * 7 = sslcr_randaug_v2_slot added (nothing else changed); 8 = optimizer parameter groups, AdamW and the global gradient norm
  * (sslcr_tensor_desc.group, sslcr_opt_desc.kind 2, sslcr_optimizer_step_groups, sslcr_grad_norm, sslcr_net_optimizer_step_groups,
- * sslcr_net_grad_norm: all additive). */
+ * sslcr_net_grad_norm: all additive); 9 = gradient accumulation (sslcr_grad_accumulate, sslcr_net_set_grad_accumulate: additive,
+ * off by default). */
 int sslcr_version(void);
 const char* sslcr_last_error(void);
 
@@ -325,6 +326,11 @@ int sslcr_optimizer_step_groups(const sslcr_tensor_desc* device_descs, int ntens
  * run, and the same bits on every rank that holds the same buffer. */
 int sslcr_grad_norm(const float* g, size_t n, float max_norm, double* partials, float* out2, void* stream);
 int sslcr_grad_norm_partials(void);
+/* library version >= 9.  What loss.backward() does to a leaf's .grad when no optimizer.zero_grad() went before it (autograd's
+ * `.grad += new`): dst[i] = dst[i] + src[i] for i < n, ONE IEEE fp32 add per element (no FMA, nothing reassociated; NaN and inf
+ * propagate as the add defines).  Any n >= 0, any two 4-byte-aligned bases -- dst and src may sit at different offsets mod 16; the
+ * ranges must not overlap.  One launch, no atomics, one writer per element: the same bits every run. */
+int sslcr_grad_accumulate(float* dst, const float* src, size_t n, void* stream);
 int sslcr_axpby(float* p, float* q, size_t n, float alpha, int copy_back, void* stream);
 int sslcr_fill(float* p, size_t n, float v, void* stream);
 
@@ -506,6 +512,20 @@ int sslcr_net_forward(sslcr_net* net, int train, const void* x1, const void* x2,
 /* backward of the last train forward from d(loss)/d(logits); zeroes then fills the engine's gradient buffer;
  * all-reduces it when a communicator is set. */
 int sslcr_net_backward(sslcr_net* net, const float* dlogits, void* stream);
+/* library version >= 9.  Gradient accumulation -- loss.backward() without a preceding optimizer.zero_grad(), i.e. autograd's
+ * `.grad +=`: k micro-batches, one optimizer step.  Sticky: applies to every later backward of this net (sslcr_net_backward and the
+ * backward leg of sslcr_step_ssl_cr / sslcr_step_supervised).
+ *   off (0, the default): the behaviour and the launches described above, nothing added.
+ *   on: after the backward the gradient buffer holds prev + new, elementwise in fp32 (sslcr_grad_accumulate), where prev is what the
+ *       buffer held when the backward was entered -- also a gradient an optimizer step has already consumed: as in torch, nothing is
+ *       cleared for the caller -- and new is what this backward alone would have left.  The backward writes `new` into a second flat
+ *       buffer (allocated at the first accumulating backward); the sum is taken on `stream` after the bucket all-reduces and the
+ *       side-stream weight gradients have been joined into it, so sharded ranks add identical buffers and need no further
+ *       collective (every micro-step still all-reduces its own gradient: correct by linearity).  Only the range from the lowest
+ *       trainable parameter to the end of the buffer is cleared, written and added: a frozen prefix costs nothing and stays zero.
+ *       A net that has had no backward since sslcr_net_create has no prev: its first backward behaves as off.
+ * The sum lives in the buffer sslcr_net_grad, sslcr_net_grad_norm and the optimizer entries read: they see it unchanged. */
+int sslcr_net_set_grad_accumulate(sslcr_net* net, int on);
 int sslcr_net_grad(sslcr_net* net, int param_index, float* out, void* stream);      /* -> PyTorch layout */
 /* diagnostics for the layer-wise backward parity test (tests/test_backward_replay_gpu.py): autograd of one BasicBlock of
  * torchvision resnet18 (reached from models/net.py:32,77) checked kernel by kernel at the size the step really runs.  With the tap

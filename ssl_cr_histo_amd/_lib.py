@@ -114,6 +114,7 @@ SIGNATURES = {
     "sslcr_optimizer_step_groups": (i32, [vp, i32, i32, P(OptDesc), i32, vp, vp]),
     "sslcr_grad_norm": (i32, [vp, sz, f32, vp, vp, vp]),
     "sslcr_grad_norm_partials": (i32, []),
+    "sslcr_grad_accumulate": (i32, [vp, vp, sz, vp]),
     "sslcr_axpby": (i32, [vp, vp, sz, f32, i32, vp]),
     "sslcr_fill": (i32, [vp, sz, f32, vp]),
     "sslcr_pack_conv": (i32, [i32, P(PackDesc), vp]),

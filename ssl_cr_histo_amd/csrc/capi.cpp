@@ -30,7 +30,7 @@ using namespace sslcr;
 
 extern "C" {
 
-int sslcr_version(void) { return 8; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
+int sslcr_version(void) { return 9; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
 const char* sslcr_last_error(void) { return g_err; }
 
 int sslcr_conv2d(int dtype, const sslcr_conv_desc* d, void* stream) {
@@ -207,6 +207,11 @@ int sslcr_grad_norm(const float* g, size_t n, float max_norm, double* partials, 
   NEED((reinterpret_cast<uintptr_t>(g) & 3) == 0 && (reinterpret_cast<uintptr_t>(partials) & 7) == 0, "alignment");
   NEED(!(max_norm < 0.f), "max_norm");
   return check(launch_grad_norm(g, n, max_norm, partials, out2, (hipStream_t)stream), "grad_norm");
+}
+int sslcr_grad_accumulate(float* dst, const float* src, size_t n, void* stream) {
+  NEED((dst && src) || n == 0, "null");
+  NEED((reinterpret_cast<uintptr_t>(dst) & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 3) == 0, "alignment");
+  return check(launch_grad_accumulate(dst, src, n, (hipStream_t)stream), "grad_accumulate");
 }
 int sslcr_axpby(float* p, float* q, size_t n, float alpha, int copy_back, void* stream) {
   NEED(p && q, "null");

@@ -222,6 +222,11 @@ struct sslcr_net {
   int nchunks = 0;
   bool opt_packs_all = false;     // the optimizer work list rewrites every non-stem conv's train-mode shadow weights
   size_t grad_count = 0;
+  // gradient accumulation (sslcr_net_set_grad_accumulate): gw is where a backward WRITES -- grads.p, or gnew.p while an accumulating
+  // backward runs, whose sum into grads follows the joins at the end of net_backward.  Everything that reads gradients reads grads.
+  DevBuf gnew;
+  float* gw = nullptr;
+  bool grad_accum = false, had_backward = false;
   PassState pass[3];
   bool ybits_ok = false;         // the passes' mask bits are allocated back to back (what the segment forms assume)
   // heads state (fp32)
@@ -1019,7 +1024,7 @@ int heads_forward(sslcr_net* n, float* const* E, int npass, int N, hipStream_t s
   return 0;
 }
 
-inline float* gptr(sslcr_net* n, int pidx) { return n->rg[pidx] ? (float*)n->grads.p + n->goff[pidx] : nullptr; }
+inline float* gptr(sslcr_net* n, int pidx) { return n->rg[pidx] ? n->gw + n->goff[pidx] : nullptr; }
 
 // dlogits -> head parameter grads and dE[0..npass-1]
 int heads_backward(sslcr_net* n, const float* dlogits, int npass, int N, bool need_dE, hipStream_t st) {
@@ -1180,7 +1185,7 @@ int wgrad_call(sslcr_net* n, const ConvL& L, const void* x, const void* dy, cons
   sslcr_ctx* c = n->ctx;
   WgradArgs a;
   memset(&a, 0, sizeof(a));
-  a.x = x; a.dy = dy; a.dw = (float*)n->grads.p + n->goff[L.pidx];
+  a.x = x; a.dy = dy; a.dw = n->gw + n->goff[L.pidx];
   if (pro) { a.in_scale = pro->scale; a.in_shift = pro->shift; a.in_relu = 1; }
   a.N = N; a.H = H; a.W = W; a.C = L.cin; a.K = L.cout; a.R = L.k; a.S = L.k; a.stride = L.stride; a.pad = L.pad; a.OH = OH; a.OW = OW;
   a.seg_images = seg_images; a.seg_stride = seg_stride;
@@ -1211,7 +1216,7 @@ int launch_bucket_allreduce(sslcr_net* n, int bucket, size_t lo, size_t hi, hipS
   TRY(hipEventRecord(c->ev_ready[bucket], st));
   TRY(hipStreamWaitEvent(c->comm_stream, c->ev_ready[bucket], 0));
   TRYI(wg_join(c, c->comm_stream));                             // ... and the weight gradients of this bucket launched on the side stream
-  float* g = (float*)n->grads.p + lo;
+  float* g = n->gw + lo;
   TRYI(all_reduce(c, 1, g, hi - lo, false, c->comm_stream));
   return 0;
 }
@@ -1499,7 +1504,7 @@ struct Backward {
     q.x = ps.raw0; q.relu_from_x = 1; q.pixels = spix; q.count = (double)spix; q.pool = &pool;
     StemWgradArgs w;
     memset(&w, 0, sizeof(w));
-    w.x = ps.x; w.x2 = ps.x2; w.n_split = ps.n_split; w.dy = dRaw0(); w.dw = (float*)n->grads.p + n->goff[0];
+    w.x = ps.x; w.x2 = ps.x2; w.n_split = ps.n_split; w.dy = dRaw0(); w.dw = n->gw + n->goff[0];
     w.N = N; w.H = ps.H; w.W = ps.W; w.OH = d.oh0; w.OW = d.ow0; w.in_f32 = ps.in_f32;
     if (!(n->rg[0] && c->fuse_stem_bwd)) {          // two kernels: the apply pass writes dRaw0, the weight gradient reads it
       q.dx = dRaw0();
@@ -1610,7 +1615,12 @@ int net_backward(sslcr_net* n, const float* dlogits, hipStream_t st) {
   if (n->last_npass == 0) return fail("sslcr_net_backward: no train-mode forward to differentiate");
   const int N = n->last_N, npass = n->last_npass;
   TRYI(n->grads.ensure(n->grad_count * sizeof(float)));
-  TRY(hipMemsetAsync(n->grads.p, 0, n->grad_count * sizeof(float), st));
+  // accumulating: this backward's gradient goes to the second buffer, and only over the range a backward can write
+  const bool acc = n->grad_accum && n->had_backward;
+  const size_t acc_lo = acc ? n->goff[lowest_trainable(n)] : 0;
+  if (acc) TRYI(n->gnew.ensure(n->grad_count * sizeof(float)));
+  n->gw = (float*)(acc ? n->gnew.p : n->grads.p);
+  TRY(hipMemsetAsync(n->gw + acc_lo, 0, (n->grad_count - acc_lo) * sizeof(float), st));
   const bool bb = lowest_trainable(n) < 60;
   if (bb) {
     TRYI(c->bn_ring.ensure((size_t)sslcr_ctx::kBnRing * sslcr_ctx::kBnSlot * sizeof(double)));
@@ -1628,6 +1638,11 @@ int net_backward(sslcr_net* n, const float* dlogits, hipStream_t st) {
   TRYI(wg_join(c, st));                       // the optimizer (and the next step's scratch writers) come after the side-stream wgrads
   c->wg_any = false;
   for (bool& pnd : c->wg_pending) pnd = false;
+  if (acc) {                                   // prev + new, behind every writer of `new` (the collectives included)
+    TRY(launch_grad_accumulate((float*)n->grads.p + acc_lo, n->gw + acc_lo, n->grad_count - acc_lo, st));
+    n->gw = (float*)n->grads.p;
+  }
+  n->had_backward = true;
   return 0;
 }
 
@@ -1853,7 +1868,7 @@ int sslcr_net_create(sslcr_ctx* c, const sslcr_net_desc* d, sslcr_net** out) {
 int sslcr_net_destroy(sslcr_net* n) {
   if (!n) return 0;
   (void)hipDeviceSynchronize();
-  n->shadow.release(); n->grads.release(); n->heads.release(); n->descs.release(); n->f8buf.release(); n->norm_ws.release();
+  n->shadow.release(); n->grads.release(); n->gnew.release(); n->heads.release(); n->descs.release(); n->f8buf.release(); n->norm_ws.release();
   for (int i = 0; i < 3; ++i) n->pass[i].mem.release();
   for (auto& row : n->tapbuf)
     for (DevBuf& b : row) b.release();
@@ -1900,6 +1915,12 @@ int sslcr_net_backward(sslcr_net* n, const float* dlogits, void* stream) {
 }
 
 int sslcr_net_segments_used(const sslcr_net* n) { return (n && n->last_segments) ? 1 : 0; }
+int sslcr_net_set_grad_accumulate(sslcr_net* n, int on) {
+  if (!n) return fail("sslcr_net_set_grad_accumulate: null net");
+  n->grad_accum = on != 0;
+  return 0;
+}
+
 int sslcr_net_debug_tap(sslcr_net* n, int on) {
   if (!n) return fail("sslcr_net_debug_tap: null net");
   n->tap = on != 0;

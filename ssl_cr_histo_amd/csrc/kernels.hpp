@@ -201,6 +201,8 @@ hipError_t launch_optimizer_chunks(const TensorDesc* d_descs, const void* d_chun
                                    const OptTable& tab, const float* coef, hipStream_t st);
 constexpr int GRAD_NORM_BLOCKS = 1024;   // workgroups of the sum-of-squares pass = doubles in `partials` (a multiple of 256)
 hipError_t launch_grad_norm(const float* g, size_t n, float max_norm, double* partials /* [GRAD_NORM_BLOCKS] */, float* out2, hipStream_t st);
+// dst[i] = dst[i] + src[i], i < n: any n, any two 4-byte-aligned bases (sslcr_grad_accumulate)
+hipError_t launch_grad_accumulate(float* dst, const float* src, size_t n, hipStream_t st);
 hipError_t launch_axpby(float* p, float* q, size_t n, float alpha, int copy_back, hipStream_t st);
 hipError_t launch_fill(float* p, size_t n, float v, hipStream_t st);
 hipError_t launch_pack_conv(int dtype, const PackArgs& a, hipStream_t st);

@@ -244,6 +244,43 @@ hipError_t launch_grad_norm(const float* g, size_t n, float max_norm, double* pa
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ gradient accumulation (autograd's `.grad +=`)
+// dst[i] = dst[i] + src[i]: one fp32 add per element, nothing to contract or reassociate, no LDS, no atomics -- every element has one
+// writer, so the bits are the same on every run and on every rank that holds the same two buffers.  Cut as grad_sumsq_kernel cuts its
+// buffer, on 16-byte boundaries of the DESTINATION address: the up-to-3 elements in front of the first boundary and the up-to-3
+// behind the last whole quad are scalars of workgroup 0, the body is whole float4 quads walked with a grid stride (the
+// elementwise family's grid: launch_grad_accumulate).  dst and src may sit at different offsets mod 16: the source quad is then
+// only 4-byte aligned, which global_load_dwordx4 serves (its type says so; the destination's load and store are aligned).
+typedef float f32x4_a4_t __attribute__((ext_vector_type(4), aligned(4)));
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ dst, const float* __restrict__ src, size_t n) {
+  size_t head = ((16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15) / 4;
+  if (head > n) head = n;
+  const size_t quads = (n - head) / 4;                                     // whole destination-aligned quads behind the head
+  float4* __restrict__ dv = reinterpret_cast<float4*>(dst + head);
+  const f32x4_a4_t* __restrict__ sv = reinterpret_cast<const f32x4_a4_t*>(src + head);
+  const size_t stride = (size_t)gridDim.x * 256;
+  for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += stride) {
+    float4 a = dv[q];
+    const f32x4_a4_t b = __builtin_nontemporal_load(sv + q);               // read once; the sum is what the optimizer reads next
+    a.x = a.x + b.x; a.y = a.y + b.y; a.z = a.z + b.z; a.w = a.w + b.w;
+    dv[q] = a;
+  }
+  if (blockIdx.x == 0) {
+    const size_t t = threadIdx.x, tail0 = head + quads * 4;
+    if (t < head) dst[t] = dst[t] + src[t];
+    if (tail0 + t < n) dst[tail0 + t] = dst[tail0 + t] + src[tail0 + t];
+  }
+}
+hipError_t launch_grad_accumulate(float* dst, const float* src, size_t n, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  // three workgroups per CU at most, as bn_eltwise.hip's ew_grid(): one quad per thread and trip
+  const size_t cap = 3 * (size_t)device_cus();
+  size_t b = (n / 4 + 255) / 256;
+  b = b < 1 ? 1 : (b > cap ? cap : b);
+  hipLaunchKernelGGL(grad_accumulate_kernel, dim3((int)b), dim3(256), 0, st, dst, src, n);
+  return hipGetLastError();
+}
+
 __global__ __launch_bounds__(256) void axpby_kernel(float* p, float* q, size_t n, float alpha, int copy_back) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
     const float v = alpha * p[i] + (1.f - alpha) * q[i];

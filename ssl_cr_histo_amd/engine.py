@@ -50,6 +50,7 @@ _ENGINE_SIGS = {
     "sslcr_net_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sslcr_net_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sslcr_net_set_grad_accumulate": (C.c_int, [C.c_void_p, C.c_int]),
     "sslcr_net_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "sslcr_net_debug_tap": (C.c_int, [C.c_void_p, C.c_int]),
     "sslcr_net_segments_used": (C.c_int, [C.c_void_p]),
@@ -222,7 +223,25 @@ class BoundNet:
             self._note_buffers_changed()
         return feats, logits
 
-    def backward(self, dlogits):
+    def set_grad_accumulate(self, on):
+        """Gradient accumulation, torch's ``loss.backward()`` without ``optimizer.zero_grad()``.  Sticky: every later backward of
+        this net (``backward`` and the backward leg of ``Engine.step_ssl_cr`` / ``step_supervised``, which set it from their own
+        ``accumulate`` argument) leaves ``prev + new`` in the gradient buffer, elementwise in fp32, where ``prev`` is what the
+        buffer held on entry and ``new`` what this backward alone would have left.  ``grad()``, ``grad_norm()`` and
+        ``optimizer_step()`` (clipping included) see the sum.  A net without an earlier backward has no ``prev``: on is off there.
+
+        * Train-mode BatchNorm uses each micro-batch's own statistics: the reference's per-replica statistics under
+          ``nn.DataParallel``.
+        * Running statistics and ``num_batches_tracked`` are updated by every micro-step in turn, as k successive torch forwards
+          would; ``DataParallel`` keeps replica 0's only.
+        * Nothing clears the buffer for the caller: accumulating onto a gradient that an optimizer step has already consumed
+          adds to that stale gradient, as torch does without ``zero_grad``."""
+        L.check(L.lib().sslcr_net_set_grad_accumulate(self.handle, int(bool(on))))
+
+    def backward(self, dlogits, accumulate=False):
+        """backward of the last train-mode forward from d(loss)/d(logits).  accumulate: see ``set_grad_accumulate`` (set on every
+        call, so the default stays off)."""
+        self.set_grad_accumulate(accumulate)
         L.check(L.lib().sslcr_net_backward(self.handle, L.ptr(dlogits.contiguous()), L.stream_ptr()))
 
     def grad(self, index):
@@ -443,11 +462,18 @@ class Engine:
         return self._dummy_cls
 
     # ------------------------------------------------------------------ fused steps
-    def step_ssl_cr(self, teacher, student, kind, x, y, u_w, u_s, lambda_u, backward=True, nx_global=None, nu_global=None):
+    def step_ssl_cr(self, teacher, student, kind, x, y, u_w, u_s, lambda_u, backward=True, nx_global=None, nu_global=None,
+                    accumulate=False):
         """one consistency-training iteration (eval_BreastPathQ_SSL_CR.py:65-100 / eval_Camelyon_SSL_CR.py:94-121).
         x [nx,3,H,W], u_w/u_s [nu,3,H,W] uint8|fp32; y [nx] fp32 (kind 'mse') or int64 (kind 'ce').
         -> dict(losses [4] device tensor: loss, loss_x, loss_u, #correct ; feats ; logits ; logits_t).  With more than one rank the
-        losses are this rank's share (scaled by 1/global-count; the SUM over ranks is the global value) -- no collective per step."""
+        losses are this rank's share (scaled by 1/global-count; the SUM over ranks is the global value) -- no collective per step.
+        accumulate: the student's gradients are ADDED to what its buffer holds (``BoundNet.set_grad_accumulate``, set on every call:
+        the default clears first).  A micro-batch is a shard in time: pass the full batch's counts as nx_global / nu_global, then
+        the sums of k micro-steps' gradients and losses are the global batch's -- with each micro-batch's own BatchNorm statistics
+        (per-replica statistics under ``nn.DataParallel``), running statistics updated by every micro-step in turn (``DataParallel``
+        keeps replica 0's), and no clearing of a gradient left from before an optimizer step."""
+        student.set_grad_accumulate(accumulate)
         teacher.sync()
         student.sync()
         x, u_w, u_s = self.as_input(x), self.as_input(u_w), self.as_input(u_s)
@@ -476,9 +502,12 @@ class Engine:
         student._note_buffers_changed()
         return dict(losses=losses, feats=feats, logits=logits, logits_t=logits_t)
 
-    def step_supervised(self, net, kind, xs, y, train=True, backward=True, n_global=None):
+    def step_supervised(self, net, kind, xs, y, train=True, backward=True, n_global=None, accumulate=False):
         """student-only step: RSP pretraining (TripletNet, 3 inputs, 'ce'; pretrain_BreastPathQ.py:42-61), supervised
-        fine-tuning (eval_Camelyon_SSL.py:52-98 'ce', eval_BreastPathQ_SSL.py:52-84 'mse') and every validate()."""
+        fine-tuning (eval_Camelyon_SSL.py:52-98 'ce', eval_BreastPathQ_SSL.py:52-84 'mse') and every validate().
+        accumulate: as in ``step_ssl_cr`` (gradients added to the buffer; n_global = the full batch's count; per-micro-batch
+        BatchNorm statistics, running statistics updated every micro-step, stale gradients are not cleared)."""
+        net.set_grad_accumulate(accumulate)
         net.sync()
         xs = [self.as_input(x) for x in xs]
         n, _, H, W = xs[0].shape

@@ -446,3 +446,16 @@ def grad_norm(flat, max_norm=float("inf")):
     out2 = torch.empty(2, dtype=torch.float32, device=flat.device)
     L.check(L.lib().sslcr_grad_norm(L.ptr(flat), flat.numel(), float(max_norm), L.ptr(partials), L.ptr(out2), L.stream_ptr()))
     return out2
+
+
+def grad_accumulate(dst, src):
+    """dst += src in place for two dense 1-D fp32 device tensors of one length (any length, any 4-byte-aligned views, which may sit
+    at different offsets mod 16 and must not overlap): one IEEE fp32 add per element, autograd's ``.grad +=``
+    (sslcr_grad_accumulate).  -> dst.  No sync."""
+    for t in (dst, src):
+        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 1 or (t.numel() > 1 and t.stride(0) != 1):
+            raise L.SslcrError("grad_accumulate: dense 1-D fp32 device tensors expected (no CPU fallback)")
+    if dst.numel() != src.numel() or dst.device != src.device:
+        raise L.SslcrError(f"grad_accumulate: dst has {dst.numel()} elements on {dst.device}, src {src.numel()} on {src.device}")
+    L.check(L.lib().sslcr_grad_accumulate(L.ptr(dst), L.ptr(src), dst.numel(), L.stream_ptr()))
+    return dst

@@ -4,6 +4,17 @@ optimizer launch.  Loaders are any iterables yielding the reference's batch tupl
 CPU or GPU.  Differences from the reference loops that do not change results: no per-iteration ``.item()`` host syncs
 (meters are filled from device scalars at print/epoch boundaries) and features are concatenated once, not per step.
 
+Gradient accumulation: every ``*_train`` reads ``k = getattr(args, "micro_batches", 1)`` (``validate()`` functions ignore it).  With
+k > 1 each loader batch is cut into k contiguous micro-batches (``micro_ranges``; labeled and unlabeled rows separately), micro-step j
+runs with the FULL batch's counts as its global counts and adds its gradients to those of the steps before it (j > 0), and ONE
+optimizer step (with ``args.clip_grad_norm`` on the accumulated gradient) follows: the reference's global batch on a card that cannot
+hold it.  The return tuples keep their shapes.  What this is, exactly:
+  * train-mode BatchNorm uses each micro-batch's own statistics -- the reference's per-replica statistics under ``nn.DataParallel``;
+  * running statistics and ``num_batches_tracked`` are updated by every micro-step in turn, as k successive torch forwards would
+    (``DataParallel`` keeps replica 0's only);
+  * the first micro-step of a batch clears the buffer; anybody who calls the engine with ``accumulate=True`` on a buffer left from
+    before an optimizer step adds to that stale gradient, as torch does without ``zero_grad``.
+
 reference                                   here
 eval_BreastPathQ_SSL_CR.train/validate      bpq_cr_train / bpq_cr_validate      (:37-128 / :131-175)
 eval_Camelyon_SSL_CR.train/validate         cam_cr_train / cam_cr_validate      (:33-157 / :160-225)
@@ -17,6 +28,7 @@ import time
 
 import torch
 
+from .dist import shard_range
 from .engine import get_engine
 from .util import AverageMeter
 
@@ -139,6 +151,58 @@ def _ahead(batches, eng, enabled):
         yield cur
 
 
+def micro_ranges(n, k):
+    """[(lo, hi)] * k: the contiguous micro-batches of a batch of n rows -- ``dist.shard_range(n, j, k)``, remainders to the lowest
+    (a micro-batch is a shard in time).  Pure host logic.  k > n (an empty micro-batch) raises ValueError."""
+    k = int(k)
+    if k < 1 or k > n:
+        raise ValueError(f"micro_batches = {k} does not cut a batch of {n} rows into non-empty micro-batches")
+    return [shard_range(n, j, k) for j in range(k)]
+
+
+def _micro_k(args):
+    """args.micro_batches; absent (or None) = 1: one engine step per loader batch, the code path of every earlier version."""
+    k = getattr(args, "micro_batches", 1)
+    return 1 if k is None else int(k)
+
+
+def _sum_losses(parts):
+    # micro-step j's losses are its share of the global-batch values (scaled by 1 / global count), #correct a count: both add.
+    # On the device, no host sync
+    return torch.stack([p["losses"] for p in parts]).sum(0)
+
+
+def _ssl_cr_step(eng, te, st, kind, x, y, u_w, u_s, lambda_u, k):
+    """one loader batch of a consistency-training loop as k accumulated micro-steps (k == 1: the plain engine step).  Rows of the
+    returned feats / logits / logits_t are in the order the single step returns them: all labeled rows, then all unlabeled."""
+    if k == 1:
+        return eng.step_ssl_cr(te, st, kind, x, y, u_w, u_s, lambda_u)
+    nx, nu = x.shape[0], u_w.shape[0]
+    if k > nx or k > nu:
+        raise ValueError(f"micro_batches = {k} exceeds the batch: nx = {nx} labeled, nu = {nu} unlabeled rows")
+    parts = []
+    for j, ((a, b), (c, d)) in enumerate(zip(micro_ranges(nx, k), micro_ranges(nu, k))):
+        parts.append(eng.step_ssl_cr(te, st, kind, x[a:b], y[a:b], u_w[c:d], u_s[c:d], lambda_u, nx_global=nx * eng.world,
+                                     nu_global=nu * eng.world, accumulate=j > 0))
+    nxj = [b - a for a, b in micro_ranges(nx, k)]                    # a part's rows: its nxj labeled ones, then its unlabeled ones
+    out = {key: torch.cat([p[key][:n] for p, n in zip(parts, nxj)] + [p[key][n:] for p, n in zip(parts, nxj)]) for key in ("feats", "logits")}
+    out["logits_t"] = torch.cat([p["logits_t"] for p in parts])
+    out["losses"] = _sum_losses(parts)
+    return out
+
+
+def _sup_step(eng, net, kind, xs, y, k):
+    """one loader batch of a student-only training loop as k accumulated micro-steps (k == 1: the plain engine step)."""
+    if k == 1:
+        return eng.step_supervised(net, kind, xs, y, train=True)
+    n = xs[0].shape[0]
+    if k > n:
+        raise ValueError(f"micro_batches = {k} exceeds the batch: n = {n} rows")
+    parts = [eng.step_supervised(net, kind, [x[a:b] for x in xs], y[a:b], train=True, n_global=n * eng.world, accumulate=j > 0)
+             for j, (a, b) in enumerate(micro_ranges(n, k))]
+    return dict(losses=_sum_losses(parts), feats=torch.cat([p["feats"] for p in parts]), logits=torch.cat([p["logits"] for p in parts]))
+
+
 def _device_of(model):
     return next(model.parameters()).device
 
@@ -170,13 +234,14 @@ def bpq_cr_train(args, model_teacher, model_student, classifier_teacher, classif
     te, st = eng.bind(model_teacher, classifier_teacher), eng.bind(model_student, classifier_student)
     meters = _meters(eng, ["loss", "loss_x", "loss_u"])
     feats, targets = [], []
+    k = _micro_k(args)
     t0 = time.time()
     for batch_idx, (data_x, data_u) in enumerate(_ahead(zip(labeled_train_loader, unlabeled_train_loader), eng, _prefetch_on(args))):
         inputs_x, targets_x = data_x
         inputs_u_w, inputs_u_s = data_u
         inputs_x = inputs_x.reshape(-1, 3, 256, 256)                         # :74 (hard-coded by the reference)
         targets_x = targets_x.float().to(eng.device)
-        r = eng.step_ssl_cr(te, st, "mse", inputs_x, targets_x.reshape(-1), inputs_u_w, inputs_u_s, args.lambda_u)
+        r = _ssl_cr_step(eng, te, st, "mse", inputs_x, targets_x.reshape(-1), inputs_u_w, inputs_u_s, args.lambda_u, k)
         st.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         meters.add(r["losses"], inputs_x.shape[0])
         feats.append(r["feats"])
@@ -217,6 +282,7 @@ def cam_cr_train(args, model_teacher, model_student, classifier_teacher, classif
     te, st = eng.bind(model_teacher, classifier_teacher), eng.bind(model_student, classifier_student)
     meters = _meters(eng, ["loss", "loss_x", "loss_u", "acc"])
     feats, targets = [], []
+    k = _micro_k(args)
     t0 = time.time()
     S = args.image_size
     loaders = zip(tumor_labeled_train_loader, normal_labeled_train_loader, tumor_unlabeled_train_loader,
@@ -233,7 +299,7 @@ def cam_cr_train(args, model_teacher, model_student, classifier_teacher, classif
         p_us = torch.randperm(2 * len(t_us))
         x, y = _cat_shuffle(t_x, n_x, p_x.to(t_x.device)), _cat_shuffle(t_y, n_y, p_x.to(t_y.device)).long()
         u_w, u_s = _cat_shuffle(t_uw, n_uw, p_uw.to(t_uw.device)), _cat_shuffle(t_us, n_us, p_us.to(t_us.device))
-        r = eng.step_ssl_cr(te, st, "ce", x, y, u_w, u_s, args.lambda_u)
+        r = _ssl_cr_step(eng, te, st, "ce", x, y, u_w, u_s, args.lambda_u, k)
         st.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         n = x.shape[0]
         meters.add(r["losses"], n)
@@ -277,13 +343,14 @@ def kather_cr_train(args, model_teacher, model_student, classifier_teacher, clas
         m.train()
     te, st = eng.bind(model_teacher, classifier_teacher), eng.bind(model_student, classifier_student)
     meters = _meters(eng, ["loss", "loss_x", "loss_u", "acc"])
+    k = _micro_k(args)
     t0 = time.time()
     for batch_idx, (data_x, data_u) in enumerate(_ahead(zip(labeled_train_loader, unlabeled_train_loader), eng, _prefetch_on(args))):
         inputs_x, targets_x = data_x
         inputs_u_w, inputs_u_s = data_u
         inputs_x = inputs_x.reshape(-1, 3, 256, 256)                          # :68
         targets_x = targets_x.reshape(-1).long()                              # :69
-        r = eng.step_ssl_cr(te, st, "ce", inputs_x, targets_x, inputs_u_w, inputs_u_s, args.lambda_u)
+        r = _ssl_cr_step(eng, te, st, "ce", inputs_x, targets_x, inputs_u_w, inputs_u_s, args.lambda_u, k)
         st.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         meters.add(r["losses"], inputs_x.shape[0])
         _maybe_print(args, batch_idx, "Train", epoch, _len(labeled_train_loader), t0, meters)
@@ -327,11 +394,12 @@ def _rsp_epoch(args, model, classifier, loader, criterion, optimizer, epoch, tra
     net = eng.bind(model, classifier)
     meters = _meters(eng, ["loss", "acc"])
     feats, targets = [], []
+    k = _micro_k(args) if train else 1
     t0 = time.time()
     for batch_idx, (input1, input2, input3, target) in enumerate(_ahead(loader, eng, _prefetch_on(args))):
         i1, i2, i3 = (v.reshape(-1, 3, args.tile_h, args.tile_w) for v in (input1, input2, input3))
         target = target.long().view(-1, 1).reshape(-1)
-        r = eng.step_supervised(net, "ce", [i1, i2, i3], target, train=train)
+        r = _sup_step(eng, net, "ce", [i1, i2, i3], target, k) if train else eng.step_supervised(net, "ce", [i1, i2, i3], target, train=False)
         if train:
             net.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         meters.add(r["losses"], target.size(0))
@@ -363,6 +431,7 @@ def cam_sup_train(args, model, classifier, tumor_labeled_train_loader, normal_la
     net = eng.bind(model, classifier)
     meters = _meters(eng, ["loss", "acc"])
     feats, targets = [], []
+    k = _micro_k(args)
     S = args.image_size
     for batch_idx, (tumor_data_x, normal_data_x) in enumerate(_ahead(zip(tumor_labeled_train_loader, normal_labeled_train_loader), eng,
                                                                      _prefetch_on(args))):
@@ -372,7 +441,7 @@ def cam_sup_train(args, model, classifier, tumor_labeled_train_loader, normal_la
         n_x, n_y = n_x.reshape(-1, 3, S, S), n_y.reshape(-1)
         perm = torch.randperm(2 * len(t_x))
         x, y = _cat_shuffle(t_x, n_x, perm.to(t_x.device)), _cat_shuffle(t_y, n_y, perm.to(t_y.device)).long()
-        r = eng.step_supervised(net, "ce", [x], y, train=True)
+        r = _sup_step(eng, net, "ce", [x], y, k)
         net.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         meters.add(r["losses"], x.shape[0])
         feats.append(r["feats"])
@@ -391,10 +460,11 @@ def bpq_sup_train(args, model, classifier, train_loader, criterion, optimizer, e
     net = eng.bind(model, classifier)
     meters = _meters(eng, ["loss"])
     feats, targets = [], []
+    k = _micro_k(args)
     for batch_idx, (input1, target) in enumerate(_ahead(train_loader, eng, _prefetch_on(args))):
         x = input1.reshape(-1, 3, args.image_size, args.image_size)
         y = target.float().reshape(-1)
-        r = eng.step_supervised(net, "mse", [x], y, train=True)
+        r = _sup_step(eng, net, "mse", [x], y, k)
         net.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         meters.add(r["losses"], y.size(0))
         feats.append(r["feats"])
@@ -411,10 +481,11 @@ def kather_sup_train(args, model, classifier, train_loader, criterion, optimizer
     classifier.train()
     net = eng.bind(model, classifier)
     meters = _meters(eng, ["loss", "acc"])
+    k = _micro_k(args)
     for batch_idx, (input, target) in enumerate(_ahead(train_loader, eng, _prefetch_on(args))):
         x = input.reshape(-1, 3, args.image_size, args.image_size)                   # :57
         y = target.reshape(-1).long()
-        r = eng.step_supervised(net, "ce", [x], y, train=True)
+        r = _sup_step(eng, net, "ce", [x], y, k)
         net.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         meters.add(r["losses"], y.size(0))
     m = meters.meters()
