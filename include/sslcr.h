@@ -29,11 +29,12 @@ extern "C" {
 #define SSLCR_BF16 1
 #define SSLCR_FP8 2   /* engine mode only (sslcr_create): bf16 storage and backward, fp8 e4m3 forward for the eligible 3x3 convs */
 
-/* the library round (9 here).  ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
+/* the library round (10 here).  ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
  * 7 = sslcr_randaug_v2_slot added (nothing else changed); 8 = optimizer parameter groups, AdamW and the global gradient norm
  * (sslcr_tensor_desc.group, sslcr_opt_desc.kind 2, sslcr_optimizer_step_groups, sslcr_grad_norm, sslcr_net_optimizer_step_groups,
  * sslcr_net_grad_norm: all additive); 9 = gradient accumulation (sslcr_grad_accumulate, sslcr_net_set_grad_accumulate: additive,
- * off by default). */
+ * off by default); 10 = loss options (sslcr_loss_opts, sslcr_loss_ex, sslcr_ce_denominator, sslcr_net_set_loss_opts: additive, the
+ * defaults issue the launches of version 9). */
 int sslcr_version(void);
 const char* sslcr_last_error(void);
 
@@ -287,6 +288,48 @@ typedef struct sslcr_loss_desc {
   float inv_nx_global, inv_nu_global;
 } sslcr_loss_desc;
 int sslcr_loss(const sslcr_loss_desc* d, void* stream);
+/* library version >= 10.  Options of the cross-entropy kinds (1, 2); sslcr_loss and its launch are unchanged.
+ * Supervised rows -- torch.nn.functional.cross_entropy(logits_x, target, weight=, label_smoothing=, ignore_index=, reduction='mean')
+ * with the three taken together as torch defines them:
+ *   loss_x = [ (1 - eps) * sum_i w[y_i] * (-log p_i[y_i])  +  eps / C * sum_i sum_c w[c] * (-log p_i[c]) ] / denominator
+ * over the rows whose target is not ignore_index, denominator = sum_i w[y_i] over the same rows.  An ignored row has zero loss and
+ * zero dlogits and is never counted in out[3].  denominator == 0 (every row ignored, or only zero-weight classes present): loss_x
+ * and loss are NaN and the dlogits of the rows that are not ignored are NaN, those of ignored rows zero -- torch's 0 / 0.  A
+ * target outside [0, C) that is not ignore_index (torch raises) is never read out of bounds: the row has no loss and zero dlogits,
+ * and it makes the denominator -- out2[0] of sslcr_ce_denominator too -- and with it loss_x, loss and the kept rows' dlogits NaN,
+ * the signal a loop can see without a sync.
+ * Consistency rows (kind 1 only; weight / smoothing / ignore_index do not apply to them, as in the reference):
+ *   mask_i = max_c softmax(logits_t_i)_c >= threshold          (FixMatch: `max_probs.ge(threshold)`; eval_Camelyon_SSL_CR.py:113
+ *                                                               computes max_probs and drops it)
+ *   loss_u = sum_i mask_i * CE_i * inv_nu_global               (`(loss * mask).mean()`: ALL unlabeled rows divide, so the term stays
+ *                                                               linear over micro-batches and ranks)
+ *   temperature 0: CE_i against the hard pseudo label argmax(logits_t_i) (sslcr_loss's arithmetic); T > 0: against the soft
+ *   targets p = softmax(logits_t_i / T) (UDA sharpening): CE_i = -sum_c p_c log softmax(logits_s_i)_c, gradient softmax(logits_s_i) - p.
+ *   The mask always reads the unsharpened softmax; at threshold 0 no test is made at all (a teacher row with a NaN propagates it,
+ *   as in sslcr_loss). */
+typedef struct sslcr_loss_opts {
+  const float* class_weight;  /* device [C] or NULL: F.cross_entropy(weight=) */
+  float label_smoothing;      /* eps in [0, 1): F.cross_entropy(label_smoothing=) */
+  int ignore_index;           /* F.cross_entropy(ignore_index=); -100 = torch's default */
+  float threshold;            /* tau in [0, 1]; 0 = no mask */
+  float temperature;          /* T >= 0; 0 = hard pseudo labels */
+  const float* denominator;   /* device [1] or NULL.  NULL: with class_weight, a non-default ignore_index or rows that carry the
+                                 default -100 the kernel sums w[y_i] over the kept rows of THIS call (sslcr_ce_denominator's order
+                                 and bits), else it scales by inv_nx_global as sslcr_loss does.  Non-NULL: the divisor of the supervised term, read on the device --
+                                 out2 of sslcr_ce_denominator over the whole global batch (all-reduced when sharded) when this call
+                                 holds a micro-batch or a shard of it. */
+  float* stats;               /* device [2] or NULL: {#rows with mask_i = 1, sum_i max_c softmax(logits_t_i)_c} of this call */
+} sslcr_loss_opts;
+/* opts == NULL: sslcr_loss.  All-default opts (NULL pointers, 0, -100, 0, 0): sslcr_loss's bits for all five kinds -- the MSE kinds
+ * by its launch, the cross-entropy kinds by this entry's kernel, whose default arithmetic is the same and which, unlike sslcr_loss
+ * (every target must be a class id there), leaves out rows labelled -100.  Errors, decided before any launch: kinds 0 / 3 with a non-default option, C > 64, label_smoothing outside [0, 1), threshold outside [0, 1],
+ * temperature < 0, threshold / temperature with kind 2.  One single-workgroup launch; row counts of any size are served. */
+int sslcr_loss_ex(const sslcr_loss_desc* d, const sslcr_loss_opts* opts, void* stream);
+/* library version >= 10.  The divisor of a weighted / ignore-index mean from the targets alone:
+ *   out2 = { sum_i class_weight[target_i[i]] (1 per row when class_weight is NULL), number of such rows }
+ * over the rows with target != ignore_index -- `weight[target[target != ignore_index]].sum()`.  n >= 0.  One launch, no atomics, summed in
+ * double in a fixed order: the same bits every run, and the bits sslcr_loss_ex derives for itself over the same rows. */
+int sslcr_ce_denominator(const int64_t* target_i, int n, int C, const float* class_weight, int ignore_index, float* out2, void* stream);
 /* out[i] = softmax(logits[i, 0..C-1])[col]: the per-tile 'tumor' probability of test_Camelyon16.py:58-60 (row f3) */
 int sslcr_softmax_col(const float* logits, float* out, int n, int C, int col, void* stream);
 
@@ -526,6 +569,13 @@ int sslcr_net_backward(sslcr_net* net, const float* dlogits, void* stream);
  *       A net that has had no backward since sslcr_net_create has no prev: its first backward behaves as off.
  * The sum lives in the buffer sslcr_net_grad, sslcr_net_grad_norm and the optimizer entries read: they see it unchanged. */
 int sslcr_net_set_grad_accumulate(sslcr_net* net, int on);
+/* library version >= 10.  The options of the loss leg of sslcr_step_ssl_cr (the student's) and sslcr_step_supervised (train = 0: the
+ * weighted validation loss).  Sticky, like sslcr_net_set_grad_accumulate; NULL sets the defaults, with which the steps issue the
+ * launches they have always issued (sslcr_loss's kernel, which expects every target to be a class id: a row labelled -100 is left
+ * out only once an option, or a stats / denominator pointer, is set).  The struct is copied; the device memory its pointers name stays the
+ * caller's and must live until the last step that uses it has run.  A step of an MSE kind (0, 3) on a net with non-default options
+ * is an error, as is an option sslcr_loss_ex refuses for the net's class count. */
+int sslcr_net_set_loss_opts(sslcr_net* net, const sslcr_loss_opts* opts);
 int sslcr_net_grad(sslcr_net* net, int param_index, float* out, void* stream);      /* -> PyTorch layout */
 /* diagnostics for the layer-wise backward parity test (tests/test_backward_replay_gpu.py): autograd of one BasicBlock of
  * torchvision resnet18 (reached from models/net.py:32,77) checked kernel by kernel at the size the step really runs.  With the tap

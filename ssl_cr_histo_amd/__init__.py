@@ -5,6 +5,7 @@ missing (there is no PyTorch/CPU fallback for the compute).
 """
 from . import net  # noqa: F401
 from .net import Classifier, FinetuneResNet, TripletNet, TripletNet_Finetune  # noqa: F401
+from .kernels import LossOptions  # noqa: F401
 from .util import AverageMeter  # noqa: F401
 
-__all__ = ["net", "Classifier", "FinetuneResNet", "TripletNet", "TripletNet_Finetune", "AverageMeter"]
+__all__ = ["net", "Classifier", "FinetuneResNet", "TripletNet", "TripletNet_Finetune", "AverageMeter", "LossOptions"]

@@ -53,6 +53,8 @@ BnBwdDesc = _S("BnBwdDesc", [("dy", vp), ("x", vp), ("yact", vp), ("scale", vp),
 LossDesc = _S("LossDesc", [("kind", i32), ("logits", vp), ("logits_t", vp), ("target_f", vp), ("target_i", vp),
                            ("dlogits", vp), ("out", vp), ("nx", i32), ("nu", i32), ("C", i32), ("lambda_u", f32),
                            ("inv_nx_global", f32), ("inv_nu_global", f32)])
+LossOpts = _S("LossOpts", [("class_weight", vp), ("label_smoothing", f32), ("ignore_index", i32), ("threshold", f32),
+                           ("temperature", f32), ("denominator", vp), ("stats", vp)])
 TensorDesc = _S("TensorDesc", [("p", vp), ("g", vp), ("s1", vp), ("s2", vp), ("n", i32), ("K", i32), ("C", i32),
                                ("RS", i32), ("w_fwd", vp), ("w_dgrad", vp), ("pack_dtype", i32), ("dgrad_flip", i32),
                                ("group", i32)])
@@ -109,6 +111,8 @@ SIGNATURES = {
     "sslcr_linear_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "sslcr_linear_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "sslcr_loss": (i32, [P(LossDesc), vp]),
+    "sslcr_loss_ex": (i32, [P(LossDesc), P(LossOpts), vp]),
+    "sslcr_ce_denominator": (i32, [vp, i32, i32, vp, i32, vp, vp]),
     "sslcr_softmax_col": (i32, [vp, vp, i32, i32, i32, vp]),
     "sslcr_optimizer_step": (i32, [vp, i32, i32, P(OptDesc), vp]),
     "sslcr_optimizer_step_groups": (i32, [vp, i32, i32, P(OptDesc), i32, vp, vp]),

@@ -30,7 +30,7 @@ using namespace sslcr;
 
 extern "C" {
 
-int sslcr_version(void) { return 9; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
+int sslcr_version(void) { return 10; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
 const char* sslcr_last_error(void) { return g_err; }
 
 int sslcr_conv2d(int dtype, const sslcr_conv_desc* d, void* stream) {
@@ -180,6 +180,23 @@ int sslcr_linear_bwd(const float* x, const float* w, const float* dy, const floa
 int sslcr_loss(const sslcr_loss_desc* d, void* stream) {
   NEED(d && d->logits && d->out && d->nx > 0 && d->C > 0 && d->C <= 64, "args");
   return check(launch_loss(*d, (hipStream_t)stream), "loss");
+}
+
+int sslcr_loss_ex(const sslcr_loss_desc* d, const sslcr_loss_opts* o, void* stream) {
+  if (!o) return sslcr_loss(d, stream);
+  NEED(d && d->logits && d->out && d->nx > 0 && d->C > 0 && d->C <= 64, "args");
+  const char* why = loss_opts_error(d->kind, d->C, *o);
+  if (why) return fail("sslcr_loss_ex: invalid argument (%s)", why);
+  // the MSE kinds have no options: sslcr_loss's own launch.  The cross-entropy kinds take the new kernel whenever opts is given --
+  // its default arithmetic is loss_kernel's, bit for bit, and rows that carry the default ignore_index are honoured
+  if (d->kind != 1 && d->kind != 2) return check(launch_loss(*d, (hipStream_t)stream), "loss");
+  NEED(d->target_i && (d->kind == 2 || d->nu == 0 || d->logits_t), "cross-entropy needs target_i (and logits_t for the consistency rows)");
+  NEED(d->nu >= 0, "nu");
+  return check(launch_loss_ex(*d, *o, (hipStream_t)stream), "loss_ex");
+}
+int sslcr_ce_denominator(const int64_t* target_i, int n, int C, const float* class_weight, int ignore_index, float* out2, void* stream) {
+  NEED(out2 && (target_i || n == 0) && n >= 0 && C > 0 && C <= 64, "args");
+  return check(launch_ce_denominator(target_i, n, C, class_weight, ignore_index, out2, (hipStream_t)stream), "ce_denominator");
 }
 
 int sslcr_softmax_col(const float* logits, float* out, int n, int C, int col, void* stream) {

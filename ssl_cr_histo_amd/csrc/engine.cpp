@@ -227,6 +227,7 @@ struct sslcr_net {
   DevBuf gnew;
   float* gw = nullptr;
   bool grad_accum = false, had_backward = false;
+  LossOpts lopts = loss_opts_default();      // sslcr_net_set_loss_opts: the loss leg of the step entries (defaults: launch_loss itself)
   PassState pass[3];
   bool ybits_ok = false;         // the passes' mask bits are allocated back to back (what the segment forms assume)
   // heads state (fp32)
@@ -1921,6 +1922,27 @@ int sslcr_net_set_grad_accumulate(sslcr_net* n, int on) {
   return 0;
 }
 
+int sslcr_net_set_loss_opts(sslcr_net* n, const sslcr_loss_opts* o) {
+  if (!n) return fail("sslcr_net_set_loss_opts: null net");
+  if (o) {
+    const char* why = loss_opts_error(1, n->ncls, *o);      // the ranges; what a step's kind refuses is that step's error
+    if (why) return fail("sslcr_net_set_loss_opts: invalid argument (%s)", why);
+  }
+  n->lopts = o ? *o : loss_opts_default();
+  return 0;
+}
+// the loss leg of the step entries: launch_loss itself unless the net carries options
+static int step_loss(sslcr_net* n, const LossArgs& L, const char* who, hipStream_t st) {
+  if (loss_opts_is_default(n->lopts)) {
+    TRY(launch_loss(L, st));
+    return 0;
+  }
+  const char* why = loss_opts_error(L.kind, L.C, n->lopts);
+  if (why) return fail("%s: %s (sslcr_net_set_loss_opts)", who, why);
+  TRY(launch_loss_ex(L, n->lopts, st));
+  return 0;
+}
+
 int sslcr_net_debug_tap(sslcr_net* n, int on) {
   if (!n) return fail("sslcr_net_debug_tap: null net");
   n->tap = on != 0;
@@ -2191,7 +2213,7 @@ int sslcr_step_ssl_cr(sslcr_net* te, sslcr_net* stn, const sslcr_ssl_cr_desc* d,
   L.inv_nu_global = 1.f / (float)(d->nu_global > 0 ? d->nu_global : d->nu);
   if (d->kind == 0 && !d->target_f) return fail("sslcr_step_ssl_cr: mse needs target_f");
   if (d->kind == 1 && !d->target_i) return fail("sslcr_step_ssl_cr: ce needs target_i");
-  TRY(launch_loss(L, st));
+  TRYI(step_loss(stn, L, "sslcr_step_ssl_cr", st));
   if (d->logits_t) TRY(hipMemcpyAsync(d->logits_t, stn->logits_t, (size_t)d->nu * stn->ncls * 4, hipMemcpyDeviceToDevice, st));
   if (d->backward) TRYI(net_backward(stn, stn->dlogits, st));
   return 0;
@@ -2211,7 +2233,7 @@ int sslcr_step_supervised(sslcr_net* n, const sslcr_sup_desc* d, void* stream) {
   L.inv_nx_global = 1.f / (float)(d->n_global > 0 ? d->n_global : d->n); L.inv_nu_global = 1.f;
   if (d->kind == 3 && !d->target_f) return fail("sslcr_step_supervised: mse needs target_f");
   if (d->kind == 2 && !d->target_i) return fail("sslcr_step_supervised: ce needs target_i");
-  TRY(launch_loss(L, st));
+  TRYI(step_loss(n, L, "sslcr_step_supervised", st));
   if (d->train && d->backward) TRYI(net_backward(n, n->dlogits, st));
   return 0;
 }

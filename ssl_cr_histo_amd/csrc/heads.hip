@@ -324,6 +324,165 @@ __global__ __launch_bounds__(256) void loss_kernel(const LossArgs a) {
   }
 }
 
+// ------------------------------------------------------------------ loss options (sslcr_loss_ex): weighted / smoothed / ignore-index
+// cross-entropy on the supervised rows, confidence mask and temperature-sharpened soft targets on the consistency rows.  Its own
+// kernel: loss_kernel above keeps its bits and its launch.
+// sum of 256 per-thread doubles in a fixed tree order; every thread receives it (sm may be reused after the call)
+__device__ __forceinline__ double block_sum_f64(double v, double* sm) {
+  __syncthreads();
+  sm[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
+    __syncthreads();
+  }
+  const double r = sm[0];
+  __syncthreads();
+  return r;
+}
+
+// a row takes part when its target is a class id other than ignore_index.  torch raises for any other id outside [0, C); here such
+// a row is never read out of bounds -- it gets no loss and no gradient -- and it turns the denominator, hence the losses, into NaN
+__device__ __forceinline__ bool ce_row_kept(long y, int C, int ignore_index) { return y >= 0 && y < C && y != (long)ignore_index; }
+
+// {sum of w[y_i], number of rows} over the kept rows, in double, one workgroup: the ONE summation order of the denominator, shared
+// by ce_denominator_kernel and loss_ex_kernel so that a supplied denominator and the in-call one over the same rows have the same bits
+__device__ __forceinline__ void ce_denominator_block(const int64_t* y, int n, int C, const float* w, int ignore_index, double* sm,
+                                                     double* wsum, double* count) {
+  double dw = 0.0, dc = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const long t = (long)y[i];
+    if (ce_row_kept(t, C, ignore_index)) { dw += w ? (double)w[t] : 1.0; dc += 1.0; }
+    else if (t != (long)ignore_index) dw = __longlong_as_double(0x7ff8000000000000LL);      // no class id and not ignored: NaN
+  }
+  *wsum = block_sum_f64(dw, sm);
+  *count = block_sum_f64(dc, sm);
+}
+
+__global__ __launch_bounds__(256) void ce_denominator_kernel(const int64_t* y, int n, int C, const float* w, int ignore_index, float* out2) {
+  __shared__ double smd[256];
+  double ws, cnt;
+  ce_denominator_block(y, n, C, w, ignore_index, smd, &ws, &cnt);
+  if (threadIdx.x == 0) { out2[0] = (float)ws; out2[1] = (float)cnt; }
+}
+
+__global__ __launch_bounds__(256) void loss_ex_kernel(const LossArgs a, const LossOpts o) {
+  __shared__ float sm[4];
+  __shared__ double smd[256];
+  const int C = a.C;
+  const float eps = o.label_smoothing;
+  const float* cw = o.class_weight;
+  // the divisor of the supervised term: the row count the caller states, as in loss_kernel -- or, with class weights, an ignore_index
+  // in use (a non-default one, or rows that carry the default -100) or a supplied denominator, the data-dependent one of torch's
+  // weighted / ignore-index mean (supplied: the global batch's; else over the rows of this call)
+  float inv_x = a.inv_nx_global;
+  bool denom_zero = false;
+  {
+    float den = 0.f;
+    bool data_denom = true;
+    if (o.denominator) {
+      den = o.denominator[0];
+    } else {
+      double ws, cnt;
+      ce_denominator_block(a.target_i, a.nx, C, cw, o.ignore_index, smd, &ws, &cnt);
+      den = (float)ws;
+      data_denom = cw || o.ignore_index != -100 || cnt != (double)a.nx;
+    }
+    if (data_denom) {
+      denom_zero = !(den != 0.f);
+      inv_x = 1.f / den;
+    }
+  }
+  float wall = 0.f;                                   // sum of all class weights (the smoothing term's gradient)
+  if (eps != 0.f)
+    for (int c = 0; c < C; ++c) wall += cw ? cw[c] : 1.f;
+  const float nanv = __int_as_float(0x7fc00000);
+  float lx = 0.f, lu = 0.f, correct = 0.f, conf = 0.f, maxp = 0.f;
+  for (int i = threadIdx.x; i < a.nx; i += 256) {
+    const float* l = a.logits + (long)i * C;
+    float* dl = a.dlogits ? a.dlogits + (long)i * C : nullptr;
+    const long y = (long)a.target_i[i];
+    if (!ce_row_kept(y, C, o.ignore_index)) {         // ignored: no loss, no gradient, never correct
+      if (dl)
+        for (int c = 0; c < C; ++c) dl[c] = 0.f;
+      continue;
+    }
+    const float wy = cw ? cw[y] : 1.f;
+    if (eps == 0.f) {
+      lx += wy * ce_row(l, C, (int)y, dl, wy * inv_x);
+    } else {
+      float m = l[0];
+      for (int c = 1; c < C; ++c) m = fmaxf(m, l[c]);
+      float s = 0.f;
+      for (int c = 0; c < C; ++c) s += expf(l[c] - m);
+      const float lse = m + logf(s);
+      float smooth = 0.f;                             // sum_c w[c] * (-log p_c)
+      for (int c = 0; c < C; ++c) smooth += (cw ? cw[c] : 1.f) * (lse - l[c]);
+      lx += (1.f - eps) * wy * (lse - l[y]) + (eps / (float)C) * smooth;
+      if (dl)
+        for (int c = 0; c < C; ++c) {
+          const float p = expf(l[c] - lse);
+          dl[c] = ((1.f - eps) * wy * (p - (c == y ? 1.f : 0.f)) + (eps / (float)C) * (wall * p - (cw ? cw[c] : 1.f))) * inv_x;
+        }
+    }
+    if (dl && denom_zero)                             // 0 / 0 in torch's backward: the whole row is NaN there
+      for (int c = 0; c < C; ++c) dl[c] = nanv;
+    correct += (row_argmax(l, C) == (int)y) ? 1.f : 0.f;
+  }
+  if (a.kind == 1) {
+    const float wu = a.lambda_u * a.inv_nu_global;
+    for (int i = threadIdx.x; i < a.nu; i += 256) {
+      const float* l = a.logits + (long)(a.nx + i) * C;
+      const float* t = a.logits_t + (long)i * C;
+      float* dl = a.dlogits ? a.dlogits + (long)(a.nx + i) * C : nullptr;
+      float tm = t[0];
+      for (int c = 1; c < C; ++c) tm = fmaxf(tm, t[c]);
+      float ts = 0.f;
+      for (int c = 0; c < C; ++c) ts += expf(t[c] - tm);
+      const float pmax = 1.f / ts;                    // max_c softmax(t)_c, always of the unsharpened teacher
+      maxp += pmax;
+      if (o.threshold > 0.f && !(pmax >= o.threshold)) {   // (threshold 0: no test at all, a NaN teacher row propagates as in loss_kernel)                   // FixMatch: the row stays in the divisor, its loss and gradient are zero
+        if (dl)
+          for (int c = 0; c < C; ++c) dl[c] = 0.f;
+        continue;
+      }
+      conf += 1.f;
+      if (o.temperature == 0.f) {
+        lu += ce_row(l, C, row_argmax(t, C), dl, wu);               // hard pseudo label: loss_kernel's arithmetic
+      } else {                                        // UDA: soft targets p = softmax(t / T)
+        const float rT = 1.f / o.temperature;
+        float ss = 0.f;
+        for (int c = 0; c < C; ++c) ss += expf((t[c] - tm) * rT);
+        float m = l[0];
+        for (int c = 1; c < C; ++c) m = fmaxf(m, l[c]);
+        float s = 0.f;
+        for (int c = 0; c < C; ++c) s += expf(l[c] - m);
+        const float lse = m + logf(s);
+        float r = 0.f;
+        for (int c = 0; c < C; ++c) {
+          const float p = expf((t[c] - tm) * rT) / ss;
+          r += p * (lse - l[c]);
+          if (dl) dl[c] = (expf(l[c] - lse) - p) * wu;
+        }
+        lu += r;
+      }
+    }
+  }
+  const float sx = block_sum(lx, sm);
+  const float su = block_sum(lu, sm);
+  const float sc = block_sum(correct, sm);
+  const float sconf = block_sum(conf, sm);
+  const float smaxp = block_sum(maxp, sm);
+  if (threadIdx.x == 0) {
+    const float loss_x = denom_zero ? nanv : sx * inv_x, loss_u = su * a.inv_nu_global;     // 0 / 0: NaN, as torch's mean
+    a.out[0] = loss_x + a.lambda_u * loss_u;
+    a.out[1] = loss_x;
+    a.out[2] = loss_u;
+    a.out[3] = sc;
+    if (o.stats) { o.stats[0] = sconf; o.stats[1] = smaxp; }
+  }
+}
+
 // out[i] = softmax(logits[i, :])[col] -- the 'tumor' probability of test_Camelyon16.py:58-60
 __global__ __launch_bounds__(256) void softmax_col_kernel(const float* logits, float* out, int n, int C, int col) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -342,6 +501,14 @@ hipError_t launch_softmax_col(const float* logits, float* out, int n, int C, int
 
 hipError_t launch_loss(const LossArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(loss_kernel, dim3(1), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t launch_loss_ex(const LossArgs& a, const LossOpts& o, hipStream_t st) {
+  hipLaunchKernelGGL(loss_ex_kernel, dim3(1), dim3(256), 0, st, a, o);
+  return hipGetLastError();
+}
+hipError_t launch_ce_denominator(const int64_t* y, int n, int C, const float* w, int ignore_index, float* out2, hipStream_t st) {
+  hipLaunchKernelGGL(ce_denominator_kernel, dim3(1), dim3(256), 0, st, y, n, C, w, ignore_index, out2);
   return hipGetLastError();
 }
 

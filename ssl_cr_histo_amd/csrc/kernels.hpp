@@ -18,6 +18,7 @@ using PoolFwdArgs = sslcr_pool_fwd_desc;
 using PoolBwdArgs = sslcr_pool_bwd_desc;
 using BnBwdArgs = sslcr_bn_bwd_desc;
 using LossArgs = sslcr_loss_desc;
+using LossOpts = sslcr_loss_opts;
 using TensorDesc = sslcr_tensor_desc;
 using OptArgs = sslcr_opt_desc;
 using PackArgs = sslcr_pack_desc;
@@ -176,6 +177,31 @@ hipError_t launch_linear_fwd(const float* x, const float* w, const float* b, flo
 hipError_t launch_linear_bwd(const float* x, const float* w, const float* dy, const float* yact, float* dx, float* dw, float* db,
                              int M, int N, int K, int dx_accumulate, float* scratch, hipStream_t st);
 hipError_t launch_loss(const LossArgs& a, hipStream_t st);
+// the loss with options (sslcr_loss_ex): its own single-workgroup kernel, launch_loss keeps its bits and its launch
+hipError_t launch_loss_ex(const LossArgs& a, const LossOpts& o, hipStream_t st);
+hipError_t launch_ce_denominator(const int64_t* y, int n, int C, const float* w, int ignore_index, float* out2, hipStream_t st);
+inline LossOpts loss_opts_default() {
+  LossOpts o;
+  o.class_weight = nullptr; o.label_smoothing = 0.f; o.ignore_index = -100; o.threshold = 0.f; o.temperature = 0.f;
+  o.denominator = nullptr; o.stats = nullptr;
+  return o;
+}
+// nothing set that launch_loss does not already compute: the caller then issues launch_loss itself
+inline bool loss_opts_is_default(const LossOpts& o) {
+  return !o.class_weight && o.label_smoothing == 0.f && o.ignore_index == -100 && o.threshold == 0.f && o.temperature == 0.f &&
+         !o.denominator && !o.stats;
+}
+// nullptr, or what is wrong with the options for a loss of this kind and class count (decided on the host, before any launch)
+inline const char* loss_opts_error(int kind, int C, const LossOpts& o) {
+  if (loss_opts_is_default(o)) return nullptr;
+  if (kind != 1 && kind != 2) return "loss options apply to the cross-entropy kinds (1, 2) only, not to the MSE kinds (0, 3)";
+  if (C > 64) return "C > 64";
+  if (!(o.label_smoothing >= 0.f && o.label_smoothing < 1.f)) return "label_smoothing outside [0, 1)";
+  if (!(o.threshold >= 0.f && o.threshold <= 1.f)) return "threshold outside [0, 1]";
+  if (!(o.temperature >= 0.f)) return "temperature < 0";
+  if (kind == 2 && (o.threshold != 0.f || o.temperature != 0.f)) return "threshold / temperature need the consistency term (kind 1)";
+  return nullptr;
+}
 hipError_t launch_softmax_col(const float* logits, float* out, int n, int C, int col, hipStream_t st);
 // augment.hip
 hipError_t launch_weak_augment(const sslcr_weak_aug_desc& a, hipStream_t st);

@@ -9,6 +9,7 @@ import weakref
 import torch
 
 from . import _lib as L
+from .kernels import LossOptions
 from .net import Classifier, FinetuneResNet, TripletNet, TripletNet_Finetune, unwrap
 
 _DTYPES = {"fp32": 0, "f32": 0, "float32": 0, "bf16": 1, "bfloat16": 1, "fp8": 2}     # fp8: bf16 engine + e4m3 forward convs (config 5)
@@ -51,6 +52,7 @@ _ENGINE_SIGS = {
                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sslcr_net_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "sslcr_net_set_grad_accumulate": (C.c_int, [C.c_void_p, C.c_int]),
+    "sslcr_net_set_loss_opts": (C.c_int, [C.c_void_p, C.POINTER(L.LossOpts)]),
     "sslcr_net_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "sslcr_net_debug_tap": (C.c_int, [C.c_void_p, C.c_int]),
     "sslcr_net_segments_used": (C.c_int, [C.c_void_p]),
@@ -158,6 +160,7 @@ class BoundNet:
         self.params = [p for _, p in model.named_parameters()] + [p for _, p in classifier.named_parameters()]
         self.param_names = ["model." + k for k, _ in model.named_parameters()] + ["classifier." + k for k, _ in classifier.named_parameters()]
         self.last_grad_norm = None
+        self._loss_keep = None          # tensors the library's sticky loss options point to (set_loss_options)
         dev = engine.device
         for p in self.params:
             if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
@@ -237,6 +240,22 @@ class BoundNet:
         * Nothing clears the buffer for the caller: accumulating onto a gradient that an optimizer step has already consumed
           adds to that stale gradient, as torch does without ``zero_grad``."""
         L.check(L.lib().sslcr_net_set_grad_accumulate(self.handle, int(bool(on))))
+
+    def set_loss_options(self, opts, denominator=None, stats=None):
+        """The options of the loss leg of ``Engine.step_ssl_cr`` (this net as the student) and ``step_supervised``: a
+        ``LossOptions`` or None (the defaults: the launches and the bits of a net that never had options).  Sticky in the library,
+        like ``set_grad_accumulate``; the step functions set it on every call from their own ``loss_options`` argument.
+        denominator: device fp32 [1+], the supervised term's divisor over the whole global batch (``kernels.ce_denominator``, all-reduced
+        when sharded) when the step holds a micro-batch or a shard; stats: device fp32 [2] that receives {#confident rows, sum of
+        the teacher's max-probs}.  The tensors are kept alive here until the next call."""
+        if opts is None and denominator is None and stats is None:
+            if self._loss_keep is not None:
+                L.check(L.lib().sslcr_net_set_loss_opts(self.handle, None))
+                self._loss_keep = None
+            return
+        o, keep = (opts if opts is not None else LossOptions()).c_opts(self.engine.device, self.ncls, denominator, stats)
+        L.check(L.lib().sslcr_net_set_loss_opts(self.handle, C.byref(o)))
+        self._loss_keep = keep
 
     def backward(self, dlogits, accumulate=False):
         """backward of the last train-mode forward from d(loss)/d(logits).  accumulate: see ``set_grad_accumulate`` (set on every
@@ -463,7 +482,7 @@ class Engine:
 
     # ------------------------------------------------------------------ fused steps
     def step_ssl_cr(self, teacher, student, kind, x, y, u_w, u_s, lambda_u, backward=True, nx_global=None, nu_global=None,
-                    accumulate=False):
+                    accumulate=False, loss_options=None, denominator=None):
         """one consistency-training iteration (eval_BreastPathQ_SSL_CR.py:65-100 / eval_Camelyon_SSL_CR.py:94-121).
         x [nx,3,H,W], u_w/u_s [nu,3,H,W] uint8|fp32; y [nx] fp32 (kind 'mse') or int64 (kind 'ce').
         -> dict(losses [4] device tensor: loss, loss_x, loss_u, #correct ; feats ; logits ; logits_t).  With more than one rank the
@@ -472,7 +491,13 @@ class Engine:
         the default clears first).  A micro-batch is a shard in time: pass the full batch's counts as nx_global / nu_global, then
         the sums of k micro-steps' gradients and losses are the global batch's -- with each micro-batch's own BatchNorm statistics
         (per-replica statistics under ``nn.DataParallel``), running statistics updated by every micro-step in turn (``DataParallel``
-        keeps replica 0's), and no clearing of a gradient left from before an optimizer step."""
+        keeps replica 0's), and no clearing of a gradient left from before an optimizer step.
+        loss_options: a ``LossOptions`` for kind 'ce' (set on every call, as accumulate is: None or the defaults give the step it
+        has always been); the result then also has ``stats`` = device [#confident unlabeled rows, sum of the teacher's max-probs].
+        denominator: the supervised term's divisor over the whole global batch (``kernels.ce_denominator`` of the full batch's
+        targets, all-reduced over ranks) -- needed whenever this call holds only a micro-batch or a shard of the batch (rows labelled -100
+        are left out once an option is set, so no part knows the batch's divisor from its own rows); None: the rows of this call."""
+        stats = self._set_loss_options(student, kind, loss_options, denominator)
         student.set_grad_accumulate(accumulate)
         teacher.sync()
         student.sync()
@@ -500,13 +525,34 @@ class Engine:
         L.check(L.lib().sslcr_step_ssl_cr(teacher.handle, student.handle, C.byref(d), L.stream_ptr()))
         student._live_inputs = (x, u_s, u_w, tf, ti)
         student._note_buffers_changed()
-        return dict(losses=losses, feats=feats, logits=logits, logits_t=logits_t)
+        out = dict(losses=losses, feats=feats, logits=logits, logits_t=logits_t)
+        if stats is not None:
+            out["stats"] = stats
+        return out
 
-    def step_supervised(self, net, kind, xs, y, train=True, backward=True, n_global=None, accumulate=False):
+    def _set_loss_options(self, net, kind, loss_options, denominator):
+        """the per-call reset of the net's sticky loss options; -> the stats tensor of a call with options (None without)"""
+        if loss_options is not None and not isinstance(loss_options, LossOptions):
+            raise TypeError(f"loss_options must be a LossOptions or None (got {type(loss_options).__name__})")
+        if loss_options is None or loss_options.is_default():
+            if denominator is not None:
+                raise ValueError("a denominator without loss options that need one")
+            net.set_loss_options(None)
+            return None
+        if kind != "ce":
+            raise ValueError(f"loss_options apply to the cross-entropy steps only (kind {kind!r})")
+        stats = torch.empty(2, dtype=torch.float32, device=self.device)          # the loss kernel writes both entries
+        net.set_loss_options(loss_options, denominator, stats)
+        return stats
+
+    def step_supervised(self, net, kind, xs, y, train=True, backward=True, n_global=None, accumulate=False, loss_options=None,
+                        denominator=None):
         """student-only step: RSP pretraining (TripletNet, 3 inputs, 'ce'; pretrain_BreastPathQ.py:42-61), supervised
         fine-tuning (eval_Camelyon_SSL.py:52-98 'ce', eval_BreastPathQ_SSL.py:52-84 'mse') and every validate().
         accumulate: as in ``step_ssl_cr`` (gradients added to the buffer; n_global = the full batch's count; per-micro-batch
-        BatchNorm statistics, running statistics updated every micro-step, stale gradients are not cleared)."""
+        BatchNorm statistics, running statistics updated every micro-step, stale gradients are not cleared).
+        loss_options / denominator: as in ``step_ssl_cr`` (kind 'ce'; with train=False the weighted validation loss)."""
+        stats = self._set_loss_options(net, kind, loss_options, denominator)
         net.set_grad_accumulate(accumulate)
         net.sync()
         xs = [self.as_input(x) for x in xs]
@@ -527,7 +573,10 @@ class Engine:
         net._live_inputs = (xs, tf, ti)
         if train:
             net._note_buffers_changed()
-        return dict(losses=losses, feats=feats, logits=logits)
+        out = dict(losses=losses, feats=feats, logits=logits)
+        if stats is not None:
+            out["stats"] = stats
+        return out
 
 
 class VirtualComm:

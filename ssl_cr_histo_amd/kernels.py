@@ -415,16 +415,101 @@ def linear_bwd(x, w, dy, *, yact=None, dw=None, db=None, want_dx=True, dx=None, 
     return dx
 
 
+class LossOptions:
+    """Options of the cross-entropy losses (include/sslcr.h: sslcr_loss_opts).  Supervised term: ``class_weight`` (a sequence or
+    tensor of C floats), ``label_smoothing`` and ``ignore_index`` of ``F.cross_entropy(..., reduction='mean')``.  Consistency term:
+    ``threshold`` tau -- FixMatch's confidence mask ``max_probs.ge(tau)`` with ``(loss * mask).mean()`` -- and ``temperature`` T --
+    0: hard pseudo labels (the reference), T > 0: UDA's soft targets ``softmax(logits_teacher / T)``.  The defaults are the
+    reference's losses, computed in the step functions by the launches the engine has always issued -- which expect every target to
+    be a class id: rows labelled -100 are left out, as torch does, once any option is set (and by ``kernels.loss(opts=...)`` always).
+    Pure host object; the weight's device copy is made once per device, on first use."""
+
+    def __init__(self, class_weight=None, label_smoothing=0.0, ignore_index=-100, threshold=0.0, temperature=0.0):
+        if class_weight is not None:
+            class_weight = torch.as_tensor(class_weight).detach().to("cpu", torch.float32).reshape(-1).contiguous()
+        self.class_weight = class_weight
+        self.label_smoothing, self.ignore_index = float(label_smoothing), int(ignore_index)
+        self.threshold, self.temperature = float(threshold), float(temperature)
+        if not 0.0 <= self.label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must lie in [0, 1) (got {label_smoothing!r})")
+        if not 0.0 <= self.threshold <= 1.0:
+            raise ValueError(f"threshold must lie in [0, 1] (got {threshold!r})")
+        if not self.temperature >= 0.0:
+            raise ValueError(f"temperature must be >= 0 (got {temperature!r})")
+        self._dev = {}
+
+    @classmethod
+    def from_criterion(cls, criterion, threshold=0.0, temperature=0.0):
+        """the options an ``nn.CrossEntropyLoss`` carries (weight, label_smoothing, ignore_index); only reduction='mean' is served"""
+        if not isinstance(criterion, torch.nn.CrossEntropyLoss):
+            raise TypeError(f"LossOptions.from_criterion: an nn.CrossEntropyLoss expected (got {type(criterion).__name__})")
+        if criterion.reduction != "mean":
+            raise ValueError(f"LossOptions.from_criterion: reduction={criterion.reduction!r}: only reduction='mean' is served")
+        return cls(criterion.weight, getattr(criterion, "label_smoothing", 0.0), criterion.ignore_index, threshold, temperature)
+
+    def is_default(self):
+        return self.class_weight is None and self.label_smoothing == 0.0 and self.ignore_index == -100 and self.threshold == 0.0 and \
+            self.temperature == 0.0
+
+    def needs_denominator(self):
+        """True when a step that holds only PART of the global batch (a micro-batch, a shard) must be handed the batch's divisor:
+        for every non-default options object.  With weights or an ignore_index in use 'mean' divides by a data-dependent sum; and
+        once any option is set, rows labelled -100 are left out as in torch, so even then the divisor is the kept rows of the
+        whole batch, which no part can know from its own rows (without weights and without ignored rows it is the row count, and
+        1 / it has the bits of the constant the engine otherwise uses)."""
+        return not self.is_default()
+
+    def weight_on(self, device, C=None):
+        """the [C] fp32 device copy of class_weight (None without weights)"""
+        if self.class_weight is None:
+            return None
+        if C is not None and self.class_weight.numel() != C:
+            raise ValueError(f"class_weight has {self.class_weight.numel()} entries for {C} classes")
+        key = str(torch.device(device))
+        if key not in self._dev:
+            self._dev[key] = self.class_weight.to(device)
+        return self._dev[key]
+
+    def c_opts(self, device, C, denominator=None, stats=None):
+        """-> (sslcr_loss_opts, the tensors its pointers name: keep them until the launch has run)"""
+        w = self.weight_on(device, C)
+        o = L.LossOpts(L.ptr(w), self.label_smoothing, self.ignore_index, self.threshold, self.temperature, L.ptr(denominator), L.ptr(stats))
+        return o, (w, denominator, stats)
+
+    def __repr__(self):
+        w = None if self.class_weight is None else self.class_weight.tolist()
+        return (f"LossOptions(class_weight={w}, label_smoothing={self.label_smoothing}, ignore_index={self.ignore_index}, "
+                f"threshold={self.threshold}, temperature={self.temperature})")
+
+
+def ce_denominator(target_i, C, class_weight=None, ignore_index=-100):
+    """-> device tensor [sum of class_weight[y] over the rows with y != ignore_index, number of those rows] (sslcr_ce_denominator):
+    the divisor of ``F.cross_entropy(weight=, ignore_index=, reduction='mean')``, left on the device.  No sync, no atomics."""
+    _chk(target_i, class_weight)
+    if target_i.dtype != torch.int64 or target_i.dim() != 1:
+        raise L.SslcrError("ce_denominator: a 1-D int64 target tensor expected")
+    out2 = torch.empty(2, dtype=torch.float32, device=target_i.device)
+    L.check(L.lib().sslcr_ce_denominator(L.ptr(target_i) if target_i.numel() else None, target_i.numel(), int(C), L.ptr(class_weight),
+                                         int(ignore_index), L.ptr(out2), L.stream_ptr()))
+    return out2
+
+
 def loss(kind, logits, *, logits_t=None, target_f=None, target_i=None, nx, lambda_u=1.0, want_grad=True,
-         nx_global=None, nu_global=None):
-    _chk(logits, logits_t, target_f, target_i)
+         nx_global=None, nu_global=None, opts=None, denominator=None, stats=None):
+    """opts: a LossOptions (None: sslcr_loss itself); denominator: device [1+] fp32, the supervised term's divisor over the whole
+    global batch (``ce_denominator``); stats: device [2] fp32 that receives {#confident rows, sum of max-probs}."""
+    _chk(logits, logits_t, target_f, target_i, denominator, stats)
     Ns, Cn = logits.shape
     nu = Ns - nx
     dl = torch.zeros_like(logits) if want_grad else None
     out = torch.zeros(4, dtype=torch.float32, device=logits.device)
     d = L.LossDesc(kind, L.ptr(logits), L.ptr(logits_t), L.ptr(target_f), L.ptr(target_i), L.ptr(dl), L.ptr(out), nx, nu,
                    Cn, lambda_u, 1.0 / (nx_global or nx), 1.0 / max(1, (nu_global or nu)))
-    L.check(L.lib().sslcr_loss(d, L.stream_ptr()))
+    if opts is None and denominator is None and stats is None:
+        L.check(L.lib().sslcr_loss(d, L.stream_ptr()))
+    else:
+        o, keep = (opts if opts is not None else LossOptions()).c_opts(logits.device, Cn, denominator, stats)
+        L.check(L.lib().sslcr_loss_ex(d, o, L.stream_ptr()))
     return out, dl
 
 

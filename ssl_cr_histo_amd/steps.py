@@ -15,6 +15,14 @@ hold it.  The return tuples keep their shapes.  What this is, exactly:
   * the first micro-step of a batch clears the buffer; anybody who calls the engine with ``accumulate=True`` on a buffer left from
     before an optimizer step adds to that stale gradient, as torch does without ``zero_grad``.
 
+Loss options: every ``*_train`` and ``*_validate`` with a cross-entropy loss reads ``getattr(args, "loss_options", None)``, a
+``LossOptions`` (class weights, label smoothing, ignore_index; FixMatch threshold and UDA temperature of the consistency term); absent,
+None or all-default: the code path of every earlier version.  The MSE loops (``bpq_*``) raise ValueError for anything else.  A
+weighted or ignore-index mean divides by the sum of w[y] over the kept rows of the WHOLE global batch: ``denominator_plan`` says when
+that sum needs a launch of its own (any option set, and micro-batches or ranks: once per loader batch, from the full batch's
+targets) and a 2-float all-reduce (ranks); one rank with k = 1 needs neither, the loss kernel sums its own rows.  The CR training loops leave
+``args.loss_stats`` = dict(rows, confident, mask_rate, mean_max_prob) of the epoch's unlabeled rows (one read at the epoch's end).
+
 reference                                   here
 eval_BreastPathQ_SSL_CR.train/validate      bpq_cr_train / bpq_cr_validate      (:37-128 / :131-175)
 eval_Camelyon_SSL_CR.train/validate         cam_cr_train / cam_cr_validate      (:33-157 / :160-225)
@@ -30,6 +38,7 @@ import torch
 
 from .dist import shard_range
 from .engine import get_engine
+from .kernels import LossOptions, ce_denominator
 from .util import AverageMeter
 
 
@@ -172,35 +181,113 @@ def _sum_losses(parts):
     return torch.stack([p["losses"] for p in parts]).sum(0)
 
 
-def _ssl_cr_step(eng, te, st, kind, x, y, u_w, u_s, lambda_u, k):
+def _loss_options(args, mse=None):
+    """args.loss_options; absent, None or all-default = None: the code path of every earlier version.  mse: the name of a loop whose
+    loss is F.mse_loss, which has no options."""
+    o = getattr(args, "loss_options", None)
+    if o is None:
+        return None
+    if not isinstance(o, LossOptions):
+        raise TypeError(f"args.loss_options must be a LossOptions (got {type(o).__name__})")
+    if o.is_default():
+        return None
+    if mse is not None:
+        raise ValueError(f"{mse}: args.loss_options = {o!r} -- the loss of this loop is F.mse_loss, which has no such options")
+    return o
+
+
+def denominator_plan(opts, k, world):
+    """-> (launch, all_reduce): does a loader batch need a denominator launch of its own (sslcr_ce_denominator over the full batch's
+    targets) and an all-reduce of it?  Pure host logic.  Never for absent or all-default options.  With any option set the divisor
+    of 'mean' is the kept rows' weight over the WHOLE global batch (class weights, an ignore_index, or just rows labelled -100,
+    which are left out once an option is set), and a step that holds only part of it -- a micro-batch (k > 1) or a shard
+    (world > 1) -- cannot derive that from its own rows; one rank with k = 1 can, and nothing is added."""
+    if opts is None or not opts.needs_denominator() or (k == 1 and world == 1):
+        return False, False
+    return True, world > 1
+
+
+def _denominator(eng, opts, y, ncls, k):
+    """the supervised term's divisor over the global batch, on the device (None where the loss kernel's own rows are the batch)"""
+    launch, reduce = denominator_plan(opts, k, eng.world)
+    if not launch:
+        return None
+    den = ce_denominator(y.to(eng.device).long().reshape(-1).contiguous(), ncls, opts.weight_on(eng.device, ncls), opts.ignore_index)
+    return eng.all_reduce_sum(den) if reduce else den
+
+
+def _loss_kw(eng, opts, y, ncls, k):
+    return {} if opts is None else dict(loss_options=opts, denominator=_denominator(eng, opts, y, ncls, k))
+
+
+class _MaskStats:
+    """{#confident unlabeled rows, sum of the teacher's max-probs, #unlabeled rows} of an epoch's steps, kept on the device until
+    the epoch's end"""
+
+    def __init__(self, eng, args, opts):
+        self.eng, self.args, self.rows, self.n = eng, args, [], 0
+        self.on = opts is not None
+
+    def add(self, r, nu):
+        if self.on:
+            self.rows.append(r["stats"])
+            self.n += nu
+
+    def finish(self):
+        """COLLECTIVE when sharded, as meters(): every rank of a run with options calls it once per epoch, whatever it gathered; the
+        row count travels in the reduced vector, so ranks need not have seen equally many rows"""
+        if not self.on:
+            return
+        tot = torch.zeros(3, dtype=torch.float32, device=self.eng.device)
+        if self.rows:
+            tot[:2] = torch.stack(self.rows).sum(0)
+        tot[2] = float(self.n)
+        conf, maxp, n = self.eng.all_reduce_sum(tot).cpu().tolist()
+        n = int(n)
+        self.args.loss_stats = dict(rows=n, confident=int(conf), mask_rate=conf / n if n else float("nan"),
+                                    mean_max_prob=maxp / n if n else float("nan"))
+
+
+def _ssl_cr_step(eng, te, st, kind, x, y, u_w, u_s, lambda_u, k, opts=None):
     """one loader batch of a consistency-training loop as k accumulated micro-steps (k == 1: the plain engine step).  Rows of the
-    returned feats / logits / logits_t are in the order the single step returns them: all labeled rows, then all unlabeled."""
+    returned feats / logits / logits_t are in the order the single step returns them: all labeled rows, then all unlabeled.
+    opts: the loop's LossOptions (None: none); the denominator of a weighted / ignore-index mean is taken ONCE, over the full
+    batch's targets, and handed to every micro-step."""
+    kw = _loss_kw(eng, opts, y, st.ncls, k)
     if k == 1:
-        return eng.step_ssl_cr(te, st, kind, x, y, u_w, u_s, lambda_u)
+        return eng.step_ssl_cr(te, st, kind, x, y, u_w, u_s, lambda_u, **kw)
     nx, nu = x.shape[0], u_w.shape[0]
     if k > nx or k > nu:
         raise ValueError(f"micro_batches = {k} exceeds the batch: nx = {nx} labeled, nu = {nu} unlabeled rows")
     parts = []
     for j, ((a, b), (c, d)) in enumerate(zip(micro_ranges(nx, k), micro_ranges(nu, k))):
         parts.append(eng.step_ssl_cr(te, st, kind, x[a:b], y[a:b], u_w[c:d], u_s[c:d], lambda_u, nx_global=nx * eng.world,
-                                     nu_global=nu * eng.world, accumulate=j > 0))
+                                     nu_global=nu * eng.world, accumulate=j > 0, **kw))
     nxj = [b - a for a, b in micro_ranges(nx, k)]                    # a part's rows: its nxj labeled ones, then its unlabeled ones
     out = {key: torch.cat([p[key][:n] for p, n in zip(parts, nxj)] + [p[key][n:] for p, n in zip(parts, nxj)]) for key in ("feats", "logits")}
     out["logits_t"] = torch.cat([p["logits_t"] for p in parts])
     out["losses"] = _sum_losses(parts)
+    if opts is not None:
+        out["stats"] = torch.stack([p["stats"] for p in parts]).sum(0)
     return out
 
 
-def _sup_step(eng, net, kind, xs, y, k):
+def _sup_step(eng, net, kind, xs, y, k, opts=None):
     """one loader batch of a student-only training loop as k accumulated micro-steps (k == 1: the plain engine step)."""
+    kw = _loss_kw(eng, opts, y, net.ncls, k)
     if k == 1:
-        return eng.step_supervised(net, kind, xs, y, train=True)
+        return eng.step_supervised(net, kind, xs, y, train=True, **kw)
     n = xs[0].shape[0]
     if k > n:
         raise ValueError(f"micro_batches = {k} exceeds the batch: n = {n} rows")
-    parts = [eng.step_supervised(net, kind, [x[a:b] for x in xs], y[a:b], train=True, n_global=n * eng.world, accumulate=j > 0)
+    parts = [eng.step_supervised(net, kind, [x[a:b] for x in xs], y[a:b], train=True, n_global=n * eng.world, accumulate=j > 0, **kw)
              for j, (a, b) in enumerate(micro_ranges(n, k))]
     return dict(losses=_sum_losses(parts), feats=torch.cat([p["feats"] for p in parts]), logits=torch.cat([p["logits"] for p in parts]))
+
+
+def _val_step(eng, net, xs, y, opts):
+    """one validate() batch with a cross-entropy loss (eval-mode forward + loss, no backward)"""
+    return eng.step_supervised(net, "ce", xs, y, train=False, **_loss_kw(eng, opts, y, net.ncls, 1))
 
 
 def _device_of(model):
@@ -226,6 +313,7 @@ def _len(x):
 def bpq_cr_train(args, model_teacher, model_student, classifier_teacher, classifier_student, labeled_train_loader,
                  unlabeled_train_loader, optimizer, epoch):
     """eval_BreastPathQ_SSL_CR.train: returns (loss_avg, loss_x_avg, loss_u_avg, final_feats, final_targets)."""
+    _loss_options(args, mse="bpq_cr_train")
     eng = get_engine(_device_of(model_student))
     for m in (model_teacher, classifier_teacher):
         m.eval()
@@ -253,6 +341,7 @@ def bpq_cr_train(args, model_teacher, model_student, classifier_teacher, classif
 
 def bpq_cr_validate(args, model_student, classifier_student, val_loader, epoch):
     """eval_BreastPathQ_SSL_CR.validate -> loss_avg."""
+    _loss_options(args, mse="bpq_cr_validate")
     eng = get_engine(_device_of(model_student))
     model_student.eval()
     classifier_student.eval()
@@ -283,6 +372,8 @@ def cam_cr_train(args, model_teacher, model_student, classifier_teacher, classif
     meters = _meters(eng, ["loss", "loss_x", "loss_u", "acc"])
     feats, targets = [], []
     k = _micro_k(args)
+    opts = _loss_options(args)
+    mask = _MaskStats(eng, args, opts)
     t0 = time.time()
     S = args.image_size
     loaders = zip(tumor_labeled_train_loader, normal_labeled_train_loader, tumor_unlabeled_train_loader,
@@ -299,14 +390,16 @@ def cam_cr_train(args, model_teacher, model_student, classifier_teacher, classif
         p_us = torch.randperm(2 * len(t_us))
         x, y = _cat_shuffle(t_x, n_x, p_x.to(t_x.device)), _cat_shuffle(t_y, n_y, p_x.to(t_y.device)).long()
         u_w, u_s = _cat_shuffle(t_uw, n_uw, p_uw.to(t_uw.device)), _cat_shuffle(t_us, n_us, p_us.to(t_us.device))
-        r = _ssl_cr_step(eng, te, st, "ce", x, y, u_w, u_s, args.lambda_u, k)
+        r = _ssl_cr_step(eng, te, st, "ce", x, y, u_w, u_s, args.lambda_u, k, opts)
         st.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         n = x.shape[0]
         meters.add(r["losses"], n)
+        mask.add(r, u_w.shape[0])
         feats.append(r["feats"][:n])
         targets.append(y.to(eng.device))
         _maybe_print(args, batch_idx, "Train", epoch, _len(tumor_labeled_train_loader) * 2, t0, meters)
     m = meters.meters()
+    mask.finish()
     return m["loss"].avg, m["loss_x"].avg, m["loss_u"].avg, m["acc"].avg, torch.cat(feats).detach(), torch.cat(targets).detach()
 
 
@@ -317,6 +410,7 @@ def cam_cr_validate(args, model_student, classifier_student, val_tumor_loader, v
     classifier_student.eval()
     st = eng.bind(model_student, classifier_student)
     meters = _meters(eng, ["loss", "acc"])
+    opts = _loss_options(args)
     t0 = time.time()
     for batch_idx, (data_tumor, data_normal) in enumerate(_ahead(zip(val_tumor_loader, val_normal_loader), eng, _prefetch_on(args))):
         t_x, t_y = data_tumor
@@ -324,7 +418,7 @@ def cam_cr_validate(args, model_student, classifier_student, val_tumor_loader, v
         perm = torch.randperm(2 * len(t_x))
         x = torch.cat([t_x, n_x])[perm.to(t_x.device)]
         y = torch.cat([t_y, n_y])[perm.to(t_y.device)].long()
-        r = eng.step_supervised(st, "ce", [x], y, train=False)
+        r = _val_step(eng, st, [x], y, opts)
         meters.add(r["losses"], y.size(0))
         _maybe_print(args, batch_idx, "Val", epoch, 2 * _len(val_tumor_loader), t0, meters)
     m = meters.meters()
@@ -344,17 +438,21 @@ def kather_cr_train(args, model_teacher, model_student, classifier_teacher, clas
     te, st = eng.bind(model_teacher, classifier_teacher), eng.bind(model_student, classifier_student)
     meters = _meters(eng, ["loss", "loss_x", "loss_u", "acc"])
     k = _micro_k(args)
+    opts = _loss_options(args)
+    mask = _MaskStats(eng, args, opts)
     t0 = time.time()
     for batch_idx, (data_x, data_u) in enumerate(_ahead(zip(labeled_train_loader, unlabeled_train_loader), eng, _prefetch_on(args))):
         inputs_x, targets_x = data_x
         inputs_u_w, inputs_u_s = data_u
         inputs_x = inputs_x.reshape(-1, 3, 256, 256)                          # :68
         targets_x = targets_x.reshape(-1).long()                              # :69
-        r = _ssl_cr_step(eng, te, st, "ce", inputs_x, targets_x, inputs_u_w, inputs_u_s, args.lambda_u, k)
+        r = _ssl_cr_step(eng, te, st, "ce", inputs_x, targets_x, inputs_u_w, inputs_u_s, args.lambda_u, k, opts)
         st.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         meters.add(r["losses"], inputs_x.shape[0])
+        mask.add(r, inputs_u_w.shape[0])
         _maybe_print(args, batch_idx, "Train", epoch, _len(labeled_train_loader), t0, meters)
     m = meters.meters()
+    mask.finish()
     return m["loss"].avg, m["loss_x"].avg, m["loss_u"].avg, m["acc"].avg
 
 
@@ -365,8 +463,9 @@ def kather_cr_validate(args, model_student, classifier_student, val_loader, epoc
     classifier_student.eval()
     st = eng.bind(model_student, classifier_student)
     meters = _meters(eng, ["loss", "acc"])
+    opts = _loss_options(args)
     for batch_idx, (input, target) in enumerate(_ahead(val_loader, eng, _prefetch_on(args))):
-        r = eng.step_supervised(st, "ce", [input], target.reshape(-1).long(), train=False)
+        r = _val_step(eng, st, [input], target.reshape(-1).long(), opts)
         meters.add(r["losses"], target.size(0))
     m = meters.meters()
     return m["loss"].avg, m["acc"].avg
@@ -383,7 +482,8 @@ def _plain_ce(criterion, where):
     if criterion.weight is not None or getattr(criterion, "label_smoothing", 0.0) != 0.0 or criterion.reduction != "mean" or \
             criterion.ignore_index != -100:
         raise NotImplementedError(f"{where}: only the default nn.CrossEntropyLoss() (no weight / label_smoothing / ignore_index, "
-                                  "reduction='mean') is implemented by the engine")
+                                  "reduction='mean') is implemented by the engine through the `criterion` argument; pass the options as "
+                                  "args.loss_options = LossOptions.from_criterion(criterion) instead")
 
 
 def _rsp_epoch(args, model, classifier, loader, criterion, optimizer, epoch, train):
@@ -395,11 +495,12 @@ def _rsp_epoch(args, model, classifier, loader, criterion, optimizer, epoch, tra
     meters = _meters(eng, ["loss", "acc"])
     feats, targets = [], []
     k = _micro_k(args) if train else 1
+    opts = _loss_options(args)
     t0 = time.time()
     for batch_idx, (input1, input2, input3, target) in enumerate(_ahead(loader, eng, _prefetch_on(args))):
         i1, i2, i3 = (v.reshape(-1, 3, args.tile_h, args.tile_w) for v in (input1, input2, input3))
         target = target.long().view(-1, 1).reshape(-1)
-        r = _sup_step(eng, net, "ce", [i1, i2, i3], target, k) if train else eng.step_supervised(net, "ce", [i1, i2, i3], target, train=False)
+        r = _sup_step(eng, net, "ce", [i1, i2, i3], target, k, opts) if train else _val_step(eng, net, [i1, i2, i3], target, opts)
         if train:
             net.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         meters.add(r["losses"], target.size(0))
@@ -432,6 +533,7 @@ def cam_sup_train(args, model, classifier, tumor_labeled_train_loader, normal_la
     meters = _meters(eng, ["loss", "acc"])
     feats, targets = [], []
     k = _micro_k(args)
+    opts = _loss_options(args)
     S = args.image_size
     for batch_idx, (tumor_data_x, normal_data_x) in enumerate(_ahead(zip(tumor_labeled_train_loader, normal_labeled_train_loader), eng,
                                                                      _prefetch_on(args))):
@@ -441,7 +543,7 @@ def cam_sup_train(args, model, classifier, tumor_labeled_train_loader, normal_la
         n_x, n_y = n_x.reshape(-1, 3, S, S), n_y.reshape(-1)
         perm = torch.randperm(2 * len(t_x))
         x, y = _cat_shuffle(t_x, n_x, perm.to(t_x.device)), _cat_shuffle(t_y, n_y, perm.to(t_y.device)).long()
-        r = _sup_step(eng, net, "ce", [x], y, k)
+        r = _sup_step(eng, net, "ce", [x], y, k, opts)
         net.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         meters.add(r["losses"], x.shape[0])
         feats.append(r["feats"])
@@ -452,6 +554,7 @@ def cam_sup_train(args, model, classifier, tumor_labeled_train_loader, normal_la
 
 def bpq_sup_train(args, model, classifier, train_loader, criterion, optimizer, epoch):
     """eval_BreastPathQ_SSL.train -> (loss, feats, targets)."""
+    _loss_options(args, mse="bpq_sup_train")
     if criterion is not None and not isinstance(criterion, torch.nn.MSELoss):
         raise NotImplementedError("the reference fine-tunes BreastPathQ with nn.MSELoss")
     eng = get_engine(_device_of(model))
@@ -482,10 +585,11 @@ def kather_sup_train(args, model, classifier, train_loader, criterion, optimizer
     net = eng.bind(model, classifier)
     meters = _meters(eng, ["loss", "acc"])
     k = _micro_k(args)
+    opts = _loss_options(args)
     for batch_idx, (input, target) in enumerate(_ahead(train_loader, eng, _prefetch_on(args))):
         x = input.reshape(-1, 3, args.image_size, args.image_size)                   # :57
         y = target.reshape(-1).long()
-        r = _sup_step(eng, net, "ce", [x], y, k)
+        r = _sup_step(eng, net, "ce", [x], y, k, opts)
         net.optimizer_step(optimizer, max_grad_norm=getattr(args, "clip_grad_norm", None))
         meters.add(r["losses"], y.size(0))
     m = meters.meters()
