@@ -29,12 +29,13 @@ extern "C" {
 #define SSLCR_BF16 1
 #define SSLCR_FP8 2   /* engine mode only (sslcr_create): bf16 storage and backward, fp8 e4m3 forward for the eligible 3x3 convs */
 
-/* the library round (10 here).  ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
+/* the library round (11 here).  ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
  * 7 = sslcr_randaug_v2_slot added (nothing else changed); 8 = optimizer parameter groups, AdamW and the global gradient norm
  * (sslcr_tensor_desc.group, sslcr_opt_desc.kind 2, sslcr_optimizer_step_groups, sslcr_grad_norm, sslcr_net_optimizer_step_groups,
  * sslcr_net_grad_norm: all additive); 9 = gradient accumulation (sslcr_grad_accumulate, sslcr_net_set_grad_accumulate: additive,
  * off by default); 10 = loss options (sslcr_loss_opts, sslcr_loss_ex, sslcr_ce_denominator, sslcr_net_set_loss_opts: additive, the
- * defaults issue the launches of version 9). */
+ * defaults issue the launches of version 9); 11 = sslcr_randaug_v2_colour added (the hed / hsv ops of the v2 pool; additive,
+ * sslcr_augv2_desc and sslcr_randaug_v2_slot are unchanged). */
 int sslcr_version(void);
 const char* sslcr_last_error(void);
 
@@ -465,6 +466,37 @@ typedef struct sslcr_augv2_desc {
   int N, H, W, src_hwc, dst_hwc;
 } sslcr_augv2_desc;
 int sslcr_randaug_v2_slot(const sslcr_augv2_desc* d, void* stream);
+
+/*      sslcr_randaug_v2_colour (library version >= 11): the two histopathology ops of the same pool, hed() :135-144 and hsv() :125-132,
+ *      IN PLACE on a uint8 batch in HBM: image n takes op[n] with row n of param; SSLCR_AUGV2C_COPY leaves it untouched (its workgroups
+ *      exit at once).  op[] lives on the device, so the entry cannot read it: it refuses an ops_mask with a bit outside the three codes
+ *      ("unknown op"), and the kernels treat like COPY every op[n] outside the three codes and every op[n] whose bit ops_mask lacks
+ *      (a HED image without the HED bit is NOT summed and NOT changed; bsum is then never read).  The class issues it on the output of the slot call, which passed
+ *      these images through as SSLCR_AUGV2_COPY.  The host makes the draws of augmentor.randomize() (augment.py); the kernels are the
+ *      deterministic arithmetic (csrc/augment_v2.hip spells it out).  With HED in ops_mask a byte-sum pass (integer atomics) runs first
+ *      over the HED images, for the cutoff test of HedColorAugmenter.transform; then one apply pass.  Reference lines per code: */
+#define SSLCR_AUGV2C_COPY 0           /* not picked for this image */
+#define SSLCR_AUGV2C_HED 1            /* hed() :135-144 = HedColorAugmenter.transform (models/augmenters/color/hedcoloraugmenter.py:149-207) on
+                                         models/augmenters/color/utils/custom_hed_transform.py:8-37, float32: x = float32(u8 * (1/255)) + 2,
+                                         stains = -log(x) . hed_from_rgb, stain_j = stain_j * param[j] + param[3 + j], rgb = exp(-stains . rgb_from_hed) - 2,
+                                         rescale_intensity(in_range=(-1, 1)), clip to [0, 1], * 255, truncate.  An image whose mean / 255 lies
+                                         outside [cutoff_lo, cutoff_hi] is left as it is (:162-163) */
+#define SSLCR_AUGV2C_HSV 2            /* hsv() :125-132 = HsbColorAugmenter.transform (models/augmenters/color/hsbcoloraugmenter.py:80-125), float64:
+                                         scikit-image 0.15.0 rgb2hsv, h = (h + param[0]) % 1, s *= 1 + param[1] (param[1] < 0) or
+                                         s *= 1 + (1 - s) param[1] (> 0), hsv2rgb, * 255, truncate */
+typedef struct sslcr_augv2_colour_desc {
+  uint8_t* img;             /* [N][3][H][W] (hwc=0) or [N][H][W][3] (hwc=1), modified in place */
+  const int32_t* op;        /* [N] device ints: SSLCR_AUGV2C_* */
+  const double* param;      /* [N][6] device doubles.  HED: float32(1 + sigma_j) for j = h, e, d, then float32(bias_j), each widened to double;
+                               HSV: (sigma_hue % 1.0, sigma_saturation), the rest unused */
+  unsigned long long* bsum; /* workspace [N], zeroed by the call; needed when ops_mask has HED */
+  double cutoff_lo, cutoff_hi;   /* HED: the cutoff_range of :141, (0.15, 0.85) */
+  float hed_from_rgb[9];    /* row-major 3x3 float32, as custom_hed_transform.py:8-11 builds them: inv(rgb_from_hed) and rgb_from_hed */
+  float rgb_from_hed[9];
+  unsigned ops_mask;        /* bit (1 << code) set for every code that occurs in op[] */
+  int N, H, W, hwc;
+} sslcr_augv2_colour_desc;
+int sslcr_randaug_v2_colour(const sslcr_augv2_colour_desc* d, void* stream);
 
 /* ==================================================================================================
  * Engine: the whole ResNet18 TripletNet(_Finetune)+head graph, forward / backward / update, orchestrated

@@ -70,6 +70,9 @@ BrightnessContrastDesc = _S("BrightnessContrastDesc", [("src", vp), ("dst", vp),
                                                        ("N", i32), ("H", i32), ("W", i32)])
 AugV2Desc = _S("AugV2Desc", [(k, vp) for k in ("src", "dst", "op", "factor", "fixed", "shift", "affine", "hist", "lsum", "lut", "tab")] +
                 [("ops_mask", C.c_uint)] + [(k, i32) for k in ("N", "H", "W", "src_hwc", "dst_hwc")])
+AugV2ColourDesc = _S("AugV2ColourDesc", [("img", vp), ("op", vp), ("param", vp), ("bsum", vp), ("cutoff_lo", f64), ("cutoff_hi", f64),
+                                         ("hed_from_rgb", f32 * 9), ("rgb_from_hed", f32 * 9), ("ops_mask", C.c_uint)] +
+                      [(k, i32) for k in ("N", "H", "W", "hwc")])
 PackDesc = _S("PackDesc", [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("gamma", vp), ("beta", vp), ("rmean", vp),
                            ("rvar", vp), ("eps", f32), ("bias_out", vp)] + [(k, i32) for k in ("K", "C", "R", "S", "dgrad_flip")] + [("scale_out", vp)])
 
@@ -127,6 +130,7 @@ SIGNATURES = {
     "sslcr_hed_colour_augment": (i32, [P(ColourAugDesc), vp]),
     "sslcr_brightness_contrast": (i32, [P(BrightnessContrastDesc), vp]),
     "sslcr_randaug_v2_slot": (i32, [P(AugV2Desc), vp]),
+    "sslcr_randaug_v2_colour": (i32, [P(AugV2ColourDesc), vp]),
 }
 
 _lib = None

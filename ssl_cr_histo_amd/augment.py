@@ -359,6 +359,87 @@ def pil_affine_bicubic(batch_u8, coefficients, apply=None, **kw):
     return randaug_v2_slot(batch_u8, [V2_BICUBIC if a else V2_COPY for a in ap], affine=coefficients, **kw)
 
 
+# The two histopathology ops of the pool (hed :135-144, hsv :125-132) run in place on the slot's output: csrc/augment_v2.hip restates
+# HedColorAugmenter / HsbColorAugmenter.transform and the scikit-image 0.15.0 conversions under them.  The host side makes the draws of
+# augmentor.randomize() and turns them into the numbers the in-place numpy ops of the reference use.
+V2C_COPY, V2C_HED, V2C_HSV = range(3)
+_V2_COLOUR = {"hed": V2C_HED, "hsv": V2C_HSV}
+HED_CUTOFF = (0.15, 0.85)                # cutoff_range of models/randaugment.py:141
+
+
+_V2_HED_MATRICES = None
+
+
+def v2_hed_matrices():
+    """-> (hed_from_rgb, rgb_from_hed) as float32 [3,3], built like custom_hed_transform.py:8-11: the float32 stain matrix and the
+    float32 of its inverse (numpy's inverse here, scipy's there)"""
+    global _V2_HED_MATRICES
+    if _V2_HED_MATRICES is None:
+        import numpy as np
+        m = np.array(_RGB_FROM_HED).astype(np.float32)
+        _V2_HED_MATRICES = (np.linalg.inv(m).astype(np.float32), m)
+    return _V2_HED_MATRICES
+
+
+def colour_param_row(name, draws):
+    """the six doubles of one image's ``param`` row from the draws of ``randomize()``: hed (s_h, s_e, s_d, b_h, b_e, b_d) ->
+    float32(1 + s_j) and float32(b_j), what ``patch_hed[:, :, j] *= (1.0 + s_j)`` / ``+= b_j`` use on a float32 array; hsv
+    (s_hue, s_sat[, s_brightness]) -> (s_hue % 1.0, s_sat), the brightness sigma of the pool's range (0, 0) being 0"""
+    import numpy as np
+    d = [float(v) for v in draws]
+    if name == "hed":
+        if len(d) != 6:
+            raise ValueError("hed: three sigmas and three biases expected")
+        return [float(np.float32(1.0 + v)) for v in d[:3]] + [float(np.float32(v)) for v in d[3:]]
+    if name == "hsv":
+        if len(d) not in (2, 3):
+            raise ValueError("hsv: hue and saturation sigma (and the unused brightness sigma) expected")
+        if len(d) == 3 and d[2] != 0.0:
+            raise ValueError("hsv: a brightness sigma other than 0 has no kernel (the pool's range is (0, 0))")
+        return [d[0] % 1.0 if d[0] != 0.0 else 0.0, d[1], 0.0, 0.0, 0.0, 0.0]
+    raise ValueError(f"no colour op {name!r}")
+
+
+def pil_colour_ops(batch_u8, names, params, *, hwc=False, out=None, workspace=None):
+    """The colour family: per image ``"hed"`` / ``"hsv"`` (``params[n]`` the draws of its ``randomize()``, see ``colour_param_row``)
+    or None = unchanged.  The kernels work in place: ``out=batch_u8`` modifies the batch itself, any other ``out`` (default: a new
+    batch) receives a copy first.  ``workspace``: an int64 [N] device tensor to reuse for the byte sums of the hed cutoff."""
+    import numpy as np
+    h, w = _v2_batch(batch_u8, hwc, "pil_colour_ops")
+    n, dev = batch_u8.shape[0], batch_u8.device
+    if len(names) != n or len(params) != n:
+        raise ValueError("one name and one parameter row per image expected")
+    codes, rows = np.zeros(n, np.int32), np.zeros((n, 6), np.float64)
+    for i, nm in enumerate(names):
+        if nm is not None:
+            if nm not in _V2_COLOUR:
+                raise ValueError(f"no colour op {nm!r}")
+            codes[i], rows[i] = _V2_COLOUR[nm], colour_param_row(nm, params[i])
+    if not np.isfinite(rows).all():
+        raise ValueError("params must be finite numbers")
+    dst = batch_u8 if out is batch_u8 else out if out is not None else torch.empty_like(batch_u8)
+    if dst is not batch_u8:
+        if dst.shape != batch_u8.shape or dst.dtype != torch.uint8 or not dst.is_contiguous() or dst.device != dev:
+            raise ValueError("out: contiguous uint8 batch of the input's shape expected")
+        dst.copy_(batch_u8)
+    mask = 0
+    for c in np.unique(codes):
+        mask |= 1 << int(c)
+    if not mask & ~(1 << V2C_COPY):
+        return dst
+    bsum = None
+    if mask & (1 << V2C_HED):
+        bsum = workspace if workspace is not None else torch.empty((n,), dtype=torch.int64, device=dev)
+        if bsum.dtype != torch.int64 or bsum.dim() != 1 or bsum.shape[0] < n or not bsum.is_contiguous() or bsum.device != dev:
+            raise ValueError("workspace: contiguous int64 [>= N] tensor on the batch's device expected")
+    t_op, t_p = torch.from_numpy(codes).to(dev), torch.from_numpy(rows).to(dev)
+    inv, fwd = v2_hed_matrices()
+    d = L.AugV2ColourDesc(L.ptr(dst), L.ptr(t_op), L.ptr(t_p), L.ptr(bsum), HED_CUTOFF[0], HED_CUTOFF[1],
+                          (L.f32 * 9)(*inv.reshape(-1).tolist()), (L.f32 * 9)(*fwd.reshape(-1).tolist()), mask, n, h, w, int(hwc))
+    L.check(L.lib().sslcr_randaug_v2_colour(d, L.stream_ptr()))
+    return dst
+
+
 class RandAugmentV2Device:
     """Batched counterpart of the RSP v2 ``RandAugment(n, m)`` (Pretraining_v2/models/randaugment.py:195-213) for a uint8 batch in HBM,
     [N,H,W,3] as the v2 dataset holds it or [N,3,H,W]; -> [N,3,H,W] uint8, what the stem ingests.
@@ -366,26 +447,48 @@ class RandAugmentV2Device:
     Per image the reference draws ``ops = random.sample(augment_pool, k=n)`` and per op ``val = np.random.uniform(1, m)``; rotate,
     translate and shear then draw ``random.choice([1, 0])``, 0 negating the level.  The same draws are made here on the host, image
     after image, from ``rng`` (a ``random.Random`` or the ``random`` module) and ``np_rng`` (a ``RandomState`` or ``numpy.random``);
-    the twelve Pillow ops then run on the device, one launch per op slot.  ``hed`` / ``hsv`` need scikit-image: they go through
-    ``host_ops[name](img_hwc_uint8_numpy, val) -> numpy`` if given (a round trip through host memory for that image and slot), else
-    NotImplementedError names the op.  A host op draws from numpy's global generator when it RUNS, after the whole batch has been
-    planned, so only batches served by the device ops alone consume the streams in the reference's image-by-image order."""
+    the twelve Pillow ops then run on the device, one launch per op slot.  ``hed`` / ``hsv`` (scikit-image arithmetic) depend on
+    ``colour_ops``:
+
+    ``"host"`` (default): they go through ``host_ops[name](img_hwc_uint8_numpy, val) -> numpy`` if given (a round trip through host
+    memory for that image and slot), else NotImplementedError names the op.  A host op draws from numpy's global generator when it
+    RUNS, after the whole batch has been planned, so only batches served by the device ops alone consume the streams in the
+    reference's image-by-image order.
+
+    ``"device"``: ``plan`` makes the op's own draws -- what ``augmentor.randomize()`` draws inside the op (:131, :143), from the same
+    numpy stream as ``val`` and right after it -- so the whole pool consumes both streams image by image as the reference does; they
+    ride in the row's third slot.  ``run`` passes those images through the slot call as COPY and then applies ``pil_colour_ops`` in
+    place to the slot's output: no host transfer, no synchronisation.  A name present in ``host_ops`` still goes to the host."""
 
     POOL = ("identity", "contrast", "brightness", "sharpness", "rotate", "translate_x", "translate_y", "shear_x", "shear_y",
             "hed", "hsv", "autocontrast", "color", "equalize")         # augment_pool() order: random.sample depends on it
     SIGNED = ("rotate", "translate_x", "translate_y", "shear_x", "shear_y")
     HOST = ("hed", "hsv")
 
-    def __init__(self, n, m, rng, np_rng, host_ops=None):
-        self.n, self.m, self.rng, self.np_rng, self.host_ops = n, m, rng, np_rng, host_ops or {}
+    def __init__(self, n, m, rng, np_rng, host_ops=None, colour_ops="host"):
+        if colour_ops not in ("host", "device"):
+            raise ValueError('colour_ops must be "host" or "device"')
+        self.n, self.m, self.rng, self.np_rng, self.host_ops, self.colour_ops = n, m, rng, np_rng, host_ops or {}, colour_ops
+
+    def _on_device(self, name):
+        return self.colour_ops == "device" and name in self.HOST and name not in self.host_ops
 
     def plan(self, count):
-        """the draws of ``count`` successive RandAugment calls -> [[(name, val, sign)] * n] * count; sign is None where none is drawn"""
+        """the draws of ``count`` successive RandAugment calls -> [[(name, val, sign)] * n] * count; sign is None where none is drawn.
+        For a device-side hed / hsv the third slot holds the op's own draws: (s_h, s_e, s_d, b_h, b_e, b_d) / (s_hue, s_sat, s_brightness)"""
         plan = []
         for _ in range(count):
             row = []
             for name in self.rng.sample(self.POOL, k=self.n):
                 val = float(self.np_rng.uniform(1, self.m))
+                if self._on_device(name):
+                    f = val * 0.03                   # hed() / hsv(): factor * 0.03, every range (-factor, factor)
+                    if name == "hed":                # HedColorAugmenter.randomize: the three sigmas, then the three biases
+                        extra = tuple(float(self.np_rng.uniform(-f, f)) for _ in range(6))
+                    else:                            # HsbColorAugmenter.randomize: the brightness range is (0, 0), not None: drawn, unused
+                        extra = (float(self.np_rng.uniform(-f, f)), float(self.np_rng.uniform(-f, f)), float(self.np_rng.uniform(0, 0)))
+                    row.append((name, val, extra))
+                    continue
                 if name in self.HOST and name not in self.host_ops:
                     raise NotImplementedError(f"RandAugment v2 op {name} (scikit-image) has no device kernel; pass host_ops[{name!r}]")
                 row.append((name, val, self.rng.choice([1, 0]) if name in self.SIGNED else None))
@@ -410,14 +513,19 @@ class RandAugmentV2Device:
             raise ValueError("one plan row per image expected")
         import numpy as np
         ws = v2_workspace(N, h, w, batch_u8.device)
+        bsum = torch.empty((N,), dtype=torch.int64, device=batch_u8.device) if self.colour_ops == "device" else None
         cur = batch_u8
         for slot in range(max(self.n, 1)):            # n = 0 still converts the layout
             codes, factor = np.zeros(N, np.int32), np.zeros(N, np.float32)
             fixed, affine, shift = np.zeros((N, 6), np.int32), np.zeros((N, 6), np.float64), np.zeros((N, 2), np.float64)
-            host = []
+            host, colour, cparams = [], [None] * N, [None] * N
             for i in range(N if self.n else 0):
                 name, val, sign = plan[i][slot]
-                if name in _V2_ENHANCE:
+                if self._on_device(name):
+                    if not isinstance(sign, tuple):
+                        raise ValueError(f"the plan row of a device-side {name} must carry its draws (plan() with colour_ops=\"device\")")
+                    colour[i], cparams[i] = name, sign          # COPY in the slot call, then in place on its output
+                elif name in _V2_ENHANCE:
                     codes[i], factor[i] = _V2_ENHANCE[name], enhance_factor(val)
                 elif name in _V2_POINT:
                     codes[i] = _V2_POINT[name]
@@ -436,6 +544,8 @@ class RandAugmentV2Device:
                         codes[i], affine[i] = V2_BICUBIC, (1, lv, 0, 0, 1, 0) if name == "shear_x" else (1, 0, 0, lv, 1, 0)
             nxt = randaug_v2_slot(cur, codes, factor=factor, fixed=fixed, shift=shift, affine=affine, hwc=hwc if slot == 0 else False,
                                   out_hwc=False, workspace=ws)
+            if any(colour):
+                pil_colour_ops(nxt, colour, cparams, out=nxt, workspace=bsum)
             for i in host:
                 name, val, _ = plan[i][slot]
                 img = nxt[i].permute(1, 2, 0).contiguous().cpu().numpy()
@@ -452,8 +562,8 @@ class TripletRandAugmentV2:
     on the three tile batches D1, D2, D3, the draws made triplet by triplet in the order D1, D2, D3 as the dataset makes them sample
     by sample.  -> three [N,3,H,W] uint8 batches."""
 
-    def __init__(self, n, m, rng, np_rng, host_ops=None):
-        self.aug = RandAugmentV2Device(n, m, rng, np_rng, host_ops)
+    def __init__(self, n, m, rng, np_rng, host_ops=None, colour_ops="host"):
+        self.aug = RandAugmentV2Device(n, m, rng, np_rng, host_ops, colour_ops)
 
     def __call__(self, d1, d2, d3, hwc=None):
         N = d1.shape[0]

@@ -16,6 +16,12 @@
 // All three are HBM-bound byte kernels (3 B in + 3 B out per pixel and slot; the statistics pass reads 3 B more for the images
 // that need it).  The point ops move 16 pixels per thread as 16-byte words when H*W is a multiple of 16; the neighbourhood ops
 // write 4 pixels per thread and gather their taps through the L1.
+//
+// The two histopathology ops of the pool, hed and hsv, run IN PLACE on the slot's output (sslcr_randaug_v2_colour):
+//   augv2c_sum_kernel    per HED image the sum of its 3 H W bytes (16-byte words, wave shuffles, one integer global add per wave):
+//                        the mean of HedColorAugmenter.transform's cutoff test, exact and order-free
+//   augv2c_apply_kernel  4 pixels per thread as dwords of the byte planes (CHW) or one 12-byte group (HWC), no LDS.  hsv is float64
+//                        (+ - x / floor and an exact remainder only: bit-reproducible), hed float32 with the accurate logf / expf
 #include "kernels.hpp"
 
 namespace sslcr {
@@ -32,7 +38,8 @@ __device__ inline bool uses_factor(int op) {
 __device__ inline uint32_t byte_of(const uint32_t* w, int k) { return (w[k >> 2] >> (8 * (k & 3))) & 255u; }
 
 // P consecutive pixels of one image, planar in registers: byte e of w[c] is channel c of pixel p0 + e.  vec: the whole batch is
-// 16-byte tileable (H*W % 16 == 0, 16-byte aligned base), so cnt == P and the accesses are P-byte (CHW) / 3P-byte (HWC) words
+// P-byte tileable (H*W % P == 0 and a P-byte aligned base: 16 bytes for P = 16, a dword for P = 4), so cnt == P and the accesses are
+// P-byte (CHW) / 3P-byte (HWC) words
 template <int P>
 struct Px { uint32_t w[3][P / 4]; };
 
@@ -400,6 +407,179 @@ __global__ __launch_bounds__(256) void augv2_apply_kernel(const sslcr_augv2_desc
     }
     store_px<4>(o, out, a.dst_hwc, hw, p0, cnt, vec);
   }
+}
+
+// ---- hed / hsv ------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// numpy's x % 1.0 for a float64: fmod, then + 1.0 where the remainder is negative.  fmod(x, 1.0) IS x - trunc(x): the difference of a
+// double and its integer part is representable, so the subtraction is exact (the zero's sign may differ; nothing downstream reads it)
+__device__ inline double mod1(double x) {
+  const double m = __dsub_rn(x, trunc(x));
+  return m < 0.0 ? __dadd_rn(m, 1.0) : m;
+}
+
+// HsbColorAugmenter.transform (hsbcoloraugmenter.py:80-125) for one pixel: scikit-image 0.15.0 rgb2hsv, the hue and saturation edits, hsv2rgb
+__device__ inline void hsv_pixel(uint32_t& R, uint32_t& G, uint32_t& B, double hshift, double ss) {
+  const double k = 1.0 / 255;                        // img_as_float: uint8 * (1 / 255)
+  const double r = __dmul_rn((double)R, k), g = __dmul_rn((double)G, k), b = __dmul_rn((double)B, k);
+  const double v = fmax(r, fmax(g, b)), mn = fmin(r, fmin(g, b));
+  const double delta = __dsub_rn(v, mn);
+  double s = 0.0, h = 0.0;
+  if (delta != 0.0) {
+    s = __ddiv_rn(delta, v);
+    double hue = 0.0;                                // red, then green, then blue: the later case overwrites the earlier one on a tie
+    if (r == v) hue = __ddiv_rn(__dsub_rn(g, b), delta);
+    if (g == v) hue = __dadd_rn(2.0, __ddiv_rn(__dsub_rn(b, r), delta));
+    if (b == v) hue = __dadd_rn(4.0, __ddiv_rn(__dsub_rn(r, g), delta));
+    h = mod1(__ddiv_rn(hue, 6.0));
+  }
+  h = mod1(__dadd_rn(h, hshift));
+  if (ss < 0.0) s = __dmul_rn(s, __dadd_rn(1.0, ss));
+  else if (ss > 0.0) s = __dmul_rn(s, __dadd_rn(1.0, __dmul_rn(__dsub_rn(1.0, s), ss)));
+  const double h6 = __dmul_rn(h, 6.0);
+  const double hi = floor(h6);
+  const double f = __dsub_rn(h6, hi);
+  const double p = __dmul_rn(v, __dsub_rn(1.0, s));
+  const double q = __dmul_rn(v, __dsub_rn(1.0, __dmul_rn(f, s)));
+  const double t = __dmul_rn(v, __dsub_rn(1.0, __dmul_rn(__dsub_rn(1.0, f), s)));
+  const int sel = (int)hi % 6;                       // hi is 0 .. 6
+  const double x0 = sel == 0 || sel == 5 ? v : sel == 1 ? q : sel == 4 ? t : p;
+  const double x1 = sel == 1 || sel == 2 ? v : sel == 0 ? t : sel == 3 ? q : p;
+  const double x2 = sel == 3 || sel == 4 ? v : sel == 2 ? t : sel == 5 ? q : p;
+  R = (uint32_t)(int)__dmul_rn(x0, 255.0) & 255u;    // (x * 255.0).astype(uint8): truncation
+  G = (uint32_t)(int)__dmul_rn(x1, 255.0) & 255u;
+  B = (uint32_t)(int)__dmul_rn(x2, 255.0) & 255u;
+}
+
+struct HedArgs { float mi[9], m[9], sig[3], bias[3]; };
+
+// HedColorAugmenter.transform (hedcoloraugmenter.py:164-202) on custom_hed_transform.py:22-37 for one pixel, float32
+__device__ inline void hed_pixel(uint32_t& R, uint32_t& G, uint32_t& B, const HedArgs& a) {
+  const double k = 1.0 / 255;
+  float L[3], st[3];
+  const uint32_t in[3] = {R, G, B};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) L[c] = -logf(__fadd_rn((float)__dmul_rn((double)in[c], k), 2.0f));
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const float d = __fadd_rn(__fadd_rn(__fmul_rn(L[0], a.mi[j]), __fmul_rn(L[1], a.mi[3 + j])), __fmul_rn(L[2], a.mi[6 + j]));
+    st[j] = -__fadd_rn(__fmul_rn(d, a.sig[j]), a.bias[j]);
+  }
+  uint32_t out[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float l = __fadd_rn(__fadd_rn(__fmul_rn(st[0], a.m[c]), __fmul_rn(st[1], a.m[3 + c])), __fmul_rn(st[2], a.m[6 + c]));
+    float x = __fsub_rn(expf(l), 2.0f);
+    x = fminf(fmaxf(x, -1.0f), 1.0f);                // rescale_intensity(in_range=(-1, 1)) of a float image: clip, normalise, scale back
+    x = __fadd_rn(__fmul_rn(__fdiv_rn(__fadd_rn(x, 1.0f), 2.0f), 2.0f), -1.0f);
+    x = fminf(fmaxf(x, 0.0f), 1.0f);
+    out[c] = (uint32_t)(int)__fmul_rn(x, 255.0f) & 255u;
+  }
+  R = out[0]; G = out[1]; B = out[2];
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void augv2c_sum_kernel(const sslcr_augv2_colour_desc a) {
+  const int n = blockIdx.y;
+  if (a.op[n] != SSLCR_AUGV2C_HED) return;           // block-uniform
+  const size_t total = (size_t)3 * a.H * a.W;        // the mean is over every byte: layout-blind
+  const uint8_t* img = a.img + (size_t)n * total;
+  const bool vec = ((uintptr_t)img & 15) == 0;
+  const size_t units = (total + 15) / 16;
+  unsigned long long sum = 0;
+  for (size_t u = (size_t)blockIdx.x * 256 + threadIdx.x; u < units; u += (size_t)gridDim.x * 256) {
+    const size_t b0 = u * 16;
+    if (vec && b0 + 16 <= total) {
+      const uint4 v = *reinterpret_cast<const uint4*>(img + b0);
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+      uint32_t s = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) s += (w[i] & 0x00ff00ffu) + ((w[i] >> 8) & 0x00ff00ffu);      // two 16-bit lanes, at most 8 * 255 each
+      sum += (s & 0xffffu) + (s >> 16);
+    } else {
+      const size_t b1 = b0 + 16 < total ? b0 + 16 : total;
+      for (size_t b = b0; b < b1; ++b) sum += img[b];
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o, 64);
+  if ((threadIdx.x & 63) == 0 && sum) atomicAdd(a.bsum + n, sum);
+}
+
+__global__ __launch_bounds__(256) void augv2c_apply_kernel(const sslcr_augv2_colour_desc a, const int vec) {
+  const int n = blockIdx.y;
+  const int op = a.op[n];
+  // block-uniform: COPY, any code the entry does not know, and a code whose bit ops_mask lacks (for HED the sum pass did not run and
+  // bsum may be NULL) leave the image as it is
+  if ((op != SSLCR_AUGV2C_HED && op != SSLCR_AUGV2C_HSV) || !(a.ops_mask & 1u << op)) return;
+  const size_t hw = (size_t)a.H * a.W;
+  uint8_t* img = a.img + (size_t)n * 3 * hw;
+  const double* prm = a.param + (size_t)n * 6;
+  const size_t units = (hw + 3) / 4;
+  const size_t t0 = (size_t)blockIdx.x * 256 + threadIdx.x, tstep = (size_t)gridDim.x * 256;
+  if (op == SSLCR_AUGV2C_HSV) {
+    const double hshift = prm[0], ss = prm[1];
+    for (size_t u = t0; u < units; u += tstep) {
+      const size_t p0 = u * 4;
+      const int cnt = hw - p0 < 4 ? (int)(hw - p0) : 4;
+      Px<4> p;
+      load_px<4>(p, img, a.hwc, hw, p0, cnt, vec);
+      uint32_t o[3] = {0, 0, 0};
+#pragma unroll 2
+      for (int e = 0; e < 4; ++e) {                  // a lane past cnt computes on zero bytes; store_px drops it
+        uint32_t r = (p.w[0][0] >> (8 * e)) & 255u, g = (p.w[1][0] >> (8 * e)) & 255u, b = (p.w[2][0] >> (8 * e)) & 255u;
+        hsv_pixel(r, g, b, hshift, ss);
+        o[0] |= r << (8 * e); o[1] |= g << (8 * e); o[2] |= b << (8 * e);
+      }
+      p.w[0][0] = o[0]; p.w[1][0] = o[1]; p.w[2][0] = o[2];
+      store_px<4>(p, img, a.hwc, hw, p0, cnt, vec);
+    }
+    return;
+  }
+  // hed: HedColorAugmenter.transform's cutoff (:162-163), np.mean(patch) / 255.0 -- the integer sum is exact in a double
+  const double mean = __ddiv_rn(__ddiv_rn((double)a.bsum[n], (double)(3 * hw)), 255.0);
+  if (!(a.cutoff_lo <= mean && mean <= a.cutoff_hi)) return;
+  HedArgs ha;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) { ha.mi[i] = a.hed_from_rgb[i]; ha.m[i] = a.rgb_from_hed[i]; }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) { ha.sig[j] = (float)prm[j]; ha.bias[j] = (float)prm[3 + j]; }
+  for (size_t u = t0; u < units; u += tstep) {
+    const size_t p0 = u * 4;
+    const int cnt = hw - p0 < 4 ? (int)(hw - p0) : 4;
+    Px<4> p;
+    load_px<4>(p, img, a.hwc, hw, p0, cnt, vec);
+    uint32_t o[3] = {0, 0, 0};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      uint32_t r = (p.w[0][0] >> (8 * e)) & 255u, g = (p.w[1][0] >> (8 * e)) & 255u, b = (p.w[2][0] >> (8 * e)) & 255u;
+      hed_pixel(r, g, b, ha);
+      o[0] |= r << (8 * e); o[1] |= g << (8 * e); o[2] |= b << (8 * e);
+    }
+    p.w[0][0] = o[0]; p.w[1][0] = o[1]; p.w[2][0] = o[2];
+    store_px<4>(p, img, a.hwc, hw, p0, cnt, vec);
+  }
+}
+
+hipError_t launch_augv2_colour(const sslcr_augv2_colour_desc& a, hipStream_t st) {
+  const size_t hw = (size_t)a.H * a.W;
+  const int vec = hw % 4 == 0 && ((uintptr_t)a.img & 3) == 0;      // every plane / every 12-byte pixel group of every image on a dword
+  hipError_t e;
+  if (a.ops_mask & 1u << SSLCR_AUGV2C_HED) {
+    if ((e = hipMemsetAsync(a.bsum, 0, (size_t)a.N * sizeof(unsigned long long), st)) != hipSuccess) return e;
+    const size_t units = (3 * hw + 15) / 16;
+    int bx = (int)((units + 255) / 256);
+    if (bx > 16) bx = 16;
+    hipLaunchKernelGGL(augv2c_sum_kernel, dim3(bx, a.N), dim3(256), 0, st, a);
+  }
+  if (a.ops_mask & (1u << SSLCR_AUGV2C_HED | 1u << SSLCR_AUGV2C_HSV)) {
+    const size_t units = (hw + 3) / 4;
+    int bx = (int)((units + 255) / 256);             // one pass of 4 pixels per thread up to 256 x 256, a grid-stride loop beyond
+    if (bx > 64) bx = 64;
+    hipLaunchKernelGGL(augv2c_apply_kernel, dim3(bx, a.N), dim3(256), 0, st, a, vec);
+  }
+  return hipGetLastError();
 }
 
 hipError_t launch_augv2(const sslcr_augv2_desc& a, hipStream_t st) {

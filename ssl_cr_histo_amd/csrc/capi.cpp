@@ -30,7 +30,7 @@ using namespace sslcr;
 
 extern "C" {
 
-int sslcr_version(void) { return 10; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
+int sslcr_version(void) { return 11; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
 const char* sslcr_last_error(void) { return g_err; }
 
 int sslcr_conv2d(int dtype, const sslcr_conv_desc* d, void* stream) {
@@ -273,6 +273,17 @@ int sslcr_randaug_v2_slot(const sslcr_augv2_desc* d, void* stream) {
   NEED(!(m & 1u << SSLCR_AUGV2_NEAREST_TABLE) || (d->shift && d->tab), "shift / tab workspace");
   NEED(!(m & 1u << SSLCR_AUGV2_BICUBIC) || d->affine, "affine");
   return check(launch_augv2(*d, (hipStream_t)stream), "randaug_v2_slot");
+}
+int sslcr_randaug_v2_colour(const sslcr_augv2_colour_desc* d, void* stream) {
+  NEED(d && d->img && d->op, "null");
+  NEED(d->param, "param");
+  NEED(d->N > 0 && d->N <= 65535 && d->H > 0 && d->W > 0 && d->H <= 16384 && d->W <= 16384, "batch shape");
+  NEED(d->ops_mask < (1u << (SSLCR_AUGV2C_HSV + 1)), "ops_mask names an unknown op");
+  NEED(!(d->ops_mask & 1u << SSLCR_AUGV2C_HED) || d->bsum, "bsum workspace");
+  NEED(!(d->ops_mask & 1u << SSLCR_AUGV2C_HED) || (reinterpret_cast<uintptr_t>(d->bsum) & 7) == 0, "bsum alignment");
+  NEED((reinterpret_cast<uintptr_t>(d->param) & 7) == 0 && (reinterpret_cast<uintptr_t>(d->op) & 3) == 0, "alignment");
+  NEED(d->cutoff_lo <= d->cutoff_hi, "cutoff range");
+  return check(launch_augv2_colour(*d, (hipStream_t)stream), "randaug_v2_colour");
 }
 int sslcr_pack_stem(int dtype, const sslcr_pack_desc* d, void* stream) {
   DT_OK(dtype);

@@ -208,6 +208,7 @@ hipError_t launch_weak_augment(const sslcr_weak_aug_desc& a, hipStream_t st);
 hipError_t launch_hed_colour(const sslcr_colour_aug_desc& a, hipStream_t st);
 hipError_t launch_brightness_contrast(const sslcr_brightness_contrast_desc& a, hipStream_t st);
 hipError_t launch_augv2(const sslcr_augv2_desc& a, hipStream_t st);
+hipError_t launch_augv2_colour(const sslcr_augv2_colour_desc& a, hipStream_t st);
 // optim.hip
 struct OptTable { OptArgs row[SSLCR_MAX_OPT_GROUPS]; };   // the kernels' by-value table: a tensor's row is row[TensorDesc.group]
 // every row a no-op (SGD with lr 0, momentum 1 and gradient scale 0: p and the momentum buffer are rewritten with their own values;
