@@ -29,13 +29,14 @@ extern "C" {
 #define SSLCR_BF16 1
 #define SSLCR_FP8 2   /* engine mode only (sslcr_create): bf16 storage and backward, fp8 e4m3 forward for the eligible 3x3 convs */
 
-/* the library round (11 here).  ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
+/* the library round (12 here).  ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
  * 7 = sslcr_randaug_v2_slot added (nothing else changed); 8 = optimizer parameter groups, AdamW and the global gradient norm
  * (sslcr_tensor_desc.group, sslcr_opt_desc.kind 2, sslcr_optimizer_step_groups, sslcr_grad_norm, sslcr_net_optimizer_step_groups,
  * sslcr_net_grad_norm: all additive); 9 = gradient accumulation (sslcr_grad_accumulate, sslcr_net_set_grad_accumulate: additive,
  * off by default); 10 = loss options (sslcr_loss_opts, sslcr_loss_ex, sslcr_ce_denominator, sslcr_net_set_loss_opts: additive, the
  * defaults issue the launches of version 9); 11 = sslcr_randaug_v2_colour added (the hed / hsv ops of the v2 pool; additive,
- * sslcr_augv2_desc and sslcr_randaug_v2_slot are unchanged). */
+ * sslcr_augv2_desc and sslcr_randaug_v2_slot are unchanged); 12 = device-resident inference: sslcr_wsi_gather and sslcr_predict added
+ * (additive; sslcr_softmax_col keeps its launch and its bits). */
 int sslcr_version(void);
 const char* sslcr_last_error(void);
 
@@ -333,6 +334,31 @@ int sslcr_loss_ex(const sslcr_loss_desc* d, const sslcr_loss_opts* opts, void* s
 int sslcr_ce_denominator(const int64_t* target_i, int n, int C, const float* class_weight, int ignore_index, float* out2, void* stream);
 /* out[i] = softmax(logits[i, 0..C-1])[col]: the per-tile 'tumor' probability of test_Camelyon16.py:58-60 (row f3) */
 int sslcr_softmax_col(const float* logits, float* out, int n, int C, int col, void* stream);
+/* library version >= 12.  What the reference's test() loops take from a batch of logits, in one launch, every output optional (NULL):
+ *   scores[i][c]              = softmax(logits[i])[c]                      torch.softmax(output, dim=-1), eval_Kather_SSL_CR.py:211
+ *   pred[i]                   = argmax_c logits[i][c]                      torch.argmax(output, dim=1), :220 / eval_Kather_SSL.py:190:
+ *                               the LOWEST index of the row maximum; a NaN counts as the maximum (the lowest NaN index wins)
+ *   confusion[target][pred]  += 1                                          sklearn's confusion_matrix(targets, predictions) of
+ *                               eval_Kather_SSL_CR.py:646-658 / eval_Kather_SSL.py:519-530, accumulated ACROSS calls by integer
+ *                               atomics (exact, order-independent); the caller zeroes it; rows with target outside [0, C) are skipped
+ *   map[map_index[i]]         = softmax(logits[i])[col]                    probs_map[x_mask, y_mask] = probs, test_Camelyon16.py:58-62;
+ *                               the value has the bits of sslcr_softmax_col (one device function); an index outside [0, map_size) is
+ *                               skipped; duplicate indices within one call are undefined
+ * Errors, decided before the launch: NULL logits, n < 0, C outside [1, 64], confusion without target, map without map_index, col outside
+ * [0, C), map_size < 0.  n == 0 is a no-op.  Rows of any count are served; no float atomics. */
+typedef struct sslcr_predict_desc {
+  const float* logits;        /* [n][C] */
+  int n, C;
+  const int64_t* target;      /* [n] or NULL */
+  float* scores;              /* [n][C] or NULL */
+  int64_t* pred;              /* [n] or NULL */
+  int64_t* confusion;         /* [C][C] or NULL (8-byte aligned) */
+  int col;                    /* 0 <= col < C */
+  float* map;                 /* [map_size] or NULL */
+  const int64_t* map_index;   /* [n] */
+  int64_t map_size;
+} sslcr_predict_desc;
+int sslcr_predict(const sslcr_predict_desc* d, void* stream);
 
 /* ---- optimizers (torch.optim.Adam / SGD nesterov as the reference configures them,
  *      eval_BreastPathQ_SSL_CR.py:481, eval_Camelyon_SSL_CR.py:514, pretrain_BreastPathQ.py:245; Lookahead lookahead.py:81-106) */
@@ -402,6 +428,21 @@ typedef struct sslcr_weak_aug_desc {
   int N, SH, SW, OH, OW, src_hwc;
 } sslcr_weak_aug_desc;
 int sslcr_weak_augment(const sslcr_weak_aug_desc* d, void* stream);
+
+/* ---- device-side WSI tiling (row f3): the read_region + np.array(...).transpose((2, 0, 1)) of DatasetCamelyon16_test.__getitem__
+ *      (dataset.py:983-996) for a whole batch of tiles, from ONE slide region that is already in HBM (library version >= 12):
+ *        dst[n][c][i][j] = src[top - origin_y + i][left - origin_x + j][c]   where that pixel lies inside the region, `fill` elsewhere
+ *      with (left, top) = xy[n]: tiles partly or wholly outside the region, on any side, are served.  Source offsets are 64-bit (a
+ *      region may exceed 2^32 bytes).  A byte gather: no floating point, no atomics, one launch.  Errors, decided before the launch:
+ *      NULL pointers, S < 1, N < 0, RH < 1, RW < 1, fill outside [0, 255].  N == 0 is a no-op. */
+typedef struct sslcr_wsi_gather_desc {
+  const uint8_t* src;     /* [RH][RW][3], the PIL / numpy layout */
+  const int32_t* xy;      /* [N][2] device ints: level-0 (left, top) of every tile */
+  uint8_t* dst;           /* [N][3][S][S] */
+  int origin_x, origin_y; /* level-0 coordinates of src[0][0] */
+  int N, RH, RW, S, fill;
+} sslcr_wsi_gather_desc;
+int sslcr_wsi_gather(const sslcr_wsi_gather_desc* d, void* stream);
 
 /* ---- device-side strong augmentation, the colour ops of the reference's RandAugment pool ("next" row f4) on a uint8 batch in HBM.
  *      As with sslcr_weak_augment the random draws stay on the host, in the reference's order (ssl_cr_histo_amd/augment.py);

@@ -73,6 +73,10 @@ AugV2Desc = _S("AugV2Desc", [(k, vp) for k in ("src", "dst", "op", "factor", "fi
 AugV2ColourDesc = _S("AugV2ColourDesc", [("img", vp), ("op", vp), ("param", vp), ("bsum", vp), ("cutoff_lo", f64), ("cutoff_hi", f64),
                                          ("hed_from_rgb", f32 * 9), ("rgb_from_hed", f32 * 9), ("ops_mask", C.c_uint)] +
                       [(k, i32) for k in ("N", "H", "W", "hwc")])
+WsiGatherDesc = _S("WsiGatherDesc", [("src", vp), ("xy", vp), ("dst", vp)] +
+                   [(k, i32) for k in ("origin_x", "origin_y", "N", "RH", "RW", "S", "fill")])
+PredictDesc = _S("PredictDesc", [("logits", vp), ("n", i32), ("C", i32), ("target", vp), ("scores", vp), ("pred", vp), ("confusion", vp),
+                                 ("col", i32), ("map", vp), ("map_index", vp), ("map_size", C.c_int64)])
 PackDesc = _S("PackDesc", [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("gamma", vp), ("beta", vp), ("rmean", vp),
                            ("rvar", vp), ("eps", f32), ("bias_out", vp)] + [(k, i32) for k in ("K", "C", "R", "S", "dgrad_flip")] + [("scale_out", vp)])
 
@@ -117,6 +121,8 @@ SIGNATURES = {
     "sslcr_loss_ex": (i32, [P(LossDesc), P(LossOpts), vp]),
     "sslcr_ce_denominator": (i32, [vp, i32, i32, vp, i32, vp, vp]),
     "sslcr_softmax_col": (i32, [vp, vp, i32, i32, i32, vp]),
+    "sslcr_predict": (i32, [P(PredictDesc), vp]),
+    "sslcr_wsi_gather": (i32, [P(WsiGatherDesc), vp]),
     "sslcr_optimizer_step": (i32, [vp, i32, i32, P(OptDesc), vp]),
     "sslcr_optimizer_step_groups": (i32, [vp, i32, i32, P(OptDesc), i32, vp, vp]),
     "sslcr_grad_norm": (i32, [vp, sz, f32, vp, vp, vp]),

@@ -30,7 +30,7 @@ using namespace sslcr;
 
 extern "C" {
 
-int sslcr_version(void) { return 11; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
+int sslcr_version(void) { return 12; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
 const char* sslcr_last_error(void) { return g_err; }
 
 int sslcr_conv2d(int dtype, const sslcr_conv_desc* d, void* stream) {
@@ -202,6 +202,28 @@ int sslcr_ce_denominator(const int64_t* target_i, int n, int C, const float* cla
 int sslcr_softmax_col(const float* logits, float* out, int n, int C, int col, void* stream) {
   NEED(logits && out && n > 0 && C > 0 && C <= 64 && col >= 0 && col < C, "args");
   return check(launch_softmax_col(logits, out, n, C, col, (hipStream_t)stream), "softmax_col");
+}
+
+int sslcr_predict(const sslcr_predict_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  NEED(d->n >= 0 && d->C >= 1 && d->C <= 64, "n >= 0 and 1 <= C <= 64");
+  if (d->n == 0) return 0;
+  NEED(d->logits, "null logits");
+  NEED(!d->confusion || d->target, "confusion needs target");
+  NEED((reinterpret_cast<uintptr_t>(d->confusion) & 7) == 0, "confusion alignment");
+  NEED(!d->map || (d->map_index && d->map_size >= 0), "map needs map_index and map_size >= 0");
+  NEED(!d->map || (d->col >= 0 && d->col < d->C), "col outside [0, C)");
+  return check(launch_predict(*d, (hipStream_t)stream), "predict");
+}
+int sslcr_wsi_gather(const sslcr_wsi_gather_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  NEED(d->S >= 1 && d->N >= 0, "S >= 1 and N >= 0");
+  NEED(d->RH >= 1 && d->RW >= 1, "empty region");
+  NEED(d->fill >= 0 && d->fill <= 255, "fill outside [0, 255]");
+  if (d->N == 0) return 0;
+  NEED(d->src && d->xy && d->dst, "null tensor");
+  NEED((reinterpret_cast<uintptr_t>(d->xy) & 3) == 0, "xy alignment");
+  return check(launch_wsi_gather(*d, (hipStream_t)stream), "wsi_gather");
 }
 
 int sslcr_optimizer_step(const sslcr_tensor_desc* device_descs, int ntensors, int max_n, const sslcr_opt_desc* o, void* stream) {

@@ -483,19 +483,77 @@ __global__ __launch_bounds__(256) void loss_ex_kernel(const LossArgs a, const Lo
   }
 }
 
+// softmax(l[0..C-1])[col] with the row's max m and sum s = sum_c expf(l[c] - m): the ONE place this quotient is formed, shared by
+// softmax_col_kernel and predict_kernel so that a probability map has the same bits whichever entry wrote it
+__device__ __forceinline__ void softmax_row_stats(const float* l, int C, float& m, float& s) {
+  m = l[0];
+  for (int c = 1; c < C; ++c) m = fmaxf(m, l[c]);
+  s = 0.f;
+  for (int c = 0; c < C; ++c) s += expf(l[c] - m);
+}
+__device__ __forceinline__ float softmax_value(const float* l, int col, float m, float s) { return expf(l[col] - m) / s; }
+
 // out[i] = softmax(logits[i, :])[col] -- the 'tumor' probability of test_Camelyon16.py:58-60
 __global__ __launch_bounds__(256) void softmax_col_kernel(const float* logits, float* out, int n, int C, int col) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const float* l = logits + (long)i * C;
-  float m = l[0];
-  for (int c = 1; c < C; ++c) m = fmaxf(m, l[c]);
-  float s = 0.f;
-  for (int c = 0; c < C; ++c) s += expf(l[c] - m);
-  out[i] = expf(l[col] - m) / s;
+  float m, s;
+  softmax_row_stats(l, C, m, s);
+  out[i] = softmax_value(l, col, m, s);
 }
 hipError_t launch_softmax_col(const float* logits, float* out, int n, int C, int col, hipStream_t st) {
   hipLaunchKernelGGL(softmax_col_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, logits, out, n, C, col);
+  return hipGetLastError();
+}
+
+// sslcr_predict: what the reference's test() loops take from a batch of logits (eval_Kather_SSL_CR.py:211-226, eval_Kather_SSL.py:190-195,
+// test_Camelyon16.py:58-62), one row per thread, every output optional.  torch.argmax's tie and NaN rules: the lowest index of the
+// maximum, a NaN is the maximum.  The confusion matrix is counted per workgroup in LDS (32-bit integer atomics, at most 256 per cell)
+// and flushed with one 64-bit integer atomic per non-empty cell: exact and order-independent, it accumulates across calls.
+__global__ __launch_bounds__(256) void predict_kernel(const sslcr_predict_desc a) {
+  __shared__ unsigned cells[64 * 64];
+  const int C = a.C;
+  if (a.confusion) {
+    for (int k = threadIdx.x; k < C * C; k += 256) cells[k] = 0u;
+    __syncthreads();
+  }
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < a.n) {
+    const float* l = a.logits + i * C;
+    if (a.scores || a.map) {
+      float m, s;
+      softmax_row_stats(l, C, m, s);
+      if (a.scores)
+        for (int c = 0; c < C; ++c) a.scores[i * C + c] = softmax_value(l, c, m, s);
+      if (a.map) {
+        const int64_t k = a.map_index[i];
+        if (k >= 0 && k < a.map_size) a.map[k] = softmax_value(l, a.col, m, s);
+      }
+    }
+    if (a.pred || a.confusion) {
+      int b = 0;
+      float m = l[0];
+      for (int c = 1; c < C; ++c) {
+        const float v = l[c];
+        if (m == m && (v > m || v != v)) { m = v; b = c; }       // once m is a NaN it stays: the lowest NaN index wins
+      }
+      if (a.pred) a.pred[i] = b;
+      if (a.confusion) {
+        const int64_t y = a.target[i];
+        if (y >= 0 && y < C) atomicAdd(&cells[(int)y * C + b], 1u);
+      }
+    }
+  }
+  if (a.confusion) {
+    __syncthreads();
+    for (int k = threadIdx.x; k < C * C; k += 256)
+      if (cells[k]) atomicAdd(reinterpret_cast<unsigned long long*>(a.confusion) + k, (unsigned long long)cells[k]);
+  }
+}
+hipError_t launch_predict(const sslcr_predict_desc& a, hipStream_t st) {
+  if (a.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(predict_kernel, dim3(cdiv(a.n, 256)), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -203,6 +203,9 @@ inline const char* loss_opts_error(int kind, int C, const LossOpts& o) {
   return nullptr;
 }
 hipError_t launch_softmax_col(const float* logits, float* out, int n, int C, int col, hipStream_t st);
+hipError_t launch_predict(const sslcr_predict_desc& a, hipStream_t st);
+// wsi.hip
+hipError_t launch_wsi_gather(const sslcr_wsi_gather_desc& a, hipStream_t st);
 // augment.hip
 hipError_t launch_weak_augment(const sslcr_weak_aug_desc& a, hipStream_t st);
 hipError_t launch_hed_colour(const sslcr_colour_aug_desc& a, hipStream_t st);

@@ -1,0 +1,156 @@
+"""Device-resident test-time inference: WSI tiling from a slide region held in HBM, and classification metrics from an integer
+confusion matrix counted on the device.
+
+WSI (row f3).  The reference's ``DatasetCamelyon16_test`` (dataset.py:943-996) makes one ``read_region`` per tissue pixel of the mask and
+hands a float32 tile to the loader; neighbouring tiles overlap by (1 - resolution / image_size) of their area.  ``WsiDeviceLoader``
+uploads the region's uint8 bytes once, computes the tile coordinates with the reference's own expressions (``tile_origins``) and cuts
+every batch on the device (``gather_tiles`` -> sslcr_wsi_gather); ``steps.camelyon16_test`` recognises it and keeps the probability map
+on the device until one copy at the end.  openslide / h5 I/O is not part of this package: the caller reads the region (for instance
+``np.asarray(slide.read_region((ox, oy), 0, (w, h)).convert('RGB'))``) and passes ``origin=(ox, oy)``.  What a tile that leaves the
+region holds is the caller's statement (``fill``): openslide returns transparent pixels there, ``.convert('RGB')`` makes them black, which
+is the default 0 -- unpinned against openslide itself.
+
+Metrics.  The Kather mains build sklearn's confusion matrix and a weighted F1 from what ``test()`` returns
+(eval_Kather_SSL_CR.py:646-658, eval_Kather_SSL.py:519-530).  ``ConfusionMeter`` counts the same matrix on the device, batch by batch,
+with integer atomics; ``metrics_from_confusion`` derives the figures from it in host float64.
+"""
+import numpy as np
+import torch
+
+from . import kernels as K
+
+
+def tile_origins(mask, resolution, image_size):
+    """-> (x_idcs, y_idcs, xy int32 [n, 2]): the tissue pixels of ``mask`` in ``np.where(mask)`` order (dataset.py:978) and the level-0
+    (left, top) of their tiles, ``int(int(x_mask * resolution) - image_size / 2)`` (dataset.py:987-991).  ``int()`` truncates toward
+    zero: ``int(0 * 64 - 224 / 2) == -112``, ``int(0 * 64 - 255 / 2) == -127``."""
+    x_idcs, y_idcs = np.where(np.asarray(mask))
+    half = image_size / 2
+    xy = np.empty((len(x_idcs), 2), dtype=np.int64)
+    for k, idcs in enumerate((x_idcs, y_idcs)):
+        centre = np.trunc(idcs * resolution)                       # int(x_mask * resolution); exact in float64 at slide magnitudes
+        xy[:, k] = np.trunc(centre - half).astype(np.int64)        # int(x_center - image_size / 2)
+    if len(xy) and (xy.min() < -(1 << 31) or xy.max() >= 1 << 31):
+        raise ValueError("tile_origins: a tile coordinate does not fit int32")
+    return x_idcs, y_idcs, xy.astype(np.int32)
+
+
+def gather_tiles(region_u8_hwc, xy, size, *, origin=(0, 0), fill=0, out=None):
+    """uint8 NCHW tiles [N, 3, size, size] from a device-resident uint8 region [RH, RW, 3]: ``kernels.wsi_gather``.  xy: device int32
+    [N, 2] level-0 (left, top); origin: level-0 coordinates of ``region[0, 0]``; fill: the value of pixels outside the region."""
+    return K.wsi_gather(region_u8_hwc, xy, size, origin=origin, fill=fill, out=out)
+
+
+def default_resolution(slide_wh, mask_shape):
+    """the reference's ``round(X_slide / X_mask)`` with its two checks (dataset.py:963-975); the mask is indexed [x, y]"""
+    X_slide, Y_slide = slide_wh
+    X_mask, Y_mask = mask_shape
+    if round(X_slide / X_mask) != round(Y_slide / Y_mask):
+        raise Exception('Slide/Mask dimension does not match , X_slide / X_mask : {} / {}, Y_slide / Y_mask : {} / {}'
+                        .format(X_slide, X_mask, Y_slide, Y_mask))
+    resolution = round(X_slide * 1.0 / X_mask)
+    if not np.log2(resolution).is_integer():
+        raise Exception('Resolution (X_slide / X_mask) is not power of 2 : {}'.format(resolution))
+    return resolution
+
+
+class _WsiDataset:
+    def __init__(self, mask, x_idcs, y_idcs, resolution, image_size):
+        self.mask, self.X_idcs, self.Y_idcs, self.resolution, self.image_size = mask, x_idcs, y_idcs, resolution, image_size
+
+    def __len__(self):
+        return len(self.X_idcs)
+
+
+class WsiDeviceLoader:
+    """The loader of ``test_Camelyon16.test`` with the slide region in HBM.  region_u8_hwc: host (numpy / torch) or device uint8
+    [RH, RW, 3], uploaded once; mask: the tissue mask, indexed [x, y] as the reference's (transposed against the image); resolution:
+    level-0 pixels per mask pixel, default ``round(RW / mask.shape[0])`` under the reference's two checks; origin: level-0 (x, y) of
+    ``region[0, 0]``; fill: what a tile holds outside the region.  ``.dataset.mask`` and ``len()`` (batches) as the reference loader.
+    The coordinate table and the flat map indices are computed and uploaded once; iterating yields the reference's
+    ``(tiles, x_mask, y_mask)`` batches with the tiles as device uint8, so any consumer of the host loader can read it too."""
+
+    def __init__(self, region_u8_hwc, mask, image_size, batch_size, *, resolution=None, origin=(0, 0), fill=0, device=None):
+        mask = np.asarray(mask)
+        if mask.ndim != 2:
+            raise ValueError("WsiDeviceLoader: a 2-D tissue mask expected")
+        region = torch.as_tensor(region_u8_hwc)
+        if region.dtype != torch.uint8 or region.dim() != 3 or region.shape[2] != 3:
+            raise ValueError("WsiDeviceLoader: a uint8 region [RH, RW, 3] expected")
+        if int(batch_size) < 1 or int(image_size) < 1:
+            raise ValueError("WsiDeviceLoader: batch_size and image_size must be positive")
+        if resolution is None:
+            resolution = default_resolution((region.shape[1], region.shape[0]), mask.shape)
+        x_idcs, y_idcs, xy = tile_origins(mask, resolution, image_size)
+        if not region.is_cuda:
+            region = region.to(torch.device(device if device is not None else "cuda"), non_blocking=True)
+        self.region = region.contiguous()
+        self.image_size, self.batch_size, self.origin, self.fill = int(image_size), int(batch_size), (int(origin[0]), int(origin[1])), int(fill)
+        self.dataset = _WsiDataset(mask, x_idcs, y_idcs, resolution, self.image_size)
+        self.x_mask, self.y_mask = torch.from_numpy(x_idcs.copy()), torch.from_numpy(y_idcs.copy())
+        dev = self.region.device
+        self.xy = torch.from_numpy(xy).to(dev)
+        self.map_index = torch.from_numpy(x_idcs.astype(np.int64) * mask.shape[1] + y_idcs).to(dev)     # probs_map[x, y], row-major
+
+    def __len__(self):
+        return (len(self.dataset) + self.batch_size - 1) // self.batch_size
+
+    def ranges(self):
+        n = len(self.dataset)
+        return [(lo, min(lo + self.batch_size, n)) for lo in range(0, n, self.batch_size)]
+
+    def tiles(self, lo, hi, out=None):
+        return gather_tiles(self.region, self.xy[lo:hi], self.image_size, origin=self.origin, fill=self.fill, out=out)
+
+    def __iter__(self):
+        for lo, hi in self.ranges():
+            yield self.tiles(lo, hi), self.x_mask[lo:hi], self.y_mask[lo:hi]
+
+
+class ConfusionMeter:
+    """int64 [C, C] confusion matrix on the device, rows = targets, columns = predictions (sklearn's ``confusion_matrix`` layout);
+    ``update(logits, target)`` adds one batch (argmax of fp32 logits [n, C]; rows with a target outside [0, C) are skipped) without a
+    sync; ``cpu()`` is the one copy."""
+
+    def __init__(self, C, device):
+        if not 1 <= int(C) <= 64:
+            raise ValueError(f"ConfusionMeter: C = {C} outside [1, 64]")
+        self.C = int(C)
+        self.matrix = torch.zeros((self.C, self.C), dtype=torch.int64, device=device)
+
+    def update(self, logits, target):
+        K.predict(logits, target, pred=False, confusion=self.matrix)
+        return self
+
+    def reset(self):
+        self.matrix.zero_()
+
+    def cpu(self):
+        return self.matrix.cpu()
+
+
+def _div(a, b):
+    """a / b with 0 where b == 0 (sklearn's zero_division default value)"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return np.divide(a, b, out=np.zeros(np.broadcast(a, b).shape, dtype=np.float64), where=b != 0)
+
+
+def metrics_from_confusion(cm):
+    """host float64 figures of an integer confusion matrix [C, C] (rows = targets): dict with ``accuracy``, per-class ``precision`` /
+    ``recall`` / ``f1`` / ``support`` (int64), ``weighted_f1`` (sklearn's ``f1_score(average='weighted')``) and ``multilabel`` [C, 2, 2]
+    int64 = ``multilabel_confusion_matrix`` ([[tn, fp], [fn, tp]] per class).  A division by zero gives 0."""
+    cm = np.asarray(cm.cpu() if torch.is_tensor(cm) else cm)
+    if cm.ndim != 2 or cm.shape[0] != cm.shape[1] or not np.issubdtype(cm.dtype, np.integer):
+        raise ValueError("metrics_from_confusion: a square integer matrix expected")
+    cm = cm.astype(np.int64)
+    total = cm.sum()
+    tp = np.diag(cm)
+    support = cm.sum(1)
+    predicted = cm.sum(0)
+    fp, fn = predicted - tp, support - tp
+    tn = total - tp - fp - fn
+    precision, recall = _div(tp, predicted), _div(tp, support)
+    f1 = _div(2 * tp, 2 * tp + fp + fn)                           # = 2 p r / (p + r)
+    return dict(accuracy=float(_div(tp.sum(), total)), precision=precision, recall=recall, f1=f1, support=support,
+                weighted_f1=float(_div((f1 * support).sum(), support.sum())),
+                multilabel=np.stack([np.stack([tn, fp], 1), np.stack([fn, tp], 1)], 1))

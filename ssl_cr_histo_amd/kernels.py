@@ -522,6 +522,71 @@ def softmax_col(logits, col=-1):
     return out
 
 
+def predict(logits, target=None, *, scores=False, pred=True, confusion=None, col=-1, map=None, map_index=None):
+    """What a test() loop takes from a batch of fp32 logits [n, C] (1 <= C <= 64), in one launch (sslcr_predict) -> dict with
+    ``scores`` [n, C] fp32 = softmax over the row (scores=True) and ``pred`` [n] int64 = torch.argmax's index (pred=True: the lowest
+    index of the row maximum, a NaN is the maximum).  confusion: int64 [C, C] device tensor, ``confusion[target, pred] += 1`` in
+    place, across calls (rows with target outside [0, C) are skipped; needs target, int64 [n]).  map: a contiguous fp32 device tensor,
+    ``map.view(-1)[map_index[i]] = softmax(logits[i])[col]`` (map_index int64 [n], no duplicates; col may be negative), the value
+    bit for bit ``softmax_col``'s.  n = 0 is a no-op.  No sync."""
+    _chk(logits, target, confusion, map, map_index)
+    if logits.dtype != torch.float32 or logits.dim() != 2:
+        raise L.SslcrError("predict: fp32 logits [n, C] expected")
+    n, c = logits.shape
+    if not 1 <= c <= 64:
+        raise L.SslcrError(f"predict: C = {c} outside [1, 64]")
+    dev = logits.device
+    for name, t in (("target", target), ("map_index", map_index)):
+        if t is not None and (t.dtype != torch.int64 or t.shape != (n,) or t.device != dev):
+            raise L.SslcrError(f"predict: {name} must be an int64 tensor [{n}] on {dev}")
+    if confusion is not None:
+        if confusion.dtype != torch.int64 or confusion.shape != (c, c) or confusion.device != dev:
+            raise L.SslcrError(f"predict: confusion must be an int64 tensor [{c}, {c}] on {dev}")
+        if target is None:
+            raise L.SslcrError("predict: confusion needs target")
+    if map is not None:
+        if map.dtype != torch.float32 or map.device != dev:
+            raise L.SslcrError(f"predict: map must be an fp32 tensor on {dev}")
+        if map_index is None:
+            raise L.SslcrError("predict: map needs map_index")
+        if not -c <= col < c:
+            raise L.SslcrError(f"predict: col = {col} outside [-{c}, {c})")
+    out = {}
+    if scores:
+        out["scores"] = torch.empty((n, c), dtype=torch.float32, device=dev)
+    if pred:
+        out["pred"] = torch.empty(n, dtype=torch.int64, device=dev)
+    d = L.PredictDesc(L.ptr(logits) if n else None, n, c, L.ptr(target), L.ptr(out.get("scores")), L.ptr(out.get("pred")), L.ptr(confusion),
+                      col % c, L.ptr(map), L.ptr(map_index), map.numel() if map is not None else 0)
+    L.check(L.lib().sslcr_predict(d, L.stream_ptr()))
+    return out
+
+
+def wsi_gather(region, xy, size, *, origin=(0, 0), fill=0, out=None):
+    """uint8 tiles [N, 3, size, size] cut from ONE device-resident slide region, uint8 [RH, RW, 3] (sslcr_wsi_gather):
+    ``out[n, c, i, j] = region[top - origin[1] + i, left - origin[0] + j, c]`` with (left, top) = xy[n] (device int32 [N, 2], level-0
+    coordinates; origin = those of region[0, 0]), ``fill`` where the pixel lies outside the region.  No sync."""
+    _chk(region, xy, out)
+    if region.dtype != torch.uint8 or region.dim() != 3 or region.shape[2] != 3:
+        raise L.SslcrError("wsi_gather: a uint8 region [RH, RW, 3] expected")
+    if xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or xy.device != region.device:
+        raise L.SslcrError("wsi_gather: xy must be an int32 tensor [N, 2] on the region's device")
+    n, size = xy.shape[0], int(size)
+    if size < 1 or not 0 <= int(fill) <= 255:
+        raise L.SslcrError(f"wsi_gather: size = {size}, fill = {fill}")
+    RH, RW = region.shape[0], region.shape[1]
+    if RH < 1 or RW < 1 or RH >= 1 << 31 or RW >= 1 << 31:
+        raise L.SslcrError(f"wsi_gather: region of {RH} x {RW} pixels")
+    if out is None:
+        out = torch.empty((n, 3, size, size), dtype=torch.uint8, device=region.device)
+    elif out.dtype != torch.uint8 or out.shape != (n, 3, size, size) or out.device != region.device:
+        raise L.SslcrError(f"wsi_gather: out must be a uint8 tensor [{n}, 3, {size}, {size}] on the region's device")
+    d = L.WsiGatherDesc(L.ptr(region), L.ptr(xy) if n else None, L.ptr(out) if n else None, int(origin[0]), int(origin[1]), n, RH, RW, size,
+                        int(fill))
+    L.check(L.lib().sslcr_wsi_gather(d, L.stream_ptr()))
+    return out
+
+
 def grad_norm(flat, max_norm=float("inf")):
     """-> device tensor [norm, coef] for a 1-D fp32 tensor (any length, any 4-byte-aligned view): its 2-norm, summed in double in a
     fixed order, and min(1, max_norm / (norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_'s two numbers (sslcr_grad_norm).  No sync."""

@@ -1,4 +1,4 @@
-"""Modules named after the reference scripts, each exporting that script's ``train`` / ``validate`` (same signatures,
+"""Modules named after the reference scripts, each exporting that script's ``train`` / ``validate`` / ``test`` (same signatures,
 same return tuples) backed by the engine -- ``import ssl_cr_histo_amd.scripts.eval_BreastPathQ_SSL_CR as m; m.train(...)``
 is the one-line swap for the reference's module-level functions.
 
@@ -13,12 +13,12 @@ import sys
 
 # reference script -> {exported name: function in ssl_cr_histo_amd.steps}; file:line of the function each one replaces is in steps.py
 SCRIPTS = {
-    "eval_BreastPathQ_SSL_CR": {"train": "bpq_cr_train", "validate": "bpq_cr_validate", "teacher_refresh": "teacher_refresh"},
+    "eval_BreastPathQ_SSL_CR": {"train": "bpq_cr_train", "validate": "bpq_cr_validate", "test": "bpq_test", "teacher_refresh": "teacher_refresh"},
     "eval_Camelyon_SSL_CR": {"train": "cam_cr_train", "validate": "cam_cr_validate", "teacher_refresh": "teacher_refresh"},
-    "eval_Kather_SSL_CR": {"train": "kather_cr_train", "validate": "kather_cr_validate", "teacher_refresh": "teacher_refresh"},
-    "eval_BreastPathQ_SSL": {"train": "bpq_sup_train", "validate": "bpq_cr_validate", "teacher_refresh": "teacher_refresh"},
+    "eval_Kather_SSL_CR": {"train": "kather_cr_train", "validate": "kather_cr_validate", "test": "kather_cr_test", "teacher_refresh": "teacher_refresh"},
+    "eval_BreastPathQ_SSL": {"train": "bpq_sup_train", "validate": "bpq_cr_validate", "test": "bpq_sup_test", "teacher_refresh": "teacher_refresh"},
     "eval_Camelyon_SSL": {"train": "cam_sup_train", "validate": "cam_cr_validate", "teacher_refresh": "teacher_refresh"},
-    "eval_Kather_SSL": {"train": "kather_sup_train", "validate": "kather_sup_validate", "teacher_refresh": "teacher_refresh"},
+    "eval_Kather_SSL": {"train": "kather_sup_train", "validate": "kather_sup_validate", "test": "kather_sup_test", "teacher_refresh": "teacher_refresh"},
     "pretrain_BreastPathQ": {"train": "rsp_train", "validate": "rsp_validate", "teacher_refresh": "teacher_refresh"},
     "pretrain_Camelyon16": {"train": "rsp_train", "validate": "rsp_validate", "teacher_refresh": "teacher_refresh"},
     "pretrain_RSP": {"train": "rsp_train", "validate": "rsp_validate", "teacher_refresh": "teacher_refresh"},

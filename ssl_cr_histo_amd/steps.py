@@ -31,6 +31,15 @@ pretrain_BreastPathQ|Camelyon16|RSP.train   rsp_train / rsp_validate            
 eval_Camelyon_SSL.train                     cam_sup_train                       (:31-119)
 eval_BreastPathQ_SSL.train                  bpq_sup_train                       (:35-103)
 eval_Kather_SSL.train/validate              kather_sup_train / kather_sup_validate (:32-99 / :102-151)
+eval_BreastPathQ_SSL_CR.test                bpq_test                            (:178-242)
+eval_BreastPathQ_SSL.test                   bpq_sup_test                        (:152-216)
+eval_Kather_SSL_CR.test                     kather_cr_test                      (:182-245)
+eval_Kather_SSL.test                        kather_sup_test                     (:154-213)
+test_Camelyon16.test                        camelyon16_test                     (:30-70)
+
+The ``*_test`` functions keep everything on the device until ONE copy at the end: predictions and softmax scores come from
+sslcr_predict, which also counts the confusion matrix of the classification variants (``last_test_confusion()``, the input of
+``inference.metrics_from_confusion``); loss and accuracy go through the validate() step and the meters, read at print boundaries only.
 """
 import time
 
@@ -602,16 +611,120 @@ def kather_sup_validate(args, model, classifier, val_loader, criterion, epoch):
     return kather_cr_validate(args, model, classifier, val_loader, epoch)
 
 
-# ------------------------------------------------------------------------------------------------ WSI inference (f3)
-def camelyon16_test(args, model, classifier, test_loader):
-    """test_Camelyon16.test (test_Camelyon16.py:30-70) -> probs_map: every tissue pixel of ``test_loader.dataset.mask``
-    gets the softmax 'tumor' probability of its tile; forward-only (BatchNorm folded, all epilogues fused)."""
-    import numpy as np
+# ------------------------------------------------------------------------------------------------ test() of the four eval scripts
+_last_test = {"confusion": None}
+
+
+def last_test_confusion():
+    """the int64 [C, C] confusion matrix (rows = targets, columns = predictions; a CPU tensor) of the most recent ``kather_cr_test`` /
+    ``kather_sup_test`` call, counted on the device by sslcr_predict -- sklearn's ``confusion_matrix(final_targets,
+    final_predictions, labels=range(C))`` of the returned tensors; None after a regression ``bpq_*_test``."""
+    return _last_test["confusion"]
+
+
+def _bpq_test(args, model, classifier, test_loader, where):
+    _loss_options(args, mse=where)
+    eng = get_engine(_device_of(model))
+    model.eval()
+    classifier.eval()
+    net = eng.bind(model, classifier)
+    meters = _meters(eng, ["loss"])
+    outputs, feats, targets_a, targets_b = [], [], [], []
+    t0 = time.time()
+    for batch_idx, (input, targetA, targetB) in enumerate(_ahead(test_loader, eng, _prefetch_on(args))):
+        targetA, targetB = targetA.float().to(eng.device), targetB.float().to(eng.device)
+        r = eng.step_supervised(net, "mse", [input], targetA.reshape(-1), train=False)          # F.mse_loss(output, targetA.view(-1, 1))
+        meters.add(r["losses"], targetA.size(0))
+        outputs.append(r["logits"].reshape(-1))
+        feats.append(r["feats"])
+        targets_a.append(targetA)
+        targets_b.append(targetB)
+        _maybe_print(args, batch_idx, "Test", 0, _len(test_loader), t0, meters)
+    _last_test["confusion"] = None
+    return tuple(torch.cat(v).detach().to("cpu") for v in (outputs, feats, targets_a, targets_b))
+
+
+def bpq_test(args, model_student, classifier_student, test_loader):
+    """eval_BreastPathQ_SSL_CR.test (:178-242) -> (outputs [n], feats [n, 768], targetsA, targetsB) on the CPU."""
+    return _bpq_test(args, model_student, classifier_student, test_loader, "bpq_test")
+
+
+def bpq_sup_test(args, model, classifier, criterion, test_loader):
+    """eval_BreastPathQ_SSL.test (:152-216; ``criterion`` before the loader, as there) -> (outputs, feats, targetsA, targetsB)."""
+    if criterion is not None and not isinstance(criterion, torch.nn.MSELoss):
+        raise NotImplementedError("the reference tests BreastPathQ with nn.MSELoss")
+    return _bpq_test(args, model, classifier, test_loader, "bpq_sup_test")
+
+
+def _cls_test(args, model, classifier, test_loader, want_scores):
     from . import kernels as K
     eng = get_engine(_device_of(model))
     model.eval()
     classifier.eval()
     net = eng.bind(model, classifier)
+    meters = _meters(eng, ["loss", "acc"])
+    opts = _loss_options(args)
+    confusion = torch.zeros((net.ncls, net.ncls), dtype=torch.int64, device=eng.device)
+    preds, targets, scores = [], [], []
+    t0 = time.time()
+    for batch_idx, (input, target) in enumerate(_ahead(test_loader, eng, _prefetch_on(args))):
+        target = target.long().reshape(-1).to(eng.device).contiguous()
+        r = _val_step(eng, net, [input], target, opts)
+        meters.add(r["losses"], target.size(0))
+        p = K.predict(r["logits"], target, scores=want_scores, pred=True, confusion=confusion)
+        preds.append(p["pred"])
+        targets.append(target)
+        if want_scores:
+            scores.append(p["scores"])
+        _maybe_print(args, batch_idx, "Test", 0, _len(test_loader), t0, meters)
+    out = [torch.cat(preds).to("cpu"), torch.cat(targets).to("cpu")]
+    if want_scores:
+        out.append(torch.cat(scores).to("cpu"))
+    _last_test["confusion"] = confusion.to("cpu")
+    return tuple(out)
+
+
+def kather_cr_test(args, model, classifier, test_loader):
+    """eval_Kather_SSL_CR.test (:182-245) -> (predictions int64 [n], targets int64 [n], pred_score [n, 9]) on the CPU."""
+    return _cls_test(args, model, classifier, test_loader, True)
+
+
+def kather_sup_test(args, model, classifier, test_loader, criterion):
+    """eval_Kather_SSL.test (:154-213; ``criterion`` last, as there) -> (predictions, targets)."""
+    _plain_ce(criterion, "Kather test (eval_Kather_SSL.py:154-213)")
+    return _cls_test(args, model, classifier, test_loader, False)
+
+
+# ------------------------------------------------------------------------------------------------ WSI inference (f3)
+def _camelyon16_test_device(args, net, loader):
+    """the device-resident loader: per batch a tile gather, the eval forward and the softmax column scattered into the map, all on
+    the current stream; no host sync and no device-to-host copy before the one copy of the finished map."""
+    import numpy as np
+    from . import kernels as K
+    mask = loader.dataset.mask
+    probs = torch.zeros(mask.shape, dtype=torch.float32, device=loader.region.device)
+    t0 = time.time()
+    for batch_idx, (lo, hi) in enumerate(loader.ranges()):
+        _, output = net.forward((loader.tiles(lo, hi),), train=False)
+        K.predict(output, pred=False, col=-1, map=probs, map_index=loader.map_index[lo:hi])       # second column 'tumor' (:58-62)
+        if (batch_idx + 1) % 10 == 0 and getattr(args, "print_freq", 0):
+            print("Test: [{0}/{1}]\tBT {2:.3f} (enqueue)".format(batch_idx, len(loader), (time.time() - t0) / (batch_idx + 1)))
+    return probs.cpu().numpy().astype(np.float64)
+
+
+def camelyon16_test(args, model, classifier, test_loader):
+    """test_Camelyon16.test (test_Camelyon16.py:30-70) -> probs_map: every tissue pixel of ``test_loader.dataset.mask``
+    gets the softmax 'tumor' probability of its tile; forward-only (BatchNorm folded, all epilogues fused).  An
+    ``inference.WsiDeviceLoader`` is served from the slide bytes it holds in HBM (same map, no per-batch host traffic)."""
+    import numpy as np
+    from . import kernels as K
+    from .inference import WsiDeviceLoader
+    eng = get_engine(_device_of(model))
+    model.eval()
+    classifier.eval()
+    net = eng.bind(model, classifier)
+    if isinstance(test_loader, WsiDeviceLoader):
+        return _camelyon16_test_device(args, net, test_loader)
     probs_map = np.zeros(test_loader.dataset.mask.shape)
     t0 = time.time()
     for batch_idx, (input, x_mask, y_mask) in enumerate(_ahead(test_loader, eng, _prefetch_on(args))):

@@ -1,0 +1,180 @@
+"""CPU-only: the host side of device-resident inference -- the two C-ABI entries (header, ctypes, exports, argument checks), the tile
+coordinates of DatasetCamelyon16_test, the metrics derived from a confusion matrix, and the test() rows of the script table."""
+import ctypes as C
+import inspect
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("sslcr_wsi_gather", "sslcr_predict")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from ssl_cr_histo_amd import _lib, build
+    if not os.path.exists(_lib.LIB_PATH):
+        build.build()
+    return _lib.lib()
+
+
+def test_header_ctypes_and_exports_agree_on_the_new_entries(lib):
+    from ssl_cr_histo_amd import _lib, build
+    names = build.header_symbols()
+    for n in NEW:
+        assert n in names, f"{n} not declared in include/sslcr.h"
+        assert n in _lib.SIGNATURES, f"no ctypes signature for {n}"
+        assert hasattr(lib, n), f"{n} not exported by libsslcr.so"
+    assert lib.sslcr_version() >= 12
+
+
+def test_new_descriptor_mirrors_match_the_header_layout(tmp_path):
+    from ssl_cr_histo_amd import _lib as L
+    if not shutil.which("gcc"):
+        pytest.skip("no host C compiler")
+    pairs = {"sslcr_wsi_gather_desc": L.WsiGatherDesc, "sslcr_predict_desc": L.PredictDesc}
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "sslcr.h"', 'int main(void) {']
+    for cname, cls in pairs.items():
+        lines.append(f'  printf("{cname} . %zu\\n", sizeof({cname}));')
+        for fname, _ in cls._fields_:
+            lines.append(f'  printf("{cname} {fname} %zu\\n", offsetof({cname}, {fname}));')
+    lines += ['  return 0;', '}']
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines))
+    exe = tmp_path / "layout"
+    r = subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    want = {}
+    for ln in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines():
+        cname, fname, v = ln.split()
+        want[(cname, fname)] = int(v)
+    for cname, cls in pairs.items():
+        assert C.sizeof(cls) == want[(cname, ".")], cname
+        for fname, _ in cls._fields_:
+            assert getattr(cls, fname).offset == want[(cname, fname)], f"{cname}.{fname}"
+
+
+def test_argument_errors_are_decided_before_any_launch(lib):
+    """no device here: every call below must return before it touches one"""
+    from ssl_cr_histo_amd import _lib as L
+    one = C.c_void_p(16)                                    # a non-null pointer that is never followed
+    g = L.WsiGatherDesc(one, one, one, 0, 0, 1, 8, 8, 4, 0)
+    assert lib.sslcr_wsi_gather(None, None) == -1
+    for field, bad, word in (("S", 0, b"S >= 1"), ("N", -1, b"N >= 0"), ("src", None, b"null"), ("xy", None, b"null"), ("dst", None, b"null"),
+                             ("fill", 256, b"fill"), ("RH", 0, b"region")):
+        d = L.WsiGatherDesc.from_buffer_copy(g)
+        setattr(d, field, bad)
+        assert lib.sslcr_wsi_gather(d, None) == -1, field
+        assert word in lib.sslcr_last_error(), (field, lib.sslcr_last_error())
+    d = L.WsiGatherDesc.from_buffer_copy(g)
+    d.N, d.xy, d.dst = 0, None, None
+    assert lib.sslcr_wsi_gather(d, None) == 0                # N == 0: a no-op
+
+    p = L.PredictDesc(one, 4, 9, None, None, None, None, 0, None, None, 0)
+    assert lib.sslcr_predict(None, None) == -1
+    for fields, word in (({"C": 0}, b"C <= 64"), ({"C": 65}, b"C <= 64"), ({"n": -1}, b"n >= 0"), ({"logits": None}, b"null logits"),
+                         ({"confusion": one}, b"confusion needs target"), ({"map": one}, b"map_index"),
+                         ({"map": one, "map_index": one, "col": 9}, b"col"), ({"map": one, "map_index": one, "col": -1}, b"col")):
+        d = L.PredictDesc.from_buffer_copy(p)
+        for k, v in fields.items():
+            setattr(d, k, v)
+        assert lib.sslcr_predict(d, None) == -1, fields
+        assert word in lib.sslcr_last_error(), (fields, lib.sslcr_last_error())
+    d = L.PredictDesc.from_buffer_copy(p)
+    d.n, d.logits = 0, None
+    assert lib.sslcr_predict(d, None) == 0                   # n == 0: a no-op
+
+
+def _corner_masks():
+    rs = np.random.RandomState(11)
+    masks = []
+    for shape in ((7, 5), (4, 9)):
+        m = rs.rand(*shape) < 0.4
+        m[0, 0] = m[0, -1] = m[-1, 0] = m[-1, -1] = True      # tissue at all four corners
+        masks.append(m)
+    return masks
+
+
+@pytest.mark.parametrize("image_size", [224, 256, 255])
+@pytest.mark.parametrize("resolution", [1, 32, 64])
+def test_tile_origins_are_the_reference_expressions(image_size, resolution):
+    from ssl_cr_histo_amd.inference import tile_origins
+    for mask in _corner_masks():
+        x_idcs, y_idcs, xy = tile_origins(mask, resolution, image_size)
+        # dataset.py:978-991, restated literally
+        X_idcs, Y_idcs = np.where(mask)
+        assert np.array_equal(x_idcs, X_idcs) and np.array_equal(y_idcs, Y_idcs)
+        assert xy.dtype == np.int32 and xy.shape == (len(X_idcs), 2)
+        for idx in range(len(X_idcs)):
+            x_mask, y_mask = X_idcs[idx], Y_idcs[idx]
+            x_center = int((x_mask) * resolution)
+            y_center = int((y_mask) * resolution)
+            x = int(x_center - image_size / 2)
+            y = int(y_center - image_size / 2)
+            assert (int(xy[idx, 0]), int(xy[idx, 1])) == (x, y), (idx, xy[idx], x, y)
+    assert int(0 * 64 - 224 / 2) == -112 and int(tile_origins(np.ones((1, 1), bool), 64, 224)[2][0, 0]) == -112
+    assert int(tile_origins(np.ones((1, 1), bool), 64, 255)[2][0, 0]) == -127          # toward zero, not floor (-128)
+
+
+def test_resolution_checks_raise_as_the_reference_does():
+    from ssl_cr_histo_amd.inference import WsiDeviceLoader, default_resolution
+    assert default_resolution((1280, 1024), (20, 16)) == 64
+    assert default_resolution((1290, 1030), (20, 16)) == 64              # round(64.5) == round(64.4) == 64
+    with pytest.raises(Exception, match="Slide/Mask dimension does not match"):
+        default_resolution((1280, 1024), (20, 8))
+    with pytest.raises(Exception, match="is not power of 2"):
+        default_resolution((1200, 960), (20, 16))                        # 60
+    # the loader applies them before anything is uploaded
+    region = np.zeros((96, 120, 3), np.uint8)                            # [RH, RW, 3]: X_slide = 120, Y_slide = 96
+    with pytest.raises(Exception, match="Slide/Mask dimension does not match"):
+        WsiDeviceLoader(region, np.ones((20, 8), bool), 8, 4)
+    with pytest.raises(Exception, match="is not power of 2"):
+        WsiDeviceLoader(region, np.ones((20, 16), bool), 8, 4)           # 6
+
+
+def test_metrics_from_confusion_against_sklearn():
+    from sklearn.metrics import confusion_matrix, f1_score, multilabel_confusion_matrix, precision_recall_fscore_support
+    from ssl_cr_histo_amd.inference import metrics_from_confusion
+    rs = np.random.RandomState(5)
+    n, Cn = 500, 9
+    y = rs.randint(0, Cn, n)
+    p = np.where(rs.rand(n) < 0.6, y, rs.randint(0, Cn, n))
+    p[p == 3] = 4                      # class 3 is never predicted
+    keep = y != 7                      # class 7 is absent from the targets (it is still predicted)
+    y, p = y[keep], p[keep]
+    assert 3 not in p and 3 in y and 7 not in y and 7 in p
+    labels = list(range(Cn))
+    cm = confusion_matrix(y, p, labels=labels)
+    m = metrics_from_confusion(cm)
+    assert np.array_equal(m["multilabel"], multilabel_confusion_matrix(y, p, labels=labels)) and m["multilabel"].dtype == np.int64
+    pr, rc, f1, sup = precision_recall_fscore_support(y, p, labels=labels, zero_division=0)
+    assert np.array_equal(m["support"], sup)
+    for got, want in ((m["precision"], pr), (m["recall"], rc), (m["f1"], f1)):
+        assert got.dtype == np.float64 and np.abs(got - want).max() <= 1e-12
+    assert m["precision"][3] == 0.0 and m["recall"][7] == 0.0 and m["f1"][3] == 0.0 and m["f1"][7] == 0.0     # x / 0 -> 0
+    assert abs(m["weighted_f1"] - f1_score(y, p, labels=labels, average="weighted", zero_division=0)) <= 1e-12
+    assert abs(m["accuracy"] - float((y == p).mean())) <= 1e-12
+    import torch
+    m2 = metrics_from_confusion(torch.from_numpy(cm))
+    assert m2["weighted_f1"] == m["weighted_f1"]
+    z = metrics_from_confusion(np.zeros((3, 3), np.int64))                # nothing counted: every division is by zero
+    assert z["accuracy"] == 0.0 and z["weighted_f1"] == 0.0 and not z["f1"].any()
+
+
+def test_script_modules_expose_test_with_the_reference_parameter_names():
+    import importlib
+    from ssl_cr_histo_amd import scripts
+    want = {"eval_BreastPathQ_SSL_CR": ["args", "model_student", "classifier_student", "test_loader"],        # :178
+            "eval_BreastPathQ_SSL": ["args", "model", "classifier", "criterion", "test_loader"],                # :152
+            "eval_Kather_SSL_CR": ["args", "model", "classifier", "test_loader"],                               # :182
+            "eval_Kather_SSL": ["args", "model", "classifier", "test_loader", "criterion"],                     # :154
+            "test_Camelyon16": ["args", "model", "classifier", "test_loader"]}                                  # test_Camelyon16.py:30
+    for name, params in want.items():
+        assert "test" in scripts.SCRIPTS[name]
+        mod = importlib.import_module(f"ssl_cr_histo_amd.scripts.{name}")
+        assert list(inspect.signature(mod.test).parameters) == params, name
+    from ssl_cr_histo_amd import steps
+    assert callable(steps.last_test_confusion)
