@@ -293,11 +293,10 @@ hipError_t launch_bn_act(int dtype, const BnActArgs& a, hipStream_t st) {
   const int nseg = a.nseg > 1 ? a.nseg : 1;
   if (a.pixels % nseg != 0) return hipErrorInvalidValue;
   const size_t per = a.pixels / nseg;
-  if (dtype == DT_BF16) {
-    hipLaunchKernelGGL(bn_act_kernel<bf16_t>, dim3(ew_grid_cols(per * (a.C / 8), a.C / 8), nseg), dim3(256), 0, st, a);
-  } else {
-    hipLaunchKernelGGL(bn_act_kernel<float>, dim3(ew_grid_cols(per * (a.C / 4), a.C / 4), nseg), dim3(256), 0, st, a);
-  }
+  by_dtype(dtype, [&](auto t) {
+    const int cols = a.C / Elem<decltype(t)>::EPC;
+    hipLaunchKernelGGL(bn_act_kernel<decltype(t)>, dim3(ew_grid_cols(per * cols, cols), nseg), dim3(256), 0, st, a);
+  });
   return hipGetLastError();
 }
 
@@ -487,22 +486,16 @@ hipError_t launch_bn_relu_maxpool(int dtype, const PoolFwdArgs& a, hipStream_t s
   if (!a.scale || !a.shift) {          // plain max-pool (capi.cpp admits it only without argmax and for the row form's widths)
     const int rows = a.N * a.OH;
     const int grid = rows < 256 * 16 ? rows : 256 * 16;
-    if (dtype == DT_BF16) hipLaunchKernelGGL(maxpool_rows_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, a, bands);
-    else hipLaunchKernelGGL(maxpool_rows_kernel<float>, dim3(grid), dim3(256), 0, st, a, bands);
+    by_dtype(dtype, [&](auto t) { hipLaunchKernelGGL(maxpool_rows_kernel<decltype(t)>, dim3(grid), dim3(256), 0, st, a, bands); });
     return hipGetLastError();
   }
   if (cols >= 1 && cols <= 256 && 256 % cols == 0) {
     const int rows = a.N * a.OH;
     const int grid = rows < 256 * 16 ? rows : 256 * 16;
-    if (dtype == DT_BF16) hipLaunchKernelGGL(bn_relu_maxpool_rows_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, a, bands);
-    else hipLaunchKernelGGL(bn_relu_maxpool_rows_kernel<float>, dim3(grid), dim3(256), 0, st, a, bands);
+    by_dtype(dtype, [&](auto t) { hipLaunchKernelGGL(bn_relu_maxpool_rows_kernel<decltype(t)>, dim3(grid), dim3(256), 0, st, a, bands); });
     return hipGetLastError();
   }
-  if (dtype == DT_BF16) {
-    hipLaunchKernelGGL(bn_relu_maxpool_kernel<bf16_t>, dim3(ew_grid_cols(px * (a.C / 8), a.C / 8)), dim3(256), 0, st, a);
-  } else {
-    hipLaunchKernelGGL(bn_relu_maxpool_kernel<float>, dim3(ew_grid_cols(px * (a.C / 4), a.C / 4)), dim3(256), 0, st, a);
-  }
+  by_dtype(dtype, [&](auto t) { hipLaunchKernelGGL(bn_relu_maxpool_kernel<decltype(t)>, dim3(ew_grid_cols(px * cols, cols)), dim3(256), 0, st, a); });
   return hipGetLastError();
 }
 
@@ -560,11 +553,9 @@ __global__ __launch_bounds__(256) void maxpool_relu_bwd_kernel(const PoolBwdArgs
 
 hipError_t launch_maxpool_relu_bwd(int dtype, const PoolBwdArgs& a, hipStream_t st) {
   size_t px = (size_t)a.N * a.H * a.W;
-  if (dtype == DT_BF16) {
-    hipLaunchKernelGGL(maxpool_relu_bwd_kernel<bf16_t>, dim3(ew_grid(px * (a.C / 8))), dim3(256), 0, st, a);
-  } else {
-    hipLaunchKernelGGL(maxpool_relu_bwd_kernel<float>, dim3(ew_grid(px * (a.C / 4))), dim3(256), 0, st, a);
-  }
+  by_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(maxpool_relu_bwd_kernel<decltype(t)>, dim3(ew_grid(px * (a.C / Elem<decltype(t)>::EPC))), dim3(256), 0, st, a);
+  });
   return hipGetLastError();
 }
 
@@ -627,19 +618,15 @@ __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const float* dy, void*
 }
 
 hipError_t launch_avgpool_fwd(int dtype, const void* x, float* y, int N, int HW, int C, hipStream_t st) {
-  if (dtype == DT_BF16) {
-    hipLaunchKernelGGL(avgpool_fwd_kernel<bf16_t>, dim3(cdiv(N * (C / 8), 64)), dim3(256), 0, st, x, y, N, HW, C);
-  } else {
-    hipLaunchKernelGGL(avgpool_fwd_kernel<float>, dim3(cdiv(N * (C / 4), 64)), dim3(256), 0, st, x, y, N, HW, C);
-  }
+  by_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(avgpool_fwd_kernel<decltype(t)>, dim3(cdiv(N * (C / Elem<decltype(t)>::EPC), 64)), dim3(256), 0, st, x, y, N, HW, C);
+  });
   return hipGetLastError();
 }
 hipError_t launch_avgpool_bwd(int dtype, const float* dy, void* dx, int N, int HW, int C, hipStream_t st) {
-  if (dtype == DT_BF16) {
-    hipLaunchKernelGGL(avgpool_bwd_kernel<bf16_t>, dim3(ew_grid((size_t)N * HW * (C / 8))), dim3(256), 0, st, dy, dx, N, HW, C);
-  } else {
-    hipLaunchKernelGGL(avgpool_bwd_kernel<float>, dim3(ew_grid((size_t)N * HW * (C / 4))), dim3(256), 0, st, dy, dx, N, HW, C);
-  }
+  by_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(avgpool_bwd_kernel<decltype(t)>, dim3(ew_grid((size_t)N * HW * (C / Elem<decltype(t)>::EPC))), dim3(256), 0, st, dy, dx, N, HW, C);
+  });
   return hipGetLastError();
 }
 
@@ -818,8 +805,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdArgs a0) {
 // shortcut's BatchNorm, torchvision BasicBlock: out = bn2(conv2(..)) + downsample(x) -> both get g = dOut * (y > 0)) in one reduce and
 // one apply pass: g is formed once (a's dy / mask), written once (a.gout) and read once by the apply pass, where the two separate
 // BatchNorm-backward passes read it twice each.  b is the second BatchNorm's descriptor (x, mean, scale, invstd, sums, dx, dgamma ...;
-// its dy is a.gout by construction and is not read).  Same grid, same per-thread element order as the single kernels: both
-// BatchNorms' sums come out with the bits of the separate launches.
+// its dy is a.gout by construction and is not read).  Same grid (bn_bwd_reduce_grid, asked by both launchers), same per-thread
+// element order as the single kernels: both BatchNorms' sums come out with the bits of the separate launches
+// (tests: test_bn_backward_pair_equals_the_separate_passes).
 // keep_g = 0: g is not written at all -- the apply pass forms it again from (dy, mask bits): one tensor write and one read less for
 // 1/16 of a read (the engine's choice where nothing else reads g: a downsampling block has no identity path)
 template <typename T, int NB>
@@ -1082,57 +1070,54 @@ __global__ __launch_bounds__(1024) void bn_bwd_sums_kernel(const double* __restr
   sums[(size_t)blockIdx.y * sums_stride + v] = s;
 }
 
+// The reduce pass's grid over `pixels` pixels of `cols` 16-byte columns: nrows workgroups (= rows of partial sums) of NB threads.
+// At least 8 passes per workgroup; big tensors take a quarter of the workgroups with four times the threads each (the pooled stem
+// form has no such instance).  The single and the pair launcher both ask here: that is what "the same sums" above rests on.
+struct BnRedGrid { int nrows, NB; };
+static BnRedGrid bn_bwd_reduce_grid(size_t pixels, int cols, bool pooled) {
+  auto rows_of = [&](int nb, size_t most) {
+    const size_t rpp = nb / cols, blocks = ((pixels + rpp - 1) / rpp + 7) / 8;
+    return (int)(blocks > most ? most : blocks < 1 ? 1 : blocks);
+  };
+  const int blocks = rows_of(256, 1024);
+  if (blocks < 512 || pooled) return {blocks, 256};
+  return {rows_of(1024, 256), 1024};
+}
+// sums[y] = the rows of grid-y slice y (a segment, or a BatchNorm of the pair) in bn_bwd_sums_kernel's fixed order
+static hipError_t bn_bwd_fold(const double* rows, int nrows, int C, int ny, double* sums, int sums_stride, hipStream_t st) {
+  hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(cdiv(2 * C, 64), ny), dim3(64, 16), 0, st, rows, nrows, 2 * C, sums, sums_stride);
+  return hipGetLastError();
+}
+
 // the reduce pass: per-workgroup rows, then their ordered sum OVERWRITES a.sums (no atomics: the same bits run after run)
+template <int NB>
+static hipError_t bn_bwd_reduce_nb(int dtype, const BnBwdArgs& a, int nrows, int nseg, double* rows, hipStream_t st) {
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    const size_t lds = (size_t)NB * (2 * Elem<T>::EPC + 1) * sizeof(float);
+    return launch_lds<bn_bwd_reduce_kernel<T, NB>>(dim3(nrows, nseg), dim3(NB), lds, 96 * 1024, st, a, rows);
+  });
+}
 hipError_t launch_bn_bwd_reduce(int dtype, const BnBwdArgs& a, hipStream_t st) {
-  const int epc = dtype == DT_BF16 ? 8 : 4;
-  const int cols = a.C / epc;
+  const int cols = a.C / (dtype == DT_BF16 ? 8 : 4);
   if (cols > 256 || (256 % cols) != 0) return hipErrorInvalidValue;
   const int nseg = a.nseg > 1 ? a.nseg : 1;      // grid y; the kernels take their segment's share (bn_bwd_segment)
   if (nseg > 1 && (a.pool_dy || a.pixels % nseg != 0)) return hipErrorInvalidValue;
-  const size_t pixels = a.pixels / nseg;
-  const int rpp = 256 / cols;
-  size_t blocks = (pixels + rpp - 1) / rpp;
-  blocks = (blocks + 7) / 8;                              // >= 8 passes per block
-  if (blocks > 1024) blocks = 1024;
-  if (blocks < 1) blocks = 1;
-  const bool big = blocks >= 512 && !(a.pool_dy && a.pool_y);      // big tensors: a quarter of the workgroups, four times the threads each
-  size_t b4 = 0;
-  if (big) {
-    b4 = ((pixels + 1024 / cols - 1) / (1024 / cols) + 7) / 8;
-    if (b4 > 256) b4 = 256;
-  }
-  const int nrows = (int)(big ? b4 : blocks);
-  double* rows = reinterpret_cast<double*>(stream_scratch(st, (size_t)nseg * nrows * 2 * a.C * sizeof(double)));
+  const bool pooled = a.pool_dy && a.pool_y;
+  const BnRedGrid g = bn_bwd_reduce_grid(a.pixels / nseg, cols, pooled);
+  double* rows = reinterpret_cast<double*>(stream_scratch(st, (size_t)nseg * g.nrows * 2 * a.C * sizeof(double)));
   if (!rows) return hipErrorOutOfMemory;
-  auto fold = [&]() {
-    hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(cdiv(2 * a.C, 64), nseg), dim3(64, 16), 0, st, rows, nrows, 2 * a.C, a.sums, nseg > 1 ? a.sums_stride : 0);
-    return hipGetLastError();
-  };
-  if (a.pool_dy && a.pool_y) {
-    if (dtype == DT_BF16) hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel<bf16_t>, dim3((int)blocks), dim3(256), 0, st, a, rows);
-    else hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel<float>, dim3((int)blocks), dim3(256), 0, st, a, rows);
-    return fold();
-  }
-  if (big) {
-    constexpr int NB = 1024;
-    const size_t lds = (size_t)NB * (2 * epc + 1) * sizeof(float);
-    static std::atomic<bool> attr_done{false};
-    if (!attr_done) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bn_bwd_reduce_kernel<bf16_t, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bn_bwd_reduce_kernel<float, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-      attr_done = true;
-    }
-    if (dtype == DT_BF16) hipLaunchKernelGGL((bn_bwd_reduce_kernel<bf16_t, 1024>), dim3((int)b4, nseg), dim3(NB), lds, st, a, rows);
-    else hipLaunchKernelGGL((bn_bwd_reduce_kernel<float, 1024>), dim3((int)b4, nseg), dim3(NB), lds, st, a, rows);
-    return fold();
-  }
-  const size_t lds = (size_t)256 * (2 * epc + 1) * sizeof(float);
-  if (dtype == DT_BF16) {
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<bf16_t, 256>), dim3((int)blocks, nseg), dim3(256), lds, st, a, rows);
+  hipError_t e;
+  if (pooled) {
+    e = by_dtype(dtype, [&](auto t) {
+      hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel<decltype(t)>, dim3(g.nrows), dim3(256), 0, st, a, rows);
+      return hipGetLastError();
+    });
   } else {
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<float, 256>), dim3((int)blocks, nseg), dim3(256), lds, st, a, rows);
+    e = g.NB == 1024 ? bn_bwd_reduce_nb<1024>(dtype, a, g.nrows, nseg, rows, st) : bn_bwd_reduce_nb<256>(dtype, a, g.nrows, nseg, rows, st);
   }
-  return fold();
+  if (e != hipSuccess) return e;
+  return bn_bwd_fold(rows, g.nrows, a.C, nseg, a.sums, nseg > 1 ? a.sums_stride : 0, st);
 }
 
 // the two-BatchNorm forms (bn_bwd_reduce_pair_kernel): a = the residual branch's bn2 (g_in_reduce: its reduce pass writes g to gout),
@@ -1142,49 +1127,35 @@ bool bn_bwd_pair_ok(const BnBwdArgs& a, const BnBwdArgs& b) {
   return on && a.g_in_reduce && a.gout && b.dy == a.gout && !b.yact && !b.yact_bits && !b.relu_from_x && !b.gout && !a.pool_dy && !b.pool_dy &&
          a.nseg <= 1 && b.nseg <= 1 && a.C == b.C && a.pixels == b.pixels && b.sums == a.sums + 2 * a.C && a.dx && b.dx && b.x && a.x;
 }
+template <int NB>
+static hipError_t bn_bwd_reduce_pair_nb(int dtype, const BnBwdArgs& a, const BnBwdArgs& b, int nrows, double* rows, int keep_g, hipStream_t st) {
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    const size_t lds = (size_t)NB * (3 * Elem<T>::EPC + 1) * sizeof(float);
+    return launch_lds<bn_bwd_reduce_pair_kernel<T, NB>>(dim3(nrows), dim3(NB), lds, 128 * 1024, st, a, b, rows, keep_g);
+  });
+}
 hipError_t launch_bn_bwd_reduce_pair(int dtype, const BnBwdArgs& a, const BnBwdArgs& b, int keep_g, hipStream_t st) {
-  const int epc = dtype == DT_BF16 ? 8 : 4;
-  const int cols = a.C / epc;
+  const int cols = a.C / (dtype == DT_BF16 ? 8 : 4);
   if (cols > 256 || (256 % cols) != 0 || !bn_bwd_pair_ok(a, b)) return hipErrorInvalidValue;
   // the grid of launch_bn_bwd_reduce for this tensor (same rows, same per-thread order: the same sums)
-  const int rpp = 256 / cols;
-  size_t blocks = (a.pixels + rpp - 1) / rpp;
-  blocks = (blocks + 7) / 8;
-  if (blocks > 1024) blocks = 1024;
-  if (blocks < 1) blocks = 1;
-  const bool big = blocks >= 512;
-  size_t b4 = 0;
-  if (big) {
-    b4 = ((a.pixels + 1024 / cols - 1) / (1024 / cols) + 7) / 8;
-    if (b4 > 256) b4 = 256;
-  }
-  const int nrows = (int)(big ? b4 : blocks);
-  double* rows = reinterpret_cast<double*>(stream_scratch(st, (size_t)2 * nrows * 2 * a.C * sizeof(double)));
+  const BnRedGrid g = bn_bwd_reduce_grid(a.pixels, cols, false);
+  double* rows = reinterpret_cast<double*>(stream_scratch(st, (size_t)2 * g.nrows * 2 * a.C * sizeof(double)));
   if (!rows) return hipErrorOutOfMemory;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bn_bwd_reduce_pair_kernel<bf16_t, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bn_bwd_reduce_pair_kernel<float, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    attr_done = true;
-  }
-  const int NB = big ? 1024 : 256;
-  const size_t lds = (size_t)NB * (3 * epc + 1) * sizeof(float);
-  if (big) {
-    if (dtype == DT_BF16) hipLaunchKernelGGL((bn_bwd_reduce_pair_kernel<bf16_t, 1024>), dim3(nrows), dim3(1024), lds, st, a, b, rows, keep_g);
-    else hipLaunchKernelGGL((bn_bwd_reduce_pair_kernel<float, 1024>), dim3(nrows), dim3(1024), lds, st, a, b, rows, keep_g);
-  } else {
-    if (dtype == DT_BF16) hipLaunchKernelGGL((bn_bwd_reduce_pair_kernel<bf16_t, 256>), dim3(nrows), dim3(256), lds, st, a, b, rows, keep_g);
-    else hipLaunchKernelGGL((bn_bwd_reduce_pair_kernel<float, 256>), dim3(nrows), dim3(256), lds, st, a, b, rows, keep_g);
-  }
+  const hipError_t e = g.NB == 1024 ? bn_bwd_reduce_pair_nb<1024>(dtype, a, b, g.nrows, rows, keep_g, st)
+                                    : bn_bwd_reduce_pair_nb<256>(dtype, a, b, g.nrows, rows, keep_g, st);
+  if (e != hipSuccess) return e;
   // one fold for both BatchNorms: "segment" y = the BatchNorm, sums 2 C doubles apart
-  hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(cdiv(2 * a.C, 64), 2), dim3(64, 16), 0, st, rows, nrows, 2 * a.C, a.sums, 2 * a.C);
-  return hipGetLastError();
+  return bn_bwd_fold(rows, g.nrows, a.C, 2, a.sums, 2 * a.C, st);
 }
 hipError_t launch_bn_bwd_apply_pair(int dtype, const BnBwdArgs& a, const BnBwdArgs& b, int from_g, hipStream_t st) {
   if (!bn_bwd_pair_ok(a, b)) return hipErrorInvalidValue;
-  if (dtype == DT_BF16) hipLaunchKernelGGL(bn_bwd_apply_pair_kernel<bf16_t>, dim3(ew_grid_cols(a.pixels * (a.C / 8), a.C / 8)), dim3(256), 0, st, a, b, from_g);
-  else hipLaunchKernelGGL(bn_bwd_apply_pair_kernel<float>, dim3(ew_grid_cols(a.pixels * (a.C / 4), a.C / 4)), dim3(256), 0, st, a, b, from_g);
-  return hipGetLastError();
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    const int cols = a.C / Elem<T>::EPC;
+    hipLaunchKernelGGL(bn_bwd_apply_pair_kernel<T>, dim3(ew_grid_cols(a.pixels * cols, cols)), dim3(256), 0, st, a, b, from_g);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_bn_bwd_apply(int dtype, const BnBwdArgs& a0, hipStream_t st) {
@@ -1193,22 +1164,19 @@ hipError_t launch_bn_bwd_apply(int dtype, const BnBwdArgs& a0, hipStream_t st) {
     a.dy = a.gout; a.yact = nullptr; a.yact_bits = nullptr; a.relu_from_x = 0; a.gout = nullptr; a.g_in_reduce = 0;
   }
   if (a.pool_dy && a.nseg > 1) return hipErrorInvalidValue;
-  if (a.pool_dy) {
-    const int epc = dtype == DT_BF16 ? 8 : 4;
-    const size_t items = (a.pixels / ((size_t)a.pH * a.pW)) * ((a.pH + 1) / 2) * ((a.pW + 1) / 2) * (a.C / epc);
-    if (dtype == DT_BF16) hipLaunchKernelGGL(bn_bwd_apply_pool_kernel<bf16_t>, dim3(ew_grid_cols(items, a.C / epc)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(bn_bwd_apply_pool_kernel<float>, dim3(ew_grid_cols(items, a.C / epc)), dim3(256), 0, st, a);
-    return hipGetLastError();
-  }
   const int nseg = a.nseg > 1 ? a.nseg : 1;
   if (a.pixels % nseg != 0) return hipErrorInvalidValue;
-  const size_t per = a.pixels / nseg;
-  if (dtype == DT_BF16) {
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, dim3(ew_grid_cols(per * (a.C / 8), a.C / 8), nseg), dim3(256), 0, st, a);
-  } else {
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(ew_grid_cols(per * (a.C / 4), a.C / 4), nseg), dim3(256), 0, st, a);
-  }
-  return hipGetLastError();
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    const int cols = a.C / Elem<T>::EPC;
+    if (a.pool_dy) {
+      const size_t items = (a.pixels / ((size_t)a.pH * a.pW)) * ((a.pH + 1) / 2) * ((a.pW + 1) / 2) * cols;
+      hipLaunchKernelGGL(bn_bwd_apply_pool_kernel<T>, dim3(ew_grid_cols(items, cols)), dim3(256), 0, st, a);
+    } else {
+      hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(ew_grid_cols(a.pixels / nseg * cols, cols), nseg), dim3(256), 0, st, a);
+    }
+    return hipGetLastError();
+  });
 }
 
 __global__ void bn_param_grads_kernel(const double* sums, const float* invstd, float* dgamma, float* dbeta, int C, float scale) {

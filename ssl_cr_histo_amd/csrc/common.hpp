@@ -3,8 +3,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
-
 namespace sslcr {
 
 typedef uint16_t bf16_t;                                    // raw bf16 bits

@@ -299,16 +299,8 @@ template <typename T, int BP, int BKO>
 static hipError_t launch_d(DmaInst<T, BP, BKO>, const ConvArgs& a, hipStream_t st) {
   const int M = a.N * a.PH * a.PW;
   const size_t lds = 2 * (BP + BKO) * 128;
-  auto kern = conv_dma_kernel<T, BP, BKO>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
   if (a.par4 && (!a.transposed || a.stride != 2 || a.pix_mul != 2 || a.R != 3 || a.S != 3 || a.pad != 1 || a.stats)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kern, dim3(cdiv(M, BP) * (a.K / BKO), 1, a.par4 ? 4 : 1), dim3(256), lds, st, a);
-  return hipGetLastError();
+  return launch_lds<conv_dma_kernel<T, BP, BKO>>(dim3(cdiv(M, BP) * (a.K / BKO), 1, a.par4 ? 4 : 1), dim3(256), lds, 96 * 1024, st, a);
 }
 
 // the instance of pixel block bp (conv_dma_bp): f(DmaInst<T, BP, BKO>{})

@@ -377,13 +377,6 @@ static hipError_t launch_f8(const ConvArgs& a, const Fp8Args& q, hipStream_t st)
   constexpr int HP = (256 / (TW * TW)) * (TW + 2) * (TW + 2);
   constexpr int HBUF = ((HP * 128 + 1023) / 1024) * 1024;
   const size_t lds = 2 * HBUF + 3 * 128 * 128 + (XF ? 2 * a.C * sizeof(float) : 0);
-  auto kern = conv3x3_fp8_kernel<TW, XF>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
   const int cus = device_cus();
   const int ntiles = TW == 16 ? a.N * (a.H / 16) * (a.W / 16) : a.N / 4;
   if ((size_t)a.N * a.H * a.W * a.C * 2 >= ((size_t)1 << 32)) return hipErrorInvalidValue;      // 32-bit lane offsets (see load_chunk)
@@ -391,8 +384,7 @@ static hipError_t launch_f8(const ConvArgs& a, const Fp8Args& q, hipStream_t st)
   int gx = cus / gy;                               // one persistent workgroup per CU over (tile walkers) x (128-kout blocks)
   if (gx < 1) gx = 1;
   if (gx > ntiles) gx = ntiles;
-  hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(512), lds, st, a, q, ntiles);
-  return hipGetLastError();
+  return launch_lds<conv3x3_fp8_kernel<TW, XF>>(dim3(gx, gy), dim3(512), lds, 160 * 1024, st, a, q, ntiles);
 }
 
 hipError_t launch_conv_fp8(const ConvArgs& a, const Fp8Args& q, hipStream_t st) {

@@ -104,6 +104,16 @@ __global__ __launch_bounds__(256 * WK, WK == 1 ? 1 : 2) void conv3x3_h16s_kernel
 #include "conv_h16_body.hpp"
 }
 
+// bf16 64 -> 64: one 128-byte slab of input channels and one kout block, the filter bank fits LDS whole
+static bool h16_resident(const ConvArgs& a) { return a.C == 64 && a.K == 64; }
+// dynamic LDS of an instance: the halo of the tile form, `filter_stages` x 3 taps of a kout block (ring: 2, resident bank: 3), the
+// input transform's 2 C floats, 8 floats per kout of the block, and k_arrays K-float arrays (bias; + output scale; mask_x: 3)
+static size_t h16_lds_bytes(int tile, int bko, int filter_stages, int C, int K, int k_arrays) {
+  return (size_t)(tile == 16 ? 18 * 24 : 4 * 10 * 10) * 128 + (size_t)filter_stages * 3 * bko * 128 + 2 * (size_t)C * sizeof(float) +
+         8 * (size_t)bko * sizeof(float) + (size_t)k_arrays * K * sizeof(float);
+}
+constexpr size_t H16_LDS_CAP = 160 * 1024;
+
 // 16: 16x16 tiles of one image; 8: four whole 8x8 images per tile (128-kout blocks: ResNet18 layer4 at 256x256 input); 0: not served.
 // q: the conv3x3_halo256 tiling of the descriptor that both dtypes agree on (conv_plan: the launches must tile identically)
 int conv_h16_mode(const ConvArgs& a, int q) {
@@ -111,31 +121,34 @@ int conv_h16_mode(const ConvArgs& a, int q) {
   const int mode = q == 16 ? 16 : (q == 8 && on8 && a.K % 128 == 0 && !a.mask_x && (a.seg_images <= 0 || a.seg_images % 4 == 0)) ? 8 : 0;
   if (mode == 0) return 0;
   if (a.in_scale && a.residual) return 0;              // not a ResNet combination; the older halo kernels take it
+  // The LDS checks below have no dtype to go by: a 64 -> 64 descriptor is counted with the resident bank's three filter stages, which
+  // launch_h uses in bf16 only (fp32 keeps the ring's two).  Either count fits, so the answer is the launcher's for both.
+  const int bko = a.K % 128 == 0 ? 128 : 64, stages = h16_resident(a) ? 3 : 2;
   if (a.mask_x) {
     // (a.stats is checked at launch: sslcr_conv2d_partial_rows asks before the rows buffer exists)
     if (!a.mask_scale || !a.mask_shift || !a.mask_mean || a.in_scale || a.bias || a.residual || a.relu || a.out_scale) return 0;
-    if (18 * 24 * 128 + 2 * 3 * (a.K % 128 == 0 ? 128 : 64) * 128 + 2 * a.C * 4 + 8 * 128 * 4 + 3 * a.K * 4 > 160 * 1024) return 0;
+    // (mask_x: 16x16 tiles only.)  This predicate has always counted the 8 floats per kout for a 128-kout block whatever the block:
+    // 2 KiB more than launch_h asks for a 64-kout one.  Kept, so that no descriptor changes its route.
+    if (h16_lds_bytes(16, bko, stages, a.C, a.K, 3) + 8 * (128 - bko) * sizeof(float) > H16_LDS_CAP) return 0;
   }
   if (a.out_scale) {
     // one more K-float array in LDS (the input-transform and train-forward instances have no output scale: bias forms only)
     if (a.in_scale || a.stats || !a.bias) return 0;
-    const int bko = a.K % 128 == 0 ? 128 : 64;
-    if (!(a.C == 64 && a.K == 64) &&
-        (mode == 16 ? 18 * 24 : 4 * 10 * 10) * 128 + 2 * 3 * bko * 128 + 2 * a.C * 4 + 8 * bko * 4 + 2 * a.K * 4 > 160 * 1024) return 0;
+    if (h16_lds_bytes(mode, bko, stages, a.C, a.K, 2) > H16_LDS_CAP) return 0;
   }
   return mode;
 }
-static int h16_tiles(const ConvArgs& a, int nseg) {                     // per segment
-  return a.H == 8 ? (a.N / nseg) / 4 : (a.N / nseg) * (a.H / 16) * (a.W / 16);
-}
-// partial-statistics rows the launch will write: four per workgroup (see s_stat)
-// workgroups of the launch: one per CU, or per item where there are fewer; with segments, nseg equal groups
-static int h16_grid(const ConvArgs& a, int bko) {
+// The launch's geometry for kout blocks of bko, read by the row count and the launcher alike: segments, tiles and (tile, kout block)
+// items per segment, and workgroups -- one per CU, or per item where there are fewer; with segments, nseg equal groups.
+// Partial-statistics rows the launch will write: four per workgroup (see s_stat)
+struct H16Geom { int nseg, tiles, n_items, grid; };
+static H16Geom h16_geom(const ConvArgs& a, int bko) {
   const int nseg = a.seg_images > 0 ? a.N / a.seg_images : 1;
-  const int n_items = h16_tiles(a, nseg) * (a.K / bko);       // per segment
-  const int per = device_cus() / nseg;
-  return (n_items < per ? n_items : per) * nseg;
+  const int tiles = a.H == 8 ? (a.N / nseg) / 4 : (a.N / nseg) * (a.H / 16) * (a.W / 16);
+  const int n_items = tiles * (a.K / bko), per = device_cus() / nseg;
+  return {nseg, tiles, n_items, (n_items < per ? n_items : per) * nseg};
 }
+static int h16_grid(const ConvArgs& a, int bko) { return h16_geom(a, bko).grid; }
 // Four-image tiles (layer4): with one workgroup per CU walking (tile, 128-kout block) items, a last round that would occupy at most
 // half the CUs (N = 640: 640 items = 2.5 rounds of 256) runs its tiles as 64-kout items on all of them instead, in a second launch
 // over the tail images (the split conv3x3_halo256 makes for this shape).  -> tiles of the tail launch (0: one launch)
@@ -162,8 +175,6 @@ int conv_h16_rows(const ConvArgs& a) {
   return h16_grid(a, a.K % 128 == 0 ? 128 : 64) * 4;
 }
 
-// bf16 64 -> 64: one 128-byte slab of input channels and one kout block, the filter bank fits LDS whole
-static bool h16_resident(const ConvArgs& a) { return a.C == 64 && a.K == 64; }
 // the train-mode forward's output stage (the RAW instance); SSLCR_H16_RAW=0 keeps the general body for same-box A/B runs
 static bool h16_raw(const ConvArgs& a) {
   static const bool on = [] { const char* e = getenv("SSLCR_H16_RAW"); return !e || atoi(e) != 0; }();
@@ -180,28 +191,15 @@ struct H16Inst {
 
 template <typename T, int BKO, int WK, bool XF, bool WR, bool RAW, int TW, bool OSC>
 static hipError_t launch_h(H16Inst<T, BKO, WK, XF, WR, RAW, TW, OSC>, const ConvArgs& a, hipStream_t st, int row0) {
-  const size_t lds = (TW == 16 ? 18 * 24 : 4 * 10 * 10) * 128 + (WR ? 3 : 2) * 3 * BKO * 128 + 2 * a.C * sizeof(float) + 8 * BKO * sizeof(float) +
-                     (a.mask_x ? 3 : (a.out_scale ? 2 : 1)) * a.K * sizeof(float);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
   static_assert(!OSC || (!XF && !RAW), "output scale: eval forms only");
-  void (*kern)(const ConvArgs, const int, const int, const int, const int);
-  if constexpr (OSC) kern = conv3x3_h16s_kernel<T, BKO, WK, WR, TW>;
-  else kern = conv3x3_h16_kernel<T, BKO, WK, XF, WR, RAW, TW>;
   if (OSC != (a.out_scale != nullptr)) return hipErrorInvalidValue;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  const int nseg = a.seg_images > 0 ? a.N / a.seg_images : 1;
-  const int tiles = h16_tiles(a, nseg);                                 // per segment, like n_items
-  const int n_items = tiles * (a.K / BKO);
-  const int grid = h16_grid(a, BKO);                                    // one 8-wave workgroup per CU
-  const int kbn = a.K / BKO, gseg = grid / nseg;
+  const size_t lds = h16_lds_bytes(TW, BKO, WR ? 3 : 2, a.C, a.K, a.mask_x ? 3 : (a.out_scale ? 2 : 1));
+  const H16Geom g = h16_geom(a, BKO);                                   // one 8-wave workgroup per CU
+  const int kbn = a.K / BKO, gseg = g.grid / g.nseg;
   const int kshift = (kbn > 1 && (kbn & (kbn - 1)) == 0 && (gseg & (kbn - 1)) == 0) ? __builtin_ctz(kbn) : -1;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256 * WK), lds, st, a, tiles, n_items, kshift, row0);
-  return hipGetLastError();
+  const dim3 grid(g.grid), block(256 * WK);
+  if constexpr (OSC) return launch_lds<conv3x3_h16s_kernel<T, BKO, WK, WR, TW>>(grid, block, lds, H16_LDS_CAP, st, a, g.tiles, g.n_items, kshift, row0);
+  else return launch_lds<conv3x3_h16_kernel<T, BKO, WK, XF, WR, RAW, TW>>(grid, block, lds, H16_LDS_CAP, st, a, g.tiles, g.n_items, kshift, row0);
 }
 
 // The instance of one (kout block, tile, filter residency) form that a's operands select: f(H16Inst<...>{}).  The RAW output stage

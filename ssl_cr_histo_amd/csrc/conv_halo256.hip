@@ -350,16 +350,8 @@ static hipError_t launch_q(Halo256Inst<T, TW, BKO, WK, ONE>, const ConvArgs& a, 
   constexpr int HP = (256 / (TW * TW)) * (TW + 2) * (TW + 2);
   constexpr int TPB = (WK == 2 && !ONE) ? 3 : 1;
   const size_t lds = HP * 128 + 2 * TPB * BKO * 128 + 2 * a.C * sizeof(float);
-  auto kern = conv3x3_halo256_kernel<T, TW, BKO, WK, ONE>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
   dim3 grid(ntiles < 0 ? conv_halo256_tiles(a, TW) : ntiles, a.K / BKO);
-  hipLaunchKernelGGL(kern, grid, dim3(256 * WK), lds, st, a, tile0);
-  return hipGetLastError();
+  return launch_lds<conv3x3_halo256_kernel<T, TW, BKO, WK, ONE>>(grid, dim3(256 * WK), lds, 160 * 1024, st, a, tile0);
 }
 
 // the instance that serves a in this tile mode: f(Halo256Inst<...>{}) -- of the two launches a four-image shape with a thin last round

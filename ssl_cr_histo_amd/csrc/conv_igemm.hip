@@ -263,15 +263,7 @@ static hipError_t launch_cfg(IgemmInst<T, BP, BKO>, const ConvArgs& a, hipStream
   const int M = a.N * a.PH * a.PW;
   dim3 grid(cdiv(M, BP), a.K / BKO);
   size_t lds = 2 * (BP + BKO) * 128 + 2 * a.C * sizeof(float);
-  auto kern = conv_igemm_kernel<T, BP, BKO>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
-  return hipGetLastError();
+  return launch_lds<conv_igemm_kernel<T, BP, BKO>>(grid, dim3(256), lds, 96 * 1024, st, a);
 }
 
 static int igemm_bp(const ConvArgs& a) {

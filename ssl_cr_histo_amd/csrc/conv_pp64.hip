@@ -438,11 +438,17 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp64_kernel(const ConvArgs a, 
   }
 }
 
-static int pp64_grid(const ConvArgs& a) {
-  const int nseg = a.seg_images > 0 ? a.N / a.seg_images : 1;
-  const int tiles = (a.N / nseg) * (a.H / 16) * (a.W / 16);       // per segment
-  const int pairs = (tiles + 1) / 2, per = device_cus() / nseg;
-  return (pairs < per ? pairs : per) * nseg;
+// The launch's geometry, read by the row count and the launcher alike: tiles per segment, workgroups (one per pair of tiles, at most
+// one per CU; with segments, nseg equal groups) and rows of a.stats -- what conv3x3_h16 would write for this shape (one 64-kout block;
+// the caller sized the buffer before it knew the dtype); with segments -- a bf16-only form -- exactly this grid's rows, so that
+// segment s owns rows [s, s + 1) * rows / nseg
+struct Pp64Geom { int tiles, grid, rows; };
+static Pp64Geom pp64_geom(const ConvArgs& a) {
+  const int nseg = a.seg_images > 0 ? a.N / a.seg_images : 1, cus = device_cus();
+  const int tiles = (a.N / nseg) * (a.H / 16) * (a.W / 16);
+  const int pairs = (tiles + 1) / 2, per = cus / nseg;
+  const int grid = (pairs < per ? pairs : per) * nseg;
+  return {tiles, grid, (a.seg_images > 0 ? grid : (tiles < cus ? tiles : cus)) * 4};
 }
 
 // bf16 64 -> 64 on 16x16-tileable maps, every operand combination conv3x3_h16's resident-filter form serves (conv_plan asks where
@@ -455,20 +461,15 @@ bool conv_pp64_ok(int dtype, const ConvArgs& a) {
          a.H % 16 == 0 && a.W % 16 == 0 && !(a.in_scale && (a.residual || a.mask_x)) &&
          !(a.out_scale && (a.in_scale || a.mask_x || a.stats || !a.bias));
 }
-// rows of a.stats: what conv3x3_h16 would write for this shape (one 64-kout block; the caller sized the buffer before it knew the
-// dtype); with segments -- a bf16-only form -- exactly this grid's rows, so that segment s owns rows [s, s + 1) * rows / nseg
-int conv_pp64_rows(const ConvArgs& a) {
-  if (a.seg_images > 0) return pp64_grid(a) * 4;
-  const int tiles = a.N * (a.H / 16) * (a.W / 16);
-  return (tiles < device_cus() ? tiles : device_cus()) * 4;
-}
+int conv_pp64_rows(const ConvArgs& a) { return pp64_geom(a).rows; }
 
 template <bool XF, int OP>
 struct Pp64Inst { static std::string spell() { return kname("conv3x3_pp64_kernel", XF, OP); } };
 // the instance that serves a: f(Pp64Inst<XF, OP>{})
 template <bool XF, int OP>
-static void launch_pp(Pp64Inst<XF, OP>, dim3 grid, size_t lds, hipStream_t st, const ConvArgs& a, int tiles, int rows) {
-  hipLaunchKernelGGL((conv3x3_pp64_kernel<XF, OP>), grid, dim3(512), lds, st, a, tiles, rows);
+static hipError_t launch_pp(Pp64Inst<XF, OP>, const Pp64Geom& g, hipStream_t st, const ConvArgs& a) {
+  constexpr size_t lds = 9 * 64 * 128 + 2 * 18 * 18 * 128 + (320 + 1024) * sizeof(float);
+  return launch_lds<conv3x3_pp64_kernel<XF, OP>>(dim3(g.grid), dim3(512), lds, 160 * 1024, st, a, g.tiles, g.rows);
 }
 template <class F>
 static auto pp64_pick(const ConvArgs& a, F&& f) {
@@ -477,26 +478,9 @@ static auto pp64_pick(const ConvArgs& a, F&& f) {
 }
 
 hipError_t launch_conv_pp64(const ConvArgs& a, hipStream_t st) {
-  constexpr size_t lds = 9 * 64 * 128 + 2 * 18 * 18 * 128 + (320 + 1024) * sizeof(float);
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    const void* ks[4] = {reinterpret_cast<const void*>(conv3x3_pp64_kernel<false, 0>), reinterpret_cast<const void*>(conv3x3_pp64_kernel<false, 1>),
-                         reinterpret_cast<const void*>(conv3x3_pp64_kernel<false, 2>), reinterpret_cast<const void*>(conv3x3_pp64_kernel<true, 0>)};
-    for (const void* k : ks) {
-      hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-    }
-    attr_done = true;
-  }
-  const int nseg = a.seg_images > 0 ? a.N / a.seg_images : 1;
-  const int tiles = (a.N / nseg) * (a.H / 16) * (a.W / 16);       // per segment
-  const int grid = pp64_grid(a);
   if (a.mask_x && !a.stats) return hipErrorInvalidValue;
-  const int rows = conv_pp64_rows(a);
-  return pp64_pick(a, [&](auto inst) {
-    launch_pp(inst, dim3(grid), lds, st, a, tiles, rows);
-    return hipGetLastError();
-  });
+  const Pp64Geom g = pp64_geom(a);
+  return pp64_pick(a, [&](auto inst) { return launch_pp(inst, g, st, a); });
 }
 
 const char* conv_pp64_name(const ConvArgs& a) { return pp64_pick(a, InstName{}); }

@@ -7,15 +7,6 @@
 
 namespace sslcr {
 
-int device_cus() {
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-  }();
-  return cus;
-}
-
 // Segments (sslcr_conv_desc.seg_images): which kernels have the form, and where the row ranges come out right.
 //   conv3x3_h16 / conv3x3_pp64: the grid is split into nseg groups of workgroups (their statistics rows are per workgroup; with mask_x:
 //                    mask_scale / mask_shift / mask_mean + s * seg_stride)

@@ -472,22 +472,13 @@ struct S2Inst { static std::string spell() { return kname("conv_s2_kernel", PAIR
 template <bool PAIR, bool EVAL>
 static hipError_t launch_s2(S2Inst<PAIR, EVAL>, const ConvArgs& a, const ConvArgs& d, hipStream_t st) {
   const size_t lds = 3 * 289 * 128 + 3 * 128 * 128 + (EVAL ? 4 * 128 * sizeof(float) : 0);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  auto kern = conv_s2_kernel<PAIR, EVAL>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
   const int tiles = a.N * (a.PH / 16) * (a.PW / 16);
   const int kbn = a.K / 128;
   const int n_items = tiles * kbn;
   const int cus = device_cus();
   const int grid = n_items < cus ? n_items : cus;
   const int kshift = (kbn > 1 && (kbn & (kbn - 1)) == 0 && (grid & (kbn - 1)) == 0) ? __builtin_ctz(kbn) : -1;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a, d, tiles, n_items, kshift);
-  return hipGetLastError();
+  return launch_lds<conv_s2_kernel<PAIR, EVAL>>(dim3(grid), dim3(512), lds, 160 * 1024, st, a, d, tiles, n_items, kshift);
 }
 
 // the instance: f(S2Inst<PAIR, EVAL>{}) -- the bias selects the EVAL epilogue

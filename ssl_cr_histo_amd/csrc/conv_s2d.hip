@@ -297,20 +297,13 @@ bool conv_s2d_ok(int dtype, const ConvArgs& a) {
 
 hipError_t launch_conv_s2d(const ConvArgs& a, hipStream_t st) {
   const size_t lds = 2 * 289 * 128 + 3 * 3 * 64 * 128;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_s2d_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
   const int tiles = a.N * (a.H / 16) * (a.W / 16);
   const int cbn = a.K / 64;
   const int n_items = tiles * cbn;
   const int cus = device_cus();
   const int grid = n_items < cus ? n_items : cus;
   const int kshift = (cbn > 1 && (cbn & (cbn - 1)) == 0 && (grid & (cbn - 1)) == 0) ? __builtin_ctz(cbn) : -1;
-  hipLaunchKernelGGL(conv_s2d_kernel, dim3(grid), dim3(512), lds, st, a, tiles, n_items, kshift);
-  return hipGetLastError();
+  return launch_lds<conv_s2d_kernel>(dim3(grid), dim3(512), lds, 160 * 1024, st, a, tiles, n_items, kshift);
 }
 
 struct S2dInst { static std::string spell() { return kname("conv_s2d_kernel"); } };

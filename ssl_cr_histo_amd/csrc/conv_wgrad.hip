@@ -253,23 +253,12 @@ static hipError_t launch_w(WgradInst<T, TAPS, KH>, const WgradArgs& a, hipStream
   const int sps = cdiv(total_steps, splits);
   splits = cdiv(total_steps, sps);
   const size_t lds = 2 * (KH + TAPS) * 4096;
-  auto kern = wgrad_kernel<T, TAPS, KH>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
   const int gx = a.K / (64 * KH), gy = a.C / 64;
   if (TAPS != a.R * a.S) return hipErrorInvalidValue;
-  f32x4_t* slabs = nullptr;                      // accumulator slabs + the ordered fold whenever there is more than one pixel split
-  if (splits > 1) {
-    slabs = reinterpret_cast<f32x4_t*>(stream_scratch(st, (size_t)gx * gy * splits * TAPS * 4 * 256 * KH * sizeof(f32x4_t)));
-    if (!slabs) return hipErrorOutOfMemory;
-  }
-  hipLaunchKernelGGL(kern, dim3(gx * gy * splits), dim3(256 * KH), lds, st, a, sps, slabs);
-  if (slabs) return launch_wgrad_fold(slabs, a.dw, a.C, gx, gy, splits, TAPS, KH, st);
-  return hipGetLastError();
+  // accumulator slabs + the ordered fold whenever there is more than one pixel split
+  return with_slabs(st, splits > 1 ? (size_t)gx * gy * splits * TAPS * 4 * 256 * KH * sizeof(f32x4_t) : 0,
+    [&](f32x4_t* slabs) { return launch_lds<wgrad_kernel<T, TAPS, KH>>(dim3(gx * gy * splits), dim3(256 * KH), lds, 96 * 1024, st, a, sps, slabs); },
+    [&](f32x4_t* slabs) { return launch_wgrad_fold(slabs, a.dw, a.C, gx, gy, splits, TAPS, KH, st); });
 }
 
 // diagnostics: raw semantics of ds_read_b64_tr_b16 -- lane l reads at byte_addr[l] of a 2 KiB LDS image

@@ -4,6 +4,7 @@
 #include <string>
 
 #include "common.hpp"
+#include "launch.hpp"
 #include "../../include/sslcr.h"
 
 namespace sslcr {
@@ -78,7 +79,6 @@ hipError_t launch_wgrad(int dtype, const WgradArgs& a, const WgradPlan& p, hipSt
 inline hipError_t launch_wgrad(int dtype, const WgradArgs& a, hipStream_t st) { return launch_wgrad(dtype, a, wgrad_plan(dtype, a), st); }
 inline const char* wgrad_kernel_name(int dtype, const WgradArgs& a) { return wgrad_plan(dtype, a).name; }
 inline bool wgrad_dma_used(int dtype, const WgradArgs& a) { return wgrad_plan(dtype, a).route == WgradRoute::HALO_DMA; }
-int device_cus();      // compute units of the current device (asked once per process, thread-safely; 256 if the query fails)
 // conv_igemm.hip: the generic gather kernel
 int conv_igemm_rows(const ConvArgs& a);
 hipError_t launch_igemm(int dtype, const ConvArgs& a, hipStream_t st);
@@ -129,13 +129,7 @@ hipError_t launch_fp8_scale_update(float* slots, int n, hipStream_t st);
 hipError_t launch_wgrad_generic(int dtype, const WgradArgs& a, hipStream_t st);
 const char* wgrad_generic_name(int dtype, const WgradArgs& a);
 int wgrad_halo_tw(const WgradArgs& a);
-// per-stream scratch for partial results that a follow-up launch on the SAME stream folds in a fixed order: the accumulator slabs of
-// the weight-gradient kernels (wgrad_fold_kernel) and the per-workgroup rows of the BatchNorm-backward reduce pass (bn_bwd_sums_kernel);
-// the launches that fold them, wgrad_halo.hip
-void* stream_scratch(hipStream_t st, size_t bytes);
-void stream_scratch_release();      // frees every stream's scratch (sslcr_destroy, after a device synchronise)
-hipError_t launch_wgrad_fold(const void* slabs, float* dw, int C, int gx, int gy, int splits, int taps, int kh_n, hipStream_t st);
-hipError_t launch_stem_wgrad_fold(const void* slabs, float* dw, int nwg, hipStream_t st);
+// wgrad_halo.hip (and the fold launches, launch.hpp)
 int wgrad_halo_splits(const WgradArgs& a, int tw, int kh);      // pixel splits of the halo launch (the DMA form wants more than one)
 hipError_t launch_wgrad_halo(int dtype, const WgradArgs& a, const WgradPlan& p, hipStream_t st);
 const char* wgrad_halo_name(int dtype, int tw, int kh);

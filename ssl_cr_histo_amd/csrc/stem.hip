@@ -332,15 +332,7 @@ static hipError_t launch_stem_t(const StemArgs& a, hipStream_t st) {
   const int th = cdiv(a.OH, TH), tw = cdiv(a.OW, TW);
   const int ntiles = a.N * th * tw;
   const size_t lds = 64 * (224 * sizeof(T) + 16) + 2 * HR * HC * 4 * sizeof(T);
-  auto kern = stem_fwd_kernel<T, INF32>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(stem_grid(a.N, a.OH, a.OW)), dim3(256), lds, st, a, th, tw, ntiles);
-  return hipGetLastError();
+  return launch_lds<stem_fwd_kernel<T, INF32>>(dim3(stem_grid(a.N, a.OH, a.OW)), dim3(256), lds, 96 * 1024, st, a, th, tw, ntiles);
 }
 
 hipError_t launch_stem(int dtype, const StemArgs& a, hipStream_t st) {
@@ -934,28 +926,21 @@ __global__ __launch_bounds__(768) void stem_wgrad_pool2_kernel(const StemWgradAr
   }
 }
 
-template <typename T, bool INF32, bool POOL>
-static hipError_t launch_stem_wgrad_t(const StemWgradArgs& a, const BnBwdArgs& b, hipStream_t st) {
+// at most max_grid workgroups of `threads`; every workgroup holds a partial of the SAME 64 x 147 weights: slabs + the ordered fold
+// (wgrad_halo.hip), in every dtype
+template <auto Kern>
+static hipError_t launch_stem_wgrad_k(int max_grid, int threads, size_t lds, size_t cap, const StemWgradArgs& a, const BnBwdArgs& b, hipStream_t st) {
   const int th = cdiv(a.OH, TH), tw = cdiv(a.OW, TW);
   const int ntiles = a.N * th * tw;
+  const int grid = ntiles < max_grid ? ntiles : max_grid;
+  return with_slabs(st, grid > 1 ? (size_t)grid * 14 * 256 * sizeof(f32x4_t) : 0,
+    [&](f32x4_t* slabs) { return launch_lds<Kern>(dim3(grid), dim3(threads), lds, cap, st, a, b, th, tw, ntiles, slabs); },
+    [&](f32x4_t* slabs) { return launch_stem_wgrad_fold(slabs, a.dw, grid, st); });
+}
+template <typename T, bool INF32, bool POOL>
+static hipError_t launch_stem_wgrad_t(const StemWgradArgs& a, const BnBwdArgs& b, hipStream_t st) {
   const size_t lds = 2 * (TH * TW * 64 * sizeof(T) + HR * HC * 4 * sizeof(T));
-  auto kern = stem_wgrad_kernel<T, INF32, POOL>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  int grid = ntiles < 768 ? ntiles : 768;
-  // every workgroup holds a partial of the SAME 64 x 147 weights: slabs + the ordered fold (wgrad_halo.hip), in every dtype
-  f32x4_t* slabs = nullptr;
-  if (grid > 1) {
-    slabs = reinterpret_cast<f32x4_t*>(stream_scratch(st, (size_t)grid * 14 * 256 * sizeof(f32x4_t)));
-    if (!slabs) return hipErrorOutOfMemory;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, b, th, tw, ntiles, slabs);
-  if (slabs) return launch_stem_wgrad_fold(slabs, a.dw, grid, st);
-  return hipGetLastError();
+  return launch_stem_wgrad_k<stem_wgrad_kernel<T, INF32, POOL>>(768, 256, lds, 96 * 1024, a, b, st);
 }
 
 hipError_t launch_stem_wgrad(int dtype, const StemWgradArgs& a, hipStream_t st) {
@@ -968,25 +953,8 @@ hipError_t launch_stem_wgrad(int dtype, const StemWgradArgs& a, hipStream_t st) 
 // pass has run; b.dx is not written)
 template <bool INF32>
 static hipError_t launch_stem_wgrad_pool2(const StemWgradArgs& a, const BnBwdArgs& b, hipStream_t st) {
-  const int th = cdiv(a.OH, TH), tw = cdiv(a.OW, TW);
-  const int ntiles = a.N * th * tw;
-  const size_t lds = P2_NS * P2_STAGE + 2 * P2_HBUF;
-  auto kern = stem_wgrad_pool2_kernel<INF32>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  int grid = ntiles < 256 ? ntiles : 256;          // one 12-wave workgroup per CU (143 KiB of LDS)
-  f32x4_t* slabs = nullptr;
-  if (grid > 1) {
-    slabs = reinterpret_cast<f32x4_t*>(stream_scratch(st, (size_t)grid * 14 * 256 * sizeof(f32x4_t)));
-    if (!slabs) return hipErrorOutOfMemory;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(768), lds, st, a, b, th, tw, ntiles, slabs);
-  if (slabs) return launch_stem_wgrad_fold(slabs, a.dw, grid, st);
-  return hipGetLastError();
+  // one 12-wave workgroup per CU (143 KiB of LDS)
+  return launch_stem_wgrad_k<stem_wgrad_pool2_kernel<INF32>>(256, 768, P2_NS * P2_STAGE + 2 * P2_HBUF, 160 * 1024, a, b, st);
 }
 
 static int stem_pool_form() {                      // SSLCR_STEM_POOL_FORM=1: the single-role kernel in bf16 mode too (A/B runs)

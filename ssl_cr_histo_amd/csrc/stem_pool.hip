@@ -259,18 +259,11 @@ bool stem_pool_ok(int dtype, const StemArgs& a, int POH, int POW) {
 hipError_t launch_stem_pool(int dtype, const StemArgs& a, int POH, int POW, hipStream_t st) {
   if (!stem_pool_ok(dtype, a, POH, POW)) return hipErrorInvalidValue;
   const size_t lds = 64 * SP_WROW + 2 * (SP_HR * SP_HC * 4 * 2) + 2 * SP_PP + (size_t)a.OW * 128;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(stem_pool_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(stem_pool_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
   const int cus = device_cus();
   const int grid = a.N < cus ? a.N : cus;
-  if (a.in_f32) hipLaunchKernelGGL(stem_pool_fwd_kernel<true>, dim3(grid), dim3(SP_NT), lds, st, a, POH, POW);
-  else hipLaunchKernelGGL(stem_pool_fwd_kernel<false>, dim3(grid), dim3(SP_NT), lds, st, a, POH, POW);
-  return hipGetLastError();
+  const dim3 g(grid), b(SP_NT);
+  if (!a.in_f32) return launch_lds<stem_pool_fwd_kernel<false>>(g, b, lds, 160 * 1024, st, a, POH, POW);
+  return launch_lds<stem_pool_fwd_kernel<true>>(g, b, lds, 160 * 1024, st, a, POH, POW);
 }
 
 }  // namespace sslcr

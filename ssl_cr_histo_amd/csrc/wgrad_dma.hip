@@ -18,8 +18,6 @@
 // step); `s_waitcnt vmcnt(0)` + a bare barrier end the tile.
 #include <stdlib.h>
 
-#include <atomic>
-
 #include "kernels.hpp"
 
 namespace sslcr {
@@ -392,17 +390,9 @@ static hipError_t launch_wd_t(WgradDmaInst<TW, XF>, const WgradArgs& a, int tps,
   constexpr int NI = 128 / (8 * TW), PITCH = TW == 16 ? 24 : 16;
   const int nseg = a.seg_images > 0 ? a.N / a.seg_images : 1;
   const size_t lds = (size_t)2 * (256 + NI * 10 * PITCH) * 128 + 512 * nseg;
-  auto kern = wgrad3x3_dma_kernel<TW, XF>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
   const int gx = a.K / 128, gy = a.C / 64;
   static const int stagger = [] { const char* e = getenv("SSLCR_WG_STAGGER"); return e ? atoi(e) : 1; }();
-  hipLaunchKernelGGL(kern, dim3(gx * gy * splits), dim3(512), lds, st, a, tps, ntiles, slabs, stagger);
-  return hipGetLastError();
+  return launch_lds<wgrad3x3_dma_kernel<TW, XF>>(dim3(gx * gy * splits), dim3(512), lds, 160 * 1024, st, a, tps, ntiles, slabs, stagger);
 }
 
 // the instance: f(WgradDmaInst<TW, XF>{})

@@ -8,8 +8,6 @@
 // all nine taps fetch their B fragments from the halo at shifted pixel addresses -- ds_read_b64_tr_b16 takes a per-lane
 // address, so the shift is free.  4.3x less staging traffic per MAC.  Same 64(kout) x 64(cin) x 9 register tile, wave w
 // owning cin tile w; the pixel splits' accumulators go to slabs that wgrad_fold_kernel adds into dW in a fixed order.
-#include <cstdio>
-#include <mutex>
 
 #include "kernels.hpp"
 
@@ -389,65 +387,6 @@ hipError_t launch_stem_wgrad_fold(const void* slabs, float* dw, int nwg, hipStre
   return fold_launch(slabs, dw, 0, 1, 1, nwg, 14, 1, 1, st);
 }
 
-// slabs of the launches on one stream (a launch's fold has consumed them before the next launch on that stream writes; the
-// BatchNorm-backward reduce pass keeps its per-workgroup rows here too).
-// One entry per stream, 64 entries, least-recently-used eviction (logged once: it costs a device synchronise): a 65th stream (virtual-rank tests create a stream per context
-// and drop it) takes over the oldest entry after a device synchronise -- never a silent fall-back to the atomic path, whose
-// summation order differs -- and an evicted or destroyed stream's slab is freed instead of leaking.
-namespace {
-struct Slab { hipStream_t st; void* p; size_t cap; unsigned long long used; };
-constexpr int NSLAB = 64;
-Slab g_slabs[NSLAB];
-int g_nslabs = 0;
-unsigned long long g_slab_tick = 0;
-std::mutex g_slab_mu;                            // host threads driving different streams
-}  // namespace
-// sslcr_destroy: every stream's slab is freed (the device has been synchronised; a later launch allocates again)
-void stream_scratch_release() {
-  std::lock_guard<std::mutex> lock(g_slab_mu);
-  for (int i = 0; i < g_nslabs; ++i)
-    if (g_slabs[i].p) (void)hipFree(g_slabs[i].p);
-  g_nslabs = 0;
-}
-void* stream_scratch(hipStream_t st, size_t bytes) {
-  Slab* const slabs = g_slabs;
-  int& n = g_nslabs;
-  unsigned long long& tick = g_slab_tick;
-  std::lock_guard<std::mutex> lock(g_slab_mu);
-  Slab* e = nullptr;
-  for (int i = 0; i < n && !e; ++i)
-    if (slabs[i].st == st) e = &slabs[i];
-  if (!e) {
-    if (n < NSLAB) {
-      e = &slabs[n++];
-    } else {
-      e = &slabs[0];
-      for (int i = 1; i < NSLAB; ++i)
-        if (slabs[i].used < e->used) e = &slabs[i];
-      static bool warned = false;
-      if (!warned) {
-        warned = true;
-        fprintf(stderr, "sslcr: more than %d streams have launched weight-gradient / BatchNorm-backward kernels; the least recently used "
-                        "stream's slab is evicted after a device synchronise (slow when it happens per launch)\n", NSLAB);
-      }
-      (void)hipDeviceSynchronize();              // the evicted stream may be gone: wait for the device, not for the stream
-      if (e->p) (void)hipFree(e->p);
-    }
-    *e = Slab{st, nullptr, 0, 0};
-  }
-  e->used = ++tick;
-  if (e->cap < bytes) {
-    if (e->p) {
-      (void)hipStreamSynchronize(st);
-      (void)hipFree(e->p);
-    }
-    e->p = nullptr; e->cap = 0;
-    if (hipMalloc(&e->p, bytes) != hipSuccess) return nullptr;
-    e->cap = bytes;
-  }
-  return e->p;
-}
-
 int wgrad_halo_tw(const WgradArgs& a) {
   if (a.R != 3 || a.S != 3 || a.stride != 1 || a.pad != 1 || a.OH != a.H || a.OW != a.W) return 0;
   if (a.C % 64 != 0 || a.K % 64 != 0 || a.H % 8 != 0) return 0;
@@ -483,32 +422,20 @@ static hipError_t launch_wh(WgradHaloInst<T, TW, KH>, const WgradArgs& a, bool d
   constexpr int NI = 128 / (8 * TW);
   int tps, ntiles;
   const int splits = wh_splits(a, TW, KH, &tps, &ntiles);
-  const int pitch = BF ? (TW == 16 ? 24 : 16) : TW + 2;
   const int nseg = a.seg_images > 0 ? a.N / a.seg_images : 1;
   if (nseg > 8 || (a.seg_images > 0 && (a.N % a.seg_images != 0 || a.seg_images % NI != 0))) return hipErrorInvalidValue;
-  const size_t lds = (size_t)KH * (128 * KH + NI * 10 * pitch) * 64 * sizeof(T) + 512 * nseg;     // NBUF = KH buffers of (KH dY halves + halo)
-  auto kern = wgrad3x3_halo_kernel<T, TW, KH>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, KH == 1 ? 96 * 1024 : 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
   const int gx = a.K / (64 * KH), gy = a.C / 64;
-  // accumulator slabs + the ordered fold when there is more than one split (every dtype)
-  f32x4_t* slabs = nullptr;
-  if (splits > 1) {
-    slabs = reinterpret_cast<f32x4_t*>(stream_scratch(st, (size_t)gx * gy * splits * 36 * 256 * KH * sizeof(f32x4_t)));
-    if (!slabs) return hipErrorOutOfMemory;        // (no atomic path to fall back to: its summation order would differ)
-  }
-  if (dma) {
-    hipError_t e = launch_wgrad_dma(a, TW, tps, ntiles, splits, slabs, st);
-    if (e != hipSuccess) return e;
-    return launch_wgrad_fold(slabs, a.dw, a.C, gx, gy, splits, 9, KH, st);
-  }
-  hipLaunchKernelGGL(kern, dim3(gx * gy * splits), dim3(256 * KH), lds, st, a, tps, ntiles, slabs);
-  if (slabs) return launch_wgrad_fold(slabs, a.dw, a.C, gx, gy, splits, 9, KH, st);
-  return hipGetLastError();
+  // accumulator slabs + the ordered fold when there is more than one split (every dtype; the DMA route always has: wgrad_dma_ok)
+  const size_t slab_bytes = splits > 1 ? (size_t)gx * gy * splits * 36 * 256 * KH * sizeof(f32x4_t) : 0;
+  return with_slabs(st, slab_bytes,
+    [&](f32x4_t* slabs) {
+      if (dma) return launch_wgrad_dma(a, TW, tps, ntiles, splits, slabs, st);
+      const int pitch = BF ? (TW == 16 ? 24 : 16) : TW + 2;
+      const size_t lds = (size_t)KH * (128 * KH + NI * 10 * pitch) * 64 * sizeof(T) + 512 * nseg;     // NBUF = KH buffers of (KH dY halves + halo)
+      return launch_lds<wgrad3x3_halo_kernel<T, TW, KH>>(dim3(gx * gy * splits), dim3(256 * KH), lds, KH == 1 ? 96 * 1024 : 160 * 1024, st, a, tps,
+                                                         ntiles, slabs);
+    },
+    [&](f32x4_t* slabs) { return launch_wgrad_fold(slabs, a.dw, a.C, gx, gy, splits, 9, KH, st); });
 }
 
 // the instance of (tile width, kout halves): f(WgradHaloInst<T, TW, KH>{})

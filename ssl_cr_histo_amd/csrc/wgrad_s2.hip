@@ -237,8 +237,8 @@ static auto ws2_pick(const WgradArgs& a, F&& f) {
   return a.OW % 16 == 0 ? f(WgradS2Inst<16>{}) : f(WgradS2Inst<8>{});
 }
 template <int TW>
-static void launch_ws2(WgradS2Inst<TW>, dim3 grid, size_t lds, hipStream_t st, const WgradArgs& a, int tps, int ntiles, f32x4_t* slabs) {
-  hipLaunchKernelGGL(wgrad_s2_kernel<TW>, grid, dim3(512), lds, st, a, tps, ntiles, slabs);
+static hipError_t launch_ws2(WgradS2Inst<TW>, dim3 grid, size_t lds, hipStream_t st, const WgradArgs& a, int tps, int ntiles, f32x4_t* slabs) {
+  return launch_lds<wgrad_s2_kernel<TW>>(grid, dim3(512), lds, 160 * 1024, st, a, tps, ntiles, slabs);
 }
 const char* wgrad_s2_name(const WgradArgs& a) { return ws2_pick(a, InstName{}); }
 
@@ -254,22 +254,12 @@ hipError_t launch_wgrad_s2(const WgradArgs& a, hipStream_t st) {
   const int tps = cdiv(ntiles, splits);
   splits = cdiv(ntiles, tps);
   const size_t lds = 2 * (2 * 64 * 128 + 297 * 128);
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_s2_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_s2_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
   const int gx = a.K / 128, gy = a.C / 64;
-  f32x4_t* slabs = nullptr;
-  if (splits > 1) {
-    slabs = reinterpret_cast<f32x4_t*>(stream_scratch(st, (size_t)gx * gy * splits * 36 * 512 * sizeof(f32x4_t)));
-    if (!slabs) return hipErrorOutOfMemory;
-  }
-  ws2_pick(a, [&](auto inst) { launch_ws2(inst, dim3(gx * gy * splits), lds, st, a, tps, ntiles, slabs); return 0; });
-  if (slabs) return launch_wgrad_fold(slabs, a.dw, a.C, gx, gy, splits, 9, 2, st);
-  return hipGetLastError();
+  return with_slabs(st, splits > 1 ? (size_t)gx * gy * splits * 36 * 512 * sizeof(f32x4_t) : 0,
+    [&](f32x4_t* slabs) {
+      return ws2_pick(a, [&](auto inst) { return launch_ws2(inst, dim3(gx * gy * splits), lds, st, a, tps, ntiles, slabs); });
+    },
+    [&](f32x4_t* slabs) { return launch_wgrad_fold(slabs, a.dw, a.C, gx, gy, splits, 9, 2, st); });
 }
 
 }  // namespace sslcr

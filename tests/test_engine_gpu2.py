@@ -838,3 +838,52 @@ print("GP", " ".join(f"{float(g.flatten()[::7].sum()):.9e}" for g in gr))
     top = max(outs["0"]["GN"])
     for a, b in zip(outs["1"]["GN"], outs["0"]["GN"]):
         assert abs(a - b) <= 6e-2 * max(abs(b), 1e-3 * top), (a, b)
+
+
+# ------------------------------------------------------------------------------------------------ paired BatchNorm backward
+def _supervised_step_gradients(dtype, n, path):
+    """every gradient of one supervised 'ce' step on n 256x256 images and the names of the profiled kernels the step launched, saved
+    to `path` (run in a child process: see below)"""
+    from ssl_cr_histo_amd import engine as E
+    eng = E.set_engine(E.Engine(DEV, dtype))
+    model, cls = build("finetune", "finetune", 2, True)
+    model.train()
+    cls.train()
+    net_ = eng.bind(model, cls)
+    eng.profile(True)
+    eng.step_supervised(net_, "ce", [C.u8(8101, (n, 3, 256, 256))], C.ints(8102, (n,), 2).long(), train=True)
+    torch.cuda.synchronize()
+    torch.save(dict(grads=[net_.grad(i).cpu() for i in range(len(net_.params))], kernels=[r["name"] for r in eng.profile_table()]), path)
+
+
+@pytest.mark.parametrize("dtype,n", [("bf16", 64), ("fp32", 32)])
+def test_bn_backward_pair_equals_the_separate_passes(dtype, n, tmp_path):
+    """A downsampling block's two BatchNorms in one reduce and one apply pass (bn_bwd_reduce_pair_kernel, the default) against the
+    two separate BatchNorm-backward passes (SSLCR_BN_PAIR=0, read once into a static: each side in a child process of its own).
+    Both launchers take their grid from bn_bwd_reduce_grid(), so both add the same elements in the same order: every gradient of
+    the step has the same bits (so they had on the commit before that function, where each launcher wrote the grid out).  At 256x256 with these batches layer2.0's reduce pass takes the 1024-thread form (>= 512 workgroups
+    of 256 threads would be needed) and layer3.0's and layer4.0's the 256-thread form: both branches of the grid function."""
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    procs = {}
+    for flag in ("1", "0"):
+        code = (f"import sys; sys.path[:0] = [{os.path.dirname(here)!r}, {here!r}]\n"
+                "import test_engine_gpu2 as T\n"
+                f"T._supervised_step_gradients({dtype!r}, {n}, {str(tmp_path / ('pair' + flag + '.pt'))!r})\n")
+        procs[flag] = subprocess.Popen([sys.executable, "-c", code], env=dict(os.environ, SSLCR_BN_PAIR=flag), stdout=subprocess.PIPE,
+                                       stderr=subprocess.STDOUT, text=True)
+    for flag, p in procs.items():
+        out, _ = p.communicate(timeout=300)
+        assert p.returncode == 0, (flag, out[-3000:])
+    pair, separate = (torch.load(tmp_path / f"pair{flag}.pt") for flag in ("1", "0"))
+    for side, want in ((pair, True), (separate, False)):              # the switch did select the two forms
+        assert any("bn_bwd_apply_pair_kernel" in k for k in side["kernels"]) == want, side["kernels"]
+    pair, separate = pair["grads"], separate["grads"]
+    assert len(pair) == len(separate) >= 62                        # ResNet18's 62 parameters + the head's
+    errs = [rel_err(a, b) for a, b in zip(pair, separate)]
+    print(f"[{dtype}] paired against separate BatchNorm backward: largest relative error of a gradient {max(errs):.3e}, "
+          f"{sum(not torch.equal(a, b) for a, b in zip(pair, separate))} of {len(pair)} gradients differ in some bit")
+    assert all(bool(torch.isfinite(a).all()) for a in pair) and float(pair[0].abs().max()) > 0
+    for i, (a, b) in enumerate(zip(pair, separate)):
+        assert torch.equal(a, b), (i, errs[i])
