@@ -204,6 +204,88 @@ struct LdsDma {
   }
 };
 
+// ---- device idioms shared by the kernel families: ONE definition each (design rules)
+
+// 16x16 MFMA over one 16-byte fragment per operand: bf16 is one 16x16x32 step, fp32 (the parity mode) four 16x16x4 steps
+template <typename T> struct Mma;
+template <> struct Mma<bf16_t> {
+  __device__ static __forceinline__ void run(const u32x4_t& a, const u32x4_t& b, f32x4_t& c) {
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
+  }
+};
+template <> struct Mma<float> {
+  __device__ static __forceinline__ void run(const u32x4_t& a, const u32x4_t& b, f32x4_t& c) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[e]), __uint_as_float(b[e]), c, 0, 0, 0);
+  }
+};
+
+// Workgroups land on XCD (linear id % 8), each XCD with its own L2.  Two placements follow from that:
+// (1) a persistent walk b, b + G, ... of G workgroups: first item of workgroup b such that each XCD takes a CONTIGUOUS run of items
+//     per round -- neighbouring tiles' shared halo rows (and the 64-byte sectors a short row segment only partly uses) hit one L2.
+//     (a grid that is no multiple of 8 keeps the plain walk).  b keeps the caller's type -- an int, or blockIdx.x as the unsigned it is
+//     (xcd_run_start<unsigned>): the shift is a different instruction.  Written out in two places, conv_h16_body.hpp and
+//     stem_fwd_kernel: through the helper their branches are laid out in another order (tools/device_code_diff.sh).
+template <typename B>
+__device__ __forceinline__ int xcd_run_start(B b, int G) { return (G & 7) ? (int)b : (int)(b & 7) * (G >> 3) + (int)(b >> 3); }
+// (2) a grid of n_outer x n_inner workgroups whose n_inner blocks of one outer block read the same rows (the kout blocks of a pixel
+//     block, the (kout, cin) blocks of a pixel split): they are made neighbours ON ONE XCD (linear ids w, w + 8, ...), so n_inner - 1 of
+//     the n_inner reads hit that L2 instead of going out to the fabric (r03: layer4.0.conv1 fetched its 84 MB input four times).
+//     n_outer no multiple of 8: the launch order as it is, `inner_slow` saying which index is the slow one of that order.
+//     (returned by value: with two reference results the address arithmetic behind it is emitted in another order)
+struct OuterInner { int outer, inner; };
+__device__ __forceinline__ OuterInner xcd_outer_inner(int w, int n_outer, int n_inner, bool inner_slow) {
+  int outer, inner;
+  if ((n_outer & 7) == 0) {
+    const int grp = w / (8 * n_inner), r = w - grp * 8 * n_inner;
+    outer = grp * 8 + (r & 7); inner = r >> 3;
+  } else if (inner_slow) {
+    inner = w / n_outer; outer = w - inner * n_outer;
+  } else {
+    outer = w / n_inner; inner = w - outer * n_inner;
+  }
+  return {outer, inner};
+}
+
+// ---- LDS transpose read (ds_read_b64_tr_b16): both operands of a weight gradient sit in LDS pixel-major, as in NHWC memory, and the
+// reduction runs over pixels; the read takes a per-lane address and delivers the pixel-major -> K-major transpose for free.
+typedef short s16x4_t __attribute__((ext_vector_type(4)));
+typedef short s16x8_t __attribute__((ext_vector_type(8)));
+// through the intrinsic: the two halves (four pixels each) of one bf16 MFMA fragment
+__device__ __forceinline__ bf16x8_t tr_pair(const char* p0, const char* p1) {
+  s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p0));
+  s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p1));
+  s16x8_t v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_bit_cast(bf16x8_t, v);
+}
+// ... and as inline asm, for the kernels that keep LDS DMA in flight.  Through the intrinsic, the compiler's wait-count pass (no usable
+// memory operand on it) puts s_waitcnt vmcnt(0) in front of every such read while ANY LDS DMA is outstanding -- which drains the tiles
+// of DMA those kernels keep in flight (plain ds_read_b128 after a DMA, conv_dma.hip, does not get that wait).  The asm is opaque to
+// that pass, so the LDS counter is kept by hand next to the reads: s_waitcnt lgkmcnt(n) that names the registers it waits for.
+template <int OFF>
+__device__ __forceinline__ u32x2_t lds_tr16(uint32_t addr) {
+  u32x2_t v;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
+  return v;
+}
+__device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(size_t)(__attribute__((address_space(3))) const char*)(const char*)p; }
+__device__ __forceinline__ bf16x8_t frag_join(const u32x2_t& lo, const u32x2_t& hi) {
+  return __builtin_bit_cast(bf16x8_t, u32x4_t{lo[0], lo[1], hi[0], hi[1]});
+}
+
+// ---- workgroup barriers that leave the vector-memory counter alone.  __syncthreads() is a workgroup-scope fence, which the compiler
+// lowers to s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier -- and with global loads, stores or LDS DMA in flight vmcnt(0) means "wait for
+// the next tile's operands and for the last tile's stores" at every barrier.  The "memory" clobber keeps the compiler from moving
+// LDS accesses across either form.
+// LDS visibility + rendezvous: what crosses the barrier between waves is LDS data only (a DMA write it publishes is waited for
+// explicitly, in front)
+__device__ __forceinline__ void barrier_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// ... and without the lgkmcnt(0) as well (a wait for the fragment read issued two MFMAs earlier).  Enough wherever no ds_write is
+// pending and what the barrier orders are (a) this wave's completed DMA (explicit vmcnt in front) or (b) fragment reads whose MFMAs
+// have already been issued, i.e. whose data has arrived.
+__device__ __forceinline__ void barrier_bare() { asm volatile("s_barrier" ::: "memory"); }
+
 // Weight tiles sit in LDS in MFMA-fragment order: kout row r = q*(4TK) + t*4 + j of a 16*TK-row block (q = fragment lane>>2,
 // t = MFMA tile, j = lane&3 -- the permutation that gives a lane 4*TK consecutive output channels) is stored at row
 // t*16 + q*4 + j, so the 16 lanes of a fragment read 16 CONSECUTIVE LDS rows and the (row&7) XOR swizzle is conflict-free

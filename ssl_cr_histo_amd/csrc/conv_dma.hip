@@ -18,20 +18,6 @@
 
 namespace sslcr {
 
-template <typename T> struct MmaD;
-template <> struct MmaD<bf16_t> {
-  __device__ static __forceinline__ void run(const u32x4_t& a, const u32x4_t& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  }
-};
-template <> struct MmaD<float> {
-  __device__ static __forceinline__ void run(const u32x4_t& a, const u32x4_t& b, f32x4_t& c) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[e]), __uint_as_float(b[e]), c, 0, 0, 0);
-  }
-};
-
 template <typename T, int BP, int BKO>
 __global__ __launch_bounds__(256, 2) void conv_dma_kernel(const ConvArgs a) {
   constexpr int EPC = Elem<T>::EPC;
@@ -47,17 +33,10 @@ __global__ __launch_bounds__(256, 2) void conv_dma_kernel(const ConvArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, li = lane & 15;
   const int wp = wave % WP, wk = wave / WP;
-  // grid x = (pixel block, kout block) pairs; workgroups land on XCD (linear id % 8), each with its own L2.  The KB kout blocks of
-  // one pixel block read the same input rows, so they are made neighbours ON ONE XCD (ids w, w + 8, ...): KB - 1 of the KB reads hit
-  // that L2 instead of going out to the fabric (r03: layer4.0.conv1 fetched its 84 MB input four times).
+  // grid x = (pixel block, kout block) pairs.  The KB kout blocks of one pixel block read the same input rows: neighbours on one XCD
   const int KB = a.K / BKO, PB = (int)gridDim.x / KB;
-  int pb, kb_i;
-  if ((PB & 7) == 0) {
-    const int w = blockIdx.x, grp = w / (8 * KB), r = w - grp * 8 * KB;
-    pb = grp * 8 + (r & 7); kb_i = r >> 3;
-  } else {
-    kb_i = (int)blockIdx.x / PB; pb = (int)blockIdx.x - kb_i * PB;
-  }
+  const OuterInner oi = xcd_outer_inner(blockIdx.x, PB, KB, true);
+  const int pb = oi.outer, kb_i = oi.inner;
   const int m0 = pb * BP, k0 = kb_i * BKO;
   const int PHW = a.PH * a.PW;
   const int M = a.N * PHW;
@@ -195,7 +174,7 @@ __global__ __launch_bounds__(256, 2) void conv_dma_kernel(const ConvArgs a) {
 #pragma unroll
       for (int t = 0; t < TK; ++t)
 #pragma unroll
-        for (int p = 0; p < TP; ++p) MmaD<T>::run(A[kk][t], B[kk][p], acc[t][p]);
+        for (int p = 0; p < TP; ++p) Mma<T>::run(A[kk][t], B[kk][p], acc[t][p]);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_waitcnt(0x0f70);
     __syncthreads();

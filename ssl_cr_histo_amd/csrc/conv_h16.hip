@@ -28,20 +28,6 @@
 
 namespace sslcr {
 
-template <typename T> struct MmaH;
-template <> struct MmaH<bf16_t> {
-  __device__ static __forceinline__ void run(const u32x4_t& a, const u32x4_t& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  }
-};
-template <> struct MmaH<float> {
-  __device__ static __forceinline__ void run(const u32x4_t& a, const u32x4_t& b, f32x4_t& c) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[e]), __uint_as_float(b[e]), c, 0, 0, 0);
-  }
-};
-
 // inverse of wperm<TK> (common.hpp): LDS row -> kout row of the block
 template <int TK>
 __device__ __forceinline__ int wperm_inv(int rr) {
@@ -52,11 +38,6 @@ __device__ __forceinline__ int wperm_inv(int rr) {
 }
 
 #define SSLCR_WAIT_VM0() __builtin_amdgcn_s_waitcnt(0x0f70) /* vmcnt(0), lgkmcnt/expcnt untouched */
-// A barrier WITHOUT the workgroup fence of __syncthreads() (which is s_waitcnt lgkmcnt(0) first -- a wait for the fragment read
-// issued two MFMAs earlier).  Enough wherever no ds_write is pending and what the barrier orders are (a) this wave's completed DMA
-// (explicit vmcnt(0) in front) or (b) fragment reads whose MFMAs have already been issued, i.e. whose data has arrived.  The
-// "memory" clobber keeps the compiler from moving LDS accesses across it.
-#define SSLCR_BARE_BARRIER() asm volatile("s_barrier" ::: "memory")
 
 // phase timing for tools/microbench/h16_phase_bench.hip (-DSSLCR_H16_PROF; compiled out otherwise): per wave of workgroup 0, shader
 // cycles of a stage spent waiting for the weight DMA, at the publish (P) and free (F) barriers, in the stage-end halo swap and in

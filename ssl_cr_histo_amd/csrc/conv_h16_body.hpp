@@ -60,8 +60,8 @@
   const float relu_lo = a.in_relu ? 0.f : -__builtin_inff();
   const float out_lo = a.relu ? 0.f : -__builtin_inff();
 
-  // XCD-aware walk: blocks land on XCD (blockIdx % 8); each XCD takes a contiguous run of tiles per round so that
-  // neighbouring tiles' shared halo rows hit the same L2.
+  // XCD-aware walk: a contiguous run of tiles per XCD and round.  xcd_run_start() (common.hpp) written out: through the helper the
+  // branches of every instance of this body come out in another order
   const int first = (G & 7) ? lb : (lb & 7) * (G >> 3) + (lb >> 3);
   if (first >= n_items) return;
 
@@ -313,7 +313,7 @@
 #pragma unroll
       for (int t = 0; t < TK; ++t)
 #pragma unroll
-        for (int p = 0; p < TP; ++p) MmaH<T>::run(A[i & 1][t], B[i & 1][p], acc[t][p]);
+        for (int p = 0; p < TP; ++p) Mma<T>::run(A[i & 1][t], B[i & 1][p], acc[t][p]);
       if (i < 17 && sizeof(T) == 2) {
         // bf16: the next step's fragment reads are spread between this step's MFMAs (one read per ~TK*TP/(TK+TP) MFMAs)
         // instead of all being issued first: +2..7 % on every shape (micro-benchmark of the bare loop: +5 %)
@@ -336,7 +336,7 @@
         H16_T(tp0);
         SSLCR_WAIT_VM0();
         H16_T(tp1);
-        SSLCR_BARE_BARRIER();                             // P
+        barrier_bare();                             // P
         H16_T(tp2);
         H16_ACC(0, tp1 - tp0); H16_ACC(1, tp2 - tp1);
         if (i == 8) {
@@ -348,7 +348,7 @@
       }
       if (!WR && (i == 5 || i == 11)) {
         H16_T(tf0);
-        SSLCR_BARE_BARRIER();                             // F (the reads of the released half fed MFMAs that have been issued)
+        barrier_bare();                             // F (the reads of the released half fed MFMAs that have been issued)
         H16_T(tf1);
         H16_ACC(2, tf1 - tf0);
         if (i == 5) dma_w(cur.k0, slab, 6, wb); else dma_w(nxt.k0, nslab, 0, wb ^ 1);
@@ -356,7 +356,7 @@
       }
     }
     H16_T(ts0);
-    SSLCR_BARE_BARRIER();                     // every wave is done with this stage's halo (its last reads fed step 17's MFMAs)
+    barrier_bare();                     // every wave is done with this stage's halo (its last reads fed step 17's MFMAs)
     store_halo();
     __syncthreads();
     H16_T(ts1);

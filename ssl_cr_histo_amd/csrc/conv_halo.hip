@@ -10,20 +10,6 @@
 
 namespace sslcr {
 
-template <typename T> struct MmaH;
-template <> struct MmaH<bf16_t> {
-  __device__ static __forceinline__ void run(const u32x4_t& a, const u32x4_t& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  }
-};
-template <> struct MmaH<float> {
-  __device__ static __forceinline__ void run(const u32x4_t& a, const u32x4_t& b, f32x4_t& c) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[e]), __uint_as_float(b[e]), c, 0, 0, 0);
-  }
-};
-
 template <typename T, int TW, int BKO>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const ConvArgs a) {
   constexpr int EPC = Elem<T>::EPC;
@@ -173,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const ConvArgs a) 
 #pragma unroll
         for (int t = 0; t < TK; ++t)
 #pragma unroll
-          for (int p = 0; p < TP; ++p) MmaH<T>::run(cur[t][kk], bfr[p], acc[t][p]);
+          for (int p = 0; p < TP; ++p) Mma<T>::run(cur[t][kk], bfr[p], acc[t][p]);
       }
     }
     // 9 taps = odd count: the register set holding the next slab's tap 0 alternates; swap so that afA is always "current"

@@ -12,20 +12,6 @@
 
 namespace sslcr {
 
-template <typename T> struct MmaQ;
-template <> struct MmaQ<bf16_t> {
-  __device__ static __forceinline__ void run(const u32x4_t& a, const u32x4_t& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  }
-};
-template <> struct MmaQ<float> {
-  __device__ static __forceinline__ void run(const u32x4_t& a, const u32x4_t& b, f32x4_t& c) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[e]), __uint_as_float(b[e]), c, 0, 0, 0);
-  }
-};
-
 // WK = waves along kouts (2: 512 threads, each wave 64 px x BKO/2 kouts; 1: 256 threads, each wave 64 px x BKO kouts --
 // used for K = 64 so that a wave still owns a 64x64 register tile and LDS reads stay at 16 MAC per byte)
 // ONE = the layer has a single channel slab (C == 64 bf16): no halo prefetch registers are kept across the tap loop
@@ -241,7 +227,7 @@ __global__ __launch_bounds__(256 * WK, 2) void conv3x3_halo256_kernel(const Conv
 #pragma unroll
         for (int t = 0; t < TK; ++t)
 #pragma unroll
-          for (int p = 0; p < TP; ++p) MmaQ<T>::run(af[t], bfr[p], acc[t][p]);
+          for (int p = 0; p < TP; ++p) Mma<T>::run(af[t], bfr[p], acc[t][p]);
       }
       if (tap == 8 && more) {
         __syncthreads();                      // every wave is done with this slab's halo

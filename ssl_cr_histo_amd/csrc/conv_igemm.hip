@@ -17,20 +17,6 @@
 
 namespace sslcr {
 
-template <typename T> struct Mma;
-template <> struct Mma<bf16_t> {
-  __device__ static __forceinline__ void run(const u32x4_t& a, const u32x4_t& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  }
-};
-template <> struct Mma<float> {
-  __device__ static __forceinline__ void run(const u32x4_t& a, const u32x4_t& b, f32x4_t& c) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[e]), __uint_as_float(b[e]), c, 0, 0, 0);
-  }
-};
-
 template <typename T, int BP, int BKO>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a) {
   constexpr int EPC = Elem<T>::EPC;   // elements per 16-byte chunk

@@ -31,10 +31,6 @@ namespace sslcr {
 typedef const __attribute__((address_space(1))) void* gptr_pp;
 typedef __attribute__((address_space(3))) void* lptr_pp;
 
-// LDS visibility + rendezvous without the workgroup-scope fence of __syncthreads(): with global loads and stores in flight the
-// fence becomes s_waitcnt vmcnt(0), i.e. "wait for the halo of the next tile and for the stores of the last one" at every barrier
-#define SSLCR_PP_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
 // phase timing for tools/microbench/pp64_phase_bench.hip (-DSSLCR_PP_PROF): per wave of workgroup 0, shader cycles spent in M, at the
 // barrier behind M, in W, at the barrier behind W
 #ifdef SSLCR_PP_PROF
@@ -94,8 +90,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp64_kernel(const ConvArgs a, 
   const int G = gridDim.x / nseg;
   const int seg = nseg > 1 ? (int)blockIdx.x / G : 0, lb = (int)blockIdx.x - seg * G;
   const int seg_n0 = seg * a.seg_images;
-  // XCD-aware walk (blocks land on XCD blockIdx % 8): each XCD takes a contiguous run of tiles per round
-  const int vb = (G & 7) ? lb : (lb & 7) * (G >> 3) + (lb >> 3);
+  const int vb = xcd_run_start(lb, G);               // XCD-aware walk: a contiguous run of tiles per XCD and round
   const int first0 = 2 * vb;
   if (first0 >= tiles_total) return;
   const int nst = (tiles_total - first0 + 2 * G - 1) / (2 * G);       // stages of group 0 (group 1 may have one live stage less)
@@ -247,12 +242,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp64_kernel(const ConvArgs a, 
   Geo cur = geom(tile_of(0, live));
   load_halo(cur);
   __builtin_amdgcn_s_waitcnt(0x0f70);          // vmcnt(0): the DMA'd filter bank (and this halo)
-  SSLCR_PP_BAR();
+  barrier_lds();
   xform_store();
   Geo nxt = geom(tile_of(1, live_n));
   load_halo(nxt);
-  SSLCR_PP_BAR();
-  if (grp == 1) SSLCR_PP_BAR();                // group 1 idles through group 0's first M phase: from here on the groups alternate
+  barrier_lds();
+  if (grp == 1) barrier_lds();                // group 1 idles through group 0's first M phase: from here on the groups alternate
 
 #ifdef SSLCR_PP_PROF
   unsigned long long pp_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -284,7 +279,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp64_kernel(const ConvArgs a, 
       __builtin_amdgcn_sched_barrier(0);
     }
     PP_T(t1);
-    SSLCR_PP_BAR();                            // every wave of this group is done with its halo buffer
+    barrier_lds();                            // every wave of this group is done with its halo buffer
     PP_T(t2);
     PP_ACC(0, t1 - t0); PP_ACC(1, t2 - t1);
 
@@ -417,7 +412,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp64_kernel(const ConvArgs a, 
     nxt = geom(tile_of(st + 2, live_n));
     load_halo(nxt);
     PP_T(t3);
-    if (!(grp == 1 && st == nst - 1)) SSLCR_PP_BAR();     // this group's new halo is visible to it
+    if (!(grp == 1 && st == nst - 1)) barrier_lds();     // this group's new halo is visible to it
     PP_T(t4);
     PP_ACC(2, t3 - t2); PP_ACC(3, t4 - t3);
   }
@@ -426,7 +421,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp64_kernel(const ConvArgs a, 
     for (int i = 0; i < 8; ++i) g_pp_prof[wave][i] = pp_t[i];
 #endif
   // group 0 idles through group 1's last W phase: that phase's closing barrier is this one, after which both groups' sums are final
-  SSLCR_PP_BAR();
+  barrier_lds();
   if (a.stats) {
     // four partial rows per workgroup, group 0 + group 1 in that order (deterministic); the row count is the one conv3x3_h16
     // would write for this shape (conv_h16_rows: the caller sized the buffer before it knew the dtype), so rows this grid does

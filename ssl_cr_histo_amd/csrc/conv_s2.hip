@@ -35,7 +35,6 @@
 namespace sslcr {
 
 #define S2_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define S2_BARRIER() asm volatile("s_barrier" ::: "memory")
 #ifdef SSLCR_S2_PROF
 __device__ unsigned long long g_s2_prof[8][8];
 #define S2_T(v) const unsigned long long v = __builtin_readcyclecounter()
@@ -67,7 +66,7 @@ __global__ __launch_bounds__(512, 2) void conv_s2_kernel(const ConvArgs a, const
   const int tiles_w = OW / 16, tiles_h = OH / 16;
   const int G = gridDim.x;
   const int lb = blockIdx.x;
-  const int first = (G & 7) ? lb : (lb & 7) * (G >> 3) + (lb >> 3);        // XCD-contiguous runs of tiles, as conv3x3_h16
+  const int first = xcd_run_start(lb, G);        // XCD-contiguous runs of tiles, as conv3x3_h16
   if (first >= n_items) return;
   const int nslabs = a.C / CE;
   const float out_lo = a.relu ? 0.f : -__builtin_inff();
@@ -289,7 +288,7 @@ __global__ __launch_bounds__(512, 2) void conv_s2_kernel(const ConvArgs a, const
       else if ((ITEM_FIRST) && after_epi) S2_WAIT((NPREV) + NST);                                           \
       else S2_WAIT(NPREV);                                                                                  \
       S2_T(tb1);                                                                                            \
-      S2_BARRIER();                                                                                         \
+      barrier_bare();                                                                                         \
       S2_T(tb2);                                                                                            \
       S2_ACC(0, tb1 - tb0); S2_ACC(1, tb2 - tb1);                                                           \
     }                                                                                                       \

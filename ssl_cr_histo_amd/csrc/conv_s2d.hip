@@ -22,7 +22,6 @@
 namespace sslcr {
 
 #define S2D_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define S2D_BARRIER() asm volatile("s_barrier" ::: "memory")
 
 __global__ __launch_bounds__(512, 2) void conv_s2d_kernel(const ConvArgs a, const int tiles_total, const int n_items, const int kshift) {
   typedef bf16_t T;
@@ -44,7 +43,7 @@ __global__ __launch_bounds__(512, 2) void conv_s2d_kernel(const ConvArgs a, cons
   const int tiles_w = IW / 16, tiles_h = IH / 16;
   const int G = gridDim.x;
   const int lb = blockIdx.x;
-  const int first = (G & 7) ? lb : (lb & 7) * (G >> 3) + (lb >> 3);
+  const int first = xcd_run_start(lb, G);
   if (first >= n_items) return;
   const int nslabs = a.C / CE;
 
@@ -206,7 +205,7 @@ __global__ __launch_bounds__(512, 2) void conv_s2d_kernel(const ConvArgs a, cons
     if ((NPREV_HALO) && prev_halo) { if ((ITEM_FIRST) && after_epi) S2D_VMCNT(20); else S2D_VMCNT(4); }     \
     else if ((ITEM_FIRST) && after_epi) S2D_VMCNT(16);                                                      \
     else S2D_VMCNT(0);                                                                                      \
-    S2D_BARRIER();                                                                                          \
+    barrier_bare();                                                                                          \
     if (ITEM_FIRST) after_epi = false;                                                                      \
     wc_next();                                                                                              \
     if (wc.valid) issue_w(wc.c0, wc.slab, wc.grp, ws == 0 ? 2 : ws - 1);                                    \

@@ -12,8 +12,6 @@
 
 namespace sslcr {
 
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-
 template <typename T> struct WgFrag;
 template <> struct WgFrag<bf16_t> {
   static constexpr int PS = 32;          // pixels per step = one 16x16x32 MFMA depth
@@ -26,11 +24,7 @@ template <> struct WgFrag<bf16_t> {
   __device__ static __forceinline__ bf16x8_t load(const char* tile, int col0, int li, int g) {
     const int pl = 16 * (g >> 1) + 4 * (g & 1) + (li >> 2);
     const char* p = tile + pl * 128 + (((col0 >> 4) ^ ((pl >> 1) & 3)) << 5) + (li & 3) * 8;
-    s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p));
-    s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p + 8 * 128));
-    typedef short s16x8_t __attribute__((ext_vector_type(8)));
-    s16x8_t v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8_t, v);
+    return tr_pair(p, p + 8 * 128);
   }
 };
 
@@ -54,13 +48,8 @@ __global__ __launch_bounds__(256 * KH, 2) void wgrad_kernel(const WgradArgs a, i
   // grid x = (kout block, cin block, pixel split) triples, the gx * gy workgroups of one pixel split neighbours on one XCD
   // (wgrad_halo.hip): their re-reads of the same dY / X rows hit its L2
   const int gx = a.K / (64 * KH), gy = a.C / 64, GT = gx * gy, nsplit = (int)gridDim.x / GT;
-  int bz, bt;
-  if ((nsplit & 7) == 0) {
-    const int w = blockIdx.x, grp = w / (8 * GT), r = w - grp * 8 * GT;
-    bz = grp * 8 + (r & 7); bt = r >> 3;
-  } else {
-    bz = (int)blockIdx.x / GT; bt = (int)blockIdx.x - bz * GT;
-  }
+  const OuterInner oi = xcd_outer_inner(blockIdx.x, nsplit, GT, false);
+  const int bz = oi.outer, bt = oi.inner;
   const int by = bt / gx, bx = bt - by * gx;
   const int k0 = bx * (64 * KH), c0 = by * 64;
   const int OHW = a.OH * a.OW;

@@ -8,15 +8,14 @@
 // carry zero weights: 147 useful of 224 MACs).  Workgroups are persistent over tiles: the 28 KiB packed weight block
 // is staged once, and BatchNorm (sum, sumsq) partials are accumulated in registers across tiles.
 #include "kernels.hpp"
+#include "stem_halo.hpp"
 #include <type_traits>
 
 namespace sslcr {
 
 constexpr int TH = 8, TW = 16;                 // output tile
 constexpr int HR = 2 * TH + 5;                 // 21 halo rows
-constexpr int HC = 2 * TW + 6;                 // 38 halo cols (even, covers the zero-weight tap s=7)
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef short s16x8_t __attribute__((ext_vector_type(8)));
+constexpr int HC = STEM_HC;                    // 38 halo cols
 
 static int stem_grid(int N, int OH, int OW) {
   const int tiles = N * cdiv(OH, TH) * cdiv(OW, TW);
@@ -43,17 +42,7 @@ __device__ __forceinline__ void stem_load_halo(T* halo, const void* xv, int n, i
 // Split halo staging for the forward kernel: issue() puts the next tile's input bytes in flight (one value per role, roles
 // fixed per thread), commit() converts and writes them into the OTHER LDS halo buffer after the current tile's MFMAs --
 // the HBM latency of the planar uint8 gather hides under compute instead of sitting between two barriers.
-// kout owned by MFMA tile t, fragment row group q (= lane>>2 for the A fragment, lane>>4 for the accumulator), element j:
-// a lane's 16 channels form two 8-channel runs 32 channels apart, so the four lane groups of one pixel write contiguous
-// 64-byte segments (16 consecutive channels per lane would leave every 16-byte store half of a 32-byte stride)
-#define STEM_CH(t, q, j) ((((t) >> 1) * 32) + ((q) * 8) + (((t) & 1) * 4) + (j))
 constexpr int STEM_NEL = (3 * HR * HC + 255) / 256;     // 10 values per thread
-// Image n of a (possibly two-segment) input batch: the reference's torch.cat((inputs_x, inputs_u_s)) is an address select here.
-template <typename A>
-__device__ __forceinline__ const void* stem_seg(const A& a, int& n) {
-  if (a.x2 && n >= a.n_split) { n -= a.n_split; return a.x2; }
-  return a.x;
-}
 template <bool INF32>
 __device__ __forceinline__ void stem_issue(float (&pv)[STEM_NEL], const int (&role)[STEM_NEL], const void* xv, int n, int H, int W,
                                            int hi0, int wi0) {
@@ -81,25 +70,7 @@ __device__ __forceinline__ void stem_commit(T* halo, const float (&pv)[STEM_NEL]
     }
 }
 
-// uint8 fast path (W % 4 == 0): the halo window starts 3 pixels left of a 32-pixel boundary, so the aligned dwords from
-// one pixel further left cover it exactly: thread (row rr = tid/10, dword d = tid%10) of the first 210 loads ONE dword per
-// colour plane = 4 pixels x 3 channels, and writes them as four 8-byte (c0,c1,c2,0) pixels.  12 bytes per load-triple and
-// 4 LDS stores per thread per tile instead of 10 byte loads + 10 two-byte stores with per-element address arithmetic.
-struct StemRaw { uint32_t d[3]; };
-__device__ __forceinline__ StemRaw stem_issue4(const void* xv, int n, int H, int W, int hi0, int wi0, int tid = threadIdx.x) {
-  StemRaw r{{0u, 0u, 0u}};
-  if (tid < HR * 10) {
-    const int rr = tid / 10, d = tid - rr * 10;
-    const int h = hi0 + rr, w = wi0 - 1 + 4 * d;
-    if (h >= 0 && h < H && w >= 0 && w < W) {
-      const uint8_t* p = reinterpret_cast<const uint8_t*>(xv) + ((size_t)(n * 3) * H + h) * W + w;
-      const size_t plane = (size_t)H * W;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) r.d[c] = *reinterpret_cast<const uint32_t*>(p + c * plane);
-    }
-  }
-  return r;
-}
+// the commit of stem_issue4 (stem_halo.hpp)
 template <typename T>
 __device__ __forceinline__ void stem_commit4(T* halo, const StemRaw& r, int tid = threadIdx.x) {
   if (tid >= HR * 10) return;
@@ -163,7 +134,7 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const StemArgs a, int til
   }
   __syncthreads();
   int cur = 0;
-  // XCD-aware walk (workgroups land on XCD blockIdx % 8): each XCD takes a contiguous run of tiles per round, so that neighbouring
+  // XCD-aware walk, xcd_run_start() written out (through the helper this kernel's branches come out in another order): neighbouring
   // tiles' shared halo columns -- and the 64-byte sectors that a 37-byte uint8 row segment only partly uses -- hit one L2
   const int G = gridDim.x;
   const int vb = (G & 7) ? (int)blockIdx.x : (int)(blockIdx.x & 7) * (G >> 3) + (int)(blockIdx.x >> 3);
@@ -173,7 +144,7 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const StemArgs a, int til
     int ns = n;
     const void* xseg = stem_seg(a, ns);
     if (fast) {
-      raw = stem_issue4(xseg, ns, a.H, a.W, 2 * (rem / tiles_w) * TH - 3, 2 * (rem % tiles_w) * TW - 3);
+      raw = stem_issue4<HR>(xseg, ns, a.H, a.W, 2 * (rem / tiles_w) * TH - 3, 2 * (rem % tiles_w) * TW - 3);
       stem_commit4<T>(halo0, raw);
     } else {
       stem_issue<INF32>(pv, role, xseg, ns, a.H, a.W, 2 * (rem / tiles_w) * TH - 3, 2 * (rem % tiles_w) * TW - 3);
@@ -198,7 +169,7 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const StemArgs a, int til
       int nn = nxt / (tiles_h * tiles_w);
       const int nrem = nxt - nn * tiles_h * tiles_w;
       const void* xseg = stem_seg(a, nn);
-      if (fast) raw = stem_issue4(xseg, nn, a.H, a.W, 2 * (nrem / tiles_w) * TH - 3, 2 * (nrem % tiles_w) * TW - 3);
+      if (fast) raw = stem_issue4<HR>(xseg, nn, a.H, a.W, 2 * (nrem / tiles_w) * TH - 3, 2 * (nrem % tiles_w) * TW - 3);
       else stem_issue<INF32>(pv, role, xseg, nn, a.H, a.W, 2 * (nrem / tiles_w) * TH - 3, 2 * (nrem % tiles_w) * TW - 3);
     }
 
@@ -403,7 +374,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradArgs a, 
     if (fast) {
       int ns = n;
       const void* xseg = stem_seg(a, ns);
-      raw = stem_issue4(xseg, ns, a.H, a.W, 2 * ho0 - 3, 2 * wo0 - 3);
+      raw = stem_issue4<HR>(xseg, ns, a.H, a.W, 2 * ho0 - 3, 2 * wo0 - 3);
     }
     if constexpr (POOL) {
       const char* xg = reinterpret_cast<const char*>(b.x);
@@ -524,9 +495,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradArgs a, 
       if constexpr (BF) {
         // A: dY^T, kouts 16*wave + li, pixels 8g..8g+7
         const char* pa = ystep + (8 * g + (li >> 2)) * RB + (16 * wave + (li & 3) * 4) * 2;
-        s16x4_t alo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(pa));
-        s16x4_t ahi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(pa + 4 * RB));
-        const bf16x8_t af = __builtin_bit_cast(bf16x8_t, (s16x8_t)__builtin_shufflevector(alo, ahi, 0, 1, 2, 3, 4, 5, 6, 7));
+        const bf16x8_t af = tr_pair(pa, pa + 4 * RB);
         // this lane's source pixels for the transpose read: j = li>>2 (+4), feature quad q = li&3
         const int p0 = step * PS + 8 * g + (li >> 2), p1 = p0 + 4;
         const int h0 = 2 * (p0 / TW), w0 = 2 * (p0 % TW), h1 = 2 * (p1 / TW), w1 = 2 * (p1 % TW);
@@ -535,10 +504,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradArgs a, 
           const int r = f >> 1, s0 = (f & 1) * 4;
           const char* b0 = reinterpret_cast<const char*>(halo) + (((h0 + r) * HC + w0 + s0 + (li & 3)) * 4) * 2;
           const char* b1 = reinterpret_cast<const char*>(halo) + (((h1 + r) * HC + w1 + s0 + (li & 3)) * 4) * 2;
-          s16x4_t blo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(b0));
-          s16x4_t bhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(b1));
-          const bf16x8_t bfrag = __builtin_bit_cast(bf16x8_t, (s16x8_t)__builtin_shufflevector(blo, bhi, 0, 1, 2, 3, 4, 5, 6, 7));
-          acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfrag, acc[f], 0, 0, 0);
+          acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, tr_pair(b0, b1), acc[f], 0, 0, 0);
         }
       } else {
 #pragma unroll
@@ -600,27 +566,9 @@ constexpr int P2_STAGE = P2_DUMP + 1024;
 constexpr int P2_NS = 5;
 constexpr int P2_HBUF = HR * HC * 4 * 2;
 
-// LDS transpose read as inline asm.  Through the intrinsic, the compiler's wait-count pass (no usable memory operand on it) puts
-// s_waitcnt vmcnt(0) in front of every such read while ANY global_load_lds is outstanding -- which drains the three tiles of DMA
-// this kernel keeps in flight (plain ds_read_b128 after global_load_lds, conv_dma.hip, does not get that wait).  The asm is
-// opaque to that pass, so the LDS counter is handled by hand next to the reads (see the MFMA loop).
-template <int OFF>
-__device__ __forceinline__ u32x2_t p2_tr16(uint32_t addr) {
-  u32x2_t v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-__device__ __forceinline__ uint32_t p2_lds_addr(const void* p) {
-  return (uint32_t)(size_t)(__attribute__((address_space(3))) const char*)(const char*)p;
-}
-// Workgroup barrier that leaves the vector-memory counter alone: __syncthreads() is a workgroup-scope fence, which the compiler
-// lowers to s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier -- and vmcnt(0) here means "wait for the three tiles of DMA in flight".
-// What crosses this barrier between waves is LDS data only; the DMA writes it publishes were waited for explicitly.
-__device__ __forceinline__ void p2_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// The transpose reads are the inline-asm form (lds_tr16, common.hpp: three tiles of global_load_lds stay in flight) and the barrier
+// of the tile loops is barrier_lds(): the DMA writes it publishes were waited for explicitly.
 #define P2_BOFF(f) ((((f) >> 1) * HC + ((f) & 1) * 4) * 8)
-__device__ __forceinline__ bf16x8_t p2_frag(const u32x2_t& lo, const u32x2_t& hi) {
-  return __builtin_bit_cast(bf16x8_t, u32x4_t{lo[0], lo[1], hi[0], hi[1]});
-}
 
 template <bool INF32>
 __global__ __launch_bounds__(768) void stem_wgrad_pool2_kernel(const StemWgradArgs a, const BnBwdArgs b, int tiles_h, int tiles_w, int ntiles,
@@ -799,7 +747,7 @@ __global__ __launch_bounds__(768) void stem_wgrad_pool2_kernel(const StemWgradAr
     int n = tile / (tiles_h * tiles_w);
     const int rem = tile - n * tiles_h * tiles_w;
     const void* xseg = stem_seg(a, n);
-    return stem_issue4(xseg, n, a.H, a.W, 2 * (rem / tiles_w) * TH - 3, 2 * (rem % tiles_w) * TW - 3, pt);
+    return stem_issue4<HR>(xseg, n, a.H, a.W, 2 * (rem / tiles_w) * TH - 3, 2 * (rem % tiles_w) * TW - 3, pt);
   };
   auto halo_commit = [&](int tile, int buf, const StemRaw& raw) {
     T* hl = reinterpret_cast<T*>(halo_base + buf * P2_HBUF);
@@ -816,7 +764,7 @@ __global__ __launch_bounds__(768) void stem_wgrad_pool2_kernel(const StemWgradAr
 
   // XCD-aware walk like stem_fwd_kernel: an XCD takes a contiguous run of tiles per round (shared image halos and pooling windows)
   const int gs = gridDim.x;
-  const int t0 = (gs & 7) ? (int)blockIdx.x : (int)(blockIdx.x & 7) * (gs >> 3) + (int)(blockIdx.x >> 3);
+  const int t0 = xcd_run_start<unsigned>(blockIdx.x, gs);
   __syncthreads();                    // halo zero fill
   if (matrix) {
     if (t0 < ntiles) dma(t0, stage(0));
@@ -846,7 +794,7 @@ __global__ __launch_bounds__(768) void stem_wgrad_pool2_kernel(const StemWgradAr
         apply_tile(nxt, stage(i5 + 1 < P2_NS ? i5 + 1 : 0));
         halo_commit(nxt, cur ^ 1, r);
       }
-      p2_barrier();
+      barrier_lds();
       cur ^= 1;
       i5 = i5 + 1 < P2_NS ? i5 + 1 : 0;
     }
@@ -865,28 +813,28 @@ __global__ __launch_bounds__(768) void stem_wgrad_pool2_kernel(const StemWgradAr
 #pragma unroll 1
       for (int step = 0; step < TH * TW / 32; ++step) {
         // A: dY^T, kouts 16*wave + li, pixels 8g..8g+7; B: this lane's source pixels j = li>>2 (+4), feature quad li&3
-        const uint32_t pa = p2_lds_addr(sA + step * 32 * RB + (8 * g + (li >> 2)) * RB + (16 * wave + (li & 3) * 4) * 2);
+        const uint32_t pa = lds_addr(sA + step * 32 * RB + (8 * g + (li >> 2)) * RB + (16 * wave + (li & 3) * 4) * 2);
         const int p0 = step * 32 + 8 * g + (li >> 2), p1 = p0 + 4;
-        const uint32_t q0 = p2_lds_addr(halo + ((2 * (p0 / TW) * HC + 2 * (p0 % TW) + (li & 3)) * 4) * 2);
-        const uint32_t q1 = p2_lds_addr(halo + ((2 * (p1 / TW) * HC + 2 * (p1 % TW) + (li & 3)) * 4) * 2);
-        u32x2_t alo = p2_tr16<0>(pa), ahi = p2_tr16<4 * RB>(pa);
+        const uint32_t q0 = lds_addr(halo + ((2 * (p0 / TW) * HC + 2 * (p0 % TW) + (li & 3)) * 4) * 2);
+        const uint32_t q1 = lds_addr(halo + ((2 * (p1 / TW) * HC + 2 * (p1 % TW) + (li & 3)) * 4) * 2);
+        u32x2_t alo = lds_tr16<0>(pa), ahi = lds_tr16<4 * RB>(pa);
         // the 7 MFMA pairs of a step run three register sets deep: while pair k multiplies, the reads of pairs k+1 and k+2 are in
         // flight (LDS latency ~130 cycles against 32 cycles of MFMA per pair).  LDS reads return in order, so "pair k has
         // arrived" is s_waitcnt lgkmcnt(<reads issued after it>); the wait names pair k's registers, which orders its MFMAs
         // behind it
         u32x2_t x0, x1, x2, x3, y0, y1, y2, y3, z0, z1, z2, z3;
 #define P2_RD(f, r0, r1, r2, r3)                                                                       \
-        r0 = p2_tr16<P2_BOFF(f)>(q0); r1 = p2_tr16<P2_BOFF(f)>(q1);                                    \
-        r2 = p2_tr16<P2_BOFF(f + 1)>(q0); r3 = p2_tr16<P2_BOFF(f + 1)>(q1);
+        r0 = lds_tr16<P2_BOFF(f)>(q0); r1 = lds_tr16<P2_BOFF(f)>(q1);                                    \
+        r2 = lds_tr16<P2_BOFF(f + 1)>(q0); r3 = lds_tr16<P2_BOFF(f + 1)>(q1);
 #define P2_MM(f, r0, r1, r2, r3)                                                                       \
-        acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, p2_frag(r0, r1), acc[f], 0, 0, 0);       \
-        acc[f + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, p2_frag(r2, r3), acc[f + 1], 0, 0, 0);
+        acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, frag_join(r0, r1), acc[f], 0, 0, 0);       \
+        acc[f + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, frag_join(r2, r3), acc[f + 1], 0, 0, 0);
 #define P2_WAIT(n, r0, r1, r2, r3) asm volatile("s_waitcnt lgkmcnt(" #n ")" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3));
         P2_RD(0, x0, x1, x2, x3)
         P2_RD(2, y0, y1, y2, y3)
         P2_RD(4, z0, z1, z2, z3)
         asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(alo), "+v"(ahi), "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3));
-        const bf16x8_t af = p2_frag(alo, ahi);
+        const bf16x8_t af = frag_join(alo, ahi);
         P2_MM(0, x0, x1, x2, x3)   P2_RD(6, x0, x1, x2, x3)
         P2_WAIT(8, y0, y1, y2, y3) P2_MM(2, y0, y1, y2, y3)   P2_RD(8, y0, y1, y2, y3)
         P2_WAIT(8, z0, z1, z2, z3) P2_MM(4, z0, z1, z2, z3)   P2_RD(10, z0, z1, z2, z3)
@@ -903,7 +851,7 @@ __global__ __launch_bounds__(768) void stem_wgrad_pool2_kernel(const StemWgradAr
       if (nx4 < ntiles) __builtin_amdgcn_s_waitcnt(0x0f70 | 14);   // vmcnt(14)
       else __builtin_amdgcn_s_waitcnt(0x0f70);
     }
-    p2_barrier();
+    barrier_lds();
     cur ^= 1;
     i5 = i5 + 1 < P2_NS ? i5 + 1 : 0;
   }

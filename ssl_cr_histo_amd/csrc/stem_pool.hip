@@ -19,43 +19,19 @@
 #include <stdlib.h>
 
 #include "kernels.hpp"
+#include "stem_halo.hpp"
 
 namespace sslcr {
 
 namespace {
 constexpr int SP_TH = 16, SP_TW = 16;                // conv-output tile
 constexpr int SP_HR = 2 * SP_TH + 5;                 // 37 input halo rows
-constexpr int SP_HC = 2 * SP_TW + 6;                 // 38 input halo columns (even; covers the zero-weight tap s = 7)
+constexpr int SP_HC = STEM_HC;                       // 38 input halo columns
 constexpr int SP_NT = 512;
 constexpr int SP_WROW = 224 * 2;                     // bytes per packed weight row (bf16), unpadded + swizzled as in stem_fwd_kernel
 constexpr int SP_PP = 17 * 17 * 128;                 // one plane P: [17 rows][17 cols][64 ch bf16]
-// kout owned by MFMA tile t, accumulator row group q, element j (stem.hip STEM_CH): two 8-channel runs 32 channels apart
-#define SP_CH(t, q, j) ((((t) >> 1) * 32) + ((q) * 8) + (((t) & 1) * 4) + (j))
-
-typedef short s16x8_t __attribute__((ext_vector_type(8)));
-
-struct SpRaw { uint32_t d[3]; };
-
-__device__ __forceinline__ const void* sp_seg(const StemArgs& a, int& n) {
-  if (a.x2 && n >= a.n_split) { n -= a.n_split; return a.x2; }
-  return a.x;
-}
-// uint8 fast path (W % 4 == 0): thread (row rr = tid / 10, dword d = tid % 10) of the first 370 loads one aligned dword per colour plane
-__device__ __forceinline__ SpRaw sp_issue4(const void* xv, int n, int H, int W, int hi0, int wi0, int tid) {
-  SpRaw r{{0u, 0u, 0u}};
-  if (tid < SP_HR * 10) {
-    const int rr = tid / 10, d = tid - rr * 10;
-    const int h = hi0 + rr, w = wi0 - 1 + 4 * d;
-    if (h >= 0 && h < H && w >= 0 && w < W) {
-      const uint8_t* p = reinterpret_cast<const uint8_t*>(xv) + ((size_t)(n * 3) * H + h) * W + w;
-      const size_t plane = (size_t)H * W;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) r.d[c] = *reinterpret_cast<const uint32_t*>(p + c * plane);
-    }
-  }
-  return r;
-}
-__device__ __forceinline__ void sp_commit4(bf16_t* halo, const SpRaw& r, int tid) {
+// the commit of stem_issue4<SP_HR>, in this kernel's own instruction order (stem_halo.hpp)
+__device__ __forceinline__ void sp_commit4(bf16_t* halo, const StemRaw& r, int tid) {
   if (tid >= SP_HR * 10) return;
   const int rr = tid / 10, d = tid - rr * 10;
 #pragma unroll
@@ -71,7 +47,8 @@ __device__ __forceinline__ void sp_commit4(bf16_t* halo, const SpRaw& r, int tid
     *reinterpret_cast<u32x2_t*>(halo + (rr * SP_HC + cc) * 4) = u32x2_t{lo, hi};
   }
 }
-// generic path (fp32 input, odd widths): element by element, synchronous
+// generic path (fp32 input, odd widths): element by element, synchronous (stem.hip's stem_load_halo for 37 rows and 512 threads, value
+// formed before the address: see stem_halo.hpp for why it is a copy)
 template <bool INF32>
 __device__ __forceinline__ void sp_load_halo(bf16_t* halo, const void* xv, int n, int H, int W, int hi0, int wi0, int tid) {
   for (int idx = tid; idx < 3 * SP_HR * SP_HC; idx += SP_NT) {
@@ -120,8 +97,8 @@ __global__ __launch_bounds__(SP_NT) void stem_pool_fwd_kernel(const StemArgs a, 
   float bias[16], osc[16];                   // osc: sslcr_stem_desc.out_scale (1 where the BatchNorm scale sits in the filters: x * 1 + b is x + b)
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
-    bias[j] = a.bias ? a.bias[SP_CH(j >> 2, g, j & 3)] : 0.f;
-    osc[j] = a.out_scale ? a.out_scale[SP_CH(j >> 2, g, j & 3)] : 1.f;
+    bias[j] = a.bias ? a.bias[STEM_CH(j >> 2, g, j & 3)] : 0.f;
+    osc[j] = a.out_scale ? a.out_scale[STEM_CH(j >> 2, g, j & 3)] : 1.f;
   }
   __syncthreads();
 
@@ -135,14 +112,14 @@ __global__ __launch_bounds__(SP_NT) void stem_pool_fwd_kernel(const StemArgs a, 
   };
   const int n_imgs = (a.N - n_first + (int)gridDim.x - 1) / (int)gridDim.x;
   const int n_items = n_imgs * tiles_img;
-  SpRaw raw{{0u, 0u, 0u}};
+  StemRaw raw{{0u, 0u, 0u}};
   int cur = 0;
   {
     int n, tb, tc;
     origin(0, n, tb, tc);
     int ns = n;
-    const void* xseg = sp_seg(a, ns);
-    if (fast) { raw = sp_issue4(xseg, ns, a.H, a.W, 2 * tb * SP_TH - 3, 2 * tc * SP_TW - 3, tid); sp_commit4(halo0, raw, tid); }
+    const void* xseg = stem_seg(a, ns);
+    if (fast) { raw = stem_issue4<SP_HR>(xseg, ns, a.H, a.W, 2 * tb * SP_TH - 3, 2 * tc * SP_TW - 3, tid); sp_commit4(halo0, raw, tid); }
     else sp_load_halo<INF32>(halo0, xseg, ns, a.H, a.W, 2 * tb * SP_TH - 3, 2 * tc * SP_TW - 3, tid);
   }
   __syncthreads();
@@ -159,8 +136,8 @@ __global__ __launch_bounds__(SP_NT) void stem_pool_fwd_kernel(const StemArgs a, 
       origin(item + 1, nn, ntb, ntc);
       if (fast) {
         int ns = nn;
-        const void* xseg = sp_seg(a, ns);
-        raw = sp_issue4(xseg, ns, a.H, a.W, 2 * ntb * SP_TH - 3, 2 * ntc * SP_TW - 3, tid);
+        const void* xseg = stem_seg(a, ns);
+        raw = stem_issue4<SP_HR>(xseg, ns, a.H, a.W, 2 * ntb * SP_TH - 3, 2 * ntc * SP_TW - 3, tid);
       }
     }
     // ---- conv tile: wave w owns output rows 2w, 2w+1 (x 16 columns x 64 kouts); K = (r, s8, c4) as in stem_fwd_kernel
@@ -174,7 +151,7 @@ __global__ __launch_bounds__(SP_NT) void stem_pool_fwd_kernel(const StemArgs a, 
       u32x4_t af[4], bfr[2];
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const int k = SP_CH(t, li >> 2, li & 3);
+        const int k = STEM_CH(t, li >> 2, li & 3);
         af[t] = ld16(w_lds + k * SP_WROW + (r * 8 + 2 * (g ^ ((li >> 3) << 1))) * 4 * 2);
       }
 #pragma unroll
@@ -207,7 +184,7 @@ __global__ __launch_bounds__(SP_NT) void stem_pool_fwd_kernel(const StemArgs a, 
       if (fast) sp_commit4(halo0 + (cur ^ 1) * (SP_HR * SP_HC * 4), raw, tid);
       else {
         int ns = nn;
-        const void* xseg = sp_seg(a, ns);
+        const void* xseg = stem_seg(a, ns);
         sp_load_halo<INF32>(halo0 + (cur ^ 1) * (SP_HR * SP_HC * 4), xseg, ns, a.H, a.W, 2 * ntb * SP_TH - 3, 2 * ntc * SP_TW - 3, tid);
       }
     }

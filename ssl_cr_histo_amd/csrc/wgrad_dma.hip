@@ -23,17 +23,6 @@
 namespace sslcr {
 
 namespace {
-template <int OFF>
-__device__ __forceinline__ u32x2_t wd_tr(uint32_t addr) {
-  u32x2_t v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-__device__ __forceinline__ uint32_t wd_lds(const void* p) { return (uint32_t)(size_t)(__attribute__((address_space(3))) const char*)(const char*)p; }
-__device__ __forceinline__ bf16x8_t wd_frag(const u32x2_t& lo, const u32x2_t& hi) {
-  return __builtin_bit_cast(bf16x8_t, u32x4_t{lo[0], lo[1], hi[0], hi[1]});
-}
-__device__ __forceinline__ void wd_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 constexpr int WD_RB = 128;                         // LDS bytes per pixel row (64 bf16 channels)
 __device__ __forceinline__ int wd_swz(int row) { return (row >> 1) & 3; }
 // logical 16-byte chunk that lives in physical slot j of row `row` (the XOR swizzle of wgrad_halo.hip is its own inverse)
@@ -45,15 +34,15 @@ __device__ __forceinline__ void wd_issue_b(u32x2_t (&b)[2], const uint32_t (&bba
   constexpr int PITCH = TW == 16 ? 24 : 16, HH = 10;
   constexpr int HPIX = TW == 16 ? Q * 2 * PITCH : (Q >> 1) * (HH * PITCH) + ((4 * Q) & 7) * PITCH;
   constexpr int OFF = (HPIX + (T / 3) * PITCH) * WD_RB, HI = (TW == 16 ? 8 : PITCH) * WD_RB;
-  b[0] = wd_tr<OFF>(bbase[T % 3]);
-  b[1] = wd_tr<OFF + HI>(bbase[T % 3]);
+  b[0] = lds_tr16<OFF>(bbase[T % 3]);
+  b[1] = lds_tr16<OFF + HI>(bbase[T % 3]);
 }
 template <int Q>
 __device__ __forceinline__ void wd_issue_a(u32x2_t (&alo)[4], u32x2_t (&ahi)[4], const uint32_t (&abase)[4]) {
 #pragma unroll
   for (int t4 = 0; t4 < 4; ++t4) {
-    alo[t4] = wd_tr<Q * 32 * WD_RB>(abase[t4]);
-    ahi[t4] = wd_tr<Q * 32 * WD_RB + 8 * WD_RB>(abase[t4]);
+    alo[t4] = lds_tr16<Q * 32 * WD_RB>(abase[t4]);
+    ahi[t4] = lds_tr16<Q * 32 * WD_RB + 8 * WD_RB>(abase[t4]);
   }
 }
 template <int N>
@@ -109,10 +98,10 @@ __device__ __forceinline__ void wd_tap(f32x4_t (&acc)[9][4], u32x2_t (&alo)[2][4
   if constexpr (T == 0) wd_wait10<CNT>(alo[AI], ahi[AI], bf[TAU % (D + 1)][0], bf[TAU % (D + 1)][1]);
   else wd_wait2<CNT>(bf[TAU % (D + 1)][0], bf[TAU % (D + 1)][1]);
   __builtin_amdgcn_sched_barrier(0);
-  const bf16x8_t b = wd_frag(bf[TAU % (D + 1)][0], bf[TAU % (D + 1)][1]);
+  const bf16x8_t b = frag_join(bf[TAU % (D + 1)][0], bf[TAU % (D + 1)][1]);
 #pragma unroll
   for (int t4 = 0; t4 < 4; ++t4)
-    acc[T][t4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wd_frag(alo[AI][t4], ahi[AI][t4]), b, acc[T][t4], 0, 0, 0);
+    acc[T][t4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_join(alo[AI][t4], ahi[AI][t4]), b, acc[T][t4], 0, 0, 0);
   __builtin_amdgcn_sched_barrier(0);
 }
 template <int TW, int D, bool ADBL, int TAU0, int N, typename NX>
@@ -149,13 +138,8 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_dma_kernel(const WgradArgs a,
   const int wave = wave8 & 3, kh = tid >> 8;              // cin tile, kout half
   const int li = lane & 15, g = lane >> 4;
   const int gx = a.K / 128, gy = a.C / 64, GT = gx * gy, splits = (int)gridDim.x / GT;
-  int bz, bt;
-  if ((splits & 7) == 0) {                                // the gx * gy workgroups of one pixel split: neighbours on one XCD
-    const int w = blockIdx.x, grp = w / (8 * GT), r = w - grp * 8 * GT;
-    bz = grp * 8 + (r & 7); bt = r >> 3;
-  } else {
-    bz = (int)blockIdx.x / GT; bt = (int)blockIdx.x - bz * GT;
-  }
+  const OuterInner oi = xcd_outer_inner(blockIdx.x, splits, GT, false);
+  const int bz = oi.outer, bt = oi.inner;
   const int by = bt / gx, bx = bt - by * gx;
   const int k0 = bx * 128, c0 = by * 64;
   const int chunk = tid % CPR, prow = tid / CPR;          // register-staged halo role (XF)
@@ -323,11 +307,11 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_dma_kernel(const WgradArgs a,
   const int pl = 16 * (g >> 1) + 4 * (g & 1) + (li >> 2);
   uint32_t aoff[4], boff[3];
 #pragma unroll
-  for (int t4 = 0; t4 < 4; ++t4) aoff[t4] = wd_lds(smem) + kh * YH + pl * RB + ((t4 ^ wd_swz(pl)) << 5) + (li & 3) * 8;
+  for (int t4 = 0; t4 < 4; ++t4) aoff[t4] = lds_addr(smem) + kh * YH + pl * RB + ((t4 ^ wd_swz(pl)) << 5) + (li & 3) * 8;
 #pragma unroll
   for (int sx = 0; sx < 3; ++sx) {
     const int hp = hpix(pl) + sx;
-    boff[sx] = wd_lds(smem) + YBUF + hp * RB + ((wave ^ wd_swz(hp)) << 5) + (li & 3) * 8;
+    boff[sx] = lds_addr(smem) + YBUF + hp * RB + ((wave ^ wd_swz(hp)) << 5) + (li & 3) * 8;
   }
   constexpr int D = 1;                         // B fragments one tap ahead (two or three taps, and the next depth step's A fragments
   constexpr bool ADBL = false;                 // at tap 4, measured the same: NOTES r05)
@@ -339,7 +323,7 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_dma_kernel(const WgradArgs a,
     store_halo(0);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  wd_barrier();
+  barrier_lds();
   int buf = 0;
   for (int tile = t_begin; tile < t_end; ++tile) {
     const bool more = tile + 1 < t_end;
@@ -361,7 +345,7 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_dma_kernel(const WgradArgs a,
       if (more) store_halo(buf ^ 1);            // the compiler's wait for hreg also retires the (older) DMA requests
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    wd_barrier();
+    barrier_lds();
     buf ^= 1;
   }
 

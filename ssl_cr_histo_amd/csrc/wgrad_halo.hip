@@ -13,16 +13,6 @@
 
 namespace sslcr {
 
-typedef short h16x4_t __attribute__((ext_vector_type(4)));
-typedef short h16x8_t __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ bf16x8_t tr_pair(const char* p0, const char* p1) {
-  h16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) h16x4_t*)(p0));
-  h16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) h16x4_t*)(p1));
-  h16x8_t v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8_t, v);
-}
-
 // KH = 1: a workgroup of four waves owns a 64(kout) x 64(cin) block, two workgroups share a CU and cover each other's staging
 //      phases (single LDS buffer).
 // KH = 2 (bf16, K % 128 == 0): eight waves own a 128(kout) x 64(cin) block -- wave = (cin tile, kout half).  The input halo
@@ -61,13 +51,8 @@ __global__ __launch_bounds__(256 * KH, 2) void wgrad3x3_halo_kernel(const WgradA
   // (each its own channel slice, but a dY row is re-read by every cin block and an X row by every kout block): they are made
   // neighbours on one XCD (linear ids w, w + 8, ...; workgroups land on XCD id % 8) so that those re-reads hit its L2
   const int gx = a.K / (64 * KH), gy = a.C / 64, GT = gx * gy, splits = (int)gridDim.x / GT;
-  int bz, bt;
-  if ((splits & 7) == 0) {
-    const int w = blockIdx.x, grp = w / (8 * GT), r = w - grp * 8 * GT;
-    bz = grp * 8 + (r & 7); bt = r >> 3;
-  } else {
-    bz = (int)blockIdx.x / GT; bt = (int)blockIdx.x - bz * GT;
-  }
+  const OuterInner oi = xcd_outer_inner(blockIdx.x, splits, GT, false);
+  const int bz = oi.outer, bt = oi.inner;
   const int by = bt / gx, bx = bt - by * gx;
   const int k0 = bx * (64 * KH), c0 = by * 64;
   const int chunk = tid % CPR, prow = tid / CPR;          // halo staging role

@@ -15,16 +15,6 @@
 
 namespace sslcr {
 
-typedef short w2_h16x4_t __attribute__((ext_vector_type(4)));
-typedef short w2_h16x8_t __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ bf16x8_t w2_tr_pair(const char* p0, const char* p1) {
-  w2_h16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) w2_h16x4_t*)(p0));
-  w2_h16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) w2_h16x4_t*)(p1));
-  w2_h16x8_t v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8_t, v);
-}
-
 // TW = 16: tiles of 4 rows x 16 columns; TW = 8: a tile is 8 rows x 8 columns (layer4.0 at 256x256 input: one whole 8x8 map) -- a depth
 // step is then four rows of eight, the lane's second read is the next ROW instead of eight columns on
 template <int TW>
@@ -49,13 +39,8 @@ __global__ __launch_bounds__(512, 2) void wgrad_s2_kernel(const WgradArgs a, int
   const int li = lane & 15, g = lane >> 4;
   // grid x = (kout block, cin block, pixel split) triples, the gx * gy workgroups of one pixel split neighbours on one XCD (wgrad_halo.hip)
   const int gx = a.K / 128, gy = a.C / 64, GT = gx * gy, splits = (int)gridDim.x / GT;
-  int bz, bt;
-  if ((splits & 7) == 0) {
-    const int w = blockIdx.x, grp = w / (8 * GT), r = w - grp * 8 * GT;
-    bz = grp * 8 + (r & 7); bt = r >> 3;
-  } else {
-    bz = (int)blockIdx.x / GT; bt = (int)blockIdx.x - bz * GT;
-  }
+  const OuterInner oi = xcd_outer_inner(blockIdx.x, splits, GT, false);
+  const int bz = oi.outer, bt = oi.inner;
   const int by = bt / gx, bx = bt - by * gx;
   const int k0 = bx * 128, c0 = by * 64;
   const int tiles_w = a.OW / TW, tiles_h = a.OH / TH;
@@ -171,7 +156,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_s2_kernel(const WgradArgs a, int
       const int pbase = (rodd ? (codd ? P_OO : P_OE) : (codd ? P_EO : P_EE)) * RB;
       const int pitch = codd ? PO : PE;
       const char* p = hb + pbase + (codd ? B17[dc] : B16) + (RSTEP * q + dr) * pitch * RB;
-      return w2_tr_pair(p, p + (TW == 16 ? 8 : pitch) * RB);        // the lane's pixel pl + 8: eight columns on, or the next row
+      return tr_pair(p, p + (TW == 16 ? 8 : pitch) * RB);        // the lane's pixel pl + 8: eight columns on, or the next row
     };
     bf16x8_t bfr[2];
     auto qstep = [&](const int q, const int par) {       // par: which of bfr[] holds (q, tap 0)
@@ -179,7 +164,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_s2_kernel(const WgradArgs a, int
 #pragma unroll
       for (int t4 = 0; t4 < 4; ++t4) {
         const char* pa = yb + kh * YH + q * 32 * RB + Aoff[t4];
-        af[t4] = w2_tr_pair(pa, pa + 8 * RB);
+        af[t4] = tr_pair(pa, pa + 8 * RB);
       }
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
