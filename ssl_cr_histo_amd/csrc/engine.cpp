@@ -92,6 +92,11 @@ struct BlockL {
   bool has_ds = false;
   int pstart = 0;
 };
+struct Layer {                  // a conv and the BatchNorm behind it
+  ConvL* conv;
+  BnL* bn;
+};
+constexpr int kLayers = 20;     // the stem, two convs per block, three projections
 struct BnSaved {
   float *scale, *shift, *mean, *invstd;
 };
@@ -213,6 +218,10 @@ struct sslcr_net {
   ConvL stem;
   BnL bn0;
   BlockL blocks[8];
+  // every conv with its BatchNorm in parameter order (index = BnL::bidx): THE walk over the net's layers (build_topology fills it) ...
+  Layer layers[kLayers];
+  // ... and parameter -> block conv (nullptr: the stem, whose pack has its own K order, a BatchNorm or a head parameter)
+  std::vector<const ConvL*> block_conv;
   DevBuf shadow, grads, heads, descs, chunks, f8buf;
   DevBuf norm_ws;     // gradient norm: GRAD_NORM_BLOCKS double partials, then {norm, coef}
   float* f8slots = nullptr;       // [n8][2] = {x_scale, amax since the last update}: two slots (train, eval) per fp8 conv, see ConvL::f8s
@@ -246,6 +255,14 @@ struct sslcr_net {
   std::vector<float*> st1, st2;
   std::vector<int> group_of;      // parameter -> optimizer group of the descriptor table in `descs`
   int ndesc = 0, max_n = 0;
+  // every device buffer the net owns (a new DevBuf member is added here, nowhere else): what sslcr_net_destroy releases
+  std::vector<DevBuf*> bufs() {
+    std::vector<DevBuf*> v = {&shadow, &grads, &gnew, &heads, &descs, &chunks, &f8buf, &norm_ws};
+    for (PassState& ps : pass) v.push_back(&ps.mem);
+    for (auto& row : tapbuf)
+      for (DevBuf& b : row) v.push_back(&b);
+    return v;
+  }
 };
 
 namespace {
@@ -335,8 +352,7 @@ hipError_t profiled(sslcr_ctx* c, int slot, hipStream_t st, Book&& book, Launch&
   c->prof.rec[slot].push_back(r);
   return e;
 }
-hipError_t prof_conv(sslcr_ctx* c, int dt, const ConvArgs& a, hipStream_t st) {
-  const ConvPlan plan = conv_plan(dt, a);
+hipError_t prof_conv(sslcr_ctx* c, int dt, const ConvArgs& a, const ConvPlan& plan, hipStream_t st) {
   auto book = [&](ProfRec& r) {
     const double es = c->esz();
     const double rs = a.tap_mask ? (double)__builtin_popcount(a.tap_mask) : (double)a.R * a.S;
@@ -347,6 +363,7 @@ hipError_t prof_conv(sslcr_ctx* c, int dt, const ConvArgs& a, hipStream_t st) {
   };
   return profiled(c, 0, st, book, [&] { return launch_conv(dt, a, plan, st); });
 }
+hipError_t prof_conv(sslcr_ctx* c, int dt, const ConvArgs& a, hipStream_t st) { return prof_conv(c, dt, a, conv_plan(dt, a), st); }
 // a downsampling block's conv1 (3x3 / 2) and 1x1 / 2 projection of one input in one launch (conv_s2.hip)
 hipError_t prof_conv_pair(sslcr_ctx* c, const ConvArgs& a, const ConvArgs& d, hipStream_t st) {
   auto book = [&](ProfRec& r) {
@@ -361,14 +378,10 @@ hipError_t prof_conv_pair(sslcr_ctx* c, const ConvArgs& a, const ConvArgs& d, hi
 inline bool fp8_layer(const sslcr_ctx* c, const ConvL& L) {
   return c->fp8 && L.k == 3 && L.stride == 1 && L.cin % 128 == 0 && L.cout % 128 == 0;
 }
-// forward conv of layer L (folded = eval pack): the fp8 kernel where the mode, the layer and the shape allow it, else the
+// forward conv of layer L (folded = eval pack): the fp8 kernel where the mode, the layer and the shape allow it (use_fp8), else the
 // engine dtype's kernel
 inline bool use_fp8(const sslcr_ctx* c, const ConvL& L, const ConvArgs& a) { return fp8_layer(c, L) && L.w8_fwd && conv_fp8_mode(a) != 0; }
-hipError_t prof_conv_fwd(sslcr_ctx* c, int dt, const ConvArgs& a_in, const ConvL& L, bool folded, hipStream_t st) {
-  // (the e4m3 eval pack is the FOLDED filter with its own per-kout dequant factor: no output scale on that path)
-  ConvArgs a = a_in;
-  a.out_scale = nullptr;
-  if (!use_fp8(c, L, a)) return prof_conv(c, dt, a_in, st);
+hipError_t prof_conv_fp8(sslcr_ctx* c, const ConvArgs& a, const ConvL& L, bool folded, hipStream_t st) {
   Fp8Args q;
   q.w8 = folded ? L.w8_fold : L.w8_fwd;
   q.w_dequant = folded ? L.dq_fold : L.dq_fwd;
@@ -385,6 +398,12 @@ hipError_t prof_conv_fwd(sslcr_ctx* c, int dt, const ConvArgs& a_in, const ConvL
   };
   return profiled(c, 0, st, book, [&] { return launch_conv_fp8(a, q, st); });
 }
+hipError_t prof_conv_fwd(sslcr_ctx* c, int dt, const ConvArgs& a_in, const ConvL& L, bool folded, hipStream_t st) {
+  // (the e4m3 eval pack is the FOLDED filter with its own per-kout dequant factor: no output scale on that path)
+  ConvArgs a = a_in;
+  a.out_scale = nullptr;
+  return use_fp8(c, L, a) ? prof_conv_fp8(c, a, L, folded, st) : prof_conv(c, dt, a_in, st);
+}
 hipError_t prof_wgrad(sslcr_ctx* c, int dt, const WgradArgs& a, hipStream_t st) {
   const WgradPlan plan = wgrad_plan(dt, a);
   auto book = [&](ProfRec& r) {
@@ -400,49 +419,36 @@ hipError_t prof_wgrad(sslcr_ctx* c, int dt, const WgradArgs& a, hipStream_t st) 
 // the 16x16-tile kernels (conv3x3_h16 / conv3x3_pp64): the ones with the BatchNorm-backward front end (sslcr_conv_desc.mask_x)
 inline bool tile16(const ConvPlan& p) { return p.route == ConvRoute::H16 || p.route == ConvRoute::PP64; }
 
-constexpr int kMaxSeg = 3;      // TripletNet branches run as segments of one launch (backbone_forward_train_segments)
+constexpr int kMaxSeg = 3;      // TripletNet branches run as segments of one launch (backbone_forward)
 const int kBlockCfg[8][3] ={{64, 64, 1}, {64, 64, 1}, {64, 128, 2}, {128, 128, 1}, {128, 256, 2}, {256, 256, 1}, {256, 512, 2}, {512, 512, 1}};
 
 inline int out_dim(int h, int k, int stride, int pad) { return (h + 2 * pad - k) / stride + 1; }
 
 void build_topology(sslcr_net* n) {
-  int p = 0, b = 0;
-  n->stem = ConvL{3, 64, 7, 2, 3, p++};
-  n->bn0 = BnL{64, p, p + 1, b++};
-  p += 2;
+  int p = 0, nl = 0;
+  n->psize.assign(n->nparams, 0);
+  n->block_conv.assign(n->nparams, nullptr);
+  // the next layer: parameters p (filter), p + 1, p + 2 (BatchNorm weight, bias)
+  auto layer = [&](ConvL& L, BnL& bn, int cin, int cout, int k, int stride, int pad) {
+    L = ConvL{cin, cout, k, stride, pad, p};
+    bn = BnL{cout, p + 1, p + 2, nl};
+    n->psize[p] = cout * cin * k * k;
+    n->psize[p + 1] = n->psize[p + 2] = cout;
+    if (nl > 0) n->block_conv[p] = &L;
+    n->layers[nl++] = Layer{&L, &bn};
+    p += 3;
+  };
+  layer(n->stem, n->bn0, 3, 64, 7, 2, 3);
   for (int i = 0; i < 8; ++i) {
     BlockL& B = n->blocks[i];
     const int cin = kBlockCfg[i][0], cout = kBlockCfg[i][1], s = kBlockCfg[i][2];
     B.pstart = p;
-    B.c1 = ConvL{cin, cout, 3, s, 1, p++};
-    B.b1 = BnL{cout, p, p + 1, b++};
-    p += 2;
-    B.c2 = ConvL{cout, cout, 3, 1, 1, p++};
-    B.b2 = BnL{cout, p, p + 1, b++};
-    p += 2;
+    layer(B.c1, B.b1, cin, cout, 3, s, 1);
+    layer(B.c2, B.b2, cout, cout, 3, 1, 1);
     B.has_ds = (s != 1 || cin != cout);
-    if (B.has_ds) {
-      B.ds = ConvL{cin, cout, 1, s, 0, p++};
-      B.bd = BnL{cout, p, p + 1, b++};
-      p += 2;
-    }
+    if (B.has_ds) layer(B.ds, B.bd, cin, cout, 1, s, 0);
   }
-  // p == 60 ; heads: 60 fc.0.weight [512,1024], 61 fc.0.bias, 62 fc.2.weight [256,512], 63 fc.2.bias, 64.. classifier
-  n->psize.assign(n->nparams, 0);
-  auto conv_sz = [](const ConvL& c) { return c.cout * c.cin * c.k * c.k; };
-  n->psize[n->stem.pidx] = conv_sz(n->stem);
-  n->psize[n->bn0.pg] = n->psize[n->bn0.pb] = 64;
-  for (int i = 0; i < 8; ++i) {
-    BlockL& B = n->blocks[i];
-    n->psize[B.c1.pidx] = conv_sz(B.c1);
-    n->psize[B.c2.pidx] = conv_sz(B.c2);
-    n->psize[B.b1.pg] = n->psize[B.b1.pb] = B.b1.C;
-    n->psize[B.b2.pg] = n->psize[B.b2.pb] = B.b2.C;
-    if (B.has_ds) {
-      n->psize[B.ds.pidx] = conv_sz(B.ds);
-      n->psize[B.bd.pg] = n->psize[B.bd.pb] = B.bd.C;
-    }
-  }
+  // p == 60, nl == kLayers ; heads: 60 fc.0.weight [512,1024], 61 fc.0.bias, 62 fc.2.weight [256,512], 63 fc.2.bias, 64.. classifier
   n->psize[60] = 512 * 1024;
   n->psize[61] = 512;
   n->psize[62] = 256 * 512;
@@ -471,58 +477,67 @@ bool unfold_eval(const sslcr_ctx* c) {
 int alloc_shadow(sslcr_net* n) {
   const size_t es = n->ctx->esz();
   Carver c;
-  std::vector<std::pair<ConvL*, size_t>> offs;
-  auto add = [&](ConvL& L) {
-    const size_t wbytes = (L.pidx == 0 ? (size_t)64 * 224 : (size_t)L.cout * L.cin * L.k * L.k) * es;
-    size_t o = c.take(wbytes);          // w_fwd
-    c.take(wbytes);                     // w_dg
-    c.take(wbytes);                     // w_fold
-    c.take(L.cout * sizeof(float));     // b_fold
-    c.take(L.cout * sizeof(float));     // s_fold
-    if (L.pidx == 0) c.take(wbytes);    // w_foldf
-    if (fp8_layer(n->ctx, L)) {         // w8_fwd, w8_fold, dq_fwd, dq_fold
-      c.take((size_t)L.cout * 9 * L.cin); c.take((size_t)L.cout * 9 * L.cin);
-      c.take(L.cout * sizeof(float)); c.take(L.cout * sizeof(float));
+  // where take() put each pack of each layer, in the order of the buffer (kNone: this layer has no such pack)
+  constexpr size_t kNone = ~(size_t)0;
+  struct Off { size_t w_fwd, w_dg, w_fold, b_fold, s_fold, w_foldf = kNone, w8_fwd = kNone, w8_fold = kNone, dq_fwd = kNone, dq_fold = kNone; };
+  Off off[kLayers];
+  for (int l = 0; l < kLayers; ++l) {
+    const ConvL& L = *n->layers[l].conv;
+    Off& o = off[l];
+    const bool stem = L.pidx == 0;
+    const size_t wbytes = (stem ? (size_t)64 * 224 : (size_t)L.cout * L.cin * L.k * L.k) * es, kbytes = L.cout * sizeof(float);
+    o.w_fwd = c.take(wbytes);
+    o.w_dg = c.take(wbytes);
+    o.w_fold = c.take(wbytes);
+    o.b_fold = c.take(kbytes);
+    o.s_fold = c.take(kbytes);                      // (the room is there in either mode)
+    if (!unfold_eval(n->ctx)) o.s_fold = kNone;
+    if (stem) o.w_foldf = c.take(wbytes);
+    if (fp8_layer(n->ctx, L)) {
+      o.w8_fwd = c.take((size_t)L.cout * 9 * L.cin);
+      o.w8_fold = c.take((size_t)L.cout * 9 * L.cin);
+      o.dq_fwd = c.take(kbytes);
+      o.dq_fold = c.take(kbytes);
     }
-    offs.push_back({&L, o});
-  };
-  add(n->stem);
-  for (int i = 0; i < 8; ++i) {
-    add(n->blocks[i].c1);
-    add(n->blocks[i].c2);
-    if (n->blocks[i].has_ds) add(n->blocks[i].ds);
   }
   TRYI(n->shadow.ensure(c.off));
-  for (auto& pr : offs) {
-    ConvL& L = *pr.first;
-    const size_t wbytes = ((L.pidx == 0 ? (size_t)64 * 224 : (size_t)L.cout * L.cin * L.k * L.k) * es + 255) & ~(size_t)255;
-    char* base = (char*)n->shadow.p + pr.second;
-    L.w_fwd = base;
-    L.w_dg = base + wbytes;
-    L.w_fold = base + 2 * wbytes;
-    L.b_fold = (float*)(base + 3 * wbytes);
-    {
-      const size_t bb = (L.cout * sizeof(float) + 255) & ~(size_t)255;
-      L.s_fold = unfold_eval(n->ctx) ? (float*)(base + 3 * wbytes + bb) : nullptr;
-      if (L.pidx == 0) L.w_foldf = base + 3 * wbytes + 2 * bb;
-    }
-    if (fp8_layer(n->ctx, L)) {
-      const size_t bb = (L.cout * sizeof(float) + 255) & ~(size_t)255, w8 = ((size_t)L.cout * 9 * L.cin + 255) & ~(size_t)255;
-      char* q = base + 3 * wbytes + 2 * bb;
-      L.w8_fwd = (uint8_t*)q; L.w8_fold = (uint8_t*)(q + w8);
-      L.dq_fwd = (float*)(q + 2 * w8); L.dq_fold = (float*)(q + 2 * w8 + bb);
-    }
+  auto at = [&](size_t o) { return o == kNone ? nullptr : (char*)n->shadow.p + o; };
+  for (int l = 0; l < kLayers; ++l) {
+    ConvL& L = *n->layers[l].conv;
+    const Off& o = off[l];
+    L.w_fwd = at(o.w_fwd); L.w_dg = at(o.w_dg); L.w_fold = at(o.w_fold); L.w_foldf = at(o.w_foldf);
+    L.b_fold = (float*)at(o.b_fold); L.s_fold = (float*)at(o.s_fold);
+    L.w8_fwd = (uint8_t*)at(o.w8_fwd); L.w8_fold = (uint8_t*)at(o.w8_fold);
+    L.dq_fwd = (float*)at(o.dq_fwd); L.dq_fold = (float*)at(o.dq_fold);
   }
   if (n->ctx->fp8) {
     n->n8 = 0;
-    for (auto& pr : offs) if (pr.first->w8_fwd) n->n8 += 2;
+    for (const Layer& ly : n->layers) if (ly.conv->w8_fwd) n->n8 += 2;
     TRYI(n->f8buf.ensure((size_t)n->n8 * 2 * sizeof(float)));
     n->f8slots = (float*)n->f8buf.p;
     std::vector<float> init((size_t)n->n8 * 2);
     for (int i = 0; i < n->n8; ++i) { init[2 * i] = 1.f; init[2 * i + 1] = 0.f; }
     TRY(hipMemcpy(n->f8slots, init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice));
     int k = 0;
-    for (auto& pr : offs) if (pr.first->w8_fwd) { pr.first->f8s = n->f8slots + 4 * k; ++k; }
+    for (const Layer& ly : n->layers) if (ly.conv->w8_fwd) { ly.conv->f8s = n->f8slots + 4 * k; ++k; }
+  }
+  return 0;
+}
+
+// the e4m3 packs of a layer the fp8 kernel serves (mode bit 0: train, bit 1: eval-folded); nothing for the others
+int pack_fp8_layer(sslcr_net* n, const ConvL& L, const BnL& bn, int mode, hipStream_t st) {
+  if (!L.w8_fwd) return 0;
+  PackFp8Args f;
+  memset(&f, 0, sizeof(f));
+  f.w = n->params[L.pidx]; f.K = L.cout; f.C = L.cin; f.eps = 1e-5f;
+  if (mode & 1) {
+    f.w8 = L.w8_fwd; f.w_dequant = L.dq_fwd;
+    TRY(launch_pack_fp8(f, st));
+  }
+  if (mode & 2) {
+    f.w8 = L.w8_fold; f.w_dequant = L.dq_fold;
+    f.gamma = n->params[bn.pg]; f.beta = n->params[bn.pb]; f.rmean = n->bn_rm[bn.bidx]; f.rvar = n->bn_rv[bn.bidx];
+    TRY(launch_pack_fp8(f, st));        // (the folded bias is the bf16 pack's b_fold)
   }
   return 0;
 }
@@ -554,21 +569,7 @@ int pack_conv_layer(sslcr_net* n, ConvL& L, const BnL& bn, int mode, hipStream_t
       TRY(launch_pack_stem(dt, a, st));
     }
   }
-  if (L.w8_fwd) {
-    PackFp8Args f;
-    memset(&f, 0, sizeof(f));
-    f.w = n->params[L.pidx]; f.K = L.cout; f.C = L.cin; f.eps = 1e-5f;
-    if (mode & 1) {
-      f.w8 = L.w8_fwd; f.w_dequant = L.dq_fwd;
-      TRY(launch_pack_fp8(f, st));
-    }
-    if (mode & 2) {
-      f.w8 = L.w8_fold; f.w_dequant = L.dq_fold;
-      f.gamma = n->params[bn.pg]; f.beta = n->params[bn.pb]; f.rmean = n->bn_rm[bn.bidx]; f.rvar = n->bn_rv[bn.bidx];
-      TRY(launch_pack_fp8(f, st));        // (the folded bias is the bf16 pack's b_fold)
-    }
-  }
-  return 0;
+  return pack_fp8_layer(n, L, bn, mode, st);
 }
 
 // ---------------------------------------------------------------- BN finalize (optionally synced across ranks)
@@ -649,8 +650,8 @@ int partials_rows(sslcr_ctx* c, int nrows, int K, float** out) {
   *out = (float*)c->partials.p;
   return 0;
 }
-int ensure_partials(sslcr_ctx* c, const ConvArgs& a, float** out, int* rows, bool fp8 = false) {
-  *rows = fp8 ? conv_fp8_rows(a) : conv_plan(DT_BF16, a).rows;      // (asked before the dtype's launch: the routes tile alike in both)
+int ensure_partials(sslcr_ctx* c, const ConvArgs& a, float** out, int* rows) {
+  *rows = conv_plan(DT_BF16, a).rows;      // (asked before the dtype's launch: the routes tile alike in both)
   return partials_rows(c, *rows, a.K, out);
 }
 
@@ -716,25 +717,37 @@ int alloc_passes(sslcr_net* n, int npass, int N, int H, int W) {
 }
 
 // ---------------------------------------------------------------- backbone forward, train mode (saves everything)
+// the descriptors of the stem conv and of the max-pool behind it, like conv_args: shape and tensors; the mode's fields are the caller's
+StemArgs stem_args(const void* x, const void* w, void* y, int in_f32, int N, int H, int W, const Dims& d) {
+  StemArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = x; a.w = w; a.y = y;
+  a.N = N; a.H = H; a.W = W; a.OH = d.oh0; a.OW = d.ow0; a.in_f32 = in_f32;
+  return a;
+}
+PoolFwdArgs pool_args(const void* x, void* y, int N, const Dims& d) {
+  PoolFwdArgs p;
+  memset(&p, 0, sizeof(p));
+  p.x = x; p.y = y;
+  p.N = N; p.H = d.oh0; p.W = d.ow0; p.C = 64; p.OH = d.ph; p.OW = d.pw;
+  return p;
+}
+
 // stem of one pass: conv1 7x7/2 with statistics -> bn0 finalize -> BatchNorm + ReLU + max-pool into ps.pooled
 int forward_stem(sslcr_net* n, PassState& ps, const void* x, int in_f32, int N, int H, int W, int replay, hipStream_t st) {
   sslcr_ctx* c = n->ctx;
   const int dt = c->dtype;
   const Dims d = make_dims(H, W);
   ps.x = x; ps.in_f32 = in_f32;
-  StemArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.x2 = ps.x2; a.n_split = ps.n_split; a.w = n->stem.w_fwd; a.y = ps.raw0;
-  a.N = N; a.H = H; a.W = W; a.OH = d.oh0; a.OW = d.ow0; a.in_f32 = in_f32;
+  StemArgs a = stem_args(x, n->stem.w_fwd, ps.raw0, in_f32, N, H, W, d);
+  a.x2 = ps.x2; a.n_split = ps.n_split;
   const int rows = stem_partials_rows(a);
   TRYI(c->partials.ensure((size_t)rows * 2 * 64 * sizeof(float)));
   a.stats = (float*)c->partials.p;
   TRY(launch_stem(dt, a, st));
   TRYI(finalize_bn(n, n->bn0, a.stats, rows, (double)N * d.oh0 * d.ow0, ps.bn[0], replay, st));
-  PoolFwdArgs p;
-  memset(&p, 0, sizeof(p));
-  p.x = ps.raw0; p.scale = ps.bn[0].scale; p.shift = ps.bn[0].shift; p.y = ps.pooled; p.argmax = ps.argmax;
-  p.N = N; p.H = d.oh0; p.W = d.ow0; p.C = 64; p.OH = d.ph; p.OW = d.pw;
+  PoolFwdArgs p = pool_args(ps.raw0, ps.pooled, N, d);
+  p.scale = ps.bn[0].scale; p.shift = ps.bn[0].shift; p.argmax = ps.argmax;
   TRY(launch_bn_relu_maxpool(dt, p, st));
   return 0;
 }
@@ -745,13 +758,74 @@ bool ybits_on(const sslcr_ctx* c) {
   static const bool on = [] { const char* e = getenv("SSLCR_YBITS"); return !e || atoi(e) != 0; }();
   return on && c->dtype == DT_BF16;
 }
-// the bits that go with a saved block output (nullptr: not one of them)
-const uint8_t* ybits_of(const sslcr_net* n, const void* yact) {
-  if (!yact || !n->ybits_ok || !ybits_on(n->ctx)) return nullptr;
-  for (int p = 0; p < 3; ++p)
-    for (int i = 0; i < 8; ++i)
-      if (n->pass[p].blk[i].y == yact) return n->pass[p].blk[i].ybits;
-  return nullptr;
+// the bits that go with the saved output of block i (nullptr: this net keeps none)
+uint8_t* ybits_of(const sslcr_net* n, const PassState& ps, int i) { return n->ybits_ok && ybits_on(n->ctx) ? ps.blk[i].ybits : nullptr; }
+
+// THE BLOCK PLAN: everything the train-mode forward of block i decides, for `nseg` passes of N images each whose first is ps.  The only
+// place that fills the block forward's conv descriptors: forward_blocks launches from it and segments_servable asks it, so the two
+// cannot disagree.  What is still missing is where the statistics rows go: offsets here, pointers once ctx->partials is large enough.
+struct ConvStage {
+  const ConvL* L;
+  ConvArgs a;
+  ConvPlan plan;                // of `a` in the engine's dtype: what the launch switches on
+  bool fp8;                     // the e4m3 kernel takes it instead
+  int rows;                     // statistics rows the launch writes ...
+  size_t stats_off;             // ... at this offset of ctx->partials
+  size_t stats_bytes() const { return (size_t)rows * 2 * a.K * sizeof(float); }
+};
+struct BlockPlan {
+  ConvStage c1, c2, ds;         // (ds: blocks with a projection shortcut)
+  // a downsampling block's conv1 and projection read the same input: one launch where the plane-gather kernel serves the pair; else
+  // two (fp32, layer4.0's 8x8 maps, ragged shapes)
+  bool paired;
+  bool seg_ok;                  // every launch has a form for these segments and its rows split evenly among them
+  int seg_stride;               // floats from one pass's saved BatchNorm statistics to the next pass's
+  // bytes of ctx->partials that conv1 and the projection need together; conv2 then needs its own stats_bytes().  forward_blocks grows
+  // the buffer in these two steps, not once to the larger: reserving the maximum up front left every output bit alone and measured
+  // 0.02 ms per step slower on the same box, twice (another hipFree / hipMalloc history: profiles/engine_forward_refactor_ab.txt)
+  size_t c1_ds_bytes;
+};
+BlockPlan block_plan(sslcr_net* n, const PassState& ps, const Dims& d, int i, int N, int nseg) {
+  sslcr_ctx* c = n->ctx;
+  const int dt = c->dtype;
+  const BlockL& B = n->blocks[i];
+  const bool segs = nseg > 1;
+  const int xh = i ? d.lh[i - 1] : d.ph, xw = i ? d.lw[i - 1] : d.pw;
+  const char* X = i ? ps.blk[i - 1].y : ps.pooled;
+  BlockPlan bp{};
+  bp.seg_stride = segs ? (int)(n->pass[1].bn[0].scale - n->pass[0].bn[0].scale) : 0;
+  // pro: the BatchNorm + ReLU the conv applies to its input on the way in
+  auto stage = [&](ConvStage& s, const ConvL& L, const void* x, void* y, int h, int w, const BnSaved* pro) {
+    s.L = &L;
+    s.a = conv_args(L, x, L.w_fwd, y, nseg * N, h, w);
+    if (pro) { s.a.in_scale = pro->scale; s.a.in_shift = pro->shift; s.a.in_relu = 1; }
+    if (segs) { s.a.seg_images = N; s.a.seg_stride = pro ? bp.seg_stride : 0; }
+    s.a.stats = c->zeros;         // (stands for its region of ctx->partials until forward_blocks has it: the predicates look at the mode only)
+    s.fp8 = !segs && use_fp8(c, L, s.a);
+    s.plan = conv_plan(dt, s.a);
+    // (the rows buffer has no dtype: the routes tile alike in both)
+    s.rows = s.fp8 ? conv_fp8_rows(s.a) : dt == DT_BF16 ? s.plan.rows : conv_plan(DT_BF16, s.a).rows;
+  };
+  stage(bp.c1, B.c1, X, ps.blk[i].raw1, xh, xw, nullptr);
+  stage(bp.c2, B.c2, ps.blk[i].raw1, ps.blk[i].raw2, d.lh[i], d.lw[i], &ps.bn[B.b1.bidx]);
+  bp.seg_ok = bp.c1.plan.seg_ok && bp.c2.plan.seg_ok && bp.c1.rows % nseg == 0 && bp.c2.rows % nseg == 0;
+  // ctx->partials: conv1's rows, the projection's behind them; conv2 takes the buffer over from its start -- by then both finalizes
+  // have consumed what was there
+  Carver cv;
+  bp.c1.stats_off = cv.take(bp.c1.stats_bytes());
+  if (B.has_ds) {
+    stage(bp.ds, B.ds, X, ps.blk[i].rawd, xh, xw, nullptr);
+    bp.paired = !bp.c1.fp8 && conv_s2_pair_ok(dt, bp.c1.a, bp.ds.a);
+    if (bp.paired) bp.ds.rows = bp.c1.rows;       // (the pair kernel writes both sets of rows per tile of conv1)
+    bp.seg_ok = bp.seg_ok && bp.ds.plan.seg_ok && bp.ds.rows % nseg == 0;
+    bp.ds.stats_off = cv.take(bp.ds.stats_bytes());
+  }
+  bp.c1_ds_bytes = cv.off;
+  bp.c2.stats_off = 0;
+  return bp;
+}
+hipError_t launch_stage(sslcr_ctx* c, const ConvStage& s, hipStream_t st) {
+  return s.fp8 ? prof_conv_fp8(c, s.a, *s.L, false, st) : prof_conv(c, c->dtype, s.a, s.plan, st);
 }
 
 // the eight residual blocks + average pool from ps.pooled on.  nseg == 1: one pass of N images.  nseg > 1: ps is the FIRST of nseg
@@ -761,94 +835,51 @@ int forward_blocks(sslcr_net* n, PassState& ps, int N, int H, int W, int replay,
   sslcr_ctx* c = n->ctx;
   const int dt = c->dtype;
   const Dims d = make_dims(H, W);
-  const bool segs = nseg > 1;
-  const int NT = nseg * N;
-  const int seg_stride = segs ? (int)(n->pass[1].bn[0].scale - n->pass[0].bn[0].scale) : 0;
-  const char* X = ps.pooled;
-  int xh = d.ph, xw = d.pw;
   for (int i = 0; i < 8; ++i) {
     BlockL& B = n->blocks[i];
-    const int oh = d.lh[i], ow = d.lw[i];
-    const double cnt = (double)N * oh * ow;
-    float* part; int rows;
-    ConvArgs a1 = conv_args(B.c1, X, B.c1.w_fwd, ps.blk[i].raw1, NT, xh, xw);
-    if (segs) a1.seg_images = N;
-    // a downsampling block's conv1 and projection read the same input: one launch where the plane-gather kernel serves the pair
-    // (both sets of statistics rows, the projection's BatchNorm finalized before conv2 reuses the rows buffer)
-    ConvArgs ad;
-    bool paired = false;
-    if (B.has_ds) {
-      ad = conv_args(B.ds, X, B.ds.w_fwd, ps.blk[i].rawd, NT, xh, xw);
-      if (segs) ad.seg_images = N;
-      ConvArgs t1 = a1, td = ad;
-      t1.stats = td.stats = c->zeros;                // (any non-null pointer: the predicate looks at the mode only)
-      paired = !use_fp8(c, B.c1, a1) && conv_s2_pair_ok(dt, t1, td);
-    }
-    if (paired) {
-      const ConvPlan p1 = conv_plan(dt, a1);
-      if (segs && (!p1.seg_ok || !conv_plan(dt, ad).seg_ok)) return fail("forward_blocks: the paired stride-2 launch has no segment form here");
-      rows = p1.rows;
-      const size_t rb = (size_t)rows * 2 * a1.K * sizeof(float);
-      TRYI(c->partials.ensure(2 * rb));
-      part = (float*)c->partials.p;
-      a1.stats = part;
-      ad.stats = (float*)((char*)c->partials.p + rb);
-      TRY(prof_conv_pair(c, a1, ad, st));
-      TRYI(finalize_bn_pair(n, B.b1, a1.stats, rows, B.bd, ad.stats, rows, cnt, ps.bn[B.b1.bidx], ps.bn[B.bd.bidx], replay, st, nseg, seg_stride));
-    } else if (B.has_ds) {
-      // two launches (fp32, layer4.0's 8x8 maps, ragged shapes), the projection right behind conv1 so that the two BatchNorms still
-      // share one all-reduce of their sums when BatchNorm is synced across ranks
-      const int rows1 = conv_plan(DT_BF16, a1).rows, rowsd = conv_plan(DT_BF16, ad).rows;
-      const size_t rb1 = (((size_t)rows1 * 2 * a1.K * sizeof(float)) + 255) & ~(size_t)255;
-      TRYI(c->partials.ensure(rb1 + (size_t)rowsd * 2 * ad.K * sizeof(float)));
-      a1.stats = (float*)c->partials.p;
-      ad.stats = (float*)((char*)c->partials.p + rb1);
-      TRY(prof_conv(c, dt, a1, st));
-      TRY(prof_conv(c, dt, ad, st));
-      TRYI(finalize_bn_pair(n, B.b1, a1.stats, rows1, B.bd, ad.stats, rowsd, cnt, ps.bn[B.b1.bidx], ps.bn[B.bd.bidx], replay, st, nseg, seg_stride));
-      paired = true;                                   // (the projection has run: the block's tail below must not launch it again)
+    BlockPlan bp = block_plan(n, ps, d, i, N, nseg);
+    if (nseg > 1 && !bp.seg_ok) return fail("forward_blocks: block %d has no segment form here (segments_servable read the same plan)", i);
+    // every conv with statistics is the same three steps over its region of ctx->partials: reserve, launch, finalize
+    auto reserve = [&](size_t bytes, std::initializer_list<ConvStage*> stages) {
+      TRYI(c->partials.ensure(bytes));
+      for (ConvStage* s : stages) s->a.stats = (float*)((char*)c->partials.p + s->stats_off);
+      return 0;
+    };
+    TRYI(reserve(bp.c1_ds_bytes, {&bp.c1, &bp.ds}));
+    const double cnt = (double)N * d.lh[i] * d.lw[i];
+    BnSaved &sv1 = ps.bn[B.b1.bidx], &sv2 = ps.bn[B.b2.bidx];
+    // conv1, and the projection in the same launch or right behind it, so that the two BatchNorms share one all-reduce of their sums
+    // when BatchNorm is synced across ranks
+    if (bp.paired) {
+      TRY(prof_conv_pair(c, bp.c1.a, bp.ds.a, st));
     } else {
-      TRYI(ensure_partials(c, a1, &part, &rows, !segs && use_fp8(c, B.c1, a1)));
-      a1.stats = part;
-      TRY(segs ? prof_conv(c, dt, a1, st) : prof_conv_fwd(c, dt, a1, B.c1, false, st));
-      TRYI(finalize_bn(n, B.b1, part, rows, cnt, ps.bn[B.b1.bidx], replay, st, nseg, seg_stride));
+      TRY(launch_stage(c, bp.c1, st));
+      if (B.has_ds) TRY(launch_stage(c, bp.ds, st));
     }
-    ConvArgs a2 = conv_args(B.c2, ps.blk[i].raw1, B.c2.w_fwd, ps.blk[i].raw2, NT, oh, ow);
-    a2.in_scale = ps.bn[B.b1.bidx].scale; a2.in_shift = ps.bn[B.b1.bidx].shift; a2.in_relu = 1;
-    if (segs) { a2.seg_images = N; a2.seg_stride = seg_stride; }
-    TRYI(ensure_partials(c, a2, &part, &rows, !segs && use_fp8(c, B.c2, a2)));
-    a2.stats = part;
-    TRY(segs ? prof_conv(c, dt, a2, st) : prof_conv_fwd(c, dt, a2, B.c2, false, st));
-    TRYI(finalize_bn(n, B.b2, part, rows, cnt, ps.bn[B.b2.bidx], replay, st, nseg, seg_stride));
+    if (B.has_ds) {
+      TRYI(finalize_bn_pair(n, B.b1, bp.c1.a.stats, bp.c1.rows, B.bd, bp.ds.a.stats, bp.ds.rows, cnt, sv1, ps.bn[B.bd.bidx], replay, st, nseg,
+                            bp.seg_stride));
+    } else {
+      TRYI(finalize_bn(n, B.b1, bp.c1.a.stats, bp.c1.rows, cnt, sv1, replay, st, nseg, bp.seg_stride));
+    }
+    TRYI(reserve(bp.c2.stats_bytes(), {&bp.c2}));
+    TRY(launch_stage(c, bp.c2, st));
+    TRYI(finalize_bn(n, B.b2, bp.c2.a.stats, bp.c2.rows, cnt, sv2, replay, st, nseg, bp.seg_stride));
     BnActArgs e;
     memset(&e, 0, sizeof(e));
-    e.x = ps.blk[i].raw2; e.scale = ps.bn[B.b2.bidx].scale; e.shift = ps.bn[B.b2.bidx].shift;
-    e.y = ps.blk[i].y; e.pixels = (size_t)NT * oh * ow; e.C = B.c2.cout; e.relu = 1;
-    if (segs) { e.nseg = nseg; e.seg_stride = seg_stride; }
-    if (n->ybits_ok && ybits_on(c)) e.ybits = ps.blk[i].ybits;
+    e.x = ps.blk[i].raw2; e.scale = sv2.scale; e.shift = sv2.shift;
+    e.y = ps.blk[i].y; e.pixels = (size_t)nseg * N * d.lh[i] * d.lw[i]; e.C = B.c2.cout; e.relu = 1;
+    if (nseg > 1) { e.nseg = nseg; e.seg_stride = bp.seg_stride; }
+    e.ybits = ybits_of(n, ps, i);
     if (B.has_ds) {
-      if (!paired) {
-        TRYI(ensure_partials(c, ad, &part, &rows));
-        ad.stats = part;
-        TRY(prof_conv(c, dt, ad, st));
-        TRYI(finalize_bn(n, B.bd, part, rows, cnt, ps.bn[B.bd.bidx], replay, st, nseg, seg_stride));
-      }
       e.res = ps.blk[i].rawd; e.rscale = ps.bn[B.bd.bidx].scale; e.rshift = ps.bn[B.bd.bidx].shift;
     } else {
-      e.res = X;
+      e.res = bp.c1.a.x;
     }
     TRY(launch_bn_act(dt, e, st));
-    X = ps.blk[i].y; xh = oh; xw = ow;
   }
-  TRY(launch_avgpool_fwd(dt, X, ps.E, NT, xh * xw, 512, st));
+  TRY(launch_avgpool_fwd(dt, ps.blk[7].y, ps.E, nseg * N, d.lh[7] * d.lw[7], 512, st));
   return 0;
-}
-
-int backbone_forward_train(sslcr_net* n, PassState& ps, const void* x, int in_f32, int N, int H, int W, int replay, hipStream_t st) {
-  if (n->pass[0].N != N || n->pass[0].H != H || n->pass[0].W != W || !n->pass[0].mem.p) TRYI(alloc_passes(n, n->triplet ? 3 : 1, N, H, W));
-  ps.x2 = n->split_x2; ps.n_split = n->split_x2 ? n->split_n : 0;
-  TRYI(forward_stem(n, ps, x, in_f32, N, H, W, replay, st));
-  return forward_blocks(n, ps, N, H, W, replay, 1, st);
 }
 
 // The TripletNet branches (models/net.py:50-66: three tiles through ONE backbone, BatchNorm statistics per call) as SEGMENTS of one
@@ -862,39 +893,15 @@ bool segments_on() {
   static const bool on = [] { const char* e = getenv("SSLCR_SEGMENTS"); return !(e && e[0] == '0'); }();
   return on;
 }
+// (asked once the passes are allocated for N, H, W: the plans it reads are the ones forward_blocks will launch from)
 bool segments_servable(sslcr_net* n, int N, int H, int W) {
   sslcr_ctx* c = n->ctx;
+  // fp8, synced BatchNorm and the profiler keep the pass-by-pass form -- which is why the fp8 calibration pass never needs the segment form
   if (!segments_on() || !n->triplet || c->dtype != DT_BF16 || c->fp8 || (sharded(c) && c->bn_sync) || c->prof.on) return false;
   const Dims d = make_dims(H, W);
-  int xh = d.ph, xw = d.pw;
-  for (int i = 0; i < 8; ++i) {
-    BlockL& B = n->blocks[i];
-    const int oh = d.lh[i], ow = d.lw[i];
-    ConvArgs a1 = conv_args(B.c1, nullptr, nullptr, nullptr, 3 * N, xh, xw);
-    a1.seg_images = N;
-    ConvArgs a2 = conv_args(B.c2, nullptr, nullptr, nullptr, 3 * N, oh, ow);
-    a2.seg_images = N; a2.in_scale = c->ones; a2.in_shift = c->zeros;
-    const ConvPlan p1 = conv_plan(c->dtype, a1), p2 = conv_plan(c->dtype, a2);
-    if (!p1.seg_ok || !p2.seg_ok) return false;
-    if (B.has_ds) {
-      ConvArgs ad = conv_args(B.ds, nullptr, nullptr, nullptr, 3 * N, xh, xw);
-      ad.seg_images = N;
-      if (!conv_plan(c->dtype, ad).seg_ok) return false;
-    }
-    if (p1.rows % 3 || p2.rows % 3) return false;
-    xh = oh; xw = ow;
-  }
+  for (int i = 0; i < 8; ++i)
+    if (!block_plan(n, n->pass[0], d, i, N, kMaxSeg).seg_ok) return false;
   return true;
-}
-
-int backbone_forward_train_segments(sslcr_net* n, const void* const* xs, int in_f32, int N, int H, int W, hipStream_t st) {
-  constexpr int NS = 3;
-  if (n->pass[0].N != N || n->pass[0].H != H || n->pass[0].W != W || !n->pass[0].mem.p) TRYI(alloc_passes(n, NS, N, H, W));
-  for (int p = 0; p < NS; ++p) {
-    n->pass[p].x2 = nullptr; n->pass[p].n_split = 0;
-    TRYI(forward_stem(n, n->pass[p], xs[p], in_f32, N, H, W, 1, st));
-  }
-  return forward_blocks(n, n->pass[0], N, H, W, 1, NS, st);
 }
 
 // ---------------------------------------------------------------- backbone forward, eval mode (BN folded, nothing saved)
@@ -915,21 +922,16 @@ int backbone_forward_eval(sslcr_net* n, const void* const* xs, int npass, int in
   char* base = (char*)c->scratch.p;
   for (int p = 0; p < npass; ++p) {
     char* pooled = base + o_buf[0] + p * unit1;
-    StemArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = xs[p]; a.w = n->stem.w_fold; a.y = base + o_a0; a.bias = n->stem.b_fold; a.relu = 1; a.out_scale = n->stem.s_fold;
-    a.N = N; a.H = H; a.W = W; a.OH = d.oh0; a.OW = d.ow0; a.in_f32 = in_f32;
+    StemArgs a = stem_args(xs[p], n->stem.w_fold, base + o_a0, in_f32, N, H, W, d);
+    a.bias = n->stem.b_fold; a.relu = 1; a.out_scale = n->stem.s_fold;
     if (stem_pool_ok(dt, a, d.ph, d.pw)) {
       a.y = pooled;                                        // conv1 + folded BatchNorm + ReLU + max-pool in one launch: the conv output stays on the CU
       TRY(launch_stem_pool(dt, a, d.ph, d.pw, st));
     } else {
       if (a.out_scale) { a.w = n->stem.w_foldf; a.out_scale = nullptr; }      // (the two-kernel path takes the folded pack)
       TRY(launch_stem(dt, a, st));
-      PoolFwdArgs q;
-      memset(&q, 0, sizeof(q));
-      q.x = base + o_a0; q.y = pooled;                     // plain max-pool: the stem's epilogue applied the folded BatchNorm + ReLU
-      q.N = N; q.H = d.oh0; q.W = d.ow0; q.C = 64; q.OH = d.ph; q.OW = d.pw;
-      TRY(launch_bn_relu_maxpool(dt, q, st));
+      // plain max-pool: the stem's epilogue applied the folded BatchNorm + ReLU
+      TRY(launch_bn_relu_maxpool(dt, pool_args(base + o_a0, pooled, N, d), st));
     }
   }
   int xi = 0, xh = d.ph, xw = d.pw;
@@ -964,6 +966,28 @@ int backbone_forward_eval(sslcr_net* n, const void* const* xs, int npass, int in
   for (int p = 0; p < npass; ++p)
     TRY(launch_avgpool_fwd(dt, base + o_buf[xi] + (size_t)p * N * xh * xw * 512 * es, E[p], N, xh * xw, 512, st));
   return 0;
+}
+
+// the backbone over the net's passes in either mode; E[p] <- where pass p's embedding is.  Train mode: the TripletNet branches as
+// segments where every block has the form (all stems, then each layer once), else pass by pass
+int backbone_forward(sslcr_net* n, int train, const void* const* xs, int in_f32, int N, int H, int W, float** E, hipStream_t st) {
+  const int npass = n->triplet ? 3 : 1;
+  if (!train) {
+    for (int p = 0; p < npass; ++p) E[p] = n->dE[p];         // borrow the dE buffers (unused in eval) for the embeddings
+    return backbone_forward_eval(n, xs, npass, in_f32, N, H, W, E, st);
+  }
+  if (n->pass[0].N != N || n->pass[0].H != H || n->pass[0].W != W || !n->pass[0].mem.p) TRYI(alloc_passes(n, npass, N, H, W));
+  const bool segs = segments_servable(n, N, H, W);
+  const int replay = n->triplet ? 1 : 3;
+  n->last_segments = segs;
+  for (int p = 0; p < npass; ++p) {
+    PassState& ps = n->pass[p];
+    ps.x2 = n->split_x2; ps.n_split = n->split_x2 ? n->split_n : 0;      // (single-branch nets only: sslcr_step_ssl_cr)
+    TRYI(forward_stem(n, ps, xs[p], in_f32, N, H, W, replay, st));
+    if (!segs) TRYI(forward_blocks(n, ps, N, H, W, replay, 1, st));
+    E[p] = ps.E;
+  }
+  return segs ? forward_blocks(n, n->pass[0], N, H, W, replay, npass, st) : 0;
 }
 
 // ---------------------------------------------------------------- heads
@@ -1073,6 +1097,9 @@ struct PoolSrc {            // gradient arriving through the stem max-pool (see 
 // are pass 0's (the others seg_stride floats apart), the sums nseg consecutive ring slots, sum_rows / n_sum_rows cover all passes
 struct BnBwdReq {
   const void *dy = nullptr, *x = nullptr, *yact = nullptr;   // incoming gradient, saved conv output, saved block output (its ReLU mask)
+  // ... and that mask as bits, where the forward kept them: whoever sets yact sets this with it (ybits_of), or the reduce pass reads
+  // the whole of yact where it could read a sixteenth
+  const uint8_t* yact_bits = nullptr;
   void *dx = nullptr, *gout = nullptr;                        // gradient of x; g = dy * (yact > 0) for whoever reads it next
   int relu_from_x = 0;                                        // the ReLU mask is (bn(x) > 0)
   size_t pixels = 0;
@@ -1108,7 +1135,7 @@ int bn_bwd_begin(sslcr_net* n, const BnL& bn, const BnSaved& sv, const BnBwdReq&
   a.sums = sums; a.dx = q.dx; a.gout = q.gout; a.pixels = q.pixels; a.C = bn.C; a.relu_from_x = q.relu_from_x;
   if (q.nseg > 1) { a.nseg = q.nseg; a.seg_stride = q.seg_stride; a.sums_stride = sslcr_ctx::kBnSlot; }
   a.g_in_reduce = (q.g_in_reduce && q.yact && q.gout) ? 1 : 0;
-  a.yact_bits = ybits_of(n, q.yact);
+  a.yact_bits = q.yact_bits;
   const bool synced = sharded(c) && c->bn_sync;
   if (n->rg[bn.pg] || n->rg[bn.pb]) {
     // dgamma/dbeta ride on the apply pass.  Synced BN: every rank holds the GLOBAL sums and the gradient all-reduce adds
@@ -1330,7 +1357,8 @@ struct Backward {
     TRYI(wg_wait(c, 0, st));
     if (B->has_ds) TRYI(wg_wait(c, 2, st));
     BnBwdReq q2, qd;
-    q2.dy = buf(kOut, p, so); q2.x = ps.blk[i].raw2; q2.yact = ps.blk[i].y; q2.dx = dRaw2; q2.gout = G; q2.g_in_reduce = 1;
+    q2.dy = buf(kOut, p, so); q2.x = ps.blk[i].raw2; q2.yact = ps.blk[i].y; q2.yact_bits = ybits_of(n, ps, i);
+    q2.dx = dRaw2; q2.gout = G; q2.g_in_reduce = 1;
     qd.dy = G; qd.x = ps.blk[i].rawd; qd.dx = dRawD;
     q2.pixels = qd.pixels = opix * nseg; q2.count = qd.count = (double)opix;
     if (nseg > 1) { q2.nseg = qd.nseg = nseg; q2.seg_stride = qd.seg_stride = bn_stride; }
@@ -1570,40 +1598,23 @@ int backbone_backward(sslcr_net* n, int npass, hipStream_t st) {
 
 int net_forward(sslcr_net* n, int train, const void* const* xs, int in_f32, int N, int H, int W, float* feats, float* logits, hipStream_t st) {
   if (!(train ? n->packed_train : n->packed_eval)) TRYI(sslcr_net_pack(n, train ? 1 : 2, st));   // shadow weights are stale
-  const int npass_ = n->triplet ? 3 : 1;
+  const int npass = n->triplet ? 3 : 1;
+  float* E[3] = {nullptr, nullptr, nullptr};
   if (n->n8 > 0 && !n->f8_cal[train ? 0 : 1]) {
     // fp8 delayed scaling needs one forward to have seen the data: the FIRST forward of a net in a mode runs twice -- a
     // calibration pass at scale 1 (amax recorded, BatchNorm running statistics untouched, outputs overwritten below), then the
     // real one with the scales it produced
     n->f8_calib_pass = true;
     TRYI(alloc_heads(n, N));
-    int rc = 0;
-    for (int i = 0; i < npass_ && rc == 0 && train; ++i)
-      rc = backbone_forward_train(n, n->pass[i], xs[i], in_f32, N, H, W, n->triplet ? 1 : 3, st);
-    if (!train) rc = backbone_forward_eval(n, xs, npass_, in_f32, N, H, W, n->dE, st);
+    const int rc = backbone_forward(n, train, xs, in_f32, N, H, W, E, st);
     n->f8_calib_pass = false;
     if (rc) return rc;                           // not calibrated: the next forward tries again instead of running at scale 1
     n->f8_cal[train ? 0 : 1] = true;
   }
   if (n->n8 > 0) TRY(launch_fp8_scale_update(n->f8slots, n->n8, st));      // fp8 delayed scaling: last forward's amax -> this one's scales
   if (train) n->packed_eval = false;               // running statistics are about to change
-  const int npass = n->triplet ? 3 : 1;
   TRYI(alloc_heads(n, N));
-  float* E[3] = {nullptr, nullptr, nullptr};
-  const bool segs = train && npass == 3 && segments_servable(n, N, H, W);
-  if (train) n->last_segments = segs;
-  if (segs) {
-    TRYI(backbone_forward_train_segments(n, xs, in_f32, N, H, W, st));
-    for (int i = 0; i < npass; ++i) E[i] = n->pass[i].E;
-  }
-  for (int i = 0; i < npass && !segs && train; ++i) {
-    TRYI(backbone_forward_train(n, n->pass[i], xs[i], in_f32, N, H, W, n->triplet ? 1 : 3, st));
-    E[i] = n->pass[i].E;
-  }
-  if (!train) {
-    for (int i = 0; i < npass; ++i) E[i] = n->dE[i];         // borrow the dE buffers (unused in eval) for the embeddings
-    TRYI(backbone_forward_eval(n, xs, npass, in_f32, N, H, W, E, st));
-  }
+  TRYI(backbone_forward(n, train, xs, in_f32, N, H, W, E, st));
   TRYI(heads_forward(n, E, npass, N, st));
   if (feats) TRY(hipMemcpyAsync(feats, n->feats, (size_t)N * 768 * 4, hipMemcpyDeviceToDevice, st));
   if (logits) TRY(hipMemcpyAsync(logits, n->logits, (size_t)N * n->ncls * 4, hipMemcpyDeviceToDevice, st));
@@ -1869,10 +1880,7 @@ int sslcr_net_create(sslcr_ctx* c, const sslcr_net_desc* d, sslcr_net** out) {
 int sslcr_net_destroy(sslcr_net* n) {
   if (!n) return 0;
   (void)hipDeviceSynchronize();
-  n->shadow.release(); n->grads.release(); n->gnew.release(); n->heads.release(); n->descs.release(); n->f8buf.release(); n->norm_ws.release();
-  for (int i = 0; i < 3; ++i) n->pass[i].mem.release();
-  for (auto& row : n->tapbuf)
-    for (DevBuf& b : row) b.release();
+  for (DevBuf* b : n->bufs()) b->release();
   delete n;
   return 0;
 }
@@ -1887,13 +1895,7 @@ int sslcr_net_set_requires_grad(sslcr_net* n, const uint8_t* flags) {
 int sslcr_net_pack(sslcr_net* n, int mode, void* stream) {
   if (!n || !(mode & 3)) return fail("sslcr_net_pack: invalid argument");
   hipStream_t st = (hipStream_t)stream;
-  TRYI(pack_conv_layer(n, n->stem, n->bn0, mode, st));
-  for (int i = 0; i < 8; ++i) {
-    BlockL& B = n->blocks[i];
-    TRYI(pack_conv_layer(n, B.c1, B.b1, mode, st));
-    TRYI(pack_conv_layer(n, B.c2, B.b2, mode, st));
-    if (B.has_ds) TRYI(pack_conv_layer(n, B.ds, B.bd, mode, st));
-  }
+  for (const Layer& ly : n->layers) TRYI(pack_conv_layer(n, *ly.conv, *ly.bn, mode, st));
   if (mode & 1) n->packed_train = true;
   if (mode & 2) n->packed_eval = true;
   // a full re-pack is what the host asks for after it changed parameters behind the engine's back (load_state_dict, --resume):
@@ -2000,14 +2002,7 @@ int sslcr_net_grad(sslcr_net* n, int pidx, float* out, void* stream) {
   if (!n->grads.p) return fail("sslcr_net_grad: no backward has run");
   hipStream_t st = (hipStream_t)stream;
   const float* g = (const float*)n->grads.p + n->goff[pidx];
-  const ConvL* L = nullptr;
-  for (int i = 0; i < 8 && !L; ++i) {
-    BlockL& B = n->blocks[i];
-    if (B.c1.pidx == pidx) L = &B.c1;
-    else if (B.c2.pidx == pidx) L = &B.c2;
-    else if (B.has_ds && B.ds.pidx == pidx) L = &B.ds;
-  }
-  if (L) {
+  if (const ConvL* L = n->block_conv[pidx]) {
     TRY(launch_unpack_grad(g, out, L->cout, L->cin, L->k * L->k, st));
   } else {
     TRY(hipMemcpyAsync(out, g, (size_t)n->psize[pidx] * 4, hipMemcpyDeviceToDevice, st));
@@ -2081,15 +2076,11 @@ int sslcr_net_optimizer_step_groups(sslcr_net* n, const sslcr_opt_desc* groups, 
       memset(&t, 0, sizeof(t));
       t.group = grp;
       t.p = n->params[i]; t.g = (float*)n->grads.p + n->goff[i]; t.s1 = s1[i]; t.s2 = s2 ? s2[i] : nullptr; t.n = n->psize[i];
-      for (int b = 0; b < 8; ++b) {
-        BlockL& B = n->blocks[b];
-        const ConvL* L = B.c1.pidx == i ? &B.c1 : B.c2.pidx == i ? &B.c2 : (B.has_ds && B.ds.pidx == i) ? &B.ds : nullptr;
-        if (L) {
-          t.K = L->cout; t.C = L->cin; t.RS = L->k * L->k;
-          // the update writes the train-mode shadow weights of the new value (what pack_conv_layer(mode 1) would produce)
-          t.w_fwd = L->w_fwd; t.w_dgrad = L->w_dg; t.pack_dtype = n->ctx->dtype; t.dgrad_flip = (L->k == 3 && L->stride == 1);
-          ++packed_convs;
-        }
+      if (const ConvL* L = n->block_conv[i]) {
+        t.K = L->cout; t.C = L->cin; t.RS = L->k * L->k;
+        // the update writes the train-mode shadow weights of the new value (what pack_conv_layer(mode 1) would produce)
+        t.w_fwd = L->w_fwd; t.w_dgrad = L->w_dg; t.pack_dtype = n->ctx->dtype; t.dgrad_flip = (L->k == 3 && L->stride == 1);
+        ++packed_convs;
       }
       // work list: OPT_CHUNK elements per entry
       const int ti = (int)n->host_descs.size() | (t.group << OPT_CHUNK_GROUP_SHIFT);      // the chunk repeats the group (optim.hip)
@@ -2103,9 +2094,7 @@ int sslcr_net_optimizer_step_groups(sslcr_net* n, const sslcr_opt_desc* groups, 
     }
     n->ndesc = (int)n->host_descs.size();
     if (n->ndesc == 0) return 0;
-    int total_convs = 0;
-    for (int b = 0; b < 8; ++b) total_convs += n->blocks[b].has_ds ? 3 : 2;
-    n->opt_packs_all = packed_convs == total_convs;
+    n->opt_packs_all = packed_convs == kLayers - 1;      // (every layer but the stem)
     n->nchunks = (int)host_chunks.size();
     TRYI(n->chunks.ensure(host_chunks.size() * sizeof(int2)));
     TRY(hipMemcpyAsync(n->chunks.p, host_chunks.data(), host_chunks.size() * sizeof(int2), hipMemcpyHostToDevice, st));
@@ -2124,18 +2113,8 @@ int sslcr_net_optimizer_step_groups(sslcr_net* n, const sslcr_opt_desc* groups, 
   if (n->opt_packs_all) {
     // every block conv's shadow weights were rewritten with the update; only the stem's (its own K order) are left
     TRYI(pack_conv_layer(n, n->stem, n->bn0, 1, st));
-    if (n->ctx->fp8) {                 // e4m3 train packs of the updated filters (the bf16 packs were written by the update itself)
-      for (int b = 0; b < 8; ++b) {
-        ConvL* Ls[2] = {&n->blocks[b].c1, &n->blocks[b].c2};
-        for (ConvL* L : Ls) {
-          if (!L->w8_fwd) continue;
-          PackFp8Args f;
-          memset(&f, 0, sizeof(f));
-          f.w = n->params[L->pidx]; f.K = L->cout; f.C = L->cin; f.eps = 1e-5f; f.w8 = L->w8_fwd; f.w_dequant = L->dq_fwd;
-          TRY(launch_pack_fp8(f, st));
-        }
-      }
-    }
+    // e4m3 train packs of the updated filters (the bf16 packs were written by the update itself)
+    for (const Layer& ly : n->layers) TRYI(pack_fp8_layer(n, *ly.conv, *ly.bn, 1, st));
     n->packed_train = true;
   }
   return 0;
@@ -2154,19 +2133,11 @@ int sslcr_net_ema_from(sslcr_net* t, sslcr_net* s, float decay, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < t->nparams; ++i) TRY(launch_axpby(t->params[i], s->params[i], t->psize[i], decay, 0, st));
   // BN buffers are copied (deepcopy semantics for running statistics)
-  TRY(hipMemcpyAsync(t->bn_rm[0], s->bn_rm[0], 64 * 4, hipMemcpyDeviceToDevice, st));
-  TRY(hipMemcpyAsync(t->bn_rv[0], s->bn_rv[0], 64 * 4, hipMemcpyDeviceToDevice, st));
-  if (t->bn_nbt[0] && s->bn_nbt[0]) TRY(hipMemcpyAsync(t->bn_nbt[0], s->bn_nbt[0], 8, hipMemcpyDeviceToDevice, st));
-  for (int b = 0; b < 8; ++b) {
-    BlockL& B = t->blocks[b];
-    const BnL* bns[3] = {&B.b1, &B.b2, B.has_ds ? &B.bd : nullptr};
-    for (const BnL* bn : bns) {
-      if (!bn) continue;
-      TRY(hipMemcpyAsync(t->bn_rm[bn->bidx], s->bn_rm[bn->bidx], bn->C * 4, hipMemcpyDeviceToDevice, st));
-      TRY(hipMemcpyAsync(t->bn_rv[bn->bidx], s->bn_rv[bn->bidx], bn->C * 4, hipMemcpyDeviceToDevice, st));
-      if (t->bn_nbt[bn->bidx] && s->bn_nbt[bn->bidx])
-        TRY(hipMemcpyAsync(t->bn_nbt[bn->bidx], s->bn_nbt[bn->bidx], 8, hipMemcpyDeviceToDevice, st));
-    }
+  for (const Layer& ly : t->layers) {
+    const int b = ly.bn->bidx, bytes = ly.bn->C * 4;
+    TRY(hipMemcpyAsync(t->bn_rm[b], s->bn_rm[b], bytes, hipMemcpyDeviceToDevice, st));
+    TRY(hipMemcpyAsync(t->bn_rv[b], s->bn_rv[b], bytes, hipMemcpyDeviceToDevice, st));
+    if (t->bn_nbt[b] && s->bn_nbt[b]) TRY(hipMemcpyAsync(t->bn_nbt[b], s->bn_nbt[b], 8, hipMemcpyDeviceToDevice, st));
   }
   t->packed_train = false; t->packed_eval = false;
   return 0;
