@@ -29,14 +29,16 @@ extern "C" {
 #define SSLCR_BF16 1
 #define SSLCR_FP8 2   /* engine mode only (sslcr_create): bf16 storage and backward, fp8 e4m3 forward for the eligible 3x3 convs */
 
-/* the library round (12 here).  ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
+/* the library round (13 here). ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
  * 7 = sslcr_randaug_v2_slot added (nothing else changed); 8 = optimizer parameter groups, AdamW and the global gradient norm
  * (sslcr_tensor_desc.group, sslcr_opt_desc.kind 2, sslcr_optimizer_step_groups, sslcr_grad_norm, sslcr_net_optimizer_step_groups,
  * sslcr_net_grad_norm: all additive); 9 = gradient accumulation (sslcr_grad_accumulate, sslcr_net_set_grad_accumulate: additive,
  * off by default); 10 = loss options (sslcr_loss_opts, sslcr_loss_ex, sslcr_ce_denominator, sslcr_net_set_loss_opts: additive, the
  * defaults issue the launches of version 9); 11 = sslcr_randaug_v2_colour added (the hed / hsv ops of the v2 pool; additive,
  * sslcr_augv2_desc and sslcr_randaug_v2_slot are unchanged); 12 = device-resident inference: sslcr_wsi_gather and sslcr_predict added
- * (additive; sslcr_softmax_col keeps its launch and its bits). */
+ * (additive; sslcr_softmax_col keeps its launch and its bits); 13 = test-time augmentation over D4: sslcr_d4_transform,
+ * sslcr_wsi_gather_d4 and sslcr_predict_tta added (additive; sslcr_wsi_gather, sslcr_predict and their descriptors keep their launches
+ * and their bits). */
 int sslcr_version(void);
 const char* sslcr_last_error(void);
 
@@ -443,6 +445,54 @@ typedef struct sslcr_wsi_gather_desc {
   int N, RH, RW, S, fill;
 } sslcr_wsi_gather_desc;
 int sslcr_wsi_gather(const sslcr_wsi_gather_desc* d, void* stream);
+
+/* ---- test-time augmentation over the dihedral group D4 (library version >= 13): the eight flips and quarter turns of a SQUARE tile.
+ *      An orientation code g in 0..7 is f = g >> 2, a horizontal flip applied FIRST, and k = g & 3, the number of counter-clockwise
+ *      quarter turns applied SECOND; in NumPy, for t[..., S, S]:
+ *        d4(t, g) = np.rot90(t[..., ::-1] if g >> 2 else t, g & 3, axes=(-2, -1))
+ *      i.e. d4(t, g)[i][j] = t[si][sj] with (a, b) = (k & 1) ? (j, i) : (i, j), si = (k >> 1) ? S-1-a : a,
+ *      sj = ((((k + 1) >> 1) & 1) ^ f) ? S-1-b : b.  Codes 1, 3, 5, 7 are transposes.  Only the low three bits of a code are read.
+ *
+ *      sslcr_d4_transform: dst[n] = d4(src[n], orient[n]) for a batch [N][Cn][S][S] of 1-byte (the uint8 batches the stem ingests) or
+ *      4-byte (float32 batches of a host loader) elements.  Out of place only.  Any S >= 1, Cn >= 1; a byte batch whose side is no
+ *      multiple of four, or whose bases are not dword aligned, takes the per-element path of the same kernel.  No floating point, no
+ *      atomics, one launch.  Errors, decided before the launch: NULL pointers, N < 0, Cn < 1, H < 1, H != W (tiles are square),
+ *      elem_bytes outside {1, 4}, a 4-byte batch that is not 4-byte aligned, orient not 4-byte aligned, src and dst ranges that overlap.
+ *      N == 0 is a no-op.
+ *
+ *      sslcr_wsi_gather_d4: sslcr_wsi_gather writing d4(tile n, orient[n]); `fill` and tiles partly or wholly outside the region as
+ *      there, the descriptor unchanged, the same errors (plus orient alignment).  orient == NULL is sslcr_wsi_gather itself (its
+ *      launch); an all-zero orient gives the same bytes. */
+typedef struct sslcr_d4_desc {
+  const void* src;        /* [N][Cn][H][W] */
+  void* dst;              /* [N][Cn][H][W] */
+  const int32_t* orient;  /* [N] device ints, codes 0..7 */
+  int N, Cn, H, W;        /* H == W */
+  int elem_bytes;         /* 1 or 4 */
+} sslcr_d4_desc;
+int sslcr_d4_transform(const sslcr_d4_desc* d, void* stream);
+int sslcr_wsi_gather_d4(const sslcr_wsi_gather_desc* d, const int32_t* orient, void* stream);
+
+/* library version >= 13.  sslcr_predict over an ensemble of G sets of logits, p.logits = L[G][n][C] (set g at + g * n * C), in one launch:
+ *   mode 0 (probabilities)  s[i][c] = (p_0 + p_1 + ... + p_{G-1}) / (float)G   with p_g = softmax(L[g][i])[c], the device function of
+ *                           sslcr_predict; the sum left to right in fp32 with plain IEEE adds (no FMA, nothing reassociated), then ONE
+ *                           fp32 division
+ *   mode 1 (raw outputs)    the same with p_g = L[g][i][c] (a regression head)
+ *   p.scores[i][c]           = s[i][c]
+ *   p.pred[i]                = the LOWEST index of the maximum of s[i]; a NaN counts as the maximum (sslcr_predict's rule).  With G == 1
+ *                              the maximum is taken over L[0][i] as sslcr_predict takes it (the same index, except where two different
+ *                              logits round to one probability)
+ *   p.confusion[target][pred] += 1   ONCE per row, not once per member; integer atomics, rows with target outside [0, C) skipped
+ *   p.map[map_index[i]]      = s[i][col]
+ * With G == 1 (mode 0) every output has the bits of sslcr_predict.  Errors, decided before the launch: those of sslcr_predict, G outside
+ * [1, 8], mode outside {0, 1}, mode 1 combined with map, pred or confusion.  n == 0 is a no-op.  No float atomics. */
+#define SSLCR_TTA_MAX 8
+typedef struct sslcr_predict_tta_desc {
+  sslcr_predict_desc p;       /* logits: [G][n][C] */
+  int G;                      /* 1..SSLCR_TTA_MAX */
+  int mode;                   /* 0 mean of softmax probabilities, 1 mean of the raw outputs */
+} sslcr_predict_tta_desc;
+int sslcr_predict_tta(const sslcr_predict_tta_desc* d, void* stream);
 
 /* ---- device-side strong augmentation, the colour ops of the reference's RandAugment pool ("next" row f4) on a uint8 batch in HBM.
  *      As with sslcr_weak_augment the random draws stay on the host, in the reference's order (ssl_cr_histo_amd/augment.py);

@@ -77,6 +77,8 @@ WsiGatherDesc = _S("WsiGatherDesc", [("src", vp), ("xy", vp), ("dst", vp)] +
                    [(k, i32) for k in ("origin_x", "origin_y", "N", "RH", "RW", "S", "fill")])
 PredictDesc = _S("PredictDesc", [("logits", vp), ("n", i32), ("C", i32), ("target", vp), ("scores", vp), ("pred", vp), ("confusion", vp),
                                  ("col", i32), ("map", vp), ("map_index", vp), ("map_size", C.c_int64)])
+D4Desc = _S("D4Desc", [("src", vp), ("dst", vp), ("orient", vp)] + [(k, i32) for k in ("N", "Cn", "H", "W", "elem_bytes")])
+PredictTtaDesc = _S("PredictTtaDesc", [("p", PredictDesc), ("G", i32), ("mode", i32)])
 PackDesc = _S("PackDesc", [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("gamma", vp), ("beta", vp), ("rmean", vp),
                            ("rvar", vp), ("eps", f32), ("bias_out", vp)] + [(k, i32) for k in ("K", "C", "R", "S", "dgrad_flip")] + [("scale_out", vp)])
 
@@ -123,6 +125,9 @@ SIGNATURES = {
     "sslcr_softmax_col": (i32, [vp, vp, i32, i32, i32, vp]),
     "sslcr_predict": (i32, [P(PredictDesc), vp]),
     "sslcr_wsi_gather": (i32, [P(WsiGatherDesc), vp]),
+    "sslcr_wsi_gather_d4": (i32, [P(WsiGatherDesc), vp, vp]),
+    "sslcr_d4_transform": (i32, [P(D4Desc), vp]),
+    "sslcr_predict_tta": (i32, [P(PredictTtaDesc), vp]),
     "sslcr_optimizer_step": (i32, [vp, i32, i32, P(OptDesc), vp]),
     "sslcr_optimizer_step_groups": (i32, [vp, i32, i32, P(OptDesc), i32, vp, vp]),
     "sslcr_grad_norm": (i32, [vp, sz, f32, vp, vp, vp]),

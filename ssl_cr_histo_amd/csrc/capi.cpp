@@ -30,7 +30,7 @@ using namespace sslcr;
 
 extern "C" {
 
-int sslcr_version(void) { return 12; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
+int sslcr_version(void) { return 13; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
 const char* sslcr_last_error(void) { return g_err; }
 
 int sslcr_conv2d(int dtype, const sslcr_conv_desc* d, void* stream) {
@@ -204,26 +204,73 @@ int sslcr_softmax_col(const float* logits, float* out, int n, int C, int col, vo
   return check(launch_softmax_col(logits, out, n, C, col, (hipStream_t)stream), "softmax_col");
 }
 
+// the argument rules sslcr_predict and sslcr_predict_tta share; NULL = fine.  (n == 0 is a no-op the callers return from first.)
+static const char* predict_args_error(const sslcr_predict_desc& d) {
+  if (!d.logits) return "null logits";
+  if (d.confusion && !d.target) return "confusion needs target";
+  if (reinterpret_cast<uintptr_t>(d.confusion) & 7) return "confusion alignment";
+  if (d.map && !(d.map_index && d.map_size >= 0)) return "map needs map_index and map_size >= 0";
+  if (d.map && !(d.col >= 0 && d.col < d.C)) return "col outside [0, C)";
+  return nullptr;
+}
 int sslcr_predict(const sslcr_predict_desc* d, void* stream) {
   NEED(d, "null descriptor");
   NEED(d->n >= 0 && d->C >= 1 && d->C <= 64, "n >= 0 and 1 <= C <= 64");
   if (d->n == 0) return 0;
-  NEED(d->logits, "null logits");
-  NEED(!d->confusion || d->target, "confusion needs target");
-  NEED((reinterpret_cast<uintptr_t>(d->confusion) & 7) == 0, "confusion alignment");
-  NEED(!d->map || (d->map_index && d->map_size >= 0), "map needs map_index and map_size >= 0");
-  NEED(!d->map || (d->col >= 0 && d->col < d->C), "col outside [0, C)");
+  const char* why = predict_args_error(*d);
+  NEED(!why, why);
   return check(launch_predict(*d, (hipStream_t)stream), "predict");
+}
+int sslcr_predict_tta(const sslcr_predict_tta_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  NEED(d->p.n >= 0 && d->p.C >= 1 && d->p.C <= 64, "n >= 0 and 1 <= C <= 64");
+  NEED(d->G >= 1 && d->G <= SSLCR_TTA_MAX, "G outside [1, 8]");
+  NEED(d->mode == 0 || d->mode == 1, "mode outside {0, 1}");
+  NEED(d->mode == 0 || (!d->p.map && !d->p.pred && !d->p.confusion), "mode 1 (raw outputs) has no map, pred or confusion");
+  if (d->p.n == 0) return 0;
+  const char* why = predict_args_error(d->p);
+  NEED(!why, why);
+  return check(launch_predict_tta(*d, (hipStream_t)stream), "predict_tta");
+}
+// the argument rules the two gathers share
+static const char* wsi_gather_args_error(const sslcr_wsi_gather_desc& d) {
+  if (!(d.S >= 1 && d.N >= 0)) return "S >= 1 and N >= 0";
+  if (!(d.RH >= 1 && d.RW >= 1)) return "empty region";
+  if (!(d.fill >= 0 && d.fill <= 255)) return "fill outside [0, 255]";
+  if (d.N == 0) return nullptr;
+  if (!(d.src && d.xy && d.dst)) return "null tensor";
+  if (reinterpret_cast<uintptr_t>(d.xy) & 3) return "xy alignment";
+  return nullptr;
 }
 int sslcr_wsi_gather(const sslcr_wsi_gather_desc* d, void* stream) {
   NEED(d, "null descriptor");
-  NEED(d->S >= 1 && d->N >= 0, "S >= 1 and N >= 0");
-  NEED(d->RH >= 1 && d->RW >= 1, "empty region");
-  NEED(d->fill >= 0 && d->fill <= 255, "fill outside [0, 255]");
+  const char* why = wsi_gather_args_error(*d);
+  NEED(!why, why);
   if (d->N == 0) return 0;
-  NEED(d->src && d->xy && d->dst, "null tensor");
-  NEED((reinterpret_cast<uintptr_t>(d->xy) & 3) == 0, "xy alignment");
   return check(launch_wsi_gather(*d, (hipStream_t)stream), "wsi_gather");
+}
+int sslcr_wsi_gather_d4(const sslcr_wsi_gather_desc* d, const int32_t* orient, void* stream) {
+  if (!orient) return sslcr_wsi_gather(d, stream);                        // the plain gather's own launch
+  NEED(d, "null descriptor");
+  const char* why = wsi_gather_args_error(*d);
+  NEED(!why, why);
+  NEED((reinterpret_cast<uintptr_t>(orient) & 3) == 0, "orient alignment");
+  if (d->N == 0) return 0;
+  return check(launch_wsi_gather_d4(*d, orient, (hipStream_t)stream), "wsi_gather_d4");
+}
+int sslcr_d4_transform(const sslcr_d4_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  NEED(d->N >= 0 && d->Cn >= 1 && d->H >= 1, "N >= 0, Cn >= 1 and H >= 1");
+  NEED(d->H == d->W, "tiles must be square (H == W)");
+  NEED(d->elem_bytes == 1 || d->elem_bytes == 4, "elem_bytes outside {1, 4}");
+  if (d->N == 0) return 0;
+  NEED(d->src && d->dst && d->orient, "null tensor");
+  const uintptr_t s = reinterpret_cast<uintptr_t>(d->src), t = reinterpret_cast<uintptr_t>(d->dst);
+  NEED((reinterpret_cast<uintptr_t>(d->orient) & 3) == 0, "orient alignment");
+  NEED(d->elem_bytes == 1 || ((s | t) & 3) == 0, "a 4-byte batch must be 4-byte aligned");
+  const size_t bytes = (size_t)d->N * d->Cn * d->H * d->W * d->elem_bytes;
+  NEED(s + bytes <= t || t + bytes <= s, "src and dst overlap (out of place only)");
+  return check(launch_d4_transform(*d, (hipStream_t)stream), "d4_transform");
 }
 
 int sslcr_optimizer_step(const sslcr_tensor_desc* device_descs, int ntensors, int max_n, const sslcr_opt_desc* o, void* stream) {

@@ -2,6 +2,7 @@
 // Replaces nn.Linear/ReLU of models/net.py:12-15,35-36,111 (K10/K11) and F.mse_loss / F.cross_entropy /
 // softmax+max pseudo-labels of eval_BreastPathQ_SSL_CR.py:92-95, eval_Camelyon_SSL_CR.py:110-116 (K12).
 #include "kernels.hpp"
+#include "softmax_row.hpp"
 
 namespace sslcr {
 
@@ -483,15 +484,8 @@ __global__ __launch_bounds__(256) void loss_ex_kernel(const LossArgs a, const Lo
   }
 }
 
-// softmax(l[0..C-1])[col] with the row's max m and sum s = sum_c expf(l[c] - m): the ONE place this quotient is formed, shared by
-// softmax_col_kernel and predict_kernel so that a probability map has the same bits whichever entry wrote it
-__device__ __forceinline__ void softmax_row_stats(const float* l, int C, float& m, float& s) {
-  m = l[0];
-  for (int c = 1; c < C; ++c) m = fmaxf(m, l[c]);
-  s = 0.f;
-  for (int c = 0; c < C; ++c) s += expf(l[c] - m);
-}
-__device__ __forceinline__ float softmax_value(const float* l, int col, float m, float s) { return expf(l[col] - m) / s; }
+// softmax_row_stats / softmax_value (softmax_row.hpp): the ONE place the softmax quotient is formed, shared by softmax_col_kernel,
+// predict_kernel and tta.hip's predict_tta_kernel so that a probability map has the same bits whichever entry wrote it
 
 // out[i] = softmax(logits[i, :])[col] -- the 'tumor' probability of test_Camelyon16.py:58-60
 __global__ __launch_bounds__(256) void softmax_col_kernel(const float* logits, float* out, int n, int C, int col) {

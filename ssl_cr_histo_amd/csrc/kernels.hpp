@@ -200,6 +200,10 @@ hipError_t launch_softmax_col(const float* logits, float* out, int n, int C, int
 hipError_t launch_predict(const sslcr_predict_desc& a, hipStream_t st);
 // wsi.hip
 hipError_t launch_wsi_gather(const sslcr_wsi_gather_desc& a, hipStream_t st);
+// tta.hip
+hipError_t launch_wsi_gather_d4(const sslcr_wsi_gather_desc& a, const int32_t* orient, hipStream_t st);
+hipError_t launch_d4_transform(const sslcr_d4_desc& a, hipStream_t st);
+hipError_t launch_predict_tta(const sslcr_predict_tta_desc& a, hipStream_t st);
 // augment.hip
 hipError_t launch_weak_augment(const sslcr_weak_aug_desc& a, hipStream_t st);
 hipError_t launch_hed_colour(const sslcr_colour_aug_desc& a, hipStream_t st);

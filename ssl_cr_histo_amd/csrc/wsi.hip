@@ -24,19 +24,9 @@
 // Tiles that leave the region, and tile sides that are no multiple of four (or an output base that is not dword-aligned), take the
 // per-byte path of the same kernel: a bounds check per pixel, `fill` outside.  All source offsets are int64_t.
 #include "kernels.hpp"
+#include "wsi_bytes.hpp"   // wsi_fetch12, wsi_plane: shared with the oriented gather of tta.hip
 
 namespace sslcr {
-
-// bytes k = 0..11 of the three dwords d[0..2] (little endian), picked at stride 3 starting at c: one plane's four pixels
-__device__ __forceinline__ uint32_t wsi_plane(const uint32_t d[3], int c) {
-  uint32_t v = 0;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int k = 3 * e + c;
-    v |= ((d[k >> 2] >> (8 * (k & 3))) & 0xffu) << (8 * e);
-  }
-  return v;
-}
 
 __global__ __launch_bounds__(256) void wsi_gather_kernel(const sslcr_wsi_gather_desc a, const int dword_out) {
   const int S = a.S;
@@ -54,16 +44,8 @@ __global__ __launch_bounds__(256) void wsi_gather_kernel(const sslcr_wsi_gather_
     uint8_t* dst = a.dst + (n * 3 * S + i) * (size_t)S + 4 * q;            // plane 0; planes 1, 2 follow at + S * S
     const bool row_in = y >= 0 && y < a.RH;
     if (dword_out && row_in && x0 >= 0 && x0 + 4 <= a.RW) {                // (dword_out implies 4 q + 4 <= S)
-      // pointers stay derived from a.src (a global-memory kernel argument): plain global loads, not flat ones
-      const int64_t b = (y * a.RW + x0) * 3 + mis;                          // byte offset from the dword-aligned address below a.src
-      const uint32_t* w = reinterpret_cast<const uint32_t*>(a.src + ((b & ~(int64_t)3) - mis));
-      const unsigned sh = 8u * (unsigned)(b & 3);
-      const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
-      const uint32_t w3 = w[sh ? 3 : 2];                                   // aligned: the 12 bytes end with w2, and w[3] may lie past the region
       uint32_t d[3];
-      d[0] = (uint32_t)((((uint64_t)w1 << 32) | w0) >> sh);
-      d[1] = (uint32_t)((((uint64_t)w2 << 32) | w1) >> sh);
-      d[2] = (uint32_t)((((uint64_t)w3 << 32) | w2) >> sh);
+      wsi_fetch12(a.src, (y * a.RW + x0) * 3, mis, d);
 #pragma unroll
       for (int c = 0; c < 3; ++c) *reinterpret_cast<uint32_t*>(dst + c * plane) = wsi_plane(d, c);
     } else {

@@ -10,6 +10,10 @@ on the device until one copy at the end.  openslide / h5 I/O is not part of this
 region holds is the caller's statement (``fill``): openslide returns transparent pixels there, ``.convert('RGB')`` makes them black, which
 is the default 0 -- unpinned against openslide itself.
 
+Test-time augmentation.  ``d4_codes`` / ``d4_apply`` define the eight flips and quarter turns of a square tile (the dihedral group
+D4) as orientation codes 0..7; ``WsiDeviceLoader.tiles(lo, hi, orient=g)`` cuts a batch already oriented (sslcr_wsi_gather_d4), and
+``args.tta`` on the ``steps.*_test`` functions averages the scores of the listed orientations on the device (sslcr_predict_tta).
+
 Metrics.  The Kather mains build sklearn's confusion matrix and a weighted F1 from what ``test()`` returns
 (eval_Kather_SSL_CR.py:646-658, eval_Kather_SSL.py:519-530).  ``ConfusionMeter`` counts the same matrix on the device, batch by batch,
 with integer atomics; ``metrics_from_confusion`` derives the figures from it in host float64.
@@ -39,6 +43,46 @@ def gather_tiles(region_u8_hwc, xy, size, *, origin=(0, 0), fill=0, out=None):
     """uint8 NCHW tiles [N, 3, size, size] from a device-resident uint8 region [RH, RW, 3]: ``kernels.wsi_gather``.  xy: device int32
     [N, 2] level-0 (left, top); origin: level-0 coordinates of ``region[0, 0]``; fill: the value of pixels outside the region."""
     return K.wsi_gather(region_u8_hwc, xy, size, origin=origin, fill=fill, out=out)
+
+
+# ---- test-time augmentation over D4: the orientation codes of include/sslcr.h
+D4_SETS = {"d4": (0, 1, 2, 3, 4, 5, 6, 7),       # every flip and quarter turn
+           "rot90": (0, 1, 2, 3),                # the four quarter turns
+           "flips": (0, 4, 6)}                   # identity, horizontal flip, vertical flip (h-flip then a half turn)
+
+
+def d4_codes(spec):
+    """a name of ``D4_SETS`` or a sequence of codes -> the validated tuple of DISTINCT codes in 0..7, in the order given (the order
+    the ensemble is summed in).  ValueError for an unknown name, an empty sequence, a duplicate or a code outside 0..7."""
+    if isinstance(spec, str):
+        if spec not in D4_SETS:
+            raise ValueError(f"d4_codes: unknown set {spec!r} (known: {sorted(D4_SETS)})")
+        return D4_SETS[spec]
+    try:
+        raw = list(spec)
+    except TypeError:
+        raise ValueError(f"d4_codes: a set name or a sequence of codes expected, got {spec!r}") from None
+    codes = []
+    for g in raw:
+        if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or not 0 <= int(g) <= 7:
+            raise ValueError(f"d4_codes: {g!r} is not an orientation code in 0..7")
+        codes.append(int(g))
+    if not codes:
+        raise ValueError("d4_codes: no orientation given")
+    if len(set(codes)) != len(codes):
+        raise ValueError(f"d4_codes: duplicate codes in {tuple(codes)}")
+    return tuple(codes)
+
+
+def d4_apply(array, g):
+    """orientation ``g`` of square tiles ``array[..., S, S]`` (numpy, or anything ``np.asarray`` takes): a horizontal flip if
+    ``g >> 2``, THEN ``g & 3`` counter-clockwise quarter turns -- the host restatement of sslcr_d4_transform / sslcr_wsi_gather_d4."""
+    t = np.asarray(array)
+    if not 0 <= int(g) <= 7:
+        raise ValueError(f"d4_apply: {g!r} is not an orientation code in 0..7")
+    if t.ndim < 2 or t.shape[-1] != t.shape[-2]:
+        raise ValueError(f"d4_apply: square tiles [..., S, S] expected, got {t.shape}")
+    return np.ascontiguousarray(np.rot90(t[..., ::-1] if int(g) >> 2 else t, int(g) & 3, axes=(-2, -1)))
 
 
 def default_resolution(slide_wh, mask_shape):
@@ -89,6 +133,7 @@ class WsiDeviceLoader:
         self.dataset = _WsiDataset(mask, x_idcs, y_idcs, resolution, self.image_size)
         self.x_mask, self.y_mask = torch.from_numpy(x_idcs.copy()), torch.from_numpy(y_idcs.copy())
         dev = self.region.device
+        self._orient = None
         self.xy = torch.from_numpy(xy).to(dev)
         self.map_index = torch.from_numpy(x_idcs.astype(np.int64) * mask.shape[1] + y_idcs).to(dev)     # probs_map[x, y], row-major
 
@@ -99,8 +144,16 @@ class WsiDeviceLoader:
         n = len(self.dataset)
         return [(lo, min(lo + self.batch_size, n)) for lo in range(0, n, self.batch_size)]
 
-    def tiles(self, lo, hi, out=None):
-        return gather_tiles(self.region, self.xy[lo:hi], self.image_size, origin=self.origin, fill=self.fill, out=out)
+    def tiles(self, lo, hi, out=None, orient=None):
+        """tiles lo..hi of the table; orient: None (the plain gather), or ONE D4 code for the whole range (``d4_apply``)"""
+        if orient is None:
+            return gather_tiles(self.region, self.xy[lo:hi], self.image_size, origin=self.origin, fill=self.fill, out=out)
+        (g,) = d4_codes((orient,))
+        if self._orient is None:                                   # [8, batch_size] int32, row g = g: uploaded once
+            self._orient = torch.arange(8, dtype=torch.int32).repeat_interleave(self.batch_size).view(8, -1).to(self.region.device)
+        table = self._orient[g, :hi - lo] if hi - lo <= self.batch_size else torch.full((hi - lo,), g, dtype=torch.int32,
+                                                                                      device=self.region.device)
+        return K.wsi_gather(self.region, self.xy[lo:hi], self.image_size, origin=self.origin, fill=self.fill, out=out, orient=table)
 
     def __iter__(self):
         for lo, hi in self.ranges():

@@ -562,11 +562,76 @@ def predict(logits, target=None, *, scores=False, pred=True, confusion=None, col
     return out
 
 
-def wsi_gather(region, xy, size, *, origin=(0, 0), fill=0, out=None):
+def predict_tta(logits, target=None, *, mode=0, scores=False, pred=True, confusion=None, col=-1, map=None, map_index=None):
+    """``predict`` over an ensemble: fp32 logits [G, n, C] (1 <= G <= 8), one launch (sslcr_predict_tta).  mode 0: the fp32
+    left-to-right sum of the members' softmax probabilities divided by float32(G); mode 1: the same mean of the raw outputs (a
+    regression head; scores only).  ``pred`` is the lowest index of the maximum of the mean (a NaN is the maximum), the confusion
+    matrix counts every row ONCE, ``map`` receives the mean's column ``col``.  With G = 1 every output has ``predict``'s bits.  No sync."""
+    _chk(logits, target, confusion, map, map_index)
+    if logits.dtype != torch.float32 or logits.dim() != 3:
+        raise L.SslcrError("predict_tta: fp32 logits [G, n, C] expected")
+    G, n, c = logits.shape
+    if not 1 <= G <= 8:
+        raise L.SslcrError(f"predict_tta: G = {G} outside [1, 8]")
+    if not 1 <= c <= 64:
+        raise L.SslcrError(f"predict_tta: C = {c} outside [1, 64]")
+    if mode not in (0, 1):
+        raise L.SslcrError(f"predict_tta: mode = {mode} outside {{0, 1}}")
+    if mode == 1 and (pred or confusion is not None or map is not None):
+        raise L.SslcrError("predict_tta: mode 1 (raw outputs) has no map, pred or confusion")
+    dev = logits.device
+    for name, t in (("target", target), ("map_index", map_index)):
+        if t is not None and (t.dtype != torch.int64 or t.shape != (n,) or t.device != dev):
+            raise L.SslcrError(f"predict_tta: {name} must be an int64 tensor [{n}] on {dev}")
+    if confusion is not None:
+        if confusion.dtype != torch.int64 or confusion.shape != (c, c) or confusion.device != dev:
+            raise L.SslcrError(f"predict_tta: confusion must be an int64 tensor [{c}, {c}] on {dev}")
+        if target is None:
+            raise L.SslcrError("predict_tta: confusion needs target")
+    if map is not None:
+        if map.dtype != torch.float32 or map.device != dev:
+            raise L.SslcrError(f"predict_tta: map must be an fp32 tensor on {dev}")
+        if map_index is None:
+            raise L.SslcrError("predict_tta: map needs map_index")
+        if not -c <= col < c:
+            raise L.SslcrError(f"predict_tta: col = {col} outside [-{c}, {c})")
+    out = {}
+    if scores:
+        out["scores"] = torch.empty((n, c), dtype=torch.float32, device=dev)
+    if pred:
+        out["pred"] = torch.empty(n, dtype=torch.int64, device=dev)
+    p = L.PredictDesc(L.ptr(logits) if n else None, n, c, L.ptr(target), L.ptr(out.get("scores")), L.ptr(out.get("pred")), L.ptr(confusion),
+                      col % c, L.ptr(map), L.ptr(map_index), map.numel() if map is not None else 0)
+    L.check(L.lib().sslcr_predict_tta(L.PredictTtaDesc(p, G, mode), L.stream_ptr()))
+    return out
+
+
+def d4_transform(x, orient, out=None):
+    """``out[n] = d4(x[n], orient[n])`` (sslcr_d4_transform; the codes of ``inference.d4_apply``) for a uint8 or float32 device batch
+    [N, Cn, S, S]; orient: device int32 [N].  Out of place: ``out`` must not overlap ``x``.  No sync."""
+    _chk(x, orient, out)
+    if x.dtype not in (torch.uint8, torch.float32) or x.dim() != 4:
+        raise L.SslcrError("d4_transform: a uint8 or float32 batch [N, Cn, S, S] expected")
+    n, cn, h, w = x.shape
+    if h != w:
+        raise L.SslcrError(f"d4_transform: tiles must be square (got {h} x {w})")
+    if orient.dtype != torch.int32 or orient.shape != (n,) or orient.device != x.device:
+        raise L.SslcrError(f"d4_transform: orient must be an int32 tensor [{n}] on the batch's device")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.dtype != x.dtype or out.shape != x.shape or out.device != x.device:
+        raise L.SslcrError("d4_transform: out must have the batch's dtype, shape and device")
+    d = L.D4Desc(L.ptr(x) if n else None, L.ptr(out) if n else None, L.ptr(orient) if n else None, n, cn, h, w, x.element_size())
+    L.check(L.lib().sslcr_d4_transform(d, L.stream_ptr()))
+    return out
+
+
+def wsi_gather(region, xy, size, *, origin=(0, 0), fill=0, out=None, orient=None):
     """uint8 tiles [N, 3, size, size] cut from ONE device-resident slide region, uint8 [RH, RW, 3] (sslcr_wsi_gather):
     ``out[n, c, i, j] = region[top - origin[1] + i, left - origin[0] + j, c]`` with (left, top) = xy[n] (device int32 [N, 2], level-0
-    coordinates; origin = those of region[0, 0]), ``fill`` where the pixel lies outside the region.  No sync."""
-    _chk(region, xy, out)
+    coordinates; origin = those of region[0, 0]), ``fill`` where the pixel lies outside the region.  orient: None, or a device int32
+    [N] of D4 codes -- tile n is written as ``d4(tile, orient[n])`` (sslcr_wsi_gather_d4; ``inference.d4_apply``).  No sync."""
+    _chk(region, xy, out, orient)
     if region.dtype != torch.uint8 or region.dim() != 3 or region.shape[2] != 3:
         raise L.SslcrError("wsi_gather: a uint8 region [RH, RW, 3] expected")
     if xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or xy.device != region.device:
@@ -583,7 +648,13 @@ def wsi_gather(region, xy, size, *, origin=(0, 0), fill=0, out=None):
         raise L.SslcrError(f"wsi_gather: out must be a uint8 tensor [{n}, 3, {size}, {size}] on the region's device")
     d = L.WsiGatherDesc(L.ptr(region), L.ptr(xy) if n else None, L.ptr(out) if n else None, int(origin[0]), int(origin[1]), n, RH, RW, size,
                         int(fill))
-    L.check(L.lib().sslcr_wsi_gather(d, L.stream_ptr()))
+    if orient is None:
+        L.check(L.lib().sslcr_wsi_gather(d, L.stream_ptr()))
+        return out
+    if orient.dtype != torch.int32 or orient.shape != (n,) or orient.device != region.device:
+        raise L.SslcrError(f"wsi_gather: orient must be an int32 tensor [{n}] on the region's device")
+    if n:
+        L.check(L.lib().sslcr_wsi_gather_d4(d, L.ptr(orient), L.stream_ptr()))
     return out
 
 

@@ -622,12 +622,81 @@ def last_test_confusion():
     return _last_test["confusion"]
 
 
+def _tta_codes(args):
+    """args.tta: a name of ``inference.D4_SETS`` ('d4', 'rot90', 'flips') or a sequence of distinct orientation codes 0..7 -> the tuple
+    of codes; absent or None = None: the code path of every earlier version, launch for launch."""
+    spec = getattr(args, "tta", None)
+    if spec is None:
+        return None
+    from .inference import d4_codes
+    return d4_codes(spec)
+
+
+class _Orientations:
+    """the members of a host-fed batch: uploaded ONCE (``Engine.as_input``), then oriented on the device, one sslcr_d4_transform per
+    listed code (code 0 is the batch itself).  Non-square inputs raise before any launch."""
+
+    def __init__(self, eng, codes):
+        self.eng, self.codes, self._table = eng, codes, None
+
+    def members(self, input):
+        from . import kernels as K
+        x = input if torch.is_tensor(input) else torch.as_tensor(input)
+        if x.dim() != 4 or x.shape[-1] != x.shape[-2]:
+            raise ValueError(f"args.tta: square tiles [n, 3, S, S] expected, got a batch of shape {tuple(x.shape)}")
+        x = self.eng.as_input(x)
+        n = x.shape[0]
+        if self._table is None or self._table.shape[1] < n:          # [8, n] int32, row g = g
+            self._table = torch.arange(8, dtype=torch.int32).repeat_interleave(n).view(8, n).to(self.eng.device)
+        for g in self.codes:
+            yield x if g == 0 else K.d4_transform(x, self._table[g, :n])
+
+    def logits(self, net, input, first_step):
+        """-> ([G, n, C] logits of one batch, member g in slot g; the result of ``first_step(x)``): the FIRST listed orientation
+        goes through the loop's own eval step (its loss and meters), the others through the same eval forward alone -- G passes
+        over one batch layout, so every slot has the bits the plain path gives for host-oriented tiles."""
+        ens = r = None
+        for k, x in enumerate(self.members(input)):
+            if k == 0:
+                r = first_step(x)
+                logits = r["logits"]
+                ens = torch.empty((len(self.codes),) + tuple(logits.shape), dtype=torch.float32, device=self.eng.device)
+            else:
+                logits = net.forward((x,), train=False)[1]
+            ens[k].copy_(logits)
+        return ens, r
+
+
+def _bpq_test_tta(args, net, eng, test_loader, codes):
+    """``_bpq_test`` over the orientations ``codes``: ``outputs`` is the mode-1 mean of sslcr_predict_tta (the fp32 left-to-right sum of
+    the members' outputs divided by float32(G)); the printed loss meter and ``feats`` are those of the FIRST listed orientation."""
+    from . import kernels as K
+    meters = _meters(eng, ["loss"])
+    orient = _Orientations(eng, codes)
+    outputs, feats, targets_a, targets_b = [], [], [], []
+    t0 = time.time()
+    for batch_idx, (input, targetA, targetB) in enumerate(_ahead(test_loader, eng, _prefetch_on(args))):
+        targetA, targetB = targetA.float().to(eng.device), targetB.float().to(eng.device)
+        ens, r = orient.logits(net, input, lambda x: eng.step_supervised(net, "mse", [x], targetA.reshape(-1), train=False))
+        meters.add(r["losses"], targetA.size(0))
+        feats.append(r["feats"])
+        outputs.append(K.predict_tta(ens, mode=1, scores=True, pred=False)["scores"].reshape(-1))
+        targets_a.append(targetA)
+        targets_b.append(targetB)
+        _maybe_print(args, batch_idx, "Test", 0, _len(test_loader), t0, meters)
+    _last_test["confusion"] = None
+    return tuple(torch.cat(v).detach().to("cpu") for v in (outputs, feats, targets_a, targets_b))
+
+
 def _bpq_test(args, model, classifier, test_loader, where):
     _loss_options(args, mse=where)
+    codes = _tta_codes(args)
     eng = get_engine(_device_of(model))
     model.eval()
     classifier.eval()
     net = eng.bind(model, classifier)
+    if codes is not None:
+        return _bpq_test_tta(args, net, eng, test_loader, codes)
     meters = _meters(eng, ["loss"])
     outputs, feats, targets_a, targets_b = [], [], [], []
     t0 = time.time()
@@ -645,12 +714,16 @@ def _bpq_test(args, model, classifier, test_loader, where):
 
 
 def bpq_test(args, model_student, classifier_student, test_loader):
-    """eval_BreastPathQ_SSL_CR.test (:178-242) -> (outputs [n], feats [n, 768], targetsA, targetsB) on the CPU."""
+    """eval_BreastPathQ_SSL_CR.test (:178-242) -> (outputs [n], feats [n, 768], targetsA, targetsB) on the CPU.
+
+    ``args.tta`` (see ``camelyon16_test``): ``outputs`` is the mean of the regression outputs over the listed orientations (mode 1
+    of sslcr_predict_tta).  The printed loss meter and ``feats`` are those of the FIRST listed orientation: features are not averaged."""
     return _bpq_test(args, model_student, classifier_student, test_loader, "bpq_test")
 
 
 def bpq_sup_test(args, model, classifier, criterion, test_loader):
-    """eval_BreastPathQ_SSL.test (:152-216; ``criterion`` before the loader, as there) -> (outputs, feats, targetsA, targetsB)."""
+    """eval_BreastPathQ_SSL.test (:152-216; ``criterion`` before the loader, as there) -> (outputs, feats, targetsA, targetsB).
+    ``args.tta``: as ``bpq_test`` (mean outputs; loss meter and ``feats`` of the first listed orientation)."""
     if criterion is not None and not isinstance(criterion, torch.nn.MSELoss):
         raise NotImplementedError("the reference tests BreastPathQ with nn.MSELoss")
     return _bpq_test(args, model, classifier, test_loader, "bpq_sup_test")
@@ -658,6 +731,7 @@ def bpq_sup_test(args, model, classifier, criterion, test_loader):
 
 def _cls_test(args, model, classifier, test_loader, want_scores):
     from . import kernels as K
+    codes = _tta_codes(args)
     eng = get_engine(_device_of(model))
     model.eval()
     classifier.eval()
@@ -665,13 +739,19 @@ def _cls_test(args, model, classifier, test_loader, want_scores):
     meters = _meters(eng, ["loss", "acc"])
     opts = _loss_options(args)
     confusion = torch.zeros((net.ncls, net.ncls), dtype=torch.int64, device=eng.device)
+    orient = _Orientations(eng, codes) if codes is not None else None
     preds, targets, scores = [], [], []
     t0 = time.time()
     for batch_idx, (input, target) in enumerate(_ahead(test_loader, eng, _prefetch_on(args))):
         target = target.long().reshape(-1).to(eng.device).contiguous()
-        r = _val_step(eng, net, [input], target, opts)
-        meters.add(r["losses"], target.size(0))
-        p = K.predict(r["logits"], target, scores=want_scores, pred=True, confusion=confusion)
+        if orient is not None:
+            ens, r = orient.logits(net, input, lambda x: _val_step(eng, net, [x], target, opts))
+            meters.add(r["losses"], target.size(0))
+            p = K.predict_tta(ens, target, scores=want_scores, pred=True, confusion=confusion)
+        else:
+            r = _val_step(eng, net, [input], target, opts)
+            meters.add(r["losses"], target.size(0))
+            p = K.predict(r["logits"], target, scores=want_scores, pred=True, confusion=confusion)
         preds.append(p["pred"])
         targets.append(target)
         if want_scores:
@@ -685,28 +765,41 @@ def _cls_test(args, model, classifier, test_loader, want_scores):
 
 
 def kather_cr_test(args, model, classifier, test_loader):
-    """eval_Kather_SSL_CR.test (:182-245) -> (predictions int64 [n], targets int64 [n], pred_score [n, 9]) on the CPU."""
+    """eval_Kather_SSL_CR.test (:182-245) -> (predictions int64 [n], targets int64 [n], pred_score [n, 9]) on the CPU.
+
+    ``args.tta`` (see ``camelyon16_test``): ``pred_score`` is the mean softmax over the listed orientations, ``predictions`` its
+    argmax (lowest index), and ``last_test_confusion()`` counts those predictions, once per image.  The printed loss and accuracy
+    meters are those of the FIRST listed orientation."""
     return _cls_test(args, model, classifier, test_loader, True)
 
 
 def kather_sup_test(args, model, classifier, test_loader, criterion):
-    """eval_Kather_SSL.test (:154-213; ``criterion`` last, as there) -> (predictions, targets)."""
+    """eval_Kather_SSL.test (:154-213; ``criterion`` last, as there) -> (predictions, targets).  ``args.tta``: as ``kather_cr_test``
+    (ensemble predictions; the meters are the first listed orientation's)."""
     _plain_ce(criterion, "Kather test (eval_Kather_SSL.py:154-213)")
     return _cls_test(args, model, classifier, test_loader, False)
 
 
 # ------------------------------------------------------------------------------------------------ WSI inference (f3)
-def _camelyon16_test_device(args, net, loader):
+def _camelyon16_test_device(args, net, loader, codes=None):
     """the device-resident loader: per batch a tile gather, the eval forward and the softmax column scattered into the map, all on
-    the current stream; no host sync and no device-to-host copy before the one copy of the finished map."""
+    the current stream; no host sync and no device-to-host copy before the one copy of the finished map.  codes (args.tta): per
+    batch and per listed orientation one oriented gather (sslcr_wsi_gather_d4) and one eval forward into slot g of a [G, n, C]
+    logits buffer, then ONE sslcr_predict_tta into the map -- still no sync, still one copy."""
     import numpy as np
     from . import kernels as K
     mask = loader.dataset.mask
     probs = torch.zeros(mask.shape, dtype=torch.float32, device=loader.region.device)
     t0 = time.time()
     for batch_idx, (lo, hi) in enumerate(loader.ranges()):
-        _, output = net.forward((loader.tiles(lo, hi),), train=False)
-        K.predict(output, pred=False, col=-1, map=probs, map_index=loader.map_index[lo:hi])       # second column 'tumor' (:58-62)
+        if codes is not None:
+            ens = torch.empty((len(codes), hi - lo, net.ncls), dtype=torch.float32, device=loader.region.device)
+            for k, g in enumerate(codes):
+                ens[k].copy_(net.forward((loader.tiles(lo, hi, orient=g),), train=False)[1])
+            K.predict_tta(ens, pred=False, col=-1, map=probs, map_index=loader.map_index[lo:hi])
+        else:
+            _, output = net.forward((loader.tiles(lo, hi),), train=False)
+            K.predict(output, pred=False, col=-1, map=probs, map_index=loader.map_index[lo:hi])   # second column 'tumor' (:58-62)
         if (batch_idx + 1) % 10 == 0 and getattr(args, "print_freq", 0):
             print("Test: [{0}/{1}]\tBT {2:.3f} (enqueue)".format(batch_idx, len(loader), (time.time() - t0) / (batch_idx + 1)))
     return probs.cpu().numpy().astype(np.float64)
@@ -715,21 +808,32 @@ def _camelyon16_test_device(args, net, loader):
 def camelyon16_test(args, model, classifier, test_loader):
     """test_Camelyon16.test (test_Camelyon16.py:30-70) -> probs_map: every tissue pixel of ``test_loader.dataset.mask``
     gets the softmax 'tumor' probability of its tile; forward-only (BatchNorm folded, all epilogues fused).  An
-    ``inference.WsiDeviceLoader`` is served from the slide bytes it holds in HBM (same map, no per-batch host traffic)."""
+    ``inference.WsiDeviceLoader`` is served from the slide bytes it holds in HBM (same map, no per-batch host traffic).
+
+    ``args.tta`` (a name of ``inference.D4_SETS`` or a sequence of orientation codes; absent or None = off): every tile is scored
+    under each listed flip / quarter turn and the map holds the mean 'tumor' probability -- the fp32 sum of the members in the order
+    listed, divided by float32(G) (sslcr_predict_tta).  Square tiles only; a host-fed batch is uploaded once and oriented on the
+    device."""
     import numpy as np
     from . import kernels as K
     from .inference import WsiDeviceLoader
+    codes = _tta_codes(args)
     eng = get_engine(_device_of(model))
     model.eval()
     classifier.eval()
     net = eng.bind(model, classifier)
     if isinstance(test_loader, WsiDeviceLoader):
-        return _camelyon16_test_device(args, net, test_loader)
+        return _camelyon16_test_device(args, net, test_loader, codes)
+    orient = _Orientations(eng, codes) if codes is not None else None
     probs_map = np.zeros(test_loader.dataset.mask.shape)
     t0 = time.time()
     for batch_idx, (input, x_mask, y_mask) in enumerate(_ahead(test_loader, eng, _prefetch_on(args))):
-        _, output = net.forward((input,), train=False)
-        probs = K.softmax_col(output.contiguous(), -1).cpu().numpy()        # second column 'tumor' (:58-60)
+        if orient is not None:
+            ens, _ = orient.logits(net, input, lambda x: dict(logits=net.forward((x,), train=False)[1]))
+            probs = K.predict_tta(ens, scores=True, pred=False)["scores"][:, -1].cpu().numpy()
+        else:
+            _, output = net.forward((input,), train=False)
+            probs = K.softmax_col(output.contiguous(), -1).cpu().numpy()    # second column 'tumor' (:58-60)
         probs_map[x_mask.numpy(), y_mask.numpy()] = probs
         if (batch_idx + 1) % 10 == 0 and getattr(args, "print_freq", 0):
             print("Test: [{0}/{1}]\tBT {2:.3f}".format(batch_idx, _len(test_loader), (time.time() - t0) / (batch_idx + 1)))
