@@ -29,7 +29,7 @@ extern "C" {
 #define SSLCR_BF16 1
 #define SSLCR_FP8 2   /* engine mode only (sslcr_create): bf16 storage and backward, fp8 e4m3 forward for the eligible 3x3 convs */
 
-/* the library round (13 here). ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
+/* the library round (14 here). ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
  * 7 = sslcr_randaug_v2_slot added (nothing else changed); 8 = optimizer parameter groups, AdamW and the global gradient norm
  * (sslcr_tensor_desc.group, sslcr_opt_desc.kind 2, sslcr_optimizer_step_groups, sslcr_grad_norm, sslcr_net_optimizer_step_groups,
  * sslcr_net_grad_norm: all additive); 9 = gradient accumulation (sslcr_grad_accumulate, sslcr_net_set_grad_accumulate: additive,
@@ -38,7 +38,8 @@ extern "C" {
  * sslcr_augv2_desc and sslcr_randaug_v2_slot are unchanged); 12 = device-resident inference: sslcr_wsi_gather and sslcr_predict added
  * (additive; sslcr_softmax_col keeps its launch and its bits); 13 = test-time augmentation over D4: sslcr_d4_transform,
  * sslcr_wsi_gather_d4 and sslcr_predict_tta added (additive; sslcr_wsi_gather, sslcr_predict and their descriptors keep their launches
- * and their bits). */
+ * and their bits); 14 = tile mining for RSP pretraining: sslcr_tissue_bits, sslcr_lab_a_sum, sslcr_tile_popcount and sslcr_rsp_gather
+ * added (additive; no existing entry, descriptor or launch changes). */
 int sslcr_version(void);
 const char* sslcr_last_error(void);
 
@@ -493,6 +494,91 @@ typedef struct sslcr_predict_tta_desc {
   int mode;                   /* 0 mean of softmax probabilities, 1 mean of the raw outputs */
 } sslcr_predict_tta_desc;
 int sslcr_predict_tta(const sslcr_predict_tta_desc* d, void* stream);
+
+/* ---- device-side tile mining for RSP pretraining (library version >= 14): Vectorize_WSIs.get_wsi_patches + sorted_sequence
+ *      (dataset.py:27-70, 386-446 with util.py:18-23; Pretraining_v2/dataset.py:22-60, 219-316 with Pretraining_v2/util.py:9-13) on
+ *      pyramid levels that already sit in HBM as uint8 [H][W][3], the PIL / numpy layout.  Four entries, all asynchronous, no host sync
+ *      between them, no floating-point atomics.
+ *
+ *      sslcr_tissue_bits: the per-pixel predicate of isforeground() (util.py:20-21, Pretraining_v2/util.py:11-12), one bit per pixel:
+ *      bit (x & 31) of dword bits[y * pitch + (x >> 5)] is pixel (x, y); pitch >= ceil(W / 32) dwords; every dword of a row below the
+ *      pitch is written and pad bits are zero.
+ *        mode SSLCR_TISSUE_HSV_S  s > threshold with skimage 0.15 rgb2hsv's s in float64: a = u8 * (1.0 / 255), v = max, delta = max - min,
+ *                                 s = delta / v, 0 where delta == 0.  Correctly rounded operations only: the plane EQUALS a NumPy restatement.
+ *        mode SSLCR_TISSUE_LAB_A  a* > threshold with skimage 0.15 rgb2lab's a* (D65, 2 degree observer) in float64: lin[u8] per channel
+ *                                 (the 256-entry table of c > 0.04045 ? ((c + 0.055) / 1.055) ** 2.4 : c / 12.92, computed by the host),
+ *                                 X, Y from rows (0.412453, 0.357580, 0.180423), (0.212671, 0.715160, 0.072169), / (0.95047, 1.0),
+ *                                 f(t) = t > 0.008856 ? t ** (1/3) : 7.787 t + 16/116, a* = 500 (f(X) - f(Y)).  pow is the device's
+ *                                 (a few ulp): the plane equals a float64 restatement wherever |a* - threshold| exceeds ~1e-12.
+ *                                 (A float32 evaluation, error < 9e-4, decides the pixels farther than 1/64 from the threshold; the
+ *                                 float64 chain decides the rest.)
+ *      threshold: d->threshold, or -- thr_sum != NULL -- factor * (*thr_sum / count) read on the device: (1 + mu_percent) * mean a* of
+ *      the overview image (util.py:21 with dataset.py:402-403), thr_sum written by sslcr_lab_a_sum earlier on the same stream.
+ *      Errors, decided before the launch: NULL pointers, H < 1, W < 1, pitch < ceil(W / 32), mode outside {0, 1}, mode 1 without lin,
+ *      thr_sum with count <= 0, bits / lin / thr_sum misaligned. */
+#define SSLCR_TISSUE_HSV_S 0
+#define SSLCR_TISSUE_LAB_A 1
+typedef struct sslcr_tissue_bits_desc {
+  const uint8_t* img;       /* [H][W][3] */
+  uint32_t* bits;           /* [H][pitch] dwords */
+  const double* lin;        /* mode 1: [256] device doubles; unused in mode 0 */
+  const double* thr_sum;    /* NULL, or one device double: threshold = factor * (*thr_sum / count) */
+  double threshold;         /* used when thr_sum == NULL */
+  double factor, count;     /* used when thr_sum != NULL */
+  int H, W, pitch, mode;
+} sslcr_tissue_bits_desc;
+int sslcr_tissue_bits(const sslcr_tissue_bits_desc* d, void* stream);
+
+/*      sslcr_lab_a_sum: *sum = the sum of a* (as above) over a uint8 [H][W][3] image, the numerator of np.mean(lab[..., 1])
+ *      (dataset.py:400-403).  Deterministic: SSLCR_LAB_SUM_PARTIALS workgroups own fixed contiguous pixel slices and fold them in a
+ *      fixed tree into partials[], a second stage folds the partials in a fixed order: two runs give the same bits.  Errors: NULL
+ *      pointers, H < 1, W < 1, lin / partials / sum not 8-byte aligned. */
+#define SSLCR_LAB_SUM_PARTIALS 1024
+typedef struct sslcr_lab_a_sum_desc {
+  const uint8_t* img;       /* [H][W][3] */
+  const double* lin;        /* [256] device doubles */
+  double* partials;         /* workspace, [SSLCR_LAB_SUM_PARTIALS] doubles, overwritten */
+  double* sum;              /* one device double */
+  int H, W;
+} sslcr_lab_a_sum_desc;
+int sslcr_lab_a_sum(const sslcr_lab_a_sum_desc* d, void* stream);
+
+/*      sslcr_tile_popcount: the candidate grid of get_wsi_patches (dataset.py:424-425) over a bit plane of an H x W image,
+ *      ypos_j = sh (j + 1) in range(sh, H - 1 - ph, sh), xpos_i = sw (i + 1) in range(sw, W - 1 - pw, sw):
+ *        count[j][i] = set bits of the ph x pw window at (xpos_i, ypos_j)           = np.count_nonzero (util.py:23)
+ *        keep[j][i]  = (double)count / (double)(ph * pw) >= thresh                  the reference's division and comparison
+ *      ny, nx must be the lengths of the two ranges (0 where a range is empty; an empty grid is a no-op).  Errors: NULL pointers,
+ *      H, W, ph, pw, sh, sw < 1, pitch < ceil(W / 32), ny / nx not the lengths of the ranges, bits / count misaligned. */
+typedef struct sslcr_tile_popcount_desc {
+  const uint32_t* bits;     /* [H][pitch] dwords, as sslcr_tissue_bits writes them */
+  int32_t* count;           /* [ny][nx] */
+  uint8_t* keep;            /* [ny][nx], 0 / 1 */
+  double thresh;
+  int H, W, pitch, ph, pw, sh, sw, ny, nx;
+} sslcr_tile_popcount_desc;
+int sslcr_tile_popcount(const sslcr_tile_popcount_desc* d, void* stream);
+
+/*      sslcr_rsp_gather: the tiles of Vectorize_WSIs.__getitem__ (dataset.py:335-384, Pretraining_v2/dataset.py:234-266) with
+ *      sorted_sequence (dataset.py:27-70) applied, for a batch of sample indices, in ONE launch.  Sample k of the virtual dataset of
+ *      6 T samples is triplet k / 6 under ordering k % 6 of [[0,1,2],[0,2,1],[1,2,0],[1,0,2],[2,0,1],[2,1,0]] over (hr, lr1, lr2) =
+ *      levels (0, 1, 2); with k = idx[n], o = ordering k % 6, l = o[s]:
+ *        dst[s][n][c][i][j] = src[l][top + i][left + j][c]   with (left, top) = xy[l][k / 6], `fill` outside level l     s = 0, 1, 2
+ *        label[n]           = k % 6
+ *      The six-fold copy sorted_sequence builds is never materialised.  sslcr_wsi_gather's kernel body per output: dword stores where
+ *      S % 4 == 0 and the three bases are dword aligned, its per-byte path otherwise and for tiles that leave a level.  An index outside
+ *      [0, 6 T) reads nothing: three `fill` tiles, label -1.  A byte gather: no floating point, no atomics.  Errors, decided before the
+ *      launch: NULL pointers, S < 1, N < 0, T < 1, RH / RW < 1, fill outside [0, 255], xy not 4-byte / idx, label not 8-byte aligned.
+ *      N == 0 is a no-op. */
+typedef struct sslcr_rsp_gather_desc {
+  const uint8_t* src[3];    /* level l: [RH[l]][RW[l]][3] */
+  const int32_t* xy[3];     /* level l: [T][2] device ints, (left, top) in the pixels of level l */
+  const int64_t* idx;       /* [N] device int64: sample indices in [0, 6 T) */
+  uint8_t* dst[3];          /* Data_1, Data_2, Data_3: [N][3][S][S] each */
+  int64_t* label;           /* [N] */
+  int RH[3], RW[3];
+  int T, N, S, fill;
+} sslcr_rsp_gather_desc;
+int sslcr_rsp_gather(const sslcr_rsp_gather_desc* d, void* stream);
 
 /* ---- device-side strong augmentation, the colour ops of the reference's RandAugment pool ("next" row f4) on a uint8 batch in HBM.
  *      As with sslcr_weak_augment the random draws stay on the host, in the reference's order (ssl_cr_histo_amd/augment.py);

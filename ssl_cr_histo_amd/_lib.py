@@ -79,6 +79,14 @@ PredictDesc = _S("PredictDesc", [("logits", vp), ("n", i32), ("C", i32), ("targe
                                  ("col", i32), ("map", vp), ("map_index", vp), ("map_size", C.c_int64)])
 D4Desc = _S("D4Desc", [("src", vp), ("dst", vp), ("orient", vp)] + [(k, i32) for k in ("N", "Cn", "H", "W", "elem_bytes")])
 PredictTtaDesc = _S("PredictTtaDesc", [("p", PredictDesc), ("G", i32), ("mode", i32)])
+TissueBitsDesc = _S("TissueBitsDesc", [("img", vp), ("bits", vp), ("lin", vp), ("thr_sum", vp), ("threshold", f64), ("factor", f64),
+                                       ("count", f64)] + [(k, i32) for k in ("H", "W", "pitch", "mode")])
+LAB_SUM_PARTIALS = 1024       # SSLCR_LAB_SUM_PARTIALS
+LabASumDesc = _S("LabASumDesc", [("img", vp), ("lin", vp), ("partials", vp), ("sum", vp), ("H", i32), ("W", i32)])
+TilePopcountDesc = _S("TilePopcountDesc", [("bits", vp), ("count", vp), ("keep", vp), ("thresh", f64)] +
+                      [(k, i32) for k in ("H", "W", "pitch", "ph", "pw", "sh", "sw", "ny", "nx")])
+RspGatherDesc = _S("RspGatherDesc", [("src", vp * 3), ("xy", vp * 3), ("idx", vp), ("dst", vp * 3), ("label", vp), ("RH", i32 * 3),
+                                     ("RW", i32 * 3)] + [(k, i32) for k in ("T", "N", "S", "fill")])
 PackDesc = _S("PackDesc", [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("gamma", vp), ("beta", vp), ("rmean", vp),
                            ("rvar", vp), ("eps", f32), ("bias_out", vp)] + [(k, i32) for k in ("K", "C", "R", "S", "dgrad_flip")] + [("scale_out", vp)])
 
@@ -128,6 +136,10 @@ SIGNATURES = {
     "sslcr_wsi_gather_d4": (i32, [P(WsiGatherDesc), vp, vp]),
     "sslcr_d4_transform": (i32, [P(D4Desc), vp]),
     "sslcr_predict_tta": (i32, [P(PredictTtaDesc), vp]),
+    "sslcr_tissue_bits": (i32, [P(TissueBitsDesc), vp]),
+    "sslcr_lab_a_sum": (i32, [P(LabASumDesc), vp]),
+    "sslcr_tile_popcount": (i32, [P(TilePopcountDesc), vp]),
+    "sslcr_rsp_gather": (i32, [P(RspGatherDesc), vp]),
     "sslcr_optimizer_step": (i32, [vp, i32, i32, P(OptDesc), vp]),
     "sslcr_optimizer_step_groups": (i32, [vp, i32, i32, P(OptDesc), i32, vp, vp]),
     "sslcr_grad_norm": (i32, [vp, sz, f32, vp, vp, vp]),

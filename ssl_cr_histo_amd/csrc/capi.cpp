@@ -30,7 +30,7 @@ using namespace sslcr;
 
 extern "C" {
 
-int sslcr_version(void) { return 13; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
+int sslcr_version(void) { return 14; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
 const char* sslcr_last_error(void) { return g_err; }
 
 int sslcr_conv2d(int dtype, const sslcr_conv_desc* d, void* stream) {
@@ -257,6 +257,57 @@ int sslcr_wsi_gather_d4(const sslcr_wsi_gather_desc* d, const int32_t* orient, v
   NEED((reinterpret_cast<uintptr_t>(orient) & 3) == 0, "orient alignment");
   if (d->N == 0) return 0;
   return check(launch_wsi_gather_d4(*d, orient, (hipStream_t)stream), "wsi_gather_d4");
+}
+// ---- tile mining for RSP pretraining (mining.hip)
+static int grid_len(int size, int tile, int stride) {                      // len(range(stride, size - 1 - tile, stride))
+  const int64_t stop = (int64_t)size - 1 - tile;
+  return stop > stride ? (int)((stop - stride + stride - 1) / stride) : 0;
+}
+int sslcr_tissue_bits(const sslcr_tissue_bits_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  NEED(d->H >= 1 && d->W >= 1, "empty image");
+  NEED(d->pitch >= (d->W + 31) / 32, "pitch < ceil(W / 32)");
+  NEED(d->mode == SSLCR_TISSUE_HSV_S || d->mode == SSLCR_TISSUE_LAB_A, "mode outside {0, 1}");
+  NEED(d->img && d->bits, "null tensor");
+  NEED((reinterpret_cast<uintptr_t>(d->bits) & 3) == 0, "bits alignment");
+  NEED(d->mode != SSLCR_TISSUE_LAB_A || d->lin, "mode lab_a needs lin");
+  NEED(((reinterpret_cast<uintptr_t>(d->lin) | reinterpret_cast<uintptr_t>(d->thr_sum)) & 7) == 0, "lin / thr_sum alignment");
+  NEED(!d->thr_sum || d->count > 0.0, "thr_sum needs count > 0");
+  return check(launch_tissue_bits(*d, (hipStream_t)stream), "tissue_bits");
+}
+int sslcr_lab_a_sum(const sslcr_lab_a_sum_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  NEED(d->H >= 1 && d->W >= 1, "empty image");
+  NEED(d->img && d->lin && d->partials && d->sum, "null tensor");
+  NEED(((reinterpret_cast<uintptr_t>(d->lin) | reinterpret_cast<uintptr_t>(d->partials) | reinterpret_cast<uintptr_t>(d->sum)) & 7) == 0,
+       "lin / partials / sum alignment");
+  return check(launch_lab_a_sum(*d, (hipStream_t)stream), "lab_a_sum");
+}
+int sslcr_tile_popcount(const sslcr_tile_popcount_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  NEED(d->H >= 1 && d->W >= 1, "empty image");
+  NEED(d->ph >= 1 && d->pw >= 1 && d->sh >= 1 && d->sw >= 1, "tile and stride >= 1");
+  NEED(d->pitch >= (d->W + 31) / 32, "pitch < ceil(W / 32)");
+  NEED(d->ny == grid_len(d->H, d->ph, d->sh) && d->nx == grid_len(d->W, d->pw, d->sw), "ny / nx are not the lengths of the grid's ranges");
+  if (d->ny == 0 || d->nx == 0) return 0;
+  NEED((int64_t)d->ny * d->nx < (int64_t)1 << 31, "grid too large");
+  NEED(d->bits && d->count && d->keep, "null tensor");
+  NEED(((reinterpret_cast<uintptr_t>(d->bits) | reinterpret_cast<uintptr_t>(d->count)) & 3) == 0, "bits / count alignment");
+  return check(launch_tile_popcount(*d, (hipStream_t)stream), "tile_popcount");
+}
+int sslcr_rsp_gather(const sslcr_rsp_gather_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  NEED(d->S >= 1 && d->N >= 0 && d->T >= 1, "S >= 1, N >= 0 and T >= 1");
+  for (int l = 0; l < 3; ++l) NEED(d->RH[l] >= 1 && d->RW[l] >= 1, "empty level");
+  NEED(d->fill >= 0 && d->fill <= 255, "fill outside [0, 255]");
+  if (d->N == 0) return 0;
+  NEED(d->idx && d->label, "null tensor");
+  for (int l = 0; l < 3; ++l) {
+    NEED(d->src[l] && d->xy[l] && d->dst[l], "null tensor");
+    NEED((reinterpret_cast<uintptr_t>(d->xy[l]) & 3) == 0, "xy alignment");
+  }
+  NEED(((reinterpret_cast<uintptr_t>(d->idx) | reinterpret_cast<uintptr_t>(d->label)) & 7) == 0, "idx / label alignment");
+  return check(launch_rsp_gather(*d, (hipStream_t)stream), "rsp_gather");
 }
 int sslcr_d4_transform(const sslcr_d4_desc* d, void* stream) {
   NEED(d, "null descriptor");

@@ -204,6 +204,11 @@ hipError_t launch_wsi_gather(const sslcr_wsi_gather_desc& a, hipStream_t st);
 hipError_t launch_wsi_gather_d4(const sslcr_wsi_gather_desc& a, const int32_t* orient, hipStream_t st);
 hipError_t launch_d4_transform(const sslcr_d4_desc& a, hipStream_t st);
 hipError_t launch_predict_tta(const sslcr_predict_tta_desc& a, hipStream_t st);
+// mining.hip
+hipError_t launch_tissue_bits(const sslcr_tissue_bits_desc& a, hipStream_t st);
+hipError_t launch_lab_a_sum(const sslcr_lab_a_sum_desc& a, hipStream_t st);
+hipError_t launch_tile_popcount(const sslcr_tile_popcount_desc& a, hipStream_t st);
+hipError_t launch_rsp_gather(const sslcr_rsp_gather_desc& a, hipStream_t st);
 // augment.hip
 hipError_t launch_weak_augment(const sslcr_weak_aug_desc& a, hipStream_t st);
 hipError_t launch_hed_colour(const sslcr_colour_aug_desc& a, hipStream_t st);

@@ -658,6 +658,131 @@ def wsi_gather(region, xy, size, *, origin=(0, 0), fill=0, out=None, orient=None
     return out
 
 
+def _hwc_u8(name, img):
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+        raise L.SslcrError(f"{name}: a uint8 image [H, W, 3] expected")
+    H, W = img.shape[0], img.shape[1]
+    if H < 1 or W < 1 or H >= 1 << 31 or W >= (1 << 31) - 32:
+        raise L.SslcrError(f"{name}: image of {H} x {W} pixels")
+    return H, W
+
+
+def _f64_dev(name, what, t, n, dev):
+    if t is None or t.dtype != torch.float64 or t.numel() != n or t.device != dev:
+        raise L.SslcrError(f"{name}: {what} must be a float64 tensor of {n} element(s) on {dev}")
+
+
+TISSUE_MODES = {"hsv_s": 0, "lab_a": 1}
+
+
+def tissue_bits(img, mode, threshold=None, *, lin=None, thr_sum=None, factor=1.0, count=0.0, pitch=None, out=None):
+    """The foreground predicate of ``isforeground`` as one bit per pixel of a device uint8 image [H, W, 3] (sslcr_tissue_bits) -> int32
+    [H, pitch]: bit ``x & 31`` of dword ``x >> 5`` of row y is pixel (x, y), pad bits zero; pitch >= ceil(W / 32) (the default).
+    mode "hsv_s": ``s > threshold`` in float64 (equal to a NumPy restatement); mode "lab_a": ``a* > threshold`` with ``lin``, the 256
+    linearised channel values as device float64.  The threshold is the Python float ``threshold``, or -- thr_sum, a device float64 of
+    one element -- ``factor * (thr_sum / count)`` read on the device (``lab_a_sum`` wrote it; nothing syncs).  No sync."""
+    _chk(img, lin, thr_sum, out)
+    H, W = _hwc_u8("tissue_bits", img)
+    if mode not in TISSUE_MODES:
+        raise L.SslcrError(f"tissue_bits: mode {mode!r} outside {sorted(TISSUE_MODES)}")
+    if (threshold is None) == (thr_sum is None):
+        raise L.SslcrError("tissue_bits: exactly one of threshold and thr_sum")
+    if mode == "lab_a":
+        _f64_dev("tissue_bits", "lin", lin, 256, img.device)
+    if thr_sum is not None:
+        _f64_dev("tissue_bits", "thr_sum", thr_sum, 1, img.device)
+        if not float(count) > 0.0:
+            raise L.SslcrError(f"tissue_bits: count = {count} with thr_sum")
+    words = (W + 31) // 32
+    pitch = words if pitch is None else int(pitch)
+    if pitch < words:
+        raise L.SslcrError(f"tissue_bits: pitch = {pitch} < ceil({W} / 32)")
+    if out is None:
+        out = torch.empty((H, pitch), dtype=torch.int32, device=img.device)
+    elif out.dtype != torch.int32 or out.shape != (H, pitch) or out.device != img.device:
+        raise L.SslcrError(f"tissue_bits: out must be an int32 tensor [{H}, {pitch}] on the image's device")
+    d = L.TissueBitsDesc(L.ptr(img), L.ptr(out), L.ptr(lin), L.ptr(thr_sum), 0.0 if threshold is None else float(threshold),
+                         float(factor), float(count), H, W, pitch, TISSUE_MODES[mode])
+    L.check(L.lib().sslcr_tissue_bits(d, L.stream_ptr()))
+    return out
+
+
+def lab_a_sum(img, lin, out=None):
+    """-> device float64 [1]: the sum of CIELAB a* over a device uint8 image [H, W, 3] (sslcr_lab_a_sum), ``np.mean(lab[..., 1])``'s
+    numerator; lin as for ``tissue_bits``.  Fixed slices and fixed trees: two runs give the same bits.  No sync."""
+    _chk(img, lin, out)
+    H, W = _hwc_u8("lab_a_sum", img)
+    _f64_dev("lab_a_sum", "lin", lin, 256, img.device)
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=img.device)
+    else:
+        _f64_dev("lab_a_sum", "out", out, 1, img.device)
+    partials = torch.empty(L.LAB_SUM_PARTIALS, dtype=torch.float64, device=img.device)
+    d = L.LabASumDesc(L.ptr(img), L.ptr(lin), L.ptr(partials), L.ptr(out), H, W)
+    L.check(L.lib().sslcr_lab_a_sum(d, L.stream_ptr()))
+    return out
+
+
+def tile_popcount(bits, width, tile, stride, thresh):
+    """The candidate grid of ``get_wsi_patches`` over a bit plane int32 [H, pitch] of an image ``width`` pixels wide
+    (sslcr_tile_popcount); tile = (ph, pw), stride = (sh, sw).  -> (count int32 [ny, nx], keep uint8 [ny, nx]) for
+    ``ypos in range(sh, H - 1 - ph, sh)``, ``xpos in range(sw, W - 1 - pw, sw)``: the set bits of every window and
+    ``count / (ph * pw) >= thresh`` in float64.  An empty grid gives empty tensors.  No sync."""
+    _chk(bits)
+    if bits.dtype != torch.int32 or bits.dim() != 2:
+        raise L.SslcrError("tile_popcount: an int32 bit plane [H, pitch] expected")
+    H, pitch = bits.shape
+    W = int(width)
+    (ph, pw), (sh, sw) = (int(v) for v in tile), (int(v) for v in stride)
+    if min(H, W, ph, pw, sh, sw) < 1 or pitch < (W + 31) // 32:
+        raise L.SslcrError(f"tile_popcount: H = {H}, W = {W}, pitch = {pitch}, tile = {(ph, pw)}, stride = {(sh, sw)}")
+    ny, nx = len(range(sh, H - 1 - ph, sh)), len(range(sw, W - 1 - pw, sw))
+    count = torch.empty((ny, nx), dtype=torch.int32, device=bits.device)
+    keep = torch.empty((ny, nx), dtype=torch.uint8, device=bits.device)
+    if ny and nx:
+        d = L.TilePopcountDesc(L.ptr(bits), L.ptr(count), L.ptr(keep), float(thresh), H, W, pitch, ph, pw, sh, sw, ny, nx)
+        L.check(L.lib().sslcr_tile_popcount(d, L.stream_ptr()))
+    return count, keep
+
+
+def rsp_gather(levels, xy, idx, size, *, fill=0, out=None):
+    """One RSP batch from device-resident pyramid levels (sslcr_rsp_gather, one launch).  levels = (hr, lr1, lr2), uint8 [RH, RW, 3]
+    each; xy = three device int32 [T, 2] tables of (left, top) in the pixels of their level; idx: device int64 [N] of sample indices
+    into the 6 T samples ``sorted_sequence`` would build (sample k = triplet k // 6 under ordering k % 6).  -> (Data_1, Data_2,
+    Data_3, label): uint8 [N, 3, size, size] each and int64 [N] = k % 6; ``fill`` where a tile leaves its level.  out: the four
+    tensors to write into.  No sync."""
+    if len(levels) != 3 or len(xy) != 3:
+        raise L.SslcrError("rsp_gather: three levels and three coordinate tables expected")
+    _chk(*levels, *xy, idx, *(out or ()))
+    dev = levels[0].device
+    hw = [_hwc_u8("rsp_gather", lv) for lv in levels]
+    T = xy[0].shape[0] if xy[0].dim() == 2 else -1
+    for t in xy:
+        if t.dtype != torch.int32 or t.shape != (T, 2) or t.device != dev:
+            raise L.SslcrError("rsp_gather: xy must be three int32 tensors [T, 2] on the levels' device")
+    if T < 1:
+        raise L.SslcrError("rsp_gather: no triplets (T = 0)")
+    if any(lv.device != dev for lv in levels) or idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != dev:
+        raise L.SslcrError("rsp_gather: idx must be an int64 tensor [N] on the levels' device")
+    n, size = idx.shape[0], int(size)
+    if size < 1 or not 0 <= int(fill) <= 255:
+        raise L.SslcrError(f"rsp_gather: size = {size}, fill = {fill}")
+    if out is None:
+        out = tuple(torch.empty((n, 3, size, size), dtype=torch.uint8, device=dev) for _ in range(3)) + \
+            (torch.empty(n, dtype=torch.int64, device=dev),)
+    else:
+        if len(out) != 4 or any(o.dtype != torch.uint8 or o.shape != (n, 3, size, size) or o.device != dev for o in out[:3]) or \
+                out[3].dtype != torch.int64 or out[3].shape != (n,) or out[3].device != dev:
+            raise L.SslcrError(f"rsp_gather: out must be three uint8 tensors [{n}, 3, {size}, {size}] and an int64 tensor [{n}]")
+    if n:
+        vp3 = L.vp * 3
+        d = L.RspGatherDesc(vp3(*(lv.data_ptr() for lv in levels)), vp3(*(t.data_ptr() for t in xy)), L.ptr(idx),
+                            vp3(*(o.data_ptr() for o in out[:3])), L.ptr(out[3]), (L.i32 * 3)(*(h for h, _ in hw)),
+                            (L.i32 * 3)(*(w for _, w in hw)), T, n, size, int(fill))
+        L.check(L.lib().sslcr_rsp_gather(d, L.stream_ptr()))
+    return tuple(out)
+
+
 def grad_norm(flat, max_norm=float("inf")):
     """-> device tensor [norm, coef] for a 1-D fp32 tensor (any length, any 4-byte-aligned view): its 2-norm, summed in double in a
     fixed order, and min(1, max_norm / (norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_'s two numbers (sslcr_grad_norm).  No sync."""
