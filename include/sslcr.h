@@ -29,7 +29,7 @@ extern "C" {
 #define SSLCR_BF16 1
 #define SSLCR_FP8 2   /* engine mode only (sslcr_create): bf16 storage and backward, fp8 e4m3 forward for the eligible 3x3 convs */
 
-/* the library round (14 here). ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
+/* the library round (15 here). ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
  * 7 = sslcr_randaug_v2_slot added (nothing else changed); 8 = optimizer parameter groups, AdamW and the global gradient norm
  * (sslcr_tensor_desc.group, sslcr_opt_desc.kind 2, sslcr_optimizer_step_groups, sslcr_grad_norm, sslcr_net_optimizer_step_groups,
  * sslcr_net_grad_norm: all additive); 9 = gradient accumulation (sslcr_grad_accumulate, sslcr_net_set_grad_accumulate: additive,
@@ -39,7 +39,8 @@ extern "C" {
  * (additive; sslcr_softmax_col keeps its launch and its bits); 13 = test-time augmentation over D4: sslcr_d4_transform,
  * sslcr_wsi_gather_d4 and sslcr_predict_tta added (additive; sslcr_wsi_gather, sslcr_predict and their descriptors keep their launches
  * and their bits); 14 = tile mining for RSP pretraining: sslcr_tissue_bits, sslcr_lab_a_sum, sslcr_tile_popcount and sslcr_rsp_gather
- * added (additive; no existing entry, descriptor or launch changes). */
+ * added (additive; no existing entry, descriptor or launch changes); 15 = Camelyon16 annotations: sslcr_points_in_polygons and
+ * sslcr_map_confusion added (additive; no existing entry, descriptor or launch changes). */
 int sslcr_version(void);
 const char* sslcr_last_error(void);
 
@@ -579,6 +580,67 @@ typedef struct sslcr_rsp_gather_desc {
   int T, N, S, fill;
 } sslcr_rsp_gather_desc;
 int sslcr_rsp_gather(const sslcr_rsp_gather_desc* d, void* stream);
+
+/* ---- Camelyon16 annotations on the device (library version >= 15): Polygon.inside / Annotation.inside_polygons (util.py:197-205,
+ *      246-266), which every Camelyon dataset calls once per sample for its label (dataset.py:740-743) and whose truth a probability
+ *      map is scored against at the mask cells' centres (dataset.py:985-988).  Two entries, asynchronous, no floating-point atomics.
+ *
+ *      sslcr_points_in_polygons.  Polygon.inside is skimage.measure.points_in_poly([coord], vertices)[0]; the version the reference
+ *      pins (0.15.0) evaluates, per point (x, y) and polygon (xp[0..n-1], yp[0..n-1]), all float64:
+ *          c = 0; j = n - 1
+ *          for i in 0 .. n-1:
+ *              if ((yp[i] <= y and y < yp[j]) or (yp[j] <= y and y < yp[i])) and (x < (xp[j] - xp[i]) * (y - yp[i]) / (yp[j] - yp[i]) + xp[i]):
+ *                  c = not c
+ *              j = i
+ *          inside = c
+ *      one subtraction each, one product, one correctly rounded division and one addition, in that order; the division is reached
+ *      only where the y-test holds.  This restatement is the definition (unpinned against scikit-image itself: DESIGN section 8).
+ *        polygons   vertices [V][2] float64 (x, y), polygon p = vertices[offsets[p] .. offsets[p + 1]), offsets [P + 1] int32,
+ *                   non-decreasing from 0 to V (an entry outside [0, V] is read as the nearer end).  A polygon of fewer than 3
+ *                   vertices contains nothing; P == 0 gives all zeros.
+ *        bounds     NULL, or [P][4] float64 (xmin, ymin, xmax, ymax): a point outside bounds[p] is NOT tested against polygon p.  The
+ *                   caller's statement: ymin / ymax the extremes of yp, xmin / xmax the extremes of xp widened by what the chain's
+ *                   rounding can add (a few ulp; nothing on integer coordinates).  With such bounds the output is that of NULL.
+ *        points     [N][2] float64, or NULL = the grid: point n = i * ny + j is (x0 + i * step, y0 + j * step), N = nx * ny -- the
+ *                   output is the row-major [nx][ny] mask, indexed [x][y] as the reference's.
+ *        inside[n]  1 where any polygon contains point n, else 0               Annotation.inside_polygons
+ *        first[n]   the lowest index of a polygon that contains point n, or -1: the polygon at which the reference's loop returns
+ *        exact      0: the float64 chain as written.  1: the caller states that every vertex coordinate and every point coordinate is
+ *                   an integer of magnitude <= 2^24; the comparison is then decided by (x - xp[i]) d < (xp[j] - xp[i]) (y - yp[i]) for
+ *                   d = yp[j] - yp[i] > 0, reversed for d < 0, every term exact.  Same decisions: the quotient is an integer or at
+ *                   least 2^-25 from one, the chain's rounding error is below 2^-26.
+ *      The vertex list is staged SSLCR_PIP_CHUNK vertices at a time.  Errors, decided before the launch: NULL descriptor, N < 0 or
+ *      N >= 2^31, P < 0, V < 0, NULL inside / offsets (N > 0), NULL vertices with V > 0, misaligned pointers, a grid with nx * ny != N,
+ *      step outside [0, 2^31) or a coordinate of magnitude >= 2^53.  N == 0 is a no-op. */
+#define SSLCR_PIP_CHUNK 256
+typedef struct sslcr_pip_desc {
+  const double* vertices;   /* [V][2], 16-byte aligned */
+  const int32_t* offsets;   /* [P + 1] */
+  const double* bounds;     /* [P][4] or NULL */
+  const double* points;     /* [N][2], 16-byte aligned, or NULL: the grid */
+  uint8_t* inside;          /* [N] */
+  int32_t* first;           /* [N] or NULL */
+  int64_t x0, y0, step;     /* the grid (points == NULL) */
+  int64_t N;
+  int nx, ny;               /* the grid */
+  int P, V;
+  int exact;
+} sslcr_pip_desc;
+int sslcr_points_in_polygons(const sslcr_pip_desc* d, void* stream);
+
+/*      sslcr_map_confusion: one pass over a probability map [X][Y] float32, a truth mask and a tissue mask (uint8, nonzero = set), for
+ *      T <= 64 thresholds:  confusion[t][truth][map >= thresholds[t]] += 1  over the cells with tissue != 0 (a NaN is below every
+ *      threshold).  int64 [T][2][2], accumulated ACROSS calls by integer atomics (exact, order-independent); the caller zeroes it.
+ *      Errors: NULL pointers, X < 1, Y < 1, X * Y >= 2^31, T outside [1, 64], map / thresholds not 4-byte or confusion not 8-byte aligned. */
+typedef struct sslcr_map_confusion_desc {
+  const float* map;         /* [X][Y] */
+  const uint8_t* truth;     /* [X][Y] */
+  const uint8_t* tissue;    /* [X][Y] */
+  const float* thresholds;  /* [T] device floats */
+  int64_t* confusion;       /* [T][2][2] */
+  int X, Y, T;
+} sslcr_map_confusion_desc;
+int sslcr_map_confusion(const sslcr_map_confusion_desc* d, void* stream);
 
 /* ---- device-side strong augmentation, the colour ops of the reference's RandAugment pool ("next" row f4) on a uint8 batch in HBM.
  *      As with sslcr_weak_augment the random draws stay on the host, in the reference's order (ssl_cr_histo_amd/augment.py);

@@ -87,6 +87,11 @@ TilePopcountDesc = _S("TilePopcountDesc", [("bits", vp), ("count", vp), ("keep",
                       [(k, i32) for k in ("H", "W", "pitch", "ph", "pw", "sh", "sw", "ny", "nx")])
 RspGatherDesc = _S("RspGatherDesc", [("src", vp * 3), ("xy", vp * 3), ("idx", vp), ("dst", vp * 3), ("label", vp), ("RH", i32 * 3),
                                      ("RW", i32 * 3)] + [(k, i32) for k in ("T", "N", "S", "fill")])
+PIP_CHUNK = 256               # SSLCR_PIP_CHUNK
+PipDesc = _S("PipDesc", [("vertices", vp), ("offsets", vp), ("bounds", vp), ("points", vp), ("inside", vp), ("first", vp)] +
+             [(k, C.c_int64) for k in ("x0", "y0", "step", "N")] + [(k, i32) for k in ("nx", "ny", "P", "V", "exact")])
+MapConfusionDesc = _S("MapConfusionDesc", [(k, vp) for k in ("map", "truth", "tissue", "thresholds", "confusion")] +
+                      [(k, i32) for k in ("X", "Y", "T")])
 PackDesc = _S("PackDesc", [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("gamma", vp), ("beta", vp), ("rmean", vp),
                            ("rvar", vp), ("eps", f32), ("bias_out", vp)] + [(k, i32) for k in ("K", "C", "R", "S", "dgrad_flip")] + [("scale_out", vp)])
 
@@ -140,6 +145,8 @@ SIGNATURES = {
     "sslcr_lab_a_sum": (i32, [P(LabASumDesc), vp]),
     "sslcr_tile_popcount": (i32, [P(TilePopcountDesc), vp]),
     "sslcr_rsp_gather": (i32, [P(RspGatherDesc), vp]),
+    "sslcr_points_in_polygons": (i32, [P(PipDesc), vp]),
+    "sslcr_map_confusion": (i32, [P(MapConfusionDesc), vp]),
     "sslcr_optimizer_step": (i32, [vp, i32, i32, P(OptDesc), vp]),
     "sslcr_optimizer_step_groups": (i32, [vp, i32, i32, P(OptDesc), i32, vp, vp]),
     "sslcr_grad_norm": (i32, [vp, sz, f32, vp, vp, vp]),

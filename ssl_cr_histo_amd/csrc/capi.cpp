@@ -30,7 +30,7 @@ using namespace sslcr;
 
 extern "C" {
 
-int sslcr_version(void) { return 14; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
+int sslcr_version(void) { return 15; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
 const char* sslcr_last_error(void) { return g_err; }
 
 int sslcr_conv2d(int dtype, const sslcr_conv_desc* d, void* stream) {
@@ -308,6 +308,35 @@ int sslcr_rsp_gather(const sslcr_rsp_gather_desc* d, void* stream) {
   }
   NEED(((reinterpret_cast<uintptr_t>(d->idx) | reinterpret_cast<uintptr_t>(d->label)) & 7) == 0, "idx / label alignment");
   return check(launch_rsp_gather(*d, (hipStream_t)stream), "rsp_gather");
+}
+// ---- Camelyon16 annotations (annotation.hip)
+int sslcr_points_in_polygons(const sslcr_pip_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  NEED(d->N >= 0 && d->N < (int64_t)1 << 31, "N outside [0, 2^31)");
+  NEED(d->P >= 0 && d->V >= 0, "P >= 0 and V >= 0");
+  NEED(d->exact == 0 || d->exact == 1, "exact outside {0, 1}");
+  if (!d->points) {
+    const int64_t lim = (int64_t)1 << 53;
+    NEED(d->nx >= 0 && d->ny >= 0 && (int64_t)d->nx * d->ny == d->N, "grid: nx * ny != N");
+    NEED(d->step >= 0 && d->step < (int64_t)1 << 31 && d->x0 > -lim && d->x0 < lim && d->y0 > -lim && d->y0 < lim, "grid: coordinate magnitude");
+    NEED(d->x0 + (int64_t)d->nx * d->step < lim && d->y0 + (int64_t)d->ny * d->step < lim, "grid: coordinate magnitude");
+  }
+  if (d->N == 0) return 0;
+  NEED(d->inside && d->offsets, "null tensor");
+  NEED(d->V == 0 || d->vertices, "null vertices");
+  NEED(((reinterpret_cast<uintptr_t>(d->vertices) | reinterpret_cast<uintptr_t>(d->points)) & 15) == 0, "vertices / points alignment");
+  NEED((reinterpret_cast<uintptr_t>(d->bounds) & 7) == 0, "bounds alignment");
+  NEED(((reinterpret_cast<uintptr_t>(d->offsets) | reinterpret_cast<uintptr_t>(d->first)) & 3) == 0, "offsets / first alignment");
+  return check(launch_points_in_polygons(*d, (hipStream_t)stream), "points_in_polygons");
+}
+int sslcr_map_confusion(const sslcr_map_confusion_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  NEED(d->X >= 1 && d->Y >= 1 && (int64_t)d->X * d->Y < (int64_t)1 << 31, "map shape");
+  NEED(d->T >= 1 && d->T <= 64, "T outside [1, 64]");
+  NEED(d->map && d->truth && d->tissue && d->thresholds && d->confusion, "null tensor");
+  NEED(((reinterpret_cast<uintptr_t>(d->map) | reinterpret_cast<uintptr_t>(d->thresholds)) & 3) == 0, "map / thresholds alignment");
+  NEED((reinterpret_cast<uintptr_t>(d->confusion) & 7) == 0, "confusion alignment");
+  return check(launch_map_confusion(*d, (hipStream_t)stream), "map_confusion");
 }
 int sslcr_d4_transform(const sslcr_d4_desc* d, void* stream) {
   NEED(d, "null descriptor");

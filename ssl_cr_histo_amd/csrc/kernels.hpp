@@ -209,6 +209,9 @@ hipError_t launch_tissue_bits(const sslcr_tissue_bits_desc& a, hipStream_t st);
 hipError_t launch_lab_a_sum(const sslcr_lab_a_sum_desc& a, hipStream_t st);
 hipError_t launch_tile_popcount(const sslcr_tile_popcount_desc& a, hipStream_t st);
 hipError_t launch_rsp_gather(const sslcr_rsp_gather_desc& a, hipStream_t st);
+// annotation.hip
+hipError_t launch_points_in_polygons(const sslcr_pip_desc& a, hipStream_t st);
+hipError_t launch_map_confusion(const sslcr_map_confusion_desc& a, hipStream_t st);
 // augment.hip
 hipError_t launch_weak_augment(const sslcr_weak_aug_desc& a, hipStream_t st);
 hipError_t launch_hed_colour(const sslcr_colour_aug_desc& a, hipStream_t st);

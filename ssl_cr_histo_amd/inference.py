@@ -14,6 +14,11 @@ Test-time augmentation.  ``d4_codes`` / ``d4_apply`` define the eight flips and 
 D4) as orientation codes 0..7; ``WsiDeviceLoader.tiles(lo, hi, orient=g)`` cuts a batch already oriented (sslcr_wsi_gather_d4), and
 ``args.tta`` on the ``steps.*_test`` functions averages the scores of the listed orientations on the device (sslcr_predict_tta).
 
+Ground truth.  ``WsiDeviceLoader(..., annotation=)`` takes the slide's ``annotation.Annotation``: the tiles' labels (``.targets``) and
+the truth mask (``.truth``) are two launches of sslcr_points_in_polygons at construction, ``camelyon16_test`` counts the tile-level
+confusion matrix in the predict launch it already makes, and ``map_scores`` counts a finished map against the truth mask at up to 64
+thresholds in one pass (sslcr_map_confusion).
+
 Metrics.  The Kather mains build sklearn's confusion matrix and a weighted F1 from what ``test()`` returns
 (eval_Kather_SSL_CR.py:646-658, eval_Kather_SSL.py:519-530).  ``ConfusionMeter`` counts the same matrix on the device, batch by batch,
 with integer atomics; ``metrics_from_confusion`` derives the figures from it in host float64.
@@ -114,7 +119,8 @@ class WsiDeviceLoader:
     The coordinate table and the flat map indices are computed and uploaded once; iterating yields the reference's
     ``(tiles, x_mask, y_mask)`` batches with the tiles as device uint8, so any consumer of the host loader can read it too."""
 
-    def __init__(self, region_u8_hwc, mask, image_size, batch_size, *, resolution=None, origin=(0, 0), fill=0, device=None):
+    def __init__(self, region_u8_hwc, mask, image_size, batch_size, *, resolution=None, origin=(0, 0), fill=0, device=None,
+                 annotation=None):
         mask = np.asarray(mask)
         if mask.ndim != 2:
             raise ValueError("WsiDeviceLoader: a 2-D tissue mask expected")
@@ -136,6 +142,12 @@ class WsiDeviceLoader:
         self._orient = None
         self.xy = torch.from_numpy(xy).to(dev)
         self.map_index = torch.from_numpy(x_idcs.astype(np.int64) * mask.shape[1] + y_idcs).to(dev)     # probs_map[x, y], row-major
+        self.annotation, self.targets, self.truth = annotation, None, None
+        if annotation is not None:                                 # two launches, no host loop: the tiles' labels and the truth mask
+            annotation.to_device(dev)
+            centres = np.stack([np.trunc(x_idcs * resolution), np.trunc(y_idcs * resolution)], 1)      # tile_origins' centres
+            self.targets = annotation.labels(centres)
+            self.truth = annotation.mask(mask.shape, resolution)
 
     def __len__(self):
         return (len(self.dataset) + self.batch_size - 1) // self.batch_size
@@ -180,6 +192,24 @@ class ConfusionMeter:
 
     def cpu(self):
         return self.matrix.cpu()
+
+
+def map_scores(probs_map, truth, tissue, thresholds):
+    """A probability map against the truth mask over the tissue cells, at every threshold: one device pass for the counts
+    (``kernels.map_confusion``), one copy, host float64 for the figures.  probs_map: [X, Y], a device float32 tensor or what
+    ``camelyon16_test`` returns (uploaded as float32, the precision it was computed in); truth / tissue: [X, Y] masks, device uint8 or
+    host (``WsiDeviceLoader.truth`` / ``.dataset.mask``); thresholds: 1 <= T <= 64 values, compared as float32.
+    -> dict: ``thresholds`` (float32 [T]), ``confusion`` int64 [T, 2, 2] = [t, truth, map >= threshold] ([[tn, fp], [fn, tp]]),
+    ``sensitivity`` = tp / (tp + fn), ``specificity`` = tn / (tn + fp), ``dice`` = 2 tp / (2 tp + fp + fn); a division by zero gives 0."""
+    dev = next((t.device for t in (probs_map, truth, tissue) if torch.is_tensor(t) and t.is_cuda), None)
+    dev = dev if dev is not None else torch.device("cuda")
+    pm = torch.as_tensor(probs_map).to(dev, torch.float32).contiguous()
+    masks = [torch.as_tensor(np.asarray(m) != 0 if not torch.is_tensor(m) else m).to(dev).contiguous() for m in (truth, tissue)]
+    thr = np.asarray(torch.as_tensor(thresholds).cpu(), dtype=np.float32).reshape(-1)
+    cm = K.map_confusion(pm, masks[0], masks[1], torch.from_numpy(thr)).cpu().numpy()
+    tn, fp, fn, tp = cm[:, 0, 0], cm[:, 0, 1], cm[:, 1, 0], cm[:, 1, 1]
+    return dict(thresholds=thr, confusion=cm, sensitivity=_div(tp, tp + fn), specificity=_div(tn, tn + fp),
+                dice=_div(2 * tp, 2 * tp + fp + fn))
 
 
 def _div(a, b):

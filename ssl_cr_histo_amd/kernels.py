@@ -783,6 +783,106 @@ def rsp_gather(levels, xy, idx, size, *, fill=0, out=None):
     return tuple(out)
 
 
+PIP_CHUNK = L.PIP_CHUNK       # the edges one staged chunk of points_in_polygons holds
+PIP_EXACT_MAX = 1 << 24       # the integer path's precondition: integer coordinates of at most this magnitude
+
+
+def pip_exact_ok(values):
+    """the precondition of the integer path, checked on the host: every value an integer of magnitude <= 2^24.  values: a tensor (a
+    device tensor costs one sync), a NumPy array, or a sequence of Python ints (a grid's x0, y0 and last coordinates)."""
+    if torch.is_tensor(values):
+        if values.numel() == 0:
+            return True
+        return bool(((values == values.round()) & (values.abs() <= PIP_EXACT_MAX)).all().item())
+    import numpy as np
+    v = np.asarray(values)
+    if v.size == 0:
+        return True
+    if v.dtype == object:                                          # Python ints beyond int64
+        return all(isinstance(k, int) and abs(k) <= PIP_EXACT_MAX for k in v.ravel().tolist())
+    with np.errstate(invalid="ignore"):
+        return bool(np.all((v == np.round(v)) & (np.abs(v) <= PIP_EXACT_MAX)))
+
+
+def _grid_extremes(grid):
+    x0, y0, step, nx, ny = (int(v) for v in grid)
+    return [x0, y0, x0 + max(nx - 1, 0) * step, y0 + max(ny - 1, 0) * step]
+
+
+def points_in_polygons(points, vertices, offsets, *, grid=None, bounds=None, first=False, exact=None, out=None):
+    """The crossing-number test of ``Polygon.inside`` for every point against a polygon set (sslcr_points_in_polygons, one launch).
+    vertices: device float64 [V, 2] (x, y); offsets: device int32 [P + 1], polygon p = vertices[offsets[p]:offsets[p + 1]]; bounds:
+    None (no culling) or device float64 [P, 4] (xmin, ymin, xmax, ymax).  The points are EITHER ``points``, device float64 [N, 2], OR
+    (points=None) ``grid=(x0, y0, step, nx, ny)``: point ``i * ny + j`` is ``(x0 + i * step, y0 + j * step)`` in Python ints.
+    -> ``inside`` uint8 [N] ([nx, ny] for a grid): 1 where any polygon contains the point; with first=True ``(inside, first)``, first
+    int32 of the same shape = the lowest index of a containing polygon, or -1.  A polygon of fewer than 3 vertices contains nothing.
+    exact: True / False forces the integer path / the float64 chain; None checks the integer path's precondition on the host
+    (``pip_exact_ok`` on vertices and points: integers of magnitude <= 2^24, one sync per device tensor) and takes it where it holds.
+    out: ``inside``, or ``(inside, first)``, to write into.  No sync with exact given."""
+    if (points is None) == (grid is None):
+        raise L.SslcrError("points_in_polygons: exactly one of points and grid")
+    _chk(points, vertices, offsets, bounds)
+    dev = vertices.device
+    if vertices.dtype != torch.float64 or vertices.dim() != 2 or vertices.shape[1] != 2:
+        raise L.SslcrError("points_in_polygons: vertices must be a float64 tensor [V, 2]")
+    if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.numel() < 1 or offsets.device != dev:
+        raise L.SslcrError("points_in_polygons: offsets must be an int32 tensor [P + 1] on the vertices' device")
+    V, P = vertices.shape[0], offsets.numel() - 1
+    if bounds is not None and (bounds.dtype != torch.float64 or bounds.shape != (P, 4) or bounds.device != dev):
+        raise L.SslcrError(f"points_in_polygons: bounds must be a float64 tensor [{P}, 4] on the vertices' device")
+    if points is not None:
+        if points.dtype != torch.float64 or points.dim() != 2 or points.shape[1] != 2 or points.device != dev:
+            raise L.SslcrError("points_in_polygons: points must be a float64 tensor [N, 2] on the vertices' device")
+        n, shape = points.shape[0], (points.shape[0],)
+        x0 = y0 = step = nx = ny = 0
+    else:
+        x0, y0, step, nx, ny = (int(v) for v in grid)
+        if nx < 0 or ny < 0 or step < 0 or nx * ny >= 1 << 31:
+            raise L.SslcrError(f"points_in_polygons: grid = {tuple(grid)}")
+        n, shape = nx * ny, (nx, ny)
+    if exact is None:
+        exact = pip_exact_ok(vertices) and pip_exact_ok(points if points is not None else _grid_extremes(grid))
+    outs = (out,) if torch.is_tensor(out) else tuple(out or ())
+    _chk(*outs)
+    if len(outs) > (2 if first else 1):
+        raise L.SslcrError("points_in_polygons: out is inside, or (inside, first)")
+    inside = outs[0] if outs else torch.empty(shape, dtype=torch.uint8, device=dev)
+    which = (outs[1] if len(outs) == 2 else torch.empty(shape, dtype=torch.int32, device=dev)) if first else None
+    for name, t, dt in (("inside", inside, torch.uint8), ("first", which, torch.int32)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or t.device != dev):
+            raise L.SslcrError(f"points_in_polygons: {name} must be a {dt} tensor {list(shape)} on the vertices' device")
+    d = L.PipDesc(L.ptr(vertices) if V else None, L.ptr(offsets), L.ptr(bounds) if P else None,
+                  L.ptr(points) if points is not None and n else None, L.ptr(inside) if n else None,
+                  L.ptr(which) if which is not None and n else None, x0, y0, step, n, nx, ny, P, V, int(bool(exact)))
+    if n:
+        L.check(L.lib().sslcr_points_in_polygons(d, L.stream_ptr()))
+    return (inside, which) if first else inside
+
+
+def map_confusion(map, truth, tissue, thresholds):
+    """-> device int64 [T, 2, 2]: ``confusion[t, truth, map >= thresholds[t]]`` counted over the cells with ``tissue != 0`` in one pass
+    (sslcr_map_confusion).  map: device float32 [X, Y]; truth, tissue: device uint8 (or bool) [X, Y], nonzero = set; thresholds: 1 <= T
+    <= 64 float32 values, a device tensor or anything ``torch.as_tensor`` takes.  Integer counts, exact.  No sync."""
+    _chk(map, truth, tissue)
+    if map.dtype != torch.float32 or map.dim() != 2 or map.numel() < 1:
+        raise L.SslcrError("map_confusion: a float32 map [X, Y] expected")
+    masks = []
+    for name, m in (("truth", truth), ("tissue", tissue)):
+        if m.dtype == torch.bool:
+            m = m.view(torch.uint8)
+        if m.dtype != torch.uint8 or m.shape != map.shape or m.device != map.device:
+            raise L.SslcrError(f"map_confusion: {name} must be a uint8 tensor {list(map.shape)} on the map's device")
+        masks.append(m)
+    thr = torch.as_tensor(thresholds, dtype=torch.float32).reshape(-1).to(map.device).contiguous()
+    T = thr.numel()
+    if not 1 <= T <= 64:
+        raise L.SslcrError(f"map_confusion: T = {T} outside [1, 64]")
+    out = torch.zeros((T, 2, 2), dtype=torch.int64, device=map.device)
+    d = L.MapConfusionDesc(L.ptr(map), L.ptr(masks[0]), L.ptr(masks[1]), L.ptr(thr), L.ptr(out), map.shape[0], map.shape[1], T)
+    L.check(L.lib().sslcr_map_confusion(d, L.stream_ptr()))
+    return out
+
+
 def grad_norm(flat, max_norm=float("inf")):
     """-> device tensor [norm, coef] for a 1-D fp32 tensor (any length, any 4-byte-aligned view): its 2-norm, summed in double in a
     fixed order, and min(1, max_norm / (norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_'s two numbers (sslcr_grad_norm).  No sync."""

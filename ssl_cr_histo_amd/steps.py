@@ -618,7 +618,9 @@ _last_test = {"confusion": None}
 def last_test_confusion():
     """the int64 [C, C] confusion matrix (rows = targets, columns = predictions; a CPU tensor) of the most recent ``kather_cr_test`` /
     ``kather_sup_test`` call, counted on the device by sslcr_predict -- sklearn's ``confusion_matrix(final_targets,
-    final_predictions, labels=range(C))`` of the returned tensors; None after a regression ``bpq_*_test``."""
+    final_predictions, labels=range(C))`` of the returned tensors; None after a regression ``bpq_*_test``.  ``camelyon16_test`` on a
+    ``WsiDeviceLoader`` that holds an annotation leaves the 2 x 2 tile-level matrix here (rows = the label of the tile's centre, columns
+    = the argmax of the tile's, or the ensemble's, scores); any other ``camelyon16_test`` call leaves it as it was."""
     return _last_test["confusion"]
 
 
@@ -790,25 +792,36 @@ def _camelyon16_test_device(args, net, loader, codes=None):
     from . import kernels as K
     mask = loader.dataset.mask
     probs = torch.zeros(mask.shape, dtype=torch.float32, device=loader.region.device)
+    # a loader with an annotation: the same launch also counts confusion[label of the tile's centre][argmax], every tile once
+    targets = getattr(loader, "targets", None)
+    counted = {}
+    if targets is not None:
+        counted["confusion"] = torch.zeros((net.ncls, net.ncls), dtype=torch.int64, device=loader.region.device)
     t0 = time.time()
     for batch_idx, (lo, hi) in enumerate(loader.ranges()):
+        if targets is not None:
+            counted["target"] = targets[lo:hi]
         if codes is not None:
             ens = torch.empty((len(codes), hi - lo, net.ncls), dtype=torch.float32, device=loader.region.device)
             for k, g in enumerate(codes):
                 ens[k].copy_(net.forward((loader.tiles(lo, hi, orient=g),), train=False)[1])
-            K.predict_tta(ens, pred=False, col=-1, map=probs, map_index=loader.map_index[lo:hi])
+            K.predict_tta(ens, pred=False, col=-1, map=probs, map_index=loader.map_index[lo:hi], **counted)
         else:
             _, output = net.forward((loader.tiles(lo, hi),), train=False)
-            K.predict(output, pred=False, col=-1, map=probs, map_index=loader.map_index[lo:hi])   # second column 'tumor' (:58-62)
+            K.predict(output, pred=False, col=-1, map=probs, map_index=loader.map_index[lo:hi], **counted)   # second column 'tumor' (:58-62)
         if (batch_idx + 1) % 10 == 0 and getattr(args, "print_freq", 0):
             print("Test: [{0}/{1}]\tBT {2:.3f} (enqueue)".format(batch_idx, len(loader), (time.time() - t0) / (batch_idx + 1)))
-    return probs.cpu().numpy().astype(np.float64)
+    out = probs.cpu().numpy().astype(np.float64)
+    if targets is not None:
+        _last_test["confusion"] = counted["confusion"].to("cpu")
+    return out
 
 
 def camelyon16_test(args, model, classifier, test_loader):
     """test_Camelyon16.test (test_Camelyon16.py:30-70) -> probs_map: every tissue pixel of ``test_loader.dataset.mask``
     gets the softmax 'tumor' probability of its tile; forward-only (BatchNorm folded, all epilogues fused).  An
-    ``inference.WsiDeviceLoader`` is served from the slide bytes it holds in HBM (same map, no per-batch host traffic).
+    ``inference.WsiDeviceLoader`` is served from the slide bytes it holds in HBM (same map, no per-batch host traffic); one built with
+    ``annotation=`` also has the launch count the tile-level confusion matrix against the annotation's labels (``last_test_confusion()``).
 
     ``args.tta`` (a name of ``inference.D4_SETS`` or a sequence of orientation codes; absent or None = off): every tile is scored
     under each listed flip / quarter turn and the map holds the mean 'tumor' probability -- the fp32 sum of the members in the order
