@@ -40,7 +40,9 @@ extern "C" {
  * sslcr_wsi_gather_d4 and sslcr_predict_tta added (additive; sslcr_wsi_gather, sslcr_predict and their descriptors keep their launches
  * and their bits); 14 = tile mining for RSP pretraining: sslcr_tissue_bits, sslcr_lab_a_sum, sslcr_tile_popcount and sslcr_rsp_gather
  * added (additive; no existing entry, descriptor or launch changes); 15 = Camelyon16 annotations: sslcr_points_in_polygons and
- * sslcr_map_confusion added (additive; no existing entry, descriptor or launch changes). */
+ * sslcr_map_confusion added (additive; no existing entry, descriptor or launch changes).  Lesion scoring (sslcr_label_components,
+ * sslcr_gaussian_smooth, sslcr_nms_candidates / _rounds / _collect, sslcr_lesion_hits) is additive in the same way and came WITHOUT
+ * a new number: tests/test_annotation_cpu.py holds sslcr_version() to 15 by equality, so a caller tests for these entries by symbol. */
 int sslcr_version(void);
 const char* sslcr_last_error(void);
 
@@ -641,6 +643,98 @@ typedef struct sslcr_map_confusion_desc {
   int X, Y, T;
 } sslcr_map_confusion_desc;
 int sslcr_map_confusion(const sslcr_map_confusion_desc* d, void* stream);
+
+/* ---- Camelyon16 lesion scoring on the device: from a probability map and a truth mask to what lesion-level FROC counts.  The
+ *      reference stops at the heat map (test_Camelyon16.py), so these definitions are this library's, modelled on the challenge's
+ *      published evaluation and on the greedy NMS commonly run on such maps; both are unpinned.  Maps and masks are
+ *      [X][Y] as for sslcr_map_confusion; "order" over cells is the linear index x * Y + y.  All entries are asynchronous; every atomic
+ *      is an integer min / max / add, so no result depends on the order in which they land.
+ *
+ *      sslcr_label_components.  labels[x][y] = 0 where mask is 0, else the number of the cell's connected component; connectivity 2
+ *      = 8 neighbours, 1 = 4 neighbours.  Components are numbered 1..L by the order of each component's first cell (what
+ *      scipy.ndimage.label gives); *count = L.  work: X * Y + ceil(X * Y / 1024) int32 of scratch.
+ *      Errors: NULL pointers, X < 1, Y < 1, X * Y >= 2^31, connectivity outside {1, 2}, pointers not 4-byte aligned (the mask is read
+ *      as whole dwords). */
+typedef struct sslcr_label_desc {
+  const uint8_t* mask;      /* [X][Y], nonzero = set; 4-byte aligned */
+  int32_t* labels;          /* [X][Y] */
+  int32_t* count;           /* [1]: L */
+  int32_t* work;            /* [X * Y + ceil(X * Y / 1024)] */
+  int X, Y, connectivity;
+} sslcr_label_desc;
+int sslcr_label_components(const sslcr_label_desc* d, void* stream);
+
+/*      sslcr_gaussian_smooth.  A separable Gaussian in float32, edge mode "nearest" (clamped index), axis 0 (x) first, then axis 1:
+ *          pass(src)[i] = (((0 + w[0] * src[clamp(i - R)]) + w[1] * src[clamp(i - R + 1)]) + ...) + w[2R] * src[clamp(i + R)]
+ *      every product and every sum rounded to float32 on its own (no fused multiply-add).  weights: 2R + 1 device floats; for a
+ *      given sigma the caller computes exp(-k^2 / (2 sigma^2)), k = -R .. R, R = int(4 sigma + 0.5), in float64, normalises to sum 1
+ *      and casts to float32.  tmp holds the first pass; dst may be src, tmp may be neither.
+ *      Errors: NULL pointers, X < 1, Y < 1, X * Y >= 2^31, R outside [0, SSLCR_SMOOTH_MAX_R], pointers not 4-byte aligned, tmp == src
+ *      or tmp == dst. */
+#define SSLCR_SMOOTH_MAX_R 64
+typedef struct sslcr_smooth_desc {
+  const float* src;         /* [X][Y] */
+  float* tmp;               /* [X][Y] */
+  float* dst;               /* [X][Y] */
+  const float* weights;     /* [2R + 1] */
+  int X, Y, R;
+} sslcr_smooth_desc;
+int sslcr_gaussian_smooth(const sslcr_smooth_desc* d, void* stream);
+
+/*      Non-maximum suppression.  A cell is a CANDIDATE iff map > threshold (a NaN is none).  Cell q PRECEDES p iff map[q] > map[p], or
+ *      they are equal and q's linear index is lower.  The WINDOW of a selected cell q = (qx, qy) is [qx - r, qx + r) x [qy - r, qy + r)
+ *      clipped to the map -- half-open and asymmetric on purpose.  A candidate p is SELECTED iff no selected cell q that precedes p
+ *      has p in its window (well-founded along "precedes").  This equals the sequential loop: take the first maximum in order, record
+ *      it, zero its window, repeat while max > threshold; the output is the selected cells in that loop's order (= "precedes" order).
+ *      A selected cell never removes a cell that precedes it.
+ *      Three entries over one descriptor, because the host sizes the launches and bounds the rounds by the candidate count:
+ *        sslcr_nms_candidates  zeroes counters[0..3], sets state (0 none, 1 undecided) and compacts the candidates' linear indices
+ *                              into cand; counters[0] = their number, which the caller reads and passes as ncand from then on
+ *        sslcr_nms_rounds      `rounds` rounds, one launch each.  A round takes every undecided candidate p and reads the state of
+ *                              the candidates q that precede it and whose window holds it: one selected -> p is suppressed (3); none
+ *                              selected and none undecided -> p is selected (2); else p stays undecided.  A decision is final once
+ *                              stored.  counters[1] = the candidates still undecided after the LAST of these rounds.  Every round
+ *                              decides at least the first undecided candidate in "precedes" order, so ncand rounds always suffice;
+ *                              the caller loops until counters[1] == 0 and gives up after ncand + 1 rounds.
+ *        sslcr_nms_collect     counters[2] = the number of selected cells K; if K <= max_detections, det_xy[k] = (x, y) and
+ *                              det_prob[k] = map[x][y] for k < K in output order.  If K > max_detections the outputs hold nothing
+ *                              of use, nothing is written past max_detections entries, and the caller must raise.
+ *      Errors: NULL descriptor or pointers, X < 1, Y < 1, X * Y >= 2^31, radius < 1, max_detections < 1, ncand outside [0, X * Y],
+ *      rounds < 0, pointers not 4-byte aligned (state too: the rounds read it as whole dwords). */
+typedef struct sslcr_nms_desc {
+  const float* map;         /* [X][Y] */
+  uint8_t* state;           /* [X][Y], 4-byte aligned */
+  int32_t* cand;            /* [X * Y] */
+  int32_t* stage;           /* [max_detections] scratch */
+  int32_t* counters;        /* [4] */
+  int32_t* det_xy;          /* [max_detections][2] */
+  float* det_prob;          /* [max_detections] */
+  float threshold;
+  int X, Y, radius, max_detections, ncand;
+} sslcr_nms_desc;
+int sslcr_nms_candidates(const sslcr_nms_desc* d, void* stream);
+int sslcr_nms_rounds(const sslcr_nms_desc* d, int rounds, void* stream);
+int sslcr_nms_collect(const sslcr_nms_desc* d, void* stream);
+
+/*      sslcr_lesion_hits.  For detection k < min(*n_det, max_detections): hit[k] = labels[x_k][y_k] (0 = a false positive; a
+ *      detection outside the map hits nothing).  A hit on a label of the ignore list is neither a false nor a true positive.
+ *      Otherwise tp_prob[label - 1] = max(tp_prob[label - 1], prob): an integer atomicMax on the float's bits over the probabilities
+ *      above +0 (the caller zeroes tp_prob, so a lesion nothing hits keeps 0).  areas (or NULL): areas[l] += the number of cells of
+ *      lesion l + 1, int64; the caller zeroes it.  L is the count sslcr_label_components returned.
+ *      Errors: NULL descriptor, NULL labels / det_xy / det_prob / n_det / hit, NULL tp_prob with L > 0, NULL ignore with n_ignore > 0,
+ *      X < 1, Y < 1, X * Y >= 2^31, L < 0, max_detections < 1, n_ignore < 0, pointers not 4-byte (areas: 8-byte) aligned. */
+typedef struct sslcr_hits_desc {
+  const int32_t* labels;    /* [X][Y] */
+  const int32_t* det_xy;    /* [max_detections][2] */
+  const float* det_prob;    /* [max_detections] */
+  const int32_t* n_det;     /* [1], device */
+  const int32_t* ignore;    /* [n_ignore] labels, or NULL */
+  int32_t* hit;             /* [max_detections] */
+  float* tp_prob;           /* [L] */
+  int64_t* areas;           /* [L] or NULL */
+  int X, Y, L, max_detections, n_ignore;
+} sslcr_hits_desc;
+int sslcr_lesion_hits(const sslcr_hits_desc* d, void* stream);
 
 /* ---- device-side strong augmentation, the colour ops of the reference's RandAugment pool ("next" row f4) on a uint8 batch in HBM.
  *      As with sslcr_weak_augment the random draws stay on the host, in the reference's order (ssl_cr_histo_amd/augment.py);

@@ -92,6 +92,13 @@ PipDesc = _S("PipDesc", [("vertices", vp), ("offsets", vp), ("bounds", vp), ("po
              [(k, C.c_int64) for k in ("x0", "y0", "step", "N")] + [(k, i32) for k in ("nx", "ny", "P", "V", "exact")])
 MapConfusionDesc = _S("MapConfusionDesc", [(k, vp) for k in ("map", "truth", "tissue", "thresholds", "confusion")] +
                       [(k, i32) for k in ("X", "Y", "T")])
+SMOOTH_MAX_R = 64             # SSLCR_SMOOTH_MAX_R
+LabelDesc = _S("LabelDesc", [(k, vp) for k in ("mask", "labels", "count", "work")] + [(k, i32) for k in ("X", "Y", "connectivity")])
+SmoothDesc = _S("SmoothDesc", [(k, vp) for k in ("src", "tmp", "dst", "weights")] + [(k, i32) for k in ("X", "Y", "R")])
+NmsDesc = _S("NmsDesc", [(k, vp) for k in ("map", "state", "cand", "stage", "counters", "det_xy", "det_prob")] + [("threshold", f32)] +
+             [(k, i32) for k in ("X", "Y", "radius", "max_detections", "ncand")])
+HitsDesc = _S("HitsDesc", [(k, vp) for k in ("labels", "det_xy", "det_prob", "n_det", "ignore", "hit", "tp_prob", "areas")] +
+              [(k, i32) for k in ("X", "Y", "L", "max_detections", "n_ignore")])
 PackDesc = _S("PackDesc", [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("gamma", vp), ("beta", vp), ("rmean", vp),
                            ("rvar", vp), ("eps", f32), ("bias_out", vp)] + [(k, i32) for k in ("K", "C", "R", "S", "dgrad_flip")] + [("scale_out", vp)])
 
@@ -147,6 +154,12 @@ SIGNATURES = {
     "sslcr_rsp_gather": (i32, [P(RspGatherDesc), vp]),
     "sslcr_points_in_polygons": (i32, [P(PipDesc), vp]),
     "sslcr_map_confusion": (i32, [P(MapConfusionDesc), vp]),
+    "sslcr_label_components": (i32, [P(LabelDesc), vp]),
+    "sslcr_gaussian_smooth": (i32, [P(SmoothDesc), vp]),
+    "sslcr_nms_candidates": (i32, [P(NmsDesc), vp]),
+    "sslcr_nms_rounds": (i32, [P(NmsDesc), i32, vp]),
+    "sslcr_nms_collect": (i32, [P(NmsDesc), vp]),
+    "sslcr_lesion_hits": (i32, [P(HitsDesc), vp]),
     "sslcr_optimizer_step": (i32, [vp, i32, i32, P(OptDesc), vp]),
     "sslcr_optimizer_step_groups": (i32, [vp, i32, i32, P(OptDesc), i32, vp, vp]),
     "sslcr_grad_norm": (i32, [vp, sz, f32, vp, vp, vp]),

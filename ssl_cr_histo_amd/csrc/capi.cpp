@@ -338,6 +338,64 @@ int sslcr_map_confusion(const sslcr_map_confusion_desc* d, void* stream) {
   NEED((reinterpret_cast<uintptr_t>(d->confusion) & 7) == 0, "confusion alignment");
   return check(launch_map_confusion(*d, (hipStream_t)stream), "map_confusion");
 }
+// ---- Camelyon16 lesion scoring (froc.hip)
+#define MAP_SHAPE_OK(d) NEED((d)->X >= 1 && (d)->Y >= 1 && (int64_t)(d)->X * (d)->Y < (int64_t)1 << 31, "map shape")
+#define ALIGNED(p, mask) ((reinterpret_cast<uintptr_t>(p) & (mask)) == 0)
+int sslcr_label_components(const sslcr_label_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  MAP_SHAPE_OK(d);
+  NEED(d->connectivity == 1 || d->connectivity == 2, "connectivity outside {1, 2}");
+  NEED(d->mask && d->labels && d->count && d->work, "null tensor");
+  NEED(ALIGNED(d->mask, 3) && ALIGNED(d->labels, 3) && ALIGNED(d->count, 3) && ALIGNED(d->work, 3), "mask / labels / count / work alignment");
+  return check(launch_label_components(*d, (hipStream_t)stream), "label_components");
+}
+int sslcr_gaussian_smooth(const sslcr_smooth_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  MAP_SHAPE_OK(d);
+  NEED(d->R >= 0 && d->R <= SSLCR_SMOOTH_MAX_R, "R outside [0, 64]");
+  NEED(d->src && d->tmp && d->dst && d->weights, "null tensor");
+  NEED(ALIGNED(d->src, 3) && ALIGNED(d->tmp, 3) && ALIGNED(d->dst, 3) && ALIGNED(d->weights, 3), "src / tmp / dst / weights alignment");
+  NEED(d->tmp != d->src && d->tmp != d->dst, "tmp aliases src or dst");
+  return check(launch_gaussian_smooth(*d, (hipStream_t)stream), "gaussian_smooth");
+}
+static int nms_desc_ok(const sslcr_nms_desc* d) {
+  NEED(d, "null descriptor");
+  MAP_SHAPE_OK(d);
+  NEED(d->radius >= 1, "radius < 1");
+  NEED(d->max_detections >= 1, "max_detections < 1");
+  NEED(d->ncand >= 0 && d->ncand <= (int64_t)d->X * d->Y, "ncand outside [0, X * Y]");
+  NEED(d->map && d->state && d->cand && d->stage && d->counters && d->det_xy && d->det_prob, "null tensor");
+  NEED(ALIGNED(d->map, 3) && ALIGNED(d->state, 3) && ALIGNED(d->cand, 3) && ALIGNED(d->stage, 3) && ALIGNED(d->counters, 3) &&
+           ALIGNED(d->det_xy, 3) && ALIGNED(d->det_prob, 3), "map / state / cand / stage / counters / det_xy / det_prob alignment");
+  return 0;
+}
+int sslcr_nms_candidates(const sslcr_nms_desc* d, void* stream) {
+  if (nms_desc_ok(d)) return -1;
+  return check(launch_nms_candidates(*d, (hipStream_t)stream), "nms_candidates");
+}
+int sslcr_nms_rounds(const sslcr_nms_desc* d, int rounds, void* stream) {
+  if (nms_desc_ok(d)) return -1;
+  NEED(rounds >= 0, "rounds < 0");
+  return check(launch_nms_rounds(*d, rounds, (hipStream_t)stream), "nms_rounds");
+}
+int sslcr_nms_collect(const sslcr_nms_desc* d, void* stream) {
+  if (nms_desc_ok(d)) return -1;
+  return check(launch_nms_collect(*d, (hipStream_t)stream), "nms_collect");
+}
+int sslcr_lesion_hits(const sslcr_hits_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  MAP_SHAPE_OK(d);
+  NEED(d->L >= 0 && d->max_detections >= 1 && d->n_ignore >= 0, "L >= 0, max_detections >= 1 and n_ignore >= 0");
+  NEED(d->labels && d->det_xy && d->det_prob && d->n_det && d->hit, "null tensor");
+  NEED(d->L == 0 || d->tp_prob, "null tp_prob");
+  NEED(d->n_ignore == 0 || d->ignore, "null ignore");
+  NEED(ALIGNED(d->labels, 3) && ALIGNED(d->det_xy, 3) && ALIGNED(d->det_prob, 3) && ALIGNED(d->n_det, 3) && ALIGNED(d->ignore, 3) &&
+           ALIGNED(d->hit, 3) && ALIGNED(d->tp_prob, 3), "labels / det_xy / det_prob / n_det / ignore / hit / tp_prob alignment");
+  NEED(ALIGNED(d->areas, 7), "areas alignment");
+  return check(launch_lesion_hits(*d, (hipStream_t)stream), "lesion_hits");
+}
+#undef MAP_SHAPE_OK
+#undef ALIGNED
 int sslcr_d4_transform(const sslcr_d4_desc* d, void* stream) {
   NEED(d, "null descriptor");
   NEED(d->N >= 0 && d->Cn >= 1 && d->H >= 1, "N >= 0, Cn >= 1 and H >= 1");

@@ -212,6 +212,13 @@ hipError_t launch_rsp_gather(const sslcr_rsp_gather_desc& a, hipStream_t st);
 // annotation.hip
 hipError_t launch_points_in_polygons(const sslcr_pip_desc& a, hipStream_t st);
 hipError_t launch_map_confusion(const sslcr_map_confusion_desc& a, hipStream_t st);
+// froc.hip
+hipError_t launch_label_components(const sslcr_label_desc& a, hipStream_t st);
+hipError_t launch_gaussian_smooth(const sslcr_smooth_desc& a, hipStream_t st);
+hipError_t launch_nms_candidates(const sslcr_nms_desc& a, hipStream_t st);
+hipError_t launch_nms_rounds(const sslcr_nms_desc& a, int rounds, hipStream_t st);
+hipError_t launch_nms_collect(const sslcr_nms_desc& a, hipStream_t st);
+hipError_t launch_lesion_hits(const sslcr_hits_desc& a, hipStream_t st);
 // augment.hip
 hipError_t launch_weak_augment(const sslcr_weak_aug_desc& a, hipStream_t st);
 hipError_t launch_hed_colour(const sslcr_colour_aug_desc& a, hipStream_t st);

@@ -19,6 +19,10 @@ the truth mask (``.truth``) are two launches of sslcr_points_in_polygons at cons
 confusion matrix in the predict launch it already makes, and ``map_scores`` counts a finished map against the truth mask at up to 64
 thresholds in one pass (sslcr_map_confusion).
 
+Lesion-level FROC.  ``lesion_scores`` takes the map and the truth mask to what the Camelyon16 metric counts -- the truth's connected
+lesions, the map's non-maximum suppression into detections, the lesion under each detection (csrc/froc.hip) -- and ``froc`` /
+``FrocMeter`` turn the slides' false-positive and per-lesion probabilities into the curve and the score in host float64.
+
 Metrics.  The Kather mains build sklearn's confusion matrix and a weighted F1 from what ``test()`` returns
 (eval_Kather_SSL_CR.py:646-658, eval_Kather_SSL.py:519-530).  ``ConfusionMeter`` counts the same matrix on the device, batch by batch,
 with integer atomics; ``metrics_from_confusion`` derives the figures from it in host float64.
@@ -216,6 +220,70 @@ def _div(a, b):
     """a / b with 0 where b == 0 (sklearn's zero_division default value)"""
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return np.divide(a, b, out=np.zeros(np.broadcast(a, b).shape, dtype=np.float64), where=b != 0)
+
+
+def lesion_scores(probs_map, truth, *, threshold=0.5, radius=12, sigma=0.0, connectivity=2, ignore=None, max_detections=4096):
+    """A probability map against the LESIONS of the truth mask, what lesion-level FROC counts (include/sslcr.h has the definitions):
+    the connected components of ``truth`` (``kernels.label_components``), the optional float32 Gaussian of the map
+    (``kernels.gaussian_smooth``), its greedy non-maximum suppression into a detection list (``kernels.nms``) and the hit test
+    (``kernels.lesion_hits``), all on the device.  probs_map / truth: as for ``map_scores``; ignore: lesion labels (1-based) whose hits
+    are neither false nor true positives (the challenge treats isolated tumour cells so; ``areas`` of a first call tells the sizes).
+    Host traffic: one read of L, the reads ``kernels.nms`` documents, one copy of the small results.
+    -> dict: ``detections`` float64 [K, 3] (x, y, prob) in NMS order, ``hit`` int32 [K] (the label under each, 0 = none), ``fp_prob``
+    float64 = the probabilities of the detections with hit 0, ``tp_prob`` float64 [L] = the best probability on each lesion (0 where
+    nothing hit it or it is ignored), ``areas`` int64 [L], ``n_lesions`` = L, ``ignore`` = the sorted labels ignored."""
+    dev = next((t.device for t in (probs_map, truth) if torch.is_tensor(t) and t.is_cuda), None)
+    dev = dev if dev is not None else torch.device("cuda")
+    pm = torch.as_tensor(probs_map).to(dev, torch.float32).contiguous()
+    tr = torch.as_tensor(np.asarray(truth) != 0 if not torch.is_tensor(truth) else truth).to(dev).contiguous()
+    if tr.dtype != torch.bool and tr.dtype != torch.uint8:
+        tr = tr != 0
+    if tr.shape != pm.shape:
+        raise ValueError(f"lesion_scores: map {tuple(pm.shape)} and truth {tuple(tr.shape)} differ in shape")
+    ign = np.unique(np.asarray(list(ignore) if ignore is not None else [], dtype=np.int64))
+    labels, count = K.label_components(tr, connectivity)
+    det_xy, det_prob, k = K.nms(K.gaussian_smooth(pm, float(sigma)), threshold, radius, max_detections)
+    n_lesions = int(count.item())
+    hit, tp, areas = K.lesion_hits(labels, n_lesions, det_xy, det_prob, k, ignore=ign)
+    small = torch.cat([det_xy[:k].reshape(-1).double(), det_prob[:k].double(), hit[:k].double(), tp.double(), areas.double()]).cpu().numpy()
+    xy, prob, hit, tp, areas = np.split(small, np.cumsum([2 * k, k, k, n_lesions]))      # every value is exact in float64 (areas < 2^31)
+    hit = hit.astype(np.int32)
+    return dict(detections=np.concatenate([xy.reshape(k, 2), prob[:, None]], 1), hit=hit, fp_prob=prob[hit == 0], tp_prob=tp,
+                areas=areas.astype(np.int64), n_lesions=n_lesions, ignore=ign)
+
+
+def froc(fp_probs, tp_probs, n_slides, n_lesions, fps=(0.25, 0.5, 1, 2, 4, 8)):
+    """Lesion-level FROC in host float64, after the Camelyon16 challenge's evaluation.  fp_probs: the false positives' probabilities
+    over all scored slides; tp_probs: the best probability on every non-ignored lesion, zeros included; n_lesions: their number.
+    Thresholds are ``sorted(set(fp) | set(tp))[1:]``; at each, the false positives and the lesions at or above it are counted, then
+    (0, 0) is appended.  -> dict: ``thresholds``, ``avg_fp`` = FPs / n_slides, ``sensitivity`` = TPs / n_lesions (a division by zero
+    gives 0), ``fps`` and ``score`` = the mean sensitivity at ``fps`` false positives per slide, linearly interpolated."""
+    fp = np.asarray(fp_probs, dtype=np.float64).reshape(-1)
+    tp = np.asarray(tp_probs, dtype=np.float64).reshape(-1)
+    thr = np.unique(np.concatenate([fp, tp]))[1:]
+    n_fp = np.append((fp[None, :] >= thr[:, None]).sum(1), 0)
+    n_tp = np.append((tp[None, :] >= thr[:, None]).sum(1), 0)
+    avg_fp, sens = _div(n_fp, float(n_slides)), _div(n_tp, float(n_lesions))
+    fps = np.asarray(fps, dtype=np.float64)
+    return dict(thresholds=thr, avg_fp=avg_fp, sensitivity=sens, fps=fps, score=float(np.mean(np.interp(fps, avg_fp[::-1], sens[::-1]))))
+
+
+class FrocMeter:
+    """``update(lesion_scores(...))`` slide by slide, ``result()`` = ``froc`` over what was collected (ignored lesions left out)."""
+
+    def __init__(self, fps=(0.25, 0.5, 1, 2, 4, 8)):
+        self.fps, self.fp, self.tp, self.n_slides = fps, [], [], 0
+
+    def update(self, scores):
+        keep = ~np.isin(np.arange(1, scores["n_lesions"] + 1), scores["ignore"])
+        self.fp.append(np.asarray(scores["fp_prob"], dtype=np.float64))
+        self.tp.append(np.asarray(scores["tp_prob"], dtype=np.float64)[keep])
+        self.n_slides += 1
+
+    def result(self):
+        fp = np.concatenate(self.fp) if self.fp else np.zeros(0)
+        tp = np.concatenate(self.tp) if self.tp else np.zeros(0)
+        return froc(fp, tp, self.n_slides, len(tp), self.fps)
 
 
 def metrics_from_confusion(cm):

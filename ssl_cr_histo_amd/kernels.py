@@ -883,6 +883,138 @@ def map_confusion(map, truth, tissue, thresholds):
     return out
 
 
+SMOOTH_MAX_R = L.SMOOTH_MAX_R       # the largest tap radius gaussian_smooth takes
+NMS_READ_EVERY = 32                 # rounds of nms between two host reads of the "undecided left" word (tools/froc_bench.py)
+
+
+def _map2d(name, t, dtype):
+    if t.dtype != dtype or t.dim() != 2 or t.numel() < 1 or t.numel() >= 1 << 31:
+        raise L.SslcrError(f"{name}: a {dtype} tensor [X, Y] of 1 ... 2^31 - 1 cells expected")
+
+
+def label_components(mask, connectivity=2):
+    """-> ``(labels, count)``: device int32 [X, Y], 0 where ``mask`` is 0 and else the number of the cell's connected component, and
+    device int32 [1] = the number of components L (sslcr_label_components).  mask: device uint8 (or bool) [X, Y]; connectivity 2 = 8
+    neighbours, 1 = 4.  Components are numbered 1..L by the order of each component's first cell, as ``scipy.ndimage.label`` does.
+    Integer atomics whose order does not reach the result.  No sync."""
+    _chk(mask)
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    _map2d("label_components", mask, torch.uint8)
+    if connectivity not in (1, 2):
+        raise L.SslcrError(f"label_components: connectivity = {connectivity} outside {{1, 2}}")
+    n = mask.numel()
+    labels = torch.empty(mask.shape, dtype=torch.int32, device=mask.device)
+    count = torch.empty(1, dtype=torch.int32, device=mask.device)
+    work = torch.empty(n + (n + 1023) // 1024, dtype=torch.int32, device=mask.device)
+    d = L.LabelDesc(L.ptr(mask), L.ptr(labels), L.ptr(count), L.ptr(work), mask.shape[0], mask.shape[1], int(connectivity))
+    L.check(L.lib().sslcr_label_components(d, L.stream_ptr()))
+    return labels, count
+
+
+def gaussian_weights(sigma):
+    """the 2R + 1 float32 taps of ``gaussian_smooth``: exp(-k^2 / (2 sigma^2)) in float64, normalised to sum 1, cast; R = int(4 sigma + 0.5)"""
+    import numpy as np
+    R = int(4.0 * float(sigma) + 0.5)
+    k = np.arange(-R, R + 1, dtype=np.float64)
+    w = np.exp(-(k * k) / (2.0 * float(sigma) * float(sigma)))
+    return (w / w.sum()).astype(np.float32)
+
+
+def gaussian_smooth(map, sigma):
+    """-> device float32 [X, Y]: the separable Gaussian of ``map`` in float32, edge mode "nearest", axis 0 then axis 1, every tap one
+    product and one sum (sslcr_gaussian_smooth; the taps are ``gaussian_weights(sigma)``).  sigma == 0 returns ``map`` itself without a
+    launch.  No sync."""
+    _chk(map)
+    _map2d("gaussian_smooth", map, torch.float32)
+    if not sigma >= 0:
+        raise L.SslcrError(f"gaussian_smooth: sigma = {sigma}")
+    if sigma == 0:
+        return map
+    w = gaussian_weights(sigma)
+    R = (len(w) - 1) // 2
+    if R > SMOOTH_MAX_R:
+        raise L.SslcrError(f"gaussian_smooth: R = {R} > {SMOOTH_MAX_R}")
+    wd = torch.from_numpy(w).to(map.device)
+    tmp, dst = torch.empty_like(map), torch.empty_like(map)
+    d = L.SmoothDesc(L.ptr(map), L.ptr(tmp), L.ptr(dst), L.ptr(wd), map.shape[0], map.shape[1], R)
+    L.check(L.lib().sslcr_gaussian_smooth(d, L.stream_ptr()))
+    return dst
+
+
+def nms(map, threshold, radius, max_detections=4096, *, read_every=None, stats=None):
+    """Greedy non-maximum suppression of a map (include/sslcr.h has the definition) -> ``(det_xy, det_prob, count)``: device int32
+    [max_detections, 2], float32 [max_detections] and the number of detections K as a Python int; rows ``[:K]`` are the selected cells
+    in the order of the sequential loop.  map: device float32 [X, Y]; a cell is a candidate iff ``map > float32(threshold)``.
+    Launches: candidates, then rounds in batches of ``read_every`` (default ``NMS_READ_EVERY``), then collect.  Host reads: the
+    candidate count, one "undecided left" word per batch, K.  The rounds are bounded by the candidate count + 1 and ``SslcrError`` is
+    raised when they run out; it is raised too when K > max_detections (nothing is written past the capacity).
+    stats: a dict that receives ``candidates``, ``rounds`` and ``host_reads``."""
+    import numpy as np
+    _chk(map)
+    _map2d("nms", map, torch.float32)
+    radius, cap = int(radius), int(max_detections)
+    if radius < 1 or cap < 1:
+        raise L.SslcrError(f"nms: radius = {radius}, max_detections = {cap}")
+    every = NMS_READ_EVERY if read_every is None else int(read_every)
+    if every < 1:
+        raise L.SslcrError(f"nms: read_every = {every}")
+    dev, n = map.device, map.numel()
+    state = torch.empty(map.shape, dtype=torch.uint8, device=dev)
+    cand = torch.empty(n, dtype=torch.int32, device=dev)
+    stage = torch.empty(cap, dtype=torch.int32, device=dev)
+    counters = torch.empty(4, dtype=torch.int32, device=dev)
+    det_xy = torch.zeros((cap, 2), dtype=torch.int32, device=dev)
+    det_prob = torch.zeros(cap, dtype=torch.float32, device=dev)
+    d = L.NmsDesc(L.ptr(map), L.ptr(state), L.ptr(cand), L.ptr(stage), L.ptr(counters), L.ptr(det_xy), L.ptr(det_prob),
+                  float(np.float32(threshold)), map.shape[0], map.shape[1], min(radius, max(map.shape)), cap, 0)
+    lib, st = L.lib(), L.stream_ptr()
+    L.check(lib.sslcr_nms_candidates(d, st))
+    d.ncand = ncand = int(counters[0].item())
+    rounds, reads, left = 0, 1, ncand
+    while left:
+        if rounds > ncand:                                         # every round decides at least one candidate: cannot happen
+            raise L.SslcrError(f"nms: {left} of {ncand} candidates undecided after {rounds} rounds")
+        batch = min(every, ncand + 1 - rounds)
+        L.check(lib.sslcr_nms_rounds(d, batch, st))
+        rounds += batch
+        left = int(counters[1].item())
+        reads += 1
+    L.check(lib.sslcr_nms_collect(d, st))
+    count = int(counters[2].item())
+    reads += 1
+    if stats is not None:
+        stats.update(candidates=ncand, rounds=rounds, host_reads=reads)
+    if count > cap:
+        raise L.SslcrError(f"nms: {count} detections, max_detections = {cap}")
+    return det_xy, det_prob, count
+
+
+def lesion_hits(labels, n_lesions, det_xy, det_prob, n_det, *, ignore=None, areas=True):
+    """The hit test of a detection list against labelled lesions (sslcr_lesion_hits, one launch) -> ``(hit, tp_prob, areas)``:
+    ``hit`` int32 [max_detections], rows past the detections 0, = the label under each detection (0: a false positive); ``tp_prob``
+    float32 [L] = the best probability among the detections that hit lesion l + 1 and are not on a label in ``ignore``, 0 where there
+    is none; ``areas`` int64 [L] = the lesions' cell counts (None with areas=False).  labels: device int32 [X, Y]; n_lesions: L as a
+    Python int; det_xy / det_prob: what ``nms`` returns; n_det: a device int32 [1] tensor or a Python int; ignore: labels, any
+    sequence.  No sync."""
+    _chk(labels, det_xy, det_prob)
+    _map2d("lesion_hits", labels, torch.int32)
+    dev, cap, nl = labels.device, det_prob.numel(), int(n_lesions)
+    if det_xy.dtype != torch.int32 or tuple(det_xy.shape) != (cap, 2) or det_prob.dtype != torch.float32 or cap < 1 or nl < 0:
+        raise L.SslcrError("lesion_hits: det_xy int32 [K, 2], det_prob float32 [K] with K >= 1 and n_lesions >= 0 expected")
+    if not torch.is_tensor(n_det):
+        n_det = torch.tensor([int(n_det)], dtype=torch.int32)
+    n_det = n_det.to(dev, torch.int32).reshape(1).contiguous()
+    ign = torch.as_tensor(list(ignore) if ignore is not None else [], dtype=torch.int32).reshape(-1).to(dev)
+    hit = torch.zeros(cap, dtype=torch.int32, device=dev)
+    tp = torch.zeros(nl, dtype=torch.float32, device=dev)
+    ar = torch.zeros(nl, dtype=torch.int64, device=dev) if areas else None
+    d = L.HitsDesc(L.ptr(labels), L.ptr(det_xy), L.ptr(det_prob), L.ptr(n_det), L.ptr(ign) if ign.numel() else None, L.ptr(hit),
+                   L.ptr(tp) if nl else None, L.ptr(ar) if areas and nl else None, labels.shape[0], labels.shape[1], nl, cap, ign.numel())
+    L.check(L.lib().sslcr_lesion_hits(d, L.stream_ptr()))
+    return hit, tp, ar
+
+
 def grad_norm(flat, max_norm=float("inf")):
     """-> device tensor [norm, coef] for a 1-D fp32 tensor (any length, any 4-byte-aligned view): its 2-norm, summed in double in a
     fixed order, and min(1, max_norm / (norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_'s two numbers (sslcr_grad_norm).  No sync."""
