@@ -42,7 +42,10 @@ extern "C" {
  * added (additive; no existing entry, descriptor or launch changes); 15 = Camelyon16 annotations: sslcr_points_in_polygons and
  * sslcr_map_confusion added (additive; no existing entry, descriptor or launch changes).  Lesion scoring (sslcr_label_components,
  * sslcr_gaussian_smooth, sslcr_nms_candidates / _rounds / _collect, sslcr_lesion_hits) is additive in the same way and came WITHOUT
- * a new number: tests/test_annotation_cpu.py holds sslcr_version() to 15 by equality, so a caller tests for these entries by symbol. */
+ * a new number: tests/test_annotation_cpu.py holds sslcr_version() to 15 by equality, so a caller tests for these entries by symbol.
+ * The same holds for sslcr_conv2d_fp8_kernel_name and sslcr_fp8_scale_update (additive; the launches they name or issue are the
+ * ones sslcr_conv2d_fp8 and the engine's forward issued before); sslcr_conv2d_fp8 now refuses in_scale without in_shift, a
+ * descriptor whose launch read a NULL pointer on the device. */
 int sslcr_version(void);
 const char* sslcr_last_error(void);
 
@@ -123,6 +126,13 @@ typedef struct sslcr_fp8_desc {
 } sslcr_fp8_desc;
 int sslcr_conv2d_fp8(const sslcr_conv_desc* d, const sslcr_fp8_desc* q, void* stream);
 int sslcr_conv2d_fp8_partial_rows(const sslcr_conv_desc* d);      /* rows of d->stats the fp8 kernel writes; 0 = shape not served */
+/* name of the kernel instance sslcr_conv2d_fp8 would launch for this descriptor, spelled as rocprofv3 prints it (static string);
+   "" = shape not served */
+const char* sslcr_conv2d_fp8_kernel_name(const sslcr_conv_desc* d);
+/* delayed scaling, the update the engine runs between steps: slots [n][2] fp32 on the device = {x_scale, amax seen since the last
+   update}.  Per slot: x_scale <- 2^floor(log2(224 / amax)) clamped to [2^-16, 2^16] where 0 < amax < 3e38 (left as it is for a zero,
+   negative or non-finite amax), then amax <- 0. */
+int sslcr_fp8_scale_update(float* slots, int n, void* stream);
 typedef struct sslcr_pack_fp8_desc {
   const float* w;           /* [K][C][3][3] fp32 (PyTorch layout) */
   uint8_t* w8;              /* [K][3][3][C] e4m3 out */

@@ -119,6 +119,8 @@ SIGNATURES = {
     "sslcr_conv2d_s2_pair_ok": (i32, [i32, P(ConvDesc), P(ConvDesc)]),
     "sslcr_conv2d_fp8": (i32, [P(ConvDesc), P(Fp8Desc), vp]),
     "sslcr_conv2d_fp8_partial_rows": (i32, [P(ConvDesc)]),
+    "sslcr_conv2d_fp8_kernel_name": (C.c_char_p, [P(ConvDesc)]),
+    "sslcr_fp8_scale_update": (i32, [vp, i32, vp]),
     "sslcr_pack_conv_fp8": (i32, [P(PackFp8Desc), vp]),
     "sslcr_conv2d_wgrad": (i32, [i32, P(WgradDesc), vp]),
     "sslcr_conv2d_wgrad_kernel_name": (C.c_char_p, [i32, P(WgradDesc)]),

@@ -61,10 +61,16 @@ int sslcr_conv2d_s2_pair(int dtype, const sslcr_conv_desc* c1, const sslcr_conv_
 int sslcr_conv2d_fp8(const sslcr_conv_desc* d, const sslcr_fp8_desc* q, void* stream) {
   NEED(d && q && d->x && d->y && q->w8 && q->w_dequant, "null tensor");
   NEED(q->x_scale > 0.f, "x_scale must be positive");
+  NEED(!d->in_scale || d->in_shift, "in_scale without in_shift (the load path reads both)");
   NEED(conv_fp8_mode(*d) != 0, "shape not served by the fp8 kernel (3x3/1, C % 128, K % 128, 16x16-tileable or 8x8 with N % 4)");
   return check(launch_conv_fp8(*d, *q, (hipStream_t)stream), "conv2d_fp8");
 }
 int sslcr_conv2d_fp8_partial_rows(const sslcr_conv_desc* d) { return (d && conv_fp8_mode(*d)) ? conv_fp8_rows(*d) : 0; }
+const char* sslcr_conv2d_fp8_kernel_name(const sslcr_conv_desc* d) { return (d && conv_fp8_mode(*d)) ? conv_fp8_name(*d) : ""; }
+int sslcr_fp8_scale_update(float* slots, int n, void* stream) {
+  NEED(slots && n > 0, "slots");
+  return check(launch_fp8_scale_update(slots, n, (hipStream_t)stream), "fp8_scale_update");
+}
 int sslcr_pack_conv_fp8(const sslcr_pack_fp8_desc* d, void* stream) {
   NEED(d && d->w && d->w8 && d->w_dequant && d->K > 0 && d->C > 0, "args");
   NEED(!d->gamma || (d->beta && d->rmean && d->rvar), "BatchNorm fold needs gamma, beta, running mean and var");

@@ -126,23 +126,39 @@ def pack_conv_fp8(w_kcrs, *, bn=None, eps=1e-5):
 
 
 def conv2d_fp8(x, w8, w_dequant, *, x_scale=1.0, in_scale=None, in_shift=None, in_relu=False, bias=None, residual=None, relu=False,
-               want_stats=False, amax_out=None):
-    """fp8 (e4m3) forward conv 3x3 / stride 1 / pad 1: x bf16 NHWC [N,H,W,C], w8 [K,3,3,C] e4m3 bits -> y bf16 NHWC (+ stats)."""
-    _chk(x, w8, w_dequant, in_scale, in_shift, bias, residual)
+               want_stats=False, amax_out=None, x_scale_dev=None, out=None):
+    """fp8 (e4m3) forward conv 3x3 / stride 1 / pad 1: x bf16 NHWC [N,H,W,C], w8 [K,3,3,C] e4m3 bits -> y bf16 NHWC (+ stats).
+    x_scale_dev: a device float read instead of x_scale (the form the engine's delayed scaling uses)."""
+    _chk(x, w8, w_dequant, in_scale, in_shift, bias, residual, amax_out, x_scale_dev, out)
     assert x.dtype == torch.bfloat16 and w8.dtype == torch.uint8
     N, H, W, C = x.shape
     K = w8.shape[0]
-    y = torch.empty((N, H, W, K), dtype=torch.bfloat16, device=x.device)
+    assert tuple(w8.shape) == (K, 3, 3, C) and w_dequant.dtype == torch.float32 and w_dequant.numel() == K
+    assert all(t is None or (t.dtype == torch.float32 and t.numel() == C) for t in (in_scale, in_shift))
+    assert bias is None or (bias.dtype == torch.float32 and bias.numel() == K)
+    assert residual is None or (residual.dtype == torch.bfloat16 and tuple(residual.shape) == (N, H, W, K))
+    assert all(t is None or (t.dtype == torch.float32 and t.numel() >= 1) for t in (amax_out, x_scale_dev))
+    y = out if out is not None else torch.empty((N, H, W, K), dtype=torch.bfloat16, device=x.device)
+    assert y.dtype == torch.bfloat16 and tuple(y.shape) == (N, H, W, K)
     d = L.ConvDesc(L.ptr(x), None, L.ptr(y), L.ptr(in_scale), L.ptr(in_shift), L.ptr(bias), L.ptr(residual), None,
                    N, H, W, C, K, 3, 3, 1, 1, H, W, H, W, 1, 0, int(in_relu), int(relu), 0, 0, 0, 0, 0)
-    q = L.Fp8Desc(L.ptr(w8), L.ptr(w_dequant), float(x_scale), None, L.ptr(amax_out))
+    q = L.Fp8Desc(L.ptr(w8), L.ptr(w_dequant), float(x_scale), L.ptr(x_scale_dev), L.ptr(amax_out))
     stats = None
     if want_stats:
         rows = L.lib().sslcr_conv2d_fp8_partial_rows(d)
         stats = torch.full((rows, 2, K), float("nan"), dtype=torch.float32, device=x.device)
         d.stats = L.ptr(stats)
+    global last_conv_kernel
+    last_conv_kernel = L.lib().sslcr_conv2d_fp8_kernel_name(d).decode()
     L.check(L.lib().sslcr_conv2d_fp8(d, q, L.stream_ptr()))
     return (y, stats) if want_stats else y
+
+
+def fp8_scale_update(slots):
+    """delayed scaling: slots [n, 2] fp32 = (x_scale, amax since the last update), updated in place (sslcr_fp8_scale_update)"""
+    _chk(slots)
+    assert slots.dtype == torch.float32 and slots.dim() == 2 and slots.shape[1] == 2
+    L.check(L.lib().sslcr_fp8_scale_update(L.ptr(slots), slots.shape[0], L.stream_ptr()))
 
 
 def conv2d_wgrad(x, dy, dw, R, S, stride, pad, *, in_scale=None, in_shift=None, in_relu=False, seg_images=0):

@@ -141,19 +141,22 @@ def check(got, want, bnd, what, kernel="", dims="nhwk"):
     return worst
 
 
-def stats_bound(acc, amag, n, fp32_operands=False):
-    """-> (sum64, sumsq64, bound of sum, bound of sumsq) per channel of the accumulator acc [..., K] (module text)"""
+def stats_bound(acc, amag, n, fp32_operands=False, extra=None):
+    """-> (sum64, sumsq64, bound of sum, bound of sumsq) per channel of the accumulator acc [..., K] (module text); extra: a further
+    per-element error of the accumulator (the fp8 MFMA's alignment term)"""
     K = acc.shape[-1]
     a = acc.reshape(-1, K)
     e = bound(a, amag.reshape(-1, K), n, 0, fp32_operands)
+    if extra is not None:
+        e = e + extra.reshape(-1, K)
     g = LAM * math.sqrt(a.shape[0]) * U
     return a.sum(0), (a * a).sum(0), e.sum(0) + g * a.abs().sum(0), (2 * a.abs() * e + e * e).sum(0) + g * (a * a).sum(0)
 
 
-def check_stats(stats, acc, amag, n, what, kernel="", fp32_operands=False):
+def check_stats(stats, acc, amag, n, what, kernel="", fp32_operands=False, extra=None):
     """stats: the kernel's partial rows [rows, 2, K] fp32 (summed here in double)"""
     st = stats.detach().cpu().double().sum(0)
-    s, ss, bs, bss = stats_bound(acc, amag, n, fp32_operands)
+    s, ss, bs, bss = stats_bound(acc, amag, n, fp32_operands, extra)
     w1 = check(st[0], s, bs, what + " sum", kernel, dims="k")
     w2 = check(st[1], ss, bss, what + " sumsq", kernel, dims="k")
     return max(w1, w2)
@@ -603,3 +606,159 @@ def optimizer_ref(kind, p, graw, s1, s2, *, lr, beta1, beta2, eps, wd, momentum,
     e_step = 2 * U * step.abs() + lr * (momentum * e_b + e_g)
     p1 = p - step
     return dict(p=(p1, U * p1.abs() + e_step), s1=(buf, e_b))
+
+
+# ====================================================================================================================
+# The fp8 (OCP e4m3) forward conv path: conv_fp8.hip, pack_fp8_kernel, fp8_scale_update_kernel.
+#
+# Quantisation is reproduced EXACTLY, not bounded: the reference feeds conv_fwd the operands as the kernel's matrix instruction sees
+# them.  The rounded fp32 operations, per line of the source:
+#   pack          f = gamma / sqrtf(rvar + eps) [3, formed in fp32 here as well]; w * f [1]; amax; q = 448.f / amax [1]; scale = 2^(e - 1)
+#                 with q = fr * 2^e (frexpf: exact); w * f * scale (a power of two: exact); clamp; RNE to e4m3; dequant = 1 / scale (exact).
+#                 Without the fold every step is exact or a single correctly rounded operation: codes and dequant are compared bit for bit.
+#   load path     s' = in_scale * xs [1], d' = in_shift * xs [1], v = fmaf(x, s', d') [1]   (no transform: v = x * xs [1]); amax = max |v|;
+#                 clamp to [0 or -448, 448]; RNE to e4m3 (v_cvt_pk_fp8_f32).  fp8_activations() forms each of these once in float64 and
+#                 rounds it once to fp32: the same bits.
+#   conv          e4m3 x e4m3 products carry 4 + 4 significand bits: exact in fp32.  The reduction over n = 9 * C terms is the
+#                 LAM * sqrt(n) * u * mag term of bound() -- plus the alignment term below, the one part that is measured.
+#   epilogue      dq = w_dequant[k] / xs [1: the reference takes fl32(dq / xs) as out_scale, so this one is reproduced, not charged];
+#                 acc * dq [1]; + bias [1]; + residual [1] <= EPI = 4.  The statistics sum acc * dq (before bias): check_stats on it.
+#   amax_out      max |v| / xs [1]: within one fp32 ulp of the reference's value.
+# ====================================================================================================================
+E4M3_MAX = 448.0
+
+# The scaled 16x16x128 fp8 MFMA does NOT sum its 128 products like fp32 additions.  MEASURED on the MI355X (tools/fp8_mfma_probe.py: the
+# conv kernel with centre-tap filters, one product of 448 * 256 per instruction next to 127 products of about 2^-j * 256, the large term
+# taken out again by the fp32 bias; error beyond the bf16 output rounding, in units of u * (large product)):
+#     j              0      4      8     10    12    14    16         without the large product, every j
+#     worst error  4598   6146   1352   339    89    23    7.3        0 (the result is exact)
+# i.e. the products of ONE instruction are aligned to the largest of them and lose what lies about 2^-14 below it (from j = 8 on the
+# small products vanish altogether: the error is their whole sum); the accumulator operand is not affected.  Activations of modest
+# range sit far inside bound() (rows without the producer transform: the total error is 12 .. 78 u * mag where LAM * sqrt(n) + EPI is
+# 276 .. 547); a channel saturated at 448 next to channels near 1 -- in_scale = 1e3 on channel 0 of these tests -- does not: 2 .. 3526
+# elements of 18 rows lay over bound(), up to 6.1 x, with both signs, spread over 2 .. 252 output channels and up to 2279 pixels,
+# and nowhere with x_scale = 16 (everything saturates: less range).  That is precision, not indexing.
+# The per-element term for it: FP8_MFMA_U * u * pmax, pmax = the sum over the element's 9 * C / 128 instructions of an upper bound of the
+# instruction's largest product (fp8_pmax).  FP8_MFMA_MEASURED_U is the largest part of |got - y64| that bound() leaves uncovered, in
+# units of u * pmax, over the 42 rows of tests/fp8_cases.py against the float64 reference (fp8_align_needed; test_conv_fp8_f64 prints it
+# per row): 1502.1 at 3x32x48x128x256 [in_scale relu_in stats] x_scale 0.25, recorded rounded up; 24 of the 42 rows need 0.  The
+# constant is twice that value.  (The probe's adversarial 6146 is NOT covered: it takes 127 products all at the edge of the window.)
+# Worst err / bound per instance over the table (MI355X, 256 CUs), y | statistics:
+#                                  bound() alone      with the alignment term (what the tests assert)
+#   conv3x3_fp8_kernel<16, false>  0.991  | -         0.990  | -            (no statistics rows: the rows without the transform are the eval form)
+#   conv3x3_fp8_kernel<16, true>   6.087  | 2.560     0.974  | 0.111
+#   conv3x3_fp8_kernel<8, false>   0.990  | -         0.989  | -
+#   conv3x3_fp8_kernel<8, true>    2.775  | 1.175     0.955  | 0.130
+# (y near 1 is the bf16 output rounding, as for every bf16 kernel: u_out * |y64| is attained.)
+FP8_MFMA_MEASURED_U = 1503.0
+FP8_MFMA_U = 2.0 * FP8_MFMA_MEASURED_U
+
+
+def e4m3(v):
+    """float64 -> the nearest OCP e4m3 value (float64): clamp to +-448, step 2^(max(floor(log2 |v|), -6) - 3) (the subnormals share
+    the step 2^-9 of the lowest binade), round |v| / step half to even.  The sign of zero is kept."""
+    v = v.double().clamp(-E4M3_MAX, E4M3_MAX)
+    a = v.abs()
+    _, ex = torch.frexp(a)                         # a = m * 2^ex, m in [0.5, 1): floor(log2 a) = ex - 1, exactly
+    step = torch.ldexp(torch.ones_like(a), (ex - 1).clamp_min(-6) - 3)
+    return torch.copysign(torch.round(a / step) * step, v)
+
+
+def _fl32(t):
+    return t.float().double()
+
+
+def fp8_pack_ref(w_kcrs, bn=None, eps=1e-5):
+    """sslcr_pack_conv_fp8 in float64 -> (wq [K, 3, 3, C]: the e4m3 values w * f * scale, dequant [K] = 1 / scale, bias [K] | None).
+    scale = 2^(e - 1) with 448 / amax = fr * 2^e taken with math.frexp on the fp32-rounded quotient, as the kernel forms it; an
+    all-zero filter keeps scale 1."""
+    w = w_kcrs.float()
+    K = w.shape[0]
+    bias = None
+    if bn is not None:
+        g, b, rm, rv = (t.float() for t in bn)
+        f = g / torch.sqrt(rv + torch.tensor(eps, dtype=torch.float32))        # fp32, operation by operation like the kernel
+        w = w * f.view(-1, 1, 1, 1)
+        bias = b.double() - rm.double() * f.double()       # (the kernel may contract beta - rmean * f into one fma: compared within 2 u)
+    amax = w.abs().flatten(1).max(1).values
+    scale = torch.ones(K, dtype=torch.float64)
+    for k in range(K):
+        m = np.float32(amax[k].item())
+        if m > 0:
+            _, e = math.frexp(float(np.float32(448.0) / m))
+            scale[k] = math.ldexp(1.0, e - 1)
+    wq = e4m3(w.double() * scale.view(-1, 1, 1, 1))
+    return wq.permute(0, 2, 3, 1).contiguous(), 1.0 / scale, bias
+
+
+def fp8_activations(x, xs, in_scale=None, in_shift=None, in_relu=False):
+    """store_chunk of conv3x3_fp8_kernel: x NHWC (bf16 values), xs the fp32 x_scale -> (xq float64 NHWC: the e4m3 values the MFMA reads,
+    (amax_hi, amax_lo)): amax_hi = max |v| / xs over the tensor, v the fp32 value before ReLU and saturation -- what the kernel
+    tracks ("padding pixels and, with ReLU, the negative side are included") -- and amax_lo = max |relu(v)| / xs with in_relu (= amax_hi
+    without): the header's "max |transformed activation| before scaling and clamping", which an implementation may also take after the
+    ReLU.  Saturation at 448 is in neither."""
+    xs = f32(xs)
+    xd = x.double()
+    if in_scale is not None:
+        s = _fl32(in_scale.double() * xs)
+        d = _fl32(in_shift.double() * xs)
+        v = _fl32(xd * s + d)                      # fmaf: one rounding (the note in xform() applies)
+    else:
+        v = _fl32(xd * xs)
+    hi = float(v.abs().max()) / xs
+    lo = float(v.clamp_min(0.0).max()) / xs if in_relu else hi
+    return e4m3(v.clamp(0.0 if in_relu else -E4M3_MAX, E4M3_MAX)), (hi, lo)
+
+
+def fp8_out_scale(dequant, xs):
+    """the epilogue's dq = w_dequant[k] / x_scale, one fp32 division -> float64 [K]"""
+    return _fl32(dequant.double() / f32(xs))
+
+
+def fp8_conv_ref(xq, wq, dequant, xs):
+    """-> (acc64 * dq, accmag * dq, pmax * dq): the dequantised accumulator, its magnitude and the alignment companion (fp8_pmax),
+    NHWC float64 -- what the statistics sum and the epilogue (bias / residual / ReLU through epilogue()) starts from"""
+    _, _, acc, amag = conv_fwd(xq, wq, 1, 1)
+    dq = fp8_out_scale(dequant, xs)
+    return acc * dq, amag * dq, fp8_pmax(xq, wq) * dq
+
+
+def fp8_pmax(xq, wq):
+    """sum over the kernel's matrix instructions (9 taps x C / 128 slabs per output element) of an upper bound of the instruction's
+    largest product: max |x| over the slab's 128 channels of the tap's pixel times max |w| over the same 128 channels of the tap's
+    filter row -> NHWC float64.  A 3x3 convolution of the two slab-wise maxima."""
+    N, H, W, C = xq.shape
+    K = wq.shape[0]
+    xm = xq.abs().reshape(N, H, W, C // 128, 128).amax(-1)
+    wm = wq.abs().reshape(K, 3, 3, C // 128, 128).amax(-1)
+    return _nhwc(F.conv2d(_nchw(xm), wm.permute(0, 3, 1, 2), None, 1, 1))
+
+
+def fp8_bound(y64, mag, pmax, n, out_dtype=1):
+    """bound() plus the alignment term of the scaled fp8 MFMA (FP8_MFMA_U above)"""
+    u_out = U_BF16 if out_dtype == 1 else 0.0
+    return bound(y64, mag, n, out_dtype) + (1.0 + u_out) * fp8_align(pmax)
+
+
+def fp8_align(pmax):
+    return FP8_MFMA_U * U * pmax
+
+
+def fp8_align_needed(got, y64, mag, pmax, n, out_dtype=1):
+    """the measurement behind FP8_MFMA_MEASURED_U: the largest part of |got - y64| that bound() does not cover, in units of u * pmax"""
+    u_out = U_BF16 if out_dtype == 1 else 0.0
+    over = (got.detach().cpu().double() - y64).abs() - bound(y64, mag, n, out_dtype)
+    return float((over / ((1.0 + u_out) * U * pmax.clamp_min(1e-300))).clamp_min(0.0).max())
+
+
+def fp8_scale_update_ref(slots):
+    """fp8_scale_update_kernel on slots [n, 2] fp32 -> the expected slots: s = clamp(2^floor(log2(224 / m)), 2^-16, 2^16) where
+    0 < m < 3e38 (else unchanged), amax <- 0.  The quotient is rounded to fp32 first, as the kernel's is."""
+    out = slots.detach().cpu().clone()
+    for i in range(out.shape[0]):
+        m = np.float32(out[i, 1].item())
+        if m > 0 and m < np.float32(3.0e38):
+            _, e = math.frexp(float(np.float32(224.0) / m))
+            out[i, 0] = min(max(math.ldexp(1.0, e - 1), 2.0 ** -16), 2.0 ** 16)
+        out[i, 1] = 0.0
+    return out

@@ -245,3 +245,232 @@ def test_config5_per_gpu_shape_vs_oracle(dtype):
         held(f"{tag}/grad/{k}", float((mine - want).norm() / want.norm()), 0.9, floor=2e-2)
     del eng, te, st
     torch.cuda.empty_cache()
+
+
+# ------------------------------------------------------------------------------------------------ float64 per-element bounds
+# tests/fp8_cases.py through kernels.conv2d_fp8: operands tests/_fp8.py, reference and bounds tests/_f64.py (fp8 section).
+import math  # noqa: E402
+
+import _f64 as B  # noqa: E402
+import _fp8 as F8  # noqa: E402
+from fp8_cases import CASES as F8_CASES  # noqa: E402
+
+ROW_A, ROW_B, ROW_G = (1, 16, 16, 128, 128), (3, 32, 48, 128, 256), (4, 8, 8, 512, 512)
+TRAIN_SET = "in_scale relu_in stats"
+_F8_DEV = {}      # shape -> the operands on the device and the device's weight pack (one shape at a time)
+
+
+def _f8_id(r):
+    return f"{'x'.join('cus' if v is None else str(v) for v in r[0])}-{r[1].replace(' ', '+') or 'plain'}-xs{r[2]:g}"
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
+
+
+def _same_e4m3(w8, wq):
+    """device codes [K, 3, 3, C] against float64 e4m3 values, bit for bit (the sign of zero included)"""
+    got = w8.view(torch.float8_e4m3fn).float().cpu().double()
+    return torch.equal(got, wq) and torch.equal(torch.signbit(got), torch.signbit(wq))
+
+
+def _f8_operands(shape):
+    from ssl_cr_histo_amd import kernels as K
+    if shape not in _F8_DEV:
+        _F8_DEV.clear()
+        t = F8.inputs(shape)
+        w8, dq, _ = K.pack_conv_fp8(t["w"].to(DEV))
+        wq, dq_ref, _ = B.fp8_pack_ref(t["w"])
+        assert _same_e4m3(w8, wq) and torch.equal(dq.cpu().double(), dq_ref)          # the launch and the reference use the same filters
+        assert len(set(dq_ref.tolist())) >= 13 and float(dq_ref[3]) == 1.0
+        d = dict(x=t["x"].to(DEV).to(torch.bfloat16), w8=w8, dq=dq, in_scale=t["in_scale"].to(DEV), in_shift=t["in_shift"].to(DEV),
+                 bias=t["bias"].to(DEV), residual=t["residual"].to(DEV).to(torch.bfloat16))
+        _F8_DEV[shape] = (t, d)
+    return _F8_DEV[shape]
+
+
+def _f8_launch(d, flags, xs, **extra):
+    """-> (y, stats | None): y pre-filled with NaN (the wrapper pre-fills the statistics rows)"""
+    from ssl_cr_histo_amd import kernels as K
+    f = F8.flags_of(flags)
+    kw = dict(extra)
+    if "in_scale" in f:
+        kw.update(in_scale=d["in_scale"], in_shift=d["in_shift"], in_relu="relu_in" in f)
+    if "bias" in f:
+        kw["bias"] = d["bias"]
+    if "residual" in f:
+        kw["residual"] = d["residual"]
+    N, H, W, _ = d["x"].shape
+    y = torch.full((N, H, W, d["w8"].shape[0]), float("nan"), dtype=torch.bfloat16, device=DEV)
+    out = K.conv2d_fp8(d["x"], d["w8"], d["dq"], x_scale=xs, relu="relu" in f, want_stats="stats" in f, out=y, **kw)
+    return out if "stats" in f else (out, None)
+
+
+@pytest.mark.parametrize("row", F8_CASES, ids=[_f8_id(r) for r in F8_CASES])
+def test_conv_fp8_f64(row):
+    """every row of tests/fp8_cases.py: the launch is EXACTLY the row's instance, and y and the BatchNorm partial statistics hold the
+    float64 per-element bounds of tests/_f64.py with the operands quantised as the kernel quantises them: bound() plus the measured
+    alignment term of the fp8 MFMA (FP8_MFMA_U; the figure each row needs is printed).  No element is excused."""
+    from ssl_cr_histo_amd import kernels as K
+    shape, flags, xs, name, _ = row
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    walks = shape[0] is None
+    shape = F8.batch(shape, cus)
+    assert (F8.tiles(shape) > F8.walkers(shape, cus)) == walks, (shape, cus)
+    t, d = _f8_operands(shape)
+    y, stats = _f8_launch(d, flags, xs)
+    assert K.last_conv_kernel == name, K.last_conv_kernel
+    r = F8.reference(shape, flags, xs, t)
+    what = f"fp8 {'x'.join(map(str, shape))} [{flags}] xs {xs:g}"
+    print(f"[f64] {what} | {name} | over bound() without the alignment term: {B.fp8_align_needed(y, r['y'], r['mag'], r['pmax'], r['n']):.1f} u * pmax "
+          f"(FP8_MFMA_MEASURED_U = {B.FP8_MFMA_MEASURED_U:g})")
+    B.check(y, r["y"], r["bnd"], what, name)
+    if stats is not None:
+        assert stats.shape[0] == 4 * F8.tiles(shape)
+        B.check_stats(stats, r["acc"], r["amag"], r["n"], what + " statistics", name, extra=B.fp8_align(r["pmax"]))
+
+
+@pytest.mark.parametrize("flags", [TRAIN_SET, "bias residual relu"], ids=["train", "eval"])
+@pytest.mark.parametrize("shape", [ROW_A, ROW_G], ids=["a", "g"])
+def test_conv_fp8_x_scale_dev(shape, flags):
+    """x_scale_dev -- the only form the engine uses -- is read INSTEAD of the host x_scale: host 1.0 with a device 8.0 gives the bits of
+    host 8.0, and not those of host 1.0"""
+    _, d = _f8_operands(shape)
+    dev8 = torch.full((1,), 8.0, device=DEV)
+    y_dev, st_dev = _f8_launch(d, flags, 1.0, x_scale_dev=dev8)
+    y_8, st_8 = _f8_launch(d, flags, 8.0)
+    y_1, _ = _f8_launch(d, flags, 1.0)
+    assert torch.isfinite(y_8.float()).all()
+    assert torch.equal(_bits(y_dev), _bits(y_8))
+    if st_8 is not None:
+        assert torch.equal(_bits(st_dev), _bits(st_8))
+    assert not torch.equal(_bits(y_dev), _bits(y_1))
+    assert float(dev8) == 8.0
+
+
+@pytest.mark.parametrize("flags, xs", [(TRAIN_SET, 1.0), ("in_scale stats", 3.0), ("", 16.0)], ids=["relu", "no_relu-xs3", "plain-xs16"])
+@pytest.mark.parametrize("shape", [ROW_A, ROW_B, ROW_G], ids=["a", "b", "g"])
+def test_conv_fp8_amax(shape, flags, xs):
+    """amax_out, from 0: within one fp32 ulp of the reference's interval [max |relu(v)| / xs, max |v| / xs] (v the transformed activation
+    before saturation: wide with the ReLU -- channel 0's in_scale is about -1e3 on a pixel of 1000 -- and a point without); a second
+    launch into an amax_out holding twice that value leaves it bit-unchanged (the atomic only raises)"""
+    t, d = _f8_operands(shape)
+    f = F8.flags_of(flags)
+    xf = dict(in_scale=t["in_scale"], in_shift=t["in_shift"], in_relu="relu_in" in f) if "in_scale" in f else {}
+    _, (hi, lo) = B.fp8_activations(t["x"], xs, **xf)
+    assert (lo < hi / 2) if "relu_in" in f else (lo == hi)
+    amax = torch.zeros(1, device=DEV)
+    _f8_launch(d, flags, xs, amax_out=amax)
+    got = float(amax)
+    print(f"[f64] amax {'x'.join(map(str, shape))} [{flags}] xs {xs:g}: got {got!r}, interval [{lo!r}, {hi!r}]")
+    assert lo - F8.ulp32(lo) <= got <= hi + F8.ulp32(hi), (got, lo, hi)
+    twice = torch.full((1,), 2.0 * got, device=DEV)
+    _f8_launch(d, flags, xs, amax_out=twice)
+    assert torch.equal(_bits(twice), _bits(torch.full((1,), 2.0 * got, device=DEV)))
+
+
+def _planted_filters(Ko, Cc, seed):
+    """filters whose per-channel amax sits on the frexp edge of the scale rule and at the ends of the range"""
+    w = rnd(seed, (Ko, Cc, 3, 3), 0.05)
+    edge = np.float32(448.0 * 2.0 ** -15)
+    plant = {0: edge, 1: np.nextafter(edge, np.float32(0)), 2: np.nextafter(edge, np.float32(1)), 3: np.float32(1e-30), 4: np.float32(1e30)}
+    for k, v in plant.items():
+        i = int(w[k].abs().argmax())
+        w[k] = (w[k].double() * (float(v) / float(w[k].abs().max()))).float()
+        w[k].view(-1)[i] = float(v) * (1.0 if i % 2 else -1.0)
+        assert float(w[k].abs().max()) == float(v)
+    w[5] = 0.0
+    w[6] *= 37.0
+    w[7] *= 1e-3
+    return w, plant
+
+
+@pytest.mark.parametrize("Ko, Cc", [(16, 128), (9, 384)])
+def test_pack_fp8_f64(Ko, Cc):
+    """pack_fp8_kernel against the float64 restatement: without the BatchNorm fold every code and every dequant bit for bit, with amax
+    planted on the frexp edge 448 * 2^-15, its two fp32 neighbours, 1e-30, 1e30 and 0; with the fold (one fp32 ulp of w * f can flip an
+    e4m3 rounding) at most 1e-4 of the codes differ, and a gamma = 0 channel packs to zeros with dequant 1 and bias beta"""
+    from ssl_cr_histo_amd import kernels as K
+    w, plant = _planted_filters(Ko, Cc, 41)
+    w8, dq, _ = K.pack_conv_fp8(w.to(DEV))
+    wq, dq_ref, _ = B.fp8_pack_ref(w)
+    assert torch.equal(dq.cpu().double(), dq_ref), (dq.cpu(), dq_ref)
+    assert _same_e4m3(w8, wq)
+    assert [float(v) for v in dq_ref[:6]] == [2.0 ** -15, 2.0 ** -15, 2.0 ** -14, 2.0 ** -108, 2.0 ** 91, 1.0]
+    top = wq.abs().flatten(1).max(1).values
+    assert float(top[0]) == 448.0 and float(top[5]) == 0.0 and bool(((top >= 224.0) & (top <= 448.0))[[1, 2, 3, 4, 6, 7, 8]].all())
+    # the fold
+    w = rnd(42, (Ko, Cc, 3, 3), 0.05)
+    gamma, beta, rmean, rvar = rnd(43, (Ko,)).abs() + 0.5, rnd(44, (Ko,)), rnd(45, (Ko,)), rnd(46, (Ko,)).abs() + 0.5
+    gamma[7] = 0.0
+    bn = (gamma, beta, rmean, rvar)
+    w8f, dqf, bias = K.pack_conv_fp8(w.to(DEV), bn=tuple(v.to(DEV) for v in bn))
+    wqf, dqf_ref, bias_ref = B.fp8_pack_ref(w, bn=bn)
+    assert torch.equal(dqf.cpu().double(), dqf_ref)
+    gotf = w8f.view(torch.float8_e4m3fn).float().cpu().double()
+    flipped = float((gotf != wqf).double().mean())
+    print(f"[f64] pack_fp8 with the fold, K {Ko} C {Cc}: share of flipped codes {flipped:.2e}")
+    assert flipped < 1e-4
+    assert float(gotf[7].abs().max()) == 0.0 and float(dqf[7]) == 1.0 and float(bias[7]) == float(beta[7])
+    f = gamma.double() / torch.sqrt(rvar.double() + 1e-5)
+    B.check(bias, bias_ref, 2 * B.U * (beta.double().abs() + (rmean.double() * f).abs()) + 4 * B.U * (rmean.double() * f).abs(), "folded bias", dims="k")
+
+
+def test_fp8_scale_update():
+    """fp8_scale_update_kernel through sslcr_fp8_scale_update: n = 70 slots (two 64-thread blocks, the second ragged) inside a buffer
+    of 80; scale <- clamp(2^floor(log2(224 / amax)), 2^-16, 2^16) where 0 < amax < 3e38, else unchanged; every amax word 0 afterwards;
+    slots beyond n untouched.  (Values within 2 fp32 ulps of 224 * 2^k other than the exact ones are left out: there the fp32 quotient
+    may round across the power of two.)"""
+    from ssl_cr_histo_amd import kernels as K
+    vals = [0.0, -1.0, float("nan"), float("inf"), 3.2e38, 1e-30, 1e30, 224.0, 448.0, 28.0, 7168.0, 100.0, 0.01, 223.0, 225.0]
+    want = [None, None, None, None, None, 65536.0, 2.0 ** -16, 1.0, 0.5, 8.0, 2.0 ** -5, 2.0, 16384.0, 1.0, 0.5]
+    n, total = 70, 80
+    slots = torch.empty((total, 2), dtype=torch.float32)
+    slots[:, 0] = torch.arange(total, dtype=torch.float32) + 3.0
+    slots[:, 1] = torch.tensor([vals[i % len(vals)] for i in range(total)])
+    dev = slots.to(DEV)
+    K.fp8_scale_update(dev[:n])
+    got = dev.cpu()
+    expect = slots.clone()
+    for i in range(n):
+        m = vals[i % len(vals)]
+        if want[i % len(vals)] is not None:
+            s = min(max(2.0 ** math.floor(math.log2(224.0 / m)), 2.0 ** -16), 2.0 ** 16)
+            assert s == want[i % len(vals)], (m, s)
+            expect[i, 0] = s
+        expect[i, 1] = 0.0
+    assert torch.equal(expect[:n], B.fp8_scale_update_ref(slots[:n]))          # the float64 restatement agrees with the literal table
+    assert torch.equal(_bits(got[:n, 1]), torch.zeros(n, dtype=torch.int32))   # +0.0, the NaN and the negative entries included
+    assert torch.equal(_bits(got[:n, 0]), _bits(expect[:n, 0])), (got[:n, 0], expect[:n, 0])
+    assert torch.equal(_bits(got[n:]), _bits(slots[n:]))                       # (NaN bits compared as integers)
+
+
+@pytest.mark.parametrize("flags, xs", [("", 1.0), (TRAIN_SET, 1.0), ("in_scale stats", 1.0), (TRAIN_SET, 0.25), (TRAIN_SET, 16.0), ("", 16.0)],
+                         ids=["plain", "train", "no_relu", "train-xs0.25", "train-xs16", "plain-xs16"])
+@pytest.mark.parametrize("shape", [ROW_A, (2, 16, 16, 512, 512), ROW_G], ids=["a", "four_slabs", "g"])
+def test_conv_fp8_load_path_quantiser_is_exact(shape, flags, xs):
+    """the load path alone, bit for bit: with identity centre-tap filters (K = C; every weight scale 2^8) an output element is ONE
+    non-zero product, xq * 256 * 2^-8 / xs -- exact in fp32 and in bf16 for a power-of-two x_scale -- so y must EQUAL the reference's
+    e4m3 activations / xs: the tie rule, the subnormals, the saturation, in_scale * xs per channel of every slab, the ReLU clamp, and
+    the zero pixel.  (This is the check the alignment term of the bound cannot blur.)"""
+    from ssl_cr_histo_amd import kernels as K
+    N, H, W, Cc, Ko = shape
+    assert Cc == Ko
+    t = F8.inputs(shape)
+    w = torch.zeros((Ko, Cc, 3, 3))
+    w[torch.arange(Ko), torch.arange(Cc), 1, 1] = 1.0
+    w8, dq, _ = K.pack_conv_fp8(w.to(DEV))
+    assert set(dq.cpu().tolist()) == {2.0 ** -8}
+    f = F8.flags_of(flags)
+    xf = dict(in_scale=t["in_scale"], in_shift=t["in_shift"], in_relu="relu_in" in f) if "in_scale" in f else {}
+    y = torch.full((N, H, W, Ko), float("nan"), dtype=torch.bfloat16, device=DEV)
+    K.conv2d_fp8(t["x"].to(DEV).to(torch.bfloat16), w8, dq, x_scale=xs, out=y, **{k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in xf.items()})
+    xq, _ = B.fp8_activations(t["x"], xs, **xf)
+    want = xq / xs
+    got = y.float().cpu().double()
+    bad = (got != want).nonzero()
+    assert bad.shape[0] == 0, (f"{bad.shape[0]} of {got.numel()} activations quantised differently, first at (n, h, w, c) = {bad[0].tolist()}: "
+                               f"got {float(got[tuple(bad[0])])!r} want {float(want[tuple(bad[0])])!r}")
+    if xs == 1.0 and not f:
+        assert int((xq[..., F8.SUB].abs() < 2.0 ** -6).sum()) > 0.9 * xq[..., F8.SUB].numel()        # the subnormal channel is one
+        assert float(xq[0, 0, 0, :8].min()) == 448.0 and float(xq[N - 1, H // 2, W // 2].abs().max()) == 0.0
