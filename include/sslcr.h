@@ -746,6 +746,67 @@ typedef struct sslcr_hits_desc {
 } sslcr_hits_desc;
 int sslcr_lesion_hits(const sslcr_hits_desc* d, void* stream);
 
+/* ---- The Camelyon16 evaluation mask on the device: what the challenge's computeEvaluationMask / computeITCList take from
+ *      scipy.ndimage and scikit-image (csrc/evalmask.hip).  The challenge takes the Euclidean distance transform of the complement of
+ *      the annotation mask, keeps the cells with distance < 75 um / (2 * cell size), fills the holes, labels the result at
+ *      connectivity 2, and ignores every lesion whose major_axis_length is below 275 um / cell size as isolated tumour cells (ITC).
+ *      Parity with the challenge's Evaluation_FROC.py and with scikit-image's regionprops is UNPINNED: neither was available to
+ *      compare against.  PINNED instead, by equality, are the integer definitions below, restated in NumPy (tests/_evalmask_ref.py)
+ *      and held there against scipy 1.15.3: sqrt(float64(edt_squared)) is distance_transform_edt bit for bit, fill_holes is
+ *      binary_fill_holes.  Arrays are [X][Y] as for sslcr_map_confusion.  All entries are asynchronous and use integer arithmetic
+ *      only: two calls give equal bits.  These entries were added without a new version number; a caller tells them by their symbols.
+ *
+ *      sslcr_edt_squared.  A cell is a ZERO cell iff mask == 0 (invert = 0) or mask != 0 (invert = 1).
+ *          out[x][y] = min(limit, min over the zero cells (x', y') of (x - x')^2 + (y - y')^2)
+ *      so it is 0 on a zero cell, and a mask without a zero cell gives `limit` everywhere (scipy's answer there is meaningless; this
+ *      is the library's definition).  limit = INT32_MAX is the unlimited transform.  For a float64 T, sqrt(float64(k)) < T is
+ *      monotone in k, so "distance < T" is out < limit(T) with limit(T) the smallest k >= 0 with sqrt(float64(k)) >= T, which the
+ *      host finds once.  below (or NULL): below[x][y] = out[x][y] < limit ? 1 : 0.  work: X * Y int32 of scratch (the distances
+ *      within the rows).  The rows are swept in chunks of SSLCR_EDT_ROW_CELLS cells with a carry from chunk to chunk.
+ *      Errors: NULL descriptor or mask / out / work, X < 1, Y < 1, X * Y >= 2^31, X^2 + Y^2 >= 2^31 (every squared distance must
+ *      fit an int32), limit < 0, invert outside {0, 1}, pointers not 4-byte aligned (the mask is read as whole dwords). */
+#define SSLCR_EDT_ROW_CELLS 1024
+typedef struct sslcr_edt_desc {
+  const uint8_t* mask;      /* [X][Y]; 4-byte aligned */
+  int32_t* out;             /* [X][Y] */
+  uint8_t* below;           /* [X][Y] or NULL */
+  int32_t* work;            /* [X * Y] */
+  int X, Y, limit, invert;
+} sslcr_edt_desc;
+int sslcr_edt_squared(const sslcr_edt_desc* d, void* stream);
+
+/*      sslcr_fill_holes.  out[x][y] = 1 where mask != 0, or where the cell's component of the BACKGROUND (mask == 0) at connectivity 1
+ *      holds no cell of the array's border (row 0, row X - 1, column 0, column Y - 1); else 0.  A background cell joined to the
+ *      border only diagonally is therefore filled.  The background is labelled by sslcr_label_components; labels / count / work are
+ *      its outputs and scratch, of its sizes (labels [X * Y], work [X * Y + ceil(X * Y / 1024)]), and hold nothing of use afterwards.
+ *      Errors: NULL descriptor or pointers, X < 1, Y < 1, X * Y >= 2^31, out == mask, pointers not 4-byte aligned. */
+typedef struct sslcr_fill_desc {
+  const uint8_t* mask;      /* [X][Y], nonzero = set */
+  uint8_t* out;             /* [X][Y] of 0 / 1; 4-byte aligned, not mask */
+  int32_t* labels;          /* [X][Y] scratch */
+  int32_t* count;           /* [1] scratch */
+  int32_t* work;            /* [X * Y + ceil(X * Y / 1024)] scratch */
+  int X, Y;
+} sslcr_fill_desc;
+int sslcr_fill_holes(const sslcr_fill_desc* d, void* stream);
+
+/*      sslcr_region_moments.  For every label l + 1 in 1..L, over the cells (x, y) with labels[x][y] == l + 1:
+ *          moments[l] += (the number of cells, sum x, sum y, sum x^2, sum y^2, sum x y)
+ *      int64, by integer atomics (exact, order-independent); the caller zeroes it.  Labels outside 1..L are left out.  The shape
+ *      bound of sslcr_edt_squared holds here too: x, y < 46341, so every term is below 2^31 and every sum below 2^62.
+ *      From these the host takes regionprops' major_axis_length in its inertia-tensor form, with A = the area:
+ *          a = (A sum x^2 - (sum x)^2) / A^2,  c = (A sum y^2 - (sum y)^2) / A^2,  b = (A sum x y - sum x sum y) / A^2
+ *      (exact integer numerators and denominators, each quotient rounded to float64 once),
+ *          l1 = (a + c) / 2 + sqrt(((a - c) / 2)^2 + b^2),  major_axis_length = 4 sqrt(l1).
+ *      Errors: NULL descriptor or labels, NULL moments with L > 0, X < 1, Y < 1, X * Y >= 2^31, X^2 + Y^2 >= 2^31, L < 0, labels not
+ *      4-byte or moments not 8-byte aligned. */
+typedef struct sslcr_moments_desc {
+  const int32_t* labels;    /* [X][Y] */
+  int64_t* moments;         /* [L][6] */
+  int X, Y, L;
+} sslcr_moments_desc;
+int sslcr_region_moments(const sslcr_moments_desc* d, void* stream);
+
 /* ---- device-side strong augmentation, the colour ops of the reference's RandAugment pool ("next" row f4) on a uint8 batch in HBM.
  *      As with sslcr_weak_augment the random draws stay on the host, in the reference's order (ssl_cr_histo_amd/augment.py);
  *      the kernels are the deterministic per-pixel arithmetic.

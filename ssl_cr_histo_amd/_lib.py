@@ -99,6 +99,10 @@ NmsDesc = _S("NmsDesc", [(k, vp) for k in ("map", "state", "cand", "stage", "cou
              [(k, i32) for k in ("X", "Y", "radius", "max_detections", "ncand")])
 HitsDesc = _S("HitsDesc", [(k, vp) for k in ("labels", "det_xy", "det_prob", "n_det", "ignore", "hit", "tp_prob", "areas")] +
               [(k, i32) for k in ("X", "Y", "L", "max_detections", "n_ignore")])
+EDT_ROW_CELLS = 1024          # SSLCR_EDT_ROW_CELLS
+EdtDesc = _S("EdtDesc", [(k, vp) for k in ("mask", "out", "below", "work")] + [(k, i32) for k in ("X", "Y", "limit", "invert")])
+FillDesc = _S("FillDesc", [(k, vp) for k in ("mask", "out", "labels", "count", "work")] + [(k, i32) for k in ("X", "Y")])
+MomentsDesc = _S("MomentsDesc", [(k, vp) for k in ("labels", "moments")] + [(k, i32) for k in ("X", "Y", "L")])
 PackDesc = _S("PackDesc", [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("gamma", vp), ("beta", vp), ("rmean", vp),
                            ("rvar", vp), ("eps", f32), ("bias_out", vp)] + [(k, i32) for k in ("K", "C", "R", "S", "dgrad_flip")] + [("scale_out", vp)])
 
@@ -162,6 +166,9 @@ SIGNATURES = {
     "sslcr_nms_rounds": (i32, [P(NmsDesc), i32, vp]),
     "sslcr_nms_collect": (i32, [P(NmsDesc), vp]),
     "sslcr_lesion_hits": (i32, [P(HitsDesc), vp]),
+    "sslcr_edt_squared": (i32, [P(EdtDesc), vp]),
+    "sslcr_fill_holes": (i32, [P(FillDesc), vp]),
+    "sslcr_region_moments": (i32, [P(MomentsDesc), vp]),
     "sslcr_optimizer_step": (i32, [vp, i32, i32, P(OptDesc), vp]),
     "sslcr_optimizer_step_groups": (i32, [vp, i32, i32, P(OptDesc), i32, vp, vp]),
     "sslcr_grad_norm": (i32, [vp, sz, f32, vp, vp, vp]),

@@ -400,6 +400,38 @@ int sslcr_lesion_hits(const sslcr_hits_desc* d, void* stream) {
   NEED(ALIGNED(d->areas, 7), "areas alignment");
   return check(launch_lesion_hits(*d, (hipStream_t)stream), "lesion_hits");
 }
+// ---- the Camelyon16 evaluation mask (evalmask.hip)
+#define SQ_SHAPE_OK(d) NEED((int64_t)(d)->X * (d)->X + (int64_t)(d)->Y * (d)->Y < (int64_t)1 << 31, "X^2 + Y^2 >= 2^31")
+int sslcr_edt_squared(const sslcr_edt_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  MAP_SHAPE_OK(d);
+  SQ_SHAPE_OK(d);
+  NEED(d->limit >= 0, "limit < 0");
+  NEED(d->invert == 0 || d->invert == 1, "invert outside {0, 1}");
+  NEED(d->mask && d->out && d->work, "null tensor");
+  NEED(ALIGNED(d->mask, 3) && ALIGNED(d->out, 3) && ALIGNED(d->work, 3), "mask / out / work alignment");
+  NEED(d->out != d->work, "out aliases work");
+  return check(launch_edt_squared(*d, (hipStream_t)stream), "edt_squared");
+}
+int sslcr_fill_holes(const sslcr_fill_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  MAP_SHAPE_OK(d);
+  NEED(d->mask && d->out && d->labels && d->count && d->work, "null tensor");
+  NEED(d->out != d->mask, "out aliases mask");
+  NEED(ALIGNED(d->out, 3) && ALIGNED(d->labels, 3) && ALIGNED(d->count, 3) && ALIGNED(d->work, 3), "out / labels / count / work alignment");
+  return check(launch_fill_holes(*d, (hipStream_t)stream), "fill_holes");
+}
+int sslcr_region_moments(const sslcr_moments_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  MAP_SHAPE_OK(d);
+  SQ_SHAPE_OK(d);
+  NEED(d->L >= 0, "L < 0");
+  NEED(d->labels, "null tensor");
+  NEED(d->L == 0 || d->moments, "null moments");
+  NEED(ALIGNED(d->labels, 3) && ALIGNED(d->moments, 7), "labels / moments alignment");
+  return check(launch_region_moments(*d, (hipStream_t)stream), "region_moments");
+}
+#undef SQ_SHAPE_OK
 #undef MAP_SHAPE_OK
 #undef ALIGNED
 int sslcr_d4_transform(const sslcr_d4_desc* d, void* stream) {

@@ -219,6 +219,10 @@ hipError_t launch_nms_candidates(const sslcr_nms_desc& a, hipStream_t st);
 hipError_t launch_nms_rounds(const sslcr_nms_desc& a, int rounds, hipStream_t st);
 hipError_t launch_nms_collect(const sslcr_nms_desc& a, hipStream_t st);
 hipError_t launch_lesion_hits(const sslcr_hits_desc& a, hipStream_t st);
+// evalmask.hip
+hipError_t launch_edt_squared(const sslcr_edt_desc& a, hipStream_t st);
+hipError_t launch_fill_holes(const sslcr_fill_desc& a, hipStream_t st);
+hipError_t launch_region_moments(const sslcr_moments_desc& a, hipStream_t st);
 // augment.hip
 hipError_t launch_weak_augment(const sslcr_weak_aug_desc& a, hipStream_t st);
 hipError_t launch_hed_colour(const sslcr_colour_aug_desc& a, hipStream_t st);

@@ -22,6 +22,9 @@ thresholds in one pass (sslcr_map_confusion).
 Lesion-level FROC.  ``lesion_scores`` takes the map and the truth mask to what the Camelyon16 metric counts -- the truth's connected
 lesions, the map's non-maximum suppression into detections, the lesion under each detection (csrc/froc.hip) -- and ``froc`` /
 ``FrocMeter`` turn the slides' false-positive and per-lesion probabilities into the curve and the score in host float64.
+``evaluation_mask`` makes the challenge's evaluation mask from the truth mask on the device -- the 75 um dilation by an exact squared
+distance transform, the hole filling, the lesions' labels and moments (csrc/evalmask.hip) -- and the isolated-tumour-cell list from
+the major axis lengths; ``lesion_scores(..., evaluation=)`` scores against it.
 
 Metrics.  The Kather mains build sklearn's confusion matrix and a weighted F1 from what ``test()`` returns
 (eval_Kather_SSL_CR.py:646-658, eval_Kather_SSL.py:519-530).  ``ConfusionMeter`` counts the same matrix on the device, batch by batch,
@@ -222,7 +225,56 @@ def _div(a, b):
     return np.divide(a, b, out=np.zeros(np.broadcast(a, b).shape, dtype=np.float64), where=b != 0)
 
 
-def lesion_scores(probs_map, truth, *, threshold=0.5, radius=12, sigma=0.0, connectivity=2, ignore=None, max_detections=4096):
+def major_axis_lengths(moments):
+    """``regionprops``' ``major_axis_length`` of every component, in cells, from its raw moments, in host float64.  moments: [L, 6]
+    integers (area A, sum x, sum y, sum x^2, sum y^2, sum x y), what ``kernels.region_moments`` returns.  The central second moments
+    over the area, a = (A sum x^2 - (sum x)^2) / A^2, c = (A sum y^2 - (sum y)^2) / A^2, b = (A sum x y - sum x sum y) / A^2, have
+    exact Python-int numerators and are rounded once each; l1 = (a + c) / 2 + sqrt(((a - c) / 2)^2 + b^2) is the larger eigenvalue
+    of the inertia tensor and the result is 4 sqrt(l1).  A row with A == 0 gives nan.  -> float64 [L]."""
+    import math
+    rows = np.asarray(torch.as_tensor(moments).cpu()).reshape(-1, 6).tolist()
+    out = np.full(len(rows), np.nan, dtype=np.float64)
+    for i, (A, sx, sy, sxx, syy, sxy) in enumerate(rows):
+        A, sx, sy, sxx, syy, sxy = int(A), int(sx), int(sy), int(sxx), int(syy), int(sxy)
+        if A <= 0:
+            continue
+        a, c, b = (A * sxx - sx * sx) / (A * A), (A * syy - sy * sy) / (A * A), (A * sxy - sx * sy) / (A * A)
+        half = (a - c) / 2.0
+        out[i] = 4.0 * math.sqrt((a + c) / 2.0 + math.sqrt(half * half + b * b))
+    return out
+
+
+def evaluation_mask(truth, *, cell_um, dilate_um=75.0, itc_um=275.0, connectivity=2, device=None):
+    """The Camelyon16 challenge's evaluation mask and ITC list from a truth mask, on the device (include/sslcr.h has the definitions;
+    parity with the challenge's script is unpinned, the integer steps are pinned against scipy):
+    ``kernels.distance_transform_sq`` to the nearest truth cell, the cells with distance < ``dilate_um / (2 cell_um)`` (as an integer
+    limit on the squared distance, ``kernels.distance_limit``), ``kernels.fill_holes``, ``kernels.label_components(connectivity)``,
+    ``kernels.region_moments``; then ``major_axis_lengths`` on the host.  truth: [X, Y], a device uint8 / bool tensor or a host array
+    (``WsiDeviceLoader.truth``); cell_um: microns per map cell, e.g. 0.243 * 64; device: where to work (default: truth's, else cuda).
+    Host traffic: one read of L, one copy of the moments.
+    -> dict: ``mask`` device uint8 [X, Y] (the filled dilation), ``labels`` device int32 [X, Y], ``n_lesions`` = L, ``moments`` int64
+    [L, 6], ``major_axis`` float64 [L] in cells, ``itc`` = the sorted 1-based labels with ``major_axis < itc_um / cell_um``, ``limit``."""
+    cell_um = float(cell_um)
+    if not cell_um > 0:
+        raise ValueError(f"evaluation_mask: cell_um = {cell_um}")
+    if device is None:
+        device = truth.device if torch.is_tensor(truth) and truth.is_cuda else torch.device("cuda")
+    tr = torch.as_tensor(np.asarray(truth) != 0 if not torch.is_tensor(truth) else truth).to(device).contiguous()
+    if tr.dtype != torch.bool and tr.dtype != torch.uint8:
+        tr = tr != 0
+    limit = K.distance_limit(float(dilate_um) / (cell_um * 2.0))
+    _, binary = K.distance_transform_sq(tr, limit, invert=True, below=True)
+    mask = K.fill_holes(binary)
+    labels, count = K.label_components(mask, connectivity)
+    n_lesions = int(count.item())
+    moments = K.region_moments(labels, n_lesions).cpu().numpy().astype(np.int64).reshape(n_lesions, 6)
+    major = major_axis_lengths(moments)
+    itc = np.flatnonzero(major < float(itc_um) / cell_um).astype(np.int64) + 1
+    return dict(mask=mask, labels=labels, n_lesions=n_lesions, moments=moments, major_axis=major, itc=itc, limit=limit)
+
+
+def lesion_scores(probs_map, truth, *, threshold=0.5, radius=12, sigma=0.0, connectivity=2, ignore=None, max_detections=4096,
+                  evaluation=None):
     """A probability map against the LESIONS of the truth mask, what lesion-level FROC counts (include/sslcr.h has the definitions):
     the connected components of ``truth`` (``kernels.label_components``), the optional float32 Gaussian of the map
     (``kernels.gaussian_smooth``), its greedy non-maximum suppression into a detection list (``kernels.nms``) and the hit test
@@ -231,19 +283,30 @@ def lesion_scores(probs_map, truth, *, threshold=0.5, radius=12, sigma=0.0, conn
     Host traffic: one read of L, the reads ``kernels.nms`` documents, one copy of the small results.
     -> dict: ``detections`` float64 [K, 3] (x, y, prob) in NMS order, ``hit`` int32 [K] (the label under each, 0 = none), ``fp_prob``
     float64 = the probabilities of the detections with hit 0, ``tp_prob`` float64 [L] = the best probability on each lesion (0 where
-    nothing hit it or it is ignored), ``areas`` int64 [L], ``n_lesions`` = L, ``ignore`` = the sorted labels ignored."""
-    dev = next((t.device for t in (probs_map, truth) if torch.is_tensor(t) and t.is_cuda), None)
-    dev = dev if dev is not None else torch.device("cuda")
-    pm = torch.as_tensor(probs_map).to(dev, torch.float32).contiguous()
-    tr = torch.as_tensor(np.asarray(truth) != 0 if not torch.is_tensor(truth) else truth).to(dev).contiguous()
-    if tr.dtype != torch.bool and tr.dtype != torch.uint8:
-        tr = tr != 0
-    if tr.shape != pm.shape:
-        raise ValueError(f"lesion_scores: map {tuple(pm.shape)} and truth {tuple(tr.shape)} differ in shape")
-    ign = np.unique(np.asarray(list(ignore) if ignore is not None else [], dtype=np.int64))
-    labels, count = K.label_components(tr, connectivity)
-    det_xy, det_prob, k = K.nms(K.gaussian_smooth(pm, float(sigma)), threshold, radius, max_detections)
-    n_lesions = int(count.item())
+    nothing hit it or it is ignored), ``areas`` int64 [L], ``n_lesions`` = L, ``ignore`` = the sorted labels ignored.
+    evaluation: the dict ``evaluation_mask`` returns.  The map is then scored against ITS ``labels`` / ``n_lesions`` (the challenge's
+    dilated, hole-filled lesions) without labelling anything again, ``ignore`` defaults to its ``itc`` list, and ``truth`` /
+    ``connectivity`` are not used (``truth`` may be None)."""
+    if evaluation is not None:
+        labels, n_lesions = evaluation["labels"], int(evaluation["n_lesions"])
+        pm = torch.as_tensor(probs_map).to(labels.device, torch.float32).contiguous()
+        if labels.shape != pm.shape:
+            raise ValueError(f"lesion_scores: map {tuple(pm.shape)} and evaluation labels {tuple(labels.shape)} differ in shape")
+        ign = np.unique(np.asarray(list(ignore if ignore is not None else evaluation["itc"]), dtype=np.int64))
+        det_xy, det_prob, k = K.nms(K.gaussian_smooth(pm, float(sigma)), threshold, radius, max_detections)
+    else:
+        dev = next((t.device for t in (probs_map, truth) if torch.is_tensor(t) and t.is_cuda), None)
+        dev = dev if dev is not None else torch.device("cuda")
+        pm = torch.as_tensor(probs_map).to(dev, torch.float32).contiguous()
+        tr = torch.as_tensor(np.asarray(truth) != 0 if not torch.is_tensor(truth) else truth).to(dev).contiguous()
+        if tr.dtype != torch.bool and tr.dtype != torch.uint8:
+            tr = tr != 0
+        if tr.shape != pm.shape:
+            raise ValueError(f"lesion_scores: map {tuple(pm.shape)} and truth {tuple(tr.shape)} differ in shape")
+        ign = np.unique(np.asarray(list(ignore) if ignore is not None else [], dtype=np.int64))
+        labels, count = K.label_components(tr, connectivity)
+        det_xy, det_prob, k = K.nms(K.gaussian_smooth(pm, float(sigma)), threshold, radius, max_detections)
+        n_lesions = int(count.item())
     hit, tp, areas = K.lesion_hits(labels, n_lesions, det_xy, det_prob, k, ignore=ign)
     small = torch.cat([det_xy[:k].reshape(-1).double(), det_prob[:k].double(), hit[:k].double(), tp.double(), areas.double()]).cpu().numpy()
     xy, prob, hit, tp, areas = np.split(small, np.cumsum([2 * k, k, k, n_lesions]))      # every value is exact in float64 (areas < 2^31)

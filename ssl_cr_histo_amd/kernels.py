@@ -1031,6 +1031,89 @@ def lesion_hits(labels, n_lesions, det_xy, det_prob, n_det, *, ignore=None, area
     return hit, tp, ar
 
 
+EDT_ROW_CELLS = L.EDT_ROW_CELLS     # cells of a row that distance_transform_sq sweeps per chunk (a carry joins the chunks)
+EDT_UNLIMITED = (1 << 31) - 1
+
+
+def _sq_shape(name, t):
+    if t.shape[0] ** 2 + t.shape[1] ** 2 >= 1 << 31:
+        raise L.SslcrError(f"{name}: X^2 + Y^2 = {t.shape[0] ** 2 + t.shape[1] ** 2} >= 2^31 (a squared distance must fit an int32)")
+
+
+def distance_limit(T):
+    """the smallest integer k >= 0 with ``sqrt(float64(k)) >= T``: for an exact squared distance d2, ``d2 < k`` iff ``sqrt(d2) < T``
+    (the float64 square root is monotone).  Host arithmetic; T: a finite float."""
+    import math
+    T = float(T)
+    if not math.isfinite(T):
+        raise ValueError(f"distance_limit: T = {T}")
+    if T <= 0.0:
+        return 0
+    k = int(math.ceil(T * T))
+    while k > 0 and math.sqrt(float(k - 1)) >= T:   # T * T is rounded: settle the last unit against the definition
+        k -= 1
+    while math.sqrt(float(k)) < T:
+        k += 1
+    return k
+
+
+def distance_transform_sq(mask, limit=None, *, invert=False, below=False):
+    """-> device int32 [X, Y]: ``min(limit, the exact squared Euclidean distance to the nearest zero cell of mask)``, 0 on the zero
+    cells (sslcr_edt_squared, two launches, integer arithmetic only: two calls give equal bits).  ``limit=None`` is the unlimited
+    transform (``EDT_UNLIMITED`` = INT32_MAX); a mask without a zero cell gives ``limit`` everywhere.  ``sqrt`` of the unlimited
+    result in float64 is ``scipy.ndimage.distance_transform_edt(mask)``.  mask: device uint8 (or bool) [X, Y], any non-zero value
+    set, with X^2 + Y^2 < 2^31.  invert=True measures the distance to the nearest SET cell instead (the zero cells are those with
+    mask != 0); below=True returns ``(out, out < limit as uint8)``, written by the same launch.  No sync."""
+    _chk(mask)
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    _map2d("distance_transform_sq", mask, torch.uint8)
+    _sq_shape("distance_transform_sq", mask)
+    limit = EDT_UNLIMITED if limit is None else int(limit)
+    if not 0 <= limit <= EDT_UNLIMITED:
+        raise L.SslcrError(f"distance_transform_sq: limit = {limit} outside [0, 2^31 - 1]")
+    out = torch.empty(mask.shape, dtype=torch.int32, device=mask.device)
+    work = torch.empty(mask.shape, dtype=torch.int32, device=mask.device)
+    under = torch.empty(mask.shape, dtype=torch.uint8, device=mask.device) if below else None
+    d = L.EdtDesc(L.ptr(mask), L.ptr(out), L.ptr(under), L.ptr(work), mask.shape[0], mask.shape[1], limit, 1 if invert else 0)
+    L.check(L.lib().sslcr_edt_squared(d, L.stream_ptr()))
+    return (out, under) if below else out
+
+
+def fill_holes(mask):
+    """-> device uint8 [X, Y] of 0 / 1: ``mask != 0``, or a background cell whose connectivity-1 background component touches no cell
+    of the array's border -- ``scipy.ndimage.binary_fill_holes`` (sslcr_fill_holes: the complement, ``label_components`` on it, a
+    border pass, the apply pass; no host read in between).  mask: device uint8 (or bool) [X, Y].  No sync."""
+    _chk(mask)
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    _map2d("fill_holes", mask, torch.uint8)
+    n, dev = mask.numel(), mask.device
+    out = torch.empty(mask.shape, dtype=torch.uint8, device=dev)
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    work = torch.empty(n + (n + 1023) // 1024, dtype=torch.int32, device=dev)
+    d = L.FillDesc(L.ptr(mask), L.ptr(out), L.ptr(labels), L.ptr(count), L.ptr(work), mask.shape[0], mask.shape[1])
+    L.check(L.lib().sslcr_fill_holes(d, L.stream_ptr()))
+    return out
+
+
+def region_moments(labels, n):
+    """-> device int64 [n, 6]: for label l + 1, over its cells (x, y): area, sum x, sum y, sum x^2, sum y^2, sum x y
+    (sslcr_region_moments, one launch; integer atomics, exact, and below 2^62 under the shape bound X^2 + Y^2 < 2^31).  labels: device
+    int32 [X, Y] as ``label_components`` returns; n: the number of labels as a Python int (0: no launch).  No sync."""
+    _chk(labels)
+    _map2d("region_moments", labels, torch.int32)
+    _sq_shape("region_moments", labels)
+    n = int(n)
+    if n < 0:
+        raise L.SslcrError(f"region_moments: n = {n}")
+    out = torch.zeros((n, 6), dtype=torch.int64, device=labels.device)
+    d = L.MomentsDesc(L.ptr(labels), L.ptr(out) if n else None, labels.shape[0], labels.shape[1], n)
+    L.check(L.lib().sslcr_region_moments(d, L.stream_ptr()))
+    return out
+
+
 def grad_norm(flat, max_norm=float("inf")):
     """-> device tensor [norm, coef] for a 1-D fp32 tensor (any length, any 4-byte-aligned view): its 2-norm, summed in double in a
     fixed order, and min(1, max_norm / (norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_'s two numbers (sslcr_grad_norm).  No sync."""
