@@ -162,6 +162,61 @@ def check_stats(stats, acc, amag, n, what, kernel="", fp32_operands=False, extra
     return max(w1, w2)
 
 
+# ---- the input-gradient forms of the stride-2 convs.  conv_dgrad(..., residual=...) is the reference of all of them; what differs is
+# the reduction length and which positions a launch may touch.
+def parity_classes():
+    """the 3x3 / 2 / pad 1 input gradient by input-pixel parity class: input pixel (2 i + ph, 2 j + pw) receives dY through the taps
+    (r, s) with ph + 1 - r and pw + 1 - s even, and through no other -> [(ph, pw, tap_mask (bit r * 3 + s), taps kept)]: 1, 2, 2, 4 taps"""
+    out = []
+    for ph in (0, 1):
+        for pw in (0, 1):
+            taps = [r * 3 + s for r in range(3) for s in range(3) if (ph + 1 - r) % 2 == 0 and (pw + 1 - s) % 2 == 0]
+            out.append((ph, pw, sum(1 << t for t in taps), len(taps)))
+    return out
+
+
+def parity_bound(y64, mag, K, out_dtype, fp32_operands=False):
+    """bound() with every parity class's own reduction length: (the taps its mask keeps) * K"""
+    bnd = torch.empty_like(y64)
+    for ph, pw, _, taps in parity_classes():
+        bnd[:, ph::2, pw::2] = bound(y64[:, ph::2, pw::2], mag[:, ph::2, pw::2], taps * K, out_dtype, fp32_operands)
+    return bnd
+
+
+def bits_equal(a, b):
+    """the same stored values bit for bit (fp32 holds every bf16 exactly, so both storage dtypes compare as fp32 words)"""
+    a, b = a.detach().cpu().float().contiguous(), b.detach().cpu().float().contiguous()
+    return a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+def check_parity_launch(before, after, ph, pw, what):
+    """one launch of class (ph, pw) into the shared buffer wrote all of its class and nothing else: with the four classes disjoint
+    and covering the map, every element is then written exactly once"""
+    own = torch.zeros(tuple(after.shape[1:3]), dtype=torch.bool)
+    own[ph::2, pw::2] = True
+    a, b = after.detach().cpu().float(), before.detach().cpu().float()
+    assert bits_equal(a[:, ~own], b[:, ~own]), f"{what}: the launch of class ({ph}, {pw}) changed a pixel of another class"
+    assert not bool(torch.isnan(a[:, own]).any()), f"{what}: the launch of class ({ph}, {pw}) left a pixel of its class unwritten"
+
+
+def scatter_reach(shape, osh=2):
+    """the positions of dX [N, H, W, C] that the 1x1 / stride-`osh` input gradient reaches: (osh * i, osh * j)"""
+    reach = torch.zeros(tuple(shape[1:3]), dtype=torch.bool)
+    reach[::osh, ::osh] = True
+    return reach
+
+
+def check_scatter(got, base, want, bnd, what, kernel=""):
+    """the scatter-accumulate into `base` (as stored): the reached positions hold base + gradient within the bound (want = conv_dgrad
+    with residual = base), every other position is bit-equal to the base"""
+    reach = scatter_reach(got.shape)
+    g = got.detach().cpu().float()
+    if not bits_equal(g[:, ~reach], base[:, ~reach]):
+        n = int((g[:, ~reach] != base.float()[:, ~reach]).sum())
+        raise AssertionError(f"{what} [{kernel}]: {n} elements at positions the scatter does not reach differ from the base")
+    return check(g[:, reach], want[:, reach], bnd[:, reach], what, kernel, dims="npc")
+
+
 # ====================================================================================================================
 # The non-conv kernels: BatchNorm finalize / apply / backward, pooling, the fp32 heads and the losses.
 #

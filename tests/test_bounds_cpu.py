@@ -139,6 +139,94 @@ def test_wgrad_partial_slab_rounded_to_bf16_fails():
         B.check(fold(slabs), want, bnd, "wgrad with a slab rounded to bf16", dims="krsc")
 
 
+# ---------------------------------------------------------------- the input-gradient forms beside par4 (route ops dgrad_t, dgrad_parity, scatter)
+def _dgrad32(dy, w, stride, pad, hw):
+    shape = (dy.shape[0], w.shape[-1], hw[0], hw[1])
+    return torch.nn.grad.conv2d_input(shape, w.permute(0, 3, 1, 2), dy.permute(0, 3, 1, 2), stride, pad).permute(0, 2, 3, 1).contiguous()
+
+
+def _dgrad_operands(dtype, R, pad, N=3, H=9, W=11, C=64, K=128):
+    OH, OW = (H + 2 * pad - R) // 2 + 1, (W + 2 * pad - R) // 2 + 1
+    return q(rnd(41, (N, OH, OW, K)), dtype), q(rnd(42, (K, R, R, C), 0.05), dtype), q(rnd(43, (N, H, W, C)), dtype), (H, W)
+
+
+def _parity_emul(dy, w, res, hw, dtype, fault=None):
+    """four launches, one per input-pixel parity class, each with the filter taps of its mask only: fp32 accumulation, the fp32
+    residual add, the storage rounding; every launch writes its own class of one NaN-filled buffer"""
+    out = torch.full(tuple(res.shape), float("nan"))
+    for ph, pw, mask, taps in B.parity_classes():
+        keep = [t for t in range(9) if mask >> t & 1]
+        if fault == "dropped_tap" and (ph, pw) == (1, 1):
+            keep = keep[:-1]                                   # the class of four taps visits three
+        wm = torch.zeros_like(w)
+        for t in keep:
+            wm[:, t // 3, t % 3] = w[:, t // 3, t % 3]
+        v = _dgrad32(dy, wm, 2, 1, hw) + res
+        if fault == "residual_twice":
+            v = v + res
+        before = out.clone()
+        out[:, ph::2, pw::2] = (_rne(v) if dtype == 1 else v)[:, ph::2, pw::2]
+        if fault == "foreign_class" and (ph, pw) == (0, 1):
+            out[:, 0, 0] = out[:, 0, 1]                        # a launch that also writes a pixel of class (0, 0)
+        B.check_parity_launch(before, out, ph, pw, "emulated parity launch")
+    return out
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_dgrad_parity_bound(dtype):
+    dy, w, res, hw = _dgrad_operands(dtype, 3, 1)
+    K = dy.shape[-1]
+    assert [(c[2], c[3]) for c in B.parity_classes()] == [(0b000010000, 1), (0b000101000, 2), (0b010000010, 2), (0b101000101, 4)]
+    want, mag = B.conv_dgrad(dy, w, 2, 1, hw, residual=res)
+    bnd = B.parity_bound(want, mag, K, dtype, dtype == 0)
+    # each class's bound is the plain one at its own length, below the 9 K bound of the whole filter
+    assert bool((bnd < B.bound(want, mag, 9 * K, dtype, dtype == 0)).all())
+    assert torch.equal(bnd[:, 1::2, 1::2], B.bound(want, mag, 4 * K, dtype, dtype == 0)[:, 1::2, 1::2])
+    B.check(_parity_emul(dy, w, res, hw, dtype), want, bnd, "emulated dgrad by parity classes")
+    # ... and the transposed plain form (one launch, all nine taps) against the plain bound
+    one = _dgrad32(dy, w, 2, 1, hw) + res
+    B.check(_rne(one) if dtype == 1 else one, want, B.bound(want, mag, 9 * K, dtype, dtype == 0), "emulated transposed dgrad")
+    for fault in ("dropped_tap", "residual_twice"):
+        y = _parity_emul(dy, w, res, hw, dtype, fault)
+        with pytest.raises(AssertionError, match="worst err/bound"):
+            B.check(y, want, bnd, fault)
+    with pytest.raises(AssertionError, match="changed a pixel of another class"):
+        _parity_emul(dy, w, res, hw, dtype, "foreign_class")
+    hole = torch.full(tuple(res.shape), float("nan"))
+    with pytest.raises(AssertionError, match="unwritten"):
+        B.check_parity_launch(hole, hole, 0, 0, "a launch that writes nothing")
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_scatter_accumulate_bound(dtype):
+    """the 1x1 / 2 input gradient as the kernel forms it: a 1x1 conv of dY, added in fp32 onto the stored base at the even positions"""
+    dy, w, base, hw = _dgrad_operands(dtype, 1, 0, N=2, H=9, W=8, C=128, K=256)
+    K = dy.shape[-1]
+    want, mag = B.conv_dgrad(dy, w, 2, 0, hw, residual=base)
+    bnd = B.bound(want, mag, K, dtype, dtype == 0)
+    g = torch.einsum("nhwk,kc->nhwc", dy, w[:, 0, 0])
+
+    def emul(fault=None):
+        v = base.clone()
+        v[:, ::2, ::2] += g
+        if fault == "residual_twice":
+            v[:, ::2, ::2] += base[:, ::2, ::2]
+        if fault == "odd_position":
+            v[:, 1, 2] += g[:, 0, 1]                           # the gradient of (0, 2) lands on (1, 2) as well
+        if fault == "odd_rewritten":
+            v[:, 1, 1] = v[:, 1, 1] * (1.0 + 2.0 ** -20)       # an unreached position written back through another rounding
+        return _rne(v) if dtype == 1 else v
+    assert int(B.scatter_reach(base.shape).sum()) == 5 * 4
+    B.check_scatter(emul(), base, want, bnd, "emulated scatter-accumulate")
+    with pytest.raises(AssertionError, match="worst err/bound"):
+        B.check_scatter(emul("residual_twice"), base, want, bnd, "residual_twice")
+    with pytest.raises(AssertionError, match="does not reach"):
+        B.check_scatter(emul("odd_position"), base, want, bnd, "odd_position")
+    if dtype == 0:          # (in bf16 a change of 2^-20 rounds away: the stored value is the base's again)
+        with pytest.raises(AssertionError, match="does not reach"):
+            B.check_scatter(emul("odd_rewritten"), base, want, bnd, "odd_rewritten")
+
+
 # ====================================================================================================================
 # The non-conv families (BatchNorm finalize / apply / backward, pooling, heads, losses): for each, an emulation of the kernel in fp32
 # torch -- the kernel's operations, in another summation order -- passes its bound, and every injected fault fails it.

@@ -1,6 +1,7 @@
 """CPU-only: the route table (tests/kernel_routes.py) against the library's routing -- each row's descriptor maps to exactly its
 kernel name -- and against the step's profiles: every conv / stride-2 / stride-2 dgrad / wgrad instance that a profiled step
-launched has a row.  (No device here: device_cus() falls back to 256, the MI355X's count, which the routing of the persistent
+launched has a row; and against everything the router can answer: every instance named over the grid of tools/route_sweep.py has a
+row, and the family whose name elides its tile arguments a row per form.  (No device here: device_cus() falls back to 256, the MI355X's count, which the routing of the persistent
 kernels depends on.)"""
 import csv
 import os
@@ -34,7 +35,7 @@ def flags_of(spec):
     return f
 
 
-def conv_desc(op, shape, spec):
+def conv_desc(op, shape, spec, par=None):
     from ssl_cr_histo_amd import _lib as L
     N, H, W, C, K, R, stride, pad = shape
     f = flags_of(spec)
@@ -45,6 +46,16 @@ def conv_desc(op, shape, spec):
                        0, 0, 0)
         d.par4 = 1
         return d
+    if op == "dgrad_t":    # the transposed plain form: pixel space = the conv's input, with a residual
+        return L.ConvDesc(FAKE, FAKE, FAKE, None, None, None, FAKE, None, N, PH, PW, K, C, R, R, stride, pad, H, W, H, W, 1, 1, 0, 0, 0, 0,
+                          0, 0, 0)
+    if op == "dgrad_parity":       # one input-pixel parity class: par = (ph, pw, tap_mask, taps) of _f64.parity_classes()
+        ph, pw, tap_mask, _ = par
+        return L.ConvDesc(FAKE, FAKE, FAKE, None, None, None, FAKE, None, N, PH, PW, K, C, R, R, stride, pad, (H - ph + 1) // 2,
+                          (W - pw + 1) // 2, H, W, 1, 1, 0, 0, 0, 2, ph, pw, tap_mask)
+    if op == "scatter":    # the 1x1 / 2 input gradient: a plain 1x1 conv of dY, scattered to the even positions and accumulated
+        return L.ConvDesc(FAKE, FAKE, FAKE, None, None, None, None, None, N, PH, PW, K, C, 1, 1, 1, 0, PH, PW, H, W, 2, 0, 0, 0, 1, 0,
+                          0, 0, 0)
     d = L.ConvDesc(FAKE, FAKE, FAKE, p("in_scale"), p("in_scale"), p("bias"), p("residual"), p("stats"), N, H, W, C, K, R, R, stride,
                    pad, PH, PW, PH, PW, 1, 0, int(bool(f.get("in_scale"))), int(bool(f.get("relu"))), 0, 0, 0, 0, 0)
     d.out_scale = p("out_scale")
@@ -79,6 +90,11 @@ def test_route_maps_to_exactly_its_kernel(lib, row):
         single = lib.sslcr_conv2d_kernel_name(dt, d3).decode()
         # conv_s2_name(a, pair): the pair launches the same EVAL instance with PAIR = true
         assert single.startswith("sslcr::conv_s2_kernel<false, ") and single.replace("<false, ", "<true, ") == name, single
+        return
+    if op == "dgrad_parity":       # four launches, one per class: every one is the row's instance
+        import _f64 as B
+        for par in B.parity_classes():
+            assert lib.sslcr_conv2d_kernel_name(dt, conv_desc(op, shape, spec, par)).decode() == name, par
         return
     d = conv_desc(op, shape, spec)
     assert lib.sslcr_conv2d_kernel_name(dt, d).decode() == name
@@ -120,6 +136,85 @@ def test_every_truncated_profile_name_has_a_row():
             found += 1
             assert any(t.startswith(prefix) for t in table), f"no route row starts with {prefix!r}"
     assert found >= 15
+
+
+@pytest.fixture(scope="module")
+def swept(lib):
+    """tools/route_sweep.py's whole grid (nothing is launched) -> {"conv" | "wgrad": {name: (size, tag, dtype) of the smallest descriptor
+    that the router answers with this name}}"""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import route_sweep
+    finally:
+        sys.path.remove(os.path.join(ROOT, "tools"))
+    found = {"conv": {}, "wgrad": {}}
+    for kind, tag, d, _, size in route_sweep.walk():
+        fn, names = (lib.sslcr_conv2d_wgrad_kernel_name, found["wgrad"]) if kind == "wgrad" else (lib.sslcr_conv2d_kernel_name, found["conv"])
+        for dt in (0, 1):
+            name = fn(dt, d).decode()
+            if name not in names or size < names[name][0]:
+                names[name] = (size, tag, dt)
+    return found
+
+
+def _unreachable_by_name(name):
+    # the PAIR = true instances: sslcr_conv2d_s2_pair launches them; the name query answers for the single conv (PAIR = false).
+    # BEYOND_THE_GRID: named only by flag sets the grid does not hold (test_route_maps_to_exactly_its_kernel pins their rows)
+    from kernel_routes import BEYOND_THE_GRID
+    return name.startswith("sslcr::conv_s2_kernel<true, ") or name in BEYOND_THE_GRID
+
+
+def missing_rows(swept, routes, unlaunchable):
+    """-> the failure lines of the closure: every swept name without a row (with the smallest descriptor that reaches it), and every
+    row name that the grid should reach and does not"""
+    conv_rows = {r[4] for r in routes if r[0] != "wgrad"} | {r[5] for r in routes if r[5]}
+    wgrad_rows = {r[4] for r in routes if r[0] == "wgrad"}
+    lines = []
+    for kind, rows in (("conv", conv_rows), ("wgrad", wgrad_rows)):
+        for name, (_, tag, dt) in sorted(swept[kind].items()):
+            if name not in rows and name not in unlaunchable:
+                lines.append(f"no route row for {name}: smallest descriptor {tag} dt={dt}")
+        # (the tail column holds second launches: some of them no descriptor names)
+        for name in sorted({r[4] for r in routes if (r[0] == "wgrad") == (kind == "wgrad")} - set(swept[kind])):
+            if not _unreachable_by_name(name):
+                lines.append(f"the route row's {kind} name {name} is answered for no descriptor of the grid")
+    return lines
+
+
+def test_every_routable_instance_has_a_row(swept):
+    """every conv and wgrad instance that the router can answer over the sweep's grid has a row (or stands in UNLAUNCHABLE with the
+    condition that refuses it), and every row names an instance that the router answers: the two sets are equal, whatever their size"""
+    from kernel_routes import UNLAUNCHABLE
+    lines = missing_rows(swept, ROUTES, UNLAUNCHABLE)
+    assert not lines, "\n".join(lines)
+    assert {r[4] for r in ROUTES} <= _table_names()
+    from kernel_routes import BEYOND_THE_GRID
+    assert not set(BEYOND_THE_GRID) & (set(swept["conv"]) | set(swept["wgrad"])), "BEYOND_THE_GRID names an instance the grid reaches"
+    assert set(BEYOND_THE_GRID) <= {r[4] for r in ROUTES}
+    stale = sorted(set(UNLAUNCHABLE) - set(swept["conv"]) - set(swept["wgrad"]))
+    assert not stale, f"UNLAUNCHABLE names an instance the router no longer answers: {stale}"
+
+
+def test_a_deleted_row_fails_the_closure_with_its_instance(swept):
+    """the closure notices a missing row: without the rows of one instance it names that instance and a descriptor for it"""
+    for victim in ("sslcr::conv3x3_halo256_kernel<unsigned short, 8, 64, 1, true>", "sslcr::wgrad_kernel<unsigned short, 9, 1>",
+                   "sslcr::conv_igemm_kernel<float, 128, 128>"):
+        lines = missing_rows(swept, [r for r in ROUTES if victim not in (r[4], r[5])], {})
+        assert len(lines) == 1 and lines[0].startswith(f"no route row for {victim}: smallest descriptor "), lines
+
+
+def halo_form(shape):
+    """the (TW, BKO) instance of conv3x3_halo_kernel behind the elided name: conv_halo_tw's `a.W % 16 == 0 -> 16, else 8` and
+    halo_pick's `a.K % 128 == 0 -> 128, else 64`"""
+    W, K = shape[2], shape[4]
+    return (16 if W % 16 == 0 else 8, 128 if K % 128 == 0 else 64)
+
+
+def test_every_form_of_the_halo_family_has_a_row():
+    for dt, t in ((0, "float"), (1, "unsigned short")):
+        forms = {halo_form(r[2]) for r in ROUTES if r[0] == "fwd" and r[1] == dt and r[4] == f"sslcr::conv3x3_halo_kernel<{t}, ...>"}
+        assert forms == {(16, 128), (16, 64), (8, 128), (8, 64)}, (t, sorted(forms))
 
 
 @pytest.mark.parametrize("shape, seg", [((1, 16, 16, 64, 64, 3, 1, 1), 2), ((1, 16, 16, 128, 128, 3, 1, 1), 2), ((4, 8, 8, 512, 512, 3, 1, 1), 8)],

@@ -1317,9 +1317,13 @@ def _channel_scale(seed, n):
 @pytest.mark.parametrize("row", ROUTES, ids=[f"{r[0]}-{r[1]}-{'x'.join(map(str, r[2]))}-{r[3].replace(' ', '+')}" for r in ROUTES])
 def test_conv_route_f64(row):
     """every row of tests/kernel_routes.py through the kernels wrappers: the launch is EXACTLY the row's instance, and y, the
-    BatchNorm partial statistics and dW hold the float64 per-element bounds of tests/_f64.py (operands as the kernel sees them)"""
+    BatchNorm partial statistics and dW hold the float64 per-element bounds of tests/_f64.py (operands as the kernel sees them).
+    The input-gradient ops beside par4: dgrad_t (transposed, with a residual), dgrad_parity (four launches into one NaN-filled
+    buffer, each writing its class only, each class bounded with its own taps * K) and scatter (the 1x1 / 2 gradient accumulated
+    into a non-zero base: the positions it does not reach stay bit-equal)"""
     K = _k()
     op, dt, shape, spec, name, _ = row
+    print(f"\n[row] {op} {'bf16' if dt else 'fp32'} {'x'.join(map(str, shape))} [{spec}]")     # (with -s: heads the row's [f64] lines)
     f = _route_flags(spec)
     N, H, W, C, Ko, Rr, stride, pad = shape
     OH, OW = (H + 2 * pad - Rr) // stride + 1, (W + 2 * pad - Rr) // stride + 1
@@ -1354,7 +1358,37 @@ def test_conv_route_f64(row):
         want, mag = B.conv_dgrad(dy, w, stride, pad, (H, W))
         B.check(dx, want, B.bound(want, mag, Rr * Rr * Ko, dt, f32), "dgrad", name)
         return
-    bias = rnd(515, (Ko,)) if f.get("bias") else None
+    if op in ("dgrad_t", "dgrad_parity"):
+        dy = q(rnd(514, (N, OH, OW, Ko)), dt)
+        res = q(rnd(525, (N, H, W, C)), dt)
+        wd = to_dev(w.permute(3, 1, 2, 0).contiguous(), dt)
+        want, mag = B.conv_dgrad(dy, w, stride, pad, (H, W), residual=res)
+        if op == "dgrad_t":
+            dx = torch.full((N, H, W, C), float("nan"), dtype=K.tdtype(dt), device=DEV)
+            K.conv2d(to_dev(dy, dt), wd, stride, pad, transposed=True, out=dx, pixel_hw=(H, W), residual=to_dev(res, dt))
+            assert K.last_conv_kernel == name, K.last_conv_kernel
+            B.check(dx, want, B.bound(want, mag, Rr * Rr * Ko, dt, f32), f"dgrad transposed / {stride}", name)
+            return
+        # one launch per input-pixel parity class into one NaN-filled buffer; each writes its class and nothing else
+        dx = torch.full((N, H, W, C), float("nan"), dtype=K.tdtype(dt), device=DEV)
+        for ph, pw, tap_mask, _ in B.parity_classes():
+            before = dx.clone()
+            K.conv2d(to_dev(dy, dt), wd, stride, pad, transposed=True, out=dx, out_hw=(H, W), pixel_hw=((H - ph + 1) // 2, (W - pw + 1) // 2),
+                     residual=to_dev(res, dt), pix_mul=2, pix_off=(ph, pw), tap_mask=tap_mask)
+            assert K.last_conv_kernel == name, (ph, pw, K.last_conv_kernel)
+            B.check_parity_launch(before, dx, ph, pw, "dgrad by parity classes")
+        B.check(dx, want, B.parity_bound(want, mag, Ko, dt, f32), "dgrad by parity classes", name)
+        return
+    if op == "scatter":
+        dy = q(rnd(514, (N, OH, OW, Ko)), dt)
+        base = q(rnd(526, (N, H, W, C)), dt)
+        dx = to_dev(base, dt)
+        K.conv2d(to_dev(dy, dt), to_dev(w.permute(3, 1, 2, 0).contiguous(), dt), 1, 0, out=dx, out_hw=(H, W), osh=2, accumulate=True)
+        assert K.last_conv_kernel == name, K.last_conv_kernel
+        want, mag = B.conv_dgrad(dy, w, stride, pad, (H, W), residual=base)
+        B.check_scatter(dx, base, want, B.bound(want, mag, Ko, dt, f32), "1x1 / 2 scatter-accumulate", name)
+        return
+    bias =rnd(515, (Ko,)) if f.get("bias") else None
     res = q(rnd(516, (N, OH, OW, Ko)), dt) if f.get("residual") else None
     osc = _channel_scale(517, Ko) if f.get("out_scale") else None
     relu = bool(f.get("relu"))

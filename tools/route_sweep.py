@@ -3,7 +3,8 @@
 descriptors in a fixed order and prints, per descriptor and dtype, what sslcr_conv2d_kernel_name / _partial_rows / _segments_ok /
 _s2_pair_ok and sslcr_conv2d_wgrad_kernel_name answer.  Nothing is launched.  Two builds route alike where their dumps are identical
 (one process per library: the routing caches its switches in statics); the counts of distinct names go to stderr.  Rows are never
-asked for with seg_images > N (a library from before the route plan divides by zero there)."""
+asked for with seg_images > N (a library from before the route plan divides by zero there).  walk() is the grid itself:
+tests/test_kernel_routes_cpu.py walks it too, and asks that every name it answers has a row in tests/kernel_routes.py."""
 import argparse
 import ctypes as C
 import itertools
@@ -51,6 +52,29 @@ def dgrad_descs(N, H, W, C, K):
         yield form, d
 
 
+def walk():
+    """the grid in its fixed order -> (kind, tag, descriptor, pair, size): kind "conv" (the public conv descriptors), "dgrad" (the
+    stride-2 input-gradient forms) or "wgrad"; tag: the descriptor as the dump prints it; pair: the 1x1 / 2 descriptor that
+    sslcr_conv2d_s2_pair_ok is asked about beside a 3x3 / 2 one, else None; size: a measure to order descriptors by (multiply-adds,
+    then the number of flags).  Every descriptor is asked for both dtypes, 0 then 1."""
+    for N, (H, W), (Cc, K), (R, s, pad) in itertools.product(NS, MAPS, CK, RSP):
+        shape = f"{N}x{H}x{W} {Cc}->{K} k{R}s{s}p{pad}"
+        OH, OW = (H + 2 * pad - R) // s + 1, (W + 2 * pad - R) // s + 1
+        macs = N * OH * OW * R * R * Cc * K
+        for flags, seg in itertools.product(FLAGS, SEGS):
+            if seg > N:
+                continue
+            d = conv_desc(N, H, W, Cc, K, R, s, pad, flags, seg)
+            pair = conv_desc(N, H, W, Cc, K, 1, 2, 0, flags.replace("relu", ""), seg) if (R, s) == (3, 2) else None
+            yield "conv", f"conv {shape} [{flags}] seg={seg}", d, pair, (macs, len(flags.split()) + (seg > 0))
+        if (R, s) == (3, 2):
+            for form, d in dgrad_descs(N, H, W, Cc, K):
+                yield "dgrad", f"dgrad {shape} {form}", d, None, (macs, 0)
+        for xf, seg in itertools.product((None, FAKE), SEGS):
+            w = L.WgradDesc(FAKE, FAKE, FAKE, xf, xf, int(bool(xf)), N, H, W, Cc, K, R, R, s, pad, OH, OW, seg, Cc if seg else 0)
+            yield "wgrad", f"wgrad {shape} xf={int(bool(xf))} seg={seg}", w, None, (macs, int(bool(xf)) + (seg > 0))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--lib", required=True)
@@ -63,33 +87,17 @@ def main():
                "sslcr_conv2d_wgrad_kernel_name"):
         getattr(lib, fn).restype, getattr(lib, fn).argtypes = L.SIGNATURES[fn]
     out, cnames, wnames = [], set(), set()
-
-    def conv_line(tag, dt, d, pair=None):
-        name = lib.sslcr_conv2d_kernel_name(dt, d).decode()
-        cnames.add(name)
-        pok = lib.sslcr_conv2d_s2_pair_ok(dt, d, pair) if pair is not None else "-"
-        out.append(f"{tag} dt={dt} | {name} rows={lib.sslcr_conv2d_partial_rows(d)} seg={lib.sslcr_conv2d_segments_ok(dt, d)} pair={pok}")
-
-    for N, (H, W), (Cc, K), (R, s, pad) in itertools.product(NS, MAPS, CK, RSP):
-        shape = f"{N}x{H}x{W} {Cc}->{K} k{R}s{s}p{pad}"
-        for flags, seg in itertools.product(FLAGS, SEGS):
-            if seg > N:
-                continue
-            d = conv_desc(N, H, W, Cc, K, R, s, pad, flags, seg)
-            pair = conv_desc(N, H, W, Cc, K, 1, 2, 0, flags.replace("relu", ""), seg) if (R, s) == (3, 2) else None
-            for dt in (0, 1):
-                conv_line(f"conv {shape} [{flags}] seg={seg}", dt, d, pair)
-        if (R, s) == (3, 2):
-            for form, d in dgrad_descs(N, H, W, Cc, K):
-                for dt in (0, 1):
-                    conv_line(f"dgrad {shape} {form}", dt, d)
-        OH, OW = (H + 2 * pad - R) // s + 1, (W + 2 * pad - R) // s + 1
-        for xf, seg in itertools.product((None, FAKE), SEGS):
-            w = L.WgradDesc(FAKE, FAKE, FAKE, xf, xf, int(bool(xf)), N, H, W, Cc, K, R, R, s, pad, OH, OW, seg, Cc if seg else 0)
-            for dt in (0, 1):
-                name = lib.sslcr_conv2d_wgrad_kernel_name(dt, w).decode()
+    for kind, tag, d, pair, _ in walk():
+        for dt in (0, 1):
+            if kind == "wgrad":
+                name = lib.sslcr_conv2d_wgrad_kernel_name(dt, d).decode()
                 wnames.add(name)
-                out.append(f"wgrad {shape} xf={int(bool(xf))} seg={seg} dt={dt} | {name}")
+                out.append(f"{tag} dt={dt} | {name}")
+                continue
+            name = lib.sslcr_conv2d_kernel_name(dt, d).decode()
+            cnames.add(name)
+            pok = lib.sslcr_conv2d_s2_pair_ok(dt, d, pair) if pair is not None else "-"
+            out.append(f"{tag} dt={dt} | {name} rows={lib.sslcr_conv2d_partial_rows(d)} seg={lib.sslcr_conv2d_segments_ok(dt, d)} pair={pok}")
     sys.stdout.write("\n".join(out) + "\n")
     print(f"{len(out)} lines, {len(cnames)} conv names, {len(wnames)} wgrad names", file=sys.stderr)
 
