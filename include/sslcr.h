@@ -1015,8 +1015,10 @@ int sslcr_net_set_loss_opts(sslcr_net* net, const sslcr_loss_opts* opts);
 int sslcr_net_grad(sslcr_net* net, int param_index, float* out, void* stream);      /* -> PyTorch layout */
 /* diagnostics for the layer-wise backward parity test (tests/test_backward_replay_gpu.py): autograd of one BasicBlock of
  * torchvision resnet18 (reached from models/net.py:32,77) checked kernel by kernel at the size the step really runs.  With the tap
- * on, sslcr_net_backward keeps a copy of every block's transient gradient tensors of pass 0; sslcr_net_debug_tensor copies one
- * tensor of block 0..7 (layer1.0 .. layer4.1) into `out` (device memory, engine storage dtype, NHWC) and reports its dims:
+ * on, sslcr_net_backward keeps a copy of every block's transient gradient tensors of every pass (the three TripletNet branches);
+ * sslcr_net_debug_tensor copies one tensor of block 0..7 (layer1.0 .. layer4.1) into `out` (device memory, engine storage dtype,
+ * NHWC) and reports its dims.  The pass rides in the high bits of `kind`: kind | pass << 8 (pass 0: the kinds as they always were;
+ * a pass the last train-mode forward did not have is an error).  The weight packs (15..20) are the same for every pass.
  *   kind 0 G     = d(block output) * (output > 0)           1 dRaw2 = gradient at conv2's raw output (after bn2 backward)
  *        2 dAct1 = conv2's dgrad (flags bit 0: bn1's ReLU mask already applied)    3 dRaw1 = gradient at conv1's raw output
  *        4 dRawD = gradient at the projection conv's raw output                    5 dXin  = gradient at the block input
@@ -1024,6 +1026,16 @@ int sslcr_net_grad(sslcr_net* net, int param_index, float* out, void* stream);  
  *       11..14 bn1's saved scale, shift, mean, invstd (fp32 [C]; dims = {C,1,1,1})
  *       15..20 (library version >= 8) the train-mode shadow weights as the conv kernels read them, engine storage dtype: conv1's
  *              forward pack [K][R][S][C] (15) and dgrad pack [C][R][S][K] (16), conv2's (17, 18), the projection's (19, 20)
+ *       21..24 bn2's saved scale, shift, mean, invstd; 25..28 the projection BatchNorm's (as 11..14)
+ *       29 dOut = the gradient at the block output as bn2's backward reduce pass reads it (layer4.1's comes from the average pool)
+ *       (21..29 and the pass bits came without a version bump: a library that lacks them refuses the kind.)
+ * flags: which form each stage of this block took in the last step --
+ *   bit 0 dAct1 carries bn1's ReLU mask            1 the BatchNorm backward passes ran the branches as segments of one launch
+ *       2 conv2's masked dgrad ran them as segments     3 conv2's weight gradient ran them as one batched launch
+ *       4 bn2 and the projection BatchNorm's backward ran as the paired kernels     5 the stride-2 dgrad ran its four parity classes
+ *       in one launch (bits 0..5: the last backward)   6 the forward ran the branches as segments     7 conv1 and the projection
+ *       ran as the paired stride-2 launch (6, 7: the last train-mode forward).
+ *   The profiler cannot tell these apart (profiling switches the segment forms off).  The tap changes no routing decision and no output bit.
  * out == NULL: only dims4 / flags are filled. */
 int sslcr_net_debug_tap(sslcr_net* net, int on);
 /* 1 when the last train-mode forward of a TripletNet ran its three branches as segments of one launch per layer

@@ -246,11 +246,16 @@ struct sslcr_net {
   int last_N = 0, last_npass = 0;
   bool last_segments = false;      // the last train forward ran the branches as segments
   bool packed_train = false, packed_eval = false;
-  // sslcr_net_debug_tap: backward keeps copies of each block's transient gradient tensors (pass 0) for the layer-wise replay test
+  // sslcr_net_debug_tap: backward keeps copies of each block's transient gradient tensors, per pass, for the layer-wise replay test
   bool tap = false;
-  DevBuf tapbuf[8][6];
-  int tapdims[8][6][4] = {};
-  int tap_flags[8] = {};            // bit 0: dAct1 was written with bn1's ReLU mask already applied (mask_x front end of the dgrad)
+  static constexpr int kTapSlots = 7;
+  DevBuf tapbuf[3][8][kTapSlots];
+  int tapdims[3][8][kTapSlots][4] = {};
+  // which form each stage of the block took (include/sslcr.h: sslcr_net_debug_tensor's flags).  Backward bits: 0 dAct1 was written
+  // with bn1's ReLU mask already applied, 1 seg_bn, 2 seg_dg, 3 c2_batched, 4 paired BatchNorm backward, 5 par4 in one launch;
+  // fwd_flags: 6 the forward ran as segments, 7 BlockPlan::paired.  Written by every step, read by the tap only
+  int tap_flags[8] = {};
+  int fwd_flags[8] = {};
   std::vector<sslcr_tensor_desc> host_descs;
   std::vector<float*> st1, st2;
   std::vector<int> group_of;      // parameter -> optimizer group of the descriptor table in `descs`
@@ -259,8 +264,9 @@ struct sslcr_net {
   std::vector<DevBuf*> bufs() {
     std::vector<DevBuf*> v = {&shadow, &grads, &gnew, &heads, &descs, &chunks, &f8buf, &norm_ws};
     for (PassState& ps : pass) v.push_back(&ps.mem);
-    for (auto& row : tapbuf)
-      for (DevBuf& b : row) v.push_back(&b);
+    for (auto& ps : tapbuf)
+      for (auto& row : ps)
+        for (DevBuf& b : row) v.push_back(&b);
     return v;
   }
 };
@@ -839,6 +845,7 @@ int forward_blocks(sslcr_net* n, PassState& ps, int N, int H, int W, int replay,
     BlockL& B = n->blocks[i];
     BlockPlan bp = block_plan(n, ps, d, i, N, nseg);
     if (nseg > 1 && !bp.seg_ok) return fail("forward_blocks: block %d has no segment form here (segments_servable read the same plan)", i);
+    n->fwd_flags[i] = (nseg > 1 ? 1 << 6 : 0) | (bp.paired ? 1 << 7 : 0);
     // every conv with statistics is the same three steps over its region of ctx->partials: reserve, launch, finalize
     auto reserve = [&](size_t bytes, std::initializer_list<ConvStage*> stages) {
       TRYI(c->partials.ensure(bytes));
@@ -1300,14 +1307,18 @@ struct Backward {
   // pass p of a kind sits p * (tensor bytes of the current layer) behind pass 0: contiguous for the batched weight gradients
   char* buf(int kind, int p, size_t bytes) const { return S + (size_t)kind * npass * unit + (size_t)p * bytes; }
   char* dRaw0() const { return S + (size_t)kKinds * npass * unit; }
-  // debug tap (pass 0 only): slot 0 G, 1 dRaw2, 2 dAct1, 3 dRaw1, 4 dRawD, 5 dXin
-  int tap(int slot, const void* src, int h_, int w_, int c_) {
+  // debug tap: slot 0 G, 1 dRaw2, 2 dAct1, 3 dRaw1, 4 dRawD, 5 dXin, 6 dOut.  src is the tensor of pass p; np > 1: of passes p .. p + np - 1,
+  // one behind the other (a launch that took them as segments)
+  int tap(int slot, int p, int np, const void* src, int h_, int w_, int c_) {
     if (!n->tap) return 0;
     const size_t bytes = (size_t)N * h_ * w_ * c_ * es;
-    TRYI(n->tapbuf[i][slot].ensure(bytes));
-    TRY(hipMemcpyAsync(n->tapbuf[i][slot].p, src, bytes, hipMemcpyDeviceToDevice, st));
-    int* d4 = n->tapdims[i][slot];
-    d4[0] = N; d4[1] = h_; d4[2] = w_; d4[3] = c_;
+    for (int j = 0; j < np; ++j) {
+      DevBuf& b = n->tapbuf[p + j][i][slot];
+      TRYI(b.ensure(bytes));
+      TRY(hipMemcpyAsync(b.p, (const char*)src + (size_t)j * bytes, bytes, hipMemcpyDeviceToDevice, st));
+      int* d4 = n->tapdims[p + j][i][slot];
+      d4[0] = N; d4[1] = h_; d4[2] = w_; d4[3] = c_;
+    }
     return 0;
   }
 
@@ -1345,6 +1356,7 @@ struct Backward {
     // consecutive ring slots.  Not with synced BatchNorm (one all-reduce per pass) and not under the profiler.
     seg_bn = npass > 1 && segments_on() && !c->prof.on && !(sharded(c) && c->bn_sync) && c->bn_ring.p &&
              c->bn_ring_i + 2 * npass <= sslcr_ctx::kBnRing;
+    n->tap_flags[i] = (seg_bn ? 1 << 1 : 0) | (seg_dg ? 1 << 2 : 0) | (c2_batched ? 1 << 3 : 0);
   }
 
   // ---- bn2 stage: leaves G = dOut * (y > 0), dRaw2 and (projection shortcut) dRawD; taps 0, 1 and 4.
@@ -1362,12 +1374,12 @@ struct Backward {
     qd.dy = G; qd.x = ps.blk[i].rawd; qd.dx = dRawD;
     q2.pixels = qd.pixels = opix * nseg; q2.count = qd.count = (double)opix;
     if (nseg > 1) { q2.nseg = qd.nseg = nseg; q2.seg_stride = qd.seg_stride = bn_stride; }
+    TRYI(tap(6, p, nseg, q2.dy, oh, ow, B->c2.cout));
     if (!B->has_ds) TRYI(bn_backward(n, B->b2, ps.bn[B->b2.bidx], q2, st));
     else TRYI(nseg > 1 ? bn2_and_shortcut_segments(q2, qd) : bn2_and_shortcut(ps, q2, qd));
-    if (p != 0) return 0;
-    TRYI(tap(0, G, oh, ow, B->c2.cout));
-    TRYI(tap(1, dRaw2, oh, ow, B->c2.cout));
-    return B->has_ds ? tap(4, dRawD, oh, ow, B->ds.cout) : 0;
+    TRYI(tap(0, p, nseg, G, oh, ow, B->c2.cout));
+    TRYI(tap(1, p, nseg, dRaw2, oh, ow, B->c2.cout));
+    return B->has_ds ? tap(4, p, nseg, dRawD, oh, ow, B->ds.cout) : 0;
   }
   int bn2_and_shortcut_segments(const BnBwdReq& q2, const BnBwdReq& qd) {
     BnBwdArgs a2, ad;
@@ -1394,6 +1406,7 @@ struct Backward {
     //  SSLCR_BN_PAIR_G=0 selects that form; the debug tap always keeps g)
     static const bool g_free = [] { const char* e = getenv("SSLCR_BN_PAIR_G"); return e && atoi(e) == 0; }();
     const int keep_g = (n->tap || !a2.yact_bits || !g_free) ? 1 : 0;
+    if (pair) n->tap_flags[i] |= 1 << 4;
     if (pair) {
       TRY(launch_bn_bwd_reduce_pair(dt, a2, ad, keep_g, st));
     } else {
@@ -1423,7 +1436,7 @@ struct Backward {
     q.pixels = opix * nseg; q.count = (double)opix; q.sum_rows = rows; q.n_sum_rows = nrows;
     if (nseg > 1) { q.nseg = nseg; q.seg_stride = bn_stride; }
     TRYI(bn_backward(n, B->b1, P[p].bn[B->b1.bidx], q, st));
-    return p == 0 ? tap(3, q.dx, oh, ow, B->c1.cout) : 0;
+    return tap(3, p, nseg, q.dx, oh, ow, B->c1.cout);
   }
   // pass p: where the 16x16-tile kernel serves this dgrad it takes the mask front end
   int conv2_dgrad_bn1(int p) {
@@ -1438,10 +1451,8 @@ struct Backward {
       a.stats = rows;
     }
     TRY(prof_conv(c, dt, a, st));
-    if (p == 0) {
-      TRYI(tap(2, a.y, oh, ow, B->c2.cin));
-      n->tap_flags[i] = rows ? 1 : 0;
-    }
+    TRYI(tap(2, p, 1, a.y, oh, ow, B->c2.cin));
+    if (rows) n->tap_flags[i] |= 1;
     return bn1(p, 1, rows, nrows);
   }
   // all passes as segments of one launch (their scratch tensors are contiguous): segment s leaves its own rows of bn1's backward
@@ -1452,8 +1463,8 @@ struct Backward {
     TRYI(ensure_partials(c, m, &rows, &nrows));
     m.stats = rows;
     TRY(prof_conv(c, dt, m, st));
-    TRYI(tap(2, m.y, oh, ow, B->c2.cin));
-    n->tap_flags[i] = 1;
+    TRYI(tap(2, 0, npass, m.y, oh, ow, B->c2.cin));
+    n->tap_flags[i] |= 1;
     if (seg_bn) return bn1(0, npass, rows, nrows);
     const int per = nrows / npass;
     for (int p = 0; p < npass; ++p) TRYI(bn1(p, 1, rows + (size_t)p * per * 2 * B->b1.C, per));
@@ -1489,6 +1500,7 @@ struct Backward {
       ConvArgs q4 = a;
       q4.pix_mul = 2; q4.PH = xh / 2; q4.PW = xw / 2; q4.par4 = 1;
       const bool one = xh % 2 == 0 && xw % 2 == 0 && conv_plan(dt, q4).par4_one_launch;
+      if (one) n->tap_flags[i] |= 1 << 5;
       if (one) TRY(prof_conv(c, dt, q4, st));
       for (int par = 0; par < (one ? 0 : 4); ++par) {
         ConvArgs q = a;
@@ -1506,7 +1518,7 @@ struct Backward {
       s.accumulate = 1;
       TRY(prof_conv(c, dt, s, st));
     }
-    return tap(5, dXin, xh, xw, B->c1.cin);
+    return tap(5, 0, npass, dXin, xh, xw, B->c1.cin);
   }
 
   // the current block from dOut down to dRaw1 / dRawD, and its weight gradients.  Where stages go pass by pass, pass p's bn2, conv2
@@ -1949,47 +1961,55 @@ int sslcr_net_debug_tap(sslcr_net* n, int on) {
   if (!n) return fail("sslcr_net_debug_tap: null net");
   n->tap = on != 0;
   if (!on)
-    for (auto& row : n->tapbuf)
-      for (DevBuf& b : row) b.release();
+    for (auto& ps : n->tapbuf)
+      for (auto& row : ps)
+        for (DevBuf& b : row) b.release();
   return 0;
 }
 
 int sslcr_net_debug_tensor(sslcr_net* n, int block, int kind, void* out, size_t out_bytes, int* dims4, int* flags, void* stream) {
-  if (!n || block < 0 || block > 7 || kind < 0 || kind > 20 || !dims4) return fail("sslcr_net_debug_tensor: invalid argument");
+  const int pass = kind >> 8;         // the pass rides in the high bits: kind | pass << 8
+  kind &= 0xff;
+  if (!n || block < 0 || block > 7 || pass < 0 || pass > 2 || kind > 29 || !dims4) return fail("sslcr_net_debug_tensor: invalid argument");
   sslcr_ctx* c = n->ctx;
   hipStream_t st = (hipStream_t)stream;
   const BlockL& B = n->blocks[block];
-  const PassState& ps = n->pass[0];
-  if (n->last_npass == 0 || !ps.mem.p) return fail("sslcr_net_debug_tensor: no train-mode forward");
+  if (n->last_npass == 0 || !n->pass[0].mem.p) return fail("sslcr_net_debug_tensor: no train-mode forward");
+  if (pass >= n->last_npass) return fail("sslcr_net_debug_tensor: pass %d of a forward with %d", pass, n->last_npass);
+  const PassState& ps = n->pass[pass];
   const Dims d = make_dims(ps.H, ps.W);
   const int oh = d.lh[block], ow = d.lw[block];
   const int xh = block == 0 ? d.ph : d.lh[block - 1], xw = block == 0 ? d.pw : d.lw[block - 1];
   const void* src = nullptr;
   size_t esz = c->esz();
   int dm[4] = {ps.N, oh, ow, B.c2.cout};
-  if (kind <= 5) {
-    if (!n->tap || !n->tapbuf[block][kind].p) return fail("sslcr_net_debug_tensor: nothing tapped for block %d kind %d", block, kind);
-    src = n->tapbuf[block][kind].p;
-    for (int j = 0; j < 4; ++j) dm[j] = n->tapdims[block][kind][j];
+  if (kind <= 5 || kind == 29) {
+    const int slot = kind == 29 ? 6 : kind;
+    if (!n->tap || !n->tapbuf[pass][block][slot].p)
+      return fail("sslcr_net_debug_tensor: nothing tapped for block %d kind %d pass %d", block, kind, pass);
+    src = n->tapbuf[pass][block][slot].p;
+    for (int j = 0; j < 4; ++j) dm[j] = n->tapdims[pass][block][slot][j];
   } else if (kind == 6) { src = ps.blk[block].raw1; dm[3] = B.c1.cout; }
   else if (kind == 7) { src = ps.blk[block].raw2; }
   else if (kind == 8) { src = ps.blk[block].rawd; if (!B.has_ds) return fail("sslcr_net_debug_tensor: block %d has no projection", block); }
   else if (kind == 9) { src = ps.blk[block].y; }
   else if (kind == 10) { src = block == 0 ? ps.pooled : ps.blk[block - 1].y; dm[1] = xh; dm[2] = xw; dm[3] = B.c1.cin; }
-  else if (kind >= 15) {        // 15..20: the train-mode shadow weights of conv1, conv2, the projection: forward pack, dgrad pack
+  else if (kind >= 15 && kind <= 20) {   // the train-mode shadow weights of conv1, conv2, the projection: forward pack, dgrad pack
     const ConvL& L = kind < 17 ? B.c1 : kind < 19 ? B.c2 : B.ds;
     if (kind >= 19 && !B.has_ds) return fail("sslcr_net_debug_tensor: block %d has no projection", block);
     const bool fwd = (kind & 1) != 0;
     src = fwd ? L.w_fwd : L.w_dg;
     if (!src) return fail("sslcr_net_debug_tensor: block %d kind %d: this conv has no such pack", block, kind);
     dm[0] = fwd ? L.cout : L.cin; dm[1] = dm[2] = L.k; dm[3] = fwd ? L.cin : L.cout;
-  } else {                      // 11..14: bn1's saved scale, shift, mean, invstd (fp32 [C])
-    const BnSaved& sv = ps.bn[B.b1.bidx];
+  } else {                      // 11..14, 21..24, 25..28: the saved scale, shift, mean, invstd of bn1, bn2, the projection's BatchNorm (fp32 [C])
+    const BnL& bn = kind <= 14 ? B.b1 : kind <= 24 ? B.b2 : B.bd;
+    if (kind >= 25 && !B.has_ds) return fail("sslcr_net_debug_tensor: block %d has no projection", block);
+    const BnSaved& sv = ps.bn[bn.bidx];
     const float* v[4] = {sv.scale, sv.shift, sv.mean, sv.invstd};
-    src = v[kind - 11]; esz = 4; dm[0] = B.b1.C; dm[1] = dm[2] = dm[3] = 1;
+    src = v[kind <= 14 ? kind - 11 : kind <= 24 ? kind - 21 : kind - 25]; esz = 4; dm[0] = bn.C; dm[1] = dm[2] = dm[3] = 1;
   }
   for (int j = 0; j < 4; ++j) dims4[j] = dm[j];
-  if (flags) *flags = n->tap_flags[block];
+  if (flags) *flags = n->tap_flags[block] | n->fwd_flags[block];
   if (!out) return 0;
   const size_t bytes = (size_t)dm[0] * dm[1] * dm[2] * dm[3] * esz;
   if (out_bytes < bytes) return fail("sslcr_net_debug_tensor: buffer of %zu bytes, tensor has %zu", out_bytes, bytes);

@@ -278,14 +278,17 @@ class BoundNet:
         """keep copies of every block's transient gradient tensors in backward (layer-wise parity test; see include/sslcr.h)."""
         L.check(L.lib().sslcr_net_debug_tap(self.handle, int(bool(on))))
 
-    def debug_tensor(self, block, kind):
-        """-> (tensor in the engine's storage dtype, flags); kinds as in include/sslcr.h:sslcr_net_debug_tensor."""
+    def debug_tensor(self, block, kind, pass_=0):
+        """-> (tensor in the engine's storage dtype, flags) of pass `pass_` (a TripletNet branch); kinds and the bits of flags as in
+        include/sslcr.h:sslcr_net_debug_tensor."""
         dims, flags = (C.c_int * 4)(), C.c_int()
-        L.check(L.lib().sslcr_net_debug_tensor(self.handle, block, kind, None, 0, dims, C.byref(flags), L.stream_ptr()))
+        code = int(kind) | int(pass_) << 8
+        L.check(L.lib().sslcr_net_debug_tensor(self.handle, block, code, None, 0, dims, C.byref(flags), L.stream_ptr()))
         shape = [d for d in dims]
-        dt = torch.float32 if 11 <= kind <= 14 or self.engine.dtype == 0 else torch.bfloat16
-        out = torch.empty(shape[:1] if 11 <= kind <= 14 else shape, dtype=dt, device=self.engine.device)
-        L.check(L.lib().sslcr_net_debug_tensor(self.handle, block, kind, L.ptr(out), out.numel() * out.element_size(), dims,
+        vec = 11 <= kind <= 14 or 21 <= kind <= 28
+        dt = torch.float32 if vec or self.engine.dtype == 0 else torch.bfloat16
+        out = torch.empty(shape[:1] if vec else shape, dtype=dt, device=self.engine.device)
+        L.check(L.lib().sslcr_net_debug_tensor(self.handle, block, code, L.ptr(out), out.numel() * out.element_size(), dims,
                                                C.byref(flags), L.stream_ptr()))
         return out, flags.value
 

@@ -278,13 +278,18 @@ def _ld(t):
     return t.detach().cpu().double().numpy().astype(np.longdouble)
 
 
-def bn_finalize_ref(partials, count, gamma, beta, rm, rv, *, momentum=0.1, eps=1e-5, replay=1, nseg=1):
-    """partials fp32 [rows, 2, C] -> dict name -> (want64, bound), each [nseg, C] (running statistics [C], after all segments)"""
-    rows, _, C = partials.shape
-    per = rows // nseg
+def bn_finalize_ref(partials, count, gamma, beta, rm, rv, *, momentum=0.1, eps=1e-5, replay=1, nseg=1, rows=None, sum_err=None):
+    """partials fp32 [rows, 2, C] -> dict name -> (want64, bound), each [nseg, C] (running statistics [C], after all segments).
+    The chained form (a conv's statistics rows checked through the finalize, without the rows themselves): partials = the float64 sums of
+    the float64 accumulator, one row per segment; rows = the rows per segment the kernel summed (for D); sum_err = (bound of sum, bound
+    of sumsq) [nseg, C] from stats_bound.  They enter as  |d mean| += bs / n,  |d var| += bss / n + 2 |mean| bs / n + (bs / n)^2  (var =
+    ss / n - mean^2), and the variance's error then goes through  invstd = (var + eps)^-1/2  with the denominator taken at its lower
+    end, var + eps - |d var|, so that the bound holds beyond first order."""
+    C = partials.shape[-1]
+    per = partials.shape[0] // nseg
     eps = float(np.float32(eps))
     mom = float(np.float32(momentum))
-    D = (per + 8) * 2.0 ** -53
+    D = ((rows if rows is not None else per) + 8) * 2.0 ** -53
     p = _ld(partials).reshape(nseg, per, 2, C)
     out = {k: [] for k in ("scale", "shift", "mean", "invstd")}
     g, b = gamma.double(), beta.double()
@@ -305,7 +310,13 @@ def bn_finalize_ref(partials, count, gamma, beta, rm, rv, *, momentum=0.1, eps=1
         sh = b - mean * sc
         d_mean = D * sa / count
         d_var = D * (msq + 3 * mean * mean)
-        rel_i = 0.5 * d_var / (var + eps) + 4 * 2.0 ** -53
+        if sum_err is not None:
+            bs, bss = sum_err[0][z].double() / count, sum_err[1][z].double() / count
+            d_mean = d_mean + bs
+            d_var = d_var + bss + 2 * mean.abs() * bs + bs * bs
+            rel_i = 0.5 * d_var / (var + eps - d_var).clamp_min(1e-300) + 4 * 2.0 ** -53
+        else:
+            rel_i = 0.5 * d_var / (var + eps) + 4 * 2.0 ** -53
         out["mean"].append((mean, U * mean.abs() + d_mean))
         out["invstd"].append((invstd, (U + rel_i) * invstd))
         out["scale"].append((sc, (U + rel_i) * sc.abs()))

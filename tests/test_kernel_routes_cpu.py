@@ -225,3 +225,27 @@ def test_segment_larger_than_the_batch_has_no_rows(lib, shape, seg):
     d = conv_desc("fwd", shape, f"stats seg={seg}")
     assert lib.sslcr_conv2d_partial_rows(d) == -1
     assert lib.sslcr_conv2d_segments_ok(1, d) == 0
+
+
+# ---------------------------------------------------------------- the forms of the engine step (tests/step_forms.py)
+@pytest.fixture(scope="module")
+def step_forms(lib):
+    import step_forms as SF
+    return SF, {k: SF.expected_forms(lib, k) for k in SF.ROWS}
+
+
+def test_step_replay_rows_take_the_forms_they_were_chosen_for(step_forms):
+    """the form word the engine must report per (row, block) of the float64 step replay (tests/test_backward_replay_gpu.py asserts the
+    tap's flags equal it): each row still takes the forms it stands for"""
+    SF, table = step_forms
+    for key, bit, on in SF.STATED:
+        got = [i for i, w in enumerate(table[key]) if w & bit]
+        assert got == list(on), f"row {key}: {SF.word_str(bit)} is on in blocks {got}, the row was chosen for {list(on)}"
+
+
+def test_every_form_bit_is_on_somewhere_and_off_elsewhere(step_forms):
+    """set closure: a form that no (row, block) takes, or that every one takes, is a form the replay cannot tell from its sibling"""
+    SF, table = step_forms
+    assert SF.closure_gaps(table) == []
+    # ... and the check itself notices: without row A nothing runs the forward as segments
+    assert SF.closure_gaps({k: v for k, v in table.items() if k != "A"}) == ["fwd_seg"]
