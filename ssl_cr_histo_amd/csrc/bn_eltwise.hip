@@ -2,22 +2,25 @@
 // All HBM-bound: 16-byte vector accesses, channel-contiguous, grid-stride.  Replaces nn.BatchNorm2d / ReLU /
 // residual add / MaxPool2d / AdaptiveAvgPool2d of torchvision resnet18 and their autograd (K13).
 #include <stdlib.h>
+#include <type_traits>
 
 #include "kernels.hpp"
+#include "bn_bwd.hpp"
 
 namespace sslcr {
 
 // ------------------------------------------------------------------ statistics: partial rows -> sums -> scale/shift
 // stage 1: grid (C/32, SPLITS, nseg); block 256 = 32 channels x 8 row lanes.  Segment z owns rows [z * rows, (z + 1) * rows) of
-// `part` and the z-th [splits][2][C] slab of `out` (rows = rows per segment)
-__global__ __launch_bounds__(256) void bn_reduce_rows_kernel(const float* __restrict__ part, int rows, int C, double* __restrict__ out, int splits) {
+// `part` and the z-th [splits][2][C] slab of `out` (rows = rows per segment).  The workgroup's 64 sums end in wave 0: thread t < 64
+// calls wave0(which = t >> 5, channel, sum) -- how the sum of stage row blockIdx.y is stored (and what else wave 0 does) is the kernel's
+template <typename Wave0>
+__device__ __forceinline__ void bn_reduce_rows_block(const float* __restrict__ part, int rows, int C, int splits, Wave0 wave0) {
   __shared__ double sm[2][8][32];
   const int c = blockIdx.x * 32 + (threadIdx.x & 31);
   const int rl = threadIdx.x >> 5;
   const int per = (rows + splits - 1) / splits;
   const int r0 = blockIdx.y * per, r1 = min(rows, r0 + per);
   part += (size_t)blockIdx.z * rows * 2 * C;
-  out += (size_t)blockIdx.z * splits * 2 * C;
   double s = 0.0, ss = 0.0;
   if (c < C) {
     int r = r0 + rl;
@@ -42,9 +45,14 @@ __global__ __launch_bounds__(256) void bn_reduce_rows_kernel(const float* __rest
     double t = 0.0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) t += sm[which][i][cc];
-    const int ch = blockIdx.x * 32 + cc;
-    if (ch < C) out[((size_t)blockIdx.y * 2 + which) * C + ch] = t;
+    wave0(which, blockIdx.x * 32 + cc, t);
   }
+}
+__global__ __launch_bounds__(256) void bn_reduce_rows_kernel(const float* __restrict__ part, int rows, int C, double* __restrict__ out, int splits) {
+  out += (size_t)blockIdx.z * splits * 2 * C;
+  bn_reduce_rows_block(part, rows, C, splits, [&](int which, int ch, double t) {
+    if (ch < C) out[((size_t)blockIdx.y * 2 + which) * C + ch] = t;
+  });
 }
 
 // stage 2 (+ finalize): one thread per channel; with segments (a.nseg > 1) the thread finalizes them one after the other, so the
@@ -126,40 +134,10 @@ __global__ void bn_finalize_kernel(const double* __restrict__ stage, int splits,
 // these lines: kernel start invalidated them and nobody reads them before the last ticket).  The ticket word is left at 0.
 __global__ __launch_bounds__(256) void bn_reduce_finalize_kernel(const float* __restrict__ part, int rows, double* __restrict__ stage, int splits,
                                                                  const BnFinalizeArgs a) {
-  __shared__ double sm[2][8][32];
   __shared__ int s_last;
   const int C = a.C;
-  const int c = blockIdx.x * 32 + (threadIdx.x & 31);
-  const int rl = threadIdx.x >> 5;
-  const int per = (rows + splits - 1) / splits;
-  const int r0 = blockIdx.y * per, r1 = min(rows, r0 + per);
-  part += (size_t)blockIdx.z * rows * 2 * C;
   double* out = stage + (size_t)blockIdx.z * splits * 2 * C;
-  double s = 0.0, ss = 0.0;
-  if (c < C) {
-    int r = r0 + rl;
-    for (; r + 8 < r1; r += 16) {               // two rows in flight per trip
-      const float* p = part + (size_t)r * 2 * C;
-      const float* q = p + (size_t)16 * C;
-      const float a0 = p[c], a1 = p[C + c], b0 = q[c], b1 = q[C + c];
-      s += (double)a0 + (double)b0;
-      ss += (double)a1 + (double)b1;
-    }
-    for (; r < r1; r += 8) {
-      const float* p = part + (size_t)r * 2 * C;
-      s += (double)p[c];
-      ss += (double)p[C + c];
-    }
-  }
-  sm[0][rl][threadIdx.x & 31] = s;
-  sm[1][rl][threadIdx.x & 31] = ss;
-  __syncthreads();
-  if (threadIdx.x < 64) {                       // wave 0: publish, drain, ticket
-    const int which = threadIdx.x >> 5, cc = threadIdx.x & 31;
-    double t = 0.0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t += sm[which][i][cc];
-    const int ch = blockIdx.x * 32 + cc;
+  bn_reduce_rows_block(part, rows, C, splits, [&](int which, int ch, double t) {      // wave 0: publish, drain, ticket
     if (ch < C) __hip_atomic_store(&out[((size_t)blockIdx.y * 2 + which) * C + ch], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (threadIdx.x == 0) {
@@ -168,7 +146,7 @@ __global__ __launch_bounds__(256) void bn_reduce_finalize_kernel(const float* __
       s_last = old == total - 1;
       if (old == total - 1) __hip_atomic_store(a.tickets + blockIdx.x, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next launch
     }
-  }
+  });
   __syncthreads();
   if (!s_last) return;
   bn_finalize_block<true>(stage, splits, a, blockIdx.x);
@@ -631,11 +609,14 @@ hipError_t launch_avgpool_bwd(int dtype, const float* dy, void* dx, int N, int H
 }
 
 // ------------------------------------------------------------------ BatchNorm backward
-template <typename T>
+// g = the gradient that reaches the BatchNorm's output at 16-byte chunk i (and xf = x there): dy, or with POOL the pooled gradient's
+// share of this pixel, under the ReLU mask the descriptor names.  POOL is a compile-time choice: only bn_bwd_reduce_kernel ever sees a
+// pool_dy descriptor here (launch_bn_bwd_apply sends them to bn_bwd_apply_pool_kernel, bn_bwd_pair_ok refuses them)
+template <typename T, bool POOL>
 __device__ __forceinline__ void bn_bwd_g(const BnBwdArgs& a, size_t i, const float* rsc, const float* rsh, float* g, float* xf) {
   constexpr int EPC = Elem<T>::EPC;
   Elem<T>::unpack(ld16_nt(reinterpret_cast<const char*>(a.x) + i * 16), xf);
-  if (a.pool_dy) {
+  if constexpr (POOL) {
     // the gradient arrives through a 3x3/2 pad-1 max-pool (the stem): gather it from the <= 4 pooled windows that contain
     // this pixel and whose recorded argmax is this pixel -- the un-pooled gradient tensor is never materialised
     const int cols = a.C / EPC, col = (int)(i % cols);
@@ -645,31 +626,21 @@ __device__ __forceinline__ void bn_bwd_g(const BnBwdArgs& a, size_t i, const flo
     const int h = (int)(pix % a.pH), n = (int)(pix / a.pH);
 #pragma unroll
     for (int e = 0; e < EPC; ++e) g[e] = 0.f;
-    // all four candidate windows are loaded UNCONDITIONALLY (clamped addresses) so the loads go out back to back; the
-    // window is then kept or dropped by a select -- no divergent branches around memory operations
     u32x4_t dv[4];
     uint32_t am[4][2];
-    bool ok[4];
-    int code[4];
+    bn_pool_windows<T, false>(a, (size_t)n, h >> 1, w >> 1, cols, col, dv, am);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
+      // window k holds this pixel if it exists and, for the second row / column, if the pixel is an odd one
       const int dh = k >> 1, dw = k & 1;
       const int oh = (h >> 1) + dh, ow = (w >> 1) + dw;
-      ok[k] = (dh == 0 || (h & 1)) && (dw == 0 || (w & 1)) && oh < a.pOH && ow < a.pOW;
-      code[k] = (h - (2 * oh - 1)) * 3 + (w - (2 * ow - 1));
-      const int ohc = oh < a.pOH ? oh : a.pOH - 1, owc = ow < a.pOW ? ow : a.pOW - 1;
-      const size_t o = (((size_t)n * a.pOH + ohc) * a.pOW + owc) * cols + col;
-      dv[k] = ld16(reinterpret_cast<const char*>(a.pool_dy) + o * 16);
-      if (EPC == 8) { const u32x2_t v = *reinterpret_cast<const u32x2_t*>(a.pool_argmax + o * EPC); am[k][0] = v[0]; am[k][1] = v[1]; }
-      else { am[k][0] = *reinterpret_cast<const uint32_t*>(a.pool_argmax + o * EPC); am[k][1] = 0; }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
+      const bool ok = (dh == 0 || (h & 1)) && (dw == 0 || (w & 1)) && oh < a.pOH && ow < a.pOW;
+      const uint32_t code = (uint32_t)((h - (2 * oh - 1)) * 3 + (w - (2 * ow - 1)));
       float d[EPC];
       Elem<T>::unpack(dv[k], d);
 #pragma unroll
       for (int e = 0; e < EPC; ++e)
-        if (ok[k] && ((am[k][e >> 2] >> (8 * (e & 3))) & 0xffu) == (uint32_t)code[k]) g[e] += d[e];
+        if (ok && bn_pool_code(am[k], e) == code) g[e] += d[e];
     }
   } else {
     Elem<T>::unpack(ld16_nt(reinterpret_cast<const char*>(a.dy) + i * 16), g);
@@ -692,18 +663,15 @@ __device__ __forceinline__ void bn_bwd_g(const BnBwdArgs& a, size_t i, const flo
   }
 }
 
-// affine gradients from the finished sums, by workgroup 0 of the apply pass (same arithmetic as bn_param_grads_kernel); with
+// affine gradients from the finished sums, by workgroup 0 of the apply pass (bn_bwd_affine_grads, as bn_param_grads_kernel); with
 // segments the contributions are added one after the other, like the per-segment launches would
 __device__ __forceinline__ void bn_bwd_param_grads(const BnBwdArgs& a) {
   if (blockIdx.x != 0 || blockIdx.y != 0 || !a.dgamma || !a.dbeta) return;
   const int nseg = a.nseg > 1 ? a.nseg : 1;
   for (int c = threadIdx.x; c < a.C; c += 256) {
     float dg = a.dgamma[c], db = a.dbeta[c];
-    for (int z = 0; z < nseg; ++z) {
-      const double* sums = a.sums + (size_t)z * a.sums_stride;
-      dg += (float)(sums[a.C + c] * (double)a.invstd[(size_t)z * a.seg_stride + c] * (double)a.pg_scale);
-      db += (float)(sums[c] * (double)a.pg_scale);
-    }
+    for (int z = 0; z < nseg; ++z)
+      bn_bwd_affine_grads(dg, db, a.sums + (size_t)z * a.sums_stride, a.invstd + (size_t)z * a.seg_stride, a.C, c, a.pg_scale);
     a.dgamma[c] = dg;
     a.dbeta[c] = db;
   }
@@ -732,7 +700,8 @@ __device__ __forceinline__ BnBwdArgs bn_bwd_segment(const BnBwdArgs& a) {
 // NB threads per workgroup.  A workgroup leaves its 2C per-channel sums as one fp64 row of `rows` ([segment][workgroup][2][C]);
 // bn_bwd_sums_kernel adds the rows in a fixed order.  (Until round 4 the sums ended in fp64 atomics on 2C addresses: an order that
 // changes run to run, and atomics on one address serialise -- ~18 us at the end of a 1024-workgroup launch.)
-template <typename T, int NB>
+// POOL: a.pool_dy without a.pool_y -- the per-pixel gather of bn_bwd_g (with pool_y: bn_bwd_reduce_pool_kernel)
+template <typename T, int NB, bool POOL>
 __global__ __launch_bounds__(NB) void bn_bwd_reduce_kernel(const BnBwdArgs a0, double* __restrict__ rows) {
   const BnBwdArgs a = bn_bwd_segment<T>(a0);
   constexpr int EPC = Elem<T>::EPC;
@@ -750,7 +719,7 @@ __global__ __launch_bounds__(NB) void bn_bwd_reduce_kernel(const BnBwdArgs a0, d
   if (rl < rpp) {
     for (size_t p = (size_t)blockIdx.x * rpp + rl; p < a.pixels; p += (size_t)gridDim.x * rpp) {
       float g[EPC], xf[EPC];
-      bn_bwd_g<T>(a, p * cols + col, rsc, rsh, g, xf);
+      bn_bwd_g<T, POOL>(a, p * cols + col, rsc, rsh, g, xf);
       if (a.g_in_reduce) st16(reinterpret_cast<char*>(a.gout) + (p * cols + col) * 16, Elem<T>::pack(g));
 #pragma unroll
       for (int e = 0; e < EPC; ++e) { s0[e] += g[e]; s1[e] = fmaf(g[e], xf[e] - mean[e], s1[e]); }
@@ -759,14 +728,9 @@ __global__ __launch_bounds__(NB) void bn_bwd_reduce_kernel(const BnBwdArgs a0, d
 #pragma unroll
   for (int e = 0; e < EPC; ++e) { sm[threadIdx.x][e] = s0[e]; sm[threadIdx.x][EPC + e] = s1[e]; }
   __syncthreads();
-  // thread t < cols*2*EPC: (col, which/e) sums over rl
-  for (int t = threadIdx.x; t < cols * 2 * EPC; t += NB) {
-    const int cc = t / (2 * EPC), q = t - cc * 2 * EPC;
-    double acc = 0.0;
-    for (int r = 0; r < rpp; ++r) acc += (double)sm[r * cols + cc][q];
-    const int which = q / EPC, e = q - which * EPC;
-    rows[(((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 + which) * a.C + cc * EPC + e] = acc;
-  }
+  bn_bwd_fold_columns<2, EPC, NB>(sm, cols, rpp, [&](int which, int c, double acc) {
+    rows[(((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 + which) * a.C + c] = acc;
+  });
 }
 
 template <typename T>
@@ -775,25 +739,16 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdArgs a0) {
   constexpr int EPC = Elem<T>::EPC;
   const int cols = a.C / EPC;
   const size_t total = a.pixels * cols;
-  const float invM = (float)(1.0 / a.count);
-  // the grid stride (gridDim.x*256) is a multiple of cols (ew_grid_cols), so a thread always works on the same EPC channels:
-  // dx = cA*g + cB*x + cC with cA = scale, cB = -scale*invstd^2*mean(g*(x-mu)), cC = -scale*mean(g) - cB*mu
+  // the grid stride (gridDim.x*256) is a multiple of cols (ew_grid_cols), so a thread always works on the same EPC channels
   const int cb = (int)(((size_t)blockIdx.x * 256 + threadIdx.x) % cols) * EPC;
-  float cA[EPC], cB[EPC], cC[EPC], rsc[EPC], rsh[EPC];
+  float cA[EPC], cB[EPC], cC[EPC], rsh[EPC];
+  bn_bwd_coeffs(a, a.C, cb, cA, cB, cC);
 #pragma unroll
-  for (int e = 0; e < EPC; ++e) {
-    const int c = cb + e;
-    const float is = a.invstd[c], sc = a.scale[c];
-    const float m0 = (float)a.sums[c] * invM, m1 = (float)a.sums[a.C + c] * invM;
-    cA[e] = sc;
-    cB[e] = -sc * is * is * m1;
-    cC[e] = -sc * m0 - cB[e] * a.mean[c];
-    rsc[e] = sc; rsh[e] = a.shift[c];
-  }
+  for (int e = 0; e < EPC; ++e) rsh[e] = a.shift[cb + e];
   bn_bwd_param_grads(a0);
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     float g[EPC], xf[EPC], d[EPC];
-    bn_bwd_g<T>(a, i, rsc, rsh, g, xf);
+    bn_bwd_g<T, false>(a, i, cA, rsh, g, xf);
 #pragma unroll
     for (int e = 0; e < EPC; ++e) d[e] = fmaf(cA[e], g[e], fmaf(cB[e], xf[e], cC[e]));
     st16_nt(reinterpret_cast<char*>(a.dx) + i * 16, Elem<T>::pack(d));
@@ -829,7 +784,7 @@ __global__ __launch_bounds__(NB) void bn_bwd_reduce_pair_kernel(const BnBwdArgs 
     for (size_t p = (size_t)blockIdx.x * rpp + rl; p < a.pixels; p += (size_t)gridDim.x * rpp) {
       float g[EPC], xf[EPC], xb[EPC];
       const size_t i = p * cols + col;
-      bn_bwd_g<T>(a, i, rsc, rsh, g, xf);
+      bn_bwd_g<T, false>(a, i, rsc, rsh, g, xf);
       Elem<T>::unpack(ld16_nt(reinterpret_cast<const char*>(b.x) + i * 16), xb);
       if (keep_g) st16(reinterpret_cast<char*>(a.gout) + i * 16, Elem<T>::pack(g));
 #pragma unroll
@@ -845,16 +800,12 @@ __global__ __launch_bounds__(NB) void bn_bwd_reduce_pair_kernel(const BnBwdArgs 
   __syncthreads();
   // rows: [BatchNorm (a, b)][workgroup][2][C]; the second BatchNorm's sum of g is the first one's
   const size_t bstride = (size_t)gridDim.x * 2 * a.C;
-  for (int t = threadIdx.x; t < cols * 3 * EPC; t += NB) {
-    const int cc = t / (3 * EPC), q = t - cc * 3 * EPC;
-    double acc = 0.0;
-    for (int r = 0; r < rpp; ++r) acc += (double)sm[r * cols + cc][q];
-    const int which = q / EPC, e = q - which * EPC;
-    double* ra = rows + ((size_t)blockIdx.x * 2) * a.C + cc * EPC + e;
+  bn_bwd_fold_columns<3, EPC, NB>(sm, cols, rpp, [&](int which, int c, double acc) {
+    double* ra = rows + ((size_t)blockIdx.x * 2) * a.C + c;
     if (which == 0) { ra[0] = acc; ra[bstride] = acc; }
     else if (which == 1) ra[a.C] = acc;
     else ra[bstride + a.C] = acc;
-  }
+  });
 }
 
 template <typename T>
@@ -863,21 +814,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pair_kernel(const BnBwdArgs 
   const int cols = a.C / EPC;
   const size_t total = a.pixels * cols;
   const int cb = (int)(((size_t)blockIdx.x * 256 + threadIdx.x) % cols) * EPC;
-  float cA[EPC], cB[EPC], cC[EPC], dA[EPC], dB[EPC], dC[EPC], rsc[EPC], rsh[EPC];
-  {
-    const float invM = (float)(1.0 / a.count), invMb = (float)(1.0 / b.count);
+  float cA[EPC], cB[EPC], cC[EPC], dA[EPC], dB[EPC], dC[EPC], rsh[EPC];
+  bn_bwd_coeffs(a, a.C, cb, cA, cB, cC);
+  bn_bwd_coeffs(b, b.C, cb, dA, dB, dC);
 #pragma unroll
-    for (int e = 0; e < EPC; ++e) {
-      const int c = cb + e;
-      float is = a.invstd[c], sc = a.scale[c];
-      float m0 = (float)a.sums[c] * invM, m1 = (float)a.sums[a.C + c] * invM;
-      cA[e] = sc; cB[e] = -sc * is * is * m1; cC[e] = -sc * m0 - cB[e] * a.mean[c];
-      rsc[e] = sc; rsh[e] = a.shift[c];
-      is = b.invstd[c]; sc = b.scale[c];
-      m0 = (float)b.sums[c] * invMb; m1 = (float)b.sums[b.C + c] * invMb;
-      dA[e] = sc; dB[e] = -sc * is * is * m1; dC[e] = -sc * m0 - dB[e] * b.mean[c];
-    }
-  }
+  for (int e = 0; e < EPC; ++e) rsh[e] = a.shift[cb + e];
   bn_bwd_param_grads(a);
   bn_bwd_param_grads(b);
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
@@ -886,7 +827,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pair_kernel(const BnBwdArgs 
       Elem<T>::unpack(ld16_nt(reinterpret_cast<const char*>(a.gout) + i * 16), g);
       Elem<T>::unpack(ld16_nt(reinterpret_cast<const char*>(a.x) + i * 16), xa);
     } else {
-      bn_bwd_g<T>(a, i, rsc, rsh, g, xa);          // (dy, mask) again: the reduce pass kept no g
+      bn_bwd_g<T, false>(a, i, cA, rsh, g, xa);          // (dy, mask) again: the reduce pass kept no g
     }
     Elem<T>::unpack(ld16_nt(reinterpret_cast<const char*>(b.x) + i * 16), xb);
 #pragma unroll
@@ -947,13 +888,9 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_pool_kernel(const BnBwdArgs
 #pragma unroll
   for (int e = 0; e < EPC; ++e) { sm[threadIdx.x][e] = s0[e]; sm[threadIdx.x][EPC + e] = s1[e]; }
   __syncthreads();
-  for (int t = threadIdx.x; t < cols * 2 * EPC; t += 256) {
-    const int cc = t / (2 * EPC), q = t - cc * 2 * EPC;
-    double acc = 0.0;
-    for (int r = 0; r < rpp; ++r) acc += (double)sm[r * cols + cc][q];
-    const int which = q / EPC, e = q - which * EPC;
-    rows[(((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 + which) * a.C + cc * EPC + e] = acc;
-  }
+  bn_bwd_fold_columns<2, EPC, 256>(sm, cols, rpp, [&](int which, int c, double acc) {
+    rows[(((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 + which) * a.C + c] = acc;
+  });
 }
 
 // Apply pass of the stem form on 2x2 input-pixel blocks: the four pixels (2a+i, 2b+j) share the four pooling windows
@@ -966,44 +903,22 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pool_kernel(const BnBwdArgs 
   const int BH = (a.pH + 1) / 2, BW = (a.pW + 1) / 2;
   const size_t N = a.pixels / ((size_t)a.pH * a.pW);
   const size_t total = N * BH * BW * cols;
-  const float invM = (float)(1.0 / a.count);
   const int cb = (int)(((size_t)blockIdx.x * 256 + threadIdx.x) % cols) * EPC;      // grid stride is a multiple of cols (ew_grid_cols)
   float cA[EPC], cB[EPC], cC[EPC], rsh[EPC];
+  bn_bwd_coeffs(a, a.C, cb, cA, cB, cC);
 #pragma unroll
-  for (int e = 0; e < EPC; ++e) {
-    const int c = cb + e;
-    const float is = a.invstd[c], sc = a.scale[c];
-    const float m0 = (float)a.sums[c] * invM, m1 = (float)a.sums[a.C + c] * invM;
-    cA[e] = sc;
-    cB[e] = -sc * is * is * m1;
-    cC[e] = -sc * m0 - cB[e] * a.mean[c];
-    rsh[e] = a.shift[c];
-  }
+  for (int e = 0; e < EPC; ++e) rsh[e] = a.shift[cb + e];
   bn_bwd_param_grads(a);
   const char* xg = reinterpret_cast<const char*>(a.x);
-  const char* dyg = reinterpret_cast<const char*>(a.pool_dy);
   char* dxg = reinterpret_cast<char*>(a.dx);
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const int col = (int)(i % cols);
     size_t q = i / cols;
     const int bw = (int)(q % BW); q /= BW;
     const int bh = (int)(q % BH); const size_t n = q / BH;
-    // the four windows: unconditional loads from clamped addresses, validity applied by select
-    u32x4_t dv[2][2];
-    uint32_t am[2][2][2];
-    bool wok[2][2];
-#pragma unroll
-    for (int di = 0; di < 2; ++di)
-#pragma unroll
-      for (int dj = 0; dj < 2; ++dj) {
-        const int oh = bh + di, ow = bw + dj;
-        wok[di][dj] = oh < a.pOH && ow < a.pOW;
-        const int ohc = oh < a.pOH ? oh : a.pOH - 1, owc = ow < a.pOW ? ow : a.pOW - 1;
-        const size_t o = ((n * a.pOH + ohc) * a.pOW + owc) * cols + col;
-        dv[di][dj] = ld16_nt(dyg + o * 16);
-        if (EPC == 8) { const u32x2_t v = *reinterpret_cast<const u32x2_t*>(a.pool_argmax + o * EPC); am[di][dj][0] = v[0]; am[di][dj][1] = v[1]; }
-        else { am[di][dj][0] = *reinterpret_cast<const uint32_t*>(a.pool_argmax + o * EPC); am[di][dj][1] = 0; }
-      }
+    u32x4_t dv[4];
+    uint32_t am[4][2];
+    bn_pool_windows<T, true>(a, n, bh, bw, cols, col, dv, am);
     u32x4_t xv[2][2];
     bool pok[2][2];
 #pragma unroll
@@ -1015,28 +930,17 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pool_kernel(const BnBwdArgs 
         const int hc = h < a.pH ? h : a.pH - 1, wc = w < a.pW ? w : a.pW - 1;
         xv[pi][pj] = ld16_nt(xg + (((n * a.pH + hc) * a.pW + wc) * cols + col) * 16);
       }
-    float dw[2][2][EPC];
+    float dw[4][EPC];
+    uint32_t cd[4][EPC];
 #pragma unroll
-    for (int di = 0; di < 2; ++di)
-#pragma unroll
-      for (int dj = 0; dj < 2; ++dj) Elem<T>::unpack(dv[di][dj], dw[di][dj]);
+    for (int k = 0; k < 4; ++k) bn_pool_decode<T>(dv[k], am[k], bh + (k >> 1) < a.pOH && bw + (k & 1) < a.pOW, dw[k], cd[k]);
 #pragma unroll
     for (int pi = 0; pi < 2; ++pi)
 #pragma unroll
       for (int pj = 0; pj < 2; ++pj) {
         float xf[EPC], g[EPC], d[EPC];
         Elem<T>::unpack(xv[pi][pj], xf);
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) g[e] = 0.f;
-#pragma unroll
-        for (int di = 0; di <= pi; ++di)
-#pragma unroll
-          for (int dj = 0; dj <= pj; ++dj) {
-            const uint32_t code = (uint32_t)((pi - 2 * di + 1) * 3 + (pj - 2 * dj + 1));
-#pragma unroll
-            for (int e = 0; e < EPC; ++e)
-              if (wok[di][dj] && ((am[di][dj][e >> 2] >> (8 * (e & 3))) & 0xffu) == code) g[e] += dw[di][dj][e];
-          }
+        bn_pool_gather(pi, pj, dw, cd, g);
 #pragma unroll
         for (int e = 0; e < EPC; ++e) {
           if (a.relu_from_x && !(fmaf(xf[e], cA[e], rsh[e]) > 0.f)) g[e] = 0.f;   // ReLU between the BatchNorm and the pool
@@ -1083,6 +987,15 @@ static BnRedGrid bn_bwd_reduce_grid(size_t pixels, int cols, bool pooled) {
   if (blocks < 512 || pooled) return {blocks, 256};
   return {rows_of(1024, 256), 1024};
 }
+// what both reduce launchers ask first: the 16-byte columns of a pixel (0: a width the reduce kernels do not serve -- the columns must
+// divide the 256 threads of a workgroup) and the scratch for `slices` (segments, or the BatchNorms of the pair) x nrows fp64 rows of [2][C]
+static int bn_bwd_reduce_cols(int dtype, int C) {
+  const int cols = C / (dtype == DT_BF16 ? 8 : 4);
+  return cols < 1 || cols > 256 || (256 % cols) != 0 ? 0 : cols;
+}
+static double* bn_bwd_reduce_rows(hipStream_t st, int slices, int nrows, int C) {
+  return reinterpret_cast<double*>(stream_scratch(st, (size_t)slices * nrows * 2 * C * sizeof(double)));
+}
 // sums[y] = the rows of grid-y slice y (a segment, or a BatchNorm of the pair) in bn_bwd_sums_kernel's fixed order
 static hipError_t bn_bwd_fold(const double* rows, int nrows, int C, int ny, double* sums, int sums_stride, hipStream_t st) {
   hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(cdiv(2 * C, 64), ny), dim3(64, 16), 0, st, rows, nrows, 2 * C, sums, sums_stride);
@@ -1090,22 +1003,22 @@ static hipError_t bn_bwd_fold(const double* rows, int nrows, int C, int ny, doub
 }
 
 // the reduce pass: per-workgroup rows, then their ordered sum OVERWRITES a.sums (no atomics: the same bits run after run)
-template <int NB>
+template <int NB, bool POOL>
 static hipError_t bn_bwd_reduce_nb(int dtype, const BnBwdArgs& a, int nrows, int nseg, double* rows, hipStream_t st) {
   return by_dtype(dtype, [&](auto t) {
     using T = decltype(t);
     const size_t lds = (size_t)NB * (2 * Elem<T>::EPC + 1) * sizeof(float);
-    return launch_lds<bn_bwd_reduce_kernel<T, NB>>(dim3(nrows, nseg), dim3(NB), lds, 96 * 1024, st, a, rows);
+    return launch_lds<bn_bwd_reduce_kernel<T, NB, POOL>>(dim3(nrows, nseg), dim3(NB), lds, 96 * 1024, st, a, rows);
   });
 }
 hipError_t launch_bn_bwd_reduce(int dtype, const BnBwdArgs& a, hipStream_t st) {
-  const int cols = a.C / (dtype == DT_BF16 ? 8 : 4);
-  if (cols > 256 || (256 % cols) != 0) return hipErrorInvalidValue;
+  const int cols = bn_bwd_reduce_cols(dtype, a.C);
+  if (!cols) return hipErrorInvalidValue;
   const int nseg = a.nseg > 1 ? a.nseg : 1;      // grid y; the kernels take their segment's share (bn_bwd_segment)
   if (nseg > 1 && (a.pool_dy || a.pixels % nseg != 0)) return hipErrorInvalidValue;
   const bool pooled = a.pool_dy && a.pool_y;
   const BnRedGrid g = bn_bwd_reduce_grid(a.pixels / nseg, cols, pooled);
-  double* rows = reinterpret_cast<double*>(stream_scratch(st, (size_t)nseg * g.nrows * 2 * a.C * sizeof(double)));
+  double* rows = bn_bwd_reduce_rows(st, nseg, g.nrows, a.C);
   if (!rows) return hipErrorOutOfMemory;
   hipError_t e;
   if (pooled) {
@@ -1114,7 +1027,11 @@ hipError_t launch_bn_bwd_reduce(int dtype, const BnBwdArgs& a, hipStream_t st) {
       return hipGetLastError();
     });
   } else {
-    e = g.NB == 1024 ? bn_bwd_reduce_nb<1024>(dtype, a, g.nrows, nseg, rows, st) : bn_bwd_reduce_nb<256>(dtype, a, g.nrows, nseg, rows, st);
+    auto run = [&](auto pool) {
+      constexpr bool POOL = decltype(pool)::value;
+      return g.NB == 1024 ? bn_bwd_reduce_nb<1024, POOL>(dtype, a, g.nrows, nseg, rows, st) : bn_bwd_reduce_nb<256, POOL>(dtype, a, g.nrows, nseg, rows, st);
+    };
+    e = a.pool_dy ? run(std::true_type{}) : run(std::false_type{});
   }
   if (e != hipSuccess) return e;
   return bn_bwd_fold(rows, g.nrows, a.C, nseg, a.sums, nseg > 1 ? a.sums_stride : 0, st);
@@ -1136,11 +1053,11 @@ static hipError_t bn_bwd_reduce_pair_nb(int dtype, const BnBwdArgs& a, const BnB
   });
 }
 hipError_t launch_bn_bwd_reduce_pair(int dtype, const BnBwdArgs& a, const BnBwdArgs& b, int keep_g, hipStream_t st) {
-  const int cols = a.C / (dtype == DT_BF16 ? 8 : 4);
-  if (cols > 256 || (256 % cols) != 0 || !bn_bwd_pair_ok(a, b)) return hipErrorInvalidValue;
+  const int cols = bn_bwd_reduce_cols(dtype, a.C);
+  if (!cols || !bn_bwd_pair_ok(a, b)) return hipErrorInvalidValue;
   // the grid of launch_bn_bwd_reduce for this tensor (same rows, same per-thread order: the same sums)
   const BnRedGrid g = bn_bwd_reduce_grid(a.pixels, cols, false);
-  double* rows = reinterpret_cast<double*>(stream_scratch(st, (size_t)2 * g.nrows * 2 * a.C * sizeof(double)));
+  double* rows = bn_bwd_reduce_rows(st, 2, g.nrows, a.C);
   if (!rows) return hipErrorOutOfMemory;
   const hipError_t e = g.NB == 1024 ? bn_bwd_reduce_pair_nb<1024>(dtype, a, b, g.nrows, rows, keep_g, st)
                                     : bn_bwd_reduce_pair_nb<256>(dtype, a, b, g.nrows, rows, keep_g, st);
@@ -1182,8 +1099,7 @@ hipError_t launch_bn_bwd_apply(int dtype, const BnBwdArgs& a0, hipStream_t st) {
 __global__ void bn_param_grads_kernel(const double* sums, const float* invstd, float* dgamma, float* dbeta, int C, float scale) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  dgamma[c] += (float)(sums[C + c] * (double)invstd[c] * (double)scale);
-  dbeta[c] += (float)(sums[c] * (double)scale);
+  bn_bwd_affine_grads(dgamma[c], dbeta[c], sums, invstd, C, c, scale);
 }
 hipError_t launch_bn_param_grads_scaled(const double* sums, const float* invstd, float* dgamma, float* dbeta, int C, float scale, hipStream_t st) {
   hipLaunchKernelGGL(bn_param_grads_kernel, dim3(cdiv(C, 64)), dim3(64), 0, st, sums, invstd, dgamma, dbeta, C, scale);

@@ -9,6 +9,7 @@
 // is staged once, and BatchNorm (sum, sumsq) partials are accumulated in registers across tiles.
 #include "kernels.hpp"
 #include "stem_halo.hpp"
+#include "bn_bwd.hpp"
 #include <type_traits>
 
 namespace sslcr {
@@ -351,21 +352,11 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradArgs a, 
   StemPoolRaw praw[IT];
   float cA[EPC], cB[EPC], cC[EPC], rsh[EPC];     // POOL: dY = cA g + cB x + cC for this thread's channel chunk (bn_bwd_apply_pool_kernel)
   if constexpr (POOL) {
-    const float invM = (float)(1.0 / b.count);
+    bn_bwd_coeffs(b, 64, chunk * EPC, cA, cB, cC);
 #pragma unroll
-    for (int e = 0; e < EPC; ++e) {
-      const int c = chunk * EPC + e;
-      const float is = b.invstd[c], sc = b.scale[c];
-      const float m0 = (float)b.sums[c] * invM, m1 = (float)b.sums[64 + c] * invM;
-      cA[e] = sc;
-      cB[e] = -sc * is * is * m1;
-      cC[e] = -sc * m0 - cB[e] * b.mean[c];
-      rsh[e] = b.shift[c];
-    }
-    if (blockIdx.x == 0 && b.dgamma && b.dbeta && tid < 64) {        // affine gradients, as workgroup 0 of the apply pass does
-      b.dgamma[tid] += (float)(b.sums[64 + tid] * (double)b.invstd[tid] * (double)b.pg_scale);
-      b.dbeta[tid] += (float)(b.sums[tid] * (double)b.pg_scale);
-    }
+    for (int e = 0; e < EPC; ++e) rsh[e] = b.shift[chunk * EPC + e];
+    if (blockIdx.x == 0 && b.dgamma && b.dbeta && tid < 64)          // affine gradients, as workgroup 0 of the apply pass does
+      bn_bwd_affine_grads(b.dgamma[tid], b.dbeta[tid], b.sums, b.invstd, 64, tid, b.pg_scale);
   }
   StemRaw raw{{0u, 0u, 0u}};
   auto issue = [&](int tile) {
@@ -378,24 +369,14 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradArgs a, 
     }
     if constexpr (POOL) {
       const char* xg = reinterpret_cast<const char*>(b.x);
-      const char* dyg = reinterpret_cast<const char*>(b.pool_dy);
 #pragma unroll
       for (int it = 0; it < IT; ++it) {
         const int blk = (tid + 256 * it) / CPR;
         const int bh = (ho0 >> 1) + blk / (TW / 2), bw = (wo0 >> 1) + blk % (TW / 2);
         // the four windows and the four pixels: unconditional loads from clamped addresses, validity applied in commit
+        bn_pool_windows<T, true>(b, (size_t)n, bh, bw, CPR, chunk, praw[it].dv, praw[it].am);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const int oh = bh + (q >> 1), ow = bw + (q & 1);
-          const int ohc = oh < b.pOH ? oh : b.pOH - 1, owc = ow < b.pOW ? ow : b.pOW - 1;
-          const size_t o = (((size_t)n * b.pOH + ohc) * b.pOW + owc) * CPR + chunk;
-          praw[it].dv[q] = ld16_nt(dyg + o * 16);
-          if constexpr (EPC == 8) {
-            const u32x2_t v = *reinterpret_cast<const u32x2_t*>(b.pool_argmax + o * EPC);
-            praw[it].am[q][0] = v[0]; praw[it].am[q][1] = v[1];
-          } else {
-            praw[it].am[q][0] = *reinterpret_cast<const uint32_t*>(b.pool_argmax + o * EPC); praw[it].am[q][1] = 0;
-          }
           const int h = 2 * bh + (q >> 1), w = 2 * bw + (q & 1);
           const int hc = h < a.OH ? h : a.OH - 1, wc = w < a.OW ? w : a.OW - 1;
           praw[it].xv[q] = ld16_nt(xg + ((((size_t)n * a.OH + hc) * a.OW + wc) * CPR + chunk) * 16);
@@ -437,12 +418,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradArgs a, 
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const bool wok = ((ho0 + lh) >> 1) + (q >> 1) < b.pOH && ((wo0 + lw) >> 1) + (q & 1) < b.pOW;
-          u32x4_t v = praw[it].dv[q];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] = wok ? v[j] : 0u;
-          Elem<T>::unpack(v, dw[q]);
-#pragma unroll
-          for (int e = 0; e < EPC; ++e) cd[q][e] = (praw[it].am[q][e >> 2] >> (8 * (e & 3))) & 0xffu;
+          bn_pool_decode<T>(praw[it].dv[q], praw[it].am[q], wok, dw[q], cd[q]);
         }
         const float thr = b.relu_from_x ? 0.f : -__builtin_inff();   // ReLU between the BatchNorm and the pool: g lives where y > thr
 #pragma unroll
@@ -451,16 +427,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradArgs a, 
           for (int pj = 0; pj < 2; ++pj) {
             float xf[EPC], g[EPC], d[EPC];
             Elem<T>::unpack(praw[it].xv[pi * 2 + pj], xf);
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) g[e] = 0.f;
-#pragma unroll
-            for (int di = 0; di <= pi; ++di)
-#pragma unroll
-              for (int dj = 0; dj <= pj; ++dj) {
-                const uint32_t code = (uint32_t)((pi - 2 * di + 1) * 3 + (pj - 2 * dj + 1));
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) g[e] += cd[di * 2 + dj][e] == code ? dw[di * 2 + dj][e] : 0.f;
-              }
+            bn_pool_gather(pi, pj, dw, cd, g);
             const bool pok = ho0 + lh + pi < a.OH && wo0 + lw + pj < a.OW;
 #pragma unroll
             for (int e = 0; e < EPC; ++e) {
@@ -590,20 +557,9 @@ __global__ __launch_bounds__(768) void stem_wgrad_pool2_kernel(const StemWgradAr
   const int lh = 2 * (blk >> 3), lw = 2 * (blk & 7);
   float cA[4], cB[4], cC[4];
   if (!matrix) {
-    const float invM = (float)(1.0 / b.count);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int c = cq * 4 + e;
-      const float is = b.invstd[c], sc = b.scale[c];
-      const float m0 = (float)b.sums[c] * invM, m1 = (float)b.sums[64 + c] * invM;
-      cA[e] = sc;
-      cB[e] = -sc * is * is * m1;
-      cC[e] = -sc * m0 - cB[e] * b.mean[c];
-    }
-    if (blockIdx.x == 0 && b.dgamma && b.dbeta && pt < 64) {          // affine gradients, as workgroup 0 of the apply pass does
-      b.dgamma[pt] += (float)(b.sums[64 + pt] * (double)b.invstd[pt] * (double)b.pg_scale);
-      b.dbeta[pt] += (float)(b.sums[pt] * (double)b.pg_scale);
-    }
+    bn_bwd_coeffs(b, 64, cq * 4, cA, cB, cC);
+    if (blockIdx.x == 0 && b.dgamma && b.dbeta && pt < 64)            // affine gradients, as workgroup 0 of the apply pass does
+      bn_bwd_affine_grads(b.dgamma[pt], b.dbeta[pt], b.sums, b.invstd, 64, pt, b.pg_scale);
   }
   // No ReLU test here: sslcr_bn_relu_maxpool records code 9 ("nobody") for a window whose maximum is not positive, and the pixel
   // a live window names has y = that maximum > 0.  EDGE = the tile touches the border of the map (ragged tile, or its last
@@ -640,15 +596,8 @@ __global__ __launch_bounds__(768) void stem_wgrad_pool2_kernel(const StemWgradAr
       for (int pj = 0; pj < 2; ++pj) {
         const u32x2_t xw = xv[pi * 2 + pj];
         const float xf[4] = {bf_lo(xw[0]), bf_hi(xw[0]), bf_lo(xw[1]), bf_hi(xw[1])};
-        float gg[4] = {0.f, 0.f, 0.f, 0.f}, d[4];
-#pragma unroll
-        for (int di = 0; di <= pi; ++di)
-#pragma unroll
-          for (int dj = 0; dj <= pj; ++dj) {
-            const uint32_t code = (uint32_t)((pi - 2 * di + 1) * 3 + (pj - 2 * dj + 1));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) gg[e] += cd[di * 2 + dj][e] == code ? dw[di * 2 + dj][e] : 0.f;
-          }
+        float gg[4], d[4];
+        bn_pool_gather(pi, pj, dw, cd, gg);
 #pragma unroll
         for (int e = 0; e < 4; ++e) d[e] = fmaf(cA[e], gg[e], fmaf(cB[e], xf[e], cC[e]));
         if constexpr (EDGE) {

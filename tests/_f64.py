@@ -220,7 +220,8 @@ def check_scatter(got, base, want, bnd, what, kernel=""):
 # ====================================================================================================================
 # The non-conv kernels: BatchNorm finalize / apply / backward, pooling, the fp32 heads and the losses.
 #
-# Every bound below counts the ROUNDED fp32 operations of the kernel source (ssl_cr_histo_amd/csrc/bn_eltwise.hip, heads.hip) and
+# Every bound below counts the ROUNDED fp32 operations of the kernel source (ssl_cr_histo_amd/csrc/bn_eltwise.hip, heads.hip; the
+# BatchNorm-backward expressions -- coefficients, affine gradients, column fold, pool gather -- stand once, in csrc/bn_bwd.hpp) and
 # charges each one u = 2^-24 times the magnitude it works on; reductions of n terms are charged LAM*sqrt(n)*u of the sum of
 # magnitudes (Higham & Mary, as above).  The counts stand next to the formulas.
 #
@@ -249,10 +250,10 @@ def check_scatter(got, base, want, bnd, what, kernel=""):
 #               the STORED pool output y: y - shift [1], 1/scale [1], the product [1] = 3u * |y - shift|/|scale|, the subtraction [1] =
 #               u * |xm|; its reference is that expression on the stored y, not x - mean.
 # bn_bwd apply  dx = fmaf(cA, g, fmaf(cB, x, cC)): 2 roundings on mag = |cA g| + |cB x| + |sc m0| + |cB mean| (|cC| expanded into its two
-#               terms: where mean/std is large they cancel, and the fp32 rounding of each is what the result carries).  Coefficients:
+#               terms: where mean/std is large they cancel, and the fp32 rounding of each is what the result carries).  Coefficients (bn_bwd_coeffs):
 #               m = (float)sums [1] * (float)(1/count) [1, and 1 for the product] = 3 ; cB = -sc * is * is * m1: 3 + 3 products = 6 ;
 #               sc * m0: 3 + 1 = 4 ; cB * mean: 6 + 1 = 7 ; the subtraction [1] on both.  E = u * (2 mag + 6 |cB x| + 8 (|sc m0| + |cB mean|)).
-#               bn_param_grads: the double product cast to fp32 [1], added onto the existing fp32 value [1]: 2u * (|base| + |term|).
+#               bn_param_grads (bn_bwd_affine_grads): the double product cast to fp32 [1], added onto the existing fp32 value [1]: 2u * (|base| + |term|).
 # heads         linear: bound(want, mag, K, 0, fp32_operands=True), the reduction length K / N / M for forward / dx / dw (dw onto
 #               an existing value: inside EPI).  db: summation over M plus the add onto the existing value.
 # losses        cross-entropy row: d_c = l_c - m [1: rel. |d_c| u in exp], expf [X u], the sum of C terms [(C - 1) u], so

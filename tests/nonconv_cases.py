@@ -43,7 +43,7 @@ STRIDE = [
     ("bn_relu_maxpool", 1, (None, 40, 25, 40), "", "generic form ('256 % cols' != 0), cols = 5, capped grid"),
     ("bn_relu_maxpool", 0, (None, 20, 25, 40), "", "generic form, cols = 10, capped grid"),
     ("bn_relu_maxpool", 1, (None, 40, 25, 56), "", "generic form, cols = 7: m = 7"),
-    ("bn_bwd_apply", 1, (None, 40, 25, 40), "relu_from_x", "direct descriptor (launch_bn_bwd_reduce returns hipErrorInvalidValue for '256 % cols'), cols = 5"),
+    ("bn_bwd_apply", 1, (None, 40, 25, 40), "relu_from_x", "direct descriptor (launch_bn_bwd_reduce returns hipErrorInvalidValue: bn_bwd_reduce_cols, '(256 % cols) != 0'), cols = 5"),
     ("bn_bwd_apply", 0, (None, 20, 25, 40), "yact", "direct descriptor, cols = 10"),
 ]
 
@@ -71,7 +71,7 @@ BN_BWD += [
     ("bn_bwd", 1, (16, 32, 32, 512), "yact", "1024-thread form: 16384 pixels -> blocks = 512, b4 = cdiv(cdiv(16384, 16), 8) = 128 workgroups"),
     ("bn_bwd", 1, (16, 32, 32, 512), "plain", "1024-thread form"),
     ("bn_bwd", 0, (8, 32, 32, 512), "from_x", "1024-thread form, fp32: 8192 pixels -> blocks = 512, b4 = 128"),
-    ("bn_bwd", 0, (4, 15, 13, 64), "pool", "'a.pool_dy' gather in bn_bwd_g, ragged map; apply: bn_bwd_apply_pool_kernel on 2x2 blocks"),
+    ("bn_bwd", 0, (4, 15, 13, 64), "pool", "'a.pool_dy ? run(std::true_type{})': bn_bwd_reduce_kernel<T, NB, POOL = true>, the gather of bn_bwd_g (windows: bn_bwd.hpp), ragged map; apply: bn_bwd_apply_pool_kernel on 2x2 blocks"),
     ("bn_bwd", 1, (4, 15, 13, 64), "pool", "the same in bf16"),
     ("bn_bwd", 0, (4, 16, 16, 64), "pool", "gather form, even map"),
     ("bn_bwd", 1, (4, 16, 16, 64), "pool", "gather form, even map, bf16"),

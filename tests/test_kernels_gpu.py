@@ -582,7 +582,7 @@ def test_stem_wgrad_from_pooled_gradient(shape, split, in_u8, dtype):
     assert torch.equal(sums_a, sums_b)
     # same tile -> workgroup assignment and MFMA order; the only freedom is the order of the fold's fp32 atomics
     close(dw_b, dw_a.cpu(), 2e-6, "fused stem wgrad vs apply + wgrad")
-    close(dg_b, dg_a.cpu(), 1e-6, "dgamma"); close(db_b, db_a.cpu(), 1e-6, "dbeta")
+    assert torch.equal(dg_b, dg_a) and torch.equal(db_b, db_a)       # one arithmetic: bn_bwd_affine_grads
     # and against autograd of bn1 -> relu -> maxpool on the conv output the kernels saw (in bf16 mode the rounded one: the
     # argmax / ReLU pattern of a separately computed fp32 convolution differs in a few per cent of the windows), then conv1's wgrad
     leaf = R.nchw(raw.float().cpu()).requires_grad_(True)
@@ -594,6 +594,46 @@ def test_stem_wgrad_from_pooled_gradient(shape, split, in_u8, dtype):
     close(dw_b, wantw, t, "fused stem wgrad vs autograd")
     close(dg_b, gr.grad, t, "dgamma vs autograd")
     close(db_b, br.grad, t, "dbeta vs autograd")
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+@pytest.mark.parametrize("shape", [(2, 32, 32), (2, 30, 26)])     # conv1 map 16x16 -> pooled 8x8; 15x13 -> 8x7 (ragged)
+def test_bn_param_grads_one_arithmetic(shape, dtype):
+    """dgamma / dbeta are float += (float)(double product) wherever they are formed (bn_bwd_affine_grads, csrc/bn_bwd.hpp): the same
+    bits from sslcr_bn_param_grads, from workgroup 0 of the pool-form and of the plain-form apply pass, and from the fused stem
+    weight-gradient kernel (fp32: stem_wgrad_kernel<POOL>, bf16: stem_wgrad_pool2_kernel).  The buffers start at 0.25: the += counts."""
+    K = _k()
+    N, H, W = shape
+    xin = torch.from_numpy(np.random.RandomState(61).randint(0, 256, (N, 3, H, W), dtype=np.uint8)).to(DEV)
+    w = rnd(62, (64, 3, 7, 7), 0.03)
+    gamma, beta = rnd(63, (64,)).abs() + 0.5, rnd(64, (64,))
+    wp, _ = K.pack_stem(w.to(DEV), dtype)
+    raw, stats = K.stem_conv(xin, wp, want_stats=True)
+    OH, OW = raw.shape[1:3]
+    sc, sh, mean, invstd = K.bn_finalize(stats, N * OH * OW, gamma.to(DEV), beta.to(DEV))
+    pooled, am = K.bn_relu_maxpool(raw, sc, sh)
+    assert tuple(pooled.shape[1:3]) == ((OH + 1) // 2, (OW + 1) // 2)
+    dyp = to_dev(q(rnd(65, tuple(pooled.shape)), dtype), dtype)
+    grads = {}
+
+    def bufs(name):
+        grads[name] = (torch.full((64,), 0.25, device=DEV), torch.full((64,), 0.25, device=DEV))
+        return grads[name]
+    dg, db = bufs("pool-form apply")
+    dx, sums, _ = K.bn_bwd(None, raw, sc, sh, mean, invstd, relu_from_x=True, pool=(dyp, am, pooled), dgamma=dg, dbeta=db)
+    dg, db = bufs("bn_param_grads")
+    K.bn_param_grads(sums, invstd, dg, db)
+    dg, db = bufs("stem_wgrad_pool")
+    dw = torch.zeros((64, 3, 7, 7), dtype=torch.float32, device=DEV)
+    sums_w = K.stem_wgrad_pool(xin, dw, raw, sc, sh, mean, invstd, (dyp, am, pooled), dgamma=dg, dbeta=db)
+    assert torch.equal(sums_w, sums)
+    dg, db = bufs("plain-form apply")
+    K.bn_bwd(dx, raw, sc, sh, mean, invstd, sums=sums, dgamma=dg, dbeta=db)       # a dense gradient, the same statistics and sums
+    want_g, want_b = grads["bn_param_grads"]
+    assert not torch.equal(want_g, torch.full_like(want_g, 0.25)) and not torch.equal(want_b, torch.full_like(want_b, 0.25))
+    for name, (dg, db) in grads.items():
+        assert torch.equal(dg, want_g), f"dgamma: {name} vs bn_param_grads, max diff {(dg - want_g).abs().max().item():.3e}"
+        assert torch.equal(db, want_b), f"dbeta: {name} vs bn_param_grads, max diff {(db - want_b).abs().max().item():.3e}"
 
 
 def test_stem_wgrad_pool_rejects_foreign_descriptors():
