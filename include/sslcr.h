@@ -45,7 +45,8 @@ extern "C" {
  * a new number: tests/test_annotation_cpu.py holds sslcr_version() to 15 by equality, so a caller tests for these entries by symbol.
  * The same holds for sslcr_conv2d_fp8_kernel_name and sslcr_fp8_scale_update (additive; the launches they name or issue are the
  * ones sslcr_conv2d_fp8 and the engine's forward issued before); sslcr_conv2d_fp8 now refuses in_scale without in_shift, a
- * descriptor whose launch read a NULL pointer on the device. */
+ * descriptor whose launch read a NULL pointer on the device.  The ranking entries (sslcr_sort_pairs, sslcr_sort_workspace_bytes,
+ * sslcr_rank_keys, sslcr_auc_counts, sslcr_auc_workspace_bytes) are additive in the same way, again without a new number. */
 int sslcr_version(void);
 const char* sslcr_last_error(void);
 
@@ -806,6 +807,76 @@ typedef struct sslcr_moments_desc {
   int X, Y, L;
 } sslcr_moments_desc;
 int sslcr_region_moments(const sslcr_moments_desc* d, void* stream);
+
+/* ---- Ranking metrics on the device: a radix sort, and from it the exact ROC-AUC counts (csrc/rank.hip).  The Kather main prints
+ *      sklearn's roc_auc_score(targets, scores, multi_class='ovr') (eval_Kather_SSL_CR.py:658).  The area under the ROC curve of one
+ *      column is the share of (positive, negative) pairs the score orders correctly, a tie counting half, so with
+ *          U2 = sum over the positives i and the negatives j of (2 [s_i > s_j] + [s_i = s_j])
+ *      it is U2 / (2 P N): three integers, which the device counts exactly and the host divides once.  All entries are asynchronous
+ *      and use integer arithmetic only (a score is its bit pattern; there is no floating-point operation): two calls give equal bits.
+ *      Work passes between workgroups at launch boundaries only: no kernel waits for another workgroup.  These entries were added
+ *      without a new version number; a caller tells them by their symbols.
+ *
+ *      sslcr_sort_pairs.  A stable least-significant-digit radix sort of B independent rows of n uint32 keys, each with a uint32
+ *      value, ascending by the bits [lo, hi) of the key: ceil((hi - lo) / 8) passes of an 8-bit digit (the last one narrower), each a
+ *      per-tile digit histogram (SSLCR_SORT_TILE keys a workgroup), an exclusive scan of [digit][tile] (SSLCR_RANK_SCAN_TRIP tiles a
+ *      trip, with a carry) and a stable scatter.  Keys equal in [lo, hi) keep their input order.  keys[0] / values[0] hold the input
+ *      and are overwritten; the passes alternate between the two buffers and the result is in keys[p & 1] / values[p & 1], p the
+ *      number of passes (lo == hi: no launch, the input is the result).  workspace: sslcr_sort_workspace_bytes(B, n) bytes of
+ *      scratch (0 for arguments the sort refuses).
+ *      Errors: NULL descriptor or pointers, B outside [1, 65535], n < 1, not 0 <= lo <= hi <= 32, the four buffers not distinct,
+ *      pointers not 4-byte aligned. */
+#define SSLCR_SORT_TILE 4096
+#define SSLCR_RANK_SCAN_TRIP 64
+typedef struct sslcr_sort_desc {
+  uint32_t* keys[2];        /* [B][n] each */
+  uint32_t* values[2];      /* [B][n] each */
+  void* workspace;          /* sslcr_sort_workspace_bytes(B, n) */
+  int B, n, lo, hi;
+} sslcr_sort_desc;
+size_t sslcr_sort_workspace_bytes(int B, int n);
+int sslcr_sort_pairs(const sslcr_sort_desc* d, void* stream);
+
+/*      sslcr_rank_keys.  scores float32 [n][C], row-major as sslcr_predict writes them (C = 1 for a vector or a map), to one sortable
+ *      row per column: with b the bit pattern of scores[i][c], b = 0 if (b << 1) == 0 (so -0 ties with +0, as under a float compare),
+ *          keys[c][i]   = b ^ ((b >> 31) ? 0xFFFFFFFF : 0x80000000)      unsigned order of the keys = the order of the scores
+ *          values[c][i] = target[i] == positive[c] ? 1 : 0               positive NULL: positive[c] = c
+ *      An element with valid[i] == 0 (valid NULL: none) gets the value 2, which sslcr_auc_counts skips.  A NaN score
+ *      ((b & 0x7FFFFFFF) > 0x7F800000) on a valid element is counted into nan[c] (zeroed by this call) and gets the value 2 as well:
+ *      the counts of its column are those of the other elements and claim nothing about it.
+ *      Errors: NULL descriptor, scores, target, keys, values or nan, n < 1, C outside [1, 65535], scores / keys / values not 4-byte or
+ *      target / positive / nan not 8-byte aligned. */
+typedef struct sslcr_rank_keys_desc {
+  const float* scores;      /* [n][C] */
+  const int64_t* target;    /* [n] */
+  const uint8_t* valid;     /* [n] or NULL */
+  const int64_t* positive;  /* [C] or NULL */
+  uint32_t* keys;           /* [C][n] */
+  uint32_t* values;         /* [C][n] */
+  int64_t* nan;             /* [C] */
+  int n, C;
+} sslcr_rank_keys_desc;
+int sslcr_rank_keys(const sslcr_rank_keys_desc* d, void* stream);
+
+/*      sslcr_auc_counts.  keys / values: C rows of n, every row ascending by key (sslcr_sort_pairs of what sslcr_rank_keys wrote).
+ *          counts[c] = (U2, P, N, nan[c])      P / N = the elements with value 1 / 0, U2 as above over them, nan NULL: 0
+ *      A run of equal keys may span any number of workgroups: a positive's pairs are A + N - Z, A the negatives before the head of its
+ *      run and Z those after its tail; the exclusive count of negatives never decreases along the row, so A is its maximum over the run
+ *      heads at or before the element, and Z mirrors it from the other end.  Three launches: per-block partials (SSLCR_SORT_TILE
+ *      elements a block), one scan of the partials (SSLCR_RANK_SCAN_TRIP blocks a trip, with carries), one apply pass that adds each
+ *      block's integer sum.  U2 <= 2 P N < 2^62.  work: sslcr_auc_workspace_bytes(C, n) bytes of scratch.
+ *      Errors: NULL descriptor or keys / values / counts / work, n < 1, C outside [1, 65535], keys / values / work not 4-byte or
+ *      counts / nan not 8-byte aligned. */
+typedef struct sslcr_auc_desc {
+  const uint32_t* keys;     /* [C][n], ascending within a row */
+  const uint32_t* values;   /* [C][n]: 1 positive, 0 negative, anything else skipped */
+  const int64_t* nan;       /* [C] or NULL */
+  int64_t* counts;          /* [C][4] */
+  int32_t* work;            /* sslcr_auc_workspace_bytes(C, n) */
+  int n, C;
+} sslcr_auc_desc;
+size_t sslcr_auc_workspace_bytes(int C, int n);
+int sslcr_auc_counts(const sslcr_auc_desc* d, void* stream);
 
 /* ---- device-side strong augmentation, the colour ops of the reference's RandAugment pool ("next" row f4) on a uint8 batch in HBM.
  *      As with sslcr_weak_augment the random draws stay on the host, in the reference's order (ssl_cr_histo_amd/augment.py);

@@ -103,6 +103,12 @@ EDT_ROW_CELLS = 1024          # SSLCR_EDT_ROW_CELLS
 EdtDesc = _S("EdtDesc", [(k, vp) for k in ("mask", "out", "below", "work")] + [(k, i32) for k in ("X", "Y", "limit", "invert")])
 FillDesc = _S("FillDesc", [(k, vp) for k in ("mask", "out", "labels", "count", "work")] + [(k, i32) for k in ("X", "Y")])
 MomentsDesc = _S("MomentsDesc", [(k, vp) for k in ("labels", "moments")] + [(k, i32) for k in ("X", "Y", "L")])
+SORT_TILE = 4096              # SSLCR_SORT_TILE
+RANK_SCAN_TRIP = 64           # SSLCR_RANK_SCAN_TRIP
+SortDesc = _S("SortDesc", [("keys", vp * 2), ("values", vp * 2), ("workspace", vp)] + [(k, i32) for k in ("B", "n", "lo", "hi")])
+RankKeysDesc = _S("RankKeysDesc", [(k, vp) for k in ("scores", "target", "valid", "positive", "keys", "values", "nan")] +
+                  [("n", i32), ("C", i32)])
+AucDesc = _S("AucDesc", [(k, vp) for k in ("keys", "values", "nan", "counts", "work")] + [("n", i32), ("C", i32)])
 PackDesc = _S("PackDesc", [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("gamma", vp), ("beta", vp), ("rmean", vp),
                            ("rvar", vp), ("eps", f32), ("bias_out", vp)] + [(k, i32) for k in ("K", "C", "R", "S", "dgrad_flip")] + [("scale_out", vp)])
 
@@ -169,6 +175,11 @@ SIGNATURES = {
     "sslcr_edt_squared": (i32, [P(EdtDesc), vp]),
     "sslcr_fill_holes": (i32, [P(FillDesc), vp]),
     "sslcr_region_moments": (i32, [P(MomentsDesc), vp]),
+    "sslcr_sort_workspace_bytes": (sz, [i32, i32]),
+    "sslcr_sort_pairs": (i32, [P(SortDesc), vp]),
+    "sslcr_rank_keys": (i32, [P(RankKeysDesc), vp]),
+    "sslcr_auc_workspace_bytes": (sz, [i32, i32]),
+    "sslcr_auc_counts": (i32, [P(AucDesc), vp]),
     "sslcr_optimizer_step": (i32, [vp, i32, i32, P(OptDesc), vp]),
     "sslcr_optimizer_step_groups": (i32, [vp, i32, i32, P(OptDesc), i32, vp, vp]),
     "sslcr_grad_norm": (i32, [vp, sz, f32, vp, vp, vp]),

@@ -431,6 +431,46 @@ int sslcr_region_moments(const sslcr_moments_desc* d, void* stream) {
   NEED(ALIGNED(d->labels, 3) && ALIGNED(d->moments, 7), "labels / moments alignment");
   return check(launch_region_moments(*d, (hipStream_t)stream), "region_moments");
 }
+// ---- ranking metrics (rank.hip)
+static int64_t rank_tiles(int n) { return ((int64_t)n + SSLCR_SORT_TILE - 1) / SSLCR_SORT_TILE; }
+size_t sslcr_sort_workspace_bytes(int B, int n) {
+  if (B < 1 || B > 65535 || n < 1) return 0;
+  return (size_t)B * 256 * (size_t)(rank_tiles(n) + 1) * sizeof(int);        // hist [B][256][tiles], then tot [B][256]
+}
+int sslcr_sort_pairs(const sslcr_sort_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  NEED(d->B >= 1 && d->B <= 65535, "B outside [1, 65535]");
+  NEED(d->n >= 1, "n < 1");
+  NEED(d->lo >= 0 && d->lo <= d->hi && d->hi <= 32, "not 0 <= lo <= hi <= 32");
+  NEED(d->keys[0] && d->keys[1] && d->values[0] && d->values[1] && d->workspace, "null tensor");
+  NEED(d->keys[0] != d->keys[1] && d->values[0] != d->values[1] && d->keys[0] != d->values[0] && d->keys[0] != d->values[1] &&
+           d->keys[1] != d->values[0] && d->keys[1] != d->values[1], "the four buffers must be distinct");
+  NEED(ALIGNED(d->keys[0], 3) && ALIGNED(d->keys[1], 3) && ALIGNED(d->values[0], 3) && ALIGNED(d->values[1], 3) && ALIGNED(d->workspace, 3),
+       "keys / values / workspace alignment");
+  return check(launch_sort_pairs(*d, (hipStream_t)stream), "sort_pairs");
+}
+int sslcr_rank_keys(const sslcr_rank_keys_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  NEED(d->n >= 1, "n < 1");
+  NEED(d->C >= 1 && d->C <= 65535, "C outside [1, 65535]");
+  NEED(d->scores && d->target && d->keys && d->values && d->nan, "null tensor");
+  NEED(ALIGNED(d->scores, 3) && ALIGNED(d->keys, 3) && ALIGNED(d->values, 3), "scores / keys / values alignment");
+  NEED(ALIGNED(d->target, 7) && ALIGNED(d->positive, 7) && ALIGNED(d->nan, 7), "target / positive / nan alignment");
+  return check(launch_rank_keys(*d, (hipStream_t)stream), "rank_keys");
+}
+size_t sslcr_auc_workspace_bytes(int C, int n) {
+  if (C < 1 || C > 65535 || n < 1) return 0;
+  return (size_t)C * (size_t)rank_tiles(n) * 8 * sizeof(int);
+}
+int sslcr_auc_counts(const sslcr_auc_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  NEED(d->n >= 1, "n < 1");
+  NEED(d->C >= 1 && d->C <= 65535, "C outside [1, 65535]");
+  NEED(d->keys && d->values && d->counts && d->work, "null tensor");
+  NEED(ALIGNED(d->keys, 3) && ALIGNED(d->values, 3) && ALIGNED(d->work, 3), "keys / values / work alignment");
+  NEED(ALIGNED(d->counts, 7) && ALIGNED(d->nan, 7), "counts / nan alignment");
+  return check(launch_auc_counts(*d, (hipStream_t)stream), "auc_counts");
+}
 #undef SQ_SHAPE_OK
 #undef MAP_SHAPE_OK
 #undef ALIGNED

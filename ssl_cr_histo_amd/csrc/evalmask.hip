@@ -7,6 +7,7 @@
 // border pass stores the constant 1: no result depends on the order in which they land.  Work proceeds between workgroups through
 // launch boundaries only; no kernel waits for another workgroup, and every loop states its bound.
 #include "kernels.hpp"
+#include "wave_scan.hpp"
 
 namespace sslcr {
 
@@ -24,28 +25,6 @@ namespace sslcr {
 constexpr int EDT_ROW_CELLS = SSLCR_EDT_ROW_CELLS, EDT_NONE = 0x7fffffff;
 constexpr int EDT_FAR = 1 << 30;                    // "no zero seen": |EDT_FAR| + a coordinate stays inside an int32
 static_assert(EDT_ROW_CELLS == 4 * 256, "one dword per thread and chunk");
-
-// exclusive max-scan over the workgroup's 256 values, in thread order (reverse = false: thread t gets the max over the threads before
-// it) or in reverse thread order (the max over the threads after it); nothing before = -EDT_FAR; *total = the max over all; sh: 4 ints
-__device__ __forceinline__ int block_scan_max(int v, bool reverse, int* sh, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int d = 1; d < 64; d <<= 1) {                // bound: 6 steps
-    const int u = reverse ? __shfl_down(v, d) : __shfl_up(v, d);
-    if (reverse ? lane + d < 64 : lane >= d) v = max(v, u);
-  }
-  if (lane == (reverse ? 0 : 63)) sh[w] = v;        // the wave's total
-  int ex = reverse ? __shfl_down(v, 1) : __shfl_up(v, 1);
-  if (lane == (reverse ? 63 : 0)) ex = -EDT_FAR;
-  __syncthreads();
-  int all = -EDT_FAR;
-  for (int k = 0; k < 4; ++k) {
-    all = max(all, sh[k]);
-    if (reverse ? k > w : k < w) ex = max(ex, sh[k]);
-  }
-  *total = all;
-  __syncthreads();
-  return ex;
-}
 
 // the four mask bytes of the aligned dword at flat address addr; bytes past the end of the array read as "not there"
 __device__ __forceinline__ unsigned mask_dword(const unsigned char* mask, int64_t addr, int64_t n) {
@@ -76,7 +55,7 @@ __global__ __launch_bounds__(256) void edt_rows_kernel(const sslcr_edt_desc a) {
       if (zero[j]) last = y;
     }
     int total;
-    const int before = block_scan_max(last, false, sh, &total);               // the threads before this one ...
+    const int before = block_scan_max(last, false, -EDT_FAR, sh, &total);     // the threads before this one ...
     int seen = max(before, carry);                                           // ... and the chunks before this one
     for (int j = 0; j < 4; ++j) {
       const int y = y0 + j;
@@ -98,7 +77,7 @@ __global__ __launch_bounds__(256) void edt_rows_kernel(const sslcr_edt_desc a) {
       if (zero[j]) first = -y;
     }
     int total;
-    const int after = block_scan_max(first, true, sh, &total);
+    const int after = block_scan_max(first, true, -EDT_FAR, sh, &total);
     int seen = max(after, carry);
     for (int j = 3; j >= 0; --j) {
       const int y = y0 + j;
@@ -204,11 +183,6 @@ hipError_t launch_fill_holes(const sslcr_fill_desc& a, hipStream_t st) {
 // registers (lane q holds moment q), so a stretch of one component costs six int64 atomics per wave and not six per cell.
 // Bounds: X^2 + Y^2 < 2^31 gives x, y < 46341 and x^2, y^2, x y < 2^31; a component has fewer than 2^31 cells: every sum < 2^62.
 constexpr int MOM_STEPS = 16;
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);                   // bound: 6 steps; every lane ends with the total
-  return v;
-}
 
 __global__ __launch_bounds__(256) void region_moments_kernel(const sslcr_moments_desc a) {
   const int64_t n = (int64_t)a.X * a.Y;

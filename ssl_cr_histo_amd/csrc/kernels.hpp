@@ -223,6 +223,10 @@ hipError_t launch_lesion_hits(const sslcr_hits_desc& a, hipStream_t st);
 hipError_t launch_edt_squared(const sslcr_edt_desc& a, hipStream_t st);
 hipError_t launch_fill_holes(const sslcr_fill_desc& a, hipStream_t st);
 hipError_t launch_region_moments(const sslcr_moments_desc& a, hipStream_t st);
+// rank.hip
+hipError_t launch_sort_pairs(const sslcr_sort_desc& a, hipStream_t st);
+hipError_t launch_rank_keys(const sslcr_rank_keys_desc& a, hipStream_t st);
+hipError_t launch_auc_counts(const sslcr_auc_desc& a, hipStream_t st);
 // augment.hip
 hipError_t launch_weak_augment(const sslcr_weak_aug_desc& a, hipStream_t st);
 hipError_t launch_hed_colour(const sslcr_colour_aug_desc& a, hipStream_t st);

@@ -26,6 +26,12 @@ lesions, the map's non-maximum suppression into detections, the lesion under eac
 distance transform, the hole filling, the lesions' labels and moments (csrc/evalmask.hip) -- and the isolated-tumour-cell list from
 the major axis lengths; ``lesion_scores(..., evaluation=)`` scores against it.
 
+Ranking metrics.  The Kather main also prints ``roc_auc_score(targets, scores, multi_class='ovr')`` (eval_Kather_SSL_CR.py:658).
+``roc_auc`` counts every column's correctly ordered (positive, negative) pairs exactly on the device -- one radix sort per column, all
+columns in one call, ties resolved over runs of equal scores (csrc/rank.hip) -- and divides once on the host; ``map_auc`` is the same
+over the tissue cells of a probability map, ``AucMeter`` the batch-by-batch form.  ``icc`` / ``bpq_icc`` are the intraclass correlation
+tables the BreastPathQ mains print (eval_BreastPathQ_SSL_CR.py:570-599), in host float64: their input is already on the host.
+
 Metrics.  The Kather mains build sklearn's confusion matrix and a weighted F1 from what ``test()`` returns
 (eval_Kather_SSL_CR.py:646-658, eval_Kather_SSL.py:519-530).  ``ConfusionMeter`` counts the same matrix on the device, batch by batch,
 with integer atomics; ``metrics_from_confusion`` derives the figures from it in host float64.
@@ -368,3 +374,196 @@ def metrics_from_confusion(cm):
     return dict(accuracy=float(_div(tp.sum(), total)), precision=precision, recall=recall, f1=f1, support=support,
                 weighted_f1=float(_div((f1 * support).sum(), support.sum())),
                 multilabel=np.stack([np.stack([tn, fp], 1), np.stack([fn, tp], 1)], 1))
+
+
+# ---- ranking metrics: exact ROC-AUC from device counts, intraclass correlation on the host
+_ONE_CLASS = "Only one class present in y_true. ROC AUC score is not defined in that case."
+_CLASS_COUNT = "Number of classes in y_true not equal to the number of columns in 'y_score'"
+
+
+def auc_from_counts(counts, multi=False, average="macro"):
+    """the host half of ``roc_auc``: integer counts [C, 4] = (U2, P, N, nan), what ``kernels.auc_counts`` returns, -> the figure, or
+    sklearn's ValueError.  multi: the one-vs-rest reading of C columns (False: one binary column)."""
+    rows = [[int(v) for v in r] for r in np.asarray(counts).reshape(-1, 4).tolist()]
+    if any(r[3] for r in rows):
+        raise ValueError("Input contains NaN.")
+    if multi:
+        # under one-vs-rest every valid element is a positive of exactly one column iff its target lies in range(C)
+        if any(r[1] == 0 or r[2] == 0 for r in rows) or sum(r[1] for r in rows) != rows[0][1] + rows[0][2]:
+            raise ValueError(_CLASS_COUNT)
+    elif rows[0][1] == 0 or rows[0][2] == 0:
+        raise ValueError(_ONE_CLASS)
+    auc = np.array([u2 / (2 * p * n) for u2, p, n, _ in rows], dtype=np.float64)      # Python integers: one correctly rounded division
+    if not multi:
+        return float(auc[0])
+    if average is None:
+        return auc
+    if average == "macro":
+        return float(np.mean(auc))
+    return float(np.average(auc, weights=np.array([r[1] for r in rows], dtype=np.float64)))
+
+
+def _auc_device(*ts):
+    dev = next((t.device for t in ts if torch.is_tensor(t) and t.is_cuda), None)
+    return dev if dev is not None else torch.device("cuda")
+
+
+def roc_auc(scores, target, *, multi_class="raise", average="macro", valid=None):
+    """sklearn's ``roc_auc_score(target, scores, multi_class=, average=)`` from exact device counts: ``kernels.auc_counts`` (keys, one
+    radix sort of all columns, the pair counts), ONE copy of the int64 [C, 4] counts, then per column ``U2 / (2 P N)`` as a Python
+    integer true division -- the correctly rounded value of the exact area, where sklearn sums a trapezoid in float64 (the two differ
+    by at most n 2^-53).  scores: [n] (or [n, 1]) scores class 1 against the rest, as sklearn's binary case does; [n, C], C >= 2, is
+    multi-class and needs ``multi_class='ovr'``: column c scores class c, and ``average`` is 'macro' (``np.mean``), 'weighted'
+    (``np.average`` with the class counts as weights) or None (the per-class float64 vector).  The rows are NOT checked to sum to 1
+    (sklearn refuses such scores): they are sslcr_predict's softmax.  target: [n] integers; valid: [n] flags, zero = leave the element
+    out (None = all in).  Device or host inputs: host ones are uploaded (scores as float32).
+    ValueError, with sklearn's wording: a NaN score; a column without a positive or without a negative ('Only one class present': sklearn raised it up to 1.5 and
+    warns and returns nan since; here it stays an error);
+    multi-class scores without ``multi_class='ovr'``; under 'ovr', a class of range(C) absent from the targets or a target outside it."""
+    dev = _auc_device(scores, target, valid)
+    sc = torch.as_tensor(scores)
+    if sc.dim() == 2 and sc.shape[1] == 1:
+        sc = sc.reshape(-1)
+    if sc.dim() not in (1, 2) or sc.numel() < 1:
+        raise ValueError(f"roc_auc: scores [n] or [n, C] expected, got {tuple(sc.shape)}")
+    multi = sc.dim() == 2
+    if multi and multi_class != "ovr":
+        if multi_class == "raise":
+            raise ValueError("multi_class must be in ('ovo', 'ovr')")
+        raise ValueError(f"roc_auc: multi_class = {multi_class!r}: only one-vs-rest ('ovr') is counted")
+    if average not in ("macro", "weighted", None):
+        raise ValueError(f"roc_auc: average = {average!r} outside ('macro', 'weighted', None)")
+    sc = sc.to(dev, torch.float32)
+    tg = torch.as_tensor(target)
+    if tg.is_floating_point() or tg.dtype == torch.bool:
+        tg = tg.to(torch.int64)
+    tg = tg.reshape(-1).to(dev)
+    if tg.numel() != sc.shape[0]:
+        raise ValueError(f"roc_auc: {sc.shape[0]} scores and {tg.numel()} targets")
+    if valid is not None:
+        valid = torch.as_tensor(np.asarray(valid) != 0 if not torch.is_tensor(valid) else valid).reshape(-1).to(dev).contiguous()
+        if valid.dtype not in (torch.bool, torch.uint8):
+            valid = valid != 0
+    counts = K.auc_counts(sc.contiguous(), tg.contiguous(), positive=None if multi else [1], valid=valid)
+    return auc_from_counts(counts.cpu().numpy(), multi, average)
+
+
+def map_auc(probs_map, truth, tissue):
+    """The ROC-AUC of a probability map against the truth mask over the tissue cells, the sibling of ``map_scores``: every cell with
+    ``tissue != 0`` is one sample, its score the map's float32 value, its class ``truth != 0``.  Inputs as for ``map_scores`` (device
+    tensors, or host arrays that are uploaded; the map as float32).  One copy of four integers; ``roc_auc``'s errors."""
+    dev = _auc_device(probs_map, truth, tissue)
+    pm = torch.as_tensor(probs_map).to(dev, torch.float32).contiguous()
+    masks = [torch.as_tensor(np.asarray(m) != 0 if not torch.is_tensor(m) else m).to(dev).contiguous() for m in (truth, tissue)]
+    if masks[0].shape != pm.shape or masks[1].shape != pm.shape:
+        raise ValueError(f"map_auc: map {tuple(pm.shape)}, truth {tuple(masks[0].shape)} and tissue {tuple(masks[1].shape)} differ in shape")
+    return roc_auc(pm.reshape(-1), (masks[0].reshape(-1) != 0).to(torch.int64), valid=masks[1].reshape(-1) != 0)
+
+
+class AucMeter:
+    """The counterpart of ``ConfusionMeter`` for the ROC-AUC: ``update(scores, target)`` keeps one batch on the device (scores float32
+    [n, C], or [n] for C = 1; the tensors are kept, not copied: hand it tensors nobody overwrites, as sslcr_predict's outputs are) without
+    a sync; ``compute(**kw)`` is ``roc_auc`` over everything kept -- the area is not a sum over batches, so the sort happens here."""
+
+    def __init__(self, C, device):
+        if not 1 <= int(C) <= 65535:
+            raise ValueError(f"AucMeter: C = {C} outside [1, 65535]")
+        self.C, self.device = int(C), torch.device(device)
+        self.reset()
+
+    def update(self, scores, target):
+        sc = torch.as_tensor(scores).to(self.device, torch.float32)
+        sc = sc.reshape(-1) if self.C == 1 else sc
+        if self.C > 1 and (sc.dim() != 2 or sc.shape[1] != self.C):
+            raise ValueError(f"AucMeter: scores [n, {self.C}] expected, got {tuple(sc.shape)}")
+        tg = torch.as_tensor(target).reshape(-1).to(self.device)
+        if tg.numel() != sc.shape[0]:
+            raise ValueError(f"AucMeter: {sc.shape[0]} scores and {tg.numel()} targets")
+        self.scores.append(sc)
+        self.targets.append(tg)
+        return self
+
+    def reset(self):
+        self.scores, self.targets = [], []
+
+    def compute(self, **kw):
+        if not self.scores:
+            raise ValueError("AucMeter: nothing to compute")
+        return roc_auc(torch.cat(self.scores), torch.cat(self.targets), **kw)
+
+
+ICC_TYPES = ("ICC1", "ICC2", "ICC3", "ICC1k", "ICC2k", "ICC3k")
+ICC_DESCRIPTIONS = ("Single raters absolute", "Single random raters", "Single fixed raters", "Average raters absolute",
+                    "Average random raters", "Average fixed raters")
+
+
+def icc_mean_squares(ratings):
+    """the mean squares of the two-way layout of ``ratings`` [n targets, k raters], float64, two-pass (sums of squared deviations from
+    the means, never of raw squares) -> dict: ``n``, ``k``, ``MSR`` (between targets, n - 1), ``MSW`` (within targets, n (k - 1)),
+    ``MSC`` (between raters, k - 1), ``MSE`` (residual, (n - 1)(k - 1))."""
+    x = np.asarray(torch.as_tensor(ratings).cpu() if torch.is_tensor(ratings) else ratings, dtype=np.float64)
+    if x.ndim != 2 or x.shape[0] < 2 or x.shape[1] < 2 or not np.isfinite(x).all():
+        raise ValueError(f"icc: finite ratings [n >= 2 targets, k >= 2 raters] expected, got shape {x.shape}")
+    n, k = x.shape
+    grand, rows, cols = x.mean(), x.mean(1, keepdims=True), x.mean(0, keepdims=True)
+    return dict(n=n, k=k, MSR=float(k * ((rows - grand) ** 2).sum() / (n - 1)), MSW=float(((x - rows) ** 2).sum() / (n * (k - 1))),
+                MSC=float(n * ((cols - grand) ** 2).sum() / (k - 1)), MSE=float(((x - rows - cols + grand) ** 2).sum() / ((n - 1) * (k - 1))))
+
+
+def icc(ratings):
+    """The six intraclass correlations of Shrout & Fleiss (1979) for ``ratings`` [n targets, k raters] in host float64, no device code:
+    from the two-way mean squares (``icc_mean_squares``),
+        ICC1 = (MSR - MSW) / (MSR + (k - 1) MSW)                           ICC1k = (MSR - MSW) / MSR
+        ICC2 = (MSR - MSE) / (MSR + (k - 1) MSE + k (MSC - MSE) / n)       ICC2k = (MSR - MSE) / (MSR + (MSC - MSE) / n)
+        ICC3 = (MSR - MSE) / (MSR + (k - 1) MSE)                           ICC3k = (MSR - MSE) / MSR
+    -> dict of arrays in the row order of ``pingouin.intraclass_corr``: ``Type``, ``Description``, ``ICC``, ``F`` (MSR / MSW for the
+    two ICC1 rows, MSR / MSE for the others), ``df1`` = n - 1, ``df2`` (n (k - 1), resp. (n - 1)(k - 1)), ``pval`` (the F test's upper
+    tail) and ``CI95`` [6, 2].  ``pval`` and ``CI95`` need ``scipy.stats``, imported here when it is there; NaN otherwise.
+    PARITY UNPINNED against pingouin, which this project never had to compare against: pinned are the mean squares and the six
+    values against a literal restatement and against Shrout & Fleiss's own table (tests/test_auc_cpu.py); ``CI95`` follows the
+    confidence limits of Shrout & Fleiss / McGraw & Wong as pingouin states them, from memory of its source, and is pinned by nothing."""
+    m = icc_mean_squares(ratings)
+    n, k, MSR, MSW, MSC, MSE = m["n"], m["k"], m["MSR"], m["MSW"], m["MSC"], m["MSE"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        MSR_, MSW_, MSC_, MSE_ = (np.float64(v) for v in (MSR, MSW, MSC, MSE))
+        values = np.array([(MSR_ - MSW_) / (MSR_ + (k - 1) * MSW_), (MSR_ - MSE_) / (MSR_ + (k - 1) * MSE_ + k * (MSC_ - MSE_) / n),
+                           (MSR_ - MSE_) / (MSR_ + (k - 1) * MSE_), (MSR_ - MSW_) / MSR_, (MSR_ - MSE_) / (MSR_ + (MSC_ - MSE_) / n),
+                           (MSR_ - MSE_) / MSR_], dtype=np.float64)
+        f1, f3 = MSR_ / MSW_, MSR_ / MSE_
+        F = np.array([f1, f3, f3, f1, f3, f3], dtype=np.float64)
+        df1 = np.full(6, n - 1, dtype=np.int64)
+        dfw, dfe = n * (k - 1), (n - 1) * (k - 1)
+        df2 = np.array([dfw, dfe, dfe, dfw, dfe, dfe], dtype=np.int64)
+        pval, ci = np.full(6, np.nan), np.full((6, 2), np.nan)
+        try:
+            from scipy.stats import f as fdist
+        except ImportError:
+            fdist = None
+        if fdist is not None:
+            pval = fdist.sf(F, df1, df2)
+            q = 0.975
+            f1l, f1u = f1 / fdist.ppf(q, n - 1, dfw), f1 * fdist.ppf(q, dfw, n - 1)
+            f3l, f3u = f3 / fdist.ppf(q, n - 1, dfe), f3 * fdist.ppf(q, dfe, n - 1)
+            icc2, fc = values[1], MSC_ / MSE_
+            vn = dfe * (k * icc2 * fc + n * (1 + (k - 1) * icc2) - k * icc2) ** 2
+            vd = (n - 1) * k ** 2 * icc2 ** 2 * fc ** 2 + (n * (1 + (k - 1) * icc2) - k * icc2) ** 2
+            v = vn / vd
+            f2u, f2l = fdist.ppf(q, n - 1, v), fdist.ppf(q, v, n - 1)
+            l2 = n * (MSR_ - f2u * MSE_) / (f2u * (k * MSC_ + (k * n - k - n) * MSE_) + n * MSR_)
+            u2 = n * (f2l * MSR_ - MSE_) / (k * MSC_ + (k * n - k - n) * MSE_ + n * f2l * MSR_)
+            ci = np.array([[(f1l - 1) / (f1l + k - 1), (f1u - 1) / (f1u + k - 1)], [l2, u2],
+                           [(f3l - 1) / (f3l + k - 1), (f3u - 1) / (f3u + k - 1)], [1 - 1 / f1l, 1 - 1 / f1u],
+                           [l2 * k / (1 + l2 * (k - 1)), u2 * k / (1 + u2 * (k - 1))], [1 - 1 / f3l, 1 - 1 / f3u]], dtype=np.float64)
+    return dict(Type=np.array(ICC_TYPES), Description=np.array(ICC_DESCRIPTIONS), ICC=values, F=F, df1=df1, df2=df2, pval=pval, CI95=ci)
+
+
+def bpq_icc(outputs, targetsA, targetsB):
+    """The three tables the BreastPathQ mains print after ``test()`` (eval_BreastPathQ_SSL_CR.py:570-599, eval_BreastPathQ_SSL.py):
+    the model against pathologist A, against pathologist B, and A against B, every image one target and the pair its two raters --
+    ``icc`` of the [n, 2] stacks.  outputs / targetsA / targetsB: [n], what ``steps.bpq_test`` returns (CPU tensors or arrays).
+    -> dict ``{"MA": ..., "MB": ..., "AB": ...}`` of ``icc`` dicts.  PARITY UNPINNED against pingouin (see ``icc``)."""
+    cols = [np.asarray(torch.as_tensor(v).cpu() if torch.is_tensor(v) else v, dtype=np.float64).reshape(-1) for v in (outputs, targetsA, targetsB)]
+    if len({len(c) for c in cols}) != 1:
+        raise ValueError(f"bpq_icc: {[len(c) for c in cols]} values in outputs / targetsA / targetsB")
+    m, a, b = cols
+    return dict(MA=icc(np.stack([m, a], 1)), MB=icc(np.stack([m, b], 1)), AB=icc(np.stack([a, b], 1)))

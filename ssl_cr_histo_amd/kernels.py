@@ -1114,6 +1114,113 @@ def region_moments(labels, n):
     return out
 
 
+SORT_TILE = L.SORT_TILE             # keys one workgroup handles per radix pass; also the elements of one auc_counts block
+RANK_SCAN_TRIP = L.RANK_SCAN_TRIP   # tiles (sort_pairs) / blocks (auc_counts) one trip of the partial scan covers; a carry joins the trips
+
+
+def _rows_u32(name, t):
+    if not t.is_cuda or t.dim() not in (1, 2) or t.numel() < 1 or t.dtype not in (torch.uint32, torch.int32):
+        raise L.SslcrError(f"{name}: a non-empty device uint32 (or int32, read as uint32) tensor [n] or [B, n] expected (no CPU fallback)")
+    if (t.shape[0] if t.dim() == 2 else 1) > 65535 or t.shape[-1] >= 1 << 31:
+        raise L.SslcrError(f"{name}: at most 65535 rows of fewer than 2^31 keys")
+    return t.contiguous()
+
+
+def sort_workspace(B, n, device):
+    """the scratch ``sort_pairs`` needs for B rows of n keys (sslcr_sort_workspace_bytes), as a device int32 tensor"""
+    return torch.empty(L.lib().sslcr_sort_workspace_bytes(int(B), int(n)) // 4, dtype=torch.int32, device=device)
+
+
+def sort_pairs(keys, values=None, *, bits=(0, 32), workspace=None):
+    """-> ``(keys, values)`` sorted ascending by the bits ``[lo, hi)`` of the keys, every row on its own: a stable LSD radix sort
+    (sslcr_sort_pairs; 3 launches per 8-bit digit, the row in the grid).  keys: device uint32 [n] or [B, n] (int32 is read as its
+    bits); values: the same shape, uint32 / int32, or None = the index within the row (the stable ``argsort``).  Keys equal in the bit
+    range keep their input order; two calls give equal bits.  The inputs are left as they were (the sort works on a copy and a second
+    buffer); workspace: ``sort_workspace(B, n, device)`` to reuse across calls.  Results come back as uint32.  No sync."""
+    keys = _rows_u32("sort_pairs", keys)
+    shape = keys.shape
+    B, n = (shape[0], shape[1]) if keys.dim() == 2 else (1, shape[0])
+    lo, hi = int(bits[0]), int(bits[1])
+    if not 0 <= lo <= hi <= 32:
+        raise L.SslcrError(f"sort_pairs: bits = ({lo}, {hi}) outside 0 <= lo <= hi <= 32")
+    dev = keys.device
+    if values is None:
+        vals = torch.arange(n, dtype=torch.int32, device=dev).repeat(B)
+    else:
+        values = _rows_u32("sort_pairs", values)
+        if values.shape != shape or values.device != dev:
+            raise L.SslcrError(f"sort_pairs: values {list(values.shape)} must match keys {list(shape)} on one device")
+        vals = values.clone()
+    k = [keys.clone().view(torch.int32).reshape(-1), None]
+    v = [vals.view(torch.int32).reshape(-1), None]
+    k[1], v[1] = torch.empty_like(k[0]), torch.empty_like(v[0])
+    if workspace is None:
+        workspace = sort_workspace(B, n, dev)
+    if workspace.device != dev or workspace.numel() * workspace.element_size() < L.lib().sslcr_sort_workspace_bytes(B, n):
+        raise L.SslcrError("sort_pairs: workspace too small or on another device (sort_workspace(B, n, device))")
+    d = L.SortDesc((L.vp * 2)(k[0].data_ptr(), k[1].data_ptr()), (L.vp * 2)(v[0].data_ptr(), v[1].data_ptr()), L.ptr(workspace), B, n, lo, hi)
+    L.check(L.lib().sslcr_sort_pairs(d, L.stream_ptr()))
+    at = ((hi - lo + 7) // 8) & 1
+    return k[at].view(torch.uint32).reshape(shape), v[at].view(torch.uint32).reshape(shape)
+
+
+def rank_keys(scores, target, *, positive=None, valid=None):
+    """-> ``(keys, values, nan)``: device uint32 [C, n], uint32 [C, n], int64 [C] (sslcr_rank_keys, one launch).  scores: device float32
+    [n, C] or [n] (C = 1); target: device integer [n]; positive: the class column c scores, C integers (None = ``arange(C)``); valid:
+    device uint8 / bool [n], zero = leave the element out (None = all in).  ``keys[c]`` orders as ``scores[:, c]`` does under float
+    compares (-0 ties with +0); ``values[c]`` is 1 where ``target == positive[c]``, else 0, and 2 on an element left out or NaN;
+    ``nan[c]`` counts the NaN scores among the valid elements.  No sync."""
+    _chk(scores, target)
+    if scores.dtype != torch.float32 or scores.dim() not in (1, 2) or scores.numel() < 1:
+        raise L.SslcrError("rank_keys: non-empty float32 scores [n] or [n, C] expected")
+    scores = scores.contiguous()
+    n, Cn = scores.shape[0], (scores.shape[1] if scores.dim() == 2 else 1)
+    dev = scores.device
+    if target.is_floating_point() or target.numel() != n or target.device != dev:
+        raise L.SslcrError(f"rank_keys: {n} integer targets on the scores' device expected")
+    target = target.reshape(-1).to(torch.int64).contiguous()
+    if not 1 <= Cn <= 65535 or n >= 1 << 31:
+        raise L.SslcrError(f"rank_keys: C = {Cn} outside [1, 65535] or n = {n} >= 2^31")
+    if positive is not None:
+        positive = torch.as_tensor(positive, dtype=torch.int64).reshape(-1).to(dev).contiguous()
+        if positive.numel() != Cn:
+            raise L.SslcrError(f"rank_keys: {positive.numel()} positive classes for {Cn} columns")
+    if valid is not None:
+        _chk(valid)
+        if valid.dtype == torch.bool:
+            valid = valid.view(torch.uint8)
+        if valid.dtype != torch.uint8 or valid.numel() != n or valid.device != dev:
+            raise L.SslcrError(f"rank_keys: valid must be {n} uint8 / bool flags on the scores' device")
+        valid = valid.reshape(-1).contiguous()
+    keys = torch.empty((Cn, n), dtype=torch.int32, device=dev)
+    values = torch.empty((Cn, n), dtype=torch.int32, device=dev)
+    nan = torch.empty(Cn, dtype=torch.int64, device=dev)
+    d = L.RankKeysDesc(L.ptr(scores), L.ptr(target), L.ptr(valid), L.ptr(positive), L.ptr(keys), L.ptr(values), L.ptr(nan), n, Cn)
+    L.check(L.lib().sslcr_rank_keys(d, L.stream_ptr()))
+    return keys.view(torch.uint32), values.view(torch.uint32), nan
+
+
+def auc_counts(scores, target, *, positive=None, valid=None):
+    """-> device int64 [C, 4] = ``(U2, P, N, nan)`` per column: P / N the valid positives / negatives, ``U2 = sum over positives i and
+    negatives j of 2 [s_i > s_j] + [s_i == s_j]`` exactly, so the column's ROC-AUC is ``U2 / (2 P N)``; nan = the valid elements with a
+    NaN score, which are in none of the other three.  ``rank_keys``, ``sort_pairs`` of the C rows in one call, then sslcr_auc_counts
+    (block partials, one scan, one apply pass); integer arithmetic throughout, two calls give equal bits.  Arguments as ``rank_keys``.
+    No sync."""
+    keys, values, nan = rank_keys(scores, target, positive=positive, valid=valid)
+    Cn, n = keys.shape
+    # the sort's second buffers and result: rank_keys' own outputs are the first buffers, nothing is cloned
+    k = [keys.view(torch.int32), torch.empty((Cn, n), dtype=torch.int32, device=keys.device)]
+    v = [values.view(torch.int32), torch.empty((Cn, n), dtype=torch.int32, device=keys.device)]
+    ws = sort_workspace(Cn, n, keys.device)
+    d = L.SortDesc((L.vp * 2)(k[0].data_ptr(), k[1].data_ptr()), (L.vp * 2)(v[0].data_ptr(), v[1].data_ptr()), L.ptr(ws), Cn, n, 0, 32)
+    L.check(L.lib().sslcr_sort_pairs(d, L.stream_ptr()))      # 4 passes: the result is back in the first buffers
+    counts = torch.empty((Cn, 4), dtype=torch.int64, device=keys.device)
+    work = torch.empty(L.lib().sslcr_auc_workspace_bytes(Cn, n) // 4, dtype=torch.int32, device=keys.device)
+    a = L.AucDesc(L.ptr(k[0]), L.ptr(v[0]), L.ptr(nan), L.ptr(counts), L.ptr(work), n, Cn)
+    L.check(L.lib().sslcr_auc_counts(a, L.stream_ptr()))
+    return counts
+
+
 def grad_norm(flat, max_norm=float("inf")):
     """-> device tensor [norm, coef] for a 1-D fp32 tensor (any length, any 4-byte-aligned view): its 2-norm, summed in double in a
     fixed order, and min(1, max_norm / (norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_'s two numbers (sslcr_grad_norm).  No sync."""

@@ -612,7 +612,26 @@ def kather_sup_validate(args, model, classifier, val_loader, criterion, epoch):
 
 
 # ------------------------------------------------------------------------------------------------ test() of the four eval scripts
-_last_test = {"confusion": None}
+_last_test = {"confusion": None, "scores": None, "targets": None, "auc": {}}
+
+
+def _keep_scores(scores, targets):
+    """the device tensors ``last_test_auc`` sorts when somebody asks (None: the test had no class scores)"""
+    _last_test["scores"], _last_test["targets"], _last_test["auc"] = scores, targets, {}
+
+
+def last_test_auc(average="macro"):
+    """``sklearn.metrics.roc_auc_score(final_targets, final_pred_score, multi_class='ovr', average=average)`` of the most recent
+    ``kather_cr_test`` call (eval_Kather_SSL_CR.py:658), from the scores and targets that call left on the device:
+    ``inference.roc_auc`` on the first call (its launches, one copy of 4 C integers), the cached value afterwards.  The test itself
+    launches and copies nothing for it.  average: 'macro', 'weighted' or None (the per-class vector).  None after a ``bpq_*_test`` or a
+    test without scores (``kather_sup_test``); ``camelyon16_test`` leaves it as it was.  ``roc_auc``'s ValueErrors pass through."""
+    if _last_test["scores"] is None:
+        return None
+    if average not in _last_test["auc"]:
+        from .inference import roc_auc
+        _last_test["auc"][average] = roc_auc(_last_test["scores"], _last_test["targets"], multi_class="ovr", average=average)
+    return _last_test["auc"][average]
 
 
 def last_test_confusion():
@@ -687,6 +706,7 @@ def _bpq_test_tta(args, net, eng, test_loader, codes):
         targets_b.append(targetB)
         _maybe_print(args, batch_idx, "Test", 0, _len(test_loader), t0, meters)
     _last_test["confusion"] = None
+    _keep_scores(None, None)
     return tuple(torch.cat(v).detach().to("cpu") for v in (outputs, feats, targets_a, targets_b))
 
 
@@ -712,6 +732,7 @@ def _bpq_test(args, model, classifier, test_loader, where):
         targets_b.append(targetB)
         _maybe_print(args, batch_idx, "Test", 0, _len(test_loader), t0, meters)
     _last_test["confusion"] = None
+    _keep_scores(None, None)
     return tuple(torch.cat(v).detach().to("cpu") for v in (outputs, feats, targets_a, targets_b))
 
 
@@ -759,10 +780,13 @@ def _cls_test(args, model, classifier, test_loader, want_scores):
         if want_scores:
             scores.append(p["scores"])
         _maybe_print(args, batch_idx, "Test", 0, _len(test_loader), t0, meters)
-    out = [torch.cat(preds).to("cpu"), torch.cat(targets).to("cpu")]
+    all_targets = torch.cat(targets)
+    out = [torch.cat(preds).to("cpu"), all_targets.to("cpu")]
     if want_scores:
-        out.append(torch.cat(scores).to("cpu"))
+        all_scores = torch.cat(scores)
+        out.append(all_scores.to("cpu"))
     _last_test["confusion"] = confusion.to("cpu")
+    _keep_scores(all_scores if want_scores else None, all_targets if want_scores else None)    # references, for last_test_auc()
     return tuple(out)
 
 
