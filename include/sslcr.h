@@ -46,7 +46,9 @@ extern "C" {
  * The same holds for sslcr_conv2d_fp8_kernel_name and sslcr_fp8_scale_update (additive; the launches they name or issue are the
  * ones sslcr_conv2d_fp8 and the engine's forward issued before); sslcr_conv2d_fp8 now refuses in_scale without in_shift, a
  * descriptor whose launch read a NULL pointer on the device.  The ranking entries (sslcr_sort_pairs, sslcr_sort_workspace_bytes,
- * sslcr_rank_keys, sslcr_auc_counts, sslcr_auc_workspace_bytes) are additive in the same way, again without a new number. */
+ * sslcr_rank_keys, sslcr_auc_counts, sslcr_auc_workspace_bytes) are additive in the same way, again without a new number, and so
+ * are the resize entries (sslcr_resample, sslcr_resample_plan, sslcr_resample_coeffs, sslcr_resample_ksize,
+ * sslcr_resample_table_ok). */
 int sslcr_version(void);
 const char* sslcr_last_error(void);
 
@@ -877,6 +879,115 @@ typedef struct sslcr_auc_desc {
 } sslcr_auc_desc;
 size_t sslcr_auc_workspace_bytes(int C, int n);
 int sslcr_auc_counts(const sslcr_auc_desc* d, void* stream);
+
+/* ---- Pillow-exact image resize on the device (csrc/resample.hip): Image.resize(size, resample, box) of an 8-bit L or RGB image,
+ *      byte for byte, for a whole batch in HBM.  Replaces the transforms.Resize(size=args.image_size) on a PIL image that every
+ *      BreastPathQ validation / test patch passes through on the host (eval_BreastPathQ_SSL_CR.py:325,365, eval_BreastPathQ_SSL.py:290,
+ *      319, the __getitem__ at dataset.py:575-599).  Additive, again WITHOUT a new version number: a caller tests for sslcr_resample,
+ *      sslcr_resample_plan, sslcr_resample_coeffs, sslcr_resample_ksize and sslcr_resample_table_ok by symbol.
+ *
+ *      The definition is Pillow's Resample.c (pinned to Pillow 12.2.0 by tests/test_resize_cpu.py).  Per axis, with inSize the source
+ *      length, [in0, in1) the box along the axis, outSize the target length and the filter f of support s --
+ *        BOX      s = 0.5   1 if -0.5 < x <= 0.5 else 0
+ *        BILINEAR s = 1     1 - |x|
+ *        HAMMING  s = 1     sin(pi x) / (pi x) * (0.54f + 0.46f * cos(pi x)), 1 at x = 0   (0.54f, 0.46f: the float32 constants
+ *                           Resample.c spells, widened to double)
+ *        BICUBIC  s = 2     a = -0.5: ((a + 2) x - (a + 3)) x^2 + 1 for |x| < 1, (((x - 5) x + 8) x - 4) a for |x| < 2
+ *        LANCZOS  s = 3     sinc(x) sinc(x / 3) on -3 <= x < 3
+ *      -- everything in double, in this order:
+ *        scale = filterscale = (in1 - in0) / outSize;  if (filterscale < 1) filterscale = 1
+ *        support = s * filterscale;  ksize = 2 * (int)ceil(support) + 1;  ss = 1 / filterscale
+ *        for xx in 0 .. outSize - 1:
+ *          center = in0 + (xx + 0.5) * scale
+ *          xmin = max((int)(center - support + 0.5), 0);  xmax = min((int)(center + support + 0.5), inSize) - xmin
+ *          w[x] = f((x + xmin - center + 0.5) * ss), x in 0 .. xmax - 1;  ww = w[0] + w[1] + ... left to right;  if (ww != 0) w[x] /= ww
+ *          k[x] = (int)(0.5 + w[x] * 2^22) if w[x] >= 0 else (int)(-0.5 + w[x] * 2^22)          (truncation toward zero)
+ *          bounds[xx] = (xmin, xmax)
+ *      A pass along an axis is out[xx] = clip(((sum_x in[xmin + x] * k[x]) + 2^21) >> 22, 0, 255), the shift arithmetic.  The
+ *      HORIZONTAL pass runs first and is rounded to uint8; the vertical pass reads those bytes.  A pass is skipped exactly when its
+ *      axis has outSize == inSize, in0 == 0 and in1 == outSize.  NEAREST is Pillow's ImagingScaleAffine (Geometry.c), a WALK per
+ *      axis: xo = in0 + scale / 2; for each xx: src = min(inSize - 1, (int)xo), xo += scale.  (The closed form floor(in0 + (xx + 0.5)
+ *      * scale) is NOT Pillow's: the accumulated sum rounds differently where scale is inexact; 138 of 400 random size pairs
+ *      differed, none with the walk.)  Pinned without a box only: the Python layer refuses NEAREST with a box.
+ *      Out of scope: RGBA / LA (Pillow premultiplies alpha), 16- and 32-bit modes, reducing_gap.
+ *
+ *      int32 accumulation.  sslcr_resample_table_ok holds of a table when every row has 255 * sum|k| + 2^21 < 2^31 and every
+ *      |k| < 2^23.  The first makes every partial sum of a pass fit int32 in any order: |2^21 + sum over a subset of pixel * k| <=
+ *      2^21 + 255 * sum|k|.  The second puts k in the signed 24-bit operand range of v_mul_i32_i24, and a pixel (< 2^8) is in it
+ *      anyway, so each product is one 24-bit multiply with an exact 32-bit result (|pixel * k| < 2^31 by the first condition).  The
+ *      bound derived for the five filters: the weights of a row are normalised to sum 1, so sum|w| = 1 + 2 * (the negative lobes'
+ *      share); BOX, BILINEAR and HAMMING have none (sum|k| <= 2^22 + ksize / 2 from rounding).  BICUBIC and LANCZOS have them, and
+ *      a window clipped at an image edge is normalised by a smaller sum: the worst rows over scales 1/600 .. 600, with and without
+ *      a fractional box, reach sum|w| = 1.251 (BICUBIC) and 1.571 (LANCZOS) (tests/test_resize_cpu.py asserts < 1.5 and < 1.75):
+ *      255 * 1.75 * 2^22 + 2^21 = 1.87e9 < 2^31 = 2.15e9.  The limit is sum|w| < 2.0058; a table past it is refused, not clamped. */
+#define SSLCR_RESAMPLE_NEAREST 0      /* Pillow's Image.Resampling codes */
+#define SSLCR_RESAMPLE_LANCZOS 1
+#define SSLCR_RESAMPLE_BILINEAR 2
+#define SSLCR_RESAMPLE_BICUBIC 3
+#define SSLCR_RESAMPLE_BOX 4
+#define SSLCR_RESAMPLE_HAMMING 5
+/*      HOST-ONLY entries: no device is touched, every pointer is HOST memory.
+ *      sslcr_resample_ksize: the ksize of the axis (NEAREST: 1), or -1 for an unknown filter / an empty axis.
+ *      sslcr_resample_coeffs: fills k[outSize][k_stride] (k_stride >= ksize; entries past a row's xmax are 0) and bounds[outSize][2]
+ *      of one axis.  NEAREST writes the gather's table: bounds[xx] = (src, 1), k[xx][0] = 2^22.  Returns 0, or -1 with NOTHING
+ *      written: bad arguments, or a table that sslcr_resample_table_ok refuses.
+ *      sslcr_resample_table_ok: 1 when k[outSize][k_stride] satisfies the two conditions above, else 0. */
+int sslcr_resample_ksize(double in0, double in1, int outSize, int filter);
+int sslcr_resample_coeffs(int inSize, double in0, double in1, int outSize, int filter, int32_t* k, int k_stride, int32_t* bounds);
+int sslcr_resample_table_ok(const int32_t* k, int outSize, int k_stride);
+/*      The launch.  src / dst: uint8 batches, each [N][H][W][C] (chw = 0) or [N][C][H][W] (chw = 1), C in {1, 3}, every
+ *      combination; dst must not overlap src.  kx / bx: the horizontal tables, T sets of [OW][ksx] and [OW][2]; ky / by: the vertical
+ *      ones, [OH][ksy] and [OH][2].  kx == bx == NULL: no horizontal pass (then OW == IW); likewise ky / by.  Both NULL: a copy
+ *      between the layouts.  nearest = 1: bx / by are gather tables (k unused).  table_index: NULL (set 0 for every image) or a
+ *      device int32 [N] naming the set of each image -- a batch in which every image has its own box in ONE launch.  bx_host /
+ *      by_host: HOST copies of bx / by (all T sets), read by the plan only: the fused form sizes its LDS from the widest column
+ *      and row range a tile reads; without them a two-pass descriptor takes the two-launch form.  workspace: the two-launch form's
+ *      uint8 intermediate, sslcr_resample_plan_info.workspace_bytes of it (else unused).  form: 0 = the plan's choice, 1 / 2 force
+ *      SSLCR_RESAMPLE_FUSED / _TWO_PASS for a descriptor that needs both passes (an error where the plan says fused does not fit,
+ *      and for a descriptor that needs one pass or none).  N == 0 returns 0 and launches nothing.
+ *      The device tables must be what sslcr_resample_coeffs wrote: the kernels clamp every range they read to the image and to
+ *      their LDS tile, so a wrong table gives wrong bytes but no access outside the buffers.
+ *
+ *      Forms (sslcr_resample_plan_info.form):
+ *        FUSED       one launch; a workgroup of 256 owns tile_h x tile_w output pixels of one image: it stages the source rows and
+ *                    columns the tile reads into LDS with whole-dword loads, runs the horizontal pass from LDS into LDS as rounded
+ *                    bytes (planar, four pixels per lane and dword), barrier, runs the vertical pass from LDS (one dword per tap
+ *                    and lane, the coefficient uniform over a row of lanes) and stores whole dwords: 4 pixels of a plane (CHW) or 4
+ *                    RGB pixels = 3 dwords (HWC).  The tile's slices of the four tables sit in LDS.  The intermediate never leaves the CU.
+ *        TWO_PASS    a horizontal launch into `workspace` (planar [N][C][IH][OW]), then a vertical launch: every descriptor whose
+ *                    fused tile would exceed SSLCR_RESAMPLE_LDS_CAP (large down-scales: ksize and the row range grow with the scale).
+ *        HORIZONTAL / VERTICAL   the one launch of a descriptor that needs one pass.
+ *        GATHER      NEAREST, and the copy.
+ *      Every form is integer arithmetic only and returns the same bytes.  Work passes between workgroups at launch boundaries only. */
+#define SSLCR_RESAMPLE_GATHER 0
+#define SSLCR_RESAMPLE_FUSED 1
+#define SSLCR_RESAMPLE_TWO_PASS 2
+#define SSLCR_RESAMPLE_HORIZONTAL 3
+#define SSLCR_RESAMPLE_VERTICAL 4
+#define SSLCR_RESAMPLE_LDS_CAP 65536   /* dynamic LDS the fused kernel may ask of the launcher: two workgroups per CU at the least */
+typedef struct sslcr_resample_desc {
+  const uint8_t* src;
+  uint8_t* dst;
+  const int32_t* kx; const int32_t* bx; const int32_t* ky; const int32_t* by;
+  const int32_t* table_index;
+  const int32_t* bx_host; const int32_t* by_host;
+  uint8_t* workspace;
+  int N, C, IH, IW, OH, OW, ksx, ksy, T;
+  int src_chw, dst_chw, nearest, form;
+} sslcr_resample_desc;
+typedef struct sslcr_resample_plan_info {
+  int form;                 /* SSLCR_RESAMPLE_* the launch takes */
+  int fused_ok;             /* 1: form = 1 (fused) is accepted for this descriptor */
+  int tile_w, tile_h;       /* FUSED: output pixels of a workgroup's tile (else 0) */
+  int rows, cols;           /* FUSED: the most source rows / columns a tile stages (else 0) */
+  int grid[2];              /* workgroups of the (first, second) launch; 0 = no such launch */
+  size_t lds_bytes;         /* dynamic LDS of the launch (FUSED only, <= SSLCR_RESAMPLE_LDS_CAP) */
+  size_t workspace_bytes;   /* TWO_PASS only */
+} sslcr_resample_plan_info;
+/* HOST-ONLY: what sslcr_resample would launch for this descriptor (the device pointers are not read, only their NULL-ness).
+ * -1 for a descriptor sslcr_resample refuses. */
+int sslcr_resample_plan(const sslcr_resample_desc* d, sslcr_resample_plan_info* out);
+int sslcr_resample(const sslcr_resample_desc* d, void* stream);
 
 /* ---- device-side strong augmentation, the colour ops of the reference's RandAugment pool ("next" row f4) on a uint8 batch in HBM.
  *      As with sslcr_weak_augment the random draws stay on the host, in the reference's order (ssl_cr_histo_amd/augment.py);

@@ -109,6 +109,13 @@ SortDesc = _S("SortDesc", [("keys", vp * 2), ("values", vp * 2), ("workspace", v
 RankKeysDesc = _S("RankKeysDesc", [(k, vp) for k in ("scores", "target", "valid", "positive", "keys", "values", "nan")] +
                   [("n", i32), ("C", i32)])
 AucDesc = _S("AucDesc", [(k, vp) for k in ("keys", "values", "nan", "counts", "work")] + [("n", i32), ("C", i32)])
+RESAMPLE_FILTERS = {"nearest": 0, "lanczos": 1, "bilinear": 2, "bicubic": 3, "box": 4, "hamming": 5}     # SSLCR_RESAMPLE_* = Pillow's codes
+RESAMPLE_FORMS = ("gather", "fused", "two_pass", "horizontal", "vertical")                             # SSLCR_RESAMPLE_GATHER ..
+RESAMPLE_LDS_CAP = 65536      # SSLCR_RESAMPLE_LDS_CAP
+ResampleDesc = _S("ResampleDesc", [(k, vp) for k in ("src", "dst", "kx", "bx", "ky", "by", "table_index", "bx_host", "by_host", "workspace")] +
+                  [(k, i32) for k in ("N", "C", "IH", "IW", "OH", "OW", "ksx", "ksy", "T", "src_chw", "dst_chw", "nearest", "form")])
+ResamplePlan = _S("ResamplePlan", [(k, i32) for k in ("form", "fused_ok", "tile_w", "tile_h", "rows", "cols")] + [("grid", i32 * 2),
+                                                                                                                ("lds_bytes", sz), ("workspace_bytes", sz)])
 PackDesc = _S("PackDesc", [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("gamma", vp), ("beta", vp), ("rmean", vp),
                            ("rvar", vp), ("eps", f32), ("bias_out", vp)] + [(k, i32) for k in ("K", "C", "R", "S", "dgrad_flip")] + [("scale_out", vp)])
 
@@ -180,6 +187,11 @@ SIGNATURES = {
     "sslcr_rank_keys": (i32, [P(RankKeysDesc), vp]),
     "sslcr_auc_workspace_bytes": (sz, [i32, i32]),
     "sslcr_auc_counts": (i32, [P(AucDesc), vp]),
+    "sslcr_resample_ksize": (i32, [f64, f64, i32, i32]),
+    "sslcr_resample_coeffs": (i32, [i32, f64, f64, i32, i32, vp, i32, vp]),
+    "sslcr_resample_table_ok": (i32, [vp, i32, i32]),
+    "sslcr_resample_plan": (i32, [P(ResampleDesc), P(ResamplePlan)]),
+    "sslcr_resample": (i32, [P(ResampleDesc), vp]),
     "sslcr_optimizer_step": (i32, [vp, i32, i32, P(OptDesc), vp]),
     "sslcr_optimizer_step_groups": (i32, [vp, i32, i32, P(OptDesc), i32, vp, vp]),
     "sslcr_grad_norm": (i32, [vp, sz, f32, vp, vp, vp]),

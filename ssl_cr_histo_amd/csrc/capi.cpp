@@ -1,7 +1,10 @@
 // extern "C" boundary of libsslcr.so: argument checks, error strings, no exceptions across the ABI.
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
+
+#include <new>
 
 #include "kernels.hpp"
 
@@ -470,6 +473,153 @@ int sslcr_auc_counts(const sslcr_auc_desc* d, void* stream) {
   NEED(ALIGNED(d->keys, 3) && ALIGNED(d->values, 3) && ALIGNED(d->work, 3), "keys / values / work alignment");
   NEED(ALIGNED(d->counts, 7) && ALIGNED(d->nan, 7), "counts / nan alignment");
   return check(launch_auc_counts(*d, (hipStream_t)stream), "auc_counts");
+}
+// ---- Pillow-exact resize (resample.hip).  The coefficient tables are host arithmetic: Pillow's precompute_coeffs and
+// normalize_coeffs_8bpc (Resample.c) in plain double with the libm Pillow itself calls, in its order of operations.
+namespace {
+constexpr double RS_PI = 3.14159265358979323846;      // M_PI
+double rs_box(double x) { return x > -0.5 && x <= 0.5 ? 1.0 : 0.0; }
+double rs_bilinear(double x) {
+  if (x < 0.0) x = -x;
+  return x < 1.0 ? 1.0 - x : 0.0;
+}
+double rs_hamming(double x) {
+  if (x < 0.0) x = -x;
+  if (x == 0.0) return 1.0;
+  if (x >= 1.0) return 0.0;
+  x = x * RS_PI;
+  return sin(x) / x * (0.54f + 0.46f * cos(x));       // float32 constants, as Resample.c spells them
+}
+double rs_bicubic(double x) {
+  const double a = -0.5;
+  if (x < 0.0) x = -x;
+  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+  return 0.0;
+}
+double rs_sinc(double x) {
+  if (x == 0.0) return 1.0;
+  x = x * RS_PI;
+  return sin(x) / x;
+}
+double rs_lanczos(double x) { return -3.0 <= x && x < 3.0 ? rs_sinc(x) * rs_sinc(x / 3) : 0.0; }
+struct RsFilter { double (*f)(double); double support; };
+bool rs_filter(int code, RsFilter* out) {
+  switch (code) {
+    case SSLCR_RESAMPLE_BOX: *out = {rs_box, 0.5}; return true;
+    case SSLCR_RESAMPLE_BILINEAR: *out = {rs_bilinear, 1.0}; return true;
+    case SSLCR_RESAMPLE_HAMMING: *out = {rs_hamming, 1.0}; return true;
+    case SSLCR_RESAMPLE_BICUBIC: *out = {rs_bicubic, 2.0}; return true;
+    case SSLCR_RESAMPLE_LANCZOS: *out = {rs_lanczos, 3.0}; return true;
+  }
+  return false;
+}
+}  // namespace
+int sslcr_resample_ksize(double in0, double in1, int outSize, int filter) {
+  RsFilter f;
+  if (filter == SSLCR_RESAMPLE_NEAREST) return outSize >= 1 && in1 > in0 ? 1 : -1;
+  if (!rs_filter(filter, &f) || outSize < 1 || !(in1 > in0)) return -1;
+  double filterscale = (in1 - in0) / outSize;
+  if (filterscale < 1.0) filterscale = 1.0;
+  const double ks = 2.0 * ceil(f.support * filterscale) + 1;
+  return ks < (double)(1 << 30) ? (int)ks : -1;
+}
+int sslcr_resample_table_ok(const int32_t* k, int outSize, int k_stride) {
+  if (!k || outSize < 1 || k_stride < 1) return 0;
+  const int64_t limit = ((int64_t)1 << 31) - ((int64_t)1 << 21);       // 255 * sum|k| + 2^21 < 2^31
+  for (int xx = 0; xx < outSize; ++xx) {
+    int64_t sum = 0;
+    for (int x = 0; x < k_stride; ++x) {
+      const int64_t v = k[(size_t)xx * k_stride + x];
+      const int64_t m = v < 0 ? -v : v;
+      if (m >= (int64_t)1 << 23) return 0;
+      sum += m;
+    }
+    if (255 * sum >= limit) return 0;
+  }
+  return 1;
+}
+int sslcr_resample_coeffs(int inSize, double in0, double in1, int outSize, int filter, int32_t* k, int k_stride, int32_t* bounds) {
+  NEED(k && bounds, "null table");
+  NEED(inSize >= 1 && outSize >= 1, "empty axis");
+  NEED(in0 >= 0.0 && in1 <= (double)inSize && in1 > in0, "box outside the image, or empty");
+  const int ksize = sslcr_resample_ksize(in0, in1, outSize, filter);
+  NEED(ksize >= 1, "unknown filter, or ksize >= 2^30");
+  NEED(k_stride >= ksize, "k_stride < ksize");
+  const double scale = (in1 - in0) / outSize;
+  const size_t cells = (size_t)outSize * k_stride;
+  int32_t* kk = new (std::nothrow) int32_t[cells]();
+  int32_t* bb = new (std::nothrow) int32_t[(size_t)outSize * 2];
+  double* w = new (std::nothrow) double[ksize];
+  int rc = 0;
+  if (!kk || !bb || !w) {
+    rc = fail("sslcr_resample_coeffs: out of host memory");
+  } else if (filter == SSLCR_RESAMPLE_NEAREST) {
+    // Pillow's ImagingScaleAffine (Geometry.c): the source position is WALKED, xo += scale per output pixel from in0 + scale / 2,
+    // and truncated.  The closed form floor(in0 + (xx + 0.5) * scale) rounds differently where scale is inexact (512 -> 257).
+    double xo = in0 + scale * 0.5;
+    for (int xx = 0; xx < outSize; ++xx, xo += scale) {
+      bb[2 * xx] = xo < inSize - 1 ? (int)xo : inSize - 1;
+      bb[2 * xx + 1] = 1;
+      kk[(size_t)xx * k_stride] = 1 << 22;
+    }
+  } else {
+    RsFilter f;
+    rs_filter(filter, &f);
+    double filterscale = scale;
+    if (filterscale < 1.0) filterscale = 1.0;
+    const double support = f.support * filterscale;
+    const double ss = 1.0 / filterscale;
+    for (int xx = 0; xx < outSize; ++xx) {
+      const double center = in0 + (xx + 0.5) * scale;
+      double ww = 0.0;
+      int xmin = (int)(center - support + 0.5);
+      if (xmin < 0) xmin = 0;
+      int xmax = (int)(center + support + 0.5);
+      if (xmax > inSize) xmax = inSize;
+      xmax -= xmin;
+      for (int x = 0; x < xmax; ++x) {
+        w[x] = f.f((x + xmin - center + 0.5) * ss);
+        ww += w[x];
+      }
+      for (int x = 0; x < xmax; ++x) {
+        if (ww != 0.0) w[x] /= ww;
+        kk[(size_t)xx * k_stride + x] = w[x] < 0 ? (int)(-0.5 + w[x] * (1 << 22)) : (int)(0.5 + w[x] * (1 << 22));
+      }
+      bb[2 * xx] = xmin;
+      bb[2 * xx + 1] = xmax;
+    }
+    if (!sslcr_resample_table_ok(kk, outSize, k_stride))
+      rc = fail("sslcr_resample_coeffs: a row of the table has 255 * sum|k| + 2^21 >= 2^31 or a |k| >= 2^23: no int32 pass");
+  }
+  if (rc == 0) {
+    memcpy(k, kk, cells * sizeof(int32_t));
+    memcpy(bounds, bb, (size_t)outSize * 2 * sizeof(int32_t));
+  }
+  delete[] kk;
+  delete[] bb;
+  delete[] w;
+  return rc;
+}
+int sslcr_resample_plan(const sslcr_resample_desc* d, sslcr_resample_plan_info* out) {
+  NEED(d && out, "null");
+  const char* why = resample_plan(*d, out);
+  NEED(!why, why);
+  return 0;
+}
+int sslcr_resample(const sslcr_resample_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  ResamplePlan p;
+  const char* why = resample_plan(*d, &p);
+  NEED(!why, why);
+  if (d->N == 0) return 0;
+  NEED(d->src && d->dst, "null tensor");
+  NEED(ALIGNED(d->kx, 3) && ALIGNED(d->bx, 3) && ALIGNED(d->ky, 3) && ALIGNED(d->by, 3) && ALIGNED(d->table_index, 3), "table alignment");
+  NEED(p.form != SSLCR_RESAMPLE_TWO_PASS || d->workspace, "the two-pass form needs a workspace (sslcr_resample_plan_info.workspace_bytes)");
+  const uintptr_t s = reinterpret_cast<uintptr_t>(d->src), t = reinterpret_cast<uintptr_t>(d->dst);
+  const size_t sb = (size_t)d->N * d->C * d->IH * d->IW, tb = (size_t)d->N * d->C * d->OH * d->OW;
+  NEED(s + sb <= t || t + tb <= s, "src and dst overlap (out of place only)");
+  return check(launch_resample(*d, p, (hipStream_t)stream), "resample");
 }
 #undef SQ_SHAPE_OK
 #undef MAP_SHAPE_OK

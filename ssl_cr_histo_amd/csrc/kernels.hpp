@@ -227,6 +227,11 @@ hipError_t launch_region_moments(const sslcr_moments_desc& a, hipStream_t st);
 hipError_t launch_sort_pairs(const sslcr_sort_desc& a, hipStream_t st);
 hipError_t launch_rank_keys(const sslcr_rank_keys_desc& a, hipStream_t st);
 hipError_t launch_auc_counts(const sslcr_auc_desc& a, hipStream_t st);
+// resample.hip: which form serves a descriptor is decided ONCE, here -- the launch, sslcr_resample_plan and the tests read this plan
+using ResamplePlan = sslcr_resample_plan_info;
+// nullptr and *out filled, or what is wrong with the descriptor (host only: no device call, no device pointer read)
+const char* resample_plan(const sslcr_resample_desc& a, ResamplePlan* out);
+hipError_t launch_resample(const sslcr_resample_desc& a, const ResamplePlan& p, hipStream_t st);
 // augment.hip
 hipError_t launch_weak_augment(const sslcr_weak_aug_desc& a, hipStream_t st);
 hipError_t launch_hed_colour(const sslcr_colour_aug_desc& a, hipStream_t st);

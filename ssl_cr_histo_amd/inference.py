@@ -26,6 +26,10 @@ lesions, the map's non-maximum suppression into detections, the lesion under eac
 distance transform, the hole filling, the lesions' labels and moments (csrc/evalmask.hip) -- and the isolated-tumour-cell list from
 the major axis lengths; ``lesion_scores(..., evaluation=)`` scores against it.
 
+Patch loaders.  The BreastPathQ validation and test loops resize every patch with Pillow on the host (``transforms.Resize``);
+``PatchDeviceLoader`` holds the patches in HBM and resizes each batch on the device with Pillow's own bytes (``kernels.pil_resize``,
+csrc/resample.hip), yielding the host loader's batches.
+
 Ranking metrics.  The Kather main also prints ``roc_auc_score(targets, scores, multi_class='ovr')`` (eval_Kather_SSL_CR.py:658).
 ``roc_auc`` counts every column's correctly ordered (positive, negative) pairs exactly on the device -- one radix sort per column, all
 columns in one call, ties resolved over runs of equal scores (csrc/rank.hip) -- and divides once on the host; ``map_auc`` is the same
@@ -183,6 +187,65 @@ class WsiDeviceLoader:
     def __iter__(self):
         for lo, hi in self.ranges():
             yield self.tiles(lo, hi), self.x_mask[lo:hi], self.y_mask[lo:hi]
+
+
+class _PatchDataset:
+    def __init__(self, n):
+        self.n = n
+
+    def __len__(self):
+        return self.n
+
+
+class PatchDeviceLoader:
+    """The evaluation loader of the patch datasets with the patches in HBM: ``DataLoader(DatasetBreastPathQ_eval(...,
+    transforms.Resize(size=image_size)), shuffle=False)`` (eval_BreastPathQ_SSL_CR.py:325,365, eval_BreastPathQ_SSL.py:290,319,
+    dataset.py:575-599) without the host's one-image-at-a-time Pillow resize.  patches_u8: ONE uint8 array [M, H, W, 3]
+    (layout='hwc', what the datasets hold) or [M, 3, H, W] ('chw'), host or device; it is uploaded once, at the first batch.
+    targets: any number of arrays of M rows, handed through in slices (host tensors, as a DataLoader collates them).  image_size: an
+    int or (h, w), ``kernels.resize_output_size``'s rule.  Iterating yields ``(tiles, *target slices)`` with tiles a device uint8
+    [n, 3, oh, ow] -- ``PIL.Image.resize((ow, oh), resample)`` of every patch (``kernels.pil_resize``), channels first -- in order,
+    the last batch short: the batch contract of the host loader, so ``steps.bpq_test``, ``bpq_sup_test``, ``bpq_cr_validate``,
+    ``kather_cr_test`` and the other loops take it unchanged (they pass device uint8 batches through ``Engine.as_input``).  Patches
+    of unequal shape are out of scope."""
+
+    def __init__(self, patches_u8, *targets, image_size, batch_size, resample="bilinear", layout="hwc", device=None):
+        patches = torch.as_tensor(patches_u8)
+        if layout not in ("hwc", "chw"):
+            raise ValueError(f"PatchDeviceLoader: layout = {layout!r} ('hwc' or 'chw')")
+        if patches.dtype != torch.uint8 or patches.dim() != 4 or patches.shape[3 if layout == "hwc" else 1] != 3:
+            raise ValueError("PatchDeviceLoader: a uint8 array [M, H, W, 3] (layout='hwc') or [M, 3, H, W] ('chw') expected")
+        if isinstance(batch_size, bool) or int(batch_size) < 1:
+            raise ValueError("PatchDeviceLoader: batch_size must be positive")
+        M = patches.shape[0]
+        H, W = (patches.shape[1], patches.shape[2]) if layout == "hwc" else (patches.shape[2], patches.shape[3])
+        self.targets = [torch.as_tensor(t) for t in targets]
+        for t in self.targets:
+            if t.dim() < 1 or t.shape[0] != M:
+                raise ValueError(f"PatchDeviceLoader: every target needs {M} rows, one per patch")
+        K.resample_filter_code(resample)                                   # ValueError for an unknown filter, here and not at the first batch
+        self.out_hw = K.resize_output_size(H, W, image_size)
+        self.patches, self.layout, self.resample, self.batch_size = patches, layout, resample, int(batch_size)
+        self.device = torch.device(device if device is not None else (patches.device if patches.is_cuda else "cuda"))
+        self.dataset = _PatchDataset(M)
+
+    def __len__(self):
+        return (len(self.dataset) + self.batch_size - 1) // self.batch_size
+
+    def ranges(self):
+        n = len(self.dataset)
+        return [(lo, min(lo + self.batch_size, n)) for lo in range(0, n, self.batch_size)]
+
+    def tiles(self, lo, hi, out=None):
+        """patches lo..hi resized: device uint8 [hi - lo, 3, oh, ow]"""
+        if not self.patches.is_cuda or not self.patches.is_contiguous():      # the one upload
+            self.patches = self.patches.to(self.device).contiguous()
+        oh, ow = self.out_hw
+        return K.pil_resize(self.patches[lo:hi], (ow, oh), self.resample, layout=self.layout, out_layout="chw", out=out)
+
+    def __iter__(self):
+        for lo, hi in self.ranges():
+            yield (self.tiles(lo, hi),) + tuple(t[lo:hi] for t in self.targets)
 
 
 class ConfusionMeter:

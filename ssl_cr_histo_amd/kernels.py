@@ -1243,3 +1243,222 @@ def grad_accumulate(dst, src):
         raise L.SslcrError(f"grad_accumulate: dst has {dst.numel()} elements on {dst.device}, src {src.numel()} on {src.device}")
     L.check(L.lib().sslcr_grad_accumulate(L.ptr(dst), L.ptr(src), dst.numel(), L.stream_ptr()))
     return dst
+
+
+# ---- Pillow-exact resize (csrc/resample.hip; the definition stands in include/sslcr.h)
+RESAMPLE_FILTERS = L.RESAMPLE_FILTERS
+_FAKE = 4096                  # a non-NULL "device pointer" for plan queries: sslcr_resample_plan reads NULL-ness only
+_RESAMPLE_CACHE_MAX = 64      # table sets kept (a loader uses one; a random-scale crop a new one per batch)
+_resample_cache = {}
+
+
+def resize_output_size(h, w, size):
+    """-> (oh, ow) of ``torchvision.transforms.Resize(size)`` for an image of h x w.  An int: the shorter edge becomes ``size`` and
+    the other ``int(size * long / short)`` (torchvision's ``_compute_resized_output_size``); a pair is taken as (h, w).
+    PARITY UNPINNED against torchvision (it is not installed where the goldens are made): the rule is transcribed,
+    the tests hold it to literal values."""
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError(f"resize_output_size: image of {h} x {w}")
+    if isinstance(size, (tuple, list)) and len(size) == 2:
+        oh, ow = int(size[0]), int(size[1])
+    else:
+        if isinstance(size, (tuple, list)):
+            if len(size) != 1:
+                raise ValueError(f"resize_output_size: size = {size!r}")
+            size = size[0]
+        short, long = (w, h) if w <= h else (h, w)
+        new_short, new_long = int(size), int(int(size) * long / short)
+        ow, oh = (new_short, new_long) if w <= h else (new_long, new_short)
+    if oh < 1 or ow < 1:
+        raise ValueError(f"resize_output_size: size = {size!r} gives {oh} x {ow}")
+    return oh, ow
+
+
+def resample_axis(in_size, in0, in1, out_size, resample, k_stride=None):
+    """-> (k int32 [out_size, k_stride], bounds int32 [out_size, 2]) of one axis, host numpy (sslcr_resample_coeffs; no device).
+    SslcrError where the entry refuses: an unknown filter, a box outside the axis, a table no int32 pass can take."""
+    import numpy as np
+    code = resample_filter_code(resample)
+    ks = L.lib().sslcr_resample_ksize(float(in0), float(in1), int(out_size), code)
+    if ks < 1:
+        raise L.SslcrError(f"resample_axis: no table for [{in0}, {in1}) -> {out_size} with filter {resample!r}")
+    stride = ks if k_stride is None else int(k_stride)
+    k = np.zeros((int(out_size), stride), dtype=np.int32)
+    b = np.zeros((int(out_size), 2), dtype=np.int32)
+    L.check(L.lib().sslcr_resample_coeffs(int(in_size), float(in0), float(in1), int(out_size), code, k.ctypes.data, stride, b.ctypes.data))
+    return k, b
+
+
+def resample_filter_code(resample):
+    """a filter name ('nearest', 'box', 'bilinear', 'hamming', 'bicubic', 'lanczos') or Pillow's code -> the SSLCR_RESAMPLE_* code;
+    ValueError for anything else"""
+    if isinstance(resample, str):
+        if resample.lower() not in RESAMPLE_FILTERS:
+            raise ValueError(f"unknown resample filter {resample!r} (known: {sorted(RESAMPLE_FILTERS)})")
+        return RESAMPLE_FILTERS[resample.lower()]
+    if int(resample) not in RESAMPLE_FILTERS.values():
+        raise ValueError(f"unknown resample filter code {resample!r}")
+    return int(resample)                     # Pillow's Image.Resampling members are these ints
+
+
+def _resample_boxes(box, n, IH, IW, nearest):
+    """box -> (float64 [T, 4] distinct boxes, int32 [n] set of each image or None), rounded to float32 and checked as Pillow does"""
+    import numpy as np
+    if box is None:
+        return np.array([[0.0, 0.0, IW, IH]]), None
+    if nearest:
+        raise ValueError("pil_resize: NEAREST takes box=None only (Pillow walks a box in fixed point: not reproduced)")
+    b = np.asarray(box, dtype=np.float32).astype(np.float64)         # Pillow parses the box into C floats
+    if b.shape == (4,):
+        b, index = b[None], None
+    elif b.ndim == 2 and b.shape == (n, 4):
+        b, inv = np.unique(b, axis=0, return_inverse=True)
+        index = np.ascontiguousarray(inv.reshape(-1).astype(np.int32))
+    else:
+        raise ValueError(f"pil_resize: box must be None, one (left, upper, right, lower) or an array [{n}, 4]")
+    if len(b):
+        if (b[:, :2] < 0).any():
+            raise ValueError("box offset can't be negative")
+        if (b[:, 2] > IW).any() or (b[:, 3] > IH).any():
+            raise ValueError("box can't exceed original image size")
+        if (b[:, 2] - b[:, 0] <= 0).any() or (b[:, 3] - b[:, 1] <= 0).any():
+            raise ValueError("box can't be empty")
+    return b, index
+
+
+class _ResampleTables:
+    """the table sets of one (sizes, boxes, filter): host arrays (the plan reads the bounds) and their per-device uploads"""
+
+    def __init__(self, IH, IW, OH, OW, code, boxes):
+        import numpy as np
+        self.T, self.nearest = len(boxes), int(code == RESAMPLE_FILTERS["nearest"])
+        self.k, self.b, self.ks, self.dev, self.index = [None, None], [None, None], [1, 1], {}, {}
+        for axis, (isz, osz, lo, hi) in enumerate(((IW, OW, boxes[:, 0], boxes[:, 2]), (IH, OH, boxes[:, 1], boxes[:, 3]))):
+            # Pillow skips the pass of an axis exactly when outSize == inSize, in0 == 0 and in1 == outSize.  In a batch of several
+            # boxes the pass runs for all once one of them needs it: the table of an axis that could be skipped is the identity
+            # (one coefficient of 2^22 at the pixel itself, the rest round to 0), so the bytes are the same.
+            if osz == isz and (lo == 0).all() and (hi == osz).all():
+                continue
+            ks = max(L.lib().sslcr_resample_ksize(float(a), float(c), osz, code) for a, c in zip(lo, hi))
+            parts = [resample_axis(isz, a, c, osz, code, ks) for a, c in zip(lo, hi)]
+            self.k[axis] = np.ascontiguousarray(np.stack([p[0] for p in parts]))
+            self.b[axis] = np.ascontiguousarray(np.stack([p[1] for p in parts]))
+            self.ks[axis] = ks
+
+    def on(self, device):
+        if device not in self.dev:
+            self.dev[device] = [None if a is None else torch.from_numpy(a).to(device) for a in (self.k[0], self.b[0], self.k[1], self.b[1])]
+        return self.dev[device]
+
+    def index_on(self, device, index):
+        """the per-image set index on the device: uploaded when this (tables, device, index) is first seen, then reused"""
+        key = (device, index.tobytes())
+        if key not in self.index:
+            while len(self.index) >= 8:
+                self.index.pop(next(iter(self.index)))
+            self.index[key] = torch.from_numpy(index).to(device)
+        return self.index[key]
+
+
+def _resample_tables(IH, IW, OH, OW, code, boxes):
+    key = (IH, IW, OH, OW, code, boxes.tobytes())
+    t = _resample_cache.get(key)
+    if t is None:
+        while len(_resample_cache) >= _RESAMPLE_CACHE_MAX:
+            _resample_cache.pop(next(iter(_resample_cache)))
+        t = _resample_cache[key] = _ResampleTables(IH, IW, OH, OW, code, boxes)
+    return t
+
+
+_RESAMPLE_FORMS = {None: 0, "fused": 1, "two_pass": 2}
+
+
+def _resample_desc(t, ptrs, index_ptr, N, C, IH, IW, OH, OW, src_chw, dst_chw, form):
+    if form not in _RESAMPLE_FORMS:
+        raise ValueError(f"pil_resize: form = {form!r} (None, 'fused' or 'two_pass')")
+    src, dst, kx, bx, ky, by = ptrs
+    host = [None if a is None else a.ctypes.data for a in t.b]
+    return L.ResampleDesc(src, dst, kx, bx, ky, by, index_ptr, host[0], host[1], None, N, C, IH, IW, OH, OW, t.ks[0], t.ks[1], max(t.T, 1),
+                          int(src_chw), int(dst_chw), t.nearest, _RESAMPLE_FORMS[form])
+
+
+def _resample_plan(d):
+    p = L.ResamplePlan()
+    L.check(L.lib().sslcr_resample_plan(d, p))
+    return p
+
+
+def resample_plan(in_hw, size, resample="bilinear", box=None, *, n=1, channels=3, layout="hwc", out_layout=None, form=None):
+    """What ``pil_resize`` would launch for n images of in_hw = (h, w) -> size = (ow, oh): sslcr_resample_plan's answer as a dict --
+    form ('fused', 'two_pass', 'horizontal', 'vertical', 'gather'), fused_ok, tile (w, h), window (rows, cols), grid, lds_bytes,
+    workspace_bytes.  Host only: no device is needed.  SslcrError where the entry refuses (form='fused' where it does not fit)."""
+    IH, IW = int(in_hw[0]), int(in_hw[1])
+    OW, OH = int(size[0]), int(size[1])
+    code = resample_filter_code(resample)
+    boxes, index = _resample_boxes(box, n, IH, IW, code == RESAMPLE_FILTERS["nearest"])
+    t = _resample_tables(IH, IW, OH, OW, code, boxes)
+    fake = [_FAKE, _FAKE] + [None if a is None else _FAKE for a in (t.k[0], t.b[0], t.k[1], t.b[1])]
+    d = _resample_desc(t, fake, None if index is None else _FAKE, n, channels, IH, IW, OH, OW, layout == "chw",
+                       (out_layout or layout) == "chw", form)
+    p = _resample_plan(d)
+    return {"form": L.RESAMPLE_FORMS[p.form], "fused_ok": bool(p.fused_ok), "tile": (p.tile_w, p.tile_h), "window": (p.rows, p.cols),
+            "grid": (p.grid[0], p.grid[1]), "lds_bytes": int(p.lds_bytes), "workspace_bytes": int(p.workspace_bytes)}
+
+
+def _resize_layout(x, layout):
+    if layout is None:
+        layout = "hwc" if x.shape[3] in (1, 3) else "chw"
+    if layout not in ("hwc", "chw"):
+        raise ValueError(f"pil_resize: layout = {layout!r} ('hwc' or 'chw')")
+    n, a, b, c = x.shape
+    C, H, W = (c, a, b) if layout == "hwc" else (a, b, c)
+    if C not in (1, 3):
+        raise L.SslcrError(f"pil_resize: {C} channels in a {layout} batch of shape {tuple(x.shape)} (modes L and RGB: 1 or 3)")
+    return layout, n, C, H, W
+
+
+def pil_resize(x, size, resample="bilinear", box=None, out=None, out_layout=None, form=None, *, layout=None):
+    """``PIL.Image.resize(size, resample, box)`` of every image of a device uint8 batch, byte for byte (sslcr_resample; pinned to
+    Pillow 12.2.0 by tests/test_resize_*.py).  x: [N, H, W, C] ('hwc') or [N, C, H, W] ('chw'), C in {1, 3}; layout=None takes 'hwc'
+    when the last dimension is 1 or 3, else 'chw'.  size = (ow, oh), as Pillow's.  resample: 'nearest', 'box', 'bilinear', 'hamming',
+    'bicubic', 'lanczos' or Pillow's code.  box: None, one (left, upper, right, lower), or a host array [N, 4] -- every image its
+    own box, still one launch (the distinct boxes become table sets, chosen per image by a device index).  A box is rounded to
+    float32 and checked as Pillow does.  out / out_layout: the result's buffer / layout (default: x's layout).  form: None = the
+    plan's choice; 'fused' / 'two_pass' force one (SslcrError where 'fused' does not fit).  The coefficient tables are made on the
+    host once per (sizes, box, filter) and uploaded once per device, and so is the per-image index of an [N, 4] box.  A call whose
+    tables are cached launches without a sync; the FIRST call of a (sizes, box, filter) builds the tables on the host and copies
+    them from pageable memory, which blocks the host until the copy is done -- a batch with fresh boxes every call (a random-scale
+    crop) pays that every call.  The uploads are ordered on the stream that is current at that first call: a later call on ANOTHER
+    stream must be ordered after it by the caller (the loaders here use one stream)."""
+    _chk(x, out)
+    if x.dtype != torch.uint8 or x.dim() != 4:
+        raise L.SslcrError("pil_resize: a uint8 batch [N, H, W, C] or [N, C, H, W] expected")
+    layout, N, C, IH, IW = _resize_layout(x, layout)
+    out_layout = out_layout or layout
+    if out_layout not in ("hwc", "chw"):
+        raise ValueError(f"pil_resize: out_layout = {out_layout!r} ('hwc' or 'chw')")
+    OW, OH = int(size[0]), int(size[1])
+    if OW < 1 or OH < 1:
+        raise ValueError("height and width must be > 0")
+    code = resample_filter_code(resample)
+    boxes, index = _resample_boxes(box, N, IH, IW, code == RESAMPLE_FILTERS["nearest"])
+    shape = (N, OH, OW, C) if out_layout == "hwc" else (N, C, OH, OW)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != x.device:
+        raise L.SslcrError(f"pil_resize: out must be a uint8 tensor {list(shape)} on the batch's device")
+    if N == 0:
+        return out
+    t = _resample_tables(IH, IW, OH, OW, code, boxes)
+    tables = t.on(x.device)
+    idx = None if index is None else t.index_on(x.device, index)
+    d = _resample_desc(t, [L.ptr(x), L.ptr(out)] + [L.ptr(a) for a in tables], L.ptr(idx), N, C, IH, IW, OH, OW, layout == "chw",
+                       out_layout == "chw", form)
+    p = _resample_plan(d)
+    work = None
+    if p.workspace_bytes:
+        work = torch.empty(p.workspace_bytes, dtype=torch.uint8, device=x.device)
+        d.workspace = L.ptr(work)
+    L.check(L.lib().sslcr_resample(d, L.stream_ptr()))
+    return out
