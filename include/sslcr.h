@@ -665,14 +665,15 @@ int sslcr_map_confusion(const sslcr_map_confusion_desc* d, void* stream);
  *
  *      sslcr_label_components.  labels[x][y] = 0 where mask is 0, else the number of the cell's connected component; connectivity 2
  *      = 8 neighbours, 1 = 4 neighbours.  Components are numbered 1..L by the order of each component's first cell (what
- *      scipy.ndimage.label gives); *count = L.  work: X * Y + ceil(X * Y / 1024) int32 of scratch.
+ *      scipy.ndimage.label gives); *count = L.  work: X * Y + ceil(X * Y / SSLCR_LABEL_RUN_CELLS) int32 of scratch.
  *      Errors: NULL pointers, X < 1, Y < 1, X * Y >= 2^31, connectivity outside {1, 2}, pointers not 4-byte aligned (the mask is read
  *      as whole dwords). */
+#define SSLCR_LABEL_RUN_CELLS 1024 /* the labeller numbers the components over runs of this many cells: one int32 of work per run */
 typedef struct sslcr_label_desc {
   const uint8_t* mask;      /* [X][Y], nonzero = set; 4-byte aligned */
   int32_t* labels;          /* [X][Y] */
   int32_t* count;           /* [1]: L */
-  int32_t* work;            /* [X * Y + ceil(X * Y / 1024)] */
+  int32_t* work;            /* [X * Y + ceil(X * Y / SSLCR_LABEL_RUN_CELLS)] */
   int X, Y, connectivity;
 } sslcr_label_desc;
 int sslcr_label_components(const sslcr_label_desc* d, void* stream);
@@ -781,14 +782,14 @@ int sslcr_edt_squared(const sslcr_edt_desc* d, void* stream);
 /*      sslcr_fill_holes.  out[x][y] = 1 where mask != 0, or where the cell's component of the BACKGROUND (mask == 0) at connectivity 1
  *      holds no cell of the array's border (row 0, row X - 1, column 0, column Y - 1); else 0.  A background cell joined to the
  *      border only diagonally is therefore filled.  The background is labelled by sslcr_label_components; labels / count / work are
- *      its outputs and scratch, of its sizes (labels [X * Y], work [X * Y + ceil(X * Y / 1024)]), and hold nothing of use afterwards.
+ *      its outputs and scratch, of its sizes (labels [X * Y], work [X * Y + ceil(X * Y / SSLCR_LABEL_RUN_CELLS)]), and hold nothing of use afterwards.
  *      Errors: NULL descriptor or pointers, X < 1, Y < 1, X * Y >= 2^31, out == mask, pointers not 4-byte aligned. */
 typedef struct sslcr_fill_desc {
   const uint8_t* mask;      /* [X][Y], nonzero = set */
   uint8_t* out;             /* [X][Y] of 0 / 1; 4-byte aligned, not mask */
   int32_t* labels;          /* [X][Y] scratch */
   int32_t* count;           /* [1] scratch */
-  int32_t* work;            /* [X * Y + ceil(X * Y / 1024)] scratch */
+  int32_t* work;            /* [X * Y + ceil(X * Y / SSLCR_LABEL_RUN_CELLS)] scratch */
   int X, Y;
 } sslcr_fill_desc;
 int sslcr_fill_holes(const sslcr_fill_desc* d, void* stream);

@@ -18,110 +18,128 @@ class SslcrError(RuntimeError):
     pass
 
 
-def _S(name, fields):
-    return type(name, (C.Structure,), {"_fields_": fields})
+MIRRORS = {}     # C struct name in include/sslcr.h -> its ctypes mirror: the one place a descriptor is registered (engine.py adds its three)
 
 
-ConvDesc = _S("ConvDesc", [("x", vp), ("w", vp), ("y", vp), ("in_scale", vp), ("in_shift", vp), ("bias", vp),
+def _S(cname, pyname, fields):
+    """the ctypes mirror of the header's struct cname, registered in MIRRORS under that name; tests/test_abi_cpu.py holds every entry
+    to the header's size and field offsets, and MIRRORS' keys to the header's structs"""
+    assert cname not in MIRRORS, cname
+    MIRRORS[cname] = type(pyname, (C.Structure,), {"_fields_": fields})
+    return MIRRORS[cname]
+
+
+ConvDesc = _S("sslcr_conv_desc", "ConvDesc", [("x", vp), ("w", vp), ("y", vp), ("in_scale", vp), ("in_shift", vp), ("bias", vp),
                            ("residual", vp), ("stats", vp)] +
               [(k, i32) for k in ("N", "H", "W", "C", "K", "R", "S", "stride", "pad", "PH", "PW", "OH", "OW", "osh",
                                   "transposed", "in_relu", "relu", "accumulate", "pix_mul", "pix_off_h", "pix_off_w")] +
               [("tap_mask", C.c_uint), ("mask_x", vp), ("mask_scale", vp), ("mask_shift", vp), ("mask_mean", vp),
                ("par4", i32), ("seg_images", i32), ("seg_stride", i32), ("out_scale", vp)])
-WgradDesc = _S("WgradDesc", [("x", vp), ("dy", vp), ("dw", vp), ("in_scale", vp), ("in_shift", vp), ("in_relu", i32)] +
+WgradDesc = _S("sslcr_wgrad_desc", "WgradDesc", [("x", vp), ("dy", vp), ("dw", vp), ("in_scale", vp), ("in_shift", vp), ("in_relu", i32)] +
                [(k, i32) for k in ("N", "H", "W", "C", "K", "R", "S", "stride", "pad", "OH", "OW", "seg_images", "seg_stride")])
-StemDesc = _S("StemDesc", [("x", vp), ("w", vp), ("y", vp), ("bias", vp), ("stats", vp)] +
+StemDesc = _S("sslcr_stem_desc", "StemDesc", [("x", vp), ("w", vp), ("y", vp), ("bias", vp), ("stats", vp)] +
               [(k, i32) for k in ("N", "H", "W", "OH", "OW", "in_f32", "relu")] + [("x2", vp), ("n_split", i32), ("out_scale", vp)])
-StemWgradDesc = _S("StemWgradDesc", [("x", vp), ("dy", vp), ("dw", vp)] +
+StemWgradDesc = _S("sslcr_stem_wgrad_desc", "StemWgradDesc", [("x", vp), ("dy", vp), ("dw", vp)] +
                    [(k, i32) for k in ("N", "H", "W", "OH", "OW", "in_f32")] + [("x2", vp), ("n_split", i32)])
-BnFinalizeDesc = _S("BnFinalizeDesc", [("partials", vp), ("rows", i32), ("C", i32), ("count", f64), ("gamma", vp),
+BnFinalizeDesc = _S("sslcr_bn_finalize_desc", "BnFinalizeDesc", [("partials", vp), ("rows", i32), ("C", i32), ("count", f64), ("gamma", vp),
                                        ("beta", vp), ("scale", vp), ("shift", vp), ("mean", vp), ("invstd", vp),
                                        ("running_mean", vp), ("running_var", vp), ("num_batches_tracked", vp),
                                        ("momentum", f32), ("eps", f32), ("replay", i32), ("sums_out", vp),
                                        ("sums_in", vp), ("stage", vp), ("nseg", i32), ("seg_stride", i32), ("tickets", vp)])
-BnActDesc = _S("BnActDesc", [("x", vp), ("scale", vp), ("shift", vp), ("res", vp), ("rscale", vp), ("rshift", vp),
+BnActDesc = _S("sslcr_bn_act_desc", "BnActDesc", [("x", vp), ("scale", vp), ("shift", vp), ("res", vp), ("rscale", vp), ("rshift", vp),
                              ("y", vp), ("pixels", sz), ("C", i32), ("relu", i32), ("nseg", i32), ("seg_stride", i32), ("ybits", vp)])
-PoolFwdDesc = _S("PoolFwdDesc", [("x", vp), ("scale", vp), ("shift", vp), ("y", vp), ("argmax", vp)] +
+PoolFwdDesc = _S("sslcr_pool_fwd_desc", "PoolFwdDesc", [("x", vp), ("scale", vp), ("shift", vp), ("y", vp), ("argmax", vp)] +
                  [(k, i32) for k in ("N", "H", "W", "C", "OH", "OW")])
-PoolBwdDesc = _S("PoolBwdDesc", [("dy", vp), ("argmax", vp), ("x", vp), ("scale", vp), ("shift", vp), ("dx", vp)] +
+PoolBwdDesc = _S("sslcr_pool_bwd_desc", "PoolBwdDesc", [("dy", vp), ("argmax", vp), ("x", vp), ("scale", vp), ("shift", vp), ("dx", vp)] +
                  [(k, i32) for k in ("N", "H", "W", "C", "OH", "OW")])
-BnBwdDesc = _S("BnBwdDesc", [("dy", vp), ("x", vp), ("yact", vp), ("scale", vp), ("shift", vp), ("mean", vp),
+BnBwdDesc = _S("sslcr_bn_bwd_desc", "BnBwdDesc", [("dy", vp), ("x", vp), ("yact", vp), ("scale", vp), ("shift", vp), ("mean", vp),
                              ("invstd", vp), ("sums", vp), ("dx", vp), ("gout", vp), ("pixels", sz), ("C", i32),
                              ("relu_from_x", i32), ("count", f64), ("pool_dy", vp), ("pool_argmax", vp), ("pH", i32),
                              ("pW", i32), ("pOH", i32), ("pOW", i32), ("pool_y", vp), ("g_in_reduce", i32), ("dgamma", vp), ("dbeta", vp),
                              ("pg_scale", f32), ("nseg", i32), ("seg_stride", i32), ("sums_stride", i32), ("yact_bits", vp)])
-LossDesc = _S("LossDesc", [("kind", i32), ("logits", vp), ("logits_t", vp), ("target_f", vp), ("target_i", vp),
+LossDesc = _S("sslcr_loss_desc", "LossDesc", [("kind", i32), ("logits", vp), ("logits_t", vp), ("target_f", vp), ("target_i", vp),
                            ("dlogits", vp), ("out", vp), ("nx", i32), ("nu", i32), ("C", i32), ("lambda_u", f32),
                            ("inv_nx_global", f32), ("inv_nu_global", f32)])
-LossOpts = _S("LossOpts", [("class_weight", vp), ("label_smoothing", f32), ("ignore_index", i32), ("threshold", f32),
+LossOpts = _S("sslcr_loss_opts", "LossOpts", [("class_weight", vp), ("label_smoothing", f32), ("ignore_index", i32), ("threshold", f32),
                            ("temperature", f32), ("denominator", vp), ("stats", vp)])
-TensorDesc = _S("TensorDesc", [("p", vp), ("g", vp), ("s1", vp), ("s2", vp), ("n", i32), ("K", i32), ("C", i32),
+TensorDesc = _S("sslcr_tensor_desc", "TensorDesc", [("p", vp), ("g", vp), ("s1", vp), ("s2", vp), ("n", i32), ("K", i32), ("C", i32),
                                ("RS", i32), ("w_fwd", vp), ("w_dgrad", vp), ("pack_dtype", i32), ("dgrad_flip", i32),
                                ("group", i32)])
-OptDesc = _S("OptDesc", [("kind", i32), ("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("wd", f32),
+OptDesc = _S("sslcr_opt_desc", "OptDesc", [("kind", i32), ("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("wd", f32),
                          ("momentum", f32), ("bc1", f32), ("bc2", f32), ("first_step", i32), ("grad_scale", f32)])
-ClipDesc = _S("ClipDesc", [("max_norm", f32), ("out2", vp)])
+ClipDesc = _S("sslcr_clip_desc", "ClipDesc", [("max_norm", f32), ("out2", vp)])
 MAX_OPT_GROUPS = 8
-WeakAugDesc = _S("WeakAugDesc", [("src", vp), ("dst", vp), ("params", vp)] +
+WeakAugDesc = _S("sslcr_weak_aug_desc", "WeakAugDesc", [("src", vp), ("dst", vp), ("params", vp)] +
                  [(k, i32) for k in ("N", "SH", "SW", "OH", "OW", "src_hwc")])
-ColourAugDesc = _S("ColourAugDesc", [("src", vp), ("dst", vp), ("shift", vp), ("apply", vp), ("hed_from_rgb", f64 * 9),
+ColourAugDesc = _S("sslcr_colour_aug_desc", "ColourAugDesc", [("src", vp), ("dst", vp), ("shift", vp), ("apply", vp), ("hed_from_rgb", f64 * 9),
                                      ("rgb_from_hed", f64 * 9), ("N", i32), ("H", i32), ("W", i32), ("hwc", i32)])
-BrightnessContrastDesc = _S("BrightnessContrastDesc", [("src", vp), ("dst", vp), ("alpha_beta", vp), ("apply", vp), ("stats", vp),
+BrightnessContrastDesc = _S("sslcr_brightness_contrast_desc", "BrightnessContrastDesc", [("src", vp), ("dst", vp), ("alpha_beta", vp), ("apply", vp), ("stats", vp),
                                                        ("N", i32), ("H", i32), ("W", i32)])
-AugV2Desc = _S("AugV2Desc", [(k, vp) for k in ("src", "dst", "op", "factor", "fixed", "shift", "affine", "hist", "lsum", "lut", "tab")] +
+AugV2Desc = _S("sslcr_augv2_desc", "AugV2Desc", [(k, vp) for k in ("src", "dst", "op", "factor", "fixed", "shift", "affine", "hist", "lsum", "lut", "tab")] +
                 [("ops_mask", C.c_uint)] + [(k, i32) for k in ("N", "H", "W", "src_hwc", "dst_hwc")])
-AugV2ColourDesc = _S("AugV2ColourDesc", [("img", vp), ("op", vp), ("param", vp), ("bsum", vp), ("cutoff_lo", f64), ("cutoff_hi", f64),
+AugV2ColourDesc = _S("sslcr_augv2_colour_desc", "AugV2ColourDesc", [("img", vp), ("op", vp), ("param", vp), ("bsum", vp), ("cutoff_lo", f64), ("cutoff_hi", f64),
                                          ("hed_from_rgb", f32 * 9), ("rgb_from_hed", f32 * 9), ("ops_mask", C.c_uint)] +
                       [(k, i32) for k in ("N", "H", "W", "hwc")])
-WsiGatherDesc = _S("WsiGatherDesc", [("src", vp), ("xy", vp), ("dst", vp)] +
+WsiGatherDesc = _S("sslcr_wsi_gather_desc", "WsiGatherDesc", [("src", vp), ("xy", vp), ("dst", vp)] +
                    [(k, i32) for k in ("origin_x", "origin_y", "N", "RH", "RW", "S", "fill")])
-PredictDesc = _S("PredictDesc", [("logits", vp), ("n", i32), ("C", i32), ("target", vp), ("scores", vp), ("pred", vp), ("confusion", vp),
+PredictDesc = _S("sslcr_predict_desc", "PredictDesc", [("logits", vp), ("n", i32), ("C", i32), ("target", vp), ("scores", vp), ("pred", vp), ("confusion", vp),
                                  ("col", i32), ("map", vp), ("map_index", vp), ("map_size", C.c_int64)])
-D4Desc = _S("D4Desc", [("src", vp), ("dst", vp), ("orient", vp)] + [(k, i32) for k in ("N", "Cn", "H", "W", "elem_bytes")])
-PredictTtaDesc = _S("PredictTtaDesc", [("p", PredictDesc), ("G", i32), ("mode", i32)])
-TissueBitsDesc = _S("TissueBitsDesc", [("img", vp), ("bits", vp), ("lin", vp), ("thr_sum", vp), ("threshold", f64), ("factor", f64),
+D4Desc = _S("sslcr_d4_desc", "D4Desc", [("src", vp), ("dst", vp), ("orient", vp)] + [(k, i32) for k in ("N", "Cn", "H", "W", "elem_bytes")])
+PredictTtaDesc = _S("sslcr_predict_tta_desc", "PredictTtaDesc", [("p", PredictDesc), ("G", i32), ("mode", i32)])
+TISSUE_MODES = {"hsv_s": 0, "lab_a": 1}
+TissueBitsDesc = _S("sslcr_tissue_bits_desc", "TissueBitsDesc", [("img", vp), ("bits", vp), ("lin", vp), ("thr_sum", vp), ("threshold", f64), ("factor", f64),
                                        ("count", f64)] + [(k, i32) for k in ("H", "W", "pitch", "mode")])
-LAB_SUM_PARTIALS = 1024       # SSLCR_LAB_SUM_PARTIALS
-LabASumDesc = _S("LabASumDesc", [("img", vp), ("lin", vp), ("partials", vp), ("sum", vp), ("H", i32), ("W", i32)])
-TilePopcountDesc = _S("TilePopcountDesc", [("bits", vp), ("count", vp), ("keep", vp), ("thresh", f64)] +
+LAB_SUM_PARTIALS = 1024
+LabASumDesc = _S("sslcr_lab_a_sum_desc", "LabASumDesc", [("img", vp), ("lin", vp), ("partials", vp), ("sum", vp), ("H", i32), ("W", i32)])
+TilePopcountDesc = _S("sslcr_tile_popcount_desc", "TilePopcountDesc", [("bits", vp), ("count", vp), ("keep", vp), ("thresh", f64)] +
                       [(k, i32) for k in ("H", "W", "pitch", "ph", "pw", "sh", "sw", "ny", "nx")])
-RspGatherDesc = _S("RspGatherDesc", [("src", vp * 3), ("xy", vp * 3), ("idx", vp), ("dst", vp * 3), ("label", vp), ("RH", i32 * 3),
+RspGatherDesc = _S("sslcr_rsp_gather_desc", "RspGatherDesc", [("src", vp * 3), ("xy", vp * 3), ("idx", vp), ("dst", vp * 3), ("label", vp), ("RH", i32 * 3),
                                      ("RW", i32 * 3)] + [(k, i32) for k in ("T", "N", "S", "fill")])
-PIP_CHUNK = 256               # SSLCR_PIP_CHUNK
-PipDesc = _S("PipDesc", [("vertices", vp), ("offsets", vp), ("bounds", vp), ("points", vp), ("inside", vp), ("first", vp)] +
+PIP_CHUNK = 256
+PipDesc = _S("sslcr_pip_desc", "PipDesc", [("vertices", vp), ("offsets", vp), ("bounds", vp), ("points", vp), ("inside", vp), ("first", vp)] +
              [(k, C.c_int64) for k in ("x0", "y0", "step", "N")] + [(k, i32) for k in ("nx", "ny", "P", "V", "exact")])
-MapConfusionDesc = _S("MapConfusionDesc", [(k, vp) for k in ("map", "truth", "tissue", "thresholds", "confusion")] +
+MapConfusionDesc = _S("sslcr_map_confusion_desc", "MapConfusionDesc", [(k, vp) for k in ("map", "truth", "tissue", "thresholds", "confusion")] +
                       [(k, i32) for k in ("X", "Y", "T")])
-SMOOTH_MAX_R = 64             # SSLCR_SMOOTH_MAX_R
-LabelDesc = _S("LabelDesc", [(k, vp) for k in ("mask", "labels", "count", "work")] + [(k, i32) for k in ("X", "Y", "connectivity")])
-SmoothDesc = _S("SmoothDesc", [(k, vp) for k in ("src", "tmp", "dst", "weights")] + [(k, i32) for k in ("X", "Y", "R")])
-NmsDesc = _S("NmsDesc", [(k, vp) for k in ("map", "state", "cand", "stage", "counters", "det_xy", "det_prob")] + [("threshold", f32)] +
+SMOOTH_MAX_R = 64
+LABEL_RUN_CELLS = 1024        # cells per run of the labeller's numbering: one int32 of its scratch per run
+LabelDesc = _S("sslcr_label_desc", "LabelDesc", [(k, vp) for k in ("mask", "labels", "count", "work")] + [(k, i32) for k in ("X", "Y", "connectivity")])
+SmoothDesc = _S("sslcr_smooth_desc", "SmoothDesc", [(k, vp) for k in ("src", "tmp", "dst", "weights")] + [(k, i32) for k in ("X", "Y", "R")])
+NmsDesc = _S("sslcr_nms_desc", "NmsDesc", [(k, vp) for k in ("map", "state", "cand", "stage", "counters", "det_xy", "det_prob")] + [("threshold", f32)] +
              [(k, i32) for k in ("X", "Y", "radius", "max_detections", "ncand")])
-HitsDesc = _S("HitsDesc", [(k, vp) for k in ("labels", "det_xy", "det_prob", "n_det", "ignore", "hit", "tp_prob", "areas")] +
+HitsDesc = _S("sslcr_hits_desc", "HitsDesc", [(k, vp) for k in ("labels", "det_xy", "det_prob", "n_det", "ignore", "hit", "tp_prob", "areas")] +
               [(k, i32) for k in ("X", "Y", "L", "max_detections", "n_ignore")])
-EDT_ROW_CELLS = 1024          # SSLCR_EDT_ROW_CELLS
-EdtDesc = _S("EdtDesc", [(k, vp) for k in ("mask", "out", "below", "work")] + [(k, i32) for k in ("X", "Y", "limit", "invert")])
-FillDesc = _S("FillDesc", [(k, vp) for k in ("mask", "out", "labels", "count", "work")] + [(k, i32) for k in ("X", "Y")])
-MomentsDesc = _S("MomentsDesc", [(k, vp) for k in ("labels", "moments")] + [(k, i32) for k in ("X", "Y", "L")])
-SORT_TILE = 4096              # SSLCR_SORT_TILE
-RANK_SCAN_TRIP = 64           # SSLCR_RANK_SCAN_TRIP
-SortDesc = _S("SortDesc", [("keys", vp * 2), ("values", vp * 2), ("workspace", vp)] + [(k, i32) for k in ("B", "n", "lo", "hi")])
-RankKeysDesc = _S("RankKeysDesc", [(k, vp) for k in ("scores", "target", "valid", "positive", "keys", "values", "nan")] +
+EDT_ROW_CELLS = 1024
+EdtDesc = _S("sslcr_edt_desc", "EdtDesc", [(k, vp) for k in ("mask", "out", "below", "work")] + [(k, i32) for k in ("X", "Y", "limit", "invert")])
+FillDesc = _S("sslcr_fill_desc", "FillDesc", [(k, vp) for k in ("mask", "out", "labels", "count", "work")] + [(k, i32) for k in ("X", "Y")])
+MomentsDesc = _S("sslcr_moments_desc", "MomentsDesc", [(k, vp) for k in ("labels", "moments")] + [(k, i32) for k in ("X", "Y", "L")])
+SORT_TILE = 4096
+RANK_SCAN_TRIP = 64
+SortDesc = _S("sslcr_sort_desc", "SortDesc", [("keys", vp * 2), ("values", vp * 2), ("workspace", vp)] + [(k, i32) for k in ("B", "n", "lo", "hi")])
+RankKeysDesc = _S("sslcr_rank_keys_desc", "RankKeysDesc", [(k, vp) for k in ("scores", "target", "valid", "positive", "keys", "values", "nan")] +
                   [("n", i32), ("C", i32)])
-AucDesc = _S("AucDesc", [(k, vp) for k in ("keys", "values", "nan", "counts", "work")] + [("n", i32), ("C", i32)])
-RESAMPLE_FILTERS = {"nearest": 0, "lanczos": 1, "bilinear": 2, "bicubic": 3, "box": 4, "hamming": 5}     # SSLCR_RESAMPLE_* = Pillow's codes
-RESAMPLE_FORMS = ("gather", "fused", "two_pass", "horizontal", "vertical")                             # SSLCR_RESAMPLE_GATHER ..
-RESAMPLE_LDS_CAP = 65536      # SSLCR_RESAMPLE_LDS_CAP
-ResampleDesc = _S("ResampleDesc", [(k, vp) for k in ("src", "dst", "kx", "bx", "ky", "by", "table_index", "bx_host", "by_host", "workspace")] +
+AucDesc = _S("sslcr_auc_desc", "AucDesc", [(k, vp) for k in ("keys", "values", "nan", "counts", "work")] + [("n", i32), ("C", i32)])
+RESAMPLE_FILTERS = {"nearest": 0, "lanczos": 1, "bilinear": 2, "bicubic": 3, "box": 4, "hamming": 5}     # Pillow's codes
+RESAMPLE_FORMS = ("gather", "fused", "two_pass", "horizontal", "vertical")
+RESAMPLE_LDS_CAP = 65536
+ResampleDesc = _S("sslcr_resample_desc", "ResampleDesc", [(k, vp) for k in ("src", "dst", "kx", "bx", "ky", "by", "table_index", "bx_host", "by_host", "workspace")] +
                   [(k, i32) for k in ("N", "C", "IH", "IW", "OH", "OW", "ksx", "ksy", "T", "src_chw", "dst_chw", "nearest", "form")])
-ResamplePlan = _S("ResamplePlan", [(k, i32) for k in ("form", "fused_ok", "tile_w", "tile_h", "rows", "cols")] + [("grid", i32 * 2),
+ResamplePlan = _S("sslcr_resample_plan_info", "ResamplePlan", [(k, i32) for k in ("form", "fused_ok", "tile_w", "tile_h", "rows", "cols")] + [("grid", i32 * 2),
                                                                                                                 ("lds_bytes", sz), ("workspace_bytes", sz)])
-PackDesc = _S("PackDesc", [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("gamma", vp), ("beta", vp), ("rmean", vp),
+PackDesc = _S("sslcr_pack_desc", "PackDesc", [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("gamma", vp), ("beta", vp), ("rmean", vp),
                            ("rvar", vp), ("eps", f32), ("bias_out", vp)] + [(k, i32) for k in ("K", "C", "R", "S", "dgrad_flip")] + [("scale_out", vp)])
 
-Fp8Desc = _S("Fp8Desc", [("w8", vp), ("w_dequant", vp), ("x_scale", f32), ("x_scale_dev", vp), ("amax_out", vp)])
-PackFp8Desc = _S("PackFp8Desc", [("w", vp), ("w8", vp), ("w_dequant", vp), ("gamma", vp), ("beta", vp), ("rmean", vp), ("rvar", vp),
+Fp8Desc = _S("sslcr_fp8_desc", "Fp8Desc", [("w8", vp), ("w_dequant", vp), ("x_scale", f32), ("x_scale_dev", vp), ("amax_out", vp)])
+PackFp8Desc = _S("sslcr_pack_fp8_desc", "PackFp8Desc", [("w", vp), ("w8", vp), ("w_dequant", vp), ("gamma", vp), ("beta", vp), ("rmean", vp), ("rvar", vp),
                                  ("eps", f32), ("bias_out", vp), ("K", i32), ("C", i32)])
+
+# SSLCR_* macro of include/sslcr.h -> its value on this side: the one place a mirrored #define is registered (tests/test_abi_cpu.py
+# holds every entry to the header)
+CONSTANTS = {"SSLCR_MAX_OPT_GROUPS": MAX_OPT_GROUPS, "SSLCR_LAB_SUM_PARTIALS": LAB_SUM_PARTIALS, "SSLCR_PIP_CHUNK": PIP_CHUNK,
+             "SSLCR_SMOOTH_MAX_R": SMOOTH_MAX_R, "SSLCR_LABEL_RUN_CELLS": LABEL_RUN_CELLS, "SSLCR_EDT_ROW_CELLS": EDT_ROW_CELLS,
+             "SSLCR_SORT_TILE": SORT_TILE, "SSLCR_RANK_SCAN_TRIP": RANK_SCAN_TRIP, "SSLCR_RESAMPLE_LDS_CAP": RESAMPLE_LDS_CAP}
+CONSTANTS.update({"SSLCR_TISSUE_" + k.upper(): v for k, v in TISSUE_MODES.items()})
+CONSTANTS.update({"SSLCR_RESAMPLE_" + k.upper(): v for k, v in RESAMPLE_FILTERS.items()})
+CONSTANTS.update({"SSLCR_RESAMPLE_" + k.upper(): v for v, k in enumerate(RESAMPLE_FORMS)})
 
 # symbol -> (restype, argtypes); every symbol include/sslcr.h declares
 P = C.POINTER

@@ -42,6 +42,25 @@ def header_symbols():
     return sorted(set(re.findall(r"\b(sslcr_[a-z0-9_]+)\s*\(", text)))
 
 
+def header_defines():
+    """the integer #defines of include/sslcr.h: macro name -> value"""
+    import re
+    with open(os.path.join(os.path.dirname(HERE), "include", "sslcr.h")) as f:
+        return {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define (SSLCR_\w+)[ \t]+(\d+)\b", f.read(), flags=re.M)}
+
+
+def header_structs():
+    """the structs include/sslcr.h defines (typedef struct ... { ... } name;): name -> the names of its fields, in order"""
+    import re
+    with open(os.path.join(os.path.dirname(HERE), "include", "sslcr.h")) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    out = {}
+    for m in re.finditer(r"typedef struct \w+ \{(.*?)\}\s*(sslcr_\w+);", text, flags=re.S):
+        decls = [d for d in m.group(1).split(";") if d.strip()]
+        out[m.group(2)] = [re.sub(r"\[.*", "", part).split()[-1].lstrip("*") for d in decls for part in d.split(",")]
+    return out
+
+
 def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objdir = os.path.join(HERE, "build")

@@ -8,6 +8,7 @@
 // addition, in that order; a contracted multiply-add would round once where the definition rounds twice.
 // No floating-point atomics.  The point kernel has no atomics at all; the confusion kernel counts in integers.
 #include "kernels.hpp"
+#include "softmax_row.hpp"   // confusion_flush_cell
 
 namespace sslcr {
 
@@ -171,7 +172,7 @@ hipError_t launch_points_in_polygons(const sslcr_pip_desc& a, hipStream_t st) {
 // A wave takes 64 cells at a time; for threshold t (a wave-uniform loop) two ballots count the tissue cells at or above the threshold
 // among the tumour and among the normal cells, and LANE t adds the two popcounts to its own registers: nothing is shared while the map
 // is read.  At the end the lanes add their counts to the workgroup's LDS counters (32-bit integer atomics; a workgroup sees fewer than
-// 2^31 cells), and one thread per counter adds it to the caller's int64 matrix (64-bit integer atomics, as sslcr_predict does).
+// 2^31 cells), and one thread per counter adds it to the caller's int64 matrix (confusion_flush_cell, as sslcr_predict does).
 // Integer sums: any order gives the same counts.
 __global__ __launch_bounds__(256) void map_confusion_kernel(const sslcr_map_confusion_desc a) {
   __shared__ unsigned cells[64 * 4];
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(256) void map_confusion_kernel(const sslcr_map_conf
     atomicAdd(&cells[4 * lane + 3], ge1);
   }
   __syncthreads();
-  if (t < 4 * a.T && cells[t]) atomicAdd(reinterpret_cast<unsigned long long*>(a.confusion) + t, (unsigned long long)cells[t]);
+  if (t < 4 * a.T) confusion_flush_cell(cells, t, a.confusion);
 }
 
 hipError_t launch_map_confusion(const sslcr_map_confusion_desc& a, hipStream_t st) {

@@ -23,6 +23,7 @@
 //   augv2c_apply_kernel  4 pixels per thread as dwords of the byte planes (CHW) or one 12-byte group (HWC), no LDS.  hsv is float64
 //                        (+ - x / floor and an exact remainder only: bit-reproducible), hed float32 with the accurate logf / expf
 #include "kernels.hpp"
+#include "wsi_bytes.hpp"   // byte_of
 
 namespace sslcr {
 namespace {
@@ -33,9 +34,6 @@ __device__ inline bool uses_lut(int op) { return op == SSLCR_AUGV2_BRIGHTNESS ||
 __device__ inline bool uses_factor(int op) {
   return op == SSLCR_AUGV2_BRIGHTNESS || op == SSLCR_AUGV2_CONTRAST || op == SSLCR_AUGV2_COLOR || op == SSLCR_AUGV2_SHARPNESS;
 }
-
-// byte k of a little-endian word array
-__device__ inline uint32_t byte_of(const uint32_t* w, int k) { return (w[k >> 2] >> (8 * (k & 3))) & 255u; }
 
 // P consecutive pixels of one image, planar in registers: byte e of w[c] is channel c of pixel p0 + e.  vec: the whole batch is
 // P-byte tileable (H*W % P == 0 and a P-byte aligned base: 16 bytes for P = 16, a dword for P = 4), so cnt == P and the accesses are
@@ -76,7 +74,10 @@ __device__ inline void load_px(Px<P>& p, const uint8_t* img, int hwc, size_t hw,
         for (int q = 0; q < Q; ++q) {
           uint32_t v = 0;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v |= byte_of(raw, 3 * (4 * q + e) + c) << (8 * e);
+          for (int e = 0; e < 4; ++e) {
+            const int k = 3 * (4 * q + e) + c;         // byte k of the interleaved run
+            v |= byte_of(raw[k >> 2], k & 3) << (8 * e);
+          }
           p.w[c][q] = v;
         }
     }
@@ -115,7 +116,7 @@ __device__ inline void store_px(const Px<P>& p, uint8_t* img, int hwc, size_t hw
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
           const int k = 4 * i + b;                     // byte k of the interleaved run = channel k % 3 of pixel k / 3
-          v |= byte_of(p.w[k % 3], k / 3) << (8 * b);
+          v |= byte_of(p.w[k % 3][(k / 3) >> 2], (k / 3) & 3) << (8 * b);
         }
         raw[i] = v;
       }
@@ -133,7 +134,7 @@ __device__ inline void store_px(const Px<P>& p, uint8_t* img, int hwc, size_t hw
   for (int c = 0; c < 3; ++c)
 #pragma unroll
     for (int i = 0; i < P; ++i)
-      if (i < cnt) img[hwc ? (p0 + i) * 3 + c : c * hw + p0 + i] = (uint8_t)byte_of(p.w[c], i);
+      if (i < cnt) img[hwc ? (p0 + i) * 3 + c : c * hw + p0 + i] = (uint8_t)byte_of(p.w[c][i >> 2], i & 3);
 }
 
 // Image.blend(degenerate, image, f) for one byte: float32 product, float32 sum, clip, truncate.  For 0 <= f <= 1 Pillow skips the
@@ -182,7 +183,7 @@ __global__ __launch_bounds__(256) void augv2_stats_kernel(const sslcr_augv2_desc
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       if (e < cnt) {
-        const uint32_t r = byte_of(p.w[0], e), g = byte_of(p.w[1], e), b = byte_of(p.w[2], e);
+        const uint32_t r = byte_of(p.w[0][e >> 2], e & 3), g = byte_of(p.w[1][e >> 2], e & 3), b = byte_of(p.w[2][e >> 2], e & 3);
         if (hist) {
           atomicAdd(&h[wave][0][r], 1u);
           atomicAdd(&h[wave][1][g], 1u);
@@ -306,7 +307,7 @@ __global__ __launch_bounds__(256) void augv2_apply_kernel(const sslcr_augv2_desc
           for (int q = 0; q < 4; ++q) {
             uint32_t v = 0;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v |= (uint32_t)lut[c * 256 + byte_of(p.w[c], 4 * q + e)] << (8 * e);
+            for (int e = 0; e < 4; ++e) v |= (uint32_t)lut[c * 256 + byte_of(p.w[c][q], e)] << (8 * e);
             p.w[c][q] = v;
           }
       } else if (op == SSLCR_AUGV2_COLOR) {          // the degenerate image is L on all three channels
@@ -315,7 +316,7 @@ __global__ __launch_bounds__(256) void augv2_apply_kernel(const sslcr_augv2_desc
           uint32_t v[3] = {0, 0, 0};
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const uint32_t r = byte_of(p.w[0], 4 * q + e), g = byte_of(p.w[1], 4 * q + e), b = byte_of(p.w[2], 4 * q + e);
+            const uint32_t r = byte_of(p.w[0][q], e), g = byte_of(p.w[1][q], e), b = byte_of(p.w[2][q], e);
             const int l = (int)luma8(r, g, b);
             v[0] |= blend8(l, (int)r, f) << (8 * e);
             v[1] |= blend8(l, (int)g, f) << (8 * e);

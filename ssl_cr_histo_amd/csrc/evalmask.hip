@@ -7,7 +7,7 @@
 // border pass stores the constant 1: no result depends on the order in which they land.  Work proceeds between workgroups through
 // launch boundaries only; no kernel waits for another workgroup, and every loop states its bound.
 #include "kernels.hpp"
-#include "wave_scan.hpp"
+#include "map_common.hpp"
 
 namespace sslcr {
 
@@ -25,15 +25,6 @@ namespace sslcr {
 constexpr int EDT_ROW_CELLS = SSLCR_EDT_ROW_CELLS, EDT_NONE = 0x7fffffff;
 constexpr int EDT_FAR = 1 << 30;                    // "no zero seen": |EDT_FAR| + a coordinate stays inside an int32
 static_assert(EDT_ROW_CELLS == 4 * 256, "one dword per thread and chunk");
-
-// the four mask bytes of the aligned dword at flat address addr; bytes past the end of the array read as "not there"
-__device__ __forceinline__ unsigned mask_dword(const unsigned char* mask, int64_t addr, int64_t n) {
-  if (addr + 4 <= n) return *reinterpret_cast<const unsigned*>(mask + addr);
-  unsigned v = 0;
-  for (int j = 0; j < 4; ++j)
-    if (addr + j < n) v |= (unsigned)mask[addr + j] << (8 * j);
-  return v;
-}
 
 __global__ __launch_bounds__(256) void edt_rows_kernel(const sslcr_edt_desc a) {
   __shared__ int sh[4];
@@ -196,6 +187,7 @@ __global__ __launch_bounds__(256) void region_moments_kernel(const sslcr_moments
     int label = g < n ? a.labels[g] : 0;
     if (label < 1 || label > a.L) label = 0;
     const unsigned long long x = g < n ? (unsigned long long)(g / a.Y) : 0, y = g < n ? (unsigned long long)(g % a.Y) : 0;
+    // lesion_hits_kernel's walk over the labels (froc.hip); both keep it inline: a shared helper changes the code of both kernels
     unsigned long long todo = __ballot(label != 0);
     for (int k = 0; k < 64 && todo; ++k) {                                   // bound: 64 lanes hold at most 64 distinct labels
       const int which = __shfl(label, __ffsll(todo) - 1);

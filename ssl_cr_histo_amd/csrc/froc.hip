@@ -8,6 +8,7 @@
 // Every atomic here is an integer min, max or add: the results do not depend on the order in which they land.  Work proceeds
 // between workgroups through launch boundaries only; no kernel waits for another workgroup, and every loop states its bound.
 #include "kernels.hpp"
+#include "map_common.hpp"
 
 namespace sslcr {
 
@@ -22,7 +23,8 @@ namespace sslcr {
 //   cc_flatten   parent[g] = root, and the number of roots of every run of CC_SCAN cells
 //   cc_offsets   one workgroup: exclusive scan of those counts in run order (= row-major order), and L
 //   cc_number    the roots get their number (stored as -(number) - 1 in parent), then cc_relabel writes labels
-constexpr int CC_TX = 16, CC_TY = 64, CC_CELLS = CC_TX * CC_TY, CC_SCAN = 1024;
+constexpr int CC_TX = 16, CC_TY = 64, CC_CELLS = CC_TX * CC_TY, CC_SCAN = SSLCR_LABEL_RUN_CELLS;
+static_assert(CC_SCAN == 4 * 256, "a run is one workgroup's cells, four per thread");
 constexpr int CC_ROW_DWORDS = CC_TY / 4 + 1;     // aligned dwords that cover CC_TY bytes starting anywhere
 
 __device__ __forceinline__ int cc_find(const int* parent, int i) {
@@ -66,13 +68,7 @@ __global__ __launch_bounds__(256) void cc_local_kernel(const sslcr_label_desc a,
     if (r >= nxr) continue;
     const int64_t start = (int64_t)(x0 + r) * a.Y + y0, addr = (start & ~(int64_t)3) + 4 * k;
     if (addr >= start + nyr) continue;
-    unsigned v = 0;
-    if (addr + 4 <= n) {
-      v = *reinterpret_cast<const unsigned*>(a.mask + addr);
-    } else {                                      // the last, partial dword of the array: bytes, none past the end
-      for (int j = 0; j < 4; ++j)
-        if (addr + j < n) v |= (unsigned)a.mask[addr + j] << (8 * j);
-    }
+    const unsigned v = mask_dword(a.mask, addr, n);
     for (int j = 0; j < 4; ++j) {
       const int64_t c = addr + j - start;
       if (c >= 0 && c < nyr) m[r][c] = (unsigned char)((v >> (8 * j)) & 0xffu);
@@ -129,26 +125,9 @@ __global__ __launch_bounds__(256) void cc_borders_kernel(const sslcr_label_desc 
   }
 }
 
-// the workgroup's 256 values -> their exclusive prefix sums (in thread order) and the total, through LDS
-__device__ __forceinline__ int block_exclusive_scan(int v, int* sh, int* total) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    const int u = t >= d ? sh[t - d] : 0;
-    __syncthreads();
-    sh[t] += u;
-    __syncthreads();
-  }
-  const int incl = sh[t];
-  *total = sh[255];
-  __syncthreads();
-  return incl - v;
-}
-
-// thread t of run b holds the cells b * CC_SCAN + 4 t .. + 3
+// thread t of run b holds the cells b * CC_SCAN + 4 t .. + 3; all 256 threads of the three kernels below reach block_excl_sum
 __global__ __launch_bounds__(256) void cc_flatten_kernel(const sslcr_label_desc a, int* run_roots) {
-  __shared__ int sh[256];
+  __shared__ int sh[4];
   const int64_t n = (int64_t)a.X * a.Y, base = (int64_t)blockIdx.x * CC_SCAN + 4 * threadIdx.x;
   int roots = 0;
   for (int j = 0; j < 4; ++j) {
@@ -159,18 +138,18 @@ __global__ __launch_bounds__(256) void cc_flatten_kernel(const sslcr_label_desc 
     else a.work[g] = r;                           // a root keeps itself; any value a concurrent walk reads here is an ancestor
   }
   int total;
-  block_exclusive_scan(roots, sh, &total);
+  block_excl_sum(roots, sh, &total);
   if (threadIdx.x == 0) run_roots[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(256) void cc_offsets_kernel(int* run_roots, int runs, int* count) {
-  __shared__ int sh[256];
+  __shared__ int sh[4];
   int carry = 0;
   for (int base = 0; base < runs; base += 256) {  // bound: runs / 256 rounds
     const int i = base + threadIdx.x;
     const int v = i < runs ? run_roots[i] : 0;
     int total;
-    const int ex = block_exclusive_scan(v, sh, &total);
+    const int ex = block_excl_sum(v, sh, &total);
     if (i < runs) run_roots[i] = carry + ex;
     carry += total;
   }
@@ -178,7 +157,7 @@ __global__ __launch_bounds__(256) void cc_offsets_kernel(int* run_roots, int run
 }
 
 __global__ __launch_bounds__(256) void cc_number_kernel(const sslcr_label_desc a, const int* run_offsets) {
-  __shared__ int sh[256];
+  __shared__ int sh[4];
   const int64_t n = (int64_t)a.X * a.Y, base = (int64_t)blockIdx.x * CC_SCAN + 4 * threadIdx.x;
   bool root[4];
   int mine = 0;
@@ -188,7 +167,7 @@ __global__ __launch_bounds__(256) void cc_number_kernel(const sslcr_label_desc a
     mine += root[j];
   }
   int total;
-  int number = run_offsets[blockIdx.x] + block_exclusive_scan(mine, sh, &total);
+  int number = run_offsets[blockIdx.x] + block_excl_sum(mine, sh, &total);
   for (int j = 0; j < 4; ++j)
     if (root[j]) a.work[base + j] = -(++number) - 1;      // <= -2: a numbered root; -1 stays the zero cell
 }
@@ -257,7 +236,7 @@ __global__ __launch_bounds__(256) void nms_candidates_kernel(const sslcr_nms_des
   const int64_t n = (int64_t)a.X * a.Y, g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const bool cand = g < n && a.map[g] > a.threshold;                         // a NaN compares false
   if (g < n) a.state[g] = cand ? NMS_UNDECIDED : NMS_NONE;
-  const unsigned long long votes = __ballot(cand);
+  const unsigned long long votes = __ballot(cand);                           // wave_vote_add's add, and a slot for every voting lane
   if (!votes) return;
   const int lane = threadIdx.x & 63, leader = __ffsll(votes) - 1;
   int base = 0;
@@ -289,13 +268,7 @@ __global__ __launch_bounds__(256) void nms_round_kernel(const sslcr_nms_desc a, 
       for (int qx = qx0; qx <= qx1 && !suppressed; ++qx) {                   // bound: at most (2 r)^2 cells, clipped to the map
         const int64_t lo = (int64_t)qx * a.Y + qy0, hi = (int64_t)qx * a.Y + qy1;
         for (int64_t w = lo & ~(int64_t)3; w <= hi && !suppressed; w += 4) {
-          unsigned v = 0;
-          if (w + 4 <= n) {
-            v = *reinterpret_cast<const unsigned*>(a.state + w);
-          } else {                                                           // the array's last, partial dword: bytes, none past the end
-            for (int j = 0; j < 4; ++j)
-              if (w + j < n) v |= (unsigned)a.state[w + j] << (8 * j);
-          }
+          const unsigned v = mask_dword(a.state, w, n);
           if (!(zero_bytes(v ^ 0x02020202u) | (waits ? 0u : zero_bytes(v ^ 0x01010101u)))) continue;
           for (int j = 0; j < 4; ++j) {
             const int64_t q = w + j;
@@ -316,10 +289,7 @@ __global__ __launch_bounds__(256) void nms_round_kernel(const sslcr_nms_desc a, 
       else left = true;
     }
   }
-  if (count_left) {
-    const unsigned long long votes = __ballot(left);
-    if (votes && (threadIdx.x & 63) == __ffsll(votes) - 1) atomicAdd(&a.counters[1], __popcll(votes));
-  }
+  if (count_left) wave_vote_add(&a.counters[1], left);
 }
 
 // the selected candidates, in any order, into the staging list (the upper half of det_xy / det_prob's workspace `stage`)
@@ -411,7 +381,7 @@ __global__ __launch_bounds__(256) void lesion_hits_kernel(const sslcr_hits_desc 
     const int64_t g = base + 64 * j + lane;
     int label = g < n ? a.labels[g] : 0;
     if (label < 1 || label > a.L) label = 0;
-    unsigned long long todo = __ballot(label != 0);
+    unsigned long long todo = __ballot(label != 0);                          // (region_moments_kernel, evalmask.hip, walks its labels alike)
     for (int k = 0; k < 64 && todo; ++k) {                                   // bound: 64 lanes hold at most 64 distinct labels
       const int which = __shfl(label, __ffsll(todo) - 1);
       const unsigned long long same = __ballot(label == which);

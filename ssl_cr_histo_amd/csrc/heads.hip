@@ -503,15 +503,12 @@ hipError_t launch_softmax_col(const float* logits, float* out, int n, int C, int
 
 // sslcr_predict: what the reference's test() loops take from a batch of logits (eval_Kather_SSL_CR.py:211-226, eval_Kather_SSL.py:190-195,
 // test_Camelyon16.py:58-62), one row per thread, every output optional.  torch.argmax's tie and NaN rules: the lowest index of the
-// maximum, a NaN is the maximum.  The confusion matrix is counted per workgroup in LDS (32-bit integer atomics, at most 256 per cell)
-// and flushed with one 64-bit integer atomic per non-empty cell: exact and order-independent, it accumulates across calls.
+// maximum, a NaN is the maximum (argmax_step).  The confusion matrix is counted per workgroup in LDS and flushed per non-empty cell
+// (softmax_row.hpp): exact and order-independent, it accumulates across calls.
 __global__ __launch_bounds__(256) void predict_kernel(const sslcr_predict_desc a) {
-  __shared__ unsigned cells[64 * 64];
+  __shared__ unsigned cells[CONFUSION_MAX_C * CONFUSION_MAX_C];
   const int C = a.C;
-  if (a.confusion) {
-    for (int k = threadIdx.x; k < C * C; k += 256) cells[k] = 0u;
-    __syncthreads();
-  }
+  if (a.confusion) confusion_clear(cells, C * C);
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i < a.n) {
     const float* l = a.logits + i * C;
@@ -529,21 +526,13 @@ __global__ __launch_bounds__(256) void predict_kernel(const sslcr_predict_desc a
       int b = 0;
       float m = l[0];
       for (int c = 1; c < C; ++c) {
-        const float v = l[c];
-        if (m == m && (v > m || v != v)) { m = v; b = c; }       // once m is a NaN it stays: the lowest NaN index wins
+        argmax_step(m, b, l[c], c);
       }
       if (a.pred) a.pred[i] = b;
-      if (a.confusion) {
-        const int64_t y = a.target[i];
-        if (y >= 0 && y < C) atomicAdd(&cells[(int)y * C + b], 1u);
-      }
+      if (a.confusion) confusion_count(cells, C, a.target[i], b);
     }
   }
-  if (a.confusion) {
-    __syncthreads();
-    for (int k = threadIdx.x; k < C * C; k += 256)
-      if (cells[k]) atomicAdd(reinterpret_cast<unsigned long long*>(a.confusion) + k, (unsigned long long)cells[k]);
-  }
+  if (a.confusion) confusion_flush(cells, C * C, a.confusion);
 }
 hipError_t launch_predict(const sslcr_predict_desc& a, hipStream_t st) {
   if (a.n == 0) return hipSuccess;

@@ -12,6 +12,7 @@
 // once where NumPy rounds twice), which is what makes the hsv_s plane EQUAL to a NumPy restatement.
 // No floating-point atomics, no integer atomics, no byte stores to the bit plane.
 #include "kernels.hpp"
+#include "map_common.hpp"   // wave_sum
 #include "wsi_bytes.hpp"   // wsi_fetch12, wsi_plane: the read side of the tile gathers
 
 namespace sslcr {
@@ -195,8 +196,7 @@ __global__ __launch_bounds__(256) void tile_popcount_kernel(const sslcr_tile_pop
       cnt += __popc(v);
     }
   }
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) cnt += __shfl_xor(cnt, s);
+  cnt = wave_sum(cnt);
   if (lane == 0) {
     a.count[cand] = cnt;
     a.keep[cand] = (uint8_t)((double)cnt / (double)((int64_t)a.ph * a.pw) >= a.thresh);

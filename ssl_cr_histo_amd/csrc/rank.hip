@@ -6,7 +6,7 @@
 // is an integer add whose order does not reach the result, so two calls give equal bits.  Work proceeds between workgroups through
 // launch boundaries only: no kernel waits for another workgroup, there is no look-back and no ticket, and every loop states its bound.
 #include "kernels.hpp"
-#include "wave_scan.hpp"
+#include "map_common.hpp"
 
 namespace sslcr {
 
@@ -14,38 +14,6 @@ constexpr int SORT_TILE = SSLCR_SORT_TILE, SORT_ITEMS = SORT_TILE / 256, SORT_RA
 static_assert(SORT_TILE == 4096 && SORT_ITEMS == 16, "a wave owns 16 chunks of 64 consecutive keys; the AUC kernels pack 16 flags per thread");
 static_assert(SCAN_TRIP == 64, "one trip of a partial scan is one wave");
 
-// inclusive sum / max over the wave's 64 lanes, in lane order; every lane must be active
-__device__ __forceinline__ int wave_incl_sum(int v) {
-  const int lane = threadIdx.x & 63;
-  for (int d = 1; d < 64; d <<= 1) {                // bound: 6 steps
-    const int u = __shfl_up(v, d);
-    if (lane >= d) v += u;
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_incl_max(int v) {
-  const int lane = threadIdx.x & 63;
-  for (int d = 1; d < 64; d <<= 1) {                // bound: 6 steps
-    const int u = __shfl_up(v, d);
-    if (lane >= d) v = max(v, u);
-  }
-  return v;
-}
-// exclusive sum over the workgroup's 256 values in thread order; *total = the sum over all; sh: 4 ints
-__device__ __forceinline__ int block_excl_sum(int v, int* sh, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int incl = wave_incl_sum(v);
-  if (lane == 63) sh[w] = incl;
-  __syncthreads();
-  int off = 0, all = 0;
-  for (int k = 0; k < 4; ++k) {
-    all += sh[k];
-    if (k < w) off += sh[k];
-  }
-  *total = all;
-  __syncthreads();
-  return off + incl - v;
-}
 // ------------------------------------------------------------------------------------------------ 1. radix sort
 // One pass over the digit (key >> shift) & mask, three launches:
 //   sort_hist     workgroup (tile, row): the tile's digit counts by LDS adds -> hist[row][digit][tile]
@@ -196,7 +164,6 @@ hipError_t launch_sort_pairs(const sslcr_sort_desc& a, hipStream_t st) {
 
 // ------------------------------------------------------------------------------------------------ 2. keys and class values
 __global__ __launch_bounds__(256) void rank_keys_kernel(const sslcr_rank_keys_desc a) {
-  const int lane = threadIdx.x & 63;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const bool in = i < a.n;
   const uint32_t* bits = reinterpret_cast<const uint32_t*>(a.scores);
@@ -214,8 +181,7 @@ __global__ __launch_bounds__(256) void rank_keys_kernel(const sslcr_rank_keys_de
       a.keys[(int64_t)c * a.n + i] = key;
       a.values[(int64_t)c * a.n + i] = value;
     }
-    const unsigned long long nans = __ballot(is_nan);
-    if (nans && lane == 0) atomicAdd(nan + c, (unsigned long long)__popcll(nans));
+    wave_vote_add(nan + c, is_nan);
   }
 }
 

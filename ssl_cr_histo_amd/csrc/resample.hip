@@ -25,6 +25,7 @@
 #include <string.h>
 
 #include "kernels.hpp"
+#include "wsi_bytes.hpp"   // byte_of
 
 namespace sslcr {
 namespace {
@@ -46,7 +47,6 @@ __host__ __device__ inline Lay lay_of(int chw, int C, int H, int W) {
 // bits 31:16 of that register being zero, which this kernel's bytes 2 and 3 showed they are not.  To check: spell it
 // min(max(acc >> RS_BITS, 0), 255), look for the instruction in the fused kernel's ISA, run tests/test_resize_gpu.py.
 __device__ inline uint32_t clip8(int acc) { return (uint32_t)min(max(acc, 0), (256 << RS_BITS) - 1) >> RS_BITS; }
-__device__ inline uint32_t byte_of(uint32_t v, int i) { return (v >> (8 * i)) & 255u; }
 __device__ inline int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 __device__ inline int table_of(const int32_t* table_index, int T, int64_t n) { return table_index ? clampi(table_index[n], 0, T - 1) : 0; }
 

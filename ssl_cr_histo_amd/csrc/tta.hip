@@ -261,16 +261,12 @@ hipError_t launch_d4_transform(const sslcr_d4_desc& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-// sslcr_predict_tta.  The confusion matrix as predict_kernel counts it: per workgroup in LDS (32-bit integer atomics, at most 256 per
-// cell), flushed with one 64-bit integer atomic per non-empty cell -- one count per ROW, whatever G.
+// sslcr_predict_tta.  The confusion matrix as predict_kernel counts it (softmax_row.hpp) -- one count per ROW, whatever G.
 __global__ __launch_bounds__(256) void predict_tta_kernel(const sslcr_predict_tta_desc t) {
-  __shared__ unsigned cells[64 * 64];
+  __shared__ unsigned cells[CONFUSION_MAX_C * CONFUSION_MAX_C];
   const sslcr_predict_desc& a = t.p;
   const int C = a.C, G = t.G;
-  if (a.confusion) {
-    for (int k = threadIdx.x; k < C * C; k += 256) cells[k] = 0u;
-    __syncthreads();
-  }
+  if (a.confusion) confusion_clear(cells, C * C);
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i < a.n) {
     const size_t set = (size_t)a.n * C;                                  // floats between two members' logits
@@ -304,22 +300,14 @@ __global__ __launch_bounds__(256) void predict_tta_kernel(const sslcr_predict_tt
       const float key = G == 1 ? l0[c] : v;                              // G == 1: sslcr_predict's own argmax, over the logits
       if (c == 0) {
         best = key;
-      } else if (best == best && (key > best || key != key)) {           // once best is a NaN it stays: the lowest NaN index wins
-        best = key;
-        b = c;
+      } else {
+        argmax_step(best, b, key, c);
       }
     }
     if (a.pred) a.pred[i] = b;
-    if (a.confusion) {
-      const int64_t y = a.target[i];
-      if (y >= 0 && y < C) atomicAdd(&cells[(int)y * C + b], 1u);
-    }
+    if (a.confusion) confusion_count(cells, C, a.target[i], b);
   }
-  if (a.confusion) {
-    __syncthreads();
-    for (int k = threadIdx.x; k < C * C; k += 256)
-      if (cells[k]) atomicAdd(reinterpret_cast<unsigned long long*>(a.confusion) + k, (unsigned long long)cells[k]);
-  }
+  if (a.confusion) confusion_flush(cells, C * C, a.confusion);
 }
 
 hipError_t launch_predict_tta(const sslcr_predict_tta_desc& a, hipStream_t st) {

@@ -1,10 +1,14 @@
-// The read side of the WSI tile gathers (wsi.hip: wsi_gather_kernel, tta.hip: the oriented gather): four RGB pixels of one region row
+// Bytes in registers.  byte_of: byte i of a little-endian dword, for every kernel that keeps pixels as dwords (augment_v2.hip,
+// resample.hip, the gathers below).  The read side of the WSI tile gathers (wsi.hip: wsi_gather_kernel, tta.hip: the oriented gather): four RGB pixels of one region row
 // are 12 contiguous, UNALIGNED source bytes; they are fetched as the 3 or 4 ALIGNED dwords that cover them, shifted into three dwords
 // and deinterleaved into one dword per colour plane in registers.  wsi.hip's header comment has the reasoning and the measurements.
 #pragma once
 #include "common.hpp"
 
 namespace sslcr {
+
+// byte i (0..3) of a little-endian dword
+__device__ __forceinline__ uint32_t byte_of(uint32_t v, int i) { return (v >> (8 * i)) & 255u; }
 
 // the 12 bytes at src + off as three dwords R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3.  mis = (address of src) & 3.  Never a byte load:
 // a dword that holds at least one wanted byte lies in that byte's page, so no load leaves the pages of the region.  The pointer stays
@@ -26,7 +30,7 @@ __device__ __forceinline__ uint32_t wsi_plane(const uint32_t d[3], int c) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int k = 3 * e + c;
-    v |= ((d[k >> 2] >> (8 * (k & 3))) & 0xffu) << (8 * e);
+    v |= byte_of(d[k >> 2], k & 3) << (8 * e);
   }
   return v;
 }

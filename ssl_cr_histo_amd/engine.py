@@ -14,19 +14,19 @@ from .net import Classifier, FinetuneResNet, TripletNet, TripletNet_Finetune, un
 
 _DTYPES = {"fp32": 0, "f32": 0, "float32": 0, "bf16": 1, "bfloat16": 1, "fp8": 2}     # fp8: bf16 engine + e4m3 forward convs (config 5)
 
-SslcrNetDesc = type("SslcrNetDesc", (C.Structure,), {"_fields_": [
+SslcrNetDesc = L._S("sslcr_net_desc", "SslcrNetDesc", [
     ("params", C.POINTER(C.c_void_p)), ("nparams", C.c_int), ("bn_running_mean", C.POINTER(C.c_void_p)),
     ("bn_running_var", C.POINTER(C.c_void_p)), ("bn_num_batches_tracked", C.POINTER(C.c_void_p)),
-    ("requires_grad", C.POINTER(C.c_uint8)), ("head_kind", C.c_int), ("num_classes", C.c_int), ("triplet", C.c_int)]})
-SslCrDesc = type("SslCrDesc", (C.Structure,), {"_fields_": [
+    ("requires_grad", C.POINTER(C.c_uint8)), ("head_kind", C.c_int), ("num_classes", C.c_int), ("triplet", C.c_int)])
+SslCrDesc = L._S("sslcr_ssl_cr_desc", "SslCrDesc", [
     ("kind", C.c_int), ("x_student", C.c_void_p), ("x_teacher", C.c_void_p), ("in_f32", C.c_int), ("nx", C.c_int),
     ("nu", C.c_int), ("H", C.c_int), ("W", C.c_int), ("target_f", C.c_void_p), ("target_i", C.c_void_p),
     ("lambda_u", C.c_float), ("nx_global", C.c_int), ("nu_global", C.c_int), ("feats", C.c_void_p), ("logits", C.c_void_p),
-    ("logits_t", C.c_void_p), ("losses", C.c_void_p), ("backward", C.c_int), ("x_student2", C.c_void_p)]})
-SupDesc = type("SupDesc", (C.Structure,), {"_fields_": [
+    ("logits_t", C.c_void_p), ("losses", C.c_void_p), ("backward", C.c_int), ("x_student2", C.c_void_p)])
+SupDesc = L._S("sslcr_sup_desc", "SupDesc", [
     ("kind", C.c_int), ("x1", C.c_void_p), ("x2", C.c_void_p), ("x3", C.c_void_p), ("in_f32", C.c_int), ("n", C.c_int),
     ("H", C.c_int), ("W", C.c_int), ("target_f", C.c_void_p), ("target_i", C.c_void_p), ("n_global", C.c_int),
-    ("feats", C.c_void_p), ("logits", C.c_void_p), ("losses", C.c_void_p), ("train", C.c_int), ("backward", C.c_int)]})
+    ("feats", C.c_void_p), ("logits", C.c_void_p), ("losses", C.c_void_p), ("train", C.c_int), ("backward", C.c_int)])
 
 _ENGINE_SIGS = {
     "sslcr_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),

@@ -31,6 +31,20 @@ def _chk(*ts):
                 raise L.SslcrError("sslcr kernels need contiguous tensors")
 
 
+def _out(out, shape, dtype, device, rule):
+    """``out`` as the caller gave it, held to shape, dtype and device (rule: the error's text), or a new tensor of them"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or out.device != device:
+        raise L.SslcrError(rule)
+    return out
+
+
+def _u8(t):
+    """a bool tensor viewed as uint8 (the same bytes, False = 0 and True = 1); any other tensor as it is, for the caller's dtype check"""
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
 last_conv_kernel = ""        # kernel instance the most recent conv2d() launched (rocprofv3 spelling), for tests / profiles
 last_wgrad_kernel = ""       # ... and the most recent conv2d_wgrad()
 
@@ -538,6 +552,35 @@ def softmax_col(logits, col=-1):
     return out
 
 
+def _predict_desc(who, logits, n, c, target, scores, pred, confusion, col, map, map_index):
+    """what ``predict`` and ``predict_tta`` share once n and C are known: the rules for target / map_index / confusion / map, the
+    output dict, and the sslcr_predict_desc over both -> ``(out, desc)``"""
+    dev = logits.device
+    for name, t in (("target", target), ("map_index", map_index)):
+        if t is not None and (t.dtype != torch.int64 or t.shape != (n,) or t.device != dev):
+            raise L.SslcrError(f"{who}: {name} must be an int64 tensor [{n}] on {dev}")
+    if confusion is not None:
+        if confusion.dtype != torch.int64 or confusion.shape != (c, c) or confusion.device != dev:
+            raise L.SslcrError(f"{who}: confusion must be an int64 tensor [{c}, {c}] on {dev}")
+        if target is None:
+            raise L.SslcrError(f"{who}: confusion needs target")
+    if map is not None:
+        if map.dtype != torch.float32 or map.device != dev:
+            raise L.SslcrError(f"{who}: map must be an fp32 tensor on {dev}")
+        if map_index is None:
+            raise L.SslcrError(f"{who}: map needs map_index")
+        if not -c <= col < c:
+            raise L.SslcrError(f"{who}: col = {col} outside [-{c}, {c})")
+    out = {}
+    if scores:
+        out["scores"] = torch.empty((n, c), dtype=torch.float32, device=dev)
+    if pred:
+        out["pred"] = torch.empty(n, dtype=torch.int64, device=dev)
+    d = L.PredictDesc(L.ptr(logits) if n else None, n, c, L.ptr(target), L.ptr(out.get("scores")), L.ptr(out.get("pred")), L.ptr(confusion),
+                      col % c, L.ptr(map), L.ptr(map_index), map.numel() if map is not None else 0)
+    return out, d
+
+
 def predict(logits, target=None, *, scores=False, pred=True, confusion=None, col=-1, map=None, map_index=None):
     """What a test() loop takes from a batch of fp32 logits [n, C] (1 <= C <= 64), in one launch (sslcr_predict) -> dict with
     ``scores`` [n, C] fp32 = softmax over the row (scores=True) and ``pred`` [n] int64 = torch.argmax's index (pred=True: the lowest
@@ -551,29 +594,7 @@ def predict(logits, target=None, *, scores=False, pred=True, confusion=None, col
     n, c = logits.shape
     if not 1 <= c <= 64:
         raise L.SslcrError(f"predict: C = {c} outside [1, 64]")
-    dev = logits.device
-    for name, t in (("target", target), ("map_index", map_index)):
-        if t is not None and (t.dtype != torch.int64 or t.shape != (n,) or t.device != dev):
-            raise L.SslcrError(f"predict: {name} must be an int64 tensor [{n}] on {dev}")
-    if confusion is not None:
-        if confusion.dtype != torch.int64 or confusion.shape != (c, c) or confusion.device != dev:
-            raise L.SslcrError(f"predict: confusion must be an int64 tensor [{c}, {c}] on {dev}")
-        if target is None:
-            raise L.SslcrError("predict: confusion needs target")
-    if map is not None:
-        if map.dtype != torch.float32 or map.device != dev:
-            raise L.SslcrError(f"predict: map must be an fp32 tensor on {dev}")
-        if map_index is None:
-            raise L.SslcrError("predict: map needs map_index")
-        if not -c <= col < c:
-            raise L.SslcrError(f"predict: col = {col} outside [-{c}, {c})")
-    out = {}
-    if scores:
-        out["scores"] = torch.empty((n, c), dtype=torch.float32, device=dev)
-    if pred:
-        out["pred"] = torch.empty(n, dtype=torch.int64, device=dev)
-    d = L.PredictDesc(L.ptr(logits) if n else None, n, c, L.ptr(target), L.ptr(out.get("scores")), L.ptr(out.get("pred")), L.ptr(confusion),
-                      col % c, L.ptr(map), L.ptr(map_index), map.numel() if map is not None else 0)
+    out, d = _predict_desc("predict", logits, n, c, target, scores, pred, confusion, col, map, map_index)
     L.check(L.lib().sslcr_predict(d, L.stream_ptr()))
     return out
 
@@ -595,29 +616,7 @@ def predict_tta(logits, target=None, *, mode=0, scores=False, pred=True, confusi
         raise L.SslcrError(f"predict_tta: mode = {mode} outside {{0, 1}}")
     if mode == 1 and (pred or confusion is not None or map is not None):
         raise L.SslcrError("predict_tta: mode 1 (raw outputs) has no map, pred or confusion")
-    dev = logits.device
-    for name, t in (("target", target), ("map_index", map_index)):
-        if t is not None and (t.dtype != torch.int64 or t.shape != (n,) or t.device != dev):
-            raise L.SslcrError(f"predict_tta: {name} must be an int64 tensor [{n}] on {dev}")
-    if confusion is not None:
-        if confusion.dtype != torch.int64 or confusion.shape != (c, c) or confusion.device != dev:
-            raise L.SslcrError(f"predict_tta: confusion must be an int64 tensor [{c}, {c}] on {dev}")
-        if target is None:
-            raise L.SslcrError("predict_tta: confusion needs target")
-    if map is not None:
-        if map.dtype != torch.float32 or map.device != dev:
-            raise L.SslcrError(f"predict_tta: map must be an fp32 tensor on {dev}")
-        if map_index is None:
-            raise L.SslcrError("predict_tta: map needs map_index")
-        if not -c <= col < c:
-            raise L.SslcrError(f"predict_tta: col = {col} outside [-{c}, {c})")
-    out = {}
-    if scores:
-        out["scores"] = torch.empty((n, c), dtype=torch.float32, device=dev)
-    if pred:
-        out["pred"] = torch.empty(n, dtype=torch.int64, device=dev)
-    p = L.PredictDesc(L.ptr(logits) if n else None, n, c, L.ptr(target), L.ptr(out.get("scores")), L.ptr(out.get("pred")), L.ptr(confusion),
-                      col % c, L.ptr(map), L.ptr(map_index), map.numel() if map is not None else 0)
+    out, p = _predict_desc("predict_tta", logits, n, c, target, scores, pred, confusion, col, map, map_index)
     L.check(L.lib().sslcr_predict_tta(L.PredictTtaDesc(p, G, mode), L.stream_ptr()))
     return out
 
@@ -633,10 +632,7 @@ def d4_transform(x, orient, out=None):
         raise L.SslcrError(f"d4_transform: tiles must be square (got {h} x {w})")
     if orient.dtype != torch.int32 or orient.shape != (n,) or orient.device != x.device:
         raise L.SslcrError(f"d4_transform: orient must be an int32 tensor [{n}] on the batch's device")
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.dtype != x.dtype or out.shape != x.shape or out.device != x.device:
-        raise L.SslcrError("d4_transform: out must have the batch's dtype, shape and device")
+    out = _out(out, x.shape, x.dtype, x.device, "d4_transform: out must have the batch's dtype, shape and device")
     d = L.D4Desc(L.ptr(x) if n else None, L.ptr(out) if n else None, L.ptr(orient) if n else None, n, cn, h, w, x.element_size())
     L.check(L.lib().sslcr_d4_transform(d, L.stream_ptr()))
     return out
@@ -658,10 +654,8 @@ def wsi_gather(region, xy, size, *, origin=(0, 0), fill=0, out=None, orient=None
     RH, RW = region.shape[0], region.shape[1]
     if RH < 1 or RW < 1 or RH >= 1 << 31 or RW >= 1 << 31:
         raise L.SslcrError(f"wsi_gather: region of {RH} x {RW} pixels")
-    if out is None:
-        out = torch.empty((n, 3, size, size), dtype=torch.uint8, device=region.device)
-    elif out.dtype != torch.uint8 or out.shape != (n, 3, size, size) or out.device != region.device:
-        raise L.SslcrError(f"wsi_gather: out must be a uint8 tensor [{n}, 3, {size}, {size}] on the region's device")
+    out = _out(out, (n, 3, size, size), torch.uint8, region.device,
+               f"wsi_gather: out must be a uint8 tensor [{n}, 3, {size}, {size}] on the region's device")
     d = L.WsiGatherDesc(L.ptr(region), L.ptr(xy) if n else None, L.ptr(out) if n else None, int(origin[0]), int(origin[1]), n, RH, RW, size,
                         int(fill))
     if orient is None:
@@ -688,7 +682,7 @@ def _f64_dev(name, what, t, n, dev):
         raise L.SslcrError(f"{name}: {what} must be a float64 tensor of {n} element(s) on {dev}")
 
 
-TISSUE_MODES = {"hsv_s": 0, "lab_a": 1}
+TISSUE_MODES = L.TISSUE_MODES
 
 
 def tissue_bits(img, mode, threshold=None, *, lin=None, thr_sum=None, factor=1.0, count=0.0, pitch=None, out=None):
@@ -713,10 +707,7 @@ def tissue_bits(img, mode, threshold=None, *, lin=None, thr_sum=None, factor=1.0
     pitch = words if pitch is None else int(pitch)
     if pitch < words:
         raise L.SslcrError(f"tissue_bits: pitch = {pitch} < ceil({W} / 32)")
-    if out is None:
-        out = torch.empty((H, pitch), dtype=torch.int32, device=img.device)
-    elif out.dtype != torch.int32 or out.shape != (H, pitch) or out.device != img.device:
-        raise L.SslcrError(f"tissue_bits: out must be an int32 tensor [{H}, {pitch}] on the image's device")
+    out = _out(out, (H, pitch), torch.int32, img.device, f"tissue_bits: out must be an int32 tensor [{H}, {pitch}] on the image's device")
     d = L.TissueBitsDesc(L.ptr(img), L.ptr(out), L.ptr(lin), L.ptr(thr_sum), 0.0 if threshold is None else float(threshold),
                          float(factor), float(count), H, W, pitch, TISSUE_MODES[mode])
     L.check(L.lib().sslcr_tissue_bits(d, L.stream_ptr()))
@@ -884,8 +875,7 @@ def map_confusion(map, truth, tissue, thresholds):
         raise L.SslcrError("map_confusion: a float32 map [X, Y] expected")
     masks = []
     for name, m in (("truth", truth), ("tissue", tissue)):
-        if m.dtype == torch.bool:
-            m = m.view(torch.uint8)
+        m = _u8(m)
         if m.dtype != torch.uint8 or m.shape != map.shape or m.device != map.device:
             raise L.SslcrError(f"map_confusion: {name} must be a uint8 tensor {list(map.shape)} on the map's device")
         masks.append(m)
@@ -908,21 +898,31 @@ def _map2d(name, t, dtype):
         raise L.SslcrError(f"{name}: a {dtype} tensor [X, Y] of 1 ... 2^31 - 1 cells expected")
 
 
+def _mask2d(name, mask):
+    """a device mask [X, Y] of 1 ... 2^31 - 1 cells, uint8 or bool -> the mask as uint8"""
+    _chk(mask)
+    mask = _u8(mask)
+    _map2d(name, mask, torch.uint8)
+    return mask
+
+
+def _label_work(n, device):
+    """the labeller's scratch for n cells: n parents, and one count per run of ``LABEL_RUN_CELLS`` cells (include/sslcr.h: work)"""
+    return torch.empty(n + (n + L.LABEL_RUN_CELLS - 1) // L.LABEL_RUN_CELLS, dtype=torch.int32, device=device)
+
+
 def label_components(mask, connectivity=2):
     """-> ``(labels, count)``: device int32 [X, Y], 0 where ``mask`` is 0 and else the number of the cell's connected component, and
     device int32 [1] = the number of components L (sslcr_label_components).  mask: device uint8 (or bool) [X, Y]; connectivity 2 = 8
     neighbours, 1 = 4.  Components are numbered 1..L by the order of each component's first cell, as ``scipy.ndimage.label`` does.
     Integer atomics whose order does not reach the result.  No sync."""
-    _chk(mask)
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
-    _map2d("label_components", mask, torch.uint8)
+    mask = _mask2d("label_components", mask)
     if connectivity not in (1, 2):
         raise L.SslcrError(f"label_components: connectivity = {connectivity} outside {{1, 2}}")
     n = mask.numel()
     labels = torch.empty(mask.shape, dtype=torch.int32, device=mask.device)
     count = torch.empty(1, dtype=torch.int32, device=mask.device)
-    work = torch.empty(n + (n + 1023) // 1024, dtype=torch.int32, device=mask.device)
+    work = _label_work(n, mask.device)
     d = L.LabelDesc(L.ptr(mask), L.ptr(labels), L.ptr(count), L.ptr(work), mask.shape[0], mask.shape[1], int(connectivity))
     L.check(L.lib().sslcr_label_components(d, L.stream_ptr()))
     return labels, count
@@ -1064,10 +1064,7 @@ def distance_transform_sq(mask, limit=None, *, invert=False, below=False):
     result in float64 is ``scipy.ndimage.distance_transform_edt(mask)``.  mask: device uint8 (or bool) [X, Y], any non-zero value
     set, with X^2 + Y^2 < 2^31.  invert=True measures the distance to the nearest SET cell instead (the zero cells are those with
     mask != 0); below=True returns ``(out, out < limit as uint8)``, written by the same launch.  No sync."""
-    _chk(mask)
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
-    _map2d("distance_transform_sq", mask, torch.uint8)
+    mask = _mask2d("distance_transform_sq", mask)
     _sq_shape("distance_transform_sq", mask)
     limit = EDT_UNLIMITED if limit is None else int(limit)
     if not 0 <= limit <= EDT_UNLIMITED:
@@ -1084,15 +1081,12 @@ def fill_holes(mask):
     """-> device uint8 [X, Y] of 0 / 1: ``mask != 0``, or a background cell whose connectivity-1 background component touches no cell
     of the array's border -- ``scipy.ndimage.binary_fill_holes`` (sslcr_fill_holes: the complement, ``label_components`` on it, a
     border pass, the apply pass; no host read in between).  mask: device uint8 (or bool) [X, Y].  No sync."""
-    _chk(mask)
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
-    _map2d("fill_holes", mask, torch.uint8)
+    mask = _mask2d("fill_holes", mask)
     n, dev = mask.numel(), mask.device
     out = torch.empty(mask.shape, dtype=torch.uint8, device=dev)
     labels = torch.empty(n, dtype=torch.int32, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
-    work = torch.empty(n + (n + 1023) // 1024, dtype=torch.int32, device=dev)
+    work = _label_work(n, dev)
     d = L.FillDesc(L.ptr(mask), L.ptr(out), L.ptr(labels), L.ptr(count), L.ptr(work), mask.shape[0], mask.shape[1])
     L.check(L.lib().sslcr_fill_holes(d, L.stream_ptr()))
     return out
@@ -1187,8 +1181,7 @@ def rank_keys(scores, target, *, positive=None, valid=None):
             raise L.SslcrError(f"rank_keys: {positive.numel()} positive classes for {Cn} columns")
     if valid is not None:
         _chk(valid)
-        if valid.dtype == torch.bool:
-            valid = valid.view(torch.uint8)
+        valid = _u8(valid)
         if valid.dtype != torch.uint8 or valid.numel() != n or valid.device != dev:
             raise L.SslcrError(f"rank_keys: valid must be {n} uint8 / bool flags on the scores' device")
         valid = valid.reshape(-1).contiguous()
@@ -1444,10 +1437,7 @@ def pil_resize(x, size, resample="bilinear", box=None, out=None, out_layout=None
     code = resample_filter_code(resample)
     boxes, index = _resample_boxes(box, N, IH, IW, code == RESAMPLE_FILTERS["nearest"])
     shape = (N, OH, OW, C) if out_layout == "hwc" else (N, C, OH, OW)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=x.device)
-    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != x.device:
-        raise L.SslcrError(f"pil_resize: out must be a uint8 tensor {list(shape)} on the batch's device")
+    out = _out(out, shape, torch.uint8, x.device, f"pil_resize: out must be a uint8 tensor {list(shape)} on the batch's device")
     if N == 0:
         return out
     t = _resample_tables(IH, IW, OH, OW, code, boxes)

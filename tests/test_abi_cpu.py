@@ -78,26 +78,27 @@ def test_product_never_imports_the_oracle():
 
 
 def test_ctypes_mirrors_match_the_header_layout(tmp_path):
-    """every ctypes Structure of the Python layer against the C struct it mirrors: same size, same offset of every field
-    (a small C program over include/sslcr.h, compiled with the host gcc).  Fields appended to a descriptor on one side only
-    would otherwise show up as garbage pointers on the GPU."""
+    """every struct include/sslcr.h defines against its ctypes mirror in _lib.MIRRORS (engine.py registers its three there): the same
+    set of structs, the same fields in the same order, the same size, the same offset of every field (a small C program over the
+    header, compiled with the host gcc).  A struct or a field added on one side only fails here by name; it would otherwise show up
+    as garbage pointers on the GPU."""
     import ctypes as C
     import shutil
     import subprocess
     from ssl_cr_histo_amd import _lib as L
-    from ssl_cr_histo_amd import engine as E
+    from ssl_cr_histo_amd import build
+    from ssl_cr_histo_amd import engine  # noqa: F401  registers its mirrors
+    structs = build.header_structs()
+    assert len(structs) == len(re.findall(r"^typedef struct \w+ \{", open(os.path.join(ROOT, "include", "sslcr.h")).read(), flags=re.M))
+    assert sorted(L.MIRRORS) == sorted(structs), f"header only: {sorted(set(structs) - set(L.MIRRORS))}, mirrors only: {sorted(set(L.MIRRORS) - set(structs))}"
+    for cname, cls in L.MIRRORS.items():
+        have = [f for f, _ in cls._fields_]
+        assert have == structs[cname], (f"{cname}: header only {[f for f in structs[cname] if f not in have]}, "
+                                        f"mirror only {[f for f in have if f not in structs[cname]]}, or another order")
     if not shutil.which("gcc"):
         pytest.skip("no host C compiler")
-    pairs = {"sslcr_conv_desc": L.ConvDesc, "sslcr_wgrad_desc": L.WgradDesc, "sslcr_stem_desc": L.StemDesc,
-             "sslcr_stem_wgrad_desc": L.StemWgradDesc, "sslcr_bn_finalize_desc": L.BnFinalizeDesc, "sslcr_bn_act_desc": L.BnActDesc,
-             "sslcr_pool_fwd_desc": L.PoolFwdDesc, "sslcr_pool_bwd_desc": L.PoolBwdDesc, "sslcr_bn_bwd_desc": L.BnBwdDesc,
-             "sslcr_loss_desc": L.LossDesc, "sslcr_tensor_desc": L.TensorDesc, "sslcr_opt_desc": L.OptDesc,
-             "sslcr_pack_desc": L.PackDesc, "sslcr_weak_aug_desc": L.WeakAugDesc}
-    for cname, pyname in (("sslcr_net_desc", "SslcrNetDesc"), ("sslcr_ssl_cr_desc", "SslCrDesc"), ("sslcr_sup_desc", "SupDesc")):
-        assert hasattr(E, pyname), f"engine.py has no ctypes mirror of {cname}"
-        pairs[cname] = getattr(E, pyname)
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "sslcr.h"', 'int main(void) {']
-    for cname, cls in pairs.items():
+    for cname, cls in L.MIRRORS.items():
         lines.append(f'  printf("{cname} . %zu\\n", sizeof({cname}));')
         for fname, _ in cls._fields_:
             lines.append(f'  printf("{cname} {fname} %zu\\n", offsetof({cname}, {fname}));')
@@ -106,13 +107,36 @@ def test_ctypes_mirrors_match_the_header_layout(tmp_path):
     src.write_text("\n".join(lines))
     exe = tmp_path / "layout"
     r = subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr          # a field the header does not have fails here, by name
+    assert r.returncode == 0, r.stderr
     out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout
     want = {}
     for ln in out.splitlines():
         cname, fname, v = ln.split()
         want[(cname, fname)] = int(v)
-    for cname, cls in pairs.items():
-        assert C.sizeof(cls) == want[(cname, ".")], f"sizeof {cname}: header {want[(cname, '.')]} vs ctypes {C.sizeof(cls)}"
+    for cname, cls in L.MIRRORS.items():
         for fname, _ in cls._fields_:
             assert getattr(cls, fname).offset == want[(cname, fname)], f"{cname}.{fname}"
+        assert C.sizeof(cls) == want[(cname, ".")], f"sizeof {cname}: header {want[(cname, '.')]} vs ctypes {C.sizeof(cls)}"
+    assert L.PredictTtaDesc.p.size == C.sizeof(L.PredictDesc)
+
+
+def test_mirrored_constants_match_the_header():
+    """every #define the Python layer mirrors (_lib.CONSTANTS: macro name -> value) against include/sslcr.h, the names kernels.py
+    re-exports against _lib's, and the two values the kernels' fixtures are written for"""
+    from ssl_cr_histo_amd import _lib as L
+    from ssl_cr_histo_amd import build
+    from ssl_cr_histo_amd import kernels as K
+    defs = build.header_defines()
+    assert len(L.CONSTANTS) >= 22
+    for name, value in L.CONSTANTS.items():
+        assert name in defs, f"{name} is not an integer #define of include/sslcr.h"
+        assert defs[name] == value, f"{name}: header {defs[name]} vs _lib {value}"
+    # every code of a mirrored family is mirrored: a filter, form or tissue mode added to the header alone fails by name
+    forms = {"SSLCR_RESAMPLE_" + f.upper() for f in L.RESAMPLE_FORMS}
+    for name in defs:
+        if name.startswith(("SSLCR_RESAMPLE_", "SSLCR_TISSUE_")):
+            assert name in L.CONSTANTS, name
+    assert forms <= set(defs)
+    for name in ("PIP_CHUNK", "SMOOTH_MAX_R", "EDT_ROW_CELLS", "SORT_TILE", "RANK_SCAN_TRIP", "RESAMPLE_FILTERS", "TISSUE_MODES"):
+        assert getattr(K, name) == getattr(L, name), name
+    assert defs["SSLCR_SMOOTH_MAX_R"] == 64 and defs["SSLCR_EDT_ROW_CELLS"] == 1024

@@ -54,6 +54,27 @@ def test_labels_equal_the_flood_fill_and_two_calls_agree_bit_for_bit(shape, conn
         assert torch.equal(labels, again), name
 
 
+@pytest.mark.parametrize("connectivity", [1, 2])
+def test_labels_when_the_run_offsets_take_a_second_trip(connectivity):
+    """515 x 520 = 267800 cells are 262 runs of SSLCR_LABEL_RUN_CELLS = 1024: the one workgroup that turns the runs' root counts into
+    offsets scans 256 of them per trip, so the last six runs are numbered from the first trip's carry (257 x 300 above makes 76 runs)"""
+    from ssl_cr_histo_amd import kernels as K
+    X, Y = 515, 520
+    assert (X * Y + 1023) // 1024 > 256
+    rs = np.random.RandomState(1000 * X + Y)
+    cases = [("one", np.ones((X, Y), np.uint8)), ("checkerboard", R.checkerboard(X, Y))]
+    for density in (0.45, 0.6):
+        cases.append((f"random{density}", (rs.rand(X, Y) < density).astype(np.uint8) * rs.randint(1, 256, (X, Y)).astype(np.uint8)))
+    for name, mask in cases:
+        want, n = R.label(mask, connectivity)
+        m = _dev(mask)
+        labels, count = K.label_components(m, connectivity)
+        again, count2 = K.label_components(m, connectivity)
+        assert int(count.item()) == n == int(count2.item()), (name, int(count.item()), n)
+        assert np.array_equal(labels.cpu().numpy(), want), name
+        assert torch.equal(labels, again), name
+
+
 def test_labels_of_a_bool_mask_and_an_unaligned_row_pitch():
     """Y = 67: no row but the first starts on a dword, and the last dword of the array is partial"""
     from ssl_cr_histo_amd import kernels as K
