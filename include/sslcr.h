@@ -48,7 +48,7 @@ extern "C" {
  * descriptor whose launch read a NULL pointer on the device.  The ranking entries (sslcr_sort_pairs, sslcr_sort_workspace_bytes,
  * sslcr_rank_keys, sslcr_auc_counts, sslcr_auc_workspace_bytes) are additive in the same way, again without a new number, and so
  * are the resize entries (sslcr_resample, sslcr_resample_plan, sslcr_resample_coeffs, sslcr_resample_ksize,
- * sslcr_resample_table_ok). */
+ * sslcr_resample_table_ok) and the k-NN probe's (sslcr_knn_plan, sslcr_knn_topk, sslcr_knn_vote, sslcr_l2_normalize). */
 int sslcr_version(void);
 const char* sslcr_last_error(void);
 
@@ -989,6 +989,112 @@ typedef struct sslcr_resample_plan_info {
  * -1 for a descriptor sslcr_resample refuses. */
 int sslcr_resample_plan(const sslcr_resample_desc* d, sslcr_resample_plan_info* out);
 int sslcr_resample(const sslcr_resample_desc* d, void* stream);
+
+/* ---- k-nearest-neighbour feature probe on the device (csrc/knn.hip): a fused fp32 similarity and top-k, the vote over the
+ *      neighbours, and the row normalisation cosine similarity needs.  The reference's train() functions return final_feats,
+ *      final_targets for a t-SNE plot (pretrain_BreastPathQ.py:89-92, :322-340); the quantitative form of that plot is a k-NN probe
+ *      of the embeddings.  Additive, again WITHOUT a new version number: a caller tests for sslcr_knn_plan, sslcr_knn_topk,
+ *      sslcr_knn_vote and sslcr_l2_normalize by symbol.  Every entry is asynchronous; none synchronises with the host.
+ *
+ *      sslcr_knn_topk.  queries Q [nq][D] and bank B [nb][D], contiguous float32, D % 4 == 0, 4 <= D <= 2048, both 16-byte aligned.
+ *      For every query i the k (1 <= k <= 64) admissible bank rows j with the greatest similarity s(i, j) = sum_d Q[i][d] B[j][d], best
+ *      first, into scores [nq][k] and indices [nq][k].  The nq x nb similarities never reach memory.
+ *        Arithmetic: v_mfma_f32_16x16x4_f32; every s(i, j) is accumulated over d = 0 .. D - 1 in RISING order from a +0 accumulator,
+ *        one rounding per product-and-add: an fmaf chain in d order.  A ragged last chunk of D is padded with zeros for both operands.
+ *        The value therefore does not depend on the tile, on the slice count or on the route: two plans return equal bits.
+ *        Order: a TOTAL order on integers.  A candidate's 64-bit key is (score key << 32) | ~j: the score key is that of
+ *        sslcr_rank_keys (b ^ 0x80000000 for b >= 0, ~b for b < 0, -0 tied to +0; csrc/score_key.hpp is the one definition), so a
+ *        greater score is a greater key and of two equal scores the LOWER bank index is.  A NaN score gets the score key 1, below
+ *        that of -inf (0x007FFFFF): it ranks below every number, NaNs among themselves by index, and is returned as the NaN
+ *        0x7FC00000.  A score of -0 is returned as +0.  The key 0 is the empty slot.
+ *        Admissible: j < nb_valid (0 <= nb_valid <= nb restricts the search to a prefix of the bank; bank tiles wholly past it are not
+ *        walked, but the plan, and so the slices, are those of nb: a caller with nb_valid far below nb does better to state nb_valid as nb), and j != i + self_offset when
+ *        self_offset >= 0 (-1: none): leave-one-out for queries that are rows self_offset .. of the bank.  With fewer than k admissible
+ *        rows the trailing slots hold index -1 and score -inf.
+ *        Launches: (1) grid = query tiles x S bank slices; a workgroup owns SSLCR_KNN_TILE queries and walks its slice in tiles of
+ *        SSLCR_KNN_TILE bank rows: operands staged through LDS as whole rows, D in chunks of SSLCR_KNN_CHUNK, 2 x 2 accumulator tiles
+ *        a wave; the tile's scores pass through LDS to the selection, one wave per 16 queries: a query's 64 candidates, one per lane,
+ *        are tested against its current k-th key by ballot, and only where one passes are they sorted over the lanes (bitonic) and
+ *        merged into the query's sorted list (one slot per lane).  Each (tile, slice) writes k keys per query to `workspace`.
+ *        (2) one wave per query merges the S lists the same way and writes scores and indices.  Work passes between workgroups at
+ *        the launch boundary only: no tickets, no look-back, no spinning, no floating-point atomics.
+ *      sslcr_knn_plan: HOST-ONLY, usable without a device: the tile shape, S, the workspace bytes and the form of (nq, nb, D, k);
+ *      slices_hint > 0 asks for that S (honoured up to the bank's tile count and SSLCR_KNN_MAX_SLICES; a trailing slice may then be
+ *      empty), 0 lets the plan choose: the chip holds 512 of the first launch's workgroups at a time (two a CU), so the grid runs in
+ *      rounds of 512, and the plan takes the smallest S whose rounds are at least 95 % full, else the fullest -- never fewer than 4
+ *      bank tiles a slice, no empty slice.  For few queries that is as many slices as the bank allows; the second launch reads the
+ *      (sorted) slice lists backwards, so a slice costs a query one 6-exchange merge.  The launch, the Python layer and the tests
+ *      read this plan.  -1 for arguments sslcr_knn_topk refuses.
+ *      Errors: NULL descriptor or pointers, nq < 0 (nq == 0: nothing is launched), nb < 1 or >= 2^31 - 64, D, k outside their ranges, ceil(nq / 64) * S >= 2^31,
+ *      nb_valid outside [0, nb], self_offset < -1, slices < 0, queries / bank not 16-byte, workspace not 8-byte or scores / indices not
+ *      4-byte aligned. */
+#define SSLCR_KNN_TILE 64          /* queries of a workgroup = bank rows of a tile */
+#define SSLCR_KNN_CHUNK 64         /* elements of D per LDS stage */
+#define SSLCR_KNN_MAX_K 64
+#define SSLCR_KNN_MAX_D 2048
+#define SSLCR_KNN_MAX_SLICES 1024
+#define SSLCR_KNN_DIRECT 0         /* form: one slice, the second launch only decodes */
+#define SSLCR_KNN_SLICED 1         /* form: S > 1 slices, the second launch merges them */
+typedef struct sslcr_knn_desc {
+  const float* queries;     /* [nq][D] */
+  const float* bank;        /* [nb][D] */
+  float* scores;            /* [nq][k] */
+  int32_t* indices;         /* [nq][k] */
+  void* workspace;          /* sslcr_knn_plan_info.workspace_bytes */
+  int nq, nb, D, k;
+  int nb_valid;             /* rows [0, nb_valid) of the bank are searched */
+  int self_offset;          /* >= 0: query i ignores bank row i + self_offset; -1: none */
+  int slices;               /* the plan's slices_hint */
+} sslcr_knn_desc;
+typedef struct sslcr_knn_plan_info {
+  int form;                 /* SSLCR_KNN_DIRECT | SSLCR_KNN_SLICED */
+  int tile_q, tile_b, chunk;
+  int slices;               /* S */
+  int tiles_per_slice;      /* bank tiles a slice walks; slice s starts at bank row s * tiles_per_slice * tile_b */
+  int grid[2];              /* workgroups of the (first, second) launch */
+  size_t lds_bytes;         /* static LDS of the first launch's workgroup */
+  size_t workspace_bytes;   /* S * nq * k keys of 8 bytes */
+} sslcr_knn_plan_info;
+int sslcr_knn_plan(int nq, int nb, int D, int k, int slices_hint, sslcr_knn_plan_info* out);
+int sslcr_knn_topk(const sslcr_knn_desc* d, void* stream);
+
+/*      sslcr_l2_normalize.  y[i][:] = x[i][:] / max(||x[i]||, eps), torch.nn.functional.normalize(x, dim = 1), one wave per row: the
+ *      squares are summed in float64 in a fixed order (lane l takes elements l, l + 64, ...; then a butterfly over the lanes), the
+ *      root is taken in float64 and rounded to float32 once, the maximum with eps is taken in float32, and every element is ONE
+ *      correctly rounded float32 division.  y may alias x.
+ *      Errors: NULL descriptor or pointers, n < 0 (n == 0: nothing is launched), D < 1, eps not >= 0, pointers not 4-byte aligned. */
+int sslcr_l2_normalize(const float* x, float* y, int n, int D, float eps, void* stream);
+
+/*      sslcr_knn_vote.  What a k-NN classifier or regressor makes of sslcr_knn_topk's output, one thread per query; a slot with index
+ *      -1 (or outside [0, nb)) takes no part, nor does a neighbour whose label lies outside [0, C).
+ *        UNIFORM  votes[i][c] = the number of neighbours with label c; pred[i] = the class with the most, a tie going to the LOWEST
+ *                 class: sklearn's KNeighborsClassifier(weights = "uniform") (pinned to sklearn 1.7.2 by tests/test_knn_cpu.py).
+ *        SOFTMAX  votes[i][c] = sum over the neighbours with label c, in rank order in float32, of expf((s - s_0) / temperature), s_0
+ *                 the row's best score (slot 0): the weighted vote of DINO / InstDisc; the shift changes no ratio.  pred as above.
+ *        REGRESS  pred_value[i] = (sum of the neighbours' targets, in rank order in float32) / their number; votes, pred unused.
+ *      confusion (classification, optional): int64 [C][C], rows = query_labels; cell (query_labels[i], pred[i]) += 1 by integer
+ *      atomics, counted per workgroup first as sslcr_predict does; it accumulates across calls.  A query without a neighbour
+ *      predicts class 0 with all votes 0 (REGRESS: NaN).
+ *      Errors: NULL descriptor, indices, or the mode's inputs / outputs, nq < 0 (0: nothing launched), k outside [1, 64], nb < 1, a
+ *      classification C outside [1, 64], mode outside the three, SOFTMAX without scores or with temperature not > 0, confusion without
+ *      query_labels, 8-byte tensors not 8-byte or 4-byte tensors not 4-byte aligned. */
+#define SSLCR_KNN_VOTE_UNIFORM 0
+#define SSLCR_KNN_VOTE_SOFTMAX 1
+#define SSLCR_KNN_VOTE_REGRESS 2
+typedef struct sslcr_knn_vote_desc {
+  const int32_t* indices;   /* [nq][k] */
+  const float* scores;      /* [nq][k]; SOFTMAX only (else may be NULL) */
+  const int64_t* labels;    /* [nb] bank labels (classification) */
+  const float* targets;     /* [nb] bank targets (REGRESS) */
+  const int64_t* query_labels;  /* [nq] or NULL */
+  int64_t* pred;            /* [nq] (classification) */
+  float* pred_value;        /* [nq] (REGRESS) */
+  float* votes;             /* [nq][C] (classification) */
+  int64_t* confusion;       /* [C][C] or NULL */
+  int nq, k, nb, C, mode;
+  float temperature;
+} sslcr_knn_vote_desc;
+int sslcr_knn_vote(const sslcr_knn_vote_desc* d, void* stream);
 
 /* ---- device-side strong augmentation, the colour ops of the reference's RandAugment pool ("next" row f4) on a uint8 batch in HBM.
  *      As with sslcr_weak_augment the random draws stay on the host, in the reference's order (ssl_cr_histo_amd/augment.py);

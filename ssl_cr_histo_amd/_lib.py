@@ -125,6 +125,16 @@ ResampleDesc = _S("sslcr_resample_desc", "ResampleDesc", [(k, vp) for k in ("src
                   [(k, i32) for k in ("N", "C", "IH", "IW", "OH", "OW", "ksx", "ksy", "T", "src_chw", "dst_chw", "nearest", "form")])
 ResamplePlan = _S("sslcr_resample_plan_info", "ResamplePlan", [(k, i32) for k in ("form", "fused_ok", "tile_w", "tile_h", "rows", "cols")] + [("grid", i32 * 2),
                                                                                                                 ("lds_bytes", sz), ("workspace_bytes", sz)])
+KNN_TILE, KNN_CHUNK, KNN_MAX_K, KNN_MAX_D, KNN_MAX_SLICES = 64, 64, 64, 2048, 1024
+KNN_FORMS = ("direct", "sliced")
+KNN_VOTES = {"uniform": 0, "softmax": 1, "regress": 2}
+KnnDesc = _S("sslcr_knn_desc", "KnnDesc", [(k, vp) for k in ("queries", "bank", "scores", "indices", "workspace")] +
+             [(k, i32) for k in ("nq", "nb", "D", "k", "nb_valid", "self_offset", "slices")])
+KnnPlan = _S("sslcr_knn_plan_info", "KnnPlan", [(k, i32) for k in ("form", "tile_q", "tile_b", "chunk", "slices", "tiles_per_slice")] +
+             [("grid", i32 * 2), ("lds_bytes", sz), ("workspace_bytes", sz)])
+KnnVoteDesc = _S("sslcr_knn_vote_desc", "KnnVoteDesc", [(k, vp) for k in ("indices", "scores", "labels", "targets", "query_labels", "pred", "pred_value",
+                                                                          "votes", "confusion")] +
+                 [(k, i32) for k in ("nq", "k", "nb", "C", "mode")] + [("temperature", f32)])
 PackDesc = _S("sslcr_pack_desc", "PackDesc", [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("gamma", vp), ("beta", vp), ("rmean", vp),
                            ("rvar", vp), ("eps", f32), ("bias_out", vp)] + [(k, i32) for k in ("K", "C", "R", "S", "dgrad_flip")] + [("scale_out", vp)])
 
@@ -140,6 +150,10 @@ CONSTANTS = {"SSLCR_MAX_OPT_GROUPS": MAX_OPT_GROUPS, "SSLCR_LAB_SUM_PARTIALS": L
 CONSTANTS.update({"SSLCR_TISSUE_" + k.upper(): v for k, v in TISSUE_MODES.items()})
 CONSTANTS.update({"SSLCR_RESAMPLE_" + k.upper(): v for k, v in RESAMPLE_FILTERS.items()})
 CONSTANTS.update({"SSLCR_RESAMPLE_" + k.upper(): v for v, k in enumerate(RESAMPLE_FORMS)})
+CONSTANTS.update({"SSLCR_KNN_TILE": KNN_TILE, "SSLCR_KNN_CHUNK": KNN_CHUNK, "SSLCR_KNN_MAX_K": KNN_MAX_K, "SSLCR_KNN_MAX_D": KNN_MAX_D,
+                  "SSLCR_KNN_MAX_SLICES": KNN_MAX_SLICES})
+CONSTANTS.update({"SSLCR_KNN_" + k.upper(): v for v, k in enumerate(KNN_FORMS)})
+CONSTANTS.update({"SSLCR_KNN_VOTE_" + k.upper(): v for k, v in KNN_VOTES.items()})
 
 # symbol -> (restype, argtypes); every symbol include/sslcr.h declares
 P = C.POINTER
@@ -210,6 +224,10 @@ SIGNATURES = {
     "sslcr_resample_table_ok": (i32, [vp, i32, i32]),
     "sslcr_resample_plan": (i32, [P(ResampleDesc), P(ResamplePlan)]),
     "sslcr_resample": (i32, [P(ResampleDesc), vp]),
+    "sslcr_knn_plan": (i32, [i32, i32, i32, i32, i32, P(KnnPlan)]),
+    "sslcr_knn_topk": (i32, [P(KnnDesc), vp]),
+    "sslcr_l2_normalize": (i32, [vp, vp, i32, i32, f32, vp]),
+    "sslcr_knn_vote": (i32, [P(KnnVoteDesc), vp]),
     "sslcr_optimizer_step": (i32, [vp, i32, i32, P(OptDesc), vp]),
     "sslcr_optimizer_step_groups": (i32, [vp, i32, i32, P(OptDesc), i32, vp, vp]),
     "sslcr_grad_norm": (i32, [vp, sz, f32, vp, vp, vp]),

@@ -621,6 +621,57 @@ int sslcr_resample(const sslcr_resample_desc* d, void* stream) {
   NEED(s + sb <= t || t + tb <= s, "src and dst overlap (out of place only)");
   return check(launch_resample(*d, p, (hipStream_t)stream), "resample");
 }
+// ---- k-NN feature probe (knn.hip)
+int sslcr_knn_plan(int nq, int nb, int D, int k, int slices_hint, sslcr_knn_plan_info* out) {
+  NEED(out, "null");
+  const char* why = knn_plan(nq, nb, D, k, slices_hint, out);
+  NEED(!why, why);
+  return 0;
+}
+int sslcr_knn_topk(const sslcr_knn_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  KnnPlan p;
+  const char* why = knn_plan(d->nq, d->nb, d->D, d->k, d->slices, &p);
+  NEED(!why, why);
+  NEED(d->nb_valid >= 0 && d->nb_valid <= d->nb, "nb_valid outside [0, nb]");
+  NEED(d->self_offset >= -1, "self_offset < -1");
+  if (d->nq == 0) return 0;
+  NEED(d->queries && d->bank && d->scores && d->indices && d->workspace, "null tensor");
+  NEED(ALIGNED(d->queries, 15) && ALIGNED(d->bank, 15), "queries / bank must be 16-byte aligned");
+  NEED(ALIGNED(d->workspace, 7) && ALIGNED(d->scores, 3) && ALIGNED(d->indices, 3), "workspace / scores / indices alignment");
+  return check(launch_knn_topk(*d, p, (hipStream_t)stream), "knn_topk");
+}
+int sslcr_l2_normalize(const float* x, float* y, int n, int D, float eps, void* stream) {
+  NEED(n >= 0 && D >= 1, "n >= 0 and D >= 1");
+  NEED(eps >= 0.f, "eps must be >= 0");
+  if (n == 0) return 0;
+  NEED(x && y, "null tensor");
+  NEED(ALIGNED(x, 3) && ALIGNED(y, 3), "x / y alignment");
+  return check(launch_l2_normalize(x, y, n, D, eps, (hipStream_t)stream), "l2_normalize");
+}
+int sslcr_knn_vote(const sslcr_knn_vote_desc* d, void* stream) {
+  NEED(d, "null descriptor");
+  NEED(d->nq >= 0 && d->nb >= 1, "nq >= 0 and nb >= 1");
+  NEED(d->k >= 1 && d->k <= SSLCR_KNN_MAX_K, "k outside [1, 64]");
+  NEED(d->mode == SSLCR_KNN_VOTE_UNIFORM || d->mode == SSLCR_KNN_VOTE_SOFTMAX || d->mode == SSLCR_KNN_VOTE_REGRESS, "mode outside {0, 1, 2}");
+  if (d->mode == SSLCR_KNN_VOTE_REGRESS) {
+    NEED(!d->confusion, "the regression mode has no confusion counts");
+  } else {
+    NEED(d->C >= 1 && d->C <= 64, "C outside [1, 64]");
+    NEED(d->mode != SSLCR_KNN_VOTE_SOFTMAX || d->temperature > 0.f, "temperature must be > 0");
+    NEED(!d->confusion || d->query_labels, "confusion needs query_labels");
+  }
+  if (d->nq == 0) return 0;
+  NEED(d->indices, "null indices");
+  if (d->mode == SSLCR_KNN_VOTE_REGRESS) NEED(d->targets && d->pred_value, "the regression mode needs targets and pred_value");
+  else NEED(d->labels && d->pred && d->votes, "classification needs labels, pred and votes");
+  NEED(d->mode != SSLCR_KNN_VOTE_SOFTMAX || d->scores, "the softmax vote needs scores");
+  NEED(ALIGNED(d->indices, 3) && ALIGNED(d->scores, 3) && ALIGNED(d->targets, 3) && ALIGNED(d->pred_value, 3) && ALIGNED(d->votes, 3),
+       "indices / scores / targets / pred_value / votes alignment");
+  NEED(ALIGNED(d->labels, 7) && ALIGNED(d->query_labels, 7) && ALIGNED(d->pred, 7) && ALIGNED(d->confusion, 7),
+       "labels / query_labels / pred / confusion alignment");
+  return check(launch_knn_vote(*d, (hipStream_t)stream), "knn_vote");
+}
 #undef SQ_SHAPE_OK
 #undef MAP_SHAPE_OK
 #undef ALIGNED

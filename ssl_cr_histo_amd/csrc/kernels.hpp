@@ -232,6 +232,13 @@ using ResamplePlan = sslcr_resample_plan_info;
 // nullptr and *out filled, or what is wrong with the descriptor (host only: no device call, no device pointer read)
 const char* resample_plan(const sslcr_resample_desc& a, ResamplePlan* out);
 hipError_t launch_resample(const sslcr_resample_desc& a, const ResamplePlan& p, hipStream_t st);
+// knn.hip: the tile shape and the slice count are decided ONCE, here -- the launch, sslcr_knn_plan, the Python layer and the tests read this plan
+using KnnPlan = sslcr_knn_plan_info;
+// nullptr and *out filled, or what is wrong with the arguments (host only)
+const char* knn_plan(int nq, int nb, int D, int k, int slices_hint, KnnPlan* out);
+hipError_t launch_knn_topk(const sslcr_knn_desc& a, const KnnPlan& p, hipStream_t st);
+hipError_t launch_l2_normalize(const float* x, float* y, int n, int D, float eps, hipStream_t st);
+hipError_t launch_knn_vote(const sslcr_knn_vote_desc& a, hipStream_t st);
 // augment.hip
 hipError_t launch_weak_augment(const sslcr_weak_aug_desc& a, hipStream_t st);
 hipError_t launch_hed_colour(const sslcr_colour_aug_desc& a, hipStream_t st);

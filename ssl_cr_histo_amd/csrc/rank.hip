@@ -7,6 +7,7 @@
 // launch boundaries only: no kernel waits for another workgroup, there is no look-back and no ticket, and every loop states its bound.
 #include "kernels.hpp"
 #include "map_common.hpp"
+#include "score_key.hpp"
 
 namespace sslcr {
 
@@ -172,9 +173,8 @@ __global__ __launch_bounds__(256) void rank_keys_kernel(const sslcr_rank_keys_de
   unsigned long long* nan = reinterpret_cast<unsigned long long*>(a.nan);
   for (int c = 0; c < a.C; ++c) {                   // bound: C columns
     uint32_t b = in ? bits[i * a.C + c] : 0u;
-    const bool is_nan = ok && (b & 0x7fffffffu) > 0x7f800000u;
-    if ((b << 1) == 0u) b = 0u;                     // -0 ties with +0
-    const uint32_t key = b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+    const bool is_nan = ok && score_is_nan(b);
+    const uint32_t key = score_key(b);              // score_key.hpp: -0 ties with +0
     const int64_t positive = a.positive ? a.positive[c] : (int64_t)c;
     const uint32_t value = (!ok || is_nan) ? 2u : (target == positive ? 1u : 0u);
     if (in) {

@@ -630,3 +630,133 @@ def bpq_icc(outputs, targetsA, targetsB):
         raise ValueError(f"bpq_icc: {[len(c) for c in cols]} values in outputs / targetsA / targetsB")
     m, a, b = cols
     return dict(MA=icc(np.stack([m, a], 1)), MB=icc(np.stack([m, b], 1)), AB=icc(np.stack([a, b], 1)))
+
+
+# ---- k-nearest-neighbour feature probe: the quantitative form of the reference's t-SNE plot of final_feats / final_targets
+class FeatureBank:
+    """Embeddings and their targets held on the device for ``knn_classify`` / ``knn_regress`` / ``knn_probe``.  ``add(feats, targets)``
+    appends a device batch (float32 [n, dim]; integer labels or float targets [n]) without a copy to the host -- into a buffer of
+    ``capacity`` rows when one was stated, else into a list ``finalize()`` concatenates.  ``finalize()`` normalises the rows once
+    for ``metric="cosine"`` (``kernels.l2_normalize``; "dot" keeps them) and never synchronises.  ``n_classes``: the class count of
+    integer labels; a label outside ``[0, n_classes)`` takes no part in a vote.  Without it ``class_count()`` reads the largest label
+    off the device -- ONE scalar copy, a synchronisation -- when a classification first needs the count.  dim % 4 == 0,
+    4 <= dim <= 2048."""
+
+    def __init__(self, dim, capacity=None, metric="cosine", n_classes=None):
+        if metric not in ("cosine", "dot"):
+            raise ValueError(f"FeatureBank: metric = {metric!r} outside ('cosine', 'dot')")
+        if dim % 4 or not 4 <= dim <= K.KNN_MAX_D:
+            raise ValueError(f"FeatureBank: dim = {dim} must be a multiple of 4 in [4, {K.KNN_MAX_D}]")
+        self.dim, self.capacity, self.metric, self.n_classes = int(dim), capacity, metric, n_classes
+        self.n = 0
+        self._feats, self._targets = [], []
+        self._buf = self._tbuf = None
+        self.feats = self.targets = None
+
+    def add(self, feats, targets):
+        if self.feats is not None:
+            raise RuntimeError("FeatureBank: add() after finalize()")
+        if not feats.is_cuda or feats.dtype != torch.float32 or feats.dim() != 2 or feats.shape[1] != self.dim:
+            raise K.L.SslcrError(f"FeatureBank.add: device float32 [n, {self.dim}] expected (no CPU fallback)")
+        targets = targets.reshape(-1).to(feats.device)
+        if targets.numel() != feats.shape[0]:
+            raise ValueError(f"FeatureBank.add: {targets.numel()} targets for {feats.shape[0]} rows")
+        targets = targets.float() if targets.is_floating_point() else targets.long()
+        n = feats.shape[0]
+        if self.capacity is not None:
+            if self.n + n > self.capacity:
+                raise ValueError(f"FeatureBank.add: {self.n + n} rows exceed the capacity {self.capacity}")
+            if self._buf is None:
+                self._buf = torch.empty((self.capacity, self.dim), dtype=torch.float32, device=feats.device)
+                self._tbuf = torch.empty(self.capacity, dtype=targets.dtype, device=feats.device)
+            self._buf[self.n:self.n + n].copy_(feats)
+            self._tbuf[self.n:self.n + n].copy_(targets)
+        else:
+            self._feats.append(feats.detach())
+            self._targets.append(targets)
+        self.n += n
+        return self
+
+    def finalize(self):
+        if self.feats is None:
+            if self.n == 0:
+                raise ValueError("FeatureBank.finalize: the bank is empty")
+            feats = self._buf[:self.n] if self.capacity is not None else torch.cat(self._feats)
+            self.targets = self._tbuf[:self.n] if self.capacity is not None else torch.cat(self._targets)
+            self.feats = K.l2_normalize(feats) if self.metric == "cosine" else feats.contiguous()
+            self._feats, self._targets, self._buf, self._tbuf = [], [], None, None
+        return self
+
+    def class_count(self, query_labels=None):
+        """``n_classes`` as stated; else 1 + the largest label of the bank and of ``query_labels`` (one scalar copy: a sync)"""
+        if self.n_classes is not None:
+            return int(self.n_classes)
+        self.finalize()
+        top = self.targets.max()
+        if query_labels is not None and query_labels.numel():
+            top = torch.maximum(top, query_labels.max().to(top.dtype))
+        return int(top.item()) + 1
+
+    def queries(self, feats):
+        """query rows in the bank's metric: normalised for cosine"""
+        return K.l2_normalize(feats) if self.metric == "cosine" else feats.contiguous()
+
+
+def _bank_topk(bank, queries, k, exclude_self):
+    bank.finalize()
+    q = bank.feats if queries is None else bank.queries(queries)
+    return K.knn_topk(q, bank.feats, k, exclude_self=exclude_self)
+
+
+def knn_classify(bank, queries, k=20, weights="uniform", temperature=0.07, *, query_labels=None, exclude_self=None):
+    """k-NN classification of device float32 ``queries`` [nq, dim] (None: the bank's own rows) from a ``FeatureBank`` of integer
+    labels: ``kernels.knn_topk`` then ``kernels.knn_vote``, everything on the device; no sync when the bank states ``n_classes`` (else
+    the one scalar copy of ``FeatureBank.class_count``, over the bank's and the query labels).  -> dict with ``pred`` int64 [nq],
+    ``votes`` float32 [nq, C], ``scores`` / ``indices`` [nq, k] and, with ``query_labels``, ``confusion`` int64 [C, C].  weights:
+    "uniform" (sklearn's ``KNeighborsClassifier``) or "softmax" (``exp((s - s_0) / temperature)``, the DINO / InstDisc vote).
+    exclude_self: query i ignores bank row i + exclude_self (leave-one-out)."""
+    scores, indices = _bank_topk(bank, queries, k, exclude_self)
+    if bank.targets.is_floating_point():
+        raise ValueError("knn_classify: the bank holds float targets (knn_regress)")
+    Cn = bank.class_count(query_labels)
+    out = K.knn_vote(indices, scores, labels=bank.targets, n_classes=Cn, weights=weights, temperature=temperature,
+                     query_labels=query_labels)
+    out.update(scores=scores, indices=indices, n_classes=Cn)
+    return out
+
+
+def knn_regress(bank, queries, k=5, *, exclude_self=None):
+    """k-NN regression from a ``FeatureBank`` of float targets (the BreastPathQ cellularity scores): -> dict with ``pred`` float32
+    [nq], the mean of the k neighbours' targets (sklearn's ``KNeighborsRegressor``), and ``scores`` / ``indices``.  No sync."""
+    scores, indices = _bank_topk(bank, queries, k, exclude_self)
+    if not bank.targets.is_floating_point():
+        raise ValueError("knn_regress: the bank holds integer labels (knn_classify)")
+    out = K.knn_vote(indices, scores, targets=bank.targets)
+    out.update(scores=scores, indices=indices)
+    return out
+
+
+def knn_probe(feats, targets, k=20, leave_one_out=True, *, queries=None, query_targets=None, metric="cosine", weights="uniform",
+              temperature=0.07, n_classes=None):
+    """How good are these embeddings: the accuracy of a k-NN classifier on them.  feats / targets: device float32 [n, dim] and integer
+    [n] -- what ``steps.rsp_train`` returns as ``final_feats, final_targets`` feeds it as it is.  leave_one_out: every row is classified
+    from the others (``exclude_self``); otherwise ``queries`` / ``query_targets`` are classified from the bank.  -> dict with
+    ``accuracy`` and the other figures of ``metrics_from_confusion``, ``confusion`` (int64 [C, C] array, rows = targets) and ``pred``
+    (int64 array).  With ``n_classes`` stated there is ONE copy to the host, of the final numbers; without it the class count is
+    read off the labels first (one more scalar copy, ``FeatureBank.class_count``).  A target outside ``[0, n_classes)`` cannot be
+    counted: the confusion matrix then holds fewer rows than there are queries, and this raises instead of averaging over fewer."""
+    bank = FeatureBank(feats.shape[1], metric=metric, n_classes=n_classes).add(feats, targets).finalize()
+    if leave_one_out:
+        r = knn_classify(bank, None, k, weights, temperature, query_labels=bank.targets, exclude_self=0)
+    else:
+        if queries is None or query_targets is None:
+            raise ValueError("knn_probe: leave_one_out=False needs queries and query_targets")
+        r = knn_classify(bank, queries, k, weights, temperature, query_labels=query_targets.reshape(-1).to(feats.device))
+    Cn = r["n_classes"]
+    flat = torch.cat([r["confusion"].reshape(-1), r["pred"]]).cpu().numpy()             # the one copy
+    cm = flat[:Cn * Cn].reshape(Cn, Cn)
+    if int(cm.sum()) != r["pred"].numel():
+        raise ValueError(f"knn_probe: {r['pred'].numel() - int(cm.sum())} query targets lie outside [0, {Cn}): state n_classes to cover them")
+    out = metrics_from_confusion(cm)
+    out.update(confusion=cm, pred=flat[Cn * Cn:])
+    return out

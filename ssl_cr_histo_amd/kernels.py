@@ -1214,6 +1214,136 @@ def auc_counts(scores, target, *, positive=None, valid=None):
     return counts
 
 
+# ---- k-nearest-neighbour feature probe (csrc/knn.hip)
+KNN_TILE, KNN_CHUNK, KNN_MAX_K, KNN_MAX_D = L.KNN_TILE, L.KNN_CHUNK, L.KNN_MAX_K, L.KNN_MAX_D
+KNN_FORMS = L.KNN_FORMS
+KNN_VOTES = L.KNN_VOTES
+
+
+def knn_plan(nq, nb, dim, k, slices=None):
+    """what ``knn_topk`` launches for these sizes (sslcr_knn_plan; host only, no device needed): dict with ``form`` ("direct" |
+    "sliced"), ``tile_q``, ``tile_b``, ``chunk``, ``slices``, ``tiles_per_slice``, ``grid`` (workgroups of the two launches),
+    ``lds_bytes`` and ``workspace_bytes``.  slices: the hint (None / 0 = the plan's choice)."""
+    p = L.KnnPlan()
+    L.check(L.lib().sslcr_knn_plan(int(nq), int(nb), int(dim), int(k), int(slices or 0), p))
+    out = {f: getattr(p, f) for f, _ in L.KnnPlan._fields_}
+    out["grid"] = tuple(p.grid)
+    out["form"] = KNN_FORMS[p.form]
+    return out
+
+
+def _f32_rows(name, t):
+    if not t.is_cuda:
+        raise L.SslcrError(f"{name}: device tensors expected (no CPU fallback)")
+    if t.dtype != torch.float32 or t.dim() != 2:
+        raise L.SslcrError(f"{name}: float32 [n, D] expected, got {t.dtype} {list(t.shape)}")
+    return t.contiguous()
+
+
+def knn_topk(queries, bank, k, *, nb_valid=None, exclude_self=None, slices=None, out=None):
+    """-> ``(scores, indices)``: device float32 [nq, k] and int32 [nq, k], per query the k bank rows with the greatest dot product,
+    best first (sslcr_knn_topk: a fused fp32 MFMA similarity and top-k, the [nq, nb] product never reaches memory; two launches).
+    queries [nq, D], bank [nb, D]: device float32, D % 4 == 0, 4 <= D <= 2048; 1 <= k <= 64.  Every score is an fp32 fma chain over
+    D in rising order, whatever the plan: ``slices`` (the bank slices of the grid; None = the plan's choice) changes no bit.  The
+    order is total: the greater score first, of equal scores (-0 == +0) the lower bank index; a NaN score ranks below every number.
+    nb_valid: search rows ``[0, nb_valid)`` only; exclude_self: an offset o >= 0 (True = 0) making query i ignore bank row i + o, for
+    leave-one-out when the queries are rows of the bank.  With fewer than k admissible rows the trailing slots are index -1 and score
+    -inf.  out: ``(scores, indices)`` to write into.  No sync."""
+    queries, bank = _f32_rows("knn_topk", queries), _f32_rows("knn_topk", bank)
+    (nq, D), nb = queries.shape, bank.shape[0]
+    if bank.shape[1] != D or bank.device != queries.device:
+        raise L.SslcrError(f"knn_topk: queries {list(queries.shape)} and bank {list(bank.shape)} must share D and the device")
+    nb_valid = nb if nb_valid is None else int(nb_valid)
+    if not 0 <= nb_valid <= nb:
+        raise L.SslcrError(f"knn_topk: nb_valid = {nb_valid} outside [0, {nb}]")
+    if 1 <= nb_valid < nb:                           # the prefix IS the bank: the plan and its slices are sized for the rows searched
+        bank, nb = bank[:nb_valid], nb_valid
+    if exclude_self is None or exclude_self is False:
+        off = -1
+    else:
+        off = 0 if exclude_self is True else int(exclude_self)
+        if off < 0:
+            raise L.SslcrError("knn_topk: exclude_self must be an offset >= 0 (or True = 0)")
+    p = L.KnnPlan()
+    L.check(L.lib().sslcr_knn_plan(nq, nb, D, int(k), int(slices or 0), p))
+    dev = queries.device
+    scores = _out(out[0] if out else None, (nq, k), torch.float32, dev, f"knn_topk: out[0] must be float32 [{nq}, {k}] on the queries' device")
+    indices = _out(out[1] if out else None, (nq, k), torch.int32, dev, f"knn_topk: out[1] must be int32 [{nq}, {k}] on the queries' device")
+    _chk(scores, indices)
+    ws = torch.empty(max(1, p.workspace_bytes // 8), dtype=torch.int64, device=dev)
+    d = L.KnnDesc(L.ptr(queries), L.ptr(bank), L.ptr(scores), L.ptr(indices), L.ptr(ws), nq, nb, D, int(k), nb_valid, off, int(slices or 0))
+    L.check(L.lib().sslcr_knn_topk(d, L.stream_ptr()))
+    return scores, indices
+
+
+def l2_normalize(x, eps=1e-12, out=None):
+    """-> ``x / max(||x||, eps)`` per row of a device float32 [n, D] (sslcr_l2_normalize, one wave per row):
+    ``torch.nn.functional.normalize(x, dim=1)`` with the norm summed in float64 in a fixed order, rounded to float32 once, and one
+    correctly rounded float32 division per element.  out may be x.  No sync."""
+    x = _f32_rows("l2_normalize", x)
+    y = _out(out, x.shape, torch.float32, x.device, "l2_normalize: out must match x")
+    _chk(y)
+    L.check(L.lib().sslcr_l2_normalize(L.ptr(x), L.ptr(y), x.shape[0], x.shape[1], float(eps), L.stream_ptr()))
+    return y
+
+
+def knn_vote(indices, scores, labels=None, targets=None, *, n_classes=None, weights="uniform", temperature=0.07, query_labels=None,
+             confusion=None):
+    """What a k-NN classifier or regressor makes of ``knn_topk``'s output (sslcr_knn_vote, one launch, no sync).  indices / scores:
+    device int32 / float32 [nq, k].  Classification (``labels``: device integer [nb] bank labels, ``n_classes`` <= 64): -> dict with
+    ``pred`` int64 [nq], ``votes`` float32 [nq, C] and, with ``query_labels`` (device integer [nq]), ``confusion`` int64 [C, C] (rows =
+    query labels; pass ``confusion=`` to accumulate into an existing matrix).  weights "uniform": integer counts, the most votes win, a
+    tie goes to the lowest class (sklearn's ``KNeighborsClassifier``); "softmax": ``expf((s - s_0) / temperature)`` summed per class in
+    rank order (the DINO / InstDisc weighted vote).  Regression (``targets``: device float32 [nb]): -> dict with ``pred`` float32 [nq],
+    the float32 mean of the neighbours' targets summed in rank order.  A slot with index -1 takes no part."""
+    _chk(indices, scores, labels, targets, query_labels, confusion)
+    if indices.dtype != torch.int32 or indices.dim() != 2:
+        raise L.SslcrError("knn_vote: int32 indices [nq, k] expected")
+    nq, k = indices.shape
+    dev = indices.device
+    if (labels is None) == (targets is None):
+        raise L.SslcrError("knn_vote: exactly one of labels (classification) and targets (regression) expected")
+    if scores is not None and (scores.dtype != torch.float32 or scores.shape != indices.shape or scores.device != dev):
+        raise L.SslcrError("knn_vote: scores must be float32 of the indices' shape and device")
+    if targets is not None:
+        if targets.dtype != torch.float32 or targets.dim() != 1 or targets.device != dev:
+            raise L.SslcrError("knn_vote: float32 targets [nb] on the indices' device expected")
+        pred = torch.empty(nq, dtype=torch.float32, device=dev)
+        d = L.KnnVoteDesc(L.ptr(indices), L.ptr(scores), None, L.ptr(targets), None, None, L.ptr(pred), None, None, nq, k, targets.numel(), 1,
+                          L.KNN_VOTES["regress"], 0.0)
+        L.check(L.lib().sslcr_knn_vote(d, L.stream_ptr()))
+        return dict(pred=pred)
+    if weights not in ("uniform", "softmax"):
+        raise L.SslcrError(f"knn_vote: weights = {weights!r} outside ('uniform', 'softmax')")
+    if labels.is_floating_point() or labels.dim() != 1 or labels.device != dev:
+        raise L.SslcrError("knn_vote: integer labels [nb] on the indices' device expected")
+    if n_classes is None:
+        raise L.SslcrError("knn_vote: n_classes expected (reading it off the labels would synchronise)")
+    Cn = int(n_classes)
+    labels = labels.to(torch.int64).contiguous()
+    if weights == "softmax" and scores is None:
+        raise L.SslcrError("knn_vote: the softmax vote needs scores")
+    if query_labels is not None:
+        if query_labels.is_floating_point() or query_labels.numel() != nq or query_labels.device != dev:
+            raise L.SslcrError(f"knn_vote: {nq} integer query_labels on the indices' device expected")
+        query_labels = query_labels.reshape(-1).to(torch.int64).contiguous()
+        if confusion is None and 1 <= Cn <= 64:
+            confusion = torch.zeros((Cn, Cn), dtype=torch.int64, device=dev)
+        elif confusion is not None and (confusion.dtype != torch.int64 or tuple(confusion.shape) != (Cn, Cn) or confusion.device != dev):
+            raise L.SslcrError(f"knn_vote: confusion must be int64 [{Cn}, {Cn}] on the indices' device")
+    elif confusion is not None:
+        raise L.SslcrError("knn_vote: confusion needs query_labels")
+    pred = torch.empty(nq, dtype=torch.int64, device=dev)
+    votes = torch.empty((nq, max(Cn, 0)), dtype=torch.float32, device=dev)
+    d = L.KnnVoteDesc(L.ptr(indices), L.ptr(scores), L.ptr(labels), None, L.ptr(query_labels), L.ptr(pred), None, L.ptr(votes), L.ptr(confusion),
+                      nq, k, labels.numel(), Cn, L.KNN_VOTES[weights], float(temperature))
+    L.check(L.lib().sslcr_knn_vote(d, L.stream_ptr()))
+    out = dict(pred=pred, votes=votes)
+    if confusion is not None:
+        out["confusion"] = confusion
+    return out
+
+
 def grad_norm(flat, max_norm=float("inf")):
     """-> device tensor [norm, coef] for a 1-D fp32 tensor (any length, any 4-byte-aligned view): its 2-norm, summed in double in a
     fixed order, and min(1, max_norm / (norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_'s two numbers (sslcr_grad_norm).  No sync."""

@@ -883,3 +883,47 @@ def teacher_refresh(model_teacher, classifier_teacher, model_student, classifier
     eng = get_engine(_device_of(model_student))
     te, st = eng.bind(model_teacher, classifier_teacher), eng.bind(model_student, classifier_student)
     te.ema_from(st, ema_decay)
+
+
+# ------------------------------------------------------------------------------------------------ k-NN feature probe
+def _probe_features(args, eng, net, loader):
+    """the eval forward ``*_validate`` runs (``BoundNet.forward(train=False)``; one tile, or the three RSP tiles) over a loader of
+    ``(*tiles, target)`` batches: -> (feats [n, 768], targets [n]) gathered on the device"""
+    feats, targets = [], []
+    for batch in _ahead(loader, eng, _prefetch_on(args)):
+        *tiles, target = batch
+        xs = [v.reshape(-1, *v.shape[-3:]) for v in tiles]
+        f, _ = net.forward(xs, train=False)
+        feats.append(f)
+        targets.append(target.reshape(-1).to(eng.device))
+    return torch.cat(feats), torch.cat(targets)
+
+
+def knn_probe(args, model, classifier, bank_loader, query_loader=None, k=20, **kw):
+    """The k-NN probe of the features a (model, classifier) pair computes: leave-one-out over ``bank_loader`` when there is no
+    ``query_loader``, else the bank's labels voted onto the queries.  Integer targets -> ``inference.knn_probe``'s dict
+    (``accuracy``, ``confusion``, ``pred``, ...); float targets (BreastPathQ) -> dict with ``pred`` and ``mse``, the k-NN regressor's
+    predictions (leave-one-out or on the queries) and their mean squared error.  Features and targets stay on the device; one copy of
+    the final numbers: the class count is the classifier's own (``n_classes=`` overrides it), nothing is read off the labels.  Keywords:
+    ``inference.knn_probe``'s (``metric``, ``weights``, ``temperature``, ``n_classes``) for integer targets, ``metric`` alone for float
+    targets; any other raises."""
+    from . import inference as I
+    eng = get_engine(_device_of(model))
+    model.eval()
+    classifier.eval()
+    net = eng.bind(model, classifier)
+    feats, targets = _probe_features(args, eng, net, bank_loader)
+    q = qt = None
+    if query_loader is not None:
+        q, qt = _probe_features(args, eng, net, query_loader)
+    if not targets.is_floating_point():
+        kw.setdefault("n_classes", net.ncls)
+        return I.knn_probe(feats, targets, k, query_loader is None, queries=q, query_targets=qt, **kw)
+    metric = kw.pop("metric", "cosine")
+    if kw:
+        raise TypeError(f"knn_probe: {sorted(kw)} do not apply to float targets (the k-NN regressor takes metric only)")
+    bank = I.FeatureBank(feats.shape[1], metric=metric).add(feats, targets).finalize()
+    r = I.knn_regress(bank, q, k, exclude_self=0 if q is None else None)
+    truth = (targets if qt is None else qt).float()
+    flat = torch.cat([r["pred"], ((r["pred"] - truth) ** 2).mean().reshape(1)]).cpu().numpy()
+    return dict(pred=flat[:-1], mse=float(flat[-1]))
