@@ -293,6 +293,8 @@ int sslcr_bn_param_grads(const double* sums, const float* invstd, float* dgamma,
  * each workgroup derives its 8x16 dY tile in LDS.  dgamma/dbeta are accumulated as sslcr_bn_bwd_apply would.  Same result, bit for
  * bit, as sslcr_bn_bwd_apply followed by sslcr_stem_wgrad. */
 int sslcr_stem_wgrad_pool(int dtype, const sslcr_stem_wgrad_desc* w, const sslcr_bn_bwd_desc* bn, void* stream);
+/* diagnostics: the kernel instance sslcr_stem_wgrad_pool launches for (dtype, w), spelled as rocprofv3 prints it */
+const char* sslcr_stem_wgrad_pool_kernel_name(int dtype, const sslcr_stem_wgrad_desc* w);
 
 /* ---- heads and losses (models/net.py:12-15,35-36,111; F.mse_loss / F.cross_entropy at
  *      eval_BreastPathQ_SSL_CR.py:92-95, eval_Camelyon_SSL_CR.py:110-116, pretrain_BreastPathQ.py:56) */

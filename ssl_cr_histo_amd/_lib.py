@@ -179,6 +179,7 @@ SIGNATURES = {
     "sslcr_stem_conv_pool": (i32, [i32, P(StemDesc), i32, i32, vp]),
     "sslcr_stem_wgrad": (i32, [i32, P(StemWgradDesc), vp]),
     "sslcr_stem_wgrad_pool": (i32, [i32, P(StemWgradDesc), P(BnBwdDesc), vp]),
+    "sslcr_stem_wgrad_pool_kernel_name": (C.c_char_p, [i32, P(StemWgradDesc)]),
     "sslcr_bn_finalize": (i32, [P(BnFinalizeDesc), vp]),
     "sslcr_bn_act": (i32, [i32, P(BnActDesc), vp]),
     "sslcr_bn_relu_maxpool": (i32, [i32, P(PoolFwdDesc), vp]),

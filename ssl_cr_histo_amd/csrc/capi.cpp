@@ -114,6 +114,7 @@ int sslcr_stem_wgrad(int dtype, const sslcr_stem_wgrad_desc* d, void* stream) {
   NEED(!d->x2 || (d->n_split >= 0 && d->n_split <= d->N), "n_split outside the batch");
   return check(launch_stem_wgrad(dtype, *d, (hipStream_t)stream), "stem_wgrad");
 }
+const char* sslcr_stem_wgrad_pool_kernel_name(int dtype, const sslcr_stem_wgrad_desc* w) { return w ? stem_wgrad_pool_name(dtype, *w) : ""; }
 int sslcr_stem_wgrad_pool(int dtype, const sslcr_stem_wgrad_desc* w, const sslcr_bn_bwd_desc* bn, void* stream) {
   DT_OK(dtype);
   NEED(w && w->x && w->dw && bn && bn->pool_dy && bn->pool_argmax && bn->x && bn->sums && bn->mean && bn->invstd && bn->scale && bn->shift, "null tensor");

@@ -859,11 +859,28 @@ static int stem_pool_form() {                      // SSLCR_STEM_POOL_FORM=1: th
   return v;
 }
 
+// one tag per instance of the pool form: the role-split kernel (P2; bf16 only) or stem_wgrad_kernel<T, INF32, POOL = true>
+template <bool P2, typename T, bool INF32>
+struct StemPoolInst {
+  static std::string spell() { return P2 ? kname("stem_wgrad_pool2_kernel", INF32) : kname("stem_wgrad_kernel", ktype<T>(), INF32, true); }
+};
+template <bool P2, typename T, bool INF32>
+static hipError_t launch_stem_pool_inst(StemPoolInst<P2, T, INF32>, const StemWgradArgs& a, const BnBwdArgs& b, hipStream_t st) {
+  if constexpr (P2) return launch_stem_wgrad_pool2<INF32>(a, b, st);
+  else return launch_stem_wgrad_t<T, INF32, true>(a, b, st);
+}
+// the instance that serves (dtype, a): f(StemPoolInst<...>{}) -- read by the launcher and by the name query alike
+template <class F>
+static auto stem_wgrad_pool_pick(int dtype, const StemWgradArgs& a, F&& f) {
+  if (dtype == DT_BF16 && stem_pool_form() == 2) return a.in_f32 ? f(StemPoolInst<true, bf16_t, true>{}) : f(StemPoolInst<true, bf16_t, false>{});
+  if (dtype == DT_BF16) return a.in_f32 ? f(StemPoolInst<false, bf16_t, true>{}) : f(StemPoolInst<false, bf16_t, false>{});
+  return a.in_f32 ? f(StemPoolInst<false, float, true>{}) : f(StemPoolInst<false, float, false>{});
+}
+
 hipError_t launch_stem_wgrad_pool(int dtype, const StemWgradArgs& a, const BnBwdArgs& b, hipStream_t st) {
   if (!b.pool_dy || !b.pool_argmax || !b.x || b.C != 64 || b.pH != a.OH || b.pW != a.OW || b.g_in_reduce || b.gout) return hipErrorInvalidValue;
-  if (dtype == DT_BF16 && stem_pool_form() == 2) return a.in_f32 ? launch_stem_wgrad_pool2<true>(a, b, st) : launch_stem_wgrad_pool2<false>(a, b, st);
-  if (dtype == DT_BF16) return a.in_f32 ? launch_stem_wgrad_t<bf16_t, true, true>(a, b, st) : launch_stem_wgrad_t<bf16_t, false, true>(a, b, st);
-  return a.in_f32 ? launch_stem_wgrad_t<float, true, true>(a, b, st) : launch_stem_wgrad_t<float, false, true>(a, b, st);
+  return stem_wgrad_pool_pick(dtype, a, [&](auto inst) { return launch_stem_pool_inst(inst, a, b, st); });
 }
+const char* stem_wgrad_pool_name(int dtype, const StemWgradArgs& a) { return stem_wgrad_pool_pick(dtype, a, InstName{}); }
 
 }  // namespace sslcr

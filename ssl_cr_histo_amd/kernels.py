@@ -47,6 +47,7 @@ def _u8(t):
 
 last_conv_kernel = ""        # kernel instance the most recent conv2d() launched (rocprofv3 spelling), for tests / profiles
 last_wgrad_kernel = ""       # ... and the most recent conv2d_wgrad()
+last_stem_wgrad_kernel = ""  # ... and the most recent stem_wgrad_pool()
 
 
 def conv2d(x, w, stride, pad, *, in_scale=None, in_shift=None, in_relu=False, bias=None, residual=None, relu=False,
@@ -298,6 +299,8 @@ def stem_wgrad_pool(x_nchw, dw, raw, scale, shift, mean, invstd, pool, *, x2=Non
     L.check(L.lib().sslcr_bn_bwd_reduce(_dt(raw), b, L.stream_ptr()))
     w = L.StemWgradDesc(L.ptr(x_nchw), None, L.ptr(dw), N, H, W, OH, OW, int(x_nchw.dtype == torch.float32),
                         L.ptr(x2), int(n_split))
+    global last_stem_wgrad_kernel
+    last_stem_wgrad_kernel = L.lib().sslcr_stem_wgrad_pool_kernel_name(_dt(raw), w).decode()
     L.check(L.lib().sslcr_stem_wgrad_pool(_dt(raw), w, b, L.stream_ptr()))
     return sums
 

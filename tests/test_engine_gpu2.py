@@ -841,9 +841,9 @@ print("GP", " ".join(f"{float(g.flatten()[::7].sum()):.9e}" for g in gr))
 
 
 # ------------------------------------------------------------------------------------------------ paired BatchNorm backward
-def _supervised_step_gradients(dtype, n, path):
-    """every gradient of one supervised 'ce' step on n 256x256 images and the names of the profiled kernels the step launched, saved
-    to `path` (run in a child process: see below)"""
+def _supervised_step_gradients(dtype, n, path, hw=256):
+    """every gradient of one supervised 'ce' step on n hw x hw images, the names of the profiled kernels the step launched and the bytes
+    the profile books per name, saved to `path` (run in a child process: see below)"""
     from ssl_cr_histo_amd import engine as E
     eng = E.set_engine(E.Engine(DEV, dtype))
     model, cls = build("finetune", "finetune", 2, True)
@@ -851,9 +851,11 @@ def _supervised_step_gradients(dtype, n, path):
     cls.train()
     net_ = eng.bind(model, cls)
     eng.profile(True)
-    eng.step_supervised(net_, "ce", [C.u8(8101, (n, 3, 256, 256))], C.ints(8102, (n,), 2).long(), train=True)
+    eng.step_supervised(net_, "ce", [C.u8(8101, (n, 3, hw, hw))], C.ints(8102, (n,), 2).long(), train=True)
     torch.cuda.synchronize()
-    torch.save(dict(grads=[net_.grad(i).cpu() for i in range(len(net_.params))], kernels=[r["name"] for r in eng.profile_table()]), path)
+    table = eng.profile_table()
+    torch.save(dict(grads=[net_.grad(i).cpu() for i in range(len(net_.params))], kernels=[r["name"] for r in table],
+                    bytes={r["name"]: r["bytes"] for r in table}), path)
 
 
 @pytest.mark.parametrize("dtype,n", [("bf16", 64), ("fp32", 32)])

@@ -10,10 +10,12 @@ import re
 import pytest
 
 from kernel_routes import ROUTES
+from switch_routes import ROUTING
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# the routing caches these A/B switches in statics: a set one would route (and pass) a different table
-SWITCHES = ("SSLCR_PP64", "SSLCR_S2", "SSLCR_S2D", "SSLCR_BN_ONE_LAUNCH")
+# the routing caches these A/B switches in statics: a set one would route (and pass) a different table.  Every routing switch of
+# tests/switch_routes.py (the routes behind them have a table and a walk of their own: tests/test_switch_routes_cpu.py)
+SWITCHES = tuple(ROUTING) + ("SSLCR_BN_ONE_LAUNCH",)
 FAKE = 4096        # a non-NULL pointer for the descriptor fields that select a route (nothing is launched)
 
 
