@@ -48,7 +48,8 @@ extern "C" {
  * descriptor whose launch read a NULL pointer on the device.  The ranking entries (sslcr_sort_pairs, sslcr_sort_workspace_bytes,
  * sslcr_rank_keys, sslcr_auc_counts, sslcr_auc_workspace_bytes) are additive in the same way, again without a new number, and so
  * are the resize entries (sslcr_resample, sslcr_resample_plan, sslcr_resample_coeffs, sslcr_resample_ksize,
- * sslcr_resample_table_ok) and the k-NN probe's (sslcr_knn_plan, sslcr_knn_topk, sslcr_knn_vote, sslcr_l2_normalize). */
+ * sslcr_resample_table_ok), the k-NN probe's (sslcr_knn_plan, sslcr_knn_topk, sslcr_knn_vote, sslcr_l2_normalize) and the t-SNE
+ * embedding's (sslcr_tsne_plan, sslcr_tsne_pair_dist2, sslcr_tsne_affinities, sslcr_tsne_repulsion, sslcr_tsne_update, sslcr_tsne_kl). */
 int sslcr_version(void);
 const char* sslcr_last_error(void);
 
@@ -1097,6 +1098,79 @@ typedef struct sslcr_knn_vote_desc {
   float temperature;
 } sslcr_knn_vote_desc;
 int sslcr_knn_vote(const sslcr_knn_vote_desc* d, void* stream);
+
+/* ---- t-SNE embedding on the device (csrc/tsne.hip): what every main() of the reference does with final_feats after its best epoch,
+ *      TSNE().fit_transform(final_feats) (pretrain_BreastPathQ.py:322-340), without the plot.  Two components, one degree of freedom,
+ *      squared Euclidean distances, k <= 64 neighbours (sslcr_knn_topk's cap; sklearn takes 3 * perplexity + 1 = 91 at its default),
+ *      an EXACT repulsive sum over all pairs.  tests/_tsne_ref.py is the float64 restatement, pinned to sklearn 1.7.2.  Additive,
+ *      WITHOUT a new version number: a caller tests for sslcr_tsne_plan, sslcr_tsne_pair_dist2, sslcr_tsne_affinities,
+ *      sslcr_tsne_repulsion, sslcr_tsne_update and sslcr_tsne_kl by symbol.  Every entry is asynchronous; none synchronises.
+ *
+ *      sslcr_tsne_pair_dist2.  dist2[i][r] = sum_d (x[i][d] - x[j][d])^2 for j = indices[i][r]: x float32 [n][D], every difference
+ *      exact in float64, every square one float64 rounding, the sum one float64 rounding per term in RISING d, the result rounded to
+ *      float32 once.  An index outside [0, n) gives +inf.  One thread per (i, r).
+ *
+ *      sslcr_tsne_affinities.  sklearn/manifold/_utils.pyx, _binary_search_perplexity, statement by statement: dist2 float32 [n][k]
+ *      (1 <= k <= 64), P float32 [n][k] and beta float64 [n] out.  Per row: beta = 1, at most 100 steps of
+ *      P_j = exp(-d_j beta), s = sum P (1e-8 if 0), P_j /= s, H = log(s) + beta sum d_j P_j, stop when |H - log(perplexity)| <= 1e-5,
+ *      else double / halve / bisect beta as sklearn does.  float64 inside.  One wave per row, one neighbour per lane; both sums are
+ *      xor-butterflies over the 64 lanes (lanes >= k hold 0): a fixed tree, every lane ends with the same bits.
+ *
+ *      sslcr_tsne_repulsion.  sklearn/manifold/_t_sne.py, _kl_divergence: q_ij = 1 / (1 + |y_i - y_j|^2), the self pair left out BY
+ *      INDEX (coincident points count with q = 1).  Grid = row tiles (SSLCR_TSNE_TILE rows, one a thread) x S column slices; a
+ *      workgroup stages SSLCR_TSNE_CHUNK points of y as float2 in LDS and every lane reads the same address.  Per lane, in float32 and
+ *      RISING j: (sum q, sum q^2 dx, sum q^2 dy), q by v_rcp_f32; the three go to workspace[(i * S + s)] as one float4.  An empty
+ *      slice writes zeros.  A second launch of ONE workgroup folds the n * S values of sum q into the float64 Z in a fixed order
+ *      (thread t takes t, t + 1024, ...; then a tree).  No floating-point atomics, no tickets, no spins.
+ *
+ *      sslcr_tsne_update.  One wave per row i.  rep_i = the S partials folded in float64 in rising s; attr_i = sum over the row's CSR
+ *      entries of p_ij q_ij (y_i - y_j) in float64 (lanes stride over the entries, then the butterfly); grad_i = 4 (exaggeration
+ *      attr_i - rep_i / Z), written as float32.  kl_rows (optional): sum_j p_ij log(p_ij / max(q_ij / Z, DBL_EPSILON)) of the row.
+ *      With y_out (sklearn/manifold/_t_sne.py, _gradient_descent, one iteration, float64 from the float32 state, each result
+ *      rounded once): inc = update * grad < 0; gains = inc ? gains + 0.2 : gains * 0.8, floored at min_gain; update = momentum *
+ *      update - lr * gains * grad; y_out = y + update.  y_out must not be y (other rows still read y).  y_out NULL: gradient only.
+ *
+ *      sslcr_tsne_kl.  One workgroup: log_row[0] = sum of kl_rows, [1] = |grad|_2, [2] = Z, [3] = iteration, float64, fixed order.
+ *
+ *      sslcr_tsne_plan: HOST-ONLY: tile, chunk, S, chunks per slice and workspace bytes of n points; slices_hint > 0 asks for that S
+ *      (up to the chunk count and SSLCR_TSNE_MAX_SLICES), 0 lets the plan fill the chip (1024 workgroups).  2 <= n <= 2^20.
+ *      Errors: NULL descriptor or tensors, n outside [2, 2^20], k outside [1, 64], D < 1, perplexity not > 0, slices < 0,
+ *      y_out == y, float2 / float4 / float64 tensors not 8- / 16- / 8-byte aligned, others not 4-byte. */
+#define SSLCR_TSNE_TILE 256        /* rows of a repulsion workgroup, one a thread */
+#define SSLCR_TSNE_CHUNK 1024      /* points of y per LDS stage */
+#define SSLCR_TSNE_MAX_SLICES 64
+#define SSLCR_TSNE_MAX_N 1048576
+#define SSLCR_TSNE_LOG_COLS 4
+typedef struct sslcr_tsne_plan_info {
+  int tile, chunk;
+  int slices;               /* S */
+  int chunks_per_slice;     /* slice s covers columns [s * chunks_per_slice * chunk, ...) */
+  int grid[3];              /* workgroups of the repulsion launch (row tiles * S), of the Z fold (1) and of the update */
+  size_t lds_bytes;
+  size_t workspace_bytes;   /* n * S float4 */
+} sslcr_tsne_plan_info;
+typedef struct sslcr_tsne_grad_desc {
+  const float* y;           /* [n][2] */
+  float* y_out;             /* [n][2] or NULL (gradient only) */
+  float* update;            /* [n][2] */
+  float* gains;             /* [n][2] */
+  float* grad;              /* [n][2] out */
+  const int32_t* rowptr;    /* [n + 1] */
+  const int32_t* col;
+  const float* val;
+  void* workspace;          /* sslcr_tsne_plan_info.workspace_bytes */
+  double* Z;                /* [1] */
+  double* kl_rows;          /* [n] or NULL */
+  int n, slices;            /* slices: the plan's slices_hint */
+  int nnz;                  /* entries col / val hold: rowptr is clamped to it */
+  double exaggeration, momentum, lr, min_gain;   /* sklearn's are float64 */
+} sslcr_tsne_grad_desc;
+int sslcr_tsne_plan(int n, int slices_hint, sslcr_tsne_plan_info* out);
+int sslcr_tsne_pair_dist2(const float* x, const int32_t* indices, float* dist2, int n, int D, int k, void* stream);
+int sslcr_tsne_affinities(const float* dist2, float* P, double* beta, int n, int k, float perplexity, void* stream);
+int sslcr_tsne_repulsion(const sslcr_tsne_grad_desc* d, void* stream);
+int sslcr_tsne_update(const sslcr_tsne_grad_desc* d, void* stream);
+int sslcr_tsne_kl(const double* kl_rows, const float* grad, const double* Z, double* log_row, int n, int iteration, void* stream);
 
 /* ---- device-side strong augmentation, the colour ops of the reference's RandAugment pool ("next" row f4) on a uint8 batch in HBM.
  *      As with sslcr_weak_augment the random draws stay on the host, in the reference's order (ssl_cr_histo_amd/augment.py);

@@ -135,6 +135,12 @@ KnnPlan = _S("sslcr_knn_plan_info", "KnnPlan", [(k, i32) for k in ("form", "tile
 KnnVoteDesc = _S("sslcr_knn_vote_desc", "KnnVoteDesc", [(k, vp) for k in ("indices", "scores", "labels", "targets", "query_labels", "pred", "pred_value",
                                                                           "votes", "confusion")] +
                  [(k, i32) for k in ("nq", "k", "nb", "C", "mode")] + [("temperature", f32)])
+TSNE_TILE, TSNE_CHUNK, TSNE_MAX_SLICES, TSNE_MAX_N, TSNE_LOG_COLS = 256, 1024, 64, 1 << 20, 4
+TsnePlan = _S("sslcr_tsne_plan_info", "TsnePlan", [(k, i32) for k in ("tile", "chunk", "slices", "chunks_per_slice")] +
+              [("grid", i32 * 3), ("lds_bytes", sz), ("workspace_bytes", sz)])
+TsneGradDesc = _S("sslcr_tsne_grad_desc", "TsneGradDesc", [(k, vp) for k in ("y", "y_out", "update", "gains", "grad", "rowptr", "col", "val", "workspace",
+                                                                             "Z", "kl_rows")] +
+                  [(k, i32) for k in ("n", "slices", "nnz")] + [(k, f64) for k in ("exaggeration", "momentum", "lr", "min_gain")])
 PackDesc = _S("sslcr_pack_desc", "PackDesc", [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("gamma", vp), ("beta", vp), ("rmean", vp),
                            ("rvar", vp), ("eps", f32), ("bias_out", vp)] + [(k, i32) for k in ("K", "C", "R", "S", "dgrad_flip")] + [("scale_out", vp)])
 
@@ -153,6 +159,8 @@ CONSTANTS.update({"SSLCR_RESAMPLE_" + k.upper(): v for v, k in enumerate(RESAMPL
 CONSTANTS.update({"SSLCR_KNN_TILE": KNN_TILE, "SSLCR_KNN_CHUNK": KNN_CHUNK, "SSLCR_KNN_MAX_K": KNN_MAX_K, "SSLCR_KNN_MAX_D": KNN_MAX_D,
                   "SSLCR_KNN_MAX_SLICES": KNN_MAX_SLICES})
 CONSTANTS.update({"SSLCR_KNN_" + k.upper(): v for v, k in enumerate(KNN_FORMS)})
+CONSTANTS.update({"SSLCR_TSNE_TILE": TSNE_TILE, "SSLCR_TSNE_CHUNK": TSNE_CHUNK, "SSLCR_TSNE_MAX_SLICES": TSNE_MAX_SLICES,
+                  "SSLCR_TSNE_MAX_N": TSNE_MAX_N, "SSLCR_TSNE_LOG_COLS": TSNE_LOG_COLS})
 CONSTANTS.update({"SSLCR_KNN_VOTE_" + k.upper(): v for k, v in KNN_VOTES.items()})
 
 # symbol -> (restype, argtypes); every symbol include/sslcr.h declares
@@ -229,6 +237,12 @@ SIGNATURES = {
     "sslcr_knn_topk": (i32, [P(KnnDesc), vp]),
     "sslcr_l2_normalize": (i32, [vp, vp, i32, i32, f32, vp]),
     "sslcr_knn_vote": (i32, [P(KnnVoteDesc), vp]),
+    "sslcr_tsne_plan": (i32, [i32, i32, P(TsnePlan)]),
+    "sslcr_tsne_pair_dist2": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "sslcr_tsne_affinities": (i32, [vp, vp, vp, i32, i32, f32, vp]),
+    "sslcr_tsne_repulsion": (i32, [P(TsneGradDesc), vp]),
+    "sslcr_tsne_update": (i32, [P(TsneGradDesc), vp]),
+    "sslcr_tsne_kl": (i32, [vp, vp, vp, vp, i32, i32, vp]),
     "sslcr_optimizer_step": (i32, [vp, i32, i32, P(OptDesc), vp]),
     "sslcr_optimizer_step_groups": (i32, [vp, i32, i32, P(OptDesc), i32, vp, vp]),
     "sslcr_grad_norm": (i32, [vp, sz, f32, vp, vp, vp]),

@@ -673,6 +673,63 @@ int sslcr_knn_vote(const sslcr_knn_vote_desc* d, void* stream) {
        "labels / query_labels / pred / confusion alignment");
   return check(launch_knn_vote(*d, (hipStream_t)stream), "knn_vote");
 }
+// ---- t-SNE embedding (tsne.hip)
+int sslcr_tsne_plan(int n, int slices_hint, sslcr_tsne_plan_info* out) {
+  NEED(out, "null");
+  const char* why = tsne_plan(n, slices_hint, out);
+  NEED(!why, why);
+  return 0;
+}
+int sslcr_tsne_pair_dist2(const float* x, const int32_t* indices, float* dist2, int n, int D, int k, void* stream) {
+  NEED(n >= 2 && n <= SSLCR_TSNE_MAX_N, "n outside [2, 2^20]");
+  NEED(D >= 1, "D < 1");
+  NEED(k >= 1 && k <= SSLCR_KNN_MAX_K, "k outside [1, 64]");
+  NEED(x && indices && dist2, "null tensor");
+  NEED(ALIGNED(x, 3) && ALIGNED(indices, 3) && ALIGNED(dist2, 3), "x / indices / dist2 alignment");
+  return check(launch_tsne_pair_dist2(x, indices, dist2, n, D, k, (hipStream_t)stream), "tsne_pair_dist2");
+}
+int sslcr_tsne_affinities(const float* dist2, float* P, double* beta, int n, int k, float perplexity, void* stream) {
+  NEED(n >= 2 && n <= SSLCR_TSNE_MAX_N, "n outside [2, 2^20]");
+  NEED(k >= 1 && k <= SSLCR_KNN_MAX_K, "k outside [1, 64]");
+  NEED(perplexity > 0.f, "perplexity must be > 0");
+  NEED(dist2 && P && beta, "null tensor");
+  NEED(ALIGNED(dist2, 3) && ALIGNED(P, 3) && ALIGNED(beta, 7), "dist2 / P / beta alignment");
+  return check(launch_tsne_affinities(dist2, P, beta, n, k, perplexity, (hipStream_t)stream), "tsne_affinities");
+}
+static int tsne_grad_ok(const sslcr_tsne_grad_desc* d, TsnePlan* p, bool update) {
+  NEED(d, "null descriptor");
+  const char* why = tsne_plan(d->n, d->slices, p);
+  NEED(!why, why);
+  NEED(d->y && d->workspace && d->Z, "null tensor");
+  NEED(ALIGNED(d->y, 7) && ALIGNED(d->workspace, 15) && ALIGNED(d->Z, 7), "y / workspace / Z alignment");
+  if (!update) return 0;
+  NEED(d->grad && d->rowptr && d->col && d->val, "null tensor");
+  NEED(d->nnz >= 0, "nnz < 0");
+  NEED(ALIGNED(d->grad, 7) && ALIGNED(d->rowptr, 3) && ALIGNED(d->col, 3) && ALIGNED(d->val, 3) && ALIGNED(d->kl_rows, 7),
+       "grad / rowptr / col / val / kl_rows alignment");
+  if (d->y_out) {
+    NEED(d->y_out != d->y, "y_out == y (other rows still read y)");
+    NEED(d->update && d->gains, "null tensor");
+    NEED(ALIGNED(d->y_out, 7) && ALIGNED(d->update, 7) && ALIGNED(d->gains, 7), "y_out / update / gains alignment");
+  }
+  return 0;
+}
+int sslcr_tsne_repulsion(const sslcr_tsne_grad_desc* d, void* stream) {
+  TsnePlan p;
+  if (tsne_grad_ok(d, &p, false)) return -1;
+  return check(launch_tsne_repulsion(*d, p, (hipStream_t)stream), "tsne_repulsion");
+}
+int sslcr_tsne_update(const sslcr_tsne_grad_desc* d, void* stream) {
+  TsnePlan p;
+  if (tsne_grad_ok(d, &p, true)) return -1;
+  return check(launch_tsne_update(*d, p, (hipStream_t)stream), "tsne_update");
+}
+int sslcr_tsne_kl(const double* kl_rows, const float* grad, const double* Z, double* log_row, int n, int iteration, void* stream) {
+  NEED(n >= 2 && n <= SSLCR_TSNE_MAX_N, "n outside [2, 2^20]");
+  NEED(kl_rows && grad && Z && log_row, "null tensor");
+  NEED(ALIGNED(kl_rows, 7) && ALIGNED(grad, 3) && ALIGNED(Z, 7) && ALIGNED(log_row, 7), "kl_rows / grad / Z / log_row alignment");
+  return check(launch_tsne_kl(kl_rows, grad, Z, log_row, n, iteration, (hipStream_t)stream), "tsne_kl");
+}
 #undef SQ_SHAPE_OK
 #undef MAP_SHAPE_OK
 #undef ALIGNED

@@ -240,6 +240,15 @@ const char* knn_plan(int nq, int nb, int D, int k, int slices_hint, KnnPlan* out
 hipError_t launch_knn_topk(const sslcr_knn_desc& a, const KnnPlan& p, hipStream_t st);
 hipError_t launch_l2_normalize(const float* x, float* y, int n, int D, float eps, hipStream_t st);
 hipError_t launch_knn_vote(const sslcr_knn_vote_desc& a, hipStream_t st);
+// tsne.hip: the row tile, the chunk and the slice count are decided ONCE, here -- the launches, sslcr_tsne_plan, the Python layer and the tests read this plan
+using TsnePlan = sslcr_tsne_plan_info;
+// nullptr and *out filled, or what is wrong with the arguments (host only)
+const char* tsne_plan(int n, int slices_hint, TsnePlan* out);
+hipError_t launch_tsne_pair_dist2(const float* x, const int32_t* indices, float* dist2, int n, int D, int k, hipStream_t st);
+hipError_t launch_tsne_affinities(const float* dist2, float* P, double* beta, int n, int k, float perplexity, hipStream_t st);
+hipError_t launch_tsne_repulsion(const sslcr_tsne_grad_desc& a, const TsnePlan& p, hipStream_t st);
+hipError_t launch_tsne_update(const sslcr_tsne_grad_desc& a, const TsnePlan& p, hipStream_t st);
+hipError_t launch_tsne_kl(const double* kl_rows, const float* grad, const double* Z, double* log_row, int n, int iteration, hipStream_t st);
 // augment.hip
 hipError_t launch_weak_augment(const sslcr_weak_aug_desc& a, hipStream_t st);
 hipError_t launch_hed_colour(const sslcr_colour_aug_desc& a, hipStream_t st);

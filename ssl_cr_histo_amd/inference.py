@@ -760,3 +760,177 @@ def knn_probe(feats, targets, k=20, leave_one_out=True, *, queries=None, query_t
     out = metrics_from_confusion(cm)
     out.update(confusion=cm, pred=flat[Cn * Cn:])
     return out
+
+
+# ---- t-SNE embedding: what the reference's mains do with final_feats after the best epoch (TSNE().fit_transform), without the plot
+class Tsne:
+    """t-SNE of device features into two components, every launch on the caller's stream (csrc/tsne.hip; the arithmetic is sklearn
+    1.7.2's ``TSNE(method="exact")`` on k-nearest-neighbour affinities, restated and pinned in tests/_tsne_ref.py):
+    ``kernels.euclidean_topk`` (k = min(n - 1, int(3 perplexity + 1), 64); sklearn has no cap at 64), ``tsne_affinities``,
+    ``tsne_joint``, then ``max_iter`` times ``tsne_step`` -- the EXACT repulsive sum over all pairs, no tree and no grid --
+    with early exaggeration and momentum 0.5 for the first 250 iterations, then 1 and 0.8.  learning_rate "auto" =
+    max(n / early_exaggeration / 4, 50).
+
+    init: "pca" (float64 covariance and ``torch.linalg.eigh`` on the device, each axis signed so that its largest-magnitude loading
+    is positive, scaled to std(y[:, 0]) = 1e-4 -- PARITY UNPINNED against sklearn's randomized PCA, whose axes differ in sign and in
+    the last bits), "random" (1e-4 randn, ``generator``) or a device tensor [n, 2].
+
+    ``fit(feats)`` (device float32 [n, D], 2 <= n <= 2^20, D % 4 == 0, 4 <= D <= 2044) queues everything and makes ONE copy at the
+    end, of the log; KL and |grad| go to a device log every ``check_every`` iterations and once at the end.  ``early_stop=True``
+    applies sklearn's two stopping rules (no progress for 250 / 300 iterations, |grad| <= 1e-7 -- of the plain gradient, where
+    sklearn measures it after the gains) and pays one host read per check; the default never reads inside the loop.  ``reads`` counts
+    the calls of the one read site.  After a fit: ``embedding_`` (device [n, 2]), ``kl_divergence_``, ``log`` (array [checks, 4]:
+    KL, |grad|, Z, iteration), ``n_iter_``.  ``step()`` runs one iteration; ``state`` holds y, update, gains, grad and iteration."""
+    STOP_LYING, MIN_GRAD_NORM = 250, 1e-7
+
+    def __init__(self, perplexity=30.0, early_exaggeration=12.0, learning_rate="auto", max_iter=1000, init="pca", generator=None,
+                 check_every=50, early_stop=False, slices=None):
+        if not (isinstance(init, torch.Tensor) or init in ("pca", "random")):
+            raise ValueError(f"Tsne: init = {init!r} outside ('pca', 'random', tensor [n, 2])")
+        if learning_rate != "auto" and not float(learning_rate) > 0:
+            raise ValueError(f"Tsne: learning_rate = {learning_rate!r} must be 'auto' or > 0")
+        if max_iter < 0 or check_every < 1 or not perplexity > 0:
+            raise ValueError("Tsne: max_iter >= 0, check_every >= 1 and perplexity > 0 expected")
+        self.perplexity, self.early_exaggeration, self.learning_rate = float(perplexity), float(early_exaggeration), learning_rate
+        self.max_iter, self.init, self.generator, self.check_every, self.early_stop, self.slices = int(max_iter), init, generator, int(check_every), early_stop, slices
+        self.reads = 0
+        self.iteration = 0
+        self.P = None
+
+    # the one read site
+    def _read(self, t):
+        self.reads += 1
+        return t.cpu().numpy()
+
+    @staticmethod
+    def neighbours(n, perplexity):
+        k = min(n - 1, int(3.0 * perplexity + 1), K.KNN_MAX_K)
+        if not perplexity < k:
+            raise ValueError(f"Tsne: perplexity = {perplexity} must be below the neighbour count k = {k} (n = {n}; k is capped at {K.KNN_MAX_K})")
+        return k
+
+    @staticmethod
+    def center(x):
+        """x minus the float32 rounding of its float64 column mean"""
+        return x - x.double().mean(0).float()[None, :]
+
+    @staticmethod
+    def pca_init(xc):
+        x = xc.double()
+        x = x - x.mean(0)
+        _, v = torch.linalg.eigh(x.T @ x / (x.shape[0] - 1))
+        v = v.flip(1)[:, :2]
+        top = v.gather(0, v.abs().argmax(0, keepdim=True))
+        y = x @ (v * torch.sign(top))
+        return (y / y[:, 0].std(unbiased=False) * 1e-4).float()
+
+    def prepare(self, feats):
+        """everything before the first iteration: neighbours, affinities, the joint CSR, the initial state"""
+        if not isinstance(feats, torch.Tensor) or not feats.is_cuda or feats.dtype != torch.float32 or feats.dim() != 2:
+            raise K.L.SslcrError("Tsne.fit: device float32 [n, D] expected (no CPU fallback)")
+        n, D = feats.shape
+        if not 2 <= n <= K.TSNE_MAX_N or D % 4 or not 4 <= D <= K.KNN_MAX_D - 4:
+            raise K.L.SslcrError(f"Tsne.fit: n = {n} outside [2, 2^20] or D = {D} not a multiple of 4 in [4, {K.KNN_MAX_D - 4}]")
+        k = self.neighbours(n, self.perplexity)
+        dev = feats.device
+        xc = self.center(feats.detach()).contiguous()
+        idx, d2 = K.euclidean_topk(xc, k)
+        cond, self.beta = K.tsne_affinities(d2, self.perplexity)
+        self.P = K.tsne_joint(idx, cond)
+        if isinstance(self.init, torch.Tensor):
+            if tuple(self.init.shape) != (n, 2):
+                raise ValueError(f"Tsne.fit: init must be [{n}, 2]")
+            y = self.init.to(dev, torch.float32).contiguous().clone()
+        elif self.init == "pca":
+            y = self.pca_init(xc).contiguous()
+        else:
+            y = (1e-4 * torch.randn((n, 2), generator=self.generator, device=dev if self.generator is None else self.generator.device)).to(dev, torch.float32)
+        self.n = n
+        self.lr = max(n / self.early_exaggeration / 4.0, 50.0) if self.learning_rate == "auto" else float(self.learning_rate)
+        self._y = [y, torch.empty_like(y)]
+        self._cur = 0
+        self._update, self._gains, self._grad = torch.zeros_like(y), torch.ones_like(y), torch.zeros_like(y)
+        self._w = K.tsne_workspace(n, dev, self.slices)
+        self._kl_rows = torch.empty(n, dtype=torch.float64, device=dev)
+        rows = self.max_iter // self.check_every + 2
+        self._log = torch.zeros((rows, K.TSNE_LOG_COLS), dtype=torch.float64, device=dev)
+        self._log_rows = 0
+        self.iteration = 0
+        return self
+
+    @property
+    def state(self):
+        return dict(y=self._y[self._cur], update=self._update, gains=self._gains, grad=self._grad,
+                    iteration=torch.tensor(self.iteration, device=self._grad.device))
+
+    def schedule(self, it):
+        return (self.early_exaggeration, 0.5) if it < self.STOP_LYING else (1.0, 0.8)
+
+    def _log_kl(self, it):
+        if self._log_rows >= self._log.shape[0]:                                         # step() called past max_iter: a longer log
+            self._log = torch.cat([self._log, torch.zeros_like(self._log)])
+        K.tsne_kl(self._kl_rows, self._grad, self._w["Z"], self._log[self._log_rows], it)
+        self._log_rows += 1
+        return self._log[self._log_rows - 1]
+
+    def step(self):
+        """one iteration: three launches (four on a check iteration), no host read.  -> the log row on a check iteration, else None"""
+        it = self.iteration
+        e, mom = self.schedule(it)
+        check = (it + 1) % self.check_every == 0
+        K.tsne_step(self._y[self._cur], self._y[1 - self._cur], self._update, self._gains, self.P, exaggeration=e, momentum=mom, lr=self.lr,
+                    workspace=self._w, grad=self._grad, kl_rows=self._kl_rows if check else None)
+        row = self._log_kl(it) if check else None
+        self._cur ^= 1
+        self.iteration = it + 1
+        return row
+
+    def fit(self, feats):
+        self.prepare(feats)
+        best = {}                                    # per stage (False: exaggerated): (the lowest KL so far, its iteration)
+        while self.iteration < self.max_iter:
+            it = self.iteration
+            row = self.step()
+            if row is not None and self.early_stop:
+                kl, gnorm = self._read(row)[:2]
+                second = it >= self.STOP_LYING
+                low, low_it = best.get(second, (float("inf"), self.STOP_LYING if second else 0))
+                stop = gnorm <= self.MIN_GRAD_NORM
+                if kl < low:
+                    best[second] = (kl, it)
+                elif it - low_it > (300 if second else 250):
+                    stop = True
+                if stop and second:
+                    break
+                if stop:                             # sklearn ends the exaggerated stage and goes on with the second
+                    self.iteration = self.STOP_LYING
+        return self._finish()
+
+    def _finish(self):
+        # the KL of the final embedding: a gradient without an update
+        g, _ = K.tsne_gradient(self._y[self._cur], self.P, 1.0, workspace=self._w, kl_rows=self._kl_rows)
+        self._grad = g
+        self._log_kl(self.iteration)
+        self.log = self._read(self._log[:self._log_rows])                                # the one copy
+        self.embedding_ = self._y[self._cur]
+        self.kl_divergence_ = float(self.log[-1, 0])
+        self.n_iter_ = self.iteration
+        return self
+
+
+def tsne(feats, targets=None, **kw):
+    """The embedding the reference's mains plot: feats / targets as ``steps.rsp_train`` returns them (device float32 [n, D]; targets
+    pass through untouched for the plot's colours).  -> dict with ``embedding`` (DEVICE float32 [n, 2]: hand ``.cpu()`` of it to
+    matplotlib), ``kl_divergence``, ``n_iter`` and ``targets``.  kw: ``Tsne``'s arguments.  One copy to the host, of the log."""
+    t = Tsne(**kw).fit(feats)
+    return dict(embedding=t.embedding_, kl_divergence=t.kl_divergence_, n_iter=t.n_iter_, targets=targets, log=t.log)
+
+
+def neighbour_preservation(x, y, k):
+    """The mean share of each point's k nearest neighbours in x (device float32 [n, D], D <= 2044) that are also among its k nearest in
+    y (device float32 [n, d]): two ``kernels.euclidean_topk`` calls and one scalar copy.  The small quantitative companion of the
+    embedding."""
+    ix, _ = K.euclidean_topk(x.contiguous(), k)
+    iy, _ = K.euclidean_topk(y.contiguous(), k)
+    both = ((ix[:, :, None] == iy[:, None, :]) & (ix[:, :, None] >= 0)).any(2)
+    return float(both.sum().item()) / (ix.shape[0] * k)

@@ -1347,6 +1347,163 @@ def knn_vote(indices, scores, labels=None, targets=None, *, n_classes=None, weig
     return out
 
 
+# ---- t-SNE embedding (csrc/tsne.hip)
+TSNE_TILE, TSNE_CHUNK, TSNE_MAX_SLICES, TSNE_MAX_N, TSNE_LOG_COLS = L.TSNE_TILE, L.TSNE_CHUNK, L.TSNE_MAX_SLICES, L.TSNE_MAX_N, L.TSNE_LOG_COLS
+
+
+def tsne_plan(n, slices=None):
+    """what the t-SNE gradient launches for n points (sslcr_tsne_plan; host only, no device needed): dict with ``tile`` (rows of a
+    repulsion workgroup), ``chunk`` (points per LDS stage), ``slices`` (column slices S), ``chunks_per_slice``, ``grid`` (workgroups
+    of the repulsion, the Z fold and the update), ``lds_bytes`` and ``workspace_bytes``.  slices: the hint (None / 0 = the plan's)."""
+    p = L.TsnePlan()
+    L.check(L.lib().sslcr_tsne_plan(int(n), int(slices or 0), p))
+    out = {f: getattr(p, f) for f, _ in L.TsnePlan._fields_}
+    out["grid"] = tuple(p.grid)
+    return out
+
+
+def euclidean_topk(x, k, *, slices=None):
+    """-> ``(indices, dist2)``: device int32 [n, k] and float32 [n, k], per row of x (device float32 [n, D], D <= 2044) its k nearest
+    OTHER rows by squared Euclidean distance, nearest first.  The search is ``knn_topk`` unchanged, on the query rows ``[x, 1, 0..]``
+    against the bank rows ``[x, -|x|^2 / 2, 0..]`` (the width padded to a multiple of 4; the norm summed in float64, rounded once) with
+    ``exclude_self``: the greatest dot product is the least distance, and the order is ``knn_topk``'s total order.  The distances are
+    then recomputed directly (sslcr_tsne_pair_dist2: float64 sum over rising d, rounded to float32 once).  With fewer than k other
+    rows the trailing slots are index -1 and distance +inf.  Centre x first where its mean is far from 0.  No sync."""
+    x = _f32_rows("euclidean_topk", x)
+    n, D = x.shape
+    W = (D + 1 + 3) // 4 * 4
+    if not 2 <= n <= TSNE_MAX_N or W > KNN_MAX_D:
+        raise L.SslcrError(f"euclidean_topk: n = {n} outside [2, 2^20] or D = {D} above {KNN_MAX_D - 4}")
+    q = torch.zeros((n, W), dtype=torch.float32, device=x.device)
+    q[:, :D] = x
+    b = q.clone()
+    q[:, D] = 1.0
+    b[:, D] = (-0.5 * x.double().square().sum(1)).float()
+    _, indices = knn_topk(q, b, k, exclude_self=True, slices=slices)
+    dist2 = torch.empty((n, k), dtype=torch.float32, device=x.device)
+    L.check(L.lib().sslcr_tsne_pair_dist2(L.ptr(x), L.ptr(indices), L.ptr(dist2), n, D, int(k), L.stream_ptr()))
+    return indices, dist2
+
+
+def tsne_affinities(dist2, perplexity):
+    """-> ``(P, beta)``: device float32 [n, k] and float64 [n]: sklearn's ``_binary_search_perplexity`` on float32 squared distances
+    [n, k], k <= 64 (sslcr_tsne_affinities, one wave per row): the conditional p_{j|i} at the beta whose entropy is log(perplexity)
+    to 1e-5, found in at most 100 steps from beta = 1.  No sync."""
+    dist2 = _f32_rows("tsne_affinities", dist2)
+    n, k = dist2.shape
+    if not 1 <= k <= KNN_MAX_K or not 2 <= n <= TSNE_MAX_N or not float(perplexity) > 0:
+        raise L.SslcrError(f"tsne_affinities: k = {k} outside [1, 64], n = {n} outside [2, 2^20] or perplexity = {perplexity} not > 0")
+    P = torch.empty_like(dist2)
+    beta = torch.empty(n, dtype=torch.float64, device=dist2.device)
+    L.check(L.lib().sslcr_tsne_affinities(L.ptr(dist2), L.ptr(P), L.ptr(beta), n, k, float(perplexity), L.stream_ptr()))
+    return P, beta
+
+
+def tsne_joint(indices, P):
+    """-> ``(rowptr, col, val)``: the symmetric joint affinities p_ij = (p_{j|i} + p_{i|j}) / (2 n) as CSR: device int32 [n + 1], int32
+    [2 n k] and float32 [2 n k], columns rising within a row.  ``col`` / ``val`` have the CAPACITY 2 n k; the first ``rowptr[n]`` entries
+    are the matrix (reading that count is the caller's copy; nothing here synchronises).  The 2 n k directed entries are sorted by
+    two stable ``sort_pairs`` passes (column, then row); adjacent equal pairs are merged -- at most two meet, their float64 sum is
+    exact -- divided by 2 n in float64 and rounded to float32.  Two calls return equal bits.  A slot with index -1 takes no part."""
+    _chk(indices, P)
+    if indices.dtype != torch.int32 or indices.dim() != 2 or P.dtype != torch.float32 or P.shape != indices.shape or P.device != indices.device:
+        raise L.SslcrError("tsne_joint: int32 indices [n, k] and float32 P [n, k] on one device expected")
+    n, k = indices.shape
+    if not 2 <= n <= TSNE_MAX_N:
+        raise L.SslcrError(f"tsne_joint: n = {n} outside [2, 2^20]")
+    dev = indices.device
+    i = torch.arange(n, dtype=torch.int32, device=dev).repeat_interleave(k)
+    j = indices.reshape(-1)
+    # an empty slot (-1) sorts past every row as the pair (n, n) and is dropped by the row count below
+    miss = j < 0
+    full = torch.full_like(j, n)
+    r = torch.cat([torch.where(miss, full, i), torch.where(miss, full, j)])
+    c = torch.cat([torch.where(miss, full, j), torch.where(miss, full, i)])
+    v = torch.cat([P.reshape(-1), P.reshape(-1)]).double()
+    bits = (0, max(1, int(n).bit_length()))
+    c1, o1 = (t.view(torch.int32).long() for t in sort_pairs(c, bits=bits))             # by column ...
+    r2, o2 = (t.view(torch.int32).long() for t in sort_pairs(r[o1], bits=bits))         # ... then, stably, by row
+    c2, v2 = c1[o2], v[o1[o2]]
+    first = torch.ones_like(r2, dtype=torch.bool)
+    first[1:] = (r2[1:] != r2[:-1]) | (c2[1:] != c2[:-1])
+    seg = torch.cumsum(first, 0) - 1
+    M = r2.numel()
+    val = torch.zeros(M, dtype=torch.float64, device=dev).index_add_(0, seg, v2)        # at most two addends a cell: exact, any order
+    col = torch.zeros(M, dtype=torch.int32, device=dev).scatter_(0, seg, c2.int())      # equal values where two meet
+    counts = torch.zeros(n + 2, dtype=torch.int64, device=dev).index_add_(0, r2 + 1, first.long())
+    rowptr = torch.cumsum(counts[:n + 1], 0).int()
+    return rowptr, col, (val / (2.0 * n)).float()
+
+
+def _tsne_P(name, P, n, dev):
+    rowptr, col, val = P
+    _chk(rowptr, col, val)
+    if (rowptr.dtype != torch.int32 or rowptr.numel() != n + 1 or col.dtype != torch.int32 or val.dtype != torch.float32 or col.numel() != val.numel()
+            or any(t.device != dev for t in P)):
+        raise L.SslcrError(f"{name}: P = (rowptr int32 [{n + 1}], col int32 [nnz], val float32 [nnz]) on y's device expected")
+    return rowptr, col, val
+
+
+def _tsne_y(name, y):
+    if not y.is_cuda or y.dtype != torch.float32 or y.dim() != 2 or y.shape[1] != 2 or not y.is_contiguous():
+        raise L.SslcrError(f"{name}: contiguous device float32 [n, 2] expected (no CPU fallback)")
+    if not 2 <= y.shape[0] <= TSNE_MAX_N:
+        raise L.SslcrError(f"{name}: n = {y.shape[0]} outside [2, 2^20]")
+    return y.shape[0]
+
+
+def tsne_workspace(n, device, slices=None):
+    """the scratch a t-SNE gradient needs (``tsne_plan(n, slices)["workspace_bytes"]`` and the float64 Z): dict of device tensors"""
+    p = tsne_plan(n, slices)
+    return dict(ws=torch.empty(max(1, p["workspace_bytes"] // 4), dtype=torch.float32, device=device),
+                Z=torch.empty(1, dtype=torch.float64, device=device), slices=int(slices or 0))
+
+
+def tsne_gradient(y, P, exaggeration=1.0, *, slices=None, workspace=None, kl_rows=None):
+    """-> ``(grad, Z)``: device float32 [n, 2] and float64 [1]: sklearn's exact ``_kl_divergence`` gradient
+    4 (exaggeration sum_j p_ij q_ij (y_i - y_j) - (1 / Z) sum_{j != i} q_ij^2 (y_i - y_j)) of the embedding y (device float32 [n, 2])
+    under the joint affinities ``P = (rowptr, col, val)`` (``tsne_joint``).  Three launches: sslcr_tsne_repulsion (the exact O(n^2)
+    sum, grid = row tiles x ``slices``, and the fold of Z) and sslcr_tsne_update without a state.  kl_rows: device float64 [n] to
+    receive every row's share of the KL divergence.  Two calls return equal bits; ``slices`` changes only where the float32 partial
+    sums are cut.  No sync."""
+    n = _tsne_y("tsne_gradient", y)
+    rowptr, col, val = _tsne_P("tsne_gradient", P, n, y.device)
+    w = workspace or tsne_workspace(n, y.device, slices)
+    grad = torch.empty_like(y)
+    d = L.TsneGradDesc(L.ptr(y), None, None, None, L.ptr(grad), L.ptr(rowptr), L.ptr(col), L.ptr(val), L.ptr(w["ws"]), L.ptr(w["Z"]), L.ptr(kl_rows),
+                       n, w["slices"], col.numel(), float(exaggeration), 0.0, 0.0, 0.0)
+    L.check(L.lib().sslcr_tsne_repulsion(d, L.stream_ptr()))
+    L.check(L.lib().sslcr_tsne_update(d, L.stream_ptr()))
+    return grad, w["Z"]
+
+
+def tsne_step(y, y_out, update, gains, P, *, exaggeration, momentum, lr, min_gain=0.01, workspace=None, slices=None, grad=None, kl_rows=None):
+    """one t-SNE iteration (three launches, no sync): the gradient of ``tsne_gradient`` at y, then sklearn's ``_gradient_descent``
+    update: ``gains`` += 0.2 where ``update * grad < 0`` else *= 0.8, floored at min_gain; ``update`` = momentum update - lr gains grad
+    (both in place); ``y_out`` = y + update.  y_out is the OTHER of two ping-pong buffers: other rows still read y.  -> grad."""
+    n = _tsne_y("tsne_step", y)
+    rowptr, col, val = _tsne_P("tsne_step", P, n, y.device)
+    for t in (y_out, update, gains):
+        if _tsne_y("tsne_step", t) != n or t.device != y.device:
+            raise L.SslcrError("tsne_step: y, y_out, update and gains must share shape and device")
+    if y_out.data_ptr() == y.data_ptr():
+        raise L.SslcrError("tsne_step: y_out must not be y")
+    w = workspace or tsne_workspace(n, y.device, slices)
+    grad = torch.empty_like(y) if grad is None else grad
+    d = L.TsneGradDesc(L.ptr(y), L.ptr(y_out), L.ptr(update), L.ptr(gains), L.ptr(grad), L.ptr(rowptr), L.ptr(col), L.ptr(val), L.ptr(w["ws"]),
+                       L.ptr(w["Z"]), L.ptr(kl_rows), n, w["slices"], col.numel(), float(exaggeration), float(momentum), float(lr), float(min_gain))
+    L.check(L.lib().sslcr_tsne_repulsion(d, L.stream_ptr()))
+    L.check(L.lib().sslcr_tsne_update(d, L.stream_ptr()))
+    return grad
+
+
+def tsne_kl(kl_rows, grad, Z, log_row, iteration):
+    """``log_row`` (device float64 [4]) = (sum of kl_rows, |grad|_2, Z, iteration) (sslcr_tsne_kl, one workgroup, no sync)"""
+    _chk(kl_rows, grad, Z, log_row)
+    L.check(L.lib().sslcr_tsne_kl(L.ptr(kl_rows), L.ptr(grad), L.ptr(Z), L.ptr(log_row), kl_rows.numel(), int(iteration), L.stream_ptr()))
+    return log_row
+
+
 def grad_norm(flat, max_norm=float("inf")):
     """-> device tensor [norm, coef] for a 1-D fp32 tensor (any length, any 4-byte-aligned view): its 2-norm, summed in double in a
     fixed order, and min(1, max_norm / (norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_'s two numbers (sslcr_grad_norm).  No sync."""
