@@ -9,7 +9,12 @@
  *   - `stream` is the caller's hipStream_t (torch.cuda.current_stream().cuda_stream); all calls are asynchronous;
  *   - activations are NHWC, conv weights [K][R][S][C] ("KRSC"), dtype 0 = fp32 (exact-parity mode,
  *     v_mfma_f32_16x16x4_f32), 1 = bf16 storage with fp32 accumulate (v_mfma_f32_16x16x32_bf16);
- *   - one sslcr_ctx per process per device, not thread safe (single training thread, like the reference).
+ *   - one sslcr_ctx per process per device, not thread safe (single training thread, like the reference);
+ *   - alignment: a comment "Alignment (owner): names N-byte aligned; ..." states, for every pointer of a descriptor or of a
+ *     prototype, the least alignment of the address the caller may pass: the widest access a kernel makes through it.  A pointer
+ *     below it is an error decided before any launch (-1, the message names the pointer); NULL, where allowed, passes.  A contiguous
+ *     view into a larger allocation is fine as long as ITS first byte is aligned (tests/test_arena_gpu.py runs the training
+ *     kernels at exactly these alignments and at no multiple of twice them).
  */
 #ifndef SSLCR_H_
 #define SSLCR_H_
@@ -95,6 +100,10 @@ typedef struct sslcr_conv_desc {
      (full-size iteration: 1.75e-3 -> 4.9e-4, tools/bf16_teacher_fold_experiment.py, profiles/r06_bf16_teacher_fold_experiment.txt).
      Only with bias (the eval forms); not with stats / mask_x. */
   const float* out_scale;
+  /* Alignment (sslcr_conv_desc): x, w, y, residual, mask_x, bias, stats, out_scale 16-byte aligned (16-byte vector loads / stores and
+     16-byte lanes of buffer_load ... lds; bias, out_scale and the stats rows as float4); in_scale, in_shift, mask_scale, mask_shift,
+     mask_mean 4-byte aligned (scalar loads).  Errors of sslcr_conv2d, sslcr_conv2d_s2_pair (both descriptors) and sslcr_conv2d_fp8:
+     a pointer below its alignment. */
 } sslcr_conv_desc;
 int sslcr_conv2d(int dtype, const sslcr_conv_desc* d, void* stream);
 int sslcr_conv2d_partial_rows(const sslcr_conv_desc* d);                /* -1: d is NULL, or no segment fits (seg_images > N) */
@@ -127,6 +136,8 @@ typedef struct sslcr_fp8_desc {
   float* amax_out;          /* optional device float (>= 0 on entry): atomically raised to max |transformed activation| seen by this
                                launch, before scaling and clamping -- the engine turns it into the NEXT step's x_scale
                                (scale = 2^floor(log2(448 / (2 amax))): a factor 2 of headroom), the delayed-scaling recipe */
+  /* Alignment (sslcr_fp8_desc): w8, w_dequant 16-byte aligned (LDS DMA lanes; the dequant scales as float4); x_scale_dev, amax_out
+     4-byte aligned.  Errors of sslcr_conv2d_fp8: a pointer below its alignment. */
 } sslcr_fp8_desc;
 int sslcr_conv2d_fp8(const sslcr_conv_desc* d, const sslcr_fp8_desc* q, void* stream);
 int sslcr_conv2d_fp8_partial_rows(const sslcr_conv_desc* d);      /* rows of d->stats the fp8 kernel writes; 0 = shape not served */
@@ -158,6 +169,8 @@ typedef struct sslcr_wgrad_desc {
   int seg_images;         /* optional (> 0, divides N; 3x3 stride-1 halo kernel shapes only): the batch is N / seg_images segments   */
   int seg_stride;         /* with their own producer BatchNorm -- segment s uses in_scale + s*seg_stride, in_shift + s*seg_stride    */
                           /* (the TripletNet branches as one batch: dW is linear in the pixels, their statistics are per branch)    */
+  /* Alignment (sslcr_wgrad_desc): x, dy 16-byte aligned; dw, in_scale, in_shift 4-byte aligned (dW is read and written one float
+     at a time by its single owner).  Errors of sslcr_conv2d_wgrad: a pointer below its alignment. */
 } sslcr_wgrad_desc;
 int sslcr_conv2d_wgrad(int dtype, const sslcr_wgrad_desc* d, void* stream);
 /* name of the kernel instance sslcr_conv2d_wgrad would launch for this descriptor (static string, as sslcr_conv2d_kernel_name) */
@@ -179,6 +192,8 @@ typedef struct sslcr_stem_desc {
                              reference's torch.cat((inputs_x, inputs_u_s)) (eval_BreastPathQ_SSL_CR.py:82) without the copy */
   int n_split;
   const float* out_scale; /* [64] or NULL, as sslcr_conv_desc.out_scale (library version >= 6) */
+  /* Alignment (sslcr_stem_desc): w, y 16-byte aligned; x, x2, bias, stats, out_scale 4-byte aligned (the uint8 planes are read as
+     whole dwords where W % 4 == 0).  Errors of sslcr_stem_conv and sslcr_stem_conv_pool: a pointer below its alignment. */
 } sslcr_stem_desc;
 int sslcr_stem_conv(int dtype, const sslcr_stem_desc* d, void* stream);
 int sslcr_stem_partial_rows(const sslcr_stem_desc* d);
@@ -193,6 +208,8 @@ typedef struct sslcr_stem_wgrad_desc {
   float* dw;              /* [64][3][7][7] fp32 (PyTorch layout), accumulated */
   int N, H, W, OH, OW, in_f32;
   const void* x2; int n_split;   /* as in sslcr_stem_desc */
+  /* Alignment (sslcr_stem_wgrad_desc): dy 16-byte aligned; x, x2, dw 4-byte aligned.  Errors of sslcr_stem_wgrad and
+     sslcr_stem_wgrad_pool: a pointer below its alignment. */
 } sslcr_stem_wgrad_desc;
 int sslcr_stem_wgrad(int dtype, const sslcr_stem_wgrad_desc* d, void* stream);
 
@@ -220,6 +237,9 @@ typedef struct sslcr_bn_finalize_desc {
      arithmetic, same bits, one launch less per BatchNorm).  Without that variable the two launches run either way: the one-launch
      form measured slower in the stream (bn_eltwise.hip). */
   int* tickets;
+  /* Alignment (sslcr_bn_finalize_desc): num_batches_tracked, sums_out, sums_in, stage 8-byte aligned; partials, gamma, beta, scale,
+     shift, mean, invstd, running_mean, running_var, tickets 4-byte aligned.  Errors of sslcr_bn_finalize: a pointer below its
+     alignment. */
 } sslcr_bn_finalize_desc;
 int sslcr_bn_finalize(const sslcr_bn_finalize_desc* d, void* stream);
 
@@ -231,6 +251,8 @@ typedef struct sslcr_bn_act_desc {      /* y = relu(x*scale+shift [+ res*rscale+
   uint8_t* ybits;         /* optional (bf16 only): one bit per element of y in NHWC order, bit (e & 7) of byte e / 8 = (y[e] > 0) -- the
                              ReLU mask of a residual block's output as BatchNorm backward wants it (sslcr_bn_bwd_desc.yact_bits):
                              a sixteenth of the bytes of y */
+  /* Alignment (sslcr_bn_act_desc): x, res, y 16-byte aligned; scale, shift, rscale, rshift 4-byte aligned; ybits 1-byte aligned (any
+     address: one byte store per chunk).  Errors of sslcr_bn_act: a pointer below its alignment. */
 } sslcr_bn_act_desc;
 /* Widths: every C % 8 == 0, in both dtypes (16-byte chunks of 8 bf16 / 4 fp32 channels; C / 8 resp. C / 4 chunks per pixel need NOT
  * divide 256).  A thread keeps its chunk's constants across its grid-stride trips: the launch rounds its grid so that the stride is
@@ -240,13 +262,19 @@ int sslcr_bn_act(int dtype, const sslcr_bn_act_desc* d, void* stream);
 typedef struct sslcr_pool_fwd_desc {    /* maxpool3x3/2 pad 1 of relu(bn(x))   (K8); scale = shift = argmax = NULL: plain
                                            max-pool of x as it is (the eval path: BatchNorm folded into conv1, ReLU in its epilogue) */
   const void* x; const float* scale; const float* shift; void* y; uint8_t* argmax; int N, H, W, C, OH, OW;
+  /* Alignment (sslcr_pool_fwd_desc): x, y 16-byte aligned; argmax 8-byte aligned (a chunk's eight codes are one 8-byte store in
+     bf16, four codes one dword in fp32); scale, shift 4-byte aligned.  Errors of sslcr_bn_relu_maxpool: a pointer below its alignment. */
 } sslcr_pool_fwd_desc;
 int sslcr_bn_relu_maxpool(int dtype, const sslcr_pool_fwd_desc* d, void* stream);
 typedef struct sslcr_pool_bwd_desc {
   const void* dy; const uint8_t* argmax; const void* x; const float* scale; const float* shift; void* dx; int N, H, W, C, OH, OW;
+  /* Alignment (sslcr_pool_bwd_desc): dy, x, dx 16-byte aligned; argmax 8-byte aligned; scale, shift 4-byte aligned.  Errors of
+     sslcr_maxpool_relu_bwd: a pointer below its alignment. */
 } sslcr_pool_bwd_desc;
 int sslcr_maxpool_relu_bwd(int dtype, const sslcr_pool_bwd_desc* d, void* stream);
 
+/* Alignment (sslcr_avgpool_fwd): x 16-byte aligned; y 4-byte aligned.  Alignment (sslcr_avgpool_bwd): dy 4-byte aligned; dx 16-byte
+   aligned.  Errors: a pointer below its alignment. */
 int sslcr_avgpool_fwd(int dtype, const void* x, float* y, int N, int HW, int C, void* stream);          /* K9 */
 int sslcr_avgpool_bwd(int dtype, const float* dy, void* dx, int N, int HW, int C, void* stream);
 
@@ -275,6 +303,9 @@ typedef struct sslcr_bn_bwd_desc {
   int nseg, seg_stride, sums_stride;
   const uint8_t* yact_bits;   /* instead of yact (bf16 only): its sign mask as written by sslcr_bn_act (ybits) -- g = dy where the bit is
                                  set, 0 elsewhere: the same g, bit for bit, for 1/16 of yact's bytes */
+  /* Alignment (sslcr_bn_bwd_desc): dy, x, yact, dx, gout, pool_dy, pool_y 16-byte aligned; sums, pool_argmax 8-byte aligned; scale,
+     shift, mean, invstd, dgamma, dbeta 4-byte aligned; yact_bits 1-byte aligned (any address).  Errors of sslcr_bn_bwd_reduce,
+     sslcr_bn_bwd_apply and sslcr_stem_wgrad_pool: a pointer below its alignment. */
 } sslcr_bn_bwd_desc;
 /* ABI note (library version >= 4): sslcr_bn_bwd_reduce OVERWRITES d->sums (until version 3 it accumulated into a buffer the caller had
  * zeroed) -- several reduce calls into one sums buffer keep only the last one; add them on the caller's side.  The reduce pass and the
@@ -287,6 +318,7 @@ typedef struct sslcr_bn_bwd_desc {
  * from sums the caller provides -- like sslcr_bn_act it rounds its grid so that a thread keeps its channels. */
 int sslcr_bn_bwd_reduce(int dtype, const sslcr_bn_bwd_desc* d, void* stream);
 int sslcr_bn_bwd_apply(int dtype, const sslcr_bn_bwd_desc* d, void* stream);
+/* Alignment (sslcr_bn_param_grads): sums 8-byte aligned; invstd, dgamma, dbeta 4-byte aligned.  Errors: a pointer below its alignment. */
 int sslcr_bn_param_grads(const double* sums, const float* invstd, float* dgamma, float* dbeta, int C, void* stream);
 /* conv1 wgrad with bn0's backward apply pass computed on the fly (autograd of resnet18.conv1 <- bn1 <- relu <- maxpool,
  * models/net.py:32,77): `bn` is a pool-form descriptor (pool_dy, pool_argmax, x = the raw conv1 output, pH/pW = w->OH/OW) whose
@@ -299,6 +331,9 @@ const char* sslcr_stem_wgrad_pool_kernel_name(int dtype, const sslcr_stem_wgrad_
 
 /* ---- heads and losses (models/net.py:12-15,35-36,111; F.mse_loss / F.cross_entropy at
  *      eval_BreastPathQ_SSL_CR.py:92-95, eval_Camelyon_SSL_CR.py:110-116, pretrain_BreastPathQ.py:56) */
+/* Alignment (sslcr_linear_fwd): x, w, b, y 4-byte aligned.  Alignment (sslcr_linear_bwd): x, w, dy, yact, dx, dw, db, scratch 4-byte
+   aligned.  (The GEMMs fetch an operand as float4 only where its base is 16-byte aligned and its row stride a multiple of four
+   floats, and one float at a time otherwise: the same sums in another order.)  Errors: a pointer below its alignment. */
 int sslcr_linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int N, int K, int relu, void* stream);
 int sslcr_linear_bwd(const float* x, const float* w, const float* dy, const float* yact, float* dx, float* dw, float* db,
                      int M, int N, int K, int dx_accumulate, float* scratch, void* stream);
@@ -310,6 +345,8 @@ typedef struct sslcr_loss_desc {
   float* out;             /* [4]: loss, loss_x, loss_u, #correct */
   int nx, nu, C; float lambda_u;
   float inv_nx_global, inv_nu_global;
+  /* Alignment (sslcr_loss_desc): target_i 8-byte aligned; logits, logits_t, target_f, dlogits, out 4-byte aligned.  Errors of
+     sslcr_loss and sslcr_loss_ex: a pointer below its alignment. */
 } sslcr_loss_desc;
 int sslcr_loss(const sslcr_loss_desc* d, void* stream);
 /* library version >= 10.  Options of the cross-entropy kinds (1, 2); sslcr_loss and its launch are unchanged.
@@ -343,6 +380,7 @@ typedef struct sslcr_loss_opts {
                                  out2 of sslcr_ce_denominator over the whole global batch (all-reduced when sharded) when this call
                                  holds a micro-batch or a shard of it. */
   float* stats;               /* device [2] or NULL: {#rows with mask_i = 1, sum_i max_c softmax(logits_t_i)_c} of this call */
+  /* Alignment (sslcr_loss_opts): class_weight, denominator, stats 4-byte aligned.  Errors of sslcr_loss_ex: a pointer below its alignment. */
 } sslcr_loss_opts;
 /* opts == NULL: sslcr_loss.  All-default opts (NULL pointers, 0, -100, 0, 0): sslcr_loss's bits for all five kinds -- the MSE kinds
  * by its launch, the cross-entropy kinds by this entry's kernel, whose default arithmetic is the same and which, unlike sslcr_loss
@@ -353,8 +391,10 @@ int sslcr_loss_ex(const sslcr_loss_desc* d, const sslcr_loss_opts* opts, void* s
  *   out2 = { sum_i class_weight[target_i[i]] (1 per row when class_weight is NULL), number of such rows }
  * over the rows with target != ignore_index -- `weight[target[target != ignore_index]].sum()`.  n >= 0.  One launch, no atomics, summed in
  * double in a fixed order: the same bits every run, and the bits sslcr_loss_ex derives for itself over the same rows. */
+/* Alignment (sslcr_ce_denominator): target_i 8-byte aligned; class_weight, out2 4-byte aligned.  Errors: a pointer below its alignment. */
 int sslcr_ce_denominator(const int64_t* target_i, int n, int C, const float* class_weight, int ignore_index, float* out2, void* stream);
 /* out[i] = softmax(logits[i, 0..C-1])[col]: the per-tile 'tumor' probability of test_Camelyon16.py:58-60 (row f3) */
+/* Alignment (sslcr_softmax_col): logits, out 4-byte aligned.  Errors: a pointer below its alignment. */
 int sslcr_softmax_col(const float* logits, float* out, int n, int C, int col, void* stream);
 /* library version >= 12.  What the reference's test() loops take from a batch of logits, in one launch, every output optional (NULL):
  *   scores[i][c]              = softmax(logits[i])[c]                      torch.softmax(output, dim=-1), eval_Kather_SSL_CR.py:211
@@ -393,6 +433,8 @@ typedef struct sslcr_tensor_desc {
   int pack_dtype;         /* 0 fp32, 1 bf16 */
   int dgrad_flip;         /* dgrad pack with the taps reversed (stride-1 3x3 dgrad runs as a plain conv of dY) */
   int group;              /* library version >= 8: the tensor's row of the `groups` table (torch param_groups); 0 with the one-row entries */
+  /* Alignment (sslcr_tensor_desc): p, g, s1, s2, w_fwd, w_dgrad 4-byte aligned (every access is one element).  The table lives in
+     device memory, so no entry point can check these: stated, not enforced. */
 } sslcr_tensor_desc;
 typedef struct sslcr_opt_desc {
   int kind;               /* 0 adam, 1 sgd-nesterov; library version >= 8: 2 adamw (torch.optim.AdamW: p *= 1 - lr * wd first, then the
@@ -402,6 +444,8 @@ typedef struct sslcr_opt_desc {
   int first_step;
   float grad_scale;
 } sslcr_opt_desc;
+/* Alignment (sslcr_optimizer_step): device_descs 8-byte aligned.  Alignment (sslcr_optimizer_step_groups): device_descs 8-byte aligned;
+   coef_dev 4-byte aligned.  Errors: a pointer below its alignment.  (o / groups are HOST pointers.) */
 int sslcr_optimizer_step(const sslcr_tensor_desc* device_descs, int ntensors, int max_n, const sslcr_opt_desc* o, void* stream);
 /* library version >= 8.  The same update with one sslcr_opt_desc row per torch param group (optimizer.param_groups: per-group lr,
  * weight_decay, betas / eps or momentum, and the bias corrections of that group's betas): tensor t takes groups[t.group], every

@@ -30,6 +30,23 @@ using namespace sslcr;
     if (!(cond)) return fail("%s: invalid argument (%s)", __func__, what); \
   } while (0)
 #define DT_OK(dt) NEED((dt) == SSLCR_F32 || (dt) == SSLCR_BF16, "dtype")
+// the alignment include/sslcr.h states for a pointer ("Alignment (...)": the widest access a kernel makes through it); NULL passes
+#define ALIGNED(p, mask) ((reinterpret_cast<uintptr_t>(p) & (mask)) == 0)
+#define NEED_AL(p, n) NEED(ALIGNED(p, (n) - 1), #p " must be " #n "-byte aligned")
+#define CONV_DESC_ALIGNED(d)                                                                                          \
+  NEED_AL(d->x, 16); NEED_AL(d->w, 16); NEED_AL(d->y, 16); NEED_AL(d->residual, 16); NEED_AL(d->mask_x, 16);          \
+  NEED_AL(d->bias, 16); NEED_AL(d->stats, 16); NEED_AL(d->out_scale, 16);                                             \
+  NEED_AL(d->in_scale, 4); NEED_AL(d->in_shift, 4); NEED_AL(d->mask_scale, 4); NEED_AL(d->mask_shift, 4); NEED_AL(d->mask_mean, 4)
+#define STEM_DESC_ALIGNED(d)                                                                                          \
+  NEED_AL(d->w, 16); NEED_AL(d->y, 16);                                                                               \
+  NEED_AL(d->x, 4); NEED_AL(d->x2, 4); NEED_AL(d->bias, 4); NEED_AL(d->stats, 4); NEED_AL(d->out_scale, 4)
+#define STEM_WGRAD_DESC_ALIGNED(d) NEED_AL(d->dy, 16); NEED_AL(d->x, 4); NEED_AL(d->x2, 4); NEED_AL(d->dw, 4)
+#define BN_BWD_DESC_ALIGNED(d)                                                                                        \
+  NEED_AL(d->dy, 16); NEED_AL(d->x, 16); NEED_AL(d->yact, 16); NEED_AL(d->dx, 16); NEED_AL(d->gout, 16);              \
+  NEED_AL(d->pool_dy, 16); NEED_AL(d->pool_y, 16); NEED_AL(d->sums, 8); NEED_AL(d->pool_argmax, 8);                   \
+  NEED_AL(d->scale, 4); NEED_AL(d->shift, 4); NEED_AL(d->mean, 4); NEED_AL(d->invstd, 4); NEED_AL(d->dgamma, 4); NEED_AL(d->dbeta, 4)
+#define LOSS_DESC_ALIGNED(d)                                                                                          \
+  NEED_AL(d->logits, 4); NEED_AL(d->logits_t, 4); NEED_AL(d->target_f, 4); NEED_AL(d->target_i, 8); NEED_AL(d->dlogits, 4); NEED_AL(d->out, 4)
 
 extern "C" {
 
@@ -39,6 +56,7 @@ const char* sslcr_last_error(void) { return g_err; }
 int sslcr_conv2d(int dtype, const sslcr_conv_desc* d, void* stream) {
   DT_OK(dtype);
   NEED(d && d->x && d->w && d->y, "null tensor");
+  CONV_DESC_ALIGNED(d);
   NEED(d->N > 0 && d->C > 0 && d->K > 0 && d->R > 0 && d->S > 0 && d->stride > 0, "shape");
   NEED(d->C % (dtype == SSLCR_BF16 ? 64 : 32) == 0, "C must be a multiple of the 128-byte channel slab");
   NEED(d->K % 64 == 0, "K % 64");
@@ -57,12 +75,16 @@ int sslcr_conv2d_s2_pair_ok(int dtype, const sslcr_conv_desc* c1, const sslcr_co
 int sslcr_conv2d_s2_pair(int dtype, const sslcr_conv_desc* c1, const sslcr_conv_desc* ds, void* stream) {
   DT_OK(dtype);
   NEED(c1 && ds && c1->x && c1->w && c1->y && ds->w && ds->y, "null tensor");
+  CONV_DESC_ALIGNED(c1);
+  CONV_DESC_ALIGNED(ds);
   NEED(conv_s2_pair_ok(dtype, *c1, *ds), "pair not served (sslcr_conv2d_s2_pair_ok)");
   return check(launch_conv_s2(*c1, ds, (hipStream_t)stream), "conv2d_s2_pair");
 }
 
 int sslcr_conv2d_fp8(const sslcr_conv_desc* d, const sslcr_fp8_desc* q, void* stream) {
   NEED(d && q && d->x && d->y && q->w8 && q->w_dequant, "null tensor");
+  CONV_DESC_ALIGNED(d);
+  NEED_AL(q->w8, 16); NEED_AL(q->w_dequant, 16); NEED_AL(q->x_scale_dev, 4); NEED_AL(q->amax_out, 4);
   NEED(q->x_scale > 0.f, "x_scale must be positive");
   NEED(!d->in_scale || d->in_shift, "in_scale without in_shift (the load path reads both)");
   NEED(conv_fp8_mode(*d) != 0, "shape not served by the fp8 kernel (3x3/1, C % 128, K % 128, 16x16-tileable or 8x8 with N % 4)");
@@ -84,6 +106,7 @@ const char* sslcr_conv2d_wgrad_kernel_name(int dtype, const sslcr_wgrad_desc* d)
 int sslcr_conv2d_wgrad(int dtype, const sslcr_wgrad_desc* d, void* stream) {
   DT_OK(dtype);
   NEED(d && d->x && d->dy && d->dw, "null tensor");
+  NEED_AL(d->x, 16); NEED_AL(d->dy, 16); NEED_AL(d->dw, 4); NEED_AL(d->in_scale, 4); NEED_AL(d->in_shift, 4);
   NEED(d->C % 64 == 0 && d->K % 64 == 0, "C,K % 64");
   NEED((d->R == 3 && d->S == 3) || (d->R == 1 && d->S == 1), "3x3 or 1x1");
   return check(launch_wgrad(dtype, *d, (hipStream_t)stream), "conv2d_wgrad");
@@ -97,6 +120,7 @@ int sslcr_probe_tr16(const uint16_t* in, const int* byte_addr, uint16_t* out, vo
 int sslcr_stem_conv(int dtype, const sslcr_stem_desc* d, void* stream) {
   DT_OK(dtype);
   NEED(d && d->x && d->w && d->y, "null tensor");
+  STEM_DESC_ALIGNED(d);
   NEED(d->OH == (d->H + 6 - 7) / 2 + 1 && d->OW == (d->W + 6 - 7) / 2 + 1, "7x7/2 pad 3 output dims");
   NEED(!d->x2 || (d->n_split >= 0 && d->n_split <= d->N), "n_split outside the batch");
   return check(launch_stem(dtype, *d, (hipStream_t)stream), "stem_conv");
@@ -104,6 +128,7 @@ int sslcr_stem_conv(int dtype, const sslcr_stem_desc* d, void* stream) {
 int sslcr_stem_conv_pool(int dtype, const sslcr_stem_desc* d, int POH, int POW, void* stream) {
   DT_OK(dtype);
   NEED(d && d->x && d->w && d->y, "null");
+  STEM_DESC_ALIGNED(d);
   NEED(stem_pool_ok(dtype, *d, POH, POW), "shape / mode not served by the fused stem + max-pool kernel");
   return check(launch_stem_pool(dtype, *d, POH, POW, (hipStream_t)stream), "stem_conv_pool");
 }
@@ -111,6 +136,7 @@ int sslcr_stem_partial_rows(const sslcr_stem_desc* d) { return d ? stem_partials
 int sslcr_stem_wgrad(int dtype, const sslcr_stem_wgrad_desc* d, void* stream) {
   DT_OK(dtype);
   NEED(d && d->x && d->dy && d->dw, "null tensor");
+  STEM_WGRAD_DESC_ALIGNED(d);
   NEED(!d->x2 || (d->n_split >= 0 && d->n_split <= d->N), "n_split outside the batch");
   return check(launch_stem_wgrad(dtype, *d, (hipStream_t)stream), "stem_wgrad");
 }
@@ -118,6 +144,8 @@ const char* sslcr_stem_wgrad_pool_kernel_name(int dtype, const sslcr_stem_wgrad_
 int sslcr_stem_wgrad_pool(int dtype, const sslcr_stem_wgrad_desc* w, const sslcr_bn_bwd_desc* bn, void* stream) {
   DT_OK(dtype);
   NEED(w && w->x && w->dw && bn && bn->pool_dy && bn->pool_argmax && bn->x && bn->sums && bn->mean && bn->invstd && bn->scale && bn->shift, "null tensor");
+  STEM_WGRAD_DESC_ALIGNED(w);
+  BN_BWD_DESC_ALIGNED(bn);
   NEED(!w->x2 || (w->n_split >= 0 && w->n_split <= w->N), "n_split outside the batch");
   NEED(bn->C == 64 && bn->pH == w->OH && bn->pW == w->OW && bn->pixels == (size_t)w->N * w->OH * w->OW, "bn descriptor is not this stem's");
   NEED(!bn->g_in_reduce && !bn->gout, "pool form has no g output");
@@ -126,6 +154,9 @@ int sslcr_stem_wgrad_pool(int dtype, const sslcr_stem_wgrad_desc* w, const sslcr
 
 int sslcr_bn_finalize(const sslcr_bn_finalize_desc* d, void* stream) {
   NEED(d && d->C > 0, "desc");
+  NEED_AL(d->partials, 4); NEED_AL(d->gamma, 4); NEED_AL(d->beta, 4); NEED_AL(d->scale, 4); NEED_AL(d->shift, 4); NEED_AL(d->mean, 4);
+  NEED_AL(d->invstd, 4); NEED_AL(d->running_mean, 4); NEED_AL(d->running_var, 4); NEED_AL(d->tickets, 4);
+  NEED_AL(d->num_batches_tracked, 8); NEED_AL(d->sums_out, 8); NEED_AL(d->sums_in, 8); NEED_AL(d->stage, 8);
   NEED(d->sums_in || (d->partials && d->stage && d->rows > 0), "partials/stage");
   NEED(d->sums_out || (d->gamma && d->beta && d->scale && d->shift && d->count > 0), "finalize outputs");
   return check(launch_bn_finalize(*d, (hipStream_t)stream), "bn_finalize");
@@ -133,12 +164,15 @@ int sslcr_bn_finalize(const sslcr_bn_finalize_desc* d, void* stream) {
 int sslcr_bn_act(int dtype, const sslcr_bn_act_desc* d, void* stream) {
   DT_OK(dtype);
   NEED(d && d->x && d->y && d->scale && d->shift, "null");
+  NEED_AL(d->x, 16); NEED_AL(d->res, 16); NEED_AL(d->y, 16);
+  NEED_AL(d->scale, 4); NEED_AL(d->shift, 4); NEED_AL(d->rscale, 4); NEED_AL(d->rshift, 4);      // (ybits: bytes, any address)
   NEED(d->C % 8 == 0, "C % 8");
   return check(launch_bn_act(dtype, *d, (hipStream_t)stream), "bn_act");
 }
 int sslcr_bn_relu_maxpool(int dtype, const sslcr_pool_fwd_desc* d, void* stream) {
   DT_OK(dtype);
   NEED(d && d->x && d->y, "null");
+  NEED_AL(d->x, 16); NEED_AL(d->y, 16); NEED_AL(d->argmax, 8); NEED_AL(d->scale, 4); NEED_AL(d->shift, 4);
   if (!d->scale || !d->shift) {
     const int cols = d->C / (dtype == SSLCR_BF16 ? 8 : 4);
     NEED(!d->scale && !d->shift && !d->argmax, "plain max-pool (scale = shift = NULL) records no argmax");
@@ -149,52 +183,63 @@ int sslcr_bn_relu_maxpool(int dtype, const sslcr_pool_fwd_desc* d, void* stream)
 int sslcr_maxpool_relu_bwd(int dtype, const sslcr_pool_bwd_desc* d, void* stream) {
   DT_OK(dtype);
   NEED(d && d->x && d->dy && d->dx && d->argmax, "null");
+  NEED_AL(d->dy, 16); NEED_AL(d->x, 16); NEED_AL(d->dx, 16); NEED_AL(d->argmax, 8); NEED_AL(d->scale, 4); NEED_AL(d->shift, 4);
   return check(launch_maxpool_relu_bwd(dtype, *d, (hipStream_t)stream), "maxpool_relu_bwd");
 }
 int sslcr_avgpool_fwd(int dtype, const void* x, float* y, int N, int HW, int C, void* stream) {
   DT_OK(dtype);
   NEED(x && y && N > 0 && HW > 0 && C % 8 == 0, "args");
+  NEED_AL(x, 16); NEED_AL(y, 4);
   return check(launch_avgpool_fwd(dtype, x, y, N, HW, C, (hipStream_t)stream), "avgpool_fwd");
 }
 int sslcr_avgpool_bwd(int dtype, const float* dy, void* dx, int N, int HW, int C, void* stream) {
   DT_OK(dtype);
   NEED(dy && dx && N > 0 && HW > 0 && C % 8 == 0, "args");
+  NEED_AL(dy, 4); NEED_AL(dx, 16);
   return check(launch_avgpool_bwd(dtype, dy, dx, N, HW, C, (hipStream_t)stream), "avgpool_bwd");
 }
 int sslcr_bn_bwd_reduce(int dtype, const sslcr_bn_bwd_desc* d, void* stream) {
   DT_OK(dtype);
   NEED(d && (d->dy || (d->pool_dy && d->pool_argmax)) && d->x && d->sums && d->mean, "null");
+  BN_BWD_DESC_ALIGNED(d);
   NEED(!d->g_in_reduce || (d->yact && d->gout && d->dy && !d->pool_dy), "g_in_reduce needs dy, yact and gout");
   return check(launch_bn_bwd_reduce(dtype, *d, (hipStream_t)stream), "bn_bwd_reduce");
 }
 int sslcr_bn_bwd_apply(int dtype, const sslcr_bn_bwd_desc* d, void* stream) {
   DT_OK(dtype);
   NEED(d && (d->dy || (d->pool_dy && d->pool_argmax)) && d->x && d->sums && d->dx && d->mean && d->invstd && d->scale, "null");
+  BN_BWD_DESC_ALIGNED(d);
   NEED(!d->g_in_reduce || (d->yact && d->gout && d->dy && !d->pool_dy), "g_in_reduce needs dy, yact and gout");
   return check(launch_bn_bwd_apply(dtype, *d, (hipStream_t)stream), "bn_bwd_apply");
 }
 int sslcr_bn_param_grads(const double* sums, const float* invstd, float* dgamma, float* dbeta, int C, void* stream) {
   NEED(sums && invstd && dgamma && dbeta, "null");
+  NEED_AL(sums, 8); NEED_AL(invstd, 4); NEED_AL(dgamma, 4); NEED_AL(dbeta, 4);
   return check(launch_bn_param_grads(sums, invstd, dgamma, dbeta, C, (hipStream_t)stream), "bn_param_grads");
 }
 
 int sslcr_linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int N, int K, int relu, void* stream) {
   NEED(x && w && y && M > 0 && N > 0 && K > 0, "args");
+  NEED_AL(x, 4); NEED_AL(w, 4); NEED_AL(b, 4); NEED_AL(y, 4);
   return check(launch_linear_fwd(x, w, b, y, M, N, K, relu, (hipStream_t)stream), "linear_fwd");
 }
 int sslcr_linear_bwd(const float* x, const float* w, const float* dy, const float* yact, float* dx, float* dw, float* db,
                      int M, int N, int K, int dx_accumulate, float* scratch, void* stream) {
   NEED(x && w && dy && scratch && M > 0 && N > 0 && K > 0, "args");
+  NEED_AL(x, 4); NEED_AL(w, 4); NEED_AL(dy, 4); NEED_AL(yact, 4); NEED_AL(dx, 4); NEED_AL(dw, 4); NEED_AL(db, 4); NEED_AL(scratch, 4);
   return check(launch_linear_bwd(x, w, dy, yact, dx, dw, db, M, N, K, dx_accumulate, scratch, (hipStream_t)stream), "linear_bwd");
 }
 int sslcr_loss(const sslcr_loss_desc* d, void* stream) {
   NEED(d && d->logits && d->out && d->nx > 0 && d->C > 0 && d->C <= 64, "args");
+  LOSS_DESC_ALIGNED(d);
   return check(launch_loss(*d, (hipStream_t)stream), "loss");
 }
 
 int sslcr_loss_ex(const sslcr_loss_desc* d, const sslcr_loss_opts* o, void* stream) {
   if (!o) return sslcr_loss(d, stream);
   NEED(d && d->logits && d->out && d->nx > 0 && d->C > 0 && d->C <= 64, "args");
+  LOSS_DESC_ALIGNED(d);
+  NEED_AL(o->class_weight, 4); NEED_AL(o->denominator, 4); NEED_AL(o->stats, 4);
   const char* why = loss_opts_error(d->kind, d->C, *o);
   if (why) return fail("sslcr_loss_ex: invalid argument (%s)", why);
   // the MSE kinds have no options: sslcr_loss's own launch.  The cross-entropy kinds take the new kernel whenever opts is given --
@@ -206,11 +251,13 @@ int sslcr_loss_ex(const sslcr_loss_desc* d, const sslcr_loss_opts* o, void* stre
 }
 int sslcr_ce_denominator(const int64_t* target_i, int n, int C, const float* class_weight, int ignore_index, float* out2, void* stream) {
   NEED(out2 && (target_i || n == 0) && n >= 0 && C > 0 && C <= 64, "args");
+  NEED_AL(target_i, 8); NEED_AL(class_weight, 4); NEED_AL(out2, 4);
   return check(launch_ce_denominator(target_i, n, C, class_weight, ignore_index, out2, (hipStream_t)stream), "ce_denominator");
 }
 
 int sslcr_softmax_col(const float* logits, float* out, int n, int C, int col, void* stream) {
   NEED(logits && out && n > 0 && C > 0 && C <= 64 && col >= 0 && col < C, "args");
+  NEED_AL(logits, 4); NEED_AL(out, 4);
   return check(launch_softmax_col(logits, out, n, C, col, (hipStream_t)stream), "softmax_col");
 }
 
@@ -350,7 +397,6 @@ int sslcr_map_confusion(const sslcr_map_confusion_desc* d, void* stream) {
 }
 // ---- Camelyon16 lesion scoring (froc.hip)
 #define MAP_SHAPE_OK(d) NEED((d)->X >= 1 && (d)->Y >= 1 && (int64_t)(d)->X * (d)->Y < (int64_t)1 << 31, "map shape")
-#define ALIGNED(p, mask) ((reinterpret_cast<uintptr_t>(p) & (mask)) == 0)
 int sslcr_label_components(const sslcr_label_desc* d, void* stream) {
   NEED(d, "null descriptor");
   MAP_SHAPE_OK(d);
@@ -732,7 +778,6 @@ int sslcr_tsne_kl(const double* kl_rows, const float* grad, const double* Z, dou
 }
 #undef SQ_SHAPE_OK
 #undef MAP_SHAPE_OK
-#undef ALIGNED
 int sslcr_d4_transform(const sslcr_d4_desc* d, void* stream) {
   NEED(d, "null descriptor");
   NEED(d->N >= 0 && d->Cn >= 1 && d->H >= 1, "N >= 0, Cn >= 1 and H >= 1");
@@ -754,6 +799,7 @@ int sslcr_optimizer_step(const sslcr_tensor_desc* device_descs, int ntensors, in
 int sslcr_optimizer_step_groups(const sslcr_tensor_desc* device_descs, int ntensors, int max_n, const sslcr_opt_desc* groups, int ngroups,
                                 const float* coef_dev, void* stream) {
   NEED(device_descs && groups && ntensors > 0 && max_n > 0, "args");
+  NEED_AL(device_descs, 8); NEED_AL(coef_dev, 4);      // (the tensors the table names live behind a device pointer: stated, not checked)
   NEED(ngroups >= 1 && ngroups <= SSLCR_MAX_OPT_GROUPS, "ngroups must be 1..8");
   OptTable tab = opt_table_noop();
   for (int i = 0; i < ngroups; ++i) {

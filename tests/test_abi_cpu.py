@@ -50,6 +50,65 @@ def test_argument_validation_without_gpu(lib):
     assert lib.sslcr_conv2d(7, d, None) == -1
     assert b"dtype" in lib.sslcr_last_error()
     assert lib.sslcr_net_forward(None, 0, None, None, None, 0, 1, 64, 64, None, None, None) == -1
+    # the alignment include/sslcr.h states for the pointers of the training entry points ("Alignment (owner): ..."): one pointer per
+    # entry point at an aligned fake address plus half its alignment -> -1 and the pointer's name, decided from the value alone.
+    # (Every descriptor here would also fail a later check, or is complete only in the pointer under test: nothing can launch.)
+    import ctypes as C
+    F = 0x7F0000010000
+
+    def D(cls, **kw):
+        d = cls()
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+    conv = dict(x=F, w=F, y=F)
+    bn_bwd = dict(dy=F, x=F, sums=F, mean=F, dx=F, invstd=F, scale=F, shift=F)
+    rows = [
+        ("d->bias", 16, lambda p: lib.sslcr_conv2d(1, D(L.ConvDesc, bias=p, **conv), None)),
+        ("d->x", 16, lambda p: lib.sslcr_conv2d(0, D(L.ConvDesc, **dict(conv, x=p)), None)),
+        ("d->in_scale", 4, lambda p: lib.sslcr_conv2d(1, D(L.ConvDesc, in_scale=p, **conv), None)),
+        ("ds->y", 16, lambda p: lib.sslcr_conv2d_s2_pair(1, D(L.ConvDesc, **conv), D(L.ConvDesc, **dict(conv, y=p)), None)),
+        ("c1->stats", 16, lambda p: lib.sslcr_conv2d_s2_pair(1, D(L.ConvDesc, stats=p, **conv), D(L.ConvDesc, **conv), None)),
+        ("q->w_dequant", 16, lambda p: lib.sslcr_conv2d_fp8(D(L.ConvDesc, **conv), D(L.Fp8Desc, w8=F, w_dequant=p), None)),
+        ("q->amax_out", 4, lambda p: lib.sslcr_conv2d_fp8(D(L.ConvDesc, **conv), D(L.Fp8Desc, w8=F, w_dequant=F, amax_out=p), None)),
+        ("d->dy", 16, lambda p: lib.sslcr_conv2d_wgrad(1, D(L.WgradDesc, x=F, dy=p, dw=F), None)),
+        ("d->dw", 4, lambda p: lib.sslcr_conv2d_wgrad(0, D(L.WgradDesc, x=F, dy=F, dw=p), None)),
+        ("d->x", 4, lambda p: lib.sslcr_stem_conv(1, D(L.StemDesc, x=p, w=F, y=F), None)),
+        ("d->w", 16, lambda p: lib.sslcr_stem_conv_pool(1, D(L.StemDesc, x=F, w=p, y=F), 0, 0, None)),
+        ("d->dy", 16, lambda p: lib.sslcr_stem_wgrad(1, D(L.StemWgradDesc, x=F, dy=p, dw=F, x2=F, n_split=-1), None)),
+        ("bn->pool_argmax", 8, lambda p: lib.sslcr_stem_wgrad_pool(1, D(L.StemWgradDesc, x=F, dw=F),
+                                                                   D(L.BnBwdDesc, pool_dy=F, pool_argmax=p, **bn_bwd), None)),
+        ("d->stage", 8, lambda p: lib.sslcr_bn_finalize(D(L.BnFinalizeDesc, C=1, partials=F, stage=p), None)),
+        ("d->gamma", 4, lambda p: lib.sslcr_bn_finalize(D(L.BnFinalizeDesc, C=1, partials=F, stage=F, gamma=p), None)),
+        ("d->res", 16, lambda p: lib.sslcr_bn_act(1, D(L.BnActDesc, x=F, y=F, scale=F, shift=F, res=p, C=4), None)),
+        ("d->x", 16, lambda p: lib.sslcr_bn_relu_maxpool(0, D(L.PoolFwdDesc, x=p, y=F), None)),
+        ("d->argmax", 8, lambda p: lib.sslcr_maxpool_relu_bwd(1, D(L.PoolBwdDesc, x=F, dy=F, dx=F, argmax=p), None)),
+        ("x", 16, lambda p: lib.sslcr_avgpool_fwd(1, p, F, 1, 1, 8, None)),
+        ("dy", 4, lambda p: lib.sslcr_avgpool_bwd(1, p, F, 1, 1, 8, None)),
+        ("d->sums", 8, lambda p: lib.sslcr_bn_bwd_reduce(1, D(L.BnBwdDesc, g_in_reduce=1, **dict(bn_bwd, sums=p)), None)),
+        ("d->gout", 16, lambda p: lib.sslcr_bn_bwd_apply(0, D(L.BnBwdDesc, g_in_reduce=1, gout=p, **bn_bwd), None)),
+        ("sums", 8, lambda p: lib.sslcr_bn_param_grads(p, F, F, F, 8, None)),
+        ("b", 4, lambda p: lib.sslcr_linear_fwd(F, F, p, F, 1, 1, 1, 0, None)),
+        ("scratch", 4, lambda p: lib.sslcr_linear_bwd(F, F, F, None, None, None, None, 1, 1, 1, 0, p, None)),
+        ("d->target_i", 8, lambda p: lib.sslcr_loss(D(L.LossDesc, logits=F, out=F, nx=1, C=2, target_i=p), None)),
+        ("o->class_weight", 4, lambda p: lib.sslcr_loss_ex(D(L.LossDesc, logits=F, out=F, nx=1, C=2), D(L.LossOpts, class_weight=p, label_smoothing=2.0), None)),
+        ("target_i", 8, lambda p: lib.sslcr_ce_denominator(p, 1, 2, None, -100, F, None)),
+        ("out", 4, lambda p: lib.sslcr_softmax_col(F, p, 1, 2, 0, None)),
+        ("device_descs", 8, lambda p: lib.sslcr_optimizer_step(p, 1, 1, D(L.OptDesc, kind=9), None)),
+        ("coef_dev", 4, lambda p: lib.sslcr_optimizer_step_groups(F, 1, 1, D(L.OptDesc, kind=9), 1, p, None)),
+    ]
+    from ssl_cr_histo_amd import engine  # noqa: F401
+    for name, align, call in rows:
+        assert call(C.c_void_p(F + align // 2) if "->" not in name else F + align // 2) == -1, name
+        msg = lib.sslcr_last_error().decode()
+        assert f"({name} must be {align}-byte aligned)" in msg, (name, msg)
+    # every entry point the alignment table of tests/_arena.py covers has a row above (its message names the entry point: __func__)
+    import _arena
+    hit = set()
+    for name, align, call in rows:
+        call(C.c_void_p(F + align // 2) if "->" not in name else F + align // 2)
+        hit.add(lib.sslcr_last_error().decode().split(":")[0])
+    assert hit | {"sslcr_optimizer_step"} >= set(_arena.ENTRY_ALIGN), sorted(set(_arena.ENTRY_ALIGN) - hit)
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU behaviour")
