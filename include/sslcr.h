@@ -34,7 +34,7 @@ extern "C" {
 #define SSLCR_BF16 1
 #define SSLCR_FP8 2   /* engine mode only (sslcr_create): bf16 storage and backward, fp8 e4m3 forward for the eligible 3x3 convs */
 
-/* the library round (15 here). ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
+/* the library round (16 here). ABI notes below name the version a behaviour changed in: 4 = sslcr_bn_bwd_reduce overwrites its sums;
  * 7 = sslcr_randaug_v2_slot added (nothing else changed); 8 = optimizer parameter groups, AdamW and the global gradient norm
  * (sslcr_tensor_desc.group, sslcr_opt_desc.kind 2, sslcr_optimizer_step_groups, sslcr_grad_norm, sslcr_net_optimizer_step_groups,
  * sslcr_net_grad_norm: all additive); 9 = gradient accumulation (sslcr_grad_accumulate, sslcr_net_set_grad_accumulate: additive,
@@ -47,16 +47,72 @@ extern "C" {
  * added (additive; no existing entry, descriptor or launch changes); 15 = Camelyon16 annotations: sslcr_points_in_polygons and
  * sslcr_map_confusion added (additive; no existing entry, descriptor or launch changes).  Lesion scoring (sslcr_label_components,
  * sslcr_gaussian_smooth, sslcr_nms_candidates / _rounds / _collect, sslcr_lesion_hits) is additive in the same way and came WITHOUT
- * a new number: tests/test_annotation_cpu.py holds sslcr_version() to 15 by equality, so a caller tests for these entries by symbol.
+ * a new number (the tests of that time held sslcr_version() to 15 by equality), so a caller tests for these entries by symbol.
  * The same holds for sslcr_conv2d_fp8_kernel_name and sslcr_fp8_scale_update (additive; the launches they name or issue are the
  * ones sslcr_conv2d_fp8 and the engine's forward issued before); sslcr_conv2d_fp8 now refuses in_scale without in_shift, a
  * descriptor whose launch read a NULL pointer on the device.  The ranking entries (sslcr_sort_pairs, sslcr_sort_workspace_bytes,
  * sslcr_rank_keys, sslcr_auc_counts, sslcr_auc_workspace_bytes) are additive in the same way, again without a new number, and so
  * are the resize entries (sslcr_resample, sslcr_resample_plan, sslcr_resample_coeffs, sslcr_resample_ksize,
  * sslcr_resample_table_ok), the k-NN probe's (sslcr_knn_plan, sslcr_knn_topk, sslcr_knn_vote, sslcr_l2_normalize) and the t-SNE
- * embedding's (sslcr_tsne_plan, sslcr_tsne_pair_dist2, sslcr_tsne_affinities, sslcr_tsne_repulsion, sslcr_tsne_update, sslcr_tsne_kl). */
+ * embedding's (sslcr_tsne_plan, sslcr_tsne_pair_dist2, sslcr_tsne_affinities, sslcr_tsne_repulsion, sslcr_tsne_update, sslcr_tsne_kl).
+ * 16 = the switch listing: sslcr_switch_count and sslcr_switch_info added (additive; every switch keeps its default and its reading of
+ * every string, no launch changes). */
 int sslcr_version(void);
 const char* sslcr_last_error(void);
+
+/* ---- environment switches (library version >= 16).  The library reads the SSLCR_* variables below and no others; they exist for
+ * same-box A/B measurements and for tests, and every default is the measured better form.  One row each:
+ *
+ *   name                    rule     when     group        default
+ *   SSLCR_PP64              ATOI     process  routing      1
+ *   SSLCR_H16_TW8           ATOI     process  routing      1
+ *   SSLCR_H16_RAW           ATOI     process  routing      1
+ *   SSLCR_S2                ATOI     process  routing      1
+ *   SSLCR_S2D               ATOI     process  routing      1
+ *   SSLCR_S2W               ATOI     process  routing      1
+ *   SSLCR_WG_DMA            ATOI     process  routing      1
+ *   SSLCR_WGRAD_WIDE        LEAD0    process  routing      1
+ *   SSLCR_GEMM_LDS          ATOI     process  form         1
+ *   SSLCR_STEM_POOL_FORM    INT      process  form         2
+ *   SSLCR_POOL_BANDS        ATOI     process  form         0
+ *   SSLCR_WG_STAGGER        INT      process  form         1
+ *   SSLCR_SEGMENTS          LEAD0    process  engine       1
+ *   SSLCR_BN_PAIR           ATOI     process  engine       1
+ *   SSLCR_BN_PAIR_G         ATOI     process  engine       1
+ *   SSLCR_YBITS             ATOI     process  engine       1
+ *   SSLCR_UNFOLD_EVAL       ATOI     process  engine       1
+ *   SSLCR_STEM_POOL         ATOI     process  engine       1
+ *   SSLCR_BN_ONE_LAUNCH     ATOI     process  engine       0
+ *   SSLCR_FUSE_STEM_BWD     ATOI     call     engine       1
+ *   SSLCR_COMM_SELFTEST     PRESENT  call     engine       0
+ *   SSLCR_BN_REPEAT         INT      process  measurement  1
+ *   SSLCR_EW_CAP            INT      process  measurement  0
+ *
+ * rule, for a variable that is set (unset is the default under every rule):
+ *   ATOI     on where atoi(value) != 0: "", "off" and " 0" turn the switch OFF; "01", "2" and "-1" leave it on
+ *   LEAD0    off only where the first character is '0': "", "off" and " 0" leave the switch ON; "00" and "01" turn it off
+ *   INT      atoi(value); SSLCR_BN_REPEAT below 1 becomes 1; SSLCR_EW_CAP is read with strtol and held to [256, 65535], and its
+ *            default 0 stands for "not set": three workgroups per compute unit, which needs the device
+ *   PRESENT  on where the variable is set at all, the empty string included
+ * when: `process` rows are read once per process, thread-safely, at the first query of any switch (the first entry point that
+ *   routes, launches or lists) -- a later putenv is not seen; `call` rows are read at every call of the entry point their meaning
+ *   names (sslcr_create, sslcr_comm_init).
+ * group: routing = changes which kernel instance the router answers (sslcr_conv2d_kernel_name, sslcr_conv2d_wgrad_kernel_name);
+ *   form = another form of a kernel under the same routed name; engine = a decision of the step path; measurement = NOT for a run
+ *   whose results are kept (SSLCR_BN_REPEAT=n updates the running statistics n times).
+ * sslcr_switch_info gives each row's one-line meaning and what this process read; it needs no device. */
+typedef struct sslcr_switch_row {
+  const char* name;       /* with its prefix, "SSLCR_PP64"; all five strings are static */
+  const char* group;      /* "routing" | "form" | "engine" | "measurement" */
+  const char* rule;       /* "ATOI" | "LEAD0" | "INT" | "PRESENT" */
+  const char* when;       /* "process" | "call" */
+  const char* meaning;
+  long long dflt;         /* the value in use where the variable is not set (0 / 1 for the on / off rules) */
+  long long value;        /* the value in use: dflt where is_set == 0 */
+  int is_set;
+} sslcr_switch_row;
+int sslcr_switch_count(void);
+int sslcr_switch_info(int i, sslcr_switch_row* out);      /* 0 <= i < sslcr_switch_count(); -1 otherwise */
 
 /* ---- conv2d forward / dgrad (replaces nn.Conv2d inside torchvision resnet18: models/net.py:32,77;
  *      BasicBlock convs K2-K4 of SURVEY 2b, and their autograd dgrad K13) */

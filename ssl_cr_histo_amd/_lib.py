@@ -29,6 +29,8 @@ def _S(cname, pyname, fields):
     return MIRRORS[cname]
 
 
+SwitchRow = _S("sslcr_switch_row", "SwitchRow", [(k, C.c_char_p) for k in ("name", "group", "rule", "when", "meaning")] +
+               [("dflt", C.c_longlong), ("value", C.c_longlong), ("is_set", i32)])
 ConvDesc = _S("sslcr_conv_desc", "ConvDesc", [("x", vp), ("w", vp), ("y", vp), ("in_scale", vp), ("in_shift", vp), ("bias", vp),
                            ("residual", vp), ("stats", vp)] +
               [(k, i32) for k in ("N", "H", "W", "C", "K", "R", "S", "stride", "pad", "PH", "PW", "OH", "OW", "osh",
@@ -168,6 +170,8 @@ P = C.POINTER
 SIGNATURES = {
     "sslcr_version": (i32, []),
     "sslcr_last_error": (C.c_char_p, []),
+    "sslcr_switch_count": (i32, []),
+    "sslcr_switch_info": (i32, [i32, P(SwitchRow)]),
     "sslcr_conv2d": (i32, [i32, P(ConvDesc), vp]),
     "sslcr_conv2d_partial_rows": (i32, [P(ConvDesc)]),
     "sslcr_conv2d_segments_ok": (i32, [i32, P(ConvDesc)]),

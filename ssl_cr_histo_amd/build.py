@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsslcr.so")
 SOURCES = ["conv_igemm.hip", "conv_halo.hip", "conv_halo256.hip", "conv_h16.hip", "conv_pp64.hip", "conv_dma.hip", "conv_s2.hip", "conv_s2d.hip", "conv_fp8.hip", "conv_wgrad.hip", "wgrad_halo.hip", "wgrad_dma.hip", "wgrad_s2.hip", "stem.hip", "stem_pool.hip", "augment.hip", "augment_v2.hip", "wsi.hip", "tta.hip", "mining.hip", "annotation.hip", "froc.hip", "evalmask.hip", "rank.hip", "knn.hip", "tsne.hip", "resample.hip", "bn_eltwise.hip", "heads.hip", "optim.hip",
-           "conv_route.cpp", "launch.cpp", "engine.cpp", "capi.cpp"]
+           "conv_route.cpp", "launch.cpp", "switches.cpp", "engine.cpp", "capi.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-fvisibility=hidden"]
 # No SLP vectoriser where a wave's VALU work runs BESIDE its SIMD partner's MFMA stream (the ping-pong conv, the role-split stem
 # backward): the vectoriser turns pairs of fp32 operations into v_pk_add_f32 / v_pk_fma_f32, and next to a full-rate MFMA stream a

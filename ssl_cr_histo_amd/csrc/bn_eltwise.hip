@@ -156,7 +156,7 @@ static hipError_t launch_bn_finalize_once(const BnFinalizeArgs& a, hipStream_t s
 hipError_t launch_bn_finalize(const BnFinalizeArgs& a, hipStream_t st) {
   // SSLCR_BN_REPEAT=n (measurement only: the running statistics take n updates): the launch(es) n times back to back -- the step
   // time difference / ((n - 1) x launches) is what one BatchNorm finalize costs IN the stream, without a profiler's per-kernel overhead
-  static const int rep = [] { const char* e = getenv("SSLCR_BN_REPEAT"); const int v = e ? atoi(e) : 1; return v < 1 ? 1 : v; }();
+  const int rep = (int)sw::value(sw::BN_REPEAT);
   hipError_t e = hipSuccess;
   for (int i = 0; i < rep && e == hipSuccess; ++i) e = launch_bn_finalize_once(a, st);
   return e;
@@ -174,8 +174,7 @@ static hipError_t launch_bn_finalize_once(const BnFinalizeArgs& a, hipStream_t s
     if (splits < 1) splits = 1;
     // OFF by default (round 6, profiles/r06_bn_one_launch_ab.txt): in the stream a finalize pair costs 4.35 us (two launches) and the
     // ticketed launch 5.9 us -- the write-through publish, the returned atomic and the sc1 reads are dearer than a launch boundary
-    static const bool one = [] { const char* e = getenv("SSLCR_BN_ONE_LAUNCH"); return e && atoi(e) != 0; }();
-    if (a.tickets && one) {
+    if (a.tickets && sw::on(sw::BN_ONE_LAUNCH)) {
       hipLaunchKernelGGL(bn_reduce_finalize_kernel, dim3(cdiv(a.C, 32), splits, nseg), dim3(256), 0, st, a.partials, rows, stage, splits, a);
       return hipGetLastError();
     }
@@ -238,16 +237,10 @@ static inline int ew_grid(size_t work_items) {
   // 512 15.86, 640 15.82, 768 15.73-15.80, 896 15.87, 1024 +0.03 over 768, 1536 / 2048 (the cap of rounds 2-4) / 3072 15.86-15.87,
   // 40960 and up +2 ms (the per-workgroup constants).  tools/microbench/hbm_bench.hip agrees for a 2-read-1-write stream: 1024
   // workgroups 6.16 TB/s, 2048 5.8, 4096 5.5 -- and more only again with one vector per thread and no prologue at all
-  // (81920 workgroups: 6.6 TB/s).  Initialised once, thread-safely (virtual ranks launch from several host threads);
-  // SSLCR_EW_CAP is read as a signed value and clamped to [256, 65535]
-  static const size_t cap = [] {
-    const char* e = getenv("SSLCR_EW_CAP");
-    const long dflt = 3L * device_cus();
-    long v = e ? strtol(e, nullptr, 10) : dflt;
-    if (v < 256) v = e ? 256 : dflt;
-    if (v > 65535) v = 65535;
-    return (size_t)v;
-  }();
+  // (81920 workgroups: 6.6 TB/s).  The default stands here, not in the switch table, because it needs the device; a set SSLCR_EW_CAP
+  // arrives held to [256, 65535]
+  const long dflt = 3L * device_cus();
+  const size_t cap = (size_t)(sw::is_set(sw::EW_CAP) ? sw::value(sw::EW_CAP) : dflt > 65535 ? 65535 : dflt);
   size_t b = (work_items + 255) / 256;
   return (int)(b < 1 ? 1 : (b > cap ? cap : b));
 }
@@ -458,7 +451,7 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_rows_kernel(const PoolFwd
 hipError_t launch_bn_relu_maxpool(int dtype, const PoolFwdArgs& a, hipStream_t st) {
   // OFF: measured +0.07 ms per step on one box (15.39 -> 15.46 ms, three alternations) -- the input row two output rows share comes from
   // L2 / the Infinity Cache either way, and interleaved rows keep more channels busy
-  static const int bands = [] { const char* e = getenv("SSLCR_POOL_BANDS"); return (e && atoi(e) != 0) ? 1 : 0; }();
+  const int bands = sw::on(sw::POOL_BANDS) ? 1 : 0;
   size_t px = (size_t)a.N * a.OH * a.OW;
   const int cols = a.C / (dtype == DT_BF16 ? 8 : 4);
   if (!a.scale || !a.shift) {          // plain max-pool (capi.cpp admits it only without argmax and for the row form's widths)
@@ -1040,8 +1033,7 @@ hipError_t launch_bn_bwd_reduce(int dtype, const BnBwdArgs& a, hipStream_t st) {
 // the two-BatchNorm forms (bn_bwd_reduce_pair_kernel): a = the residual branch's bn2 (g_in_reduce: its reduce pass writes g to gout),
 // b = the projection shortcut's BatchNorm on the same g.  b.sums must be a.sums + 2 C (one fold launch, one all-reduce for both).
 bool bn_bwd_pair_ok(const BnBwdArgs& a, const BnBwdArgs& b) {
-  static const bool on = [] { const char* e = getenv("SSLCR_BN_PAIR"); return !e || atoi(e) != 0; }();     // 0: two passes each (A/B runs)
-  return on && a.g_in_reduce && a.gout && b.dy == a.gout && !b.yact && !b.yact_bits && !b.relu_from_x && !b.gout && !a.pool_dy && !b.pool_dy &&
+  return sw::on(sw::BN_PAIR) && a.g_in_reduce && a.gout && b.dy == a.gout && !b.yact && !b.yact_bits && !b.relu_from_x && !b.gout && !a.pool_dy && !b.pool_dy &&
          a.nseg <= 1 && b.nseg <= 1 && a.C == b.C && a.pixels == b.pixels && b.sums == a.sums + 2 * a.C && a.dx && b.dx && b.x && a.x;
 }
 template <int NB>

@@ -50,8 +50,18 @@ using namespace sslcr;
 
 extern "C" {
 
-int sslcr_version(void) { return 15; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
+int sslcr_version(void) { return 16; }      // = the build round; the ABI notes in include/sslcr.h name the version a behaviour changed in
 const char* sslcr_last_error(void) { return g_err; }
+
+int sslcr_switch_count(void) { return sw::COUNT; }
+int sslcr_switch_info(int i, sslcr_switch_row* out) {
+  NEED(out && i >= 0 && i < sw::COUNT, "index");
+  static const char* const kRule[] = {"ATOI", "LEAD0", "INT", "PRESENT"};
+  const sw::Row& r = sw::row(i);
+  const sw::Value v = sw::get(r.id);
+  *out = {r.name, r.group, kRule[r.rule], r.when == sw::CALL ? "call" : "process", r.meaning, r.dflt, v.v, v.set ? 1 : 0};
+  return 0;
+}
 
 int sslcr_conv2d(int dtype, const sslcr_conv_desc* d, void* stream) {
   DT_OK(dtype);

@@ -98,7 +98,7 @@ constexpr size_t H16_LDS_CAP = 160 * 1024;
 // 16: 16x16 tiles of one image; 8: four whole 8x8 images per tile (128-kout blocks: ResNet18 layer4 at 256x256 input); 0: not served.
 // q: the conv3x3_halo256 tiling of the descriptor that both dtypes agree on (conv_plan: the launches must tile identically)
 int conv_h16_mode(const ConvArgs& a, int q) {
-  static const bool on8 = [] { const char* e = getenv("SSLCR_H16_TW8"); return !e || atoi(e) != 0; }();   // 0: conv3x3_halo256 keeps the shape (A/B runs)
+  const bool on8 = sw::on(sw::H16_TW8);                // (the switch: A/B runs against conv3x3_halo256)
   const int mode = q == 16 ? 16 : (q == 8 && on8 && a.K % 128 == 0 && !a.mask_x && (a.seg_images <= 0 || a.seg_images % 4 == 0)) ? 8 : 0;
   if (mode == 0) return 0;
   if (a.in_scale && a.residual) return 0;              // not a ResNet combination; the older halo kernels take it
@@ -158,8 +158,7 @@ int conv_h16_rows(const ConvArgs& a) {
 
 // the train-mode forward's output stage (the RAW instance); SSLCR_H16_RAW=0 keeps the general body for same-box A/B runs
 static bool h16_raw(const ConvArgs& a) {
-  static const bool on = [] { const char* e = getenv("SSLCR_H16_RAW"); return !e || atoi(e) != 0; }();
-  return on && a.stats && !a.bias && !a.relu && !a.residual && !a.mask_x;
+  return sw::on(sw::H16_RAW) && a.stats && !a.bias && !a.relu && !a.residual && !a.mask_x;
 }
 
 // one tag per template instance of the two kernels (OSC: conv3x3_h16s_kernel<T, BKO, WK, WR, TW>)

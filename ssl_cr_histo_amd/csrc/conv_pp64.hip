@@ -449,7 +449,7 @@ static Pp64Geom pp64_geom(const ConvArgs& a) {
 // bf16 64 -> 64 on 16x16-tileable maps, every operand combination conv3x3_h16's resident-filter form serves (conv_plan asks where
 // conv_h16_mode has taken the descriptor); SSLCR_PP64=0 keeps the old kernel for same-box A/B runs
 bool conv_pp64_ok(int dtype, const ConvArgs& a) {
-  static const bool on = [] { const char* e = getenv("SSLCR_PP64"); return !e || atoi(e) != 0; }();
+  const bool on = sw::on(sw::PP64);
   if ((size_t)a.N * a.H * a.W * 64 * 2 >= ((size_t)1 << 32)) return false;       // the kernel addresses with 32-bit byte offsets
   if (a.W > 2048) return false;                                                  // halo roles pack a pixel offset of up to 17 W + 17 into 16 bits
   return on && dtype == DT_BF16 && a.C == 64 && a.K == 64 && a.R == 3 && a.S == 3 && a.stride == 1 && a.pad == 1 && !a.transposed &&

@@ -436,8 +436,7 @@ __global__ __launch_bounds__(512, 2) void conv_s2_kernel(const ConvArgs a, const
 // ---- host side
 // the 3x3 / 2 descriptor this kernel serves (bf16; fp32 and everything else stay on the gather kernel)
 bool conv_s2_ok(int dtype, const ConvArgs& a) {
-  static const bool on = [] { const char* e = getenv("SSLCR_S2"); return !e || atoi(e) != 0; }();     // 0: the gather kernel keeps these shapes (A/B runs)
-  if (!on || dtype != DT_BF16) return false;
+  if (!sw::on(sw::S2) || dtype != DT_BF16) return false;       // (the switch: A/B runs against the gather kernel)
   if (a.R != 3 || a.S != 3 || a.stride != 2 || a.pad != 1 || a.transposed || a.par4 || a.tap_mask || a.pix_mul > 1 || a.pix_off_h || a.pix_off_w) return false;
   if (a.in_scale || a.residual || a.accumulate || a.mask_x || a.osh != 1) return false;
   if (a.H % 32 != 0 || a.W % 32 != 0 || a.PH != a.H / 2 || a.PW != a.W / 2 || a.OH != a.PH || a.OW != a.PW) return false;

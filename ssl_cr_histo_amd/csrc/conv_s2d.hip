@@ -284,8 +284,7 @@ __global__ __launch_bounds__(512, 2) void conv_s2d_kernel(const ConvArgs a, cons
 
 // the par4 descriptor this kernel serves (sslcr_conv_desc: transposed, stride 2, pix_mul 2, PH x PW = dY's map)
 bool conv_s2d_ok(int dtype, const ConvArgs& a) {
-  static const bool on = [] { const char* e = getenv("SSLCR_S2D"); return !e || atoi(e) != 0; }();    // 0: the gather kernel keeps the shape (A/B runs)
-  if (!on || dtype != DT_BF16) return false;
+  if (!sw::on(sw::S2D) || dtype != DT_BF16) return false;      // (the switch: A/B runs against the gather kernel)
   if (!a.par4 || !a.transposed || a.stride != 2 || a.R != 3 || a.S != 3 || a.pad != 1 || a.pix_mul != 2 || a.tap_mask) return false;
   if (a.in_scale || a.residual || a.accumulate || a.mask_x || a.bias || a.out_scale || a.relu || a.stats || a.osh != 1 || a.seg_images > 0) return false;
   if (a.H % 16 != 0 || a.W % 16 != 0 || a.PH != a.H || a.PW != a.W || a.OH != 2 * a.H || a.OW != 2 * a.W) return false;

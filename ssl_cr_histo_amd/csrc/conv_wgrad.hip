@@ -218,10 +218,7 @@ __global__ __launch_bounds__(256 * KH, 2) void wgrad_kernel(const WgradArgs a, i
       }
 }
 
-static bool wgrad_wide(int dtype, const WgradArgs& a) {
-  static const bool on = [] { const char* e = getenv("SSLCR_WGRAD_WIDE"); return !(e && e[0] == '0'); }();
-  return on && dtype == DT_BF16 && a.K % 128 == 0;
-}
+static bool wgrad_wide(int dtype, const WgradArgs& a) { return sw::on(sw::WGRAD_WIDE) && dtype == DT_BF16 && a.K % 128 == 0; }
 
 template <typename T, int TAPS, int KH>
 struct WgradInst { static std::string spell() { return kname("wgrad_kernel", ktype<T>(), TAPS, KH); } };

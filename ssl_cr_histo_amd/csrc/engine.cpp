@@ -475,10 +475,7 @@ void build_topology(sslcr_net* n) {
 
 // bf16 storage: eval-mode BatchNorm is NOT folded into the filters (the scale rides in the conv epilogues).  SSLCR_UNFOLD_EVAL=0 folds as
 // rounds 1-5 did (A/B runs, tools/bf16_teacher_fold_experiment.py)
-bool unfold_eval(const sslcr_ctx* c) {
-  static const bool on = [] { const char* e = getenv("SSLCR_UNFOLD_EVAL"); return !e || atoi(e) != 0; }();
-  return on && c->dtype == DT_BF16;
-}
+bool unfold_eval(const sslcr_ctx* c) { return sw::on(sw::UNFOLD_EVAL) && c->dtype == DT_BF16; }
 
 int alloc_shadow(sslcr_net* n) {
   const size_t es = n->ctx->esz();
@@ -760,10 +757,7 @@ int forward_stem(sslcr_net* n, PassState& ps, const void* x, int in_f32, int N, 
 
 // The ReLU mask of a block output as bits (sslcr_bn_act_desc.ybits, bf16 mode): bn2's backward reduce pass reads 1/16 of the bytes of y.
 // SSLCR_YBITS=0 keeps the tensor read (same-box A/B runs).
-bool ybits_on(const sslcr_ctx* c) {
-  static const bool on = [] { const char* e = getenv("SSLCR_YBITS"); return !e || atoi(e) != 0; }();
-  return on && c->dtype == DT_BF16;
-}
+bool ybits_on(const sslcr_ctx* c) { return sw::on(sw::YBITS) && c->dtype == DT_BF16; }
 // the bits that go with the saved output of block i (nullptr: this net keeps none)
 uint8_t* ybits_of(const sslcr_net* n, const PassState& ps, int i) { return n->ybits_ok && ybits_on(n->ctx) ? ps.blk[i].ybits : nullptr; }
 
@@ -896,10 +890,7 @@ int forward_blocks(sslcr_net* n, PassState& ps, int N, int H, int W, int replay,
 // slower per image than the same kernels at N = 640 (r03: conv3x3_h16 48.7 us against 149 us for five times the images).
 // The stem (three separate input tensors) and its pool stay per pass.  false = some layer has no segment form here: the caller
 // runs the passes one by one.
-bool segments_on() {
-  static const bool on = [] { const char* e = getenv("SSLCR_SEGMENTS"); return !(e && e[0] == '0'); }();
-  return on;
-}
+bool segments_on() { return sw::on(sw::SEGMENTS); }
 // (asked once the passes are allocated for N, H, W: the plans it reads are the ones forward_blocks will launch from)
 bool segments_servable(sslcr_net* n, int N, int H, int W) {
   sslcr_ctx* c = n->ctx;
@@ -1404,8 +1395,7 @@ struct Backward {
     // (g is read by nobody else in a downsampling block, so with the mask as bits it need not be written at all -- measured
     //  SLOWER, 15.81 -> 15.90 ms same box: forming g from (dOut, bits) a second time costs the apply pass more than reading it.
     //  SSLCR_BN_PAIR_G=0 selects that form; the debug tap always keeps g)
-    static const bool g_free = [] { const char* e = getenv("SSLCR_BN_PAIR_G"); return e && atoi(e) == 0; }();
-    const int keep_g = (n->tap || !a2.yact_bits || !g_free) ? 1 : 0;
+    const int keep_g = (n->tap || !a2.yact_bits || sw::on(sw::BN_PAIR_G)) ? 1 : 0;
     if (pair) n->tap_flags[i] |= 1 << 4;
     if (pair) {
       TRY(launch_bn_bwd_reduce_pair(dt, a2, ad, keep_g, st));
@@ -1679,7 +1669,7 @@ int sslcr_create(sslcr_ctx** out, int device, int dtype) {
   TRY(hipSetDevice(device));
   sslcr_ctx* c = new sslcr_ctx();
   c->device = device; c->dtype = dtype == SSLCR_FP8 ? SSLCR_BF16 : dtype; c->fp8 = dtype == SSLCR_FP8;
-  if (const char* e = getenv("SSLCR_FUSE_STEM_BWD")) c->fuse_stem_bwd = atoi(e) != 0;
+  c->fuse_stem_bwd = sw::on(sw::FUSE_STEM_BWD);       // asked at every create: a test sets it between two engines of one process
   // bn_stage: [kMaxSeg][32][2][C] (sslcr_bn_finalize_desc.stage with segments)
   if (c->small.ensure((size_t)kMaxSeg * 32 * 2 * 512 * sizeof(double) + 2 * 2 * 512 * sizeof(double) + 2 * 512 * sizeof(float) + 64 * sizeof(int)) != 0) { delete c; return -1; }
   c->bn_stage = (double*)c->small.p;
@@ -1804,7 +1794,7 @@ int sslcr_comm_init(sslcr_ctx* c, const void* id256, int rank, int world) {
   if (!c || !id256 || world < 1 || rank < 0 || rank >= world) return fail("sslcr_comm_init: invalid argument");
   // world == 1 normally needs no communicator; SSLCR_COMM_SELFTEST=1 creates the two 1-rank communicators anyway so that the
   // whole collective code path (RCCL calls, side stream, events) can be exercised on a single-GPU box (tests/test_engine_gpu.py)
-  if (world == 1 && !getenv("SSLCR_COMM_SELFTEST")) { c->rank = 0; c->world = 1; return 0; }
+  if (world == 1 && !sw::on(sw::COMM_SELFTEST)) { c->rank = 0; c->world = 1; return 0; }
   TRY(hipSetDevice(c->device));
   ncclUniqueId id, idg;
   memcpy(&id, id256, sizeof(id));

@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void gemm_f32_lds_kernel(const float* __restri
 
 static hipError_t gemm(const float* A, long sa_i, long sa_k, const float* B, long sb_k, long sb_j, float* C, int M, int N, int K,
                        const float* bias, int relu, int accumulate, hipStream_t st) {
-  static const bool lds_on = [] { const char* e = getenv("SSLCR_GEMM_LDS"); return !e || atoi(e) != 0; }();     // 0: the direct-fetch form for everything (A/B runs)
+  const bool lds_on = sw::on(sw::GEMM_LDS);            // (the switch: A/B runs against the direct-fetch form)
   const bool akc = sa_k == 1, bkc = sb_k == 1;
   const long sa = akc ? sa_i : sa_k, sb = bkc ? sb_j : sb_k;
   const bool lds_ok = lds_on && M % 32 == 0 && N % 32 == 0 && K % 64 == 0 && (akc || sa_i == 1) && (bkc || sb_j == 1) && (sa & 3) == 0 &&

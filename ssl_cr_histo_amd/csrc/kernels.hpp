@@ -5,6 +5,7 @@
 
 #include "common.hpp"
 #include "launch.hpp"
+#include "switches.hpp"
 #include "../../include/sslcr.h"
 
 namespace sslcr {

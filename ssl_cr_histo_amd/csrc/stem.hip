@@ -854,10 +854,7 @@ static hipError_t launch_stem_wgrad_pool2(const StemWgradArgs& a, const BnBwdArg
   return launch_stem_wgrad_k<stem_wgrad_pool2_kernel<INF32>>(256, 768, P2_NS * P2_STAGE + 2 * P2_HBUF, 160 * 1024, a, b, st);
 }
 
-static int stem_pool_form() {                      // SSLCR_STEM_POOL_FORM=1: the single-role kernel in bf16 mode too (A/B runs)
-  static const int v = [] { const char* e = getenv("SSLCR_STEM_POOL_FORM"); return e ? atoi(e) : 2; }();
-  return v;
-}
+static int stem_pool_form() { return (int)sw::value(sw::STEM_POOL_FORM); }      // (the switch: A/B runs of the single-role kernel in bf16)
 
 // one tag per instance of the pool form: the role-split kernel (P2; bf16 only) or stem_wgrad_kernel<T, INF32, POOL = true>
 template <bool P2, typename T, bool INF32>

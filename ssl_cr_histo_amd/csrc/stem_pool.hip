@@ -226,7 +226,7 @@ __global__ __launch_bounds__(SP_NT) void stem_pool_fwd_kernel(const StemArgs a, 
 
 // shapes the fused kernel serves: bf16, eval form, conv output tileable by 16 (256x256, 224x224, 64x64 ... inputs)
 bool stem_pool_ok(int dtype, const StemArgs& a, int POH, int POW) {
-  static const bool on = [] { const char* e = getenv("SSLCR_STEM_POOL"); return !e || atoi(e) != 0; }();
+  const bool on = sw::on(sw::STEM_POOL);
   // (ReLU: the pooling compares bf16 bit patterns as integers; two tile columns at least: a tile refreshes its own part of the row
   //  buffer in the phase in which the next tile's part is read)
   return on && dtype == DT_BF16 && !a.stats && a.relu && a.OH % 16 == 0 && a.OW % 16 == 0 && a.OW >= 32 && a.OW <= 256 && POH == a.OH / 2 &&

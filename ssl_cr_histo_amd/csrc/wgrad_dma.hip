@@ -360,8 +360,7 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_dma_kernel(const WgradArgs a,
 // bf16, 128-kout blocks, tensors below 2 GiB (32-bit DMA offsets), more than one pixel split (the kernel always writes slabs);
 // SSLCR_WG_DMA=0: wgrad3x3_halo_kernel (A/B runs)
 bool wgrad_dma_ok(int dtype, const WgradArgs& a, int splits) {
-  static const bool on = [] { const char* e = getenv("SSLCR_WG_DMA"); return !e || atoi(e) != 0; }();
-  if (!on || dtype != DT_BF16 || a.K % 128 != 0 || splits < 2) return false;
+  if (!sw::on(sw::WG_DMA) || dtype != DT_BF16 || a.K % 128 != 0 || splits < 2) return false;
   const long long px = (long long)a.N * a.H * a.W;
   return px * a.K * 2 < (1ll << 31) && px * a.C * 2 < (1ll << 31);
 }
@@ -375,7 +374,7 @@ static hipError_t launch_wd_t(WgradDmaInst<TW, XF>, const WgradArgs& a, int tps,
   const int nseg = a.seg_images > 0 ? a.N / a.seg_images : 1;
   const size_t lds = (size_t)2 * (256 + NI * 10 * PITCH) * 128 + 512 * nseg;
   const int gx = a.K / 128, gy = a.C / 64;
-  static const int stagger = [] { const char* e = getenv("SSLCR_WG_STAGGER"); return e ? atoi(e) : 1; }();
+  const int stagger = (int)sw::value(sw::WG_STAGGER);
   return launch_lds<wgrad3x3_dma_kernel<TW, XF>>(dim3(gx * gy * splits), dim3(512), lds, 160 * 1024, st, a, tps, ntiles, slabs, stagger);
 }
 

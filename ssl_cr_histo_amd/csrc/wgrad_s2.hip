@@ -205,8 +205,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_s2_kernel(const WgradArgs a, int
 }
 
 bool wgrad_s2_ok(int dtype, const WgradArgs& a) {
-  static const bool on = [] { const char* e = getenv("SSLCR_S2W"); return !e || atoi(e) != 0; }();     // 0: the gather kernel keeps the shape (A/B runs)
-  if (!on || dtype != DT_BF16) return false;
+  if (!sw::on(sw::S2W) || dtype != DT_BF16) return false;      // (the switch: A/B runs against the gather kernel)
   if (a.R != 3 || a.S != 3 || a.stride != 2 || a.pad != 1 || a.in_scale) return false;
   if (a.H != 2 * a.OH || a.W != 2 * a.OW || a.C % 64 != 0 || a.K % 128 != 0) return false;
   if (!((a.OH % 4 == 0 && a.OW % 16 == 0) || (a.OH % 8 == 0 && a.OW == 8))) return false;

@@ -9,7 +9,7 @@ import weakref
 import torch
 
 from . import _lib as L
-from .kernels import LossOptions
+from .kernels import LossOptions, switches
 from .net import Classifier, FinetuneResNet, TripletNet, TripletNet_Finetune, unwrap
 
 _DTYPES = {"fp32": 0, "f32": 0, "float32": 0, "bf16": 1, "bfloat16": 1, "fp8": 2}     # fp8: bf16 engine + e4m3 forward convs (config 5)
@@ -380,8 +380,10 @@ class Engine:
 
     # ------------------------------------------------------------------ distributed (one process per GPU, RCCL inside)
     def init_comm(self, rank, world, broadcast_bytes):
-        """broadcast_bytes(bytes_or_None) -> bytes : host-side broadcast of the 128-byte RCCL id from rank 0."""
-        if world == 1 and not os.environ.get("SSLCR_COMM_SELFTEST"):
+        """broadcast_bytes(bytes_or_None) -> bytes : host-side broadcast of the 128-byte RCCL id from rank 0.
+        world == 1 needs no communicator unless SSLCR_COMM_SELFTEST is set, and whether it is set is the library's answer
+        (``kernels.switches()``, rule PRESENT: set at all, so an empty value counts here as it does in sslcr_comm_init)."""
+        if world == 1 and not switches()["SSLCR_COMM_SELFTEST"]["value"]:
             return
         idbuf = (C.c_char * 256)()
         if rank == 0:

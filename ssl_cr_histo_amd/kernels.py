@@ -45,6 +45,18 @@ def _u8(t):
     return t.view(torch.uint8) if t.dtype == torch.bool else t
 
 
+def switches():
+    """the library's SSLCR_* environment switches as it read them (include/sslcr.h, the table above sslcr_switch_info): {name: {group,
+    rule, when, default, set, value, meaning}} in the table's order.  Needs no device; `set` and `value` are what THIS process runs with
+    -- a misspelt variable shows up here as a switch that is not set."""
+    lib, out, r = L.lib(), {}, L.SwitchRow()
+    for i in range(lib.sslcr_switch_count()):
+        L.check(lib.sslcr_switch_info(i, r))
+        out[r.name.decode()] = {"group": r.group.decode(), "rule": r.rule.decode(), "when": r.when.decode(), "default": r.dflt,
+                                "set": bool(r.is_set), "value": r.value, "meaning": r.meaning.decode()}
+    return out
+
+
 last_conv_kernel = ""        # kernel instance the most recent conv2d() launched (rocprofv3 spelling), for tests / profiles
 last_wgrad_kernel = ""       # ... and the most recent conv2d_wgrad()
 last_stem_wgrad_kernel = ""  # ... and the most recent stem_wgrad_pool()

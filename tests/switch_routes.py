@@ -1,5 +1,6 @@
-"""The library's SSLCR_* environment switches and the routes behind them (data only).  Every switch is read once into a static, so a
-test of one sets it in the environment of a fresh child process (tests/test_switch_routes_cpu.py, tests/test_switch_routes_gpu.py).
+"""The library's SSLCR_* environment switches and the routes behind them (data only).  The library's own table of them is
+kernels.switches(); all but two rows are read once per process, so a test of one sets it in the environment of a fresh child process
+(tests/test_switch_routes_cpu.py, tests/test_switch_routes_gpu.py).
 
 ROUTING                switch -> the value that turns its default off, for the switches that change which instance the router answers.
 SWITCH_ROUTES          switch -> rows of the shape of kernel_routes.ROUTES, (op, dtype, shape, flags, name, tail); `name` is what the

@@ -150,14 +150,14 @@ def test_annotation_first_hit_order_and_degenerate_polygons():
 
 
 # ---------------------------------------------------------------------------------------------------------------- descriptors
-def test_version_is_15_and_the_entries_are_exported():
+def test_version_is_16_and_the_entries_are_exported():
     from ssl_cr_histo_amd import _lib as L
     from ssl_cr_histo_amd import build
     if not os.path.exists(L.LIB_PATH):
         build.build()
     from ssl_cr_histo_amd import engine  # noqa: F401  registers engine signatures
     lib = L.lib()
-    assert lib.sslcr_version() == 15
+    assert lib.sslcr_version() == 16      # (15 brought these entries; 16 the switch listing)
     assert {"sslcr_points_in_polygons", "sslcr_map_confusion"} <= set(build.header_symbols())
     # argument checks run before any device work
     assert lib.sslcr_points_in_polygons(None, None) == -1

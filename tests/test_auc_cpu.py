@@ -191,7 +191,7 @@ def test_the_new_header_symbols_are_declared_bound_and_exported():
     lib = _lib.lib()
     for n in names:
         assert hasattr(lib, n)
-    assert lib.sslcr_version() == 15
+    assert lib.sslcr_version() == 16
     # sizes: hist [B][256][tiles] + tot [B][256] ints; 8 ints per block and column; 0 for refused arguments
     T = _lib.SORT_TILE
     assert lib.sslcr_sort_workspace_bytes(3, 2 * T + 1) == 3 * 256 * (3 + 1) * 4 and lib.sslcr_sort_workspace_bytes(0, 5) == 0

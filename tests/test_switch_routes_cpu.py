@@ -1,8 +1,9 @@
-"""CPU-only: the routes behind the library's A/B switches (tests/switch_routes.py).  The routing reads each SSLCR_* switch once into a
-static, so every switch is walked in a fresh child process with the variable in its environment: one walk of tools/route_sweep.py's
+"""CPU-only: the routes behind the library's A/B switches (tests/switch_routes.py).  The routing switches are read once per
+process, so every switch is walked in a fresh child process with the variable in its environment: one walk of tools/route_sweep.py's
 grid per routing switch, all started side by side, and one walk of the default routing in this process.  The closure: every distinct
 (default instance -> switched instance) transition of every switch has a row in SWITCH_ROUTES whose descriptor makes exactly that
-transition, and every row makes a transition the sweep shows.  The inventory: every getenv("SSLCR_...") of csrc/ is classified."""
+transition, and every row makes a transition the sweep shows.  The inventory: every row of the library's switch table
+(kernels.switches()) is classified, and no file of csrc/ but the table's reads the environment."""
 import json
 import os
 import re
@@ -213,22 +214,35 @@ def test_a_deleted_row_fails_the_closure_and_names_the_transition(closure):
             assert lines[0].endswith(f"with the flags [{r[3]}]") or re.search(r": smallest descriptor (conv|dgrad|wgrad) \d+x\d+x\d+ ", lines[0]), lines
 
 
-def switches_read(csrc):
+def getenv_files(csrc):
+    """the files of csrc that read the environment: any getenv at all, a getenv("SSLCR_...") among them"""
     found = set()
     for name in sorted(os.listdir(csrc)):
         with open(os.path.join(csrc, name), errors="replace") as f:
-            found |= set(re.findall(r'getenv\("(SSLCR_\w+)"\)', f.read()))
+            if re.search(r"\bgetenv\s*\(", f.read()):
+                found.add(name)
     return found
 
 
 def test_every_switch_the_library_reads_is_classified(tmp_path):
-    """a new getenv("SSLCR_...") arrives with a test or with a stated reason for having none"""
-    csrc = os.path.join(ROOT, "ssl_cr_histo_amd", "csrc")
+    """a new switch arrives with a test or with a stated reason for having none.  The inventory is the library's own table
+    (kernels.switches()); the walk over the sources holds that the table's file is the only one of csrc/ that reads the environment,
+    so that no switch exists beside the table"""
+    from ssl_cr_histo_amd import kernels
+    table = kernels.switches()
     classified = set(SR.ROUTING) | set(SR.FORMS) | set(SR.ENGINE) | set(SR.COVERED_ELSEWHERE) | set(SR.OUT_OF_SCOPE)
-    assert switches_read(csrc) == classified
+    assert set(table) == classified
+    # each row's group is where tests/switch_routes.py files the switch
+    by_group = {g: {sw for sw, row in table.items() if row["group"] == g} for g in ("routing", "form", "engine", "measurement")}
+    assert sum(len(v) for v in by_group.values()) == len(table), "a row with a group of its own"
+    assert by_group["routing"] == set(SR.ROUTING) and by_group["form"] == set(SR.FORMS)
+    assert by_group["measurement"] == {"SSLCR_BN_REPEAT", "SSLCR_EW_CAP"} <= set(SR.OUT_OF_SCOPE)
+    assert set(SR.ENGINE) | set(SR.COVERED_ELSEWHERE) <= by_group["engine"]
+    csrc = os.path.join(ROOT, "ssl_cr_histo_amd", "csrc")
+    assert getenv_files(csrc) == {"switches.cpp"}
     # ... and the scan itself notices one more
     (tmp_path / "new.hip").write_text('static const bool on = [] { const char* e = getenv("SSLCR_NEW"); return !e; }();\n')
-    assert switches_read(str(tmp_path)) == {"SSLCR_NEW"}
+    assert getenv_files(str(tmp_path)) == {"new.hip"}
 
 
 def test_covered_elsewhere_names_tests_that_exist():

@@ -1,5 +1,5 @@
 """The kernels and kernel / shape combinations that only an SSLCR_* switch reaches (tests/switch_routes.py), against float64.  The
-library reads each switch once into a static, so every test starts ONE fresh child process with the switch in its environment; the
+library reads each of these switches once per process, so every test starts ONE fresh child process with the switch in its environment; the
 child runs the existing float64 bodies of tests/test_kernels_gpu.py on the switch's rows (the derived per-element bounds of
 tests/_f64.py: no tolerance of its own here), catches AssertionError per row and leaves {row: "ok" | message} in a file.  This
 process never opens the device: a test's child is the only process on it.  A child that ends by a signal, aborts, or runs out of
@@ -65,7 +65,11 @@ def _stem_pool_form(T, shape, split, in_u8):
 def child(switch, out):
     """every row of `switch` (set in this process' environment by the parent) -> {row id: "ok" | message} in the file `out`"""
     import test_kernels_gpu as T
-    assert os.environ[switch] == {**SR.ROUTING, **SR.FORMS}[switch]
+    value = {**SR.ROUTING, **SR.FORMS}[switch]
+    assert os.environ[switch] == value
+    # ... and the library saw it: the row is set, to the value the parent gave (a misspelt name would leave the default in place)
+    seen = T._k().switches()[switch]
+    assert seen["set"] is True and seen["value"] == int(value), (switch, seen)
     results = {}
     if switch in SR.ROUTING:
         for row in SR.SWITCH_ROUTES[switch] + SR.LARGER_ROUTES.get(switch, []):

@@ -78,9 +78,10 @@ def walk():
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--lib", required=True)
+    ap.add_argument("--switched", action="store_true", help="dump the routes under the SSLCR_* variables that are set (two builds under one switch)")
     args = ap.parse_args()
     set_ = sorted(k for k in os.environ if k.startswith("SSLCR_"))
-    if set_:
+    if set_ and not args.switched:
         sys.exit(f"unset {set_}: the routing reads its switches once into statics, so this dump would not be the default routes")
     lib = C.CDLL(args.lib)
     for fn in ("sslcr_conv2d_kernel_name", "sslcr_conv2d_partial_rows", "sslcr_conv2d_segments_ok", "sslcr_conv2d_s2_pair_ok",
