@@ -1367,6 +1367,90 @@ typedef struct sslcr_augv2_colour_desc {
 } sslcr_augv2_colour_desc;
 int sslcr_randaug_v2_colour(const sslcr_augv2_colour_desc* d, void* stream);
 
+/* ---- device-side RandAugment of the consistency-training pipeline, the six OpenCV-style ops of models/randaugment.py:51-110 (HSV,
+ *      Noise, Scale_Resize_Crop, Shift_Scale_Rotate, Blur_img, Rotate_Crop) on a uint8 RGB batch in HBM.  The library version stays
+ *      16: the entries are told by their symbols.  One call serves ONE op slot of a whole batch: image n takes op[n] with row n of
+ *      the parameter tables; SSLCR_AUGV1_COPY, or apply[n] == 0, passes it through (only the layout may change).  The random draws
+ *      stay on the host, in the reference's order (ssl_cr_histo_amd/augment.py); the kernels are deterministic (no floating-point
+ *      atomics, no spins, no host reads: two calls give equal bits).
+ *
+ *      The arithmetic below IS the definition.  It is written after OpenCV 3.4.2, albumentations 0.1.8 and imgaug 0.4.0, none of
+ *      which can be run here: PARITY UNPINNED against all three.  tests/_cv_ref.py restates it in NumPy and is held to scipy,
+ *      colorsys and torch; the kernels are held to the restatement, bit for bit except where stated.
+ *
+ *      REFLECT_101 of an index p into a length n: n == 1 -> 0; else m = p mod (2n - 2) (non-negative), m >= n -> 2n - 2 - m.  This
+ *      is the repeated reflection of cv::borderInterpolate in closed form.
+ *
+ *      The cubic: A = -0.75, float32, every operation rounded on its own, for a fraction x:
+ *        c0 = ((A (x + 1) - 5A) (x + 1) + 8A) (x + 1) - 4A;  c1 = ((A + 2) x - (A + 3)) x x + 1  (left to right);
+ *        c2 = c1 at (1 - x);  c3 = 1 - c0 - c1 - c2  (left to right).
+ *
+ *      1. BLUR (Blur_img -> cv2.blur, k in {3, 5, 7}): per channel the integer sum over the k x k window centred on the pixel,
+ *         indices through REFLECT_101; out = (2 sum + k k) / (2 k k) in integers (k k is odd: no tie).
+ *      2. HSV (HSV -> shift_hsv): forward, OpenCV's 8-bit integer form with h in 0..179: v = max, diff = v - min,
+ *         s = (diff sdiv[v] + 2048) >> 12, h = (g - b) if v == r, else (b - r + 2 diff) if v == g, else (r - g + 4 diff);
+ *         h = (h hdiv[diff] + 2048) >> 12 (arithmetic shift), + 180 if negative; sdiv[i] = rint((255 << 12) / i),
+ *         hdiv[i] = rint((180 << 12) / (6 i)) in float64, entry 0 of both = 0.  The shifts are the integers rint(draw):
+ *         h += dh, then h = 255 - h where h < 0, then h -= 255 where h > 255 (the library's own wrap on the uint8 maximum, kept);
+ *         s and v are clipped to 0..255.  Back, float32, + - x only: hf = float(h) (6.f / 180.f), - 6 while >= 6; sector = floor,
+ *         f = hf - sector; s, v scaled by (1.f / 255.f); tab = {v, v (1 - s), v (1 - s f), v (1 - s (1 - f))}; the sector table
+ *         {{1,3,0},{1,0,2},{3,0,1},{0,2,1},{0,1,3},{2,1,0}} picks (b, g, r); each channel is rint(x 255.f) saturated.
+ *      3. WARP (Rotate, ShiftScaleRotate -> cv2.warpAffine(INTER_CUBIC, BORDER_REFLECT_101)): dparam row = the six doubles M0..M5 of
+ *         the INVERSE map (the host builds getRotationMatrix2D's matrix and inverts it in the library's order).  Per output pixel
+ *         X = (sat32(rint((M1 y + M2) 1024)) + 16 + sat32(rint(M0 x 1024))) >> 5 in float64 with one rounding per operation, Y likewise
+ *         from M4, M5, M3; sx = X >> 5, sy = Y >> 5, phase = (Y & 31) 32 + (X & 31); 16 taps at (sx - 1 + kx, sy - 1 + ky), each index
+ *         through REFLECT_101 and then, where the flip pair (fx, fy) = iparam[0..1] is set, mirrored (W - 1 - x / H - 1 - y): the
+ *         flip precedes the warp.  out = saturate((sum tap w[phase][4 ky + kx] + 16384) >> 15).  The host keeps
+ *         |M0| (W - 1) + |M1| (H - 1) + |M2| and its Y counterpart below 32000 (OpenCV's maps are 16-bit), so X, Y fit 32 bits.
+ *         The weight table w[1024][16] (sslcr_cv_warp_table): phase fy 32 + fx from the cubic at fy / 32 and fx / 32,
+ *         entry = saturate_short(rint(float32(cy cx) 32768.f)); the residual r = sum - 32768 is subtracted from the largest (r < 0) or
+ *         the smallest (r > 0) of the four CENTRE entries [1..2][1..2], scanned row-major, the first extreme winning, and the result
+ *         is stored as the low 16 bits.  Entry 5 (the tap at (sx, sy); its weight is never negative) is READ AS UNSIGNED: at phase 0
+ *         it holds 32768, the unit tap, which a signed read would turn into -32768.  Every other entry is read signed.
+ *      4. RESIZE (RandomScale, Resize -> cv2.resize(INTER_CUBIC)): per axis f = float32((d + 0.5) (double(src) / double(dst)) - 0.5),
+ *         s = floor(f), four taps at s - 1 .. s + 2 clamped to the image, coefficients saturate_short(rint(c 2048.f)) of the cubic at
+ *         f - s (float32); horizontal pass in integers, vertical pass out = saturate((sum + (1 << 21)) >> 22); no antialiasing.
+ *         Scale_Resize_Crop is resize S -> S', resize S' -> S + 20, crop S at (y1, x1): iparam row = (S', y1, x1) with
+ *         1 <= S' <= work_smax and 0 <= y1, x1 <= 20; H == W is required.  Two launches: the first writes the S' x S' image into the
+ *         uint8 workspace (planar), the second computes only the cropped window of the second resize.
+ *      5. NOISE (Noise -> imgaug AdditiveGaussianNoise(per_channel=False)): one normal per pixel, shared by the three channels:
+ *         out = clip(x + rint(double(sigma) double(z)), 0, 255), sigma = dparam[0].  The stream is this project's, NOT imgaug's:
+ *         Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85), key = the image's 64-bit seed
+ *         (iparam[0] the low, iparam[1] the high word), counter = (pixel_index >> 2, 0, 0, 0); from the words w0..w3,
+ *         u1 = ((w >> 8) + 1) 2^-24 and u2 = (w >> 8) 2^-24; Box-Muller in float32, r = sqrt(-2 log u1), (r cos 2 pi u2, r sin 2 pi u2)
+ *         from (w0, w1) for pixels 4q and 4q + 1 and from (w2, w3) for 4q + 2 and 4q + 3.  The integer stream is exact
+ *         (sslcr_augv1_philox shows it); log, cos and sin are the device's float32 functions, so sigma z may differ from another
+ *         float32 library's in the last bits and a pixel whose sigma z lies within 1e-3 of a half-integer may differ by one. */
+#define SSLCR_AUGV1_COPY 0
+#define SSLCR_AUGV1_BLUR 1            /* iparam[0] = k */
+#define SSLCR_AUGV1_HSV 2             /* iparam[0..2] = (dh, ds, dv) */
+#define SSLCR_AUGV1_WARP 3            /* dparam[0..5] = M0..M5 (inverse map), iparam[0..1] = (fx, fy) */
+#define SSLCR_AUGV1_RESIZE 4          /* iparam[0..2] = (S', y1, x1) */
+#define SSLCR_AUGV1_NOISE 5           /* dparam[0] = sigma, iparam[0..1] = the seed's low and high word */
+typedef struct sslcr_augv1_desc {
+  const uint8_t* src;       /* [N][3][H][W] (src_hwc=0) or [N][H][W][3] (src_hwc=1) */
+  uint8_t* dst;             /* [N][3][H][W] (dst_hwc=0) or [N][H][W][3]; must NOT alias src */
+  const int32_t* op;        /* [N] device ints: SSLCR_AUGV1_* */
+  const uint8_t* apply;     /* [N] or NULL: 0 = the image is passed through like COPY */
+  const int32_t* iparam;    /* [N][4] device ints, per code as above; NULL when ops_mask has only COPY */
+  const double* dparam;     /* [N][6] device doubles (WARP, NOISE); or NULL */
+  const int16_t* wtab;      /* [1024][16] device int16, what sslcr_cv_warp_table builds (WARP); or NULL */
+  uint8_t* work;            /* workspace of sslcr_augv1_workspace_bytes(N, H, ...) bytes (RESIZE); or NULL */
+  int work_smax;            /* the largest S' the workspace holds per image: 3 * work_smax^2 bytes, rounded up to 16 */
+  unsigned ops_mask;        /* bit (1 << code) set for every code that occurs in op[]: the host planned the slot and knows.  An image
+                               whose code is unknown, or whose tables are NULL, or whose S' / y1 / x1 / k leave their ranges, is
+                               written BLACK instead of reading through a bad pointer */
+  int N, H, W, src_hwc, dst_hwc;
+} sslcr_augv1_desc;
+int sslcr_randaug_v1_slot(const sslcr_augv1_desc* d, void* stream);
+/* host only: the 1024 x 16 weight table of WARP into table (32 KiB of host memory) */
+int sslcr_cv_warp_table(int16_t* table);
+/* host only: bytes of the RESIZE workspace for N images of S x S whose scale draws stay <= max_scale (S' <= int(S max_scale));
+   0 on bad arguments */
+size_t sslcr_augv1_workspace_bytes(int N, int S, double max_scale);
+/* the Philox words of NOISE: words[4 i + j] = word j at counter (first + i, 0, 0, 0) under key seed, i < count; words on the device */
+int sslcr_augv1_philox(unsigned long long seed, uint32_t first, int count, uint32_t* words, void* stream);
+
 /* ==================================================================================================
  * Engine: the whole ResNet18 TripletNet(_Finetune)+head graph, forward / backward / update, orchestrated
  * natively (one C call per step).  Replaces the step bodies of the reference's train()/validate():

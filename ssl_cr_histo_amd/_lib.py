@@ -82,6 +82,9 @@ AugV2Desc = _S("sslcr_augv2_desc", "AugV2Desc", [(k, vp) for k in ("src", "dst",
 AugV2ColourDesc = _S("sslcr_augv2_colour_desc", "AugV2ColourDesc", [("img", vp), ("op", vp), ("param", vp), ("bsum", vp), ("cutoff_lo", f64), ("cutoff_hi", f64),
                                          ("hed_from_rgb", f32 * 9), ("rgb_from_hed", f32 * 9), ("ops_mask", C.c_uint)] +
                       [(k, i32) for k in ("N", "H", "W", "hwc")])
+AUGV1_OPS = ("copy", "blur", "hsv", "warp", "resize", "noise")      # SSLCR_AUGV1_*: the code is the index
+AugV1Desc = _S("sslcr_augv1_desc", "AugV1Desc", [(k, vp) for k in ("src", "dst", "op", "apply", "iparam", "dparam", "wtab", "work")] +
+               [("work_smax", i32), ("ops_mask", C.c_uint)] + [(k, i32) for k in ("N", "H", "W", "src_hwc", "dst_hwc")])
 WsiGatherDesc = _S("sslcr_wsi_gather_desc", "WsiGatherDesc", [("src", vp), ("xy", vp), ("dst", vp)] +
                    [(k, i32) for k in ("origin_x", "origin_y", "N", "RH", "RW", "S", "fill")])
 PredictDesc = _S("sslcr_predict_desc", "PredictDesc", [("logits", vp), ("n", i32), ("C", i32), ("target", vp), ("scores", vp), ("pred", vp), ("confusion", vp),
@@ -164,6 +167,7 @@ CONSTANTS.update({"SSLCR_KNN_" + k.upper(): v for v, k in enumerate(KNN_FORMS)})
 CONSTANTS.update({"SSLCR_TSNE_TILE": TSNE_TILE, "SSLCR_TSNE_CHUNK": TSNE_CHUNK, "SSLCR_TSNE_MAX_SLICES": TSNE_MAX_SLICES,
                   "SSLCR_TSNE_MAX_N": TSNE_MAX_N, "SSLCR_TSNE_LOG_COLS": TSNE_LOG_COLS})
 CONSTANTS.update({"SSLCR_KNN_VOTE_" + k.upper(): v for k, v in KNN_VOTES.items()})
+CONSTANTS.update({"SSLCR_AUGV1_" + k.upper(): v for v, k in enumerate(AUGV1_OPS)})
 
 # symbol -> (restype, argtypes); every symbol include/sslcr.h declares
 P = C.POINTER
@@ -261,6 +265,10 @@ SIGNATURES = {
     "sslcr_brightness_contrast": (i32, [P(BrightnessContrastDesc), vp]),
     "sslcr_randaug_v2_slot": (i32, [P(AugV2Desc), vp]),
     "sslcr_randaug_v2_colour": (i32, [P(AugV2ColourDesc), vp]),
+    "sslcr_randaug_v1_slot": (i32, [P(AugV1Desc), vp]),
+    "sslcr_cv_warp_table": (i32, [vp]),
+    "sslcr_augv1_workspace_bytes": (sz, [i32, i32, f64]),
+    "sslcr_augv1_philox": (i32, [C.c_ulonglong, C.c_uint32, i32, vp, vp]),
 }
 
 _lib = None

@@ -165,6 +165,201 @@ def brightness_contrast(batch_u8, alpha_beta, apply=None, *, out=None):
     return dst
 
 
+# The six OpenCV-style ops of the pool (models/randaugment.py:51-110): csrc/augment_v1.hip runs the arithmetic include/sslcr.h DEFINES
+# for them, one op SLOT of a whole batch per call.  The host side below makes the draws and turns them into the integers and matrices
+# the kernels read.  PARITY UNPINNED against OpenCV 3.4.2 / albumentations 0.1.8 / imgaug 0.4.0 (none is installed): the header is the
+# definition, tests/_cv_ref.py restates it, and the draw order is the reference's.
+V1_COPY, V1_BLUR, V1_HSV, V1_WARP, V1_RESIZE, V1_NOISE = range(6)
+SRC_MARGIN = 20                          # Scale_Resize_Crop: Resize(S + 20), RandomCrop(S)
+_WARP_TABLES = {}
+
+
+def cv_warp_table():
+    """the 1024 x 16 int16 weight table of the bicubic warp, as ``sslcr_cv_warp_table`` builds it (numpy, host)"""
+    import numpy as np
+    tab = np.empty((1024, 16), dtype=np.int16)
+    L.check(L.lib().sslcr_cv_warp_table(tab.ctypes.data))
+    return tab
+
+
+def _warp_table_on(device):
+    key = (device.type, device.index)
+    if key not in _WARP_TABLES:
+        _WARP_TABLES[key] = torch.from_numpy(cv_warp_table()).to(device)
+    return _WARP_TABLES[key]
+
+
+def rotation_matrix(hw, angle, scale=1.0, dx=0.0, dy=0.0):
+    """``cv2.getRotationMatrix2D((W / 2, H / 2), angle, scale)`` with albumentations' shift added to the translations (dx, dy are
+    fractions of W, H) -> the six floats of the FORWARD matrix"""
+    import math
+    h, w = hw
+    cx, cy = w / 2, h / 2
+    a = angle * math.pi / 180
+    al, be = math.cos(a) * scale, math.sin(a) * scale
+    return [al, be, (1 - al) * cx - be * cy + dx * w, -be, al, be * cx + (1 - al) * cy + dy * h]
+
+
+def invert_affine(m):
+    """the inverse ``cv2.warpAffine`` takes of its matrix, in its order of operations"""
+    m = [float(v) for v in m]
+    D = m[0] * m[4] - m[1] * m[3]
+    D = 1.0 / D if D != 0 else 0.0
+    a11, a22 = m[4] * D, m[0] * D
+    m[0], m[1], m[3], m[4] = a11, m[1] * -D, m[3] * -D, a22
+    b1 = -m[0] * m[2] - m[1] * m[5]
+    b2 = -m[3] * m[2] - m[4] * m[5]
+    m[2], m[5] = b1, b2
+    return m
+
+
+def v1_workspace(n, s, smax, device):
+    """scratch of the RESIZE code for N images of S x S whose intermediate sizes stay <= smax -> (uint8 tensor, smax)"""
+    nbytes = L.lib().sslcr_augv1_workspace_bytes(n, s, (smax + 0.5) / s)
+    if not nbytes:
+        raise ValueError(f"Scale_Resize_Crop: no workspace for {n} images of {s} with intermediate size {smax}")
+    return torch.empty((nbytes,), dtype=torch.uint8, device=device), smax
+
+
+def randaug_v1_slot(batch_u8, codes, *, iparam=None, dparam=None, apply=None, hwc=False, out_hwc=None, out=None, workspace=None):
+    """One op slot on a uint8 batch in HBM: image n takes ``codes[n]`` (V1_*) with row n of iparam [N,4] ints and dparam [N,6] doubles
+    (include/sslcr.h says what each code reads); apply [N] bool or None.  Everything is checked here, at plan time: a bad kernel size,
+    a matrix that leaves OpenCV's 16-bit map range, a non-square Scale_Resize_Crop or an intermediate size < 1 is a ValueError.
+    -> a new batch in the layout ``out_hwc`` asks for (default: the input's)."""
+    import numpy as np
+    h, w = _v2_batch(batch_u8, hwc, "randaug_v1_slot")
+    n, dev = batch_u8.shape[0], batch_u8.device
+    out_hwc = hwc if out_hwc is None else out_hwc
+    codes = np.asarray(codes, dtype=np.int32)
+    if codes.shape != (n,) or codes.min() < V1_COPY or codes.max() > V1_NOISE:
+        raise ValueError("codes must be [N] op codes")
+    ap = np.ones(n, bool) if apply is None else np.asarray([bool(a) for a in apply])
+    if ap.shape != (n,):
+        raise ValueError("apply must be [N]")
+    codes = np.where(ap, codes, V1_COPY).astype(np.int32)
+    ip = np.zeros((n, 4), np.int64) if iparam is None else np.asarray(iparam, dtype=np.int64).copy()
+    dp = np.zeros((n, 6), np.float64) if dparam is None else np.asarray(dparam, dtype=np.float64).copy()
+    if ip.shape != (n, 4) or dp.shape != (n, 6):
+        raise ValueError("iparam must be [N, 4] and dparam [N, 6]")
+    mask, smax = 0, 0
+    for i, c in enumerate(codes.tolist()):
+        mask |= 1 << c
+        if c == V1_BLUR and ip[i, 0] not in (3, 5, 7):
+            raise ValueError(f"blur: kernel size {ip[i, 0]} is not 3, 5 or 7")
+        if c == V1_HSV and np.abs(ip[i, :3]).max() > 255:
+            raise ValueError("hsv: shifts beyond +-255")
+        if c == V1_WARP:
+            m = dp[i]
+            if not np.isfinite(m).all() or max(abs(m[0]) * (w - 1) + abs(m[1]) * (h - 1) + abs(m[2]),
+                                               abs(m[3]) * (w - 1) + abs(m[4]) * (h - 1) + abs(m[5])) >= 32000:
+                raise ValueError("warp: the matrix leaves OpenCV's 16-bit map range")
+        if c == V1_RESIZE:
+            if h != w:
+                raise ValueError(f"Scale_Resize_Crop needs a square image, got {h}x{w}")
+            if ip[i, 0] < 1 or not (0 <= ip[i, 1] <= SRC_MARGIN and 0 <= ip[i, 2] <= SRC_MARGIN):
+                raise ValueError(f"Scale_Resize_Crop: intermediate size {ip[i, 0]} / origin ({ip[i, 1]}, {ip[i, 2]}) out of range")
+            smax = max(smax, int(ip[i, 0]))
+        if c == V1_NOISE and not (np.isfinite(dp[i, 0]) and dp[i, 0] >= 0):
+            raise ValueError("noise: sigma must be finite and >= 0")
+    work, wsmax = None, 0
+    if smax:
+        work, wsmax = workspace if workspace is not None else v1_workspace(n, h, smax, dev)
+        if wsmax < smax or work.dtype != torch.uint8 or work.device != dev or work.numel() < L.lib().sslcr_augv1_workspace_bytes(n, h, (wsmax + 0.5) / h):
+            raise ValueError("workspace: too small for this slot (v1_workspace)")
+    shape = (n, h, w, 3) if out_hwc else (n, 3, h, w)
+    dst = out if out is not None else torch.empty(shape, dtype=torch.uint8, device=dev)
+    if tuple(dst.shape) != shape or dst.dtype != torch.uint8 or not dst.is_contiguous() or dst.device != dev:
+        raise ValueError("out: contiguous uint8 batch of the output layout expected")
+    t_op = torch.from_numpy(codes).to(dev)
+    t_ip = torch.from_numpy((ip & 0xFFFFFFFF).astype(np.uint32).view(np.int32)).to(dev) if mask & ~1 else None
+    t_dp = torch.from_numpy(dp).to(dev) if mask & (1 << V1_WARP | 1 << V1_NOISE) else None
+    t_w = _warp_table_on(dev) if mask & (1 << V1_WARP) else None
+    d = L.AugV1Desc(L.ptr(batch_u8), L.ptr(dst), L.ptr(t_op), None, L.ptr(t_ip), L.ptr(t_dp), L.ptr(t_w), L.ptr(work), wsmax, mask,
+                    n, h, w, int(hwc), int(out_hwc))
+    L.check(L.lib().sslcr_randaug_v1_slot(d, L.stream_ptr()))
+    return dst
+
+
+def _v1_rows(n, rows, width, name):
+    import numpy as np
+    a = np.asarray(rows, dtype=np.float64)
+    if a.shape != ((n, width) if width else (n,)) or not np.isfinite(a).all():
+        raise ValueError(f"{name} must be {[n, width] if width else [n]} finite numbers")
+    return a
+
+
+def cv_blur(batch_u8, ksize, apply=None, **kw):
+    """``cv2.blur(img, (k, k))`` with k = ksize[n] in {3, 5, 7} where apply[n] (BORDER_REFLECT_101)."""
+    import numpy as np
+    n = batch_u8.shape[0]
+    ip = np.zeros((n, 4), np.int64)
+    ip[:, 0] = _v1_rows(n, ksize, 0, "ksize")
+    return randaug_v1_slot(batch_u8, [V1_BLUR] * n, iparam=ip, apply=apply, **kw)
+
+
+def cv_shift_hsv(batch_u8, shifts, apply=None, **kw):
+    """albumentations' ``shift_hsv`` with shifts[n] = (hue, sat, val) draws where apply[n]: the planes move by rint(draw)."""
+    import numpy as np
+    n = batch_u8.shape[0]
+    ip = np.zeros((n, 4), np.int64)
+    ip[:, :3] = np.rint(_v1_rows(n, shifts, 3, "shifts"))
+    return randaug_v1_slot(batch_u8, [V1_HSV] * n, iparam=ip, apply=apply, **kw)
+
+
+def cv_warp_affine(batch_u8, matrices, flips=None, apply=None, **kw):
+    """``cv2.warpAffine(img, M, (W, H), flags=INTER_CUBIC, borderMode=BORDER_REFLECT_101)`` with the FORWARD matrix M = matrices[n]
+    (six floats, ``rotation_matrix``) where apply[n]; flips[n] = (horizontal, vertical) mirrors the source first."""
+    import numpy as np
+    n = batch_u8.shape[0]
+    m = _v1_rows(n, matrices, 6, "matrices")
+    ip = np.zeros((n, 4), np.int64)
+    if flips is not None:
+        ip[:, :2] = _v1_rows(n, flips, 2, "flips") != 0
+    dp = np.array([invert_affine(row) for row in m.tolist()], dtype=np.float64)
+    return randaug_v1_slot(batch_u8, [V1_WARP] * n, iparam=ip, dparam=dp, apply=apply, **kw)
+
+
+def cv_scale_resize_crop(batch_u8, scales, origins, apply=None, **kw):
+    """``Scale_Resize_Crop``: cv2.resize(INTER_CUBIC) S -> int(S scales[n]) (None: the scale gate did not fire, S stays), resize to
+    S + 20, crop S at origins[n] = (y1, x1) pixels, where apply[n].  Square images only."""
+    import numpy as np
+    n = batch_u8.shape[0]
+    s = batch_u8.shape[2]
+    ip = np.zeros((n, 4), np.int64)
+    ip[:, 0] = [s if sc is None else int(s * float(sc)) for sc in scales]
+    ip[:, 1:3] = _v1_rows(n, origins, 2, "origins")
+    return randaug_v1_slot(batch_u8, [V1_RESIZE] * n, iparam=ip, apply=apply, **kw)
+
+
+def gaussian_noise(batch_u8, sigmas, seeds, apply=None, **kw):
+    """Additive Gaussian noise, one normal per pixel shared by the channels: out = clip(x + rint(sigmas[n] z)); z from Philox4x32-10
+    keyed by the 64-bit seeds[n] (include/sslcr.h states the stream; it is this project's, not imgaug's)."""
+    import numpy as np
+    n = batch_u8.shape[0]
+    ip, dp = np.zeros((n, 4), np.int64), np.zeros((n, 6), np.float64)
+    dp[:, 0] = _v1_rows(n, sigmas, 0, "sigmas")
+    if len(seeds) != n:
+        raise ValueError("seeds must be [N]")
+    for i, sd in enumerate(seeds):
+        sd = int(sd)
+        if not 0 <= sd < 1 << 64:
+            raise ValueError("seeds must be 64-bit unsigned integers")
+        ip[i, 0], ip[i, 1] = sd & 0xFFFFFFFF, sd >> 32
+    return randaug_v1_slot(batch_u8, [V1_NOISE] * n, iparam=ip, dparam=dp, apply=apply, **kw)
+
+
+def philox_words(seed, count, device, first=0):
+    """the integer stream of ``gaussian_noise``: Philox4x32-10 words at counters first .. first + count - 1 -> uint32-valued int64 [count, 4]"""
+    out = torch.empty((count, 4), dtype=torch.int32, device=device)
+    L.check(L.lib().sslcr_augv1_philox(int(seed), int(first), count, L.ptr(out), L.stream_ptr()))
+    return out.to(torch.int64) & 0xFFFFFFFF
+
+
+def _uniform(rng, a, b):
+    """``random.uniform(a, b)`` = a + (b - a) r, with albumentations 0.1.8's UNSORTED ``to_tuple`` limits"""
+    return a + (b - a) * rng.random()
+
+
 class RandAugmentDevice:
     """Batched counterpart of ``RandAugment(n, m)`` (models/randaugment.py:119-144) for a uint8 NCHW batch that sits in HBM.
 
@@ -172,23 +367,75 @@ class RandAugmentDevice:
     then makes its own draws from ``random``.  Here the same draws are made on the host, image after image and op after op, from
     the generators passed in; the ops with restatable arithmetic -- Color, Brightness, Contrast -- run on the device, batched per op
     slot with an apply mask.  The six geometric / blur / noise / HSV ops are albumentations 0.1.8 + OpenCV code that is not
-    installed here and cannot be pinned: they go through ``host_ops[name](img_hwc_uint8_numpy, val) -> numpy`` if given
-    (the image makes a round trip through host memory for that slot), else NotImplementedError names the op.  A host op draws from
-    the module-level generators when it RUNS (after the whole batch has been planned), so a batch that mixes host ops in does not
-    consume the ``random`` stream in the reference's image-by-image order; batches served by the device ops alone do."""
+    installed here and cannot be pinned; they depend on ``cv_ops``:
+
+    ``"host"`` (default): they go through ``host_ops[name](img_hwc_uint8_numpy, val) -> numpy`` if given (the image makes a round
+    trip through host memory for that slot), else NotImplementedError names the op.  A host op draws from the module-level generators
+    when it RUNS (after the whole batch has been planned), so a batch that mixes host ops in does not consume the ``random`` stream in
+    the reference's image-by-image order; batches served by the device ops alone do.
+
+    ``"device"``: ``plan`` makes the op's own draws in the reference's order -- the sign flip, ``Compose``'s ``random()``, every
+    transform's gate (the p = 1 ones included), then the parameters; ``np_rng`` serves ``Blur``'s kernel choice and, as this project's
+    own order, Noise's sigma and 64-bit seed -- and ``run`` applies them with ``randaug_v1_slot``: the arithmetic include/sslcr.h
+    defines (PARITY UNPINNED against the libraries), no host transfer of pixels, no synchronisation.  Square images only for the
+    three ops that crop.  A name present in ``host_ops`` still goes to the host."""
 
     POOL = (("HSV", -1, 1), ("Noise", 0, 0.15), ("Scale_Resize_Crop", 0.8, 1.2), ("Shift_Scale_Rotate", 0.01, 0.1),
             ("Color", -0.035, 0.035), ("Blur_img", 0, 2), ("Brightness", -0.2, 0.2), ("Contrast", -0.2, 0.2), ("Rotate_Crop", -90, 90))
+    CV = ("HSV", "Noise", "Scale_Resize_Crop", "Shift_Scale_Rotate", "Blur_img", "Rotate_Crop")
 
-    def __init__(self, n, m, rng, np_rng, host_ops=None):
-        self.n, self.m, self.rng, self.np_rng, self.host_ops = n, m, rng, np_rng, host_ops or {}
+    def __init__(self, n, m, rng, np_rng, host_ops=None, cv_ops="host"):
+        if cv_ops not in ("host", "device"):
+            raise ValueError('cv_ops must be "host" or "device"')
+        self.n, self.m, self.rng, self.np_rng, self.host_ops, self.cv_ops = n, m, rng, np_rng, host_ops or {}, cv_ops
 
-    def __call__(self, batch_u8):
-        N = batch_u8.shape[0]
-        cur = batch_u8
-        # the reference finishes one image (all its ops, in order) before it draws for the next: draw everything first, in that order
+    def _on_device(self, name):
+        return self.cv_ops == "device" and name in self.CV and name not in self.host_ops
+
+    def _cv_draws(self, name, v):
+        """the draws of ONE call of the op ``name`` with level v, in the reference's order -> the row's payload"""
+        rng = self.rng
+        if name in ("HSV", "Shift_Scale_Rotate", "Rotate_Crop") and rng.random() < 0.5:
+            v = -v
+        rng.random()                                                     # Compose: random() < 1
+        if name == "HSV":                                                # HueSaturationValue(p=0.5): hue, sat, val
+            if not rng.random() < 0.5:
+                return (False, 0.0, 0.0, 0.0)
+            return (True, _uniform(rng, -v, v), _uniform(rng, -v, v), _uniform(rng, -v, v))
+        if name == "Shift_Scale_Rotate":                                 # ShiftScaleRotate(p=0.5): angle, scale, dx, dy; RandomCrop(p=1)
+            row = (False, 0.0, 1.0, 0.0, 0.0)
+            if rng.random() < 0.5:
+                lim = v + 0.5
+                row = (True, _uniform(rng, -90, 90), _uniform(rng, 1 + -lim, 1 + lim), _uniform(rng, -v, v), _uniform(rng, -v, v))
+            rng.random(); rng.random(); rng.random()                     # RandomCrop: gate, h_start, w_start (the crop is the identity)
+            return row
+        if name == "Rotate_Crop":                                        # Flip(p=0.5): randint(-1, 1); Rotate(p=0.5); CenterCrop(p=1)
+            flip = rng.randint(-1, 1) if rng.random() < 0.5 else None
+            angle = _uniform(rng, -v, v) if rng.random() < 0.5 else None
+            rng.random()
+            return (flip, angle)
+        if name == "Scale_Resize_Crop":                                  # RandomScale(p=0.5); Resize(p=1); RandomCrop(p=1): h_start, w_start
+            scale = _uniform(rng, 1 + -v, 1 + v) if rng.random() < 0.5 else None
+            rng.random()
+            rng.random()
+            return (scale, rng.random(), rng.random())
+        if name == "Blur_img":                                           # Blur(p=0.5): np.random.choice of the odd sizes up to the limit
+            import numpy as np
+            if not rng.random() < 0.5:
+                return (False, 0)
+            return (True, int(self.np_rng.choice(np.arange(3, int(v + 5) + 1, 2))))
+        # Noise: IAAAdditiveGaussianNoise(p=0.5); sigma and the seed from np_rng (this project's order: imgaug seeds its own generator)
+        import numpy as np
+        if not rng.random() < 0.5:
+            return (False, 0.0, 0)
+        return (True, float(self.np_rng.uniform(0, v * 255)), int(self.np_rng.randint(0, 1 << 64, dtype=np.uint64)))
+
+    def plan(self, count):
+        """the draws of ``count`` successive RandAugment calls -> [[(name, payload)] * n] * count.  Color: (hmod, dmod, emod);
+        Brightness / Contrast: (applied, alpha, beta); a host op: its level; a device-side cv op: what ``_cv_draws`` returns"""
         plan = []
-        for _ in range(N):
+        # the reference finishes one image (all its ops, in order) before it draws for the next
+        for _ in range(count):
             ops = self.rng.choices(self.POOL, k=self.n)
             row = []
             for name, lo, hi in ops:
@@ -200,11 +447,52 @@ class RandAugmentDevice:
                     row.append((name, brightness_contrast_params(self.rng, brightness_limit=val)))
                 elif name == "Contrast":
                     row.append((name, brightness_contrast_params(self.rng, contrast_limit=val)))
+                elif self._on_device(name):
+                    row.append((name, self._cv_draws(name, val)))
                 else:
                     if name not in self.host_ops:
                         raise NotImplementedError(f"RandAugment op {name} (albumentations 0.1.8) has no device kernel; pass host_ops[{name!r}]")
                     row.append((name, val))      # the host op makes its own draws from the module-level generators when it runs
             plan.append(row)
+        return plan
+
+    @staticmethod
+    def cv_slot_row(name, payload, hw):
+        """one image's (code, iparam row, dparam row) for ``randaug_v1_slot`` from its plan payload"""
+        h, w = hw
+        ip, dp = [0, 0, 0, 0], [0.0] * 6
+        if name == "HSV":
+            if not payload[0]:
+                return V1_COPY, ip, dp
+            return V1_HSV, [int(round(payload[1])), int(round(payload[2])), int(round(payload[3])), 0], dp
+        if name == "Shift_Scale_Rotate":
+            if not payload[0]:
+                return V1_COPY, ip, dp
+            return V1_WARP, ip, invert_affine(rotation_matrix(hw, payload[1], payload[2], payload[3], payload[4]))
+        if name == "Rotate_Crop":
+            flip, angle = payload
+            if flip is None and angle is None:
+                return V1_COPY, ip, dp
+            ip[0], ip[1] = int(flip in (1, -1)), int(flip in (0, -1))      # cv2.flip: 0 vertical, 1 horizontal, -1 both
+            return V1_WARP, ip, invert_affine(rotation_matrix(hw, angle or 0.0))
+        if name == "Scale_Resize_Crop":
+            scale, hs, ws = payload
+            return V1_RESIZE, [h if scale is None else int(h * scale), int(SRC_MARGIN * hs), int(SRC_MARGIN * ws), 0], dp
+        if name == "Blur_img":
+            return (V1_BLUR, [payload[1], 0, 0, 0], dp) if payload[0] else (V1_COPY, ip, dp)
+        if name == "Noise":
+            if not payload[0]:
+                return V1_COPY, ip, dp
+            return V1_NOISE, [payload[2] & 0xFFFFFFFF, payload[2] >> 32, 0, 0], [payload[1]] + [0.0] * 5
+        raise ValueError(f"no device op {name!r}")
+
+    def run(self, batch_u8, plan):
+        """apply a plan (one row per image) to an NCHW batch"""
+        N = batch_u8.shape[0]
+        if len(plan) != N:
+            raise ValueError("one plan row per image expected")
+        hw = (batch_u8.shape[2], batch_u8.shape[3])
+        cur = batch_u8
         for slot in range(self.n):
             names = [plan[i][slot][0] for i in range(N)]
             if "Color" in names:
@@ -215,7 +503,14 @@ class RandAugmentDevice:
                 ab = [plan[i][slot][1][1:] if bc[i] else (1.0, 0.0) for i in range(N)]
                 if any(bc):
                     cur = brightness_contrast(cur, ab, bc)
-            host = [i for i, nm in enumerate(names) if nm not in ("Color", "Brightness", "Contrast")]
+            if any(self._on_device(nm) for nm in names):
+                if hw[0] != hw[1] and any(nm in ("Scale_Resize_Crop", "Shift_Scale_Rotate", "Rotate_Crop") and self._on_device(nm) for nm in names):
+                    raise ValueError(f"the crops of the pool take a square image, got {hw[0]}x{hw[1]}")
+                rows = [self.cv_slot_row(nm, plan[i][slot][1], hw) if self._on_device(nm) else (V1_COPY, [0] * 4, [0.0] * 6)
+                        for i, nm in enumerate(names)]
+                if any(r[0] != V1_COPY for r in rows):
+                    cur = randaug_v1_slot(cur, [r[0] for r in rows], iparam=[r[1] for r in rows], dparam=[r[2] for r in rows])
+            host = [i for i, nm in enumerate(names) if nm not in ("Color", "Brightness", "Contrast") and not self._on_device(nm)]
             if host:
                 if cur is batch_u8:
                     cur = batch_u8.clone()
@@ -226,6 +521,26 @@ class RandAugmentDevice:
                         res = res["image"]
                     cur[i] = torch.from_numpy(res).permute(2, 0, 1).to(cur.device)
         return cur
+
+    def __call__(self, batch_u8):
+        return self.run(batch_u8, self.plan(batch_u8.shape[0]))
+
+
+class TransformFixDevice:
+    """Batched, device-side counterpart of the WHOLE ``TransformFix(image_size, N)`` (dataset.py:663-677): ``TransformFixGeometric``'s
+    two flip + crop gathers, then ``RandAugment(n=N, m=10)`` on the strong branch with every op of the pool on the device
+    (``cv_ops="device"``).  -> (weak uint8 [B,3,S,S], strong uint8 [B,3,S,S]); no pixel makes a host round trip."""
+
+    def __init__(self, image_size, N, generator=None, rng=None, np_rng=None):
+        import random
+        import numpy as np
+        self.geometric = TransformFixGeometric(image_size, generator)
+        self.randaugment = RandAugmentDevice(N, 10, rng if rng is not None else random, np_rng if np_rng is not None else np.random,
+                                             cv_ops="device")
+
+    def __call__(self, batch_u8, src_hwc=False):
+        weak, strong = self.geometric(batch_u8, src_hwc)
+        return weak, self.randaugment(strong)
 
 
 # ------------------------------------------------------------------------------------------------ RSP v2: the Pillow RandAugment pool

@@ -885,6 +885,38 @@ int sslcr_randaug_v2_colour(const sslcr_augv2_colour_desc* d, void* stream) {
   NEED(d->cutoff_lo <= d->cutoff_hi, "cutoff range");
   return check(launch_augv2_colour(*d, (hipStream_t)stream), "randaug_v2_colour");
 }
+int sslcr_randaug_v1_slot(const sslcr_augv1_desc* d, void* stream) {
+  NEED(d && d->src && d->dst && d->op, "null");
+  NEED(d->src != d->dst, "dst aliases src");
+  NEED(d->N > 0 && d->N <= 65535 && d->H > 0 && d->W > 0 && d->H <= 16384 && d->W <= 16384, "batch shape");
+  const unsigned m = d->ops_mask;
+  NEED(m < (1u << (SSLCR_AUGV1_NOISE + 1)), "ops_mask names an unknown op");
+  NEED(!(m & ~(1u << SSLCR_AUGV1_COPY)) || d->iparam, "iparam");
+  NEED(!(m & (1u << SSLCR_AUGV1_WARP | 1u << SSLCR_AUGV1_NOISE)) || d->dparam, "dparam");
+  NEED(!(m & 1u << SSLCR_AUGV1_WARP) || d->wtab, "wtab");
+  NEED(!(m & 1u << SSLCR_AUGV1_RESIZE) || (d->work && d->work_smax >= 1 && d->work_smax <= 32768), "resize workspace");
+  NEED(!(m & 1u << SSLCR_AUGV1_RESIZE) || d->H == d->W, "Scale_Resize_Crop needs H == W");
+  NEED((reinterpret_cast<uintptr_t>(d->op) & 3) == 0 && (reinterpret_cast<uintptr_t>(d->iparam) & 3) == 0 &&
+       (reinterpret_cast<uintptr_t>(d->dparam) & 7) == 0 && (reinterpret_cast<uintptr_t>(d->wtab) & 15) == 0 &&
+       (reinterpret_cast<uintptr_t>(d->work) & 15) == 0, "alignment");
+  return check(launch_augv1(*d, (hipStream_t)stream), "randaug_v1_slot");
+}
+int sslcr_cv_warp_table(int16_t* table) {
+  NEED(table, "null");
+  cv_warp_table(table);
+  return 0;
+}
+size_t sslcr_augv1_workspace_bytes(int N, int S, double max_scale) {
+  if (N <= 0 || S <= 0 || S > 16384 || !(max_scale > 0.0) || !(max_scale <= 2.0)) return 0;
+  const int smax = (int)(S * max_scale);
+  return smax < 1 ? 0 : (size_t)N * augv1_work_stride(smax);
+}
+int sslcr_augv1_philox(unsigned long long seed, uint32_t first, int count, uint32_t* words, void* stream) {
+  NEED(words, "null");
+  NEED(count > 0 && count <= (1 << 24), "count");
+  NEED((reinterpret_cast<uintptr_t>(words) & 15) == 0, "alignment");
+  return check(launch_augv1_philox(seed, first, count, words, (hipStream_t)stream), "augv1_philox");
+}
 int sslcr_pack_stem(int dtype, const sslcr_pack_desc* d, void* stream) {
   DT_OK(dtype);
   NEED(d && d->w && d->w_fwd && d->K == 64 && d->C == 3 && d->R == 7 && d->S == 7, "stem shape");

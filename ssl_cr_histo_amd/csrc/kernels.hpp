@@ -256,6 +256,12 @@ hipError_t launch_hed_colour(const sslcr_colour_aug_desc& a, hipStream_t st);
 hipError_t launch_brightness_contrast(const sslcr_brightness_contrast_desc& a, hipStream_t st);
 hipError_t launch_augv2(const sslcr_augv2_desc& a, hipStream_t st);
 hipError_t launch_augv2_colour(const sslcr_augv2_colour_desc& a, hipStream_t st);
+// augment_v1.hip
+hipError_t launch_augv1(const sslcr_augv1_desc& a, hipStream_t st);
+hipError_t launch_augv1_philox(unsigned long long seed, uint32_t first, int count, uint32_t* words, hipStream_t st);
+void cv_warp_table(int16_t* table);                       // host only
+// bytes per image of the RESIZE workspace: a planar S' x S' image for S' <= smax, rounded up to 16
+__host__ __device__ inline size_t augv1_work_stride(int smax) { return (((size_t)3 * smax * smax) + 15) & ~(size_t)15; }
 // optim.hip
 struct OptTable { OptArgs row[SSLCR_MAX_OPT_GROUPS]; };   // the kernels' by-value table: a tensor's row is row[TensorDesc.group]
 // every row a no-op (SGD with lr 0, momentum 1 and gradient scale 0: p and the momentum buffer are rewritten with their own values;
