@@ -54,7 +54,8 @@ extern "C" {
  * sslcr_rank_keys, sslcr_auc_counts, sslcr_auc_workspace_bytes) are additive in the same way, again without a new number, and so
  * are the resize entries (sslcr_resample, sslcr_resample_plan, sslcr_resample_coeffs, sslcr_resample_ksize,
  * sslcr_resample_table_ok), the k-NN probe's (sslcr_knn_plan, sslcr_knn_topk, sslcr_knn_vote, sslcr_l2_normalize) and the t-SNE
- * embedding's (sslcr_tsne_plan, sslcr_tsne_pair_dist2, sslcr_tsne_affinities, sslcr_tsne_repulsion, sslcr_tsne_update, sslcr_tsne_kl).
+ * embedding's (sslcr_tsne_plan, sslcr_tsne_pair_dist2, sslcr_tsne_affinities, sslcr_tsne_repulsion, sslcr_tsne_update, sslcr_tsne_kl) and the linear probe's
+ * (sslcr_linprobe_plan, sslcr_linprobe_eval, sslcr_linprobe_logits).
  * 16 = the switch listing: sslcr_switch_count and sslcr_switch_info added (additive; every switch keeps its default and its reading of
  * every string, no launch changes). */
 int sslcr_version(void);
@@ -1271,6 +1272,107 @@ int sslcr_tsne_affinities(const float* dist2, float* P, double* beta, int n, int
 int sslcr_tsne_repulsion(const sslcr_tsne_grad_desc* d, void* stream);
 int sslcr_tsne_update(const sslcr_tsne_grad_desc* d, void* stream);
 int sslcr_tsne_kl(const double* kl_rows, const float* grad, const double* Z, double* log_row, int n, int iteration, void* stream);
+
+/* ---- linear probe on the device (csrc/linprobe.hip): value and gradient of a linear classifier's loss over FIXED features, fused.
+ *      The reference's `--modules 64` mode ("fine-tune only classifier", eval_Kather_SSL.py:229, :358-370) trains
+ *      FinetuneResNet.classifier = nn.Linear(768, num_classes) on a frozen backbone: with the features fixed that is multinomial
+ *      logistic regression (ridge regression for BreastPathQ's MSE), a convex problem whose cost is the repeated evaluation below.
+ *      Additive, WITHOUT a new version number: a caller tests for sslcr_linprobe_plan, sslcr_linprobe_eval and sslcr_linprobe_logits
+ *      by symbol.  Every entry is asynchronous; none synchronises with the host.
+ *
+ *      sslcr_linprobe_eval.  X [n][D] contiguous float32, D % 4 == 0, 4 <= D <= 2048, 16-byte aligned, 1 <= n < 2^31 - 64; W [C][D] and
+ *      b [C] float32, 1 <= C <= 64; s_i = sample_weight[i] (float32 [n]; NULL: 1).  For the one point (W, b):
+ *        value   one float64: sum_i s_i l_i / sum_i s_i;
+ *        grad    float64 [C][D + 1]: the gradient of value in W (columns 0 .. D - 1) and in b (column D);
+ *        logits  optionally float32 [n][C].
+ *      The DATA term only: a penalty is the caller's host arithmetic.
+ *        SSLCR_LINPROBE_SOFTMAX  labels int64 [n]; l_i = logsumexp(z_i) - z_{i, y_i}.  A row whose label lies OUTSIDE [0, C) contributes
+ *                                nothing -- not to the value, not to the gradient -- and is LEFT OUT of sum_i s_i (its logits are
+ *                                still written).  C = 1 is accepted (l_i = 0).
+ *        SSLCR_LINPROBE_SQUARED  targets float32 [n][C]; l_i = 1/2 sum_c (z_ic - t_ic)^2.
+ *      With sum_i s_i = 0 (every row left out or weighted 0) value and grad are 0 / 0 = NaN.
+ *        Arithmetic.  Logit: v_mfma_f32_16x16x4_f32; z_ic is accumulated over d = 0 .. D - 1 in RISING order from a +0 accumulator, one
+ *        rounding per product-and-add -- an fmaf chain in d order (D is padded to a multiple of 16 with zero products, which change no
+ *        value) -- and then z_ic = chain + b[c], one float32 addition.  The value does not depend on the plan.  (tests/test_linprobe_gpu.py
+ *        holds a logit to the BITS of that chain; the row order of the gradient's chains is held by bounds only, not by bits.)
+ *        Softmax: in float32 with the accurate expf / logf: m = max_c z_ic; e_c = expf(z_ic - m); S = sum_c e_c (eight partial sums,
+ *        classes c = j, j + 8, ... in rising c, then a 3-step butterfly); l_i = logf(S) + (m - z_{i, y_i}), the two summands added in
+ *        float64; squared loss: differences, squares and their sum in float64 from the float32 z and t.  The row's term is
+ *        s_i * l_i in float64.
+ *        Residual: r_ic = s_i * (e_c / S - [c == y_i]) (softmax) or s_i * (z_ic - t_ic) (squared), formed in float64 from those float32
+ *        values and rounded to float32 ONCE.
+ *        Gradient: a workgroup owns a contiguous range of row tiles; every element sum_i r_ic x_id (and sum_i r_ic for column D) is ONE
+ *        fp32 chain over the rows that workgroup owns in RISING row order (v_mfma_f32_16x16x4_f32 again; a plain float32 addition
+ *        chain for column D), kept in accumulators across the workgroup's tiles.  The loss terms of a tile are summed in float64 by a
+ *        fixed butterfly and added to the workgroup's float64 sums in rising tile order.
+ *        Fold: the per-workgroup partials -- C (D + 1) floats, and the two float64 sums (s_i l_i and s_i) -- are folded by a SECOND
+ *        launch in float64 in rising workgroup order, then divided by sum_i s_i (one float64 division each).
+ *        Work passes between workgroups at the launch boundary only: no floating-point atomics, no tickets, no spinning, every loop
+ *        states its bound.  Two calls with the same plan give equal bits.
+ *        Launches: (0) W is repacked into `workspace`, rows padded to the MFMA block with zeros, in the operand order of the first
+ *        product (C is padded to 16 / 32 / 64 in registers and in this scratch copy only, never in the caller's tensors); (1) grid =
+ *        G workgroups x S column slices, 256 threads, tiles of SSLCR_LINPROBE_TILE rows; (2) the fold.
+ *        Forms, chosen by the plan from D alone:
+ *          SSLCR_LINPROBE_STAGED    the row tile [32][D] fits LDS (D <= 1024): it is fetched from memory ONCE, staged once, and serves both
+ *                                   products -- X is read once per evaluation;
+ *          SSLCR_LINPROBE_STREAMED  wider D: the tile passes through SSLCR_LINPROBE_CHUNK columns of LDS (two alternating stages of 256),
+ *                                   once for the logits and once more for the gradient; the second read is of lines the workgroup
+ *                                   has just fetched.
+ *        In both forms the 256 columns of the next stage (or of the next tile's first) are in flight while a stage's MFMAs run.
+ *        The gradient accumulators of a workgroup hold at most 32 blocks of 16 x 16 a wave; where ceil(C / 16) * ceil(D / 16) exceeds
+ *        what four waves hold (C > 16 and D > 1024, C > 32 and D > 512) the columns are cut into S <= 4 slices, one workgroup each,
+ *        and every slice repeats the first product; slice 0 alone writes logits, loss terms and column D.
+ *      sslcr_linprobe_plan: HOST-ONLY, usable without a device: tile rows, G, tiles per workgroup, S, form, chunk, LDS bytes and
+ *      workspace bytes of (n, D, C, loss).  groups_hint > 0 FORCES G (up to the tile count and SSLCR_LINPROBE_MAX_GROUPS; a trailing
+ *      workgroup may then own no tile and writes zero partials); 0 lets the plan choose: as many workgroups as the chip holds at once
+ *      (256 CUs x the 1 or 2 its LDS admits -- from LDS ALONE: whether the registers of the wider accumulator shapes also admit two
+ *      a CU has not been measured, so where they do not the grid runs in two rounds), so that the dirty partials stay at a few hundred x C (D + 1) floats and never become
+ *      one set per tile, rebalanced so that no workgroup is empty.  The launch, the Python layer and the tests read this plan.
+ *      -1 for arguments sslcr_linprobe_eval refuses.
+ *      sslcr_linprobe_logits: the first product alone, for queries: logits [n][C] = the SAME chain and addition, so its bits equal the
+ *      `logits` output of sslcr_linprobe_eval.  Reads x, w, b, logits, workspace, n, D, C, groups of the descriptor.
+ *      Errors: NULL descriptor or pointers (x, w, b, workspace; eval: value, grad, and labels / targets by loss; logits: logits), n, D,
+ *      C outside their ranges, loss outside the two, groups < 0, x / workspace not 16-byte, labels / value / grad not 8-byte, the
+ *      other tensors not 4-byte aligned. */
+#define SSLCR_LINPROBE_SOFTMAX 0
+#define SSLCR_LINPROBE_SQUARED 1
+#define SSLCR_LINPROBE_STAGED 0    /* form: the whole row tile in LDS, X read once */
+#define SSLCR_LINPROBE_STREAMED 1  /* form: chunks of columns, X read twice (the second time from cache) */
+#define SSLCR_LINPROBE_TILE 32     /* rows of a tile */
+#define SSLCR_LINPROBE_CHUNK 512   /* columns of LDS the streamed form passes a tile through */
+#define SSLCR_LINPROBE_MAX_C 64
+#define SSLCR_LINPROBE_MAX_D 2048
+#define SSLCR_LINPROBE_MAX_GROUPS 1024
+typedef struct sslcr_linprobe_desc {
+  const float* x;               /* [n][D] */
+  const float* w;               /* [C][D] */
+  const float* b;               /* [C] */
+  const int64_t* labels;        /* [n], SOFTMAX */
+  const float* targets;         /* [n][C], SQUARED */
+  const float* sample_weight;   /* [n] or NULL */
+  double* value;                /* one float64 */
+  double* grad;                 /* [C][D + 1] float64 */
+  float* logits;                /* [n][C] or NULL (sslcr_linprobe_logits: required) */
+  void* workspace;              /* sslcr_linprobe_plan_info.workspace_bytes */
+  int n, D, C;
+  int loss;                     /* SSLCR_LINPROBE_SOFTMAX | SSLCR_LINPROBE_SQUARED */
+  int groups;                   /* the plan's groups_hint */
+} sslcr_linprobe_desc;
+typedef struct sslcr_linprobe_plan_info {
+  int form;                     /* SSLCR_LINPROBE_STAGED | SSLCR_LINPROBE_STREAMED */
+  int tile_rows;
+  int groups;                   /* G */
+  int tiles_per_group;          /* workgroup g owns tiles [g * tiles_per_group, ...) */
+  int col_slices;               /* S */
+  int chunk;                    /* columns of X resident in LDS (STAGED: D padded to 16) */
+  int class_blocks;             /* ceil(C / 16) rounded to 1, 2 or 4: the padding, in registers only */
+  int grid[3];                  /* workgroups of the (repack, evaluation, fold) launches */
+  size_t lds_bytes;             /* dynamic LDS of the evaluation's workgroup */
+  size_t workspace_bytes;
+} sslcr_linprobe_plan_info;
+int sslcr_linprobe_plan(int n, int D, int C, int loss, int groups_hint, sslcr_linprobe_plan_info* out);
+int sslcr_linprobe_eval(const sslcr_linprobe_desc* d, void* stream);
+int sslcr_linprobe_logits(const sslcr_linprobe_desc* d, void* stream);
 
 /* ---- device-side strong augmentation, the colour ops of the reference's RandAugment pool ("next" row f4) on a uint8 batch in HBM.
  *      As with sslcr_weak_augment the random draws stay on the host, in the reference's order (ssl_cr_histo_amd/augment.py);

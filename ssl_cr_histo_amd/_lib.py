@@ -146,6 +146,15 @@ TsnePlan = _S("sslcr_tsne_plan_info", "TsnePlan", [(k, i32) for k in ("tile", "c
 TsneGradDesc = _S("sslcr_tsne_grad_desc", "TsneGradDesc", [(k, vp) for k in ("y", "y_out", "update", "gains", "grad", "rowptr", "col", "val", "workspace",
                                                                              "Z", "kl_rows")] +
                   [(k, i32) for k in ("n", "slices", "nnz")] + [(k, f64) for k in ("exaggeration", "momentum", "lr", "min_gain")])
+LINPROBE_LOSSES = {"softmax": 0, "squared": 1}
+LINPROBE_FORMS = ("staged", "streamed")
+LINPROBE_TILE, LINPROBE_CHUNK, LINPROBE_MAX_C, LINPROBE_MAX_D, LINPROBE_MAX_GROUPS = 32, 512, 64, 2048, 1024
+LinprobeDesc = _S("sslcr_linprobe_desc", "LinprobeDesc", [(k, vp) for k in ("x", "w", "b", "labels", "targets", "sample_weight", "value", "grad",
+                                                                             "logits", "workspace")] +
+                  [(k, i32) for k in ("n", "D", "C", "loss", "groups")])
+LinprobePlan = _S("sslcr_linprobe_plan_info", "LinprobePlan", [(k, i32) for k in ("form", "tile_rows", "groups", "tiles_per_group", "col_slices", "chunk",
+                                                                                  "class_blocks")] +
+                  [("grid", i32 * 3), ("lds_bytes", sz), ("workspace_bytes", sz)])
 PackDesc = _S("sslcr_pack_desc", "PackDesc", [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("gamma", vp), ("beta", vp), ("rmean", vp),
                            ("rvar", vp), ("eps", f32), ("bias_out", vp)] + [(k, i32) for k in ("K", "C", "R", "S", "dgrad_flip")] + [("scale_out", vp)])
 
@@ -167,6 +176,10 @@ CONSTANTS.update({"SSLCR_KNN_" + k.upper(): v for v, k in enumerate(KNN_FORMS)})
 CONSTANTS.update({"SSLCR_TSNE_TILE": TSNE_TILE, "SSLCR_TSNE_CHUNK": TSNE_CHUNK, "SSLCR_TSNE_MAX_SLICES": TSNE_MAX_SLICES,
                   "SSLCR_TSNE_MAX_N": TSNE_MAX_N, "SSLCR_TSNE_LOG_COLS": TSNE_LOG_COLS})
 CONSTANTS.update({"SSLCR_KNN_VOTE_" + k.upper(): v for k, v in KNN_VOTES.items()})
+CONSTANTS.update({"SSLCR_LINPROBE_" + k.upper(): v for k, v in LINPROBE_LOSSES.items()})
+CONSTANTS.update({"SSLCR_LINPROBE_" + k.upper(): v for v, k in enumerate(LINPROBE_FORMS)})
+CONSTANTS.update({"SSLCR_LINPROBE_TILE": LINPROBE_TILE, "SSLCR_LINPROBE_CHUNK": LINPROBE_CHUNK, "SSLCR_LINPROBE_MAX_C": LINPROBE_MAX_C,
+                  "SSLCR_LINPROBE_MAX_D": LINPROBE_MAX_D, "SSLCR_LINPROBE_MAX_GROUPS": LINPROBE_MAX_GROUPS})
 CONSTANTS.update({"SSLCR_AUGV1_" + k.upper(): v for v, k in enumerate(AUGV1_OPS)})
 
 # symbol -> (restype, argtypes); every symbol include/sslcr.h declares
@@ -251,6 +264,9 @@ SIGNATURES = {
     "sslcr_tsne_repulsion": (i32, [P(TsneGradDesc), vp]),
     "sslcr_tsne_update": (i32, [P(TsneGradDesc), vp]),
     "sslcr_tsne_kl": (i32, [vp, vp, vp, vp, i32, i32, vp]),
+    "sslcr_linprobe_plan": (i32, [i32, i32, i32, i32, i32, P(LinprobePlan)]),
+    "sslcr_linprobe_eval": (i32, [P(LinprobeDesc), vp]),
+    "sslcr_linprobe_logits": (i32, [P(LinprobeDesc), vp]),
     "sslcr_optimizer_step": (i32, [vp, i32, i32, P(OptDesc), vp]),
     "sslcr_optimizer_step_groups": (i32, [vp, i32, i32, P(OptDesc), i32, vp, vp]),
     "sslcr_grad_norm": (i32, [vp, sz, f32, vp, vp, vp]),
@@ -301,3 +317,8 @@ def stream_ptr():
 
 def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def ptr_at(t, byte_offset):
+    """the address ``byte_offset`` bytes past a tensor's first element"""
+    return C.c_void_p(t.data_ptr() + byte_offset)

@@ -786,6 +786,50 @@ int sslcr_tsne_kl(const double* kl_rows, const float* grad, const double* Z, dou
   NEED(ALIGNED(kl_rows, 7) && ALIGNED(grad, 3) && ALIGNED(Z, 7) && ALIGNED(log_row, 7), "kl_rows / grad / Z / log_row alignment");
   return check(launch_tsne_kl(kl_rows, grad, Z, log_row, n, iteration, (hipStream_t)stream), "tsne_kl");
 }
+// ---- linear probe (linprobe.hip)
+int sslcr_linprobe_plan(int n, int D, int C, int loss, int groups_hint, sslcr_linprobe_plan_info* out) {
+  NEED(out, "null");
+  const char* why = linprobe_plan(n, D, C, loss, groups_hint, out);
+  NEED(!why, why);
+  return 0;
+}
+static int linprobe_ok(const char* func, const sslcr_linprobe_desc* d, LinprobePlan* p, bool fwd_only) {
+#define LP_NEED(cond, what) \
+  do {                      \
+    if (!(cond)) return fail("%s: invalid argument (%s)", func, what); \
+  } while (0)
+#define LP_NEED_AL(p, n) LP_NEED(ALIGNED(p, (n) - 1), #p " must be " #n "-byte aligned")
+  LP_NEED(d, "null descriptor");
+  const char* why = linprobe_plan(d->n, d->D, d->C, fwd_only ? SSLCR_LINPROBE_SOFTMAX : d->loss, d->groups, p);
+  LP_NEED(!why, why);
+  LP_NEED(d->x && d->w && d->b && d->workspace, "null tensor");
+  if (fwd_only) {
+    LP_NEED(d->logits, "null logits");
+  } else {
+    LP_NEED(d->value && d->grad, "null value / grad");
+    LP_NEED(d->loss != SSLCR_LINPROBE_SOFTMAX || d->labels, "the softmax loss needs labels");
+    LP_NEED(d->loss != SSLCR_LINPROBE_SQUARED || d->targets, "the squared loss needs targets");
+  }
+  LP_NEED_AL(d->x, 16); LP_NEED_AL(d->workspace, 16);
+  LP_NEED_AL(d->w, 4); LP_NEED_AL(d->b, 4); LP_NEED_AL(d->logits, 4);
+  if (!fwd_only) {                                  // (sslcr_linprobe_logits does not read these fields)
+    LP_NEED_AL(d->labels, 8); LP_NEED_AL(d->value, 8); LP_NEED_AL(d->grad, 8);
+    LP_NEED_AL(d->targets, 4); LP_NEED_AL(d->sample_weight, 4);
+  }
+#undef LP_NEED_AL
+#undef LP_NEED
+  return 0;
+}
+int sslcr_linprobe_eval(const sslcr_linprobe_desc* d, void* stream) {
+  LinprobePlan p;
+  if (linprobe_ok(__func__, d, &p, false)) return -1;
+  return check(launch_linprobe(*d, p, false, (hipStream_t)stream), "linprobe_eval");
+}
+int sslcr_linprobe_logits(const sslcr_linprobe_desc* d, void* stream) {
+  LinprobePlan p;
+  if (linprobe_ok(__func__, d, &p, true)) return -1;
+  return check(launch_linprobe(*d, p, true, (hipStream_t)stream), "linprobe_logits");
+}
 #undef SQ_SHAPE_OK
 #undef MAP_SHAPE_OK
 int sslcr_d4_transform(const sslcr_d4_desc* d, void* stream) {

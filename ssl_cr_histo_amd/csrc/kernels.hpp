@@ -250,6 +250,12 @@ hipError_t launch_tsne_affinities(const float* dist2, float* P, double* beta, in
 hipError_t launch_tsne_repulsion(const sslcr_tsne_grad_desc& a, const TsnePlan& p, hipStream_t st);
 hipError_t launch_tsne_update(const sslcr_tsne_grad_desc& a, const TsnePlan& p, hipStream_t st);
 hipError_t launch_tsne_kl(const double* kl_rows, const float* grad, const double* Z, double* log_row, int n, int iteration, hipStream_t st);
+// linprobe.hip: tile rows, workgroups, column slices and the form are decided ONCE, here -- the launch, sslcr_linprobe_plan, the Python layer and the tests read this plan
+using LinprobePlan = sslcr_linprobe_plan_info;
+// nullptr and *out filled, or what is wrong with the arguments (host only)
+const char* linprobe_plan(int n, int D, int C, int loss, int groups_hint, LinprobePlan* out);
+// fwd_only: the logits alone (sslcr_linprobe_logits)
+hipError_t launch_linprobe(const sslcr_linprobe_desc& a, const LinprobePlan& p, bool fwd_only, hipStream_t st);
 // augment.hip
 hipError_t launch_weak_augment(const sslcr_weak_aug_desc& a, hipStream_t st);
 hipError_t launch_hed_colour(const sslcr_colour_aug_desc& a, hipStream_t st);

@@ -934,3 +934,191 @@ def neighbour_preservation(x, y, k):
     iy, _ = K.euclidean_topk(y.contiguous(), k)
     both = ((ix[:, :, None] == iy[:, None, :]) & (ix[:, :, None] >= 0)).any(2)
     return float(both.sum().item()) / (ix.shape[0] * k)
+
+
+# ---- linear probe: the reference's `--modules 64` ("fine-tune only classifier") as the convex problem it is
+class LinearProbe:
+    """Linear evaluation of fixed features: multinomial logistic regression (``loss="softmax"``) or ridge regression (``"squared"``,
+    BreastPathQ's MSE head) of device features, fitted by a host float64 L-BFGS (``lbfgs.minimize``) whose every value and gradient is
+    ONE fused device evaluation (``kernels.linprobe_eval``; csrc/linprobe.hip).
+
+    Objective: ``sum_i s_i l_i / sum_i s_i + (lam / 2) ||W||^2`` with ``lam = 1 / (C * sum_i s_i)`` (``C=``, sklearn's inverse
+    regularisation strength; default 1.0) or ``lam = l2`` (``l2=``) -- state one, not both; the intercept is not penalised.  For three
+    or more classes that is sklearn 1.7.2's ``LogisticRegression(C=C)``; the softmax form is used for EVERY class count (the
+    reference's two-logit Camelyon16 head), so for two classes the optimum equals sklearn's binary model at ``C_sklearn = 2 C`` with
+    ``W = [-w / 2, +w / 2]``.  ``class_weight="balanced"`` is sklearn's (``n / (classes present * count)``; their sum is n);
+    ``loss="squared"`` with ``l2 = lam`` is ``Ridge(alpha = lam * n)``.  normalize="l2": rows through ``kernels.l2_normalize`` first,
+    in ``fit`` and in every query.  Standardising features, an L1 penalty and other solvers are out of scope.
+
+    Host traffic.  Features, labels and weights never leave the device.  One evaluation is one ``linprobe_eval`` and ONE copy to the
+    host, of the value and the gradient: 8 (1 + C (D + 1)) bytes, through the one read site ``_read``; ``reads`` counts its calls, and
+    after ``fit`` it EQUALS ``n_eval_``.  With ``n_classes`` stated there is no other read: the penalty needs ``sum_i s_i`` on the host,
+    which is n without weights and under "balanced"; labels are then taken to lie in [0, n_classes) (the kernel leaves a row outside
+    it out of the data term, but n still counts it).  Without ``n_classes`` the largest label is read off the device first, and with a
+    ``sample_weight`` its sum is (one scalar copy each, counted in ``setup_reads``).
+
+    After ``fit(feats, targets, sample_weight=None)`` (feats device float32 [n, D], D % 4 == 0, 4 <= D <= 2048; integer labels [n], or
+    float targets [n] / [n, C] for "squared"): ``coef_`` [C, D] and ``intercept_`` [C] (device float32: the point the last evaluation
+    was made at), ``n_iter_``, ``n_eval_``, ``status_`` ("converged" | "precision" | "max_iter": lbfgs.py), ``log`` (array
+    [iterations, 4]: objective, max|g|, step, evaluations), ``objective_``, ``grad_max_``.  ``decision_function`` / ``predict`` /
+    ``predict_proba`` / ``score`` run on device queries (``kernels.linprobe_logits``, ``kernels.predict``); ``score`` (accuracy, or
+    R^2 for "squared") makes one scalar copy.  ``to_classifier(classifier)`` copies W, b into a ``net.FinetuneResNet``'s
+    ``classifier[0]``, so the ``*_test`` drop-ins run with the fitted head."""
+
+    def __init__(self, C=None, *, l2=None, loss="softmax", fit_intercept=True, normalize=None, class_weight=None, tol=1e-4,
+                 max_iter=1000, history=10, n_classes=None, groups=None):
+        if C is not None and l2 is not None:
+            raise ValueError("LinearProbe: state C or l2, not both")
+        if loss not in K.LINPROBE_LOSSES:
+            raise ValueError(f"LinearProbe: loss = {loss!r} outside {tuple(K.LINPROBE_LOSSES)}")
+        if normalize not in (None, "l2"):
+            raise ValueError(f"LinearProbe: normalize = {normalize!r} outside (None, 'l2')")
+        if class_weight not in (None, "balanced"):
+            raise ValueError(f"LinearProbe: class_weight = {class_weight!r} outside (None, 'balanced')")
+        if class_weight is not None and loss != "softmax":
+            raise ValueError("LinearProbe: class_weight applies to the softmax loss")
+        if l2 is None and not float(1.0 if C is None else C) > 0:
+            raise ValueError("LinearProbe: C must be > 0")
+        if l2 is not None and not float(l2) >= 0:
+            raise ValueError("LinearProbe: l2 must be >= 0")
+        self.C, self.l2 = (None if l2 is not None else float(1.0 if C is None else C)), (None if l2 is None else float(l2))
+        self.loss, self.fit_intercept, self.normalize, self.class_weight = loss, bool(fit_intercept), normalize, class_weight
+        self.tol, self.max_iter, self.history, self.n_classes, self.groups = float(tol), int(max_iter), int(history), n_classes, groups
+        self.reads = self.setup_reads = 0
+        self.coef_ = self.intercept_ = None
+
+    # the one read site of the fit's loop
+    def _read(self, t):
+        self.reads += 1
+        return t.cpu().numpy()
+
+    def _features(self, feats):
+        if not isinstance(feats, torch.Tensor) or not feats.is_cuda or feats.dtype != torch.float32 or feats.dim() != 2:
+            raise K.L.SslcrError("LinearProbe: device float32 [n, D] expected (no CPU fallback)")
+        return K.l2_normalize(feats) if self.normalize == "l2" else feats.contiguous()
+
+    def fit(self, feats, targets, sample_weight=None):
+        from . import lbfgs
+        x = self._features(feats.detach())
+        n, D = x.shape
+        dev = x.device
+        self.reads = self.setup_reads = 0
+        targets = targets.to(dev)
+        if self.loss == "softmax":
+            if targets.is_floating_point():
+                raise ValueError("LinearProbe: integer labels expected for the softmax loss (loss='squared' takes float targets)")
+            y = targets.reshape(-1).long()
+            if self.n_classes is None:
+                self.setup_reads += 1
+                Cn = int(y.max().item()) + 1
+            else:
+                Cn = int(self.n_classes)
+        else:
+            y = targets.float().reshape(n, -1).contiguous()
+            Cn = y.shape[1]
+        s, total = None, float(n)
+        if sample_weight is not None:
+            s = sample_weight.to(dev, torch.float32).reshape(-1)
+        if self.class_weight == "balanced":
+            counts = torch.bincount(y.clamp(0, Cn - 1), minlength=Cn).double()
+            cw = (float(n) / ((counts > 0).sum().double() * counts.clamp_min(1.0))).float()
+            s = cw[y.clamp(0, Cn - 1)] if s is None else s * cw[y.clamp(0, Cn - 1)]
+        if sample_weight is not None:
+            self.setup_reads += 1
+            total = float(s.double().sum().item())
+        lam = self.l2 if self.l2 is not None else 1.0 / (self.C * total)
+        self.n_classes_, self.lam_ = Cn, lam
+        E = Cn * (D + 1)
+        buf = torch.empty(1 + E, dtype=torch.float64, device=dev)
+
+        def fun(theta):
+            th32 = torch.from_numpy(theta.astype(np.float32).reshape(Cn, D + 1)).to(dev)
+            w, b = th32[:, :D].contiguous(), th32[:, D].contiguous()
+            K.linprobe_eval(x, y, w, b, self.loss, s, self.groups, out=buf)
+            flat = self._read(buf)                                                           # the one copy: value and gradient
+            W = theta.reshape(Cn, D + 1)[:, :D]
+            g = flat[1:].reshape(Cn, D + 1).copy()
+            g[:, :D] += lam * W
+            if not self.fit_intercept:
+                g[:, D] = 0.0
+            return float(flat[0]) + 0.5 * lam * float((W * W).sum()), g.ravel()
+
+        r = lbfgs.minimize(fun, np.zeros(E), tol=self.tol, max_iter=self.max_iter, history=self.history)
+        th32 = torch.from_numpy(r.x.astype(np.float32).reshape(Cn, D + 1)).to(dev)
+        self.coef_, self.intercept_ = th32[:, :D].contiguous(), th32[:, D].contiguous()
+        self.theta_ = r.x.reshape(Cn, D + 1)
+        self.n_iter_, self.n_eval_, self.status_, self.log = r.n_iter, r.n_eval, r.status, r.log
+        self.objective_, self.grad_max_ = r.f, float(np.abs(r.g).max())
+        return self
+
+    def _fitted(self):
+        if self.coef_ is None:
+            raise RuntimeError("LinearProbe: fit() first")
+
+    def decision_function(self, feats):
+        """device float32 [n, C]: ``feats W^T + b``, no sync"""
+        self._fitted()
+        return K.linprobe_logits(self._features(feats), self.coef_, self.intercept_, self.groups)
+
+    def predict(self, feats):
+        """softmax: device int64 [n], the lowest index of the row maximum; squared: the outputs [n, C] themselves.  No sync."""
+        z = self.decision_function(feats)
+        return z if self.loss == "squared" else K.predict(z)["pred"]
+
+    def predict_proba(self, feats):
+        if self.loss != "softmax":
+            raise ValueError("LinearProbe.predict_proba: the softmax loss only")
+        return K.predict(self.decision_function(feats), scores=True, pred=False)["scores"]
+
+    def score(self, feats, targets):
+        """accuracy (softmax) or R^2 over all outputs (squared): one scalar copy"""
+        p = self.predict(feats)
+        t = targets.to(p.device)
+        if self.loss == "softmax":
+            return float((p == t.reshape(-1).long()).double().mean().item())
+        t = t.double().reshape(p.shape)
+        return float((1.0 - ((p.double() - t) ** 2).sum() / ((t - t.mean(0)) ** 2).sum()).item())
+
+    def to_classifier(self, classifier):
+        """W, b into ``classifier.classifier[0]`` (``net.FinetuneResNet``: nn.Linear(768, n_classes)), in place"""
+        self._fitted()
+        if self.normalize is not None:
+            raise ValueError("LinearProbe.to_classifier: a probe of normalised features is not the head of the raw ones")
+        lin = classifier.classifier[0]
+        if tuple(lin.weight.shape) != tuple(self.coef_.shape):
+            raise ValueError(f"LinearProbe.to_classifier: the head is {list(lin.weight.shape)}, the probe {list(self.coef_.shape)}")
+        with torch.no_grad():
+            lin.weight.copy_(self.coef_)
+            lin.bias.copy_(self.intercept_)
+        return classifier
+
+
+def linear_probe(feats, targets, *, queries=None, query_targets=None, sample_weight=None, **kw):
+    """How good are these embeddings: a ``LinearProbe`` fitted on (feats, targets) -- ``steps.rsp_train``'s ``final_feats,
+    final_targets`` as they are -- and scored on ``queries`` / ``query_targets`` (without them: the fit's training figures).  Integer
+    targets -> ``knn_probe``'s dict (``accuracy`` and the other figures of ``metrics_from_confusion``, ``confusion``, ``pred``); float
+    targets (``loss="squared"`` is implied) -> ``pred`` and ``mse``.  Plus ``probe``, the fitted object.  sample_weight: ``fit``'s (device
+    float32 [n]; its sum is read once).  kw: ``LinearProbe``'s.  One
+    copy per evaluation during the fit (see ``LinearProbe``) and one of the final numbers."""
+    if targets.is_floating_point():
+        kw.setdefault("loss", "squared")
+    probe = LinearProbe(**kw).fit(feats, targets, sample_weight=sample_weight)
+    q = feats if queries is None else queries
+    qt = (targets if query_targets is None else query_targets).to(q.device)
+    if probe.loss == "squared":
+        pred = probe.predict(q)
+        truth = qt.float().reshape(pred.shape)
+        flat = torch.cat([pred.reshape(-1), ((pred - truth) ** 2).mean().reshape(1)]).cpu().numpy()
+        return dict(pred=flat[:-1].reshape(tuple(pred.shape)).squeeze(-1) if pred.shape[1] == 1 else flat[:-1].reshape(tuple(pred.shape)),
+                    mse=float(flat[-1]), probe=probe)
+    Cn = probe.n_classes_
+    cm = torch.zeros((Cn, Cn), dtype=torch.int64, device=q.device)
+    qt = qt.reshape(-1).long().contiguous()
+    r = K.predict(probe.decision_function(q), qt, confusion=cm)
+    flat = torch.cat([cm.reshape(-1), r["pred"]]).cpu().numpy()                           # the one copy
+    cm = flat[:Cn * Cn].reshape(Cn, Cn)
+    if int(cm.sum()) != r["pred"].numel():
+        raise ValueError(f"linear_probe: {r['pred'].numel() - int(cm.sum())} query targets lie outside [0, {Cn}): state n_classes to cover them")
+    out = metrics_from_confusion(cm)
+    out.update(confusion=cm, pred=flat[Cn * Cn:], probe=probe)
+    return out

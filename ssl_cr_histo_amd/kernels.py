@@ -1754,3 +1754,98 @@ def pil_resize(x, size, resample="bilinear", box=None, out=None, out_layout=None
         d.workspace = L.ptr(work)
     L.check(L.lib().sslcr_resample(d, L.stream_ptr()))
     return out
+
+
+# ---- linear probe over fixed features (csrc/linprobe.hip)
+LINPROBE_LOSSES, LINPROBE_FORMS = L.LINPROBE_LOSSES, L.LINPROBE_FORMS
+LINPROBE_TILE, LINPROBE_CHUNK, LINPROBE_MAX_C, LINPROBE_MAX_D = L.LINPROBE_TILE, L.LINPROBE_CHUNK, L.LINPROBE_MAX_C, L.LINPROBE_MAX_D
+
+
+def _linprobe_loss(name, loss):
+    if loss not in LINPROBE_LOSSES:
+        raise L.SslcrError(f"{name}: loss = {loss!r} outside {tuple(LINPROBE_LOSSES)}")
+    return LINPROBE_LOSSES[loss]
+
+
+def _linprobe_plan(n, dim, n_classes, loss, groups):
+    p = L.LinprobePlan()
+    L.check(L.lib().sslcr_linprobe_plan(int(n), int(dim), int(n_classes), int(loss), int(groups or 0), p))
+    return p
+
+
+def linprobe_plan(n, dim, n_classes, loss="softmax", groups=None):
+    """what ``linprobe_eval`` launches for these sizes (sslcr_linprobe_plan; host only, no device needed): dict with ``form``
+    ("staged": the row tile is fetched once and serves both products | "streamed": wide D, read twice), ``tile_rows``, ``groups`` (G),
+    ``tiles_per_group``, ``col_slices``, ``chunk``, ``class_blocks``, ``grid`` (workgroups of the three launches), ``lds_bytes`` and
+    ``workspace_bytes``.  groups: a hint > 0 forces G (None / 0 = the plan's choice)."""
+    p = _linprobe_plan(n, dim, n_classes, _linprobe_loss("linprobe_plan", loss), groups)
+    out = {f: getattr(p, f) for f, _ in L.LinprobePlan._fields_}
+    out["grid"] = tuple(p.grid)
+    out["form"] = LINPROBE_FORMS[p.form]
+    return out
+
+
+def _linprobe_wb(name, x, w, b):
+    x = _f32_rows(name, x)
+    n, D = x.shape
+    if w.dtype != torch.float32 or w.dim() != 2 or w.shape[1] != D or w.device != x.device:
+        raise L.SslcrError(f"{name}: w must be float32 [C, {D}] on x's device, got {w.dtype} {list(w.shape)}")
+    Cn = w.shape[0]
+    if b.dtype != torch.float32 or tuple(b.shape) != (Cn,) or b.device != x.device:
+        raise L.SslcrError(f"{name}: b must be float32 [{Cn}] on x's device")
+    return x, w.contiguous(), b.contiguous(), n, D, Cn
+
+
+def linprobe_eval(x, y, w, b, loss="softmax", sample_weight=None, groups=None, want_logits=False, out=None, logits_out=None):
+    """-> ``(value, grad)`` or ``(value, grad, logits)``: the weighted mean loss of the linear classifier ``x w^T + b`` over the rows of
+    x and its gradient, fused (sslcr_linprobe_eval: x is read once where a 32-row tile fits LDS; three launches, no sync).  x: device
+    float32 [n, D], D % 4 == 0, 4 <= D <= 2048; w float32 [C, D], b float32 [C], 1 <= C <= 64.  loss "softmax": y integer labels [n],
+    a label outside [0, C) leaves its row out of the sums AND of the weight total; "squared": y float32 [n, C], 1/2 sum_c (z - t)^2.
+    sample_weight: float32 [n] or None.  ``value`` is a 0-d float64 view and ``grad`` a float64 [C, D + 1] view (columns 0 .. D - 1 =
+    d/dW, column D = d/db) of ONE device buffer of 1 + C (D + 1) float64 -- ``value.base`` -- so that a caller copies both with one
+    copy; ``out``: that buffer, to write into.  logits: float32 [n, C] (want_logits; ``logits_out``: the tensor to write them into).  The data term only: a penalty is the caller's.
+    groups: the plan's hint (None = its choice); two calls with the same groups return equal bits."""
+    code = _linprobe_loss("linprobe_eval", loss)
+    x, w, b, n, D, Cn = _linprobe_wb("linprobe_eval", x, w, b)
+    dev = x.device
+    labels = targets = None
+    if code == LINPROBE_LOSSES["softmax"]:
+        if y.is_floating_point() or y.dim() != 1 or y.shape[0] != n or y.device != dev:
+            raise L.SslcrError(f"linprobe_eval: {n} integer labels on x's device expected")
+        labels = y.long().contiguous()
+    else:
+        if y.dtype != torch.float32 or tuple(y.shape) != (n, Cn) or y.device != dev:
+            raise L.SslcrError(f"linprobe_eval: float32 targets [{n}, {Cn}] on x's device expected")
+        targets = y.contiguous()
+    if sample_weight is not None:
+        if sample_weight.dtype != torch.float32 or tuple(sample_weight.shape) != (n,) or sample_weight.device != dev:
+            raise L.SslcrError(f"linprobe_eval: sample_weight must be float32 [{n}] on x's device")
+        sample_weight = sample_weight.contiguous()
+    p = _linprobe_plan(n, D, Cn, code, groups)
+    E = Cn * (D + 1)
+    buf = _out(out, (1 + E,), torch.float64, dev, f"linprobe_eval: out must be float64 [{1 + E}] on x's device")
+    _chk(buf)
+    logits = None
+    if want_logits or logits_out is not None:
+        logits = _out(logits_out, (n, Cn), torch.float32, dev, f"linprobe_eval: logits_out must be float32 [{n}, {Cn}] on x's device")
+        _chk(logits)
+    ws = torch.empty(p.workspace_bytes // 16 + 1, dtype=torch.complex128, device=dev)       # 16-byte elements
+    d = L.LinprobeDesc(L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(labels), L.ptr(targets), L.ptr(sample_weight), L.ptr_at(buf, 0), L.ptr_at(buf, 8),
+                       L.ptr(logits), L.ptr(ws), n, D, Cn, code, int(groups or 0))
+    L.check(L.lib().sslcr_linprobe_eval(d, L.stream_ptr()))
+    value, grad = buf[0], buf[1:].view(Cn, D + 1)
+    return (value, grad, logits) if logits is not None else (value, grad)
+
+
+def linprobe_logits(x, w, b, groups=None, out=None):
+    """-> float32 [n, C] = ``x w^T + b`` for device float32 queries x [n, D] (sslcr_linprobe_logits): the first product of
+    ``linprobe_eval`` alone -- the same fp32 chain over D in rising order plus one addition of b -- so its bits equal the ``logits``
+    ``linprobe_eval`` returns for the same rows, whatever the plan.  No sync."""
+    x, w, b, n, D, Cn = _linprobe_wb("linprobe_logits", x, w, b)
+    p = _linprobe_plan(n, D, Cn, 0, groups)
+    logits = _out(out, (n, Cn), torch.float32, x.device, f"linprobe_logits: out must be float32 [{n}, {Cn}] on x's device")
+    _chk(logits)
+    ws = torch.empty(p.workspace_bytes // 16 + 1, dtype=torch.complex128, device=x.device)
+    d = L.LinprobeDesc(L.ptr(x), L.ptr(w), L.ptr(b), None, None, None, None, None, L.ptr(logits), L.ptr(ws), n, D, Cn, 0, int(groups or 0))
+    L.check(L.lib().sslcr_linprobe_logits(d, L.stream_ptr()))
+    return logits

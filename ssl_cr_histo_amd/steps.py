@@ -927,3 +927,26 @@ def knn_probe(args, model, classifier, bank_loader, query_loader=None, k=20, **k
     truth = (targets if qt is None else qt).float()
     flat = torch.cat([r["pred"], ((r["pred"] - truth) ** 2).mean().reshape(1)]).cpu().numpy()
     return dict(pred=flat[:-1], mse=float(flat[-1]))
+
+
+def linear_probe(args, model, classifier, train_loader, test_loader=None, *, sample_weight=None, **kw):
+    """The linear probe of the features a (model, classifier) pair computes -- the reference's ``--modules 64`` ("fine-tune only
+    classifier") solved as the convex problem it is: the eval forward runs ONCE over ``train_loader`` (and ``test_loader``), then
+    ``inference.linear_probe`` fits the head on the device-resident features.  Integer targets -> ``accuracy``, ``confusion``,
+    ``pred``, ... (on ``test_loader`` when given, else the training figures); float targets (BreastPathQ) -> ``pred`` and ``mse``; plus
+    ``probe``, whose ``to_classifier(classifier)`` installs the fitted head.  The class count is the classifier's own (``n_classes=``
+    overrides it), nothing is read off the labels.  Deviation: the probe sees the EVAL forward's features (BatchNorm on running
+    statistics); the reference's frozen mode calls ``model.train()`` and so runs BatchNorm on batch statistics.  sample_weight: one
+    weight per row of ``train_loader`` in its order (device float32), passed to the fit.  kw: ``inference.LinearProbe``'s."""
+    from . import inference as I
+    eng = get_engine(_device_of(model))
+    model.eval()
+    classifier.eval()
+    net = eng.bind(model, classifier)
+    feats, targets = _probe_features(args, eng, net, train_loader)
+    q = qt = None
+    if test_loader is not None:
+        q, qt = _probe_features(args, eng, net, test_loader)
+    if not targets.is_floating_point():
+        kw.setdefault("n_classes", net.ncls)
+    return I.linear_probe(feats, targets, queries=q, query_targets=qt, sample_weight=sample_weight, **kw)
